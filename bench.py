@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - headline benchmark of the CL-DRD hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full training step of BASELINE.json configs[1] on one batch of synthetic MSMARCO-shaped input
@@ -9,9 +9,11 @@ already resident in HBM: DistilBERT-6L dual encoder (two unshared towers, random
 per-GPU batch B=8, seq_len 128 (queries 30), kl_div loss, 16-bit MFMA compute (fp16 operands by default, the reference's own mixed-precision
 mode; CLDRD_AMP=bf16 for bf16 operands, timed as an extra leg) with fp32 accumulate and master weights, dropout 0.1
 active, forward + loss + backward + RCCL gradient all-reduce (N>1) + clip_grad_norm + AdamW.  Rank 0 prints ONE JSON
-line: whole-job samples/s, the roofline of the dominant kernel (the NT MFMA GEMM, timed live with HIP events on the
-launch stream), index-encode passages/s, and the CPU oracle timed on the host cores (N=1 only; a reported baseline,
-not the target).
+line: whole-job samples/s and ms per step of the K timed steps.  A plain run does nothing else; --full adds the secondary
+legs: the roofline of the dominant kernel (the NT MFMA GEMM, timed live with HIP events on the launch stream), the
+MS MARCO-shaped and all-bf16 step timings, index-encode passages/s, the retrieve path, the one-rank RCCL path, and the
+CPU oracle timed on the host cores (N=1 only; a reported baseline, not the target).  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (rank 0; inputs are seeded, so two builds can be compared output for output).
 """
 import argparse
 import json
@@ -99,6 +101,23 @@ def pmc_traffic(kernel_substr, timeout_s=150):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SAMPLE = 1 << 20            # entries of the parameter / gradient samples (each full buffer: ~133 M fp32, both towers)
+
+
+def dump_outputs(out_dir, trainer, loss_out):
+    """What the last timed step computed, as float32 DIR/<name>.npy: its return value (loss, pair count), the logits it scored, and one
+    fixed, seeded sample of positions of the parameters it updated and of the gradients it took (8.4 MB in all)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = trainer.flat_p.numel()
+    pos = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    pos = torch.from_numpy(pos).to(trainer.flat_p.device)
+    arrays = {"loss": loss_out, "logits": trainer.last_logits, "params_sample": trainer.flat_p[pos], "grads_sample": trainer.flat_g[pos]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -110,6 +129,9 @@ def main():
     ap.add_argument("--q-len", type=int, default=30)
     ap.add_argument("--loss", default="kl_div")
     ap.add_argument("--dropout", type=float, default=0.1, help="experiments only: the judged workload is the HF default 0.1")
+    ap.add_argument("--full", action="store_true", help="run every secondary leg after the headline (the --no-* options below skip single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-index", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
@@ -122,6 +144,12 @@ def main():
     ap.add_argument("--retrieve-rows", type=int, default=1105228, help="index rows per GPU (8 841 823 / 8)")
     ap.add_argument("--retrieve-queries", type=int, default=6980, help="queries searched against the shard (MS MARCO dev: 6980)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run times the headline step only: every secondary leg belongs to --full
+        for leg in ("no_cpu_baseline", "no_index", "no_kernel_events", "no_pmc", "no_retrieve", "no_ragged", "no_bf16_leg", "no_ddp1"):
+            setattr(args, leg, True)
 
     if args.ddp1_child:
         return ddp1_child(args)
@@ -196,6 +224,8 @@ def main():
     dt = float(tmax.item())
     samples_per_s = world * B * args.steps / dt
     final_loss = float(loss_out[0].item())
+    if args.dump_outputs and rank == 0:      # before any secondary leg steps the trainer again
+        dump_outputs(args.dump_outputs, trainer, loss_out)
 
     # ---- live per-launch timing of the dominant kernel (HIP events on the launch stream).  A kernel inside a replayed graph cannot be
     # bracketed by events, so the brackets go around the SAME K steps run eagerly right after the timed region (same process, same

@@ -5,7 +5,7 @@ TAG=${1:-r06}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python3 bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.err
 bash tools/prof_train_amp.sh > $OUT/kernel_stats_train.txt 2>&1
 bash tools/pmc_step.sh $TAG > $OUT/pmc_step.log 2>&1
