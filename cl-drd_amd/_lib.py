@@ -45,6 +45,7 @@ SIGNATURES = {
     "cldrd_add_rows_strided": (ci, [vp, vp, ci, ci, ci, ci, vp]),
     "cldrd_ln_partial_blocks": (ci, [ci]),
     "cldrd_embed_ln_fwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp, vp]),
+    "cldrd_embed_ln_fwd_typed": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp, vp]),
     "cldrd_embed_ln_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cull, ci, vp, ci, vp, vp]),
     "cldrd_layernorm_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, ci, vp, ci, vp, vp]),
     "cldrd_layernorm_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cull, ci, ci, vp, vp]),
@@ -95,6 +96,8 @@ SIGNATURES = {
     "cldrd_norm_sink_used": (ci, []),
     "cldrd_loss_scale_adapt": (ci, [vp, csz, vp, csz, vp, vp]),
     "cldrd_write_step_state": (ci, [vp, cull, cull, vp, cf, cf, cf, ci, vp, vp]),
+    "cldrd_build_pairs": (ci, [vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
+    "cldrd_cls_head_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "cldrd_write_run_file": (C.c_longlong, [C.c_char_p, vp, vp, vp, C.c_longlong, ci, ci]),
     "cldrd_py_float_repr": (ci, [C.c_double, C.c_char_p]),
     "cldrd_merge_topk": (ci, [vp, vp, ci, C.c_longlong, ci, ci, vp, vp, ci]),

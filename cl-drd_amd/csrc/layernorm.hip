@@ -193,15 +193,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
 }
 
 // word + position (+ type) embedding -> LN -> dropout.  Tables are the fp32 master weights (HF keeps the
-// embedding lookup and LayerNorm in fp32 under autocast).
-template <int DC, bool DROP>
+// embedding lookup and LayerNorm in fp32 under autocast).  TYPED: `type0` is the whole [type_vocab, d] token-type table and row r adds
+// its row type_ids[r] (BERT pairs: segment A / B); otherwise `type0` (optional) is the one row every token adds.
+template <int DC, bool DROP, bool TYPED = false>
 __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ word,
                                                             const float* __restrict__ pos, const float* __restrict__ type0,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             bf16_t* __restrict__ out, float* __restrict__ out32, float* __restrict__ mean_o,
                                                             float* __restrict__ rstd_o, int T, int L, int d_rt, int vocab, float eps,
                                                             uint32_t drop_thresh, float drop_scale, SeedArg seed_a, int out_f16,
-                                                            const int* __restrict__ pos_idx, bf16_t* __restrict__ out_copy) {
+                                                            const int* __restrict__ pos_idx, bf16_t* __restrict__ out_copy,
+                                                            const int* __restrict__ type_ids = nullptr, int type_vocab = 1) {
     const uint64_t seed = seed_a.get();
     const int d = DC ? DC : d_rt;      // compile-time row width: the `c < d` tests and the unused 4th column pass fold away
     const int lane = threadIdx.x & 63;
@@ -216,7 +218,15 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
     for (int it = 0; it < MAX_IT; ++it)
 #pragma unroll
         for (int j = 0; j < 4; ++j) r.v[it][j] += p.v[it][j];
-    if (type0) {
+    if (TYPED) {
+        int ty = type_ids[row];
+        ty = ty < 0 ? 0 : (ty >= type_vocab ? type_vocab - 1 : ty);
+        load_row_f32(type0 + (size_t)ty * d, d, lane, p);
+#pragma unroll
+        for (int it = 0; it < MAX_IT; ++it)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r.v[it][j] += p.v[it][j];
+    } else if (type0) {
         load_row_f32(type0, d, lane, p);
 #pragma unroll
         for (int it = 0; it < MAX_IT; ++it)
@@ -616,7 +626,26 @@ extern "C" int cldrd_embed_ln_fwd(const long long* ids, const float* word, const
     ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
         hipLaunchKernelGGL((embed_ln_fwd_kernel<decltype(dc)::value, decltype(dr)::value>), dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                            (const int64_t*)ids, word, pos, type0, gamma, beta, (bf16_t*)out, out32, mean, rstd, T, L, d, vocab, eps, th,
-                           1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, (bf16_t*)out_bf16_copy);
+                           1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, (bf16_t*)out_bf16_copy, nullptr, 1);
+    });
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same with per-row token types (cross-encoder pairs): type_table [type_vocab, d] fp32, type_ids device int32 [T] (clamped to the table)
+extern "C" int cldrd_embed_ln_fwd_typed(const long long* ids, const float* word, const float* pos, const float* type_table,
+                                        const int* type_ids, int type_vocab, const float* gamma, const float* beta, void* out, float* mean,
+                                        float* rstd, int T, int L, int d, int vocab, float eps, float dropout_p, unsigned long long seed,
+                                        float* out32, int out_f16, const int* pos_idx, void* out_bf16_copy, void* stream) {
+    CLDRD_CHECK(out_bf16_copy == nullptr || out_f16, "embed_ln_fwd_typed: the bf16 copy goes with an fp16 output");
+    CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0 && L > 0, "embed_ln_fwd_typed: bad shape");
+    CLDRD_CHECK(type_table != nullptr && type_ids != nullptr && type_vocab > 0, "embed_ln_fwd_typed: needs the token-type table and type ids");
+    const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
+    ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
+        hipLaunchKernelGGL((embed_ln_fwd_kernel<decltype(dc)::value, decltype(dr)::value, true>), dim3((T + 3) / 4), dim3(256), 0,
+                           (hipStream_t)stream, (const int64_t*)ids, word, pos, type_table, gamma, beta, (bf16_t*)out, out32, mean, rstd, T, L,
+                           d, vocab, eps, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, (bf16_t*)out_bf16_copy,
+                           type_ids, type_vocab);
     });
     CLDRD_LAUNCH_CHECK();
     return 0;

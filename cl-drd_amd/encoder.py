@@ -620,7 +620,8 @@ class HipEncoder(nn.Module):
         return torch.empty(ops.pad_rows(rows), cols, dtype=dtype, device=dev)
 
     def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None, *, train: bool | None = None,
-               save: bool = False, seed: int | None = None, fp16: bool | None = None, lengths=None, device_seed: bool = False):
+               save: bool = False, seed: int | None = None, fp16: bool | None = None, lengths=None, device_seed: bool = False,
+               token_type_ids: torch.Tensor | None = None, packed=None):
         """CLS embeddings fp32 [M, d] (== HF ``model(**enc)[0][:, 0, :]``).  With ``save`` also returns the tape.
 
         ``fp16`` (default: ``self.hp_forward``, which NwayDualEncoder sets on the QUERY tower in the fp16 mode): the evaluation pass runs
@@ -632,17 +633,33 @@ class HipEncoder(nn.Module):
         ``lengths`` (host-side ints, one per sequence: the number of leading 1s of its mask row): with them a padded batch is PACKED -
         the Linear / LayerNorm / weight-gradient kernels run on the real tokens only (the reference pads every sequence to the longest of
         the batch and computes on the padding: ~40 % of the rows of an MS MARCO batch); attention keeps the padded layout; the CLS output
-        is the same up to the order of fp32 summation.  Without them nothing is packed (finding the row count would cost a host sync)."""
+        is the same up to the order of fp32 summation.  Without them nothing is packed (finding the row count would cost a host sync).
+
+        ``token_type_ids`` ([M, L] like ``input_ids``; BERT only, DistilBERT has no token types): the embedding adds each token's row of the
+        token-type table (cross-encoder pairs) instead of row 0.  ``packed`` = (ids int64 [T], token types int32 [T] or None, positions
+        int32 [T][, width]): rows already in the packed layout of ``lengths`` (``input_ids`` / ``attention_mask`` are then None; evaluation
+        passes only) - what cldrd_build_pairs writes for the cross-encoder.  ``width`` (default: the longest sequence) is the L the attention
+        kernels are chosen for: a caller that passes the same width for every batch gets each sequence's attention independent of the
+        batch.  Both run the evaluation pass of the tower's mode; ``fp16=True`` / ``hp_forward`` (the all-fp16 query-tower pass) is refused."""
         return self.encode_steps(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=fp16, lengths=lengths,
-                                 device_seed=device_seed).finish()
+                                 device_seed=device_seed, token_type_ids=token_type_ids, packed=packed).finish()
 
     def encode_steps(self, input_ids, attention_mask, *, train=None, save=False, seed=None, fp16=None, lengths=None, device_seed=False,
-                     window=None) -> Stepper:
+                     window=None, token_type_ids=None, packed=None) -> Stepper:
         """:meth:`encode` as a :class:`Stepper` (``.finish()`` -> what encode returns).  ``window(kind)`` (optional) is called right before
         each HBM-bound launch of the pass - kind "ln" (LayerNorm / embedding kernels) or "attn" - on the stream the pass is enqueued on: the
         hook at which a trainer releases a slice of the OTHER tower's stepper."""
         fp16 = self.hp_forward if fp16 is None else fp16
         base = getattr(self, "seed_base_ptr", None) if (device_seed and seed is None) else None
+        if token_type_ids is not None or packed is not None:
+            if save or base:
+                raise ValueError("token_type_ids / packed rows: evaluation passes only (no tape, no device seed)")
+            if fp16 and self.amp16:
+                raise ValueError("token_type_ids / packed rows run the tower's evaluation pass; the all-fp16 pass (fp16=True / hp_forward) is not supported there")
+            if seed is None:
+                seed = self.next_seed()
+            return Stepper(self._encode_gen(input_ids, attention_mask, train=train, save=False, seed=seed, fp16=False, lengths=lengths,
+                                            window=window, token_type_ids=token_type_ids, packed=packed))
         if base:
             # graph mode, NwayTrainer only (`device_seed`): the per-step part of the seed lives in device memory at `seed_base_ptr` (the
             # trainer advances step_seed and writes next_seed() there before each step); the launches carry offsets only.  Any other
@@ -699,20 +716,36 @@ class HipEncoder(nn.Module):
     def _encode(self, input_ids, attention_mask, *, train, save, seed, fp16, lengths=None):
         return _drain(self._encode_gen(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=fp16, lengths=lengths))
 
-    def _encode_gen(self, input_ids, attention_mask, *, train, save, seed, fp16, lengths=None, window=None):
+    def _encode_gen(self, input_ids, attention_mask, *, train, save, seed, fp16, lengths=None, window=None, token_type_ids=None, packed=None):
         """one forward pass as a generator: a ``yield`` behind every group of launches (:class:`Stepper`); returns cls or (cls, tape)"""
         cfg = self.cfg
         train = self.training if train is None else train
-        if input_ids.dim() != 2:
+        if packed is not None:
+            if lengths is None or len(lengths) < 1 or not self.cls_only_last or cfg.n_layers < 1 or save:
+                raise ValueError("packed rows need host lengths, an evaluation pass and the CLS-only last layer")
+            M, L = len(lengths), int(max(lengths))
+            if len(packed) > 3:
+                if int(packed[3]) < L:
+                    raise ValueError("packed rows: width must be at least the longest sequence")
+                L = int(packed[3])
+            if min(lengths) < 1:
+                raise ValueError("packed rows: every sequence has at least one token")
+        elif input_ids.dim() != 2:
             raise ValueError("input_ids must be [M, L]")
-        M, L = input_ids.shape
+        else:
+            M, L = input_ids.shape
         if L > 256 or L > cfg.max_position_embeddings:
             raise ValueError("sequence length must be <= 256 (and <= max_position_embeddings)")
         dev = self.flat_p.device
         if not self._shadows_ok(save, need_h=not (self.amp16 and save)):      # (the all-fp16 training pass reads the fp16 shadow only)
             self.refresh_shadows(need_transposed=save)
-        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        mask = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
+        typed = token_type_ids is not None and cfg.arch == "bert"      # (DistilBERT has no token-type table)
+        if packed is None:
+            ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+            mask = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
+            tt = token_type_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous() if typed else None
+        else:
+            mask = None
         T, d, f, H = M * L, cfg.dim, cfg.hidden_dim, cfg.n_heads
         p_h = cfg.dropout if train else 0.0
         p_a = cfg.attention_dropout if train else 0.0
@@ -720,10 +753,19 @@ class HipEncoder(nn.Module):
         pk = None
         if lengths is not None and len(lengths) != M:
             raise ValueError("lengths: one entry per sequence")
-        if self.would_pack(lengths, M, L, has_mask=mask is not None, fp16=fp16, train=save):
+        if packed is not None:
+            pk = _Pack.build(lengths, L, dev)
+            T = pk.Tp
+            ids, tt, pk.pos = packed[:3]
+            if ids.numel() != T or pk.pos.numel() != T or (tt is not None and tt.numel() != T):
+                raise ValueError("packed rows: ids / token types / positions must hold sum(lengths) rows")
+            tt = tt if cfg.arch == "bert" else None
+        elif self.would_pack(lengths, M, L, has_mask=mask is not None, fp16=fp16, train=save):
             pk = _Pack.build(lengths, L, dev)
             T = pk.Tp
             ids_padded, ids = ids, ops.gather_i64(ids.reshape(-1), pk.tok_idx, T)
+            if tt is not None:
+                tt = ops.gather_i64(tt, pk.tok_idx, T)          # the same row index as the ids
         tape = None
         if save:
             tape = _Tape()
@@ -744,10 +786,16 @@ class HipEncoder(nn.Module):
         type0 = self.w("embeddings.token_type_embeddings.weight")[0] if cfg.arch == "bert" else None
         if window is not None:
             window("ln")
-        ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"),
-                         self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
-                         self.w("embeddings.LayerNorm.bias"), xh if QKV16 else x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
-                         pos_idx=pk.pos if pk is not None else None)
+        if tt is not None:
+            ops.embed_ln_fwd_typed(ids.view(-1), self.w("embeddings.word_embeddings.weight"), self.w("embeddings.position_embeddings.weight"),
+                                   self.w("embeddings.token_type_embeddings.weight"), tt.to(torch.int32), self.w("embeddings.LayerNorm.weight"),
+                                   self.w("embeddings.LayerNorm.bias"), xh if QKV16 else x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
+                                   pos_idx=pk.pos if pk is not None else None)
+        else:
+            ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"),
+                             self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
+                             self.w("embeddings.LayerNorm.bias"), xh if QKV16 else x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
+                             pos_idx=pk.pos if pk is not None else None)
         if save:
             tape.mean0, tape.rstd0 = mean0, rstd0
         yield

@@ -503,6 +503,63 @@ def embed_ln_fwd(ids, word, pos, type0, gamma, beta, out, mean, rstd, T, L, eps,
     return out
 
 
+def embed_ln_fwd_typed(ids, word, pos, type_table, type_ids, gamma, beta, out, mean, rstd, T, L, eps, dropout_p=0.0, seed=0, out32=None,
+                       pos_idx=None, out_copy=None):
+    """:func:`embed_ln_fwd` with per-row token types: ``type_table`` fp32 [type_vocab, d], ``type_ids`` int32 [>= T] (cross-encoder pairs)."""
+    _chk(ids, torch.int64, "ids")
+    _chk(type_table, F32, "type_table", 2), _chk(type_ids, torch.int32, "type_ids", 1)
+    d = word.shape[1]
+    if type_table.shape[1] != d or type_ids.numel() < T:
+        raise ValueError("embed_ln_fwd_typed: type_table must be [type_vocab, d], type_ids [>= T]")
+    if out32 is not None:
+        _chk(out32, F32, "out32", 2)
+    if pos_idx is not None:
+        _chk(pos_idx, torch.int32, "pos_idx", 1)
+    call("cldrd_embed_ln_fwd_typed", _p(ids), _p(word), _p(pos), _p(type_table), _p(type_ids), type_table.shape[0], _p(gamma), _p(beta),
+         _p(out), _p(mean), _p(rstd), T, L, d, word.shape[0], eps, dropout_p, seed, _p(out32), _fmt16(out, "out"), _p(pos_idx), _p(out_copy),
+         _stream())
+    return out
+
+
+def build_pairs(q_tok, q_lens, p_tok, p_lens, q_rows, p_rows, keep_q, keep_p, cu, T):
+    """Packed ``[CLS] q' [SEP] p' [SEP]`` rows from token-cache rows (csrc/cross.hip): ``q_tok`` / ``p_tok`` [rows, stride] int32 or a
+    uint16 table viewed as int16, ``*_lens`` int32 [rows], the pair arrays int32 [n], ``cu`` int32 [n + 1] with ``cu[n] == T`` (host value).
+    Returns (ids int64 [T], token types int32 [T], positions int32 [T])."""
+    for t, n in ((q_tok, "q_tok"), (p_tok, "p_tok")):
+        if t.dtype not in (torch.int16, torch.int32) or t.dim() != 2 or not t.is_contiguous():
+            raise TypeError(f"build_pairs: {n} must be a contiguous 2-d int32 (or uint16 viewed as int16) table")
+        _chk(t, t.dtype, n, 2)
+    for t, n in ((q_lens, "q_lens"), (p_lens, "p_lens"), (q_rows, "q_rows"), (p_rows, "p_rows"), (keep_q, "keep_q"), (keep_p, "keep_p"), (cu, "cu")):
+        _chk(t, torch.int32, n, 1)
+    n = q_rows.numel()
+    if not (p_rows.numel() == keep_q.numel() == keep_p.numel() == n and cu.numel() == n + 1) or n < 1:
+        raise ValueError("build_pairs: q_rows, p_rows, keep_q, keep_p [n], cu [n + 1], n >= 1")
+    dev = q_tok.device
+    ids = torch.empty(T, dtype=torch.int64, device=dev)
+    types = torch.empty(T, dtype=torch.int32, device=dev)
+    pos = torch.empty(T, dtype=torch.int32, device=dev)
+    call("cldrd_build_pairs", _p(q_tok), _p(q_lens), q_tok.shape[1], q_tok.element_size(), _p(p_tok), _p(p_lens), p_tok.shape[1],
+         p_tok.element_size(), _p(q_rows), _p(p_rows), _p(keep_q), _p(keep_p), _p(cu), n, _p(ids), _p(types), _p(pos), _stream())
+    return ids, types, pos
+
+
+def cls_head_fwd(cls, w1, b1, w2, b2, act):
+    """Sequence-classification head on fp32 CLS rows: ``W2 act(W1 cls + b1) + b2`` -> fp32 [M, num_labels]; act "tanh" (BERT pooler) or
+    "relu" (DistilBERT pre_classifier)."""
+    _chk(cls, F32, "cls", 2), _chk(w1, F32, "w1", 2), _chk(b1, F32, "b1", 1), _chk(w2, F32, "w2", 2), _chk(b2, F32, "b2", 1)
+    M, d = cls.shape
+    nl = w2.shape[0]
+    if not (cls.is_contiguous() and w1.is_contiguous() and w2.is_contiguous()) or w1.shape != (d, d) or b1.numel() != d \
+            or w2.shape[1] != d or b2.numel() != nl:
+        raise ValueError("cls_head_fwd: cls [M, d], w1 [d, d], b1 [d], w2 [num_labels, d], b2 [num_labels], contiguous")
+    if act not in ("tanh", "relu"):
+        raise ValueError("cls_head_fwd: act is 'tanh' or 'relu'")
+    out = torch.empty(M, nl, dtype=F32, device=cls.device)
+    if M > 0:
+        call("cldrd_cls_head_fwd", _p(cls), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), M, d, nl, 0 if act == "tanh" else 1, _stream())
+    return out
+
+
 def embed_ln_bwd(dy, ids, word, pos, type0, gamma, mean, rstd, dword, dpos, dtype0, dgamma, dbeta, partial, T, L,
                  dropout_p=0.0, seed=0, accumulate=True, pos_idx=None, dy_branch=None):
     d = word.shape[1]

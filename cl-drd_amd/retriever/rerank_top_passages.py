@@ -1,0 +1,126 @@
+"""Teacher re-scoring of a candidate run file with a cross-encoder (the step of a CL-DRD iteration that makes the next iteration's
+training data: every training query's top-k student candidates re-scored by the teacher).
+
+    python -m cldrd_amd.retriever.rerank_top_passages --run_path RUN --queries_path Q.tsv --collection_path C.tsv \\
+        --model_name_or_path DIR --tokenizer_name_or_path TOK --output_path OUT [--max_len 256] [--top_k K] [--batch_size B]
+        [--token_cache_dir DIR]
+
+``RUN``: ``qid pid [rank] [score]`` lines; ``Q.tsv`` / ``C.tsv``: ``id\\ttext``; ``DIR``: an HF BertForSequenceClassification /
+DistilBertForSequenceClassification directory.  Both tables are tokenised once into token caches built at ``--max_len`` (kept in
+``--token_cache_dir`` when given), pairs are assembled on the GPU from the cache rows and scored in batches of similar length.
+Output: ``qid\\tpid\\trank\\tscore`` - queries in order of first appearance in RUN, each query's candidates (its first ``--top_k`` distinct
+pids in RUN order) by teacher score descending, ties in RUN order.  The file does not depend on ``--batch_size``
+(``CrossEncoder.score_cached``: a pair's score depends on the pair alone).  One process, one GPU.
+
+Host side at the scale of a training set (~100 M pairs): the run is parsed into int64 arrays (~16 bytes a pair), grouped and sorted with
+numpy, and written by the native run-file writer when every query has the same number of candidates (the usual top-k run); a ragged run
+goes through the writer's Python loop."""
+from __future__ import annotations
+
+import argparse
+import os
+import tempfile
+
+import numpy as np
+import torch
+
+from ..dataset import SequenceTokenCache
+from ..models.cross_encoder import CrossEncoder, pair_lengths
+from .retrieve_top_passages import write_run_file
+
+
+def get_args(argv=None):
+    ap = argparse.ArgumentParser(description="re-score a run file's (query, passage) pairs with a cross-encoder; write the re-ranked run")
+    ap.add_argument("--run_path", required=True)
+    ap.add_argument("--queries_path", required=True)
+    ap.add_argument("--collection_path", required=True)
+    ap.add_argument("--model_name_or_path", required=True)
+    ap.add_argument("--tokenizer_name_or_path", default=None, help="default: --model_name_or_path")
+    ap.add_argument("--max_len", type=int, default=256)
+    ap.add_argument("--top_k", type=int, default=0, help="candidates per query, in run order (0: all)")
+    ap.add_argument("--batch_size", type=int, default=2048,
+                    help="pairs per encoder batch (2048: profiles/rerank_teacher_timing.txt; fewer than 1024 are padded to 1024)")
+    ap.add_argument("--token_cache_dir", default="")
+    ap.add_argument("--output_path", required=True)
+    return ap.parse_args(argv)
+
+
+def read_run(path, top_k=0):
+    """(qids, pids, group, starts) int64: the distinct (qid, pid) pairs of a ``qid pid [rank] [score]`` run file, queries in order of
+    first appearance, each query's pids in run order (its first top_k); ``group[i]`` = position of pair i's query in that order, the
+    pairs of query g are ``starts[g] .. starts[g + 1]``."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                         # (an empty file)
+        a = np.loadtxt(path, dtype=np.int64, usecols=(0, 1), ndmin=2)
+    qid, pid = a[:, 0], a[:, 1]
+    # one entry per distinct pair, the first occurrence
+    _, first = np.unique(np.stack([qid, pid], 1), axis=0, return_index=True)
+    keep = np.sort(first)
+    qid, pid = qid[keep], pid[keep]
+    # queries by first appearance; pairs grouped by query, run order inside
+    uq, q_first, q_inv = np.unique(qid, return_index=True, return_inverse=True)
+    rank_of = np.empty(uq.shape[0], dtype=np.int64)
+    rank_of[np.argsort(q_first, kind="stable")] = np.arange(uq.shape[0])
+    group = rank_of[q_inv.reshape(-1)]
+    order = np.argsort(group, kind="stable")
+    qid, pid, group = qid[order], pid[order], group[order]
+    counts = np.bincount(group, minlength=uq.shape[0])
+    starts = np.zeros(uq.shape[0] + 1, dtype=np.int64)
+    np.cumsum(counts, out=starts[1:])
+    if top_k > 0:
+        sel = np.arange(qid.shape[0]) - starts[group] < top_k
+        qid, pid, group = qid[sel], pid[sel], group[sel]
+        counts = np.minimum(counts, top_k)
+        np.cumsum(counts, out=starts[1:])
+    return qid, pid, group, starts
+
+
+def length_batches(lengths, batch_size):
+    """Pair positions in (length, position) order, cut into batches of at most batch_size pairs."""
+    order = np.argsort(np.asarray(lengths), kind="stable")
+    return [order[i:i + batch_size] for i in range(0, order.shape[0], batch_size)]
+
+
+def main(args):
+    if args.max_len > 256 or args.batch_size < 1:
+        raise ValueError("--max_len is at most 256, --batch_size at least 1")
+    torch.cuda.set_device(0)
+    from transformers import AutoTokenizer
+    tokenizer = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path or args.model_name_or_path)
+    model = CrossEncoder.from_pretrained(args.model_name_or_path, max_len=args.max_len).cuda()
+    qids, pids, group, starts = read_run(args.run_path, args.top_k)
+    with tempfile.TemporaryDirectory() as tmp:
+        cache_dir = args.token_cache_dir or tmp
+        os.makedirs(cache_dir, exist_ok=True)
+        q_cache = SequenceTokenCache.open_or_build(cache_dir, args.queries_path, tokenizer, args.max_len)
+        p_cache = SequenceTokenCache.open_or_build(cache_dir, args.collection_path, tokenizer, args.max_len)
+        q_row = {int(k): i for i, k in enumerate(np.asarray(q_cache.keys))}
+        p_row = {int(k): i for i, k in enumerate(np.asarray(p_cache.keys))}
+        try:
+            uq, q_inv = np.unique(qids, return_inverse=True)
+            q_rows = np.array([q_row[int(q)] for q in uq], dtype=np.int64)[q_inv.reshape(-1)]
+            up, p_inv = np.unique(pids, return_inverse=True)
+            p_rows = np.array([p_row[int(p)] for p in up], dtype=np.int64)[p_inv.reshape(-1)]
+        except KeyError as exc:
+            raise KeyError(f"id {exc.args[0]} of {args.run_path} is not in the query / passage table") from exc
+        _, _, lengths, _ = pair_lengths(np.asarray(q_cache.lens)[q_rows] - 2, np.asarray(p_cache.lens)[p_rows] - 2, args.max_len)
+        scores = np.empty(q_rows.shape[0], dtype=np.float32)
+        for b in length_batches(lengths, args.batch_size):
+            scores[b] = model.score_cached(q_cache, p_cache, q_rows[b], p_rows[b], args.max_len).cpu().numpy()
+    # within a query: score descending, ties in run order (the pairs are already grouped by query, in run order)
+    order = np.lexsort((np.arange(scores.shape[0]), -scores.astype(np.float64), group))
+    pids, scores = pids[order], scores[order]
+    q_out = qids[starts[:-1]]
+    counts = np.diff(starts)
+    if counts.shape[0] and (counts == counts[0]).all() and counts[0] > 0:
+        total = write_run_file(args.output_path, q_out.tolist(), pids.reshape(-1, counts[0]), scores.reshape(-1, counts[0]))
+    else:
+        total = write_run_file(args.output_path, q_out.tolist(), [pids[a:b].tolist() for a, b in zip(starts[:-1], starts[1:])],
+                               [scores[a:b].tolist() for a, b in zip(starts[:-1], starts[1:])])
+    print(f"re-scored {total} pairs of {q_out.shape[0]} queries")
+    return total
+
+
+if __name__ == "__main__":
+    main(get_args())

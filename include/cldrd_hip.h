@@ -165,6 +165,12 @@ int cldrd_embed_ln_fwd(const long long* ids, const float* word, const float* pos
                        const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
                        int d, int vocab, float eps, float dropout_p, unsigned long long seed, float* out32, int out_f16,
                        const int* pos_idx, void* out_bf16_copy, void* stream);
+/* cldrd_embed_ln_fwd with per-row token types (cross-encoder pairs): type_table = the whole [type_vocab, d] token-type table, type_ids
+ * device int32 [T] (clamped to 0 .. type_vocab - 1).  With all-zero type_ids it computes what cldrd_embed_ln_fwd(type0 = table row 0) does. */
+int cldrd_embed_ln_fwd_typed(const long long* ids, const float* word, const float* pos, const float* type_table, const int* type_ids,
+                             int type_vocab, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
+                             int d, int vocab, float eps, float dropout_p, unsigned long long seed, float* out32, int out_f16,
+                             const int* pos_idx, void* out_bf16_copy, void* stream);
 int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
                        const float* gamma, const float* mean, const float* rstd, float* dword, float* dpos,
                        float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
@@ -357,6 +363,21 @@ int cldrd_copy_segments(const void* const* src, void* const* dst, const size_t* 
 int cldrd_zero_segments(void* const* dst, const size_t* bytes, int n, void* stream);
 int cldrd_write_step_state(unsigned long long* seeds, unsigned long long seed0, unsigned long long seed1, float* hyper, float lr,
                            float beta1, float beta2, int adam_step, const float* scale_state, void* stream);
+
+/* ---- cross-encoder scoring (csrc/cross.hip) --------------------------------------------------------------------------------------
+ * cldrd_build_pairs: packed rows of `[CLS] q' [SEP] p' [SEP]` from token-cache rows (`[CLS] text [SEP]`, zero padded; tables of uint16 or
+ *   int32 elements, q_bytes / p_bytes = 2 or 4, row strides in elements, lens device int32 per table row).  Pair m reads query row q_rows[m]
+ *   and passage row p_rows[m], keeps keep_q[m] / keep_p[m] content tokens and owns packed rows cu[m] .. cu[m + 1] (cu: device int32
+ *   [n_pairs + 1]; a pair of keep_q + 2 rows is the single sequence `[CLS] q' [SEP]`).  Writes token ids int64, token types int32 (0 up
+ *   to and including the first [SEP], then 1; optional) and positions int32 (optional).  The host computes keep / cu (the tokenizer's
+ *   longest_first truncation: models/cross_encoder.py pair_lengths).
+ * cldrd_cls_head_fwd: logits fp32 [M, num_labels] = W2 act(W1 cls + b1) + b2 in fp32; cls fp32 [M, d], W1 [d, d], W2 [num_labels, d];
+ *   act 0 = tanh (BERT pooler), 1 = ReLU (DistilBERT pre_classifier).  d <= 1024. */
+int cldrd_build_pairs(const void* q_tok, const int* q_lens, int q_stride, int q_bytes, const void* p_tok, const int* p_lens, int p_stride,
+                      int p_bytes, const int* q_rows, const int* p_rows, const int* keep_q, const int* keep_p, const int* cu, int n_pairs,
+                      long long* out_ids, int* out_types, int* out_pos, void* stream);
+int cldrd_cls_head_fwd(const float* cls, const float* w1, const float* b1, const float* w2, const float* b2, float* out, int M, int d,
+                       int num_labels, int act, void* stream);
 
 /* ---- run file (retriever/retrieve_top_passages.py:98-105), HOST side: no GPU work -----------------------------------------
  * Writes `qid\tdocid\trank\tscore\n` for nq queries x k hits (rank 1..k) to `path`; the score text is Python's repr of the fp32
