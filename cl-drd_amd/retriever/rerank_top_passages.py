@@ -45,6 +45,14 @@ def get_args(argv=None):
     return ap.parse_args(argv)
 
 
+def query_groups(qid):
+    """(group, n_queries): ``group[i]`` int64 = position of line i's query among the distinct qids in order of first appearance."""
+    uq, q_first, q_inv = np.unique(qid, return_index=True, return_inverse=True)
+    rank_of = np.empty(uq.shape[0], dtype=np.int64)
+    rank_of[np.argsort(q_first, kind="stable")] = np.arange(uq.shape[0])
+    return rank_of[q_inv.reshape(-1)], uq.shape[0]
+
+
 def read_run(path, top_k=0):
     """(qids, pids, group, starts) int64: the distinct (qid, pid) pairs of a ``qid pid [rank] [score]`` run file, queries in order of
     first appearance, each query's pids in run order (its first top_k); ``group[i]`` = position of pair i's query in that order, the
@@ -59,14 +67,11 @@ def read_run(path, top_k=0):
     keep = np.sort(first)
     qid, pid = qid[keep], pid[keep]
     # queries by first appearance; pairs grouped by query, run order inside
-    uq, q_first, q_inv = np.unique(qid, return_index=True, return_inverse=True)
-    rank_of = np.empty(uq.shape[0], dtype=np.int64)
-    rank_of[np.argsort(q_first, kind="stable")] = np.arange(uq.shape[0])
-    group = rank_of[q_inv.reshape(-1)]
+    group, n_q = query_groups(qid)
     order = np.argsort(group, kind="stable")
     qid, pid, group = qid[order], pid[order], group[order]
-    counts = np.bincount(group, minlength=uq.shape[0])
-    starts = np.zeros(uq.shape[0] + 1, dtype=np.int64)
+    counts = np.bincount(group, minlength=n_q)
+    starts = np.zeros(n_q + 1, dtype=np.int64)
     np.cumsum(counts, out=starts[1:])
     if top_k > 0:
         sel = np.arange(qid.shape[0]) - starts[group] < top_k
