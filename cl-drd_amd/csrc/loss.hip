@@ -352,6 +352,64 @@ __global__ __launch_bounds__(256) void logit_reg_kernel(const float* __restrict_
     }
 }
 
+// Teacher-score distillation term behind cldrd_loss_fwd_bwd: kd = KLDiv(T) or MarginMSE of logits[:, :Nt] against teacher [B, Nt]
+// (reference losses/kl_div.py:11-22, losses/margin_mse.py:8-19 on a [B, Nt] input); loss_out[0] += alpha * kd, grad[:, :Nt] += alpha * d kd,
+// *term_out = kd.  Columns Nt..Np-1 of a row (the in-batch negatives: no teacher score) are neither read nor written.
+// One workgroup, one WAVE per row (rows wave, wave + waves, ...): the C ABI gives this term no workspace for per-row partial sums, and
+// B * Nt is a few hundred to a few thousand numbers.  A row's reductions are wave shuffles (no barrier inside the row loop); each wave adds
+// its rows in ascending order, thread 0 adds the waves in ascending order: the same bits on every call, no float atomics.
+__global__ __launch_bounds__(512) void distill_term_kernel(int kind, const float* __restrict__ logits, int B, int Np,
+                                                           const float* __restrict__ teacher, int Nt, float alpha, float T,
+                                                           float* __restrict__ loss_out, float* __restrict__ grad, float* __restrict__ term_out) {
+    __shared__ float part[8];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, waves = blockDim.x >> 6;
+    const bool add = alpha != 0.f;            // alpha == 0 leaves loss_out and grad bit for bit (x + 0 would turn a -0 into +0)
+    float acc = 0.f;
+    for (int b = wave; b < B; b += waves) {
+        const float* s = logits + (size_t)b * Np;
+        const float* t = teacher + (size_t)b * Nt;
+        float* g = grad + (size_t)b * Np;
+        float row = 0.f;
+        if (kind == LOSS_KL) {
+            const float iT = 1.0f / T;
+            float ms = NEG_INF_F(), mt = ms;
+            for (int i = lane; i < Nt; i += 64) { ms = fmaxf(ms, s[i] * iT); mt = fmaxf(mt, t[i] * iT); }
+            ms = wave_max(ms); mt = wave_max(mt);
+            float es = 0.f, et = 0.f;
+            for (int i = lane; i < Nt; i += 64) { es += __expf(s[i] * iT - ms); et += __expf(t[i] * iT - mt); }
+            es = wave_sum(es); et = wave_sum(et);
+            const float lzs = ms + __logf(es), lzt = mt + __logf(et);
+            const float k = alpha * iT / (float)B;
+            for (int i = lane; i < Nt; i += 64) {
+                const float ls = s[i] * iT - lzs, lt = t[i] * iT - lzt;
+                const float pt = __expf(lt);
+                row += pt * (lt - ls);
+                if (add) g[i] += k * (__expf(ls) - pt);
+            }
+        } else {
+            float sd = 0.f;
+            for (int i = lane; i < Nt; i += 64) sd += s[i] - t[i];
+            const float mean = wave_sum(sd) / (float)Nt;
+            const float k = alpha * 4.0f / ((float)B * (float)Nt);
+            for (int i = lane; i < Nt; i += 64) {
+                const float dc = (s[i] - t[i]) - mean;
+                row += dc * dc;
+                if (add) g[i] += k * dc;
+            }
+        }
+        acc += wave_sum(row);
+    }
+    if (lane == 0) part[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float kd = 0.f;
+        for (int w = 0; w < waves; ++w) kd += part[w];
+        kd *= kind == LOSS_KL ? 1.0f / (float)B : 2.0f / ((float)B * (float)Nt);      // batchmean | 2/(B Nt^2) * Nt * sum (d - mean)^2
+        if (add) loss_out[0] += alpha * kd;
+        if (term_out) *term_out = kd;
+    }
+}
+
 }  // namespace
 
 extern "C" int cldrd_score_fwd(const float* q, const float* p, float* logits, int B, int N, int d, int mode, void* stream) {
@@ -397,6 +455,21 @@ extern "C" int cldrd_logit_norm_reg(const float* logits, int n, float reg_lambda
                                     void* stream) {
     CLDRD_CHECK(n > 0 && reg_lambda >= 0.f, "logit_norm_reg: bad arguments");
     hipLaunchKernelGGL(logit_reg_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, n, reg_lambda, loss_out, grad, reg_out);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
+// loss_out[0] += alpha * kd, grad[:, :Nt] += alpha * d kd / d logits[:, :Nt], *term_out = kd (unweighted; may be null), with
+// kd = KLDiv(T) (kind 0) or MarginMSE (kind 1) of logits[:, :Nt] (row stride Np) against teacher [B, Nt].  Columns >= Nt are untouched.
+// Call after cldrd_loss_fwd_bwd (and cldrd_logit_norm_reg) on the same stream; without a rank term the caller zeroes loss_out / grad first.
+extern "C" int cldrd_distill_term(int kind, const float* logits, int B, int Np, const float* teacher, int Nt, float alpha, float T,
+                                  float* loss_out, float* grad, float* term_out, void* stream) {
+    CLDRD_CHECK(kind == LOSS_KL || kind == LOSS_MSE, "distill_term: kind must be 0 (KLDiv) or 1 (MarginMSE)");
+    CLDRD_CHECK(B > 0 && Nt >= 1 && Nt <= Np, "distill_term: need B > 0 and 1 <= Nt <= Np");
+    CLDRD_CHECK(alpha >= 0.f && T > 0.f, "distill_term: need alpha >= 0 and T > 0");
+    CLDRD_CHECK(logits && teacher && loss_out && grad, "distill_term: null pointer");
+    hipLaunchKernelGGL(distill_term_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, kind, logits, B, Np, teacher, Nt, alpha, T, loss_out,
+                       grad, term_out);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }

@@ -2,7 +2,7 @@
 (``retriever.rerank_top_passages``) and training (``trainer.nway_listwise``).
 
     python -m cldrd_amd.dataset.curriculum_file --run_path TEACHER.run --label_mode 9 --output_path OUT.json \\
-        [--most_hard_ranks 11:100] [--semi_hard_ranks 101:200] [--n_most_hard N] [--seed S]
+        [--most_hard_ranks 11:100] [--semi_hard_ranks 101:200] [--n_most_hard N] [--seed S] [--with_scores]
 
 Input: ``qid pid rank score`` per line (tabs or spaces; more columns are ignored), what ``rerank_top_passages`` writes.  A line with
 fewer than 4 columns and a ``(qid, pid)`` pair that occurs twice are errors.  Within a query the teacher order is score descending, ties
@@ -21,6 +21,11 @@ the reference does not ship.  Counts come from the label-mode tables of ``datase
   teacher order.  Default windows ``n_rel + 1 : 100`` (most hard) and ``101 : 200`` (semi hard) are this project's choice, not the
   reference's (it does not say how its files were cut).  A window must start after ``n_rel``, the two must not overlap, and each must
   hold at least the number drawn from it; otherwise ``ValueError`` before the run is read.
+
+``--with_scores`` adds ``relT_scores``, ``most_hard_scores`` and ``semi_hard_scores``: the run's score of every written pid, parallel to
+the pid lists (what ``NwayDataset(..., teacher_scores=True)`` and ``trainer.nway_listwise --distill_loss`` read).  A score is written as
+Python prints the float64 parsed from the run, so its float32 cast is the float32 cast of the run's column; a non-finite score in a
+written position raises ``ValueError``.  The pids do not depend on the flag, and without it the file is byte for byte what it was.
 
 A query whose list does not reach the end of every window it draws from (nor ``n_rel``) is skipped and counted; no line is padded.
 
@@ -147,15 +152,21 @@ class CurriculumExamples(NamedTuple):
     most_hard: np.ndarray    # int64 [m, n_most_hard]
     semi_hard: np.ndarray    # int64 [m, n_semi_hard]
     n_skipped: int           # queries with fewer than spec.min_candidates candidates
+    relT_scores: Optional[np.ndarray] = None         # float64, parallel to relT / most_hard / semi_hard (select_examples(with_scores=True))
+    most_hard_scores: Optional[np.ndarray] = None
+    semi_hard_scores: Optional[np.ndarray] = None
 
 
-def select_examples(run: TeacherRun, spec: CurriculumSpec, seed: int = 0) -> CurriculumExamples:
-    """relT / most-hard / semi-hard pids of every query of ``run`` that has at least ``spec.min_candidates`` candidates."""
+def select_examples(run: TeacherRun, spec: CurriculumSpec, seed: int = 0, with_scores: bool = False) -> CurriculumExamples:
+    """relT / most-hard / semi-hard pids of every query of ``run`` that has at least ``spec.min_candidates`` candidates;
+    ``with_scores``: also the run's score of each of them (gathered with the indices of the pids)."""
     from ..retriever.rerank_top_passages import query_groups
     qid, pid = run.qid, run.pid
     if qid.shape[0] == 0:
         e = np.zeros(0, dtype=np.int64)
-        return CurriculumExamples(e, e.reshape(0, spec.n_rel), e.reshape(0, spec.n_most_hard), e.reshape(0, spec.n_semi_hard), 0)
+        f = np.zeros(0, dtype=np.float64)
+        sc = (f.reshape(0, spec.n_rel), f.reshape(0, spec.n_most_hard), f.reshape(0, spec.n_semi_hard)) if with_scores else ()
+        return CurriculumExamples(e, e.reshape(0, spec.n_rel), e.reshape(0, spec.n_most_hard), e.reshape(0, spec.n_semi_hard), 0, *sc)
     group, n_q = query_groups(qid)
     # duplicate pairs: one int64 code per pair, group * n_pids + pid code (< n^2, no overflow); half the time of a lexsort over
     # (group, pid) at 100 M pairs
@@ -169,6 +180,7 @@ def select_examples(run: TeacherRun, spec: CurriculumSpec, seed: int = 0) -> Cur
     # teacher order: query (first appearance), score descending, rank ascending, line order (lexsort is stable)
     order = np.lexsort((run.rank, -run.score, group))
     pid_t = pid[order]
+    score_t = run.score[order] if with_scores else None
     counts = np.bincount(group, minlength=n_q)
     starts = np.zeros(n_q + 1, dtype=np.int64)
     np.cumsum(counts, out=starts[1:])
@@ -181,21 +193,33 @@ def select_examples(run: TeacherRun, spec: CurriculumSpec, seed: int = 0) -> Cur
 
     def sample(window, n):
         if n == 0:
-            return np.zeros((first.shape[0], 0), dtype=np.int64)
+            return np.zeros((first.shape[0], 0), dtype=np.int64), (np.zeros((first.shape[0], 0), dtype=np.float64) if with_scores else None)
         lo, hi = window
-        cand = pid_t[first[:, None] + np.arange(lo - 1, hi)]                      # [m, hi - lo + 1], teacher order
+        at = first[:, None] + np.arange(lo - 1, hi)
+        cand = pid_t[at]                                                           # [m, hi - lo + 1], teacher order
         key = splitmix64(q_key[:, None] ^ cand.astype(_U64))
         pick = np.lexsort((cand, key), axis=-1)[:, :n]                             # n smallest keys, ties by pid
         pick.sort(axis=1)                                                          # back to teacher order
-        return np.take_along_axis(cand, pick, axis=1)
+        return np.take_along_axis(cand, pick, axis=1), (np.take_along_axis(score_t[at], pick, axis=1) if with_scores else None)
 
-    relT = pid_t[first[:, None] + np.arange(spec.n_rel)]
-    return CurriculumExamples(q_ids, relT, sample(spec.most_hard_ranks, spec.n_most_hard), sample(spec.semi_hard_ranks, spec.n_semi_hard),
-                              int(n_q - first.shape[0]))
+    at_rel = first[:, None] + np.arange(spec.n_rel)
+    relT = pid_t[at_rel]
+    most, most_s = sample(spec.most_hard_ranks, spec.n_most_hard)
+    semi, semi_s = sample(spec.semi_hard_ranks, spec.n_semi_hard)
+    if not with_scores:
+        return CurriculumExamples(q_ids, relT, most, semi, int(n_q - first.shape[0]))
+    relT_s = score_t[at_rel]
+    bad = ~(np.isfinite(relT_s).all(axis=1) & np.isfinite(most_s).all(axis=1) & np.isfinite(semi_s).all(axis=1))
+    if bad.any():
+        raise ValueError(f"qid {int(q_ids[np.argmax(bad)])}: the run has a non-finite teacher score for a selected passage")
+    return CurriculumExamples(q_ids, relT, most, semi, int(n_q - first.shape[0]), relT_s, most_s, semi_s)
 
 
-def write_examples(path, ex: CurriculumExamples, chunk: int = 65536) -> int:
-    """One JSON object per query; written under a temporary name next to ``path`` and renamed into place.  Returns the line count."""
+def write_examples(path, ex: CurriculumExamples, chunk: int = 65536, with_scores: bool = False) -> int:
+    """One JSON object per query; written under a temporary name next to ``path`` and renamed into place.  Returns the line count.
+    ``with_scores``: each line also gets ``relT_scores`` / ``most_hard_scores`` / ``semi_hard_scores`` (``ex`` must carry them)."""
+    if with_scores and (ex.relT_scores is None or ex.most_hard_scores is None or ex.semi_hard_scores is None):
+        raise ValueError("write_examples(with_scores=True) needs examples selected with with_scores=True")
     path = str(path)
     parent = os.path.dirname(os.path.abspath(path))
     os.makedirs(parent, exist_ok=True)
@@ -204,6 +228,13 @@ def write_examples(path, ex: CurriculumExamples, chunk: int = 65536) -> int:
         with open(tmp, "w") as fh:
             for a in range(0, ex.qid.shape[0], chunk):
                 b = a + chunk
+                if with_scores:
+                    fh.write("".join(json.dumps({"qid": q, "relT_pids": r, "most_hard_pids": m, "semi_hard_pids": s, "relT_scores": rs,
+                                                 "most_hard_scores": ms, "semi_hard_scores": ss}) + "\n"
+                                     for q, r, m, s, rs, ms, ss in zip(ex.qid[a:b].tolist(), ex.relT[a:b].tolist(), ex.most_hard[a:b].tolist(),
+                                                                       ex.semi_hard[a:b].tolist(), ex.relT_scores[a:b].tolist(),
+                                                                       ex.most_hard_scores[a:b].tolist(), ex.semi_hard_scores[a:b].tolist())))
+                    continue
                 fh.write("".join(json.dumps({"qid": q, "relT_pids": r, "most_hard_pids": m, "semi_hard_pids": s}) + "\n"
                                  for q, r, m, s in zip(ex.qid[a:b].tolist(), ex.relT[a:b].tolist(), ex.most_hard[a:b].tolist(),
                                                        ex.semi_hard[a:b].tolist())))
@@ -215,11 +246,12 @@ def write_examples(path, ex: CurriculumExamples, chunk: int = 65536) -> int:
 
 
 def build_curriculum_file(run_path, output_path, label_mode, most_hard_ranks=None, semi_hard_ranks=None,
-                          n_most_hard: Optional[int] = None, seed: int = 0) -> Tuple[int, int]:
-    """Teacher-scored run -> training file of ``label_mode``.  Returns (queries written, queries skipped)."""
+                          n_most_hard: Optional[int] = None, seed: int = 0, with_scores: bool = False) -> Tuple[int, int]:
+    """Teacher-scored run -> training file of ``label_mode`` (``with_scores``: with the teacher's score of every written pid).
+    Returns (queries written, queries skipped)."""
     spec = curriculum_spec(label_mode, most_hard_ranks, semi_hard_ranks, n_most_hard)
-    ex = select_examples(read_teacher_run(run_path), spec, seed)
-    return write_examples(output_path, ex), ex.n_skipped
+    ex = select_examples(read_teacher_run(run_path), spec, seed, with_scores=with_scores)
+    return write_examples(output_path, ex, with_scores=with_scores), ex.n_skipped
 
 
 def get_args(argv=None):
@@ -237,12 +269,15 @@ def get_args(argv=None):
                     help="negatives drawn from the most-hard window, the rest from the semi-hard one (default: the label mode's first "
                          "run of equal negative labels)")
     ap.add_argument("--seed", default=0, type=int, help="sampling seed; a query's line depends only on it and that query's own lines")
+    ap.add_argument("--with_scores", action="store_true", default=False,
+                    help="also write relT_scores / most_hard_scores / semi_hard_scores: the run's score of every written pid "
+                         "(what trainer.nway_listwise --distill_loss trains on)")
     return ap.parse_args(argv)
 
 
 def main(args):
     n, skipped = build_curriculum_file(args.run_path, args.output_path, args.label_mode, args.most_hard_ranks, args.semi_hard_ranks,
-                                       args.n_most_hard, args.seed)
+                                       args.n_most_hard, args.seed, with_scores=getattr(args, "with_scores", False))
     need = curriculum_spec(args.label_mode, args.most_hard_ranks, args.semi_hard_ranks, args.n_most_hard).min_candidates
     print(f"wrote {n} queries to {args.output_path}; skipped {skipped} with fewer than {need} candidates")
     return n, skipped

@@ -13,6 +13,10 @@ Host tokenisation becomes the bottleneck at MI355X speeds (SURVEY.md section 7 /
 from ``TokenCache``: token ids of every query / passage tokenised ONCE into memory-mapped ``[n, L]`` int32 arrays plus lengths;
 ``NwayDataset(..., token_cache=...)`` then builds batches by gather + trim, with output identical to the tokenising path
 (tests/test_nway_dataset.py).
+
+``teacher_scores=True`` (this package's addition; the reference's knowledge-distillation trainers were not published): the relT /
+most-hard / semi-hard files written by ``dataset.curriculum_file --with_scores`` carry the teacher's score of every pid, and batches
+gain ``"teacher_scores"``, float32 ``[B, N]`` in the order of ``nway_pids``.
 """
 from __future__ import annotations
 
@@ -93,8 +97,21 @@ def _read_json_lines(path: str, rank: int, nranks: Optional[int], convert: Calla
     return out
 
 
-def _hard_negatives(ex: dict) -> dict:
-    return {"qid": ex["qid"], "relT_pids": ex["relT_pids"], "neg_pids": ex["most_hard_pids"] + ex["semi_hard_pids"]}
+def _hard_negatives(ex: dict, teacher_scores: bool = False) -> dict:
+    out = {"qid": ex["qid"], "relT_pids": ex["relT_pids"], "neg_pids": ex["most_hard_pids"] + ex["semi_hard_pids"]}
+    if teacher_scores:
+        for pk, sk in (("relT_pids", "relT_scores"), ("most_hard_pids", "most_hard_scores"), ("semi_hard_pids", "semi_hard_scores")):
+            if sk not in ex:
+                raise ValueError(f"qid {ex['qid']}: the training file has no {sk} (build it with dataset.curriculum_file --with_scores)")
+            if len(ex[sk]) != len(ex[pk]):
+                raise ValueError(f"qid {ex['qid']}: {sk} has {len(ex[sk])} entries, {pk} has {len(ex[pk])}")
+        out["relT_scores"] = ex["relT_scores"]
+        out["neg_scores"] = ex["most_hard_scores"] + ex["semi_hard_scores"]
+    return out
+
+
+def _hard_negatives_scored(ex: dict) -> dict:
+    return _hard_negatives(ex, teacher_scores=True)
 
 
 class TokenCache:
@@ -182,8 +199,19 @@ def attach_lengths(batch):
 
 class NwayDataset(torch.utils.data.Dataset):
     def __init__(self, qid_to_query, pid_to_passage, train_examples, tokenizer, max_query_len, max_passage_len, label_mode="3",
-                 query_cache: Optional[TokenCache] = None, passage_cache: Optional[TokenCache] = None):
+                 query_cache: Optional[TokenCache] = None, passage_cache: Optional[TokenCache] = None, teacher_scores: bool = False):
         super().__init__()
+        self.teacher_scores = bool(teacher_scores)
+        if self.teacher_scores:
+            # checked here, at load time, not in a loader worker in the middle of an epoch
+            if label_mode == "1":
+                raise ValueError("label mode 1 files ({qid, rel_pid, neg_pids}) carry no teacher scores")
+            for ex in train_examples:
+                for pk, sk in (("relT_pids", "relT_scores"), ("neg_pids", "neg_scores")):
+                    if sk not in ex:
+                        raise ValueError(f"qid {ex.get('qid')}: the example has no {sk} (teacher_scores=True)")
+                    if len(ex[sk]) != len(ex[pk]):
+                        raise ValueError(f"qid {ex.get('qid')}: {sk} has {len(ex[sk])} entries, {pk} has {len(ex[pk])}")
         self.qid_to_query = qid_to_query
         self.pid_to_passage = pid_to_passage
         self.train_examples = train_examples
@@ -204,6 +232,8 @@ class NwayDataset(torch.utils.data.Dataset):
         assert len(rel) == _REL[self.label_mode] and len(neg) == len(_NEG[self.label_mode]), \
             f"label mode {self.label_mode} needs {_REL[self.label_mode]} relT and {len(_NEG[self.label_mode])} neg pids"
         item = {"qid": ex["qid"], "relT_pids": rel, "neg_pids": neg, "labels": list(self._labels)}
+        if self.teacher_scores:
+            item["teacher_scores"] = list(ex["relT_scores"]) + list(ex["neg_scores"])      # the order of nway_pids
         if self.query_cache is None:
             item["query"] = self.qid_to_query[ex["qid"]]
             item["relT_passages"] = [self.pid_to_passage[p] for p in rel]
@@ -229,8 +259,12 @@ class NwayDataset(torch.utils.data.Dataset):
             passages = self.tokenizer(texts, padding=True, truncation="longest_first", return_tensors="pt",
                                       max_length=self.max_passage_len)
         passages = {k: v.view(bz, nway, -1) for k, v in passages.items()}
-        return attach_lengths({"qid": qids, "relT_pids": rel, "neg_pids": neg, "nway_pids": nway_pids, "query": queries,
-                               "nway_passages": passages, "labels": torch.FloatTensor([b["labels"] for b in batch])})
+        out = {"qid": qids, "relT_pids": rel, "neg_pids": neg, "nway_pids": nway_pids, "query": queries,
+               "nway_passages": passages, "labels": torch.FloatTensor([b["labels"] for b in batch])}
+        if self.teacher_scores:
+            out["teacher_scores"] = torch.from_numpy(np.array([b["teacher_scores"] for b in batch], dtype=np.float64).astype(np.float32)
+                                                     .reshape(bz, nway))
+        return attach_lengths(out)
 
     # ---- constructors (reference :120-470) --------------------------------------------------------------------
     @classmethod
@@ -264,38 +298,46 @@ class NwayDataset(torch.utils.data.Dataset):
 
     @classmethod
     def create_from_relT_most_semi_hard_file(cls, queries_path, passages_path, training_path, tokenizer, max_query_len, max_passage_len,
-                                             label_mode, rank=-1, nranks=None, _modes=None):
+                                             label_mode, rank=-1, nranks=None, _modes=None, teacher_scores=False):
         """``{"qid", "relT_pids", "most_hard_pids", "semi_hard_pids"}`` per line; negatives = most hard then semi hard
-        (reference :213-258, and the four constructors below with their label-mode guards)"""
+        (reference :213-258, and the four constructors below with their label-mode guards).  ``teacher_scores=True``: the lines also
+        hold ``relT_scores`` / ``most_hard_scores`` / ``semi_hard_scores`` (``ValueError`` with the qid if not, or if a length differs)."""
         _check_rank(rank, nranks)
         if _modes is not None:
             assert label_mode in _modes
-        examples = _read_json_lines(training_path, rank, nranks, _hard_negatives)
-        return cls._make(queries_path, passages_path, examples, tokenizer, max_query_len, max_passage_len, label_mode)
+        if teacher_scores and label_mode == "1":
+            raise ValueError("label mode 1 files ({qid, rel_pid, neg_pids}) carry no teacher scores")
+        examples = _read_json_lines(training_path, rank, nranks, _hard_negatives_scored if teacher_scores else _hard_negatives)
+        return cls._make(queries_path, passages_path, examples, tokenizer, max_query_len, max_passage_len, label_mode,
+                         **({"teacher_scores": True} if teacher_scores else {}))
 
     @classmethod
     def create_from_10relT_20neg_file(cls, queries_path, passages_path, training_path, tokenizer, max_query_len, max_passage_len, label_mode,
-                                               rank=-1, nranks=None):
+                                               rank=-1, nranks=None, teacher_scores=False):
         return cls.create_from_relT_most_semi_hard_file(queries_path, passages_path, training_path, tokenizer, max_query_len,
-                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("3", "9"))
+                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("3", "9"),
+                                                        teacher_scores=teacher_scores)
 
     @classmethod
     def create_from_20relT_10neg_file(cls, queries_path, passages_path, training_path, tokenizer, max_query_len, max_passage_len, label_mode,
-                                               rank=-1, nranks=None):
+                                               rank=-1, nranks=None, teacher_scores=False):
         return cls.create_from_relT_most_semi_hard_file(queries_path, passages_path, training_path, tokenizer, max_query_len,
-                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("5", "10"))
+                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("5", "10"),
+                                                        teacher_scores=teacher_scores)
 
     @classmethod
     def create_from_30relT_file(cls, queries_path, passages_path, training_path, tokenizer, max_query_len, max_passage_len, label_mode,
-                                         rank=-1, nranks=None):
+                                         rank=-1, nranks=None, teacher_scores=False):
         return cls.create_from_relT_most_semi_hard_file(queries_path, passages_path, training_path, tokenizer, max_query_len,
-                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("6",))
+                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("6",),
+                                                        teacher_scores=teacher_scores)
 
     @classmethod
     def create_from_5relT_25neg_file(cls, queries_path, passages_path, training_path, tokenizer, max_query_len, max_passage_len, label_mode,
-                                              rank=-1, nranks=None):
+                                              rank=-1, nranks=None, teacher_scores=False):
         return cls.create_from_relT_most_semi_hard_file(queries_path, passages_path, training_path, tokenizer, max_query_len,
-                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("7", "8"))
+                                                        max_passage_len, label_mode, rank=rank, nranks=nranks, _modes=("7", "8"),
+                                                        teacher_scores=teacher_scores)
 
     # ---- pre-tokenised cache ------------------------------------------------------------------------------------
     def with_token_cache(self, cache_dir: Optional[str] = None, build: bool = True) -> "NwayDataset":

@@ -808,6 +808,27 @@ def logit_norm_reg(logits, reg_lambda, loss_out, grad, reg_out=None):
     call("cldrd_logit_norm_reg", _p(logits), logits.numel(), float(reg_lambda), _p(loss_out), _p(grad), _p(reg_out), _stream())
 
 
+
+DISTILL_KINDS = {"kl_div": 0, "margin_mse": 1}
+
+
+def distill_term(kind, logits, teacher, alpha, T, loss_out, grad, term_out=None):
+    """loss_out[0] += alpha * kd and grad[:, :Nt] += alpha * d kd / d logits[:, :Nt], kd = KLDiv(T) / MarginMSE of logits[:, :Nt] against
+    teacher [B, Nt] (reference losses/kl_div.py, margin_mse.py); term_out[0] = kd.  Columns >= Nt of logits / grad are not touched."""
+    if kind not in DISTILL_KINDS:
+        raise ValueError(f"distill_term: kind must be one of {tuple(DISTILL_KINDS)}")
+    _chk(logits, F32, "logits", 2), _chk(teacher, F32, "teacher", 2), _chk(loss_out, F32, "loss_out", 1), _chk(grad, F32, "grad", 2)
+    if not (logits.is_contiguous() and grad.is_contiguous() and teacher.is_contiguous()) or grad.shape != logits.shape:
+        raise ValueError("distill_term: logits, grad and teacher must be contiguous, grad of the shape of logits")
+    B, Np = logits.shape
+    if teacher.shape[0] != B or not 1 <= teacher.shape[1] <= Np:
+        raise ValueError(f"distill_term: teacher must be [{B}, 1..{Np}], got {tuple(teacher.shape)}")
+    if term_out is not None:
+        _chk(term_out, F32, "term_out", 1)
+    call("cldrd_distill_term", DISTILL_KINDS[kind], _p(logits), B, Np, _p(teacher), teacher.shape[1], float(alpha), float(T), _p(loss_out),
+         _p(grad), _p(term_out), _stream())
+
+
 def sqnorm_blocks() -> int:
     return _lib.load().cldrd_sqnorm_blocks()
 

@@ -97,8 +97,10 @@ def teacher_scores(seed: int, batch: int, nway: int) -> np.ndarray:
 
 
 def nway_batch(seed: int, batch: int, nway: int, q_len: int, p_len: int, *, vocab: int = VOCAB,
-               ragged: bool = False, label_kind: str = "teacher") -> dict:
-    """A training batch with the collate_fn layout (reference dataset/nway_dataset.py:103-118)."""
+               ragged: bool = False, label_kind: str = "teacher", with_teacher_scores: bool = False) -> dict:
+    """A training batch with the collate_fn layout (reference dataset/nway_dataset.py:103-118).  ``with_teacher_scores``: plus
+    ``"teacher_scores"`` float32 [batch, nway] as ``NwayDataset(..., teacher_scores=True)`` collates them (cross-encoder-like range,
+    descending per row as a teacher-ordered file has them), from a seed of their own."""
     q_ids = token_ids(seed + 1, batch, q_len, vocab)
     p_ids = token_ids(seed + 2, batch * nway, p_len, vocab)
     q_mask = np.ones_like(q_ids)
@@ -116,13 +118,16 @@ def nway_batch(seed: int, batch: int, nway: int, q_len: int, p_len: int, *, voca
         q_ids = np.where(arq < qlens[:, None], q_ids, 0)
         q_ids[np.arange(batch), qlens - 1] = SEP_ID if vocab > SEP_ID else 2
     labels = teacher_scores(seed + 5, batch, nway) if label_kind == "teacher" else labels_mode9(batch, nway)
-    return {
+    out = {
         "qid": torch.arange(batch, dtype=torch.int64),
         "query": {"input_ids": torch.from_numpy(q_ids), "attention_mask": torch.from_numpy(q_mask)},
         "nway_passages": {"input_ids": torch.from_numpy(p_ids.reshape(batch, nway, p_len)),
                           "attention_mask": torch.from_numpy(p_mask.reshape(batch, nway, p_len))},
         "labels": torch.from_numpy(labels),
     }
+    if with_teacher_scores:
+        out["teacher_scores"] = torch.from_numpy(teacher_scores(seed + 6, batch, nway))
+    return out
 
 
 def seq_batch(seed: int, rows: int, length: int, *, vocab: int = VOCAB, ragged: bool = False, first_id: int = 0) -> dict:

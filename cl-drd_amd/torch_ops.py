@@ -9,6 +9,7 @@ formula where the reference differentiates through the call:
 
     cldrd::listwise_loss      losses/{kl_div,margin_mse,ranknet,lambda_rank,weighted_pointwise}.py     value + d loss / d y_pred in one launch
     cldrd::lambda_loss        losses/standard_lambda_rank.py:3-95
+    cldrd::distill_term       alpha * {KLDiv(T), MarginMSE}(y_pred[:, :Nt], teacher scores): the term the fused trainer adds behind its rank loss
     cldrd::nway_score         models/nway_dual_encoder.py:30-47 (N-way / in-batch scoring), backward cldrd::nway_score_bwd
     cldrd::linear             torch.nn.Linear inside the HF encoder (bias / erf-GELU / residual epilogue), forward
     cldrd::layer_norm         HF LayerNorm (eps 1e-12), forward
@@ -83,6 +84,39 @@ def _lambda_backward(ctx, g_out, g_grad):
 
 
 torch.library.register_autograd("cldrd::lambda_loss", _lambda_backward, setup_context=_loss_setup)
+
+
+_DISTILL_KINDS = ("kl_div", "margin_mse")
+
+
+@torch.library.custom_op("cldrd::distill_term", mutates_args=(), device_types="cuda")
+def distill_term(y_pred: Tensor, teacher: Tensor, kind: int, alpha: float, T: float) -> Tuple[Tensor, Tensor]:
+    """(out float[2] = {alpha * kd, kd}, d (alpha * kd) / d y_pred [B, Np]) with kd = KLDiv(T) (kind 0) or MarginMSE (kind 1) of
+    y_pred[:, :Nt] against teacher [B, Nt]; the columns >= Nt of the gradient are zero."""
+    y = y_pred.detach().float().contiguous()
+    out = torch.zeros(2, dtype=torch.float32, device=y.device)
+    grad = torch.zeros_like(y)
+    ops.distill_term(_DISTILL_KINDS[kind], y, teacher.detach().float().contiguous(), alpha, T, out[0:1], grad, out[1:2])
+    return out, grad
+
+
+@distill_term.register_fake
+def _(y_pred, teacher, kind, alpha, T):
+    return y_pred.new_empty((2,), dtype=torch.float32), y_pred.new_empty(y_pred.shape, dtype=torch.float32)
+
+
+def _distill_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.in_dtype, ctx.alpha = inputs[0].dtype, float(inputs[3])
+
+
+def _distill_backward(ctx, g_out, g_grad):
+    (grad,) = ctx.saved_tensors          # d (alpha kd): the unweighted kd's gradient is 1 / alpha of it (alpha == 0: both are zero here)
+    coef = g_out[0] + (g_out[1] / ctx.alpha if ctx.alpha > 0.0 else 0.0)
+    return (grad * coef).to(ctx.in_dtype), None, None, None, None
+
+
+torch.library.register_autograd("cldrd::distill_term", _distill_backward, setup_context=_distill_setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------- scoring
@@ -176,4 +210,4 @@ def _(qkv, mask, nseq, L, H):
     return qkv.new_empty((qkv.shape[0], H * 64))
 
 
-OPS = ("listwise_loss", "lambda_loss", "nway_score", "nway_score_bwd", "linear", "layer_norm", "self_attention")
+OPS = ("listwise_loss", "lambda_loss", "distill_term", "nway_score", "nway_score_bwd", "linear", "layer_norm", "self_attention")

@@ -16,7 +16,10 @@ Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
     step, which - as in ``scaler.step`` - does not advance Adam's bias-correction step);
   * no per-step D2H sync: loss / train-MRR are read back only every ``logging_steps``;
   * the three stage scripts differ only in defaults, so there is one trainer with a ``--loss`` selector
-    (default ``lambda_mrr`` as in the reference).
+    (default ``lambda_mrr`` as in the reference);
+  * ``--distill_loss kl_div | margin_mse`` adds ``distill_alpha * kd(logits[:, :nway], batch["teacher_scores"])`` to that loss (one more
+    launch on the loss stream, ``cldrd_distill_term``): the role of the knowledge-distillation trainers the reference's scripts name
+    (``scripts/unity/kd_nway_listwise.sh``, ``logit_reg_nway_listwise.sh``) but never published.
 """
 from __future__ import annotations
 
@@ -33,6 +36,7 @@ from ..models.nway_dual_encoder import NwayDualEncoder, _lengths, score_mode
 from ..retriever.retrieval_utils import cap_host_threads
 
 LOSS_KINDS = ("lambda_mrr", "ranknet", "kl_div", "margin_mse")
+DISTILL_KINDS = ("kl_div", "margin_mse")      # --distill_loss: the term on batch["teacher_scores"] added to the rank loss
 
 
 def no_decay(name: str) -> bool:
@@ -80,9 +84,20 @@ def optimizer_param_groups(model):
 class NwayTrainer:
     def __init__(self, model: NwayDualEncoder, *, loss: str = "lambda_mrr", T: float = 1.0, learning_rate: float = 7e-6,
                  weight_decay: float = 0.01, adam_epsilon: float = 1e-8, max_grad_norm: float = 1.0, warmup_steps: int = 4000,
-                 total_steps: int = 100000, betas=(0.9, 0.999), bucket_layers: int = 1, reg_lambda: float = 0.0):
+                 total_steps: int = 100000, betas=(0.9, 0.999), bucket_layers: int = 1, reg_lambda: float = 0.0,
+                 distill=None, distill_alpha: float = 1.0, distill_T: float = 1.0, distill_only: bool = False):
         if loss not in LOSS_KINDS:
             raise ValueError(f"loss must be one of {LOSS_KINDS}")
+        if distill is not None and distill not in DISTILL_KINDS:
+            raise ValueError(f"distill must be None or one of {DISTILL_KINDS}")
+        if distill is not None and (not float(distill_alpha) >= 0.0 or not float(distill_T) > 0.0):
+            raise ValueError("distill_alpha must be >= 0 and distill_T > 0")
+        if distill_only and distill is None:
+            raise ValueError("distill_only needs a distill loss")
+        # teacher-score term: total = loss(logits, labels) + distill_alpha * kd(logits[:, :nway], batch["teacher_scores"]); distill_only drops
+        # the first summand.  last_kd: the unweighted term of the last step (device scalar, like last_reg)
+        self.distill, self.distill_alpha, self.distill_T, self.distill_only = distill, float(distill_alpha), float(distill_T), bool(distill_only)
+        self.last_kd = None
         self.model = model
         self.loss_kind, self.T = loss, T
         self.reg_lambda = float(reg_lambda)
@@ -271,6 +286,7 @@ class NwayTrainer:
         qe, pe = model.query_encoder, model.passage_encoder
         q, nw = batch["query"], batch["nway_passages"]
         bz, nway, L = nw["input_ids"].shape
+        teacher = self._teacher_scores(batch, bz, nway)
         write_once = not model.share_weights and not self.zero_all_grads      # (test hook: zero_all_grads = True zeroes + accumulates)
         main = torch.cuda.current_stream()
         # The query tower is ~1 % of the FLOPs but dozens of small, latency-bound launches: it runs on its own stream
@@ -336,10 +352,18 @@ class NwayTrainer:
             labels = batch["labels"].to(device=logits.device, dtype=torch.float32)
             if mode != 0:   # in-batch negatives get the -0.5 label (reference nway_listwise_1.py:341-344)
                 labels = torch.cat([labels, torch.full((bz, Np - nway), -0.5, dtype=torch.float32, device=logits.device)], dim=-1)
-            loss_out, dlogits = ops.loss_fwd_bwd(self.loss_kind, logits, labels.contiguous(), T=self.T)
+            if self.distill_only:
+                loss_out, dlogits = torch.zeros(2, dtype=torch.float32, device=logits.device), torch.zeros_like(logits)
+            else:
+                loss_out, dlogits = ops.loss_fwd_bwd(self.loss_kind, logits, labels.contiguous(), T=self.T)
             if self.reg_lambda > 0.0 and mode == 0:     # reference nway_listwise_1.py:346-350: only without in-batch negatives
                 self.last_reg = torch.empty(1, dtype=torch.float32, device=logits.device)
                 ops.logit_norm_reg(logits, self.reg_lambda, loss_out, dlogits, self.last_reg)
+            if teacher is not None:
+                # the row's own nway columns only: the in-batch columns behind them have no teacher score and keep the rank loss's gradient
+                self.last_kd = torch.empty(1, dtype=torch.float32, device=logits.device)
+                ops.distill_term(self.distill, logits, teacher.to(device=logits.device, dtype=torch.float32).contiguous(), self.distill_alpha,
+                                 self.distill_T, loss_out, dlogits, self.last_kd)
             if self.world > 1:
                 dlogits.mul_(1.0 / self.world)      # gradient mean over ranks == DDP's all-reduce / world_size
             dq, dp = torch.empty_like(q_cls), torch.empty_like(p_cls)
@@ -355,6 +379,18 @@ class NwayTrainer:
         with ops.loss_scale(self._scale_state.data_ptr() if self.amp16 else None, self.scale_growth_interval):
             return self._backward(batch, model, qe, pe, q_cls, p_cls, q_tape, p_tape, dlogits, dq, dp, bz, nway, mode, main, side, write_once, loss_out, logits,
                                   lst)
+
+    def _teacher_scores(self, batch, bz, nway):
+        """batch["teacher_scores"] of a distilling trainer ([B, nway], checked); None for a trainer without ``distill`` (the key is ignored)."""
+        if self.distill is None:
+            return None
+        t = batch.get("teacher_scores")
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"this trainer distils ({self.distill}) and needs batch['teacher_scores'] (float [B, nway]): build the training "
+                             "file with dataset.curriculum_file --with_scores and the dataset with teacher_scores=True")
+        if tuple(t.shape) != (bz, nway):
+            raise ValueError(f"batch['teacher_scores'] must be [{bz}, {nway}] like the passages, got {tuple(t.shape)}")
+        return t
 
     def _backward(self, batch, model, qe, pe, q_cls, p_cls, q_tape, p_tape, dlogits, dq, dp, bz, nway, mode, main, side, write_once, loss_out, logits,
                   lst=None):
@@ -593,10 +629,13 @@ class NwayTrainer:
         return (not self.model.share_weights and not getattr(self, "_graph_broken", False)
                 and _env_flag("CLDRD_GRAPH", "1") != "0" and self.flat_p.is_cuda)
 
-    @staticmethod
-    def _batch_key(batch):
+    def _batch_key(self, batch):
         q, nw = batch["query"], batch["nway_passages"]
-        return (tuple(q["input_ids"].shape), q.get("attention_mask") is not None, tuple(nw["input_ids"].shape), tuple(batch["labels"].shape))
+        key = (tuple(q["input_ids"].shape), q.get("attention_mask") is not None, tuple(nw["input_ids"].shape), tuple(batch["labels"].shape))
+        if self.distill is not None:
+            bz, nway, _ = nw["input_ids"].shape
+            key += (tuple(self._teacher_scores(batch, bz, nway).shape),)
+        return key
 
     def _train_step_graph(self, batch):
         key = self._batch_key(batch)
@@ -675,6 +714,8 @@ class NwayTrainer:
             for t in towers:
                 t._h_stale = True
         self.last_logits = entry["logits"]
+        if self.distill is not None:
+            self.last_kd = entry["last_kd"]          # this shape's captured output (another shape's replay or an eager step may have run since)
         return entry["loss_out"]
 
     def _agree_on_capture(self, ok: bool) -> bool:
@@ -689,12 +730,15 @@ class NwayTrainer:
             self._graph_broken = True
         return agreed
 
-    @staticmethod
-    def _flat_inputs(batch):
+    def _flat_inputs(self, batch):
+        """The per-step inputs of the captured step, in one order for the static batch and every incoming one (at most 6 segments;
+        cldrd_copy_segments takes 8).  The teacher scores are one of them: a distilling step reads this step's scores, like its labels."""
         q, nw = batch["query"], batch["nway_passages"]
         t = [q["input_ids"], nw["input_ids"], nw["attention_mask"], batch["labels"]]
         if q.get("attention_mask") is not None:
             t.append(q["attention_mask"])
+        if self.distill is not None:
+            t.append(batch["teacher_scores"])
         return t
 
     def _capture(self, batch):
@@ -706,6 +750,8 @@ class NwayTrainer:
                   "labels": batch["labels"].to(device=dev, dtype=torch.float32).clone()}
         if q.get("attention_mask") is not None:
             static["query"]["attention_mask"] = q["attention_mask"].to(dev).clone()
+        if self.distill is not None:
+            static["teacher_scores"] = batch["teacher_scores"].to(device=dev, dtype=torch.float32).contiguous().clone()
         for i, t in enumerate(towers):
             t.seed_base_ptr = self._state["seeds"].data_ptr() + 8 * i
         torch.cuda.synchronize()
@@ -727,7 +773,8 @@ class NwayTrainer:
                     if s_ is not None:
                         cur.wait_stream(s_)
                 raise
-        return {"graph": g, "inputs": self._flat_inputs(static), "loss_out": loss_out, "logits": logits, "static": static}
+        return {"graph": g, "inputs": self._flat_inputs(static), "loss_out": loss_out, "logits": logits, "static": static,
+                "last_kd": self.last_kd}
 
     # ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -882,6 +929,12 @@ def get_args(argv=None):
     ap.add_argument("--n_gpu", default=1, type=int)
     ap.add_argument("--local_rank", default=-1, type=int)
     ap.add_argument("--loss", default="lambda_mrr", choices=LOSS_KINDS)
+    ap.add_argument("--distill_loss", default=None, choices=DISTILL_KINDS,
+                    help="add distill_alpha * KLDiv(distill_T) / MarginMSE of the logits against the teacher scores of the training file "
+                         "(dataset.curriculum_file --with_scores) to --loss")
+    ap.add_argument("--distill_alpha", default=1.0, type=float, help="weight of the --distill_loss term")
+    ap.add_argument("--distill_T", default=1.0, type=float, help="temperature of --distill_loss kl_div")
+    ap.add_argument("--distill_only", action="store_true", default=False, help="drop the --loss term: total = distill_alpha * distill loss")
     ap.add_argument("--token_cache_dir", default=None)
     ap.add_argument("--loader_workers", default=4, type=int, help="collate (tokenise / gather from the token cache) worker processes; "
                     "batches arrive in pinned memory, a few steps ahead of the GPU")
@@ -891,6 +944,12 @@ def get_args(argv=None):
     ap.add_argument("--synthetic_model", default="distilbert", choices=("distilbert", "tiny"),
                     help="random-init architecture for --synthetic_steps runs without a model directory (tiny: encoder.tiny_config)")
     args = ap.parse_args(argv)
+    if args.distill_loss is None and args.distill_only:
+        ap.error("--distill_only needs --distill_loss")
+    if args.distill_loss is not None and args.label_mode == "1" and args.synthetic_steps <= 0:
+        ap.error("--distill_loss needs a relT / most-hard / semi-hard training file with scores; --label_mode 1 files have none")
+    if args.distill_loss is not None and (not args.distill_alpha >= 0.0 or not args.distill_T > 0.0):
+        ap.error("--distill_alpha must be >= 0 and --distill_T > 0")
     args.run_folder = os.path.join(args.experiment_folder, args.run_folder)
     args.log_dir = os.path.join(args.run_folder, args.log_dir)
     args.model_save_dir = os.path.join(args.run_folder, args.model_save_dir)
@@ -953,6 +1012,11 @@ def build_dataloader(args):
     kw = dict(max_query_len=args.query_max_len, max_passage_len=args.passage_max_len, label_mode=args.label_mode)
     shard = dict(rank=args.rank, nranks=args.nranks) if args.distributed else {}
     mode = args.label_mode
+    distill = getattr(args, "distill_loss", None) is not None
+    if distill and mode == "1":
+        raise ValueError("--distill_loss: label mode 1 files ({qid, rel_pid, neg_pids}) carry no teacher scores")
+    if distill:
+        shard["teacher_scores"] = True
     if mode == "1":
         if args.distributed:
             raise NotImplementedError
@@ -1005,7 +1069,8 @@ class _SyntheticBatches(torch.utils.data.Dataset):
         a = self.args
         b = syn.nway_batch(a.seed + 1000 * a.rank + i, a.train_batch_size // a.nranks, a.synthetic_nway, a.query_max_len,
                            a.passage_max_len, vocab=getattr(a, "synthetic_vocab", syn.VOCAB), ragged=not getattr(a, "synthetic_fixed", False),
-                           label_kind="teacher" if a.loss in ("kl_div", "margin_mse") else "mode9")
+                           label_kind="teacher" if a.loss in ("kl_div", "margin_mse") else "mode9",
+                           with_teacher_scores=getattr(a, "distill_loss", None) is not None)
         return attach_lengths(b)
 
 
@@ -1069,7 +1134,9 @@ def train(args):
     t_total = steps_per_epoch * args.num_train_epochs
     trainer = NwayTrainer(model, loss=args.loss, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
                           adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm, warmup_steps=args.warmup_steps,
-                          total_steps=t_total, reg_lambda=args.reg_lambda)
+                          total_steps=t_total, reg_lambda=args.reg_lambda, distill=getattr(args, "distill_loss", None),
+                          distill_alpha=getattr(args, "distill_alpha", 1.0), distill_T=getattr(args, "distill_T", 1.0),
+                          distill_only=getattr(args, "distill_only", False))
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)            # after model / loader construction, as the reference does (:282)
@@ -1087,7 +1154,7 @@ def train(args):
     if main_rank:
         os.makedirs(args.log_dir, exist_ok=True)
         os.makedirs(args.model_save_dir, exist_ok=True)
-    loss_m, mrr_m, rec_m, reg_m, ratio_m = _Avg(), _Avg(), _Avg(), _Avg(), _Avg()
+    loss_m, mrr_m, rec_m, reg_m, ratio_m, kd_m = _Avg(), _Avg(), _Avg(), _Avg(), _Avg(), _Avg()
     topk = 10
     log_file = os.path.join(args.log_dir, "train_logs.log")
     for epoch in range(start_epoch, args.num_train_epochs):
@@ -1111,11 +1178,14 @@ def train(args):
                     reg = float(trainer.last_reg.item())
                     reg_m.update(reg), ratio_m.update(reg / loss_val if loss_val else 0.0)
                     extra = dict(reg_loss=reg_m.avg, total_aux_ratio=ratio_m.avg)
+                if trainer.distill is not None and trainer.last_kd is not None:
+                    kd_m.update(float(trainer.last_kd.item()))          # the unweighted distillation term
+                    extra["kd_loss"] = kd_m.avg
                 if trainer.amp16:
                     extra["skipped_steps"] = float(trainer.skipped_steps())     # the loss-scale safety net (GradScaler's skipped steps)
                 write_train_logs(epoch + 1, trainer.global_step, loss_m.avg, mrr_m.avg, rec_m.avg, trainer.lr(), filename=log_file,
                                  cutoff=topk, **extra)
-                for m in (loss_m, mrr_m, rec_m, reg_m, ratio_m):
+                for m in (loss_m, mrr_m, rec_m, reg_m, ratio_m, kd_m):
                     m.reset()
             if main_rank and trainer.global_step % args.evaluate_steps == 0:
                 ckpt = trainer.state_dict()

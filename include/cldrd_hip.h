@@ -226,6 +226,17 @@ int cldrd_loss_fwd_bwd(int kind, const float* y_pred, const float* y_true, const
  * (reg_out may be null).  Same stream as, and after, cldrd_loss_fwd_bwd. */
 int cldrd_logit_norm_reg(const float* logits, int n, float reg_lambda, float* loss_out, float* grad, float* reg_out, void* stream);
 
+/* Teacher-score distillation term added behind cldrd_loss_fwd_bwd (and cldrd_logit_norm_reg) on the same stream.
+ * kd = KLDiv(T)(logits[:, :Nt], teacher) (kind 0; losses/kl_div.py:11-22, batchmean, no T^2 factor) or
+ *      MarginMSE()(logits[:, :Nt], teacher) (kind 1; losses/margin_mse.py:8-19, mean over B*Nt*Nt margins);
+ * loss_out[0] += alpha * kd, grad[b, i] += alpha * d kd / d logits[b, i] for i < Nt, *term_out = kd (unweighted; term_out may be null).
+ * logits and grad are [B, Np] (row stride Np), teacher is [B, Nt]; columns Nt..Np-1 (the in-batch negatives of
+ * models/nway_dual_encoder.py:30-44, which have no teacher score) are neither read nor written.  1 <= Nt <= Np, alpha >= 0, T > 0.
+ * alpha == 0 leaves loss_out and grad bit for bit.  Without a rank term the caller zeroes loss_out / grad first.  Deterministic: the
+ * cross-row sum has a fixed order (no float atomics). */
+int cldrd_distill_term(int kind, const float* logits, int B, int Np, const float* teacher, int Nt, float alpha, float T,
+                       float* loss_out, float* grad, float* term_out, void* stream);
+
 /* lambda_loss of losses/standard_lambda_rank.py:3-95 (allRank LambdaLoss framework): value + d loss / d y_pred in one call.
  * scheme: 0 None, 1 ndcgLoss1_scheme, 2 ndcgLoss2_scheme, 3 lambdaRank_scheme, 4 ndcgLoss2PP_scheme, 5 rankNet_scheme,
  * 6 rankNetWeightedByGTDiff_scheme, 7 rankNetWeightedByGTDiffPowed_scheme (:98-127); k <= 0: no truncation; gain_linear:
