@@ -85,6 +85,11 @@ SIGNATURES = {
     "cldrd_index_col_mean": (ci, [vp, csz, ci, vp, vp, csz, vp]),
     "cldrd_index_center_cast": (ci, [vp, vp, csz, ci, vp, vp, csz, csz, vp, vp, vp]),
     "cldrd_map_ids": (ci, [vp, vp, C.c_longlong, vp, csz, vp]),
+    "cldrd_query_dot64": (ci, [vp, vp, ci, vp, ci, vp]),
+    "cldrd_topk_rescore16": (ci, [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp]),
+    "cldrd_flatip_search16": (ci, [vp, vp, vp, vp, vp, vp, C.c_longlong, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp]),
+    "cldrd_gather_cast_rows16": (ci, [vp, vp, csz, csz, ci, vp]),
+    "cldrd_index_center_cast_chunk": (ci, [vp, vp, csz, csz, ci, vp, vp, csz, csz, vp, vp, vp]),
     "cldrd_unpack_rows16": (ci, [vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_gather_rows": (ci, [vp, vp, vp, ci, ci, vp]),
     "cldrd_gather_i64": (ci, [vp, vp, vp, ci, vp]),

@@ -10,7 +10,7 @@
 // lowers the threshold and rescans.
 //
 // Kernels here: per-query k-th largest of the sample scores (threshold estimate, radix select), fp32 re-score,
-// bitonic sort + cut, max row norm.
+// bitonic sort + cut, max row norm; and the fp16-row mode's re-score from the centred fp16 rows (an index without fp32 rows).
 #include "common.h"
 #ifndef CLDRD_SCAN_NT
 #define CLDRD_SCAN_NT 1
@@ -135,6 +135,66 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
     }
 }
 
+// fp16-row mode (an index that keeps mu and R16 = fp16(p - mu) and no fp32 rows): the stored row IS mu + R16[r], and its exact score is
+//   s(q, r) = fp32( <q, mu> + <q, R16[r]> ), both sums in fp64, ONE rounding.
+// qmu[q] = <q, mu> in fp64 comes from query_dot64_kernel (one wave per query, the lane-strided order of rescore_kernel); the row sum below is
+// rescore_kernel with the row read as V halves per lane and step (V = 8: one 16-byte non-temporal load, needs d % 8 == 0; V = 4: 8-byte loads).
+// A candidate row is d * 2 bytes: half of what the fp32 form gathers.
+__global__ __launch_bounds__(256) void query_dot64_kernel(const float* __restrict__ q, const float* __restrict__ mu, int d, double* __restrict__ out, int nq) {
+    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (qi >= nq) return;
+    const int lane = threadIdx.x & 63;
+    const float* qr = q + (size_t)qi * d;
+    double s = 0.0;
+    for (int j = lane * 4; j < d; j += 256) {
+        const float4 a = *(const float4*)(qr + j);
+        const float4 b = *(const float4*)(mu + j);
+        s = fma((double)a.x, (double)b.x, s); s = fma((double)a.y, (double)b.y, s);
+        s = fma((double)a.z, (double)b.z, s); s = fma((double)a.w, (double)b.w, s);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) out[qi] = s;
+}
+__device__ __forceinline__ double h2d(uint32_t bits16) { return (double)__builtin_bit_cast(_Float16, (uint16_t)bits16); }
+// s += <a, the four halves packed in (w0, w1)>, element order
+__device__ __forceinline__ double dot4_f16(const float4 a, uint32_t w0, uint32_t w1, double s) {
+    s = fma((double)a.x, h2d(w0 & 0xFFFFu), s); s = fma((double)a.y, h2d(w0 >> 16), s);
+    s = fma((double)a.z, h2d(w1 & 0xFFFFu), s); s = fma((double)a.w, h2d(w1 >> 16), s);
+    return s;
+}
+template <int V>
+__global__ __launch_bounds__(256) void rescore16_kernel(const float* __restrict__ q, const uint16_t* __restrict__ P16, const double* __restrict__ qmu,
+                                                         int d, const int* __restrict__ counts, const int* __restrict__ cand_rows,
+                                                         float* __restrict__ cand_scores, int cap) {
+    const int qi = blockIdx.y;
+    const int n = min(counts[qi], cap);
+    const int lane = threadIdx.x & 63;
+    const float* qr = q + (size_t)qi * d;
+    const double base = qmu[qi];
+    for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < n; c += gridDim.x * 4) {
+        const uint16_t* pr = P16 + (size_t)cand_rows[(size_t)qi * cap + c] * d;
+        double s = 0.0;
+        for (int j = lane * V; j < d; j += 64 * V) {
+            if constexpr (V == 8) {
+#if CLDRD_SCAN_NT
+                const uint4 bu = ld16_stream(pr + j);              // an index row is read once per pass: keep it out of the caches
+#else
+                const uint4 bu = *(const uint4*)(pr + j);
+#endif
+                s = dot4_f16(*(const float4*)(qr + j), bu.x, bu.y, s);
+                s = dot4_f16(*(const float4*)(qr + j + 4), bu.z, bu.w, s);
+            } else {
+                const uint2 bu = *(const uint2*)(pr + j);
+                s = dot4_f16(*(const float4*)(qr + j), bu.x, bu.y, s);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) cand_scores[(size_t)qi * cap + c] = (float)(base + s);
+    }
+}
+
 // per query: sort candidates by (score desc, row asc) in LDS, write the best k (missing: row -1, score -inf).
 // key = (~orderable(score)) << 32 | row, ascending.  NP = cap rounded up to a power of two (<= 8192).
 __global__ __launch_bounds__(1024) void topk_sort_kernel(const int* __restrict__ counts, const int* __restrict__ cand_rows,
@@ -210,6 +270,23 @@ __global__ __launch_bounds__(256) void gather_cast_rows_kernel(const float* __re
     }
 }
 
+// the same gather from fp16 rows (an index read from an fp16-row file has no fp32 rows): dst[i] = bf16(src16[i * stride])
+__global__ __launch_bounds__(256) void gather_cast_rows16_kernel(const uint16_t* __restrict__ src, bf16_t* __restrict__ dst, size_t n_out,
+                                                                  size_t stride, int d) {
+    const int lane = threadIdx.x & 63;
+    for (size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n_out; r += (size_t)gridDim.x * 4) {
+        const uint16_t* s = src + r * stride * d;
+        bf16_t* o = dst + r * d;
+        for (int j = lane * 4; j < d; j += 256) {
+            const uint2 a = *(const uint2*)(s + j);
+            const float f0 = (float)__builtin_bit_cast(_Float16, (uint16_t)(a.x & 0xFFFFu)), f1 = (float)__builtin_bit_cast(_Float16, (uint16_t)(a.x >> 16));
+            const float f2 = (float)__builtin_bit_cast(_Float16, (uint16_t)(a.y & 0xFFFFu)), f3 = (float)__builtin_bit_cast(_Float16, (uint16_t)(a.y >> 16));
+            uint2 u; u.x = pack2bf(f0, f1); u.y = pack2bf(f2, f3);
+            *(uint2*)(o + j) = u;
+        }
+    }
+}
+
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -275,8 +352,9 @@ __global__ __launch_bounds__(256) void index_mean_finish_kernel(const double* __
 }
 // 2. one pass: c = p - mu (fp32, as the scan's operand is defined), fp16 shadow of c, max_r |c_r|^2 (fp64 sum per row, the maximum as the
 //    bit pattern of its fp32 value: non-negative floats order like their bits), the bf16 threshold sample (row r = i * stride for
-//    i < s_rows), range flag.  One wave per row, 16-byte loads, 8-byte stores.
-__global__ __launch_bounds__(256) void index_center_cast_kernel(const float* __restrict__ P, const float* __restrict__ mu, size_t rows, int d,
+//    i < s_rows), range flag.  One wave per row, 16-byte loads, 8-byte stores.  row0: P / P16 point at row `row0` of the shard (a chunk of a
+//    chunked attach); the sample is indexed by the row's position in the whole shard.
+__global__ __launch_bounds__(256) void index_center_cast_kernel(const float* __restrict__ P, const float* __restrict__ mu, size_t rows, size_t row0, int d,
                                                                  uint16_t* __restrict__ P16, bf16_t* __restrict__ sample, size_t s_stride,
                                                                  size_t s_rows, unsigned int* __restrict__ cmax_bits, unsigned int* __restrict__ flag) {
     const int lane = threadIdx.x & 63;
@@ -285,8 +363,9 @@ __global__ __launch_bounds__(256) void index_center_cast_kernel(const float* __r
     for (size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (size_t)gridDim.x * 4) {
         const float* pr = P + r * d;
         uint16_t* o = P16 + r * d;
-        const bool in_sample = sample != nullptr && r % s_stride == 0 && r / s_stride < s_rows;
-        bf16_t* so = in_sample ? sample + (r / s_stride) * d : nullptr;
+        const size_t gr = row0 + r;
+        const bool in_sample = sample != nullptr && gr % s_stride == 0 && gr / s_stride < s_rows;
+        bf16_t* so = in_sample ? sample + (gr / s_stride) * d : nullptr;
         double s = 0.0;
         for (int j = lane * 4; j < d; j += 256) {
             const float4 a = *(const float4*)(pr + j);
@@ -758,6 +837,26 @@ extern "C" int cldrd_topk_rescore(const float* q, const float* P, int d, const i
     return 0;
 }
 
+// fp16-row mode: qmu[q] = <q, mu> in fp64 (device double [nq]); cand_scores = fp32(qmu[q] + <q, P16[row]>), sums in fp64, one rounding
+extern "C" int cldrd_query_dot64(const float* q, const float* mu, int d, double* out, int nq, void* stream) {
+    CLDRD_CHECK(nq > 0 && d > 0 && d % 4 == 0 && (uintptr_t)q % 16 == 0 && (uintptr_t)mu % 16 == 0, "query_dot64: bad arguments");
+    hipLaunchKernelGGL(query_dot64_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, mu, d, out, nq);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cldrd_topk_rescore16(const float* q, const void* P16, const double* qmu, int d, const int* counts, const int* cand_rows,
+                                    float* cand_scores, int nq, int cap, void* stream) {
+    CLDRD_CHECK(nq > 0 && d % 4 == 0 && cap > 0 && qmu != nullptr, "topk_rescore16: bad arguments");
+    CLDRD_CHECK((uintptr_t)q % 16 == 0 && (uintptr_t)P16 % (d % 8 == 0 ? 16 : 8) == 0, "topk_rescore16: aligned operands");
+    if (d % 8 == 0)
+        hipLaunchKernelGGL(rescore16_kernel<8>, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, (const uint16_t*)P16, qmu, d, counts, cand_rows, cand_scores, cap);
+    else
+        hipLaunchKernelGGL(rescore16_kernel<4>, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, (const uint16_t*)P16, qmu, d, counts, cand_rows, cand_scores, cap);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int cldrd_topk_sort(const int* counts, const int* cand_rows, const float* cand_scores, int nq, int cap, int k, float* D,
                                int* I, void* stream) {
     CLDRD_CHECK(nq > 0 && cap > 0 && cap <= 8192 && k > 0, "topk_sort: need 0 < cap <= 8192");
@@ -787,6 +886,14 @@ extern "C" int cldrd_gather_cast_rows(const float* src, void* dst, size_t n_out,
     CLDRD_CHECK(n_out > 0 && stride > 0 && d % 4 == 0, "gather_cast_rows: bad arguments");
     const int nb = (int)((n_out + 3) / 4 < 2048 ? (n_out + 3) / 4 : 2048);
     hipLaunchKernelGGL(gather_cast_rows_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n_out, stride, d);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cldrd_gather_cast_rows16(const void* src16, void* dst, size_t n_out, size_t stride, int d, void* stream) {
+    CLDRD_CHECK(n_out > 0 && stride > 0 && d % 4 == 0 && (uintptr_t)src16 % 8 == 0 && (uintptr_t)dst % 8 == 0, "gather_cast_rows16: bad arguments");
+    const int nb = (int)((n_out + 3) / 4 < 2048 ? (n_out + 3) / 4 : 2048);
+    hipLaunchKernelGGL(gather_cast_rows16_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src16, (bf16_t*)dst, n_out, stride, d);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
@@ -826,7 +933,21 @@ extern "C" int cldrd_index_center_cast(const float* P, const float* mu, size_t r
     CLDRD_CHECK(sample_bf16 == nullptr || s_stride > 0, "index_center_cast: sample stride");
     CLDRD_CHECK((uintptr_t)P % 16 == 0 && (uintptr_t)mu % 16 == 0 && (uintptr_t)P16 % 8 == 0, "index_center_cast: aligned operands");
     const int nb = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
-    hipLaunchKernelGGL(index_center_cast_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, P, mu, rows, d, (uint16_t*)P16, (bf16_t*)sample_bf16, s_stride,
+    hipLaunchKernelGGL(index_center_cast_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, P, mu, rows, (size_t)0, d, (uint16_t*)P16, (bf16_t*)sample_bf16, s_stride,
+                       s_rows, cmax_bits, flag);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+// One chunk of a chunked attach: P / P16 point at row `row0` of the shard and hold `rows` rows; `sample_bf16` is the WHOLE shard's sample
+// (row i = shard row i * s_stride, so a chunk writes the sample rows that fall inside it); *cmax_bits and *flag accumulate over the chunks
+// (zero them before the first one).
+extern "C" int cldrd_index_center_cast_chunk(const float* P, const float* mu, size_t rows, size_t row0, int d, void* P16, void* sample_bf16,
+                                             size_t s_stride, size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream) {
+    CLDRD_CHECK(rows > 0 && d > 0 && d % 4 == 0 && cmax_bits != nullptr, "index_center_cast_chunk: bad arguments");
+    CLDRD_CHECK(sample_bf16 == nullptr || s_stride > 0, "index_center_cast_chunk: sample stride");
+    CLDRD_CHECK((uintptr_t)P % 16 == 0 && (uintptr_t)mu % 16 == 0 && (uintptr_t)P16 % 8 == 0, "index_center_cast_chunk: aligned operands");
+    const int nb = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
+    hipLaunchKernelGGL(index_center_cast_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, P, mu, rows, row0, d, (uint16_t*)P16, (bf16_t*)sample_bf16, s_stride,
                        s_rows, cmax_bits, flag);
     CLDRD_LAUNCH_CHECK();
     return 0;
@@ -894,10 +1015,12 @@ extern "C" int cldrd_topk_scan_filter_tiled(const void* Q, const void* P, int nq
 // the global candidate lists - slower, but it has no on-chip hit list and so can never drop a hit (status bit 4): the retry form
 // for passes whose hit density overflowed the streaming scan's per-wave lists.  The caller reads `status` once at the end and
 // redoes the (rare) unproven queries with thresholds of its choice through this same entry point.
-extern "C" int cldrd_flatip_search(const float* q32, const void* qh, const float* thr, const float* eps, const void* Ph, const float* P32,
-                                   long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
-                                   int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
-                                   int exhaustive, void* stream) {
+// R16 != nullptr: fp16-row mode, the re-score reads the rows from R16 and adds qmu (cldrd_flatip_search16); else from P32.
+static int flatip_search_impl(const float* q32, const void* qh, const float* thr, const float* eps, const void* Ph, const float* P32,
+                              const void* R16, const double* qmu,
+                              long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
+                              int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
+                              int exhaustive, void* stream) {
     CLDRD_CHECK(nq > 0 && rows > 0 && k > 0 && cap > 0 && cap <= 8192 && cap2 > 0 && cap2 <= 8192 && d % 4 == 0, "flatip_search: bad arguments");
     CLDRD_CHECK(qtile == 128 || qtile == 256, "flatip_search: the query tile is 128 (the reference's batch) or 256 (two batches per pass over the index)");
     const int tiled = (exhaustive >> 1) & 1;
@@ -926,12 +1049,34 @@ extern "C" int cldrd_flatip_search(const float* q32, const void* qh, const float
         }
         rc = launch_select(cb, cb + m, cand_rows, cand_scores, m, cap, kk, thr + lo, eps + lo, rows2, cap2, n2 + lo, status + lo, khat + lo, exhaustive, st);
         if (rc) return rc;
-        rc = cldrd_topk_rescore(q32 + (size_t)lo * d, P32, d, n2 + lo, rows2, scores2, m, cap2, st);
+        if (R16) rc = cldrd_topk_rescore16(q32 + (size_t)lo * d, R16, qmu + lo, d, n2 + lo, rows2, scores2, m, cap2, st);
+        else rc = cldrd_topk_rescore(q32 + (size_t)lo * d, P32, d, n2 + lo, rows2, scores2, m, cap2, st);
         if (rc) return rc;
         rc = cldrd_topk_sort(n2 + lo, rows2, scores2, m, cap2, k, D + (size_t)lo * k, I + (size_t)lo * k, st);
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int cldrd_flatip_search(const float* q32, const void* qh, const float* thr, const float* eps, const void* Ph, const float* P32,
+                                   long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
+                                   int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
+                                   int exhaustive, void* stream) {
+    CLDRD_CHECK(P32 != nullptr, "flatip_search: no fp32 rows");
+    return flatip_search_impl(q32, qh, thr, eps, Ph, P32, nullptr, nullptr, rows, d, nq, k, qtile, counts, cand_rows, cand_scores, cap, rows2, scores2,
+                              cap2, n2, status, khat, D, I, exhaustive, stream);
+}
+
+// cldrd_flatip_search on an index in fp16-row mode: P16 = fp16(p - mu) is the scan's operand AND the stored row (no fp32 rows anywhere);
+// scores are fp32(qmu[q] + <q, P16[row]>) (cldrd_topk_rescore16), qmu from cldrd_query_dot64.  Scan, select, sort and the status bits are
+// those of cldrd_flatip_search; the scan's operand is now the exact stored row, so eps (both operands rounded) still bounds |scan - exact|.
+extern "C" int cldrd_flatip_search16(const float* q32, const void* qh, const float* thr, const float* eps, const void* P16, const double* qmu,
+                                     long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
+                                     int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
+                                     int exhaustive, void* stream) {
+    CLDRD_CHECK(P16 != nullptr && qmu != nullptr, "flatip_search16: need the fp16 rows and qmu");
+    return flatip_search_impl(q32, qh, thr, eps, P16, nullptr, P16, qmu, rows, d, nq, k, qtile, counts, cand_rows, cand_scores, cap, rows2, scores2,
+                              cap2, n2, status, khat, D, I, exhaustive, stream);
 }
 
 // Streaming form of cldrd_topk_scan_filter for d in {128, 256, 768} and nq <= 128 (returns -1 when it does not apply).

@@ -946,6 +946,52 @@ def flatip_search(q32, qh, thr, eps, P16, P32, k, counts, cand_rows, cand_scores
          (1 if exhaustive else 0) | (2 if tiled else 0), _stream())
 
 
+def flatip_search16(q32, qh, thr, eps, P16, qmu, k, counts, cand_rows, cand_scores, rows2, scores2, n2, status, khat, D, I, exhaustive=False,
+                    qtile=128, tiled=False):
+    """:func:`flatip_search` on an index in fp16-row mode (cldrd_flatip_search16): ``P16`` = fp16(p - mu) is the scan's operand and the row
+    the re-score reads, ``qmu`` = <q, mu> (fp64 [nq], :func:`query_dot64`)."""
+    _chk(q32, F32, "q32", 2), _chk(P16, F16, "P16", 2), _chk(qmu, torch.float64, "qmu", 1), _chk(thr, F32, "thr", 1), _chk(eps, F32, "eps", 1)
+    _chk(D, F32, "D", 2), _chk(I, torch.int32, "I", 2)
+    nq, d = q32.shape
+    rows = P16.shape[0]
+    if not exhaustive:
+        _chk(qh, F16, "qh", 2)
+    if P16.shape[1] != d or qmu.numel() < nq:
+        raise ValueError("flatip_search16: P16 must be [rows, d] and qmu [nq]")
+    if cand_rows.shape[0] < qtile or rows2.shape[0] < qtile:
+        raise ValueError("flatip_search16: the candidate buffers need qtile rows")
+    if counts.numel() < ((nq + qtile - 1) // qtile) * (qtile + 1) or n2.numel() < nq or status.numel() < nq or khat.numel() < nq or D.shape != (nq, k) or I.shape != (nq, k):
+        raise ValueError("flatip_search16: buffer sizes do not match nq / k")
+    if not (q32.is_contiguous() and P16.is_contiguous() and qmu.is_contiguous() and D.is_contiguous() and I.is_contiguous()):
+        raise ValueError("flatip_search16: operands must be contiguous")
+    call("cldrd_flatip_search16", _p(q32), _p(qh), _p(thr), _p(eps), _p(P16), _p(qmu), rows, d, nq, int(k), int(qtile), _p(counts), _p(cand_rows),
+         _p(cand_scores), cand_rows.shape[1], _p(rows2), _p(scores2), rows2.shape[1], _p(n2), _p(status), _p(khat), _p(D), _p(I),
+         (1 if exhaustive else 0) | (2 if tiled else 0), _stream())
+
+
+def query_dot64(q32, mu):
+    """<q, mu> per query in fp64 (fixed summation order) -> float64 [nq] on the device (cldrd_query_dot64)"""
+    _chk(q32, F32, "q32", 2), _chk(mu, F32, "mu", 1)
+    if not q32.is_contiguous() or mu.numel() != q32.shape[1]:
+        raise ValueError("query_dot64: contiguous q32 [nq, d] and mu [d]")
+    out = torch.empty(q32.shape[0], dtype=torch.float64, device=q32.device)
+    call("cldrd_query_dot64", _p(q32), _p(mu), q32.shape[1], _p(out), q32.shape[0], _stream())
+    return out
+
+
+def topk_rescore16(q32, P16, qmu, counts, cand_rows, cand_scores):
+    """cand_scores[q, c] = fp32(qmu[q] + <q32[q], P16[cand_rows[q, c]]>) for c < counts[q], sums in fp64 (cldrd_topk_rescore16)"""
+    _chk(q32, F32, "q32", 2), _chk(P16, F16, "P16", 2), _chk(qmu, torch.float64, "qmu", 1)
+    _chk(counts, torch.int32, "counts", 1), _chk(cand_rows, torch.int32, "cand_rows", 2), _chk(cand_scores, F32, "cand_scores", 2)
+    if not (q32.is_contiguous() and P16.is_contiguous() and cand_rows.is_contiguous() and cand_scores.is_contiguous()):
+        raise ValueError("topk_rescore16: operands must be contiguous")
+    if P16.shape[1] != q32.shape[1] or qmu.numel() < q32.shape[0] or counts.numel() < q32.shape[0] or cand_rows.shape != cand_scores.shape \
+            or cand_rows.shape[0] < q32.shape[0]:
+        raise ValueError("topk_rescore16: shape mismatch")
+    call("cldrd_topk_rescore16", _p(q32), _p(P16), _p(qmu), q32.shape[1], _p(counts), _p(cand_rows), _p(cand_scores), q32.shape[0],
+         cand_rows.shape[1], _stream())
+
+
 def topk_kth_largest(scores, S, kth, thr):
     _chk(scores, F32, "scores", 2), _chk(thr, F32, "thr", 1)
     call("cldrd_topk_kth_largest", _p(scores), scores.stride(0), scores.shape[0], S, int(kth), _p(thr), _stream())
@@ -970,9 +1016,41 @@ def row_sqnorm_max(P32) -> float:
     return float(out.view(torch.float32).item())
 
 
+def row_sqnorm_max_into(P32, out):
+    """``*out`` (int32 [1] on the device, zeroed by the caller) = max(*out, bit pattern of max_r |P32[r]|^2): the chunk-by-chunk form of
+    :func:`row_sqnorm_max`, no host synchronisation"""
+    _chk(P32, F32, "P32", 2), _chk(out, torch.int32, "out", 1)
+    if not P32.is_contiguous():
+        raise ValueError("row_sqnorm_max_into: P32 must be contiguous")
+    call("cldrd_row_sqnorm_max", _p(P32), P32.shape[0], P32.shape[1], _p(out), _stream())
+
+
 def gather_cast_rows(src32, dst_bf16, n_out, stride):
     _chk(src32, F32, "src32", 2), _chk(dst_bf16, BF16, "dst_bf16", 2)
     call("cldrd_gather_cast_rows", _p(src32), _p(dst_bf16), n_out, stride, src32.shape[1], _stream())
+
+
+def gather_cast_rows16(src16, dst_bf16, n_out, stride):
+    """dst[i] = bf16(src16[i * stride]) for i < n_out (cldrd_gather_cast_rows16)"""
+    _chk(src16, F16, "src16", 2), _chk(dst_bf16, BF16, "dst_bf16", 2)
+    if not (src16.is_contiguous() and dst_bf16.is_contiguous()) or dst_bf16.shape[1] != src16.shape[1] or n_out > dst_bf16.shape[0] \
+            or (n_out - 1) * stride >= src16.shape[0]:
+        raise ValueError("gather_cast_rows16: shape mismatch")
+    call("cldrd_gather_cast_rows16", _p(src16), _p(dst_bf16), n_out, stride, src16.shape[1], _stream())
+
+
+def index_center_cast_chunk(P32, mu, row0, P16, sample_bf16, s_stride, s_rows, cmax, flag):
+    """:func:`index_center_cast` for rows [row0, row0 + len(P32)) of a shard attached chunk by chunk: ``P16`` is that slice of the shard's
+    fp16 rows, ``sample_bf16`` the whole shard's sample; ``cmax`` (int32 [1], zeroed before the first chunk) and ``flag`` accumulate."""
+    _chk(P32, F32, "P32", 2), _chk(mu, F32, "mu", 1), _chk(P16, F16, "P16", 2), _chk(cmax, torch.int32, "cmax", 1)
+    if sample_bf16 is not None:
+        _chk(sample_bf16, BF16, "sample_bf16", 2)
+        if int(s_rows) > sample_bf16.shape[0] or sample_bf16.shape[1] != P32.shape[1] or not sample_bf16.is_contiguous():
+            raise ValueError("index_center_cast_chunk: the sample needs s_rows rows of width d")
+    if P16.shape != P32.shape or mu.numel() != P32.shape[1] or not (P32.is_contiguous() and P16.is_contiguous()):
+        raise ValueError("index_center_cast_chunk: P16 must be the contiguous [rows, d] slice that matches P32")
+    call("cldrd_index_center_cast_chunk", _p(P32), _p(mu), P32.shape[0], int(row0), P32.shape[1], _p(P16), _p(sample_bf16), int(s_stride), int(s_rows),
+         _p(cmax), _p(flag), _stream())
 
 
 def index_col_mean(P32):

@@ -1,7 +1,8 @@
 """``retriever/index_text.py`` of the reference (:30-109) on MI355X: load a checkpoint (``module.`` prefix stripped), encode
 the collection with the passage tower, build the flat inner-product index with ids, write it plus ``meta.pkl``.
 
-Same flags; extra: ``--synthetic_rows N`` (encode N synthetic MSMARCO-shaped passages instead of ``--passages_path``) and
+Same flags; extra: ``--synthetic_rows N`` (encode N synthetic MSMARCO-shaped passages instead of ``--passages_path``), ``--index_fp16``
+(write the fp16-row index format, ``retrieval_utils.FlatIPIndex.write``) and
 ``--rank/--world`` style sharding through torch.distributed env vars: rank r encodes and stores the contiguous shard r
 (independent units, no collective)."""
 from __future__ import annotations
@@ -35,6 +36,7 @@ _FLAGS = {
     "token_cache_dir": dict(default=""),                  # ours: tokenise the collection once (dataset.SequenceTokenCache), memory-map it afterwards
     "token_cache_stem": dict(default=""),                 # ours: memory-map an EXISTING token cache by its file stem (no collection / tokenizer opened)
     "loader_workers": dict(type=int, default=2),          # ours: DataLoader workers of the token-cache path
+    "index_fp16": dict(action="store_true", default=False),      # ours: write the fp16-row index format (mean row + centred fp16 rows: half the file)
     "bucket_window": dict(type=int, default=16384),       # ours (token-cache path): rows are batched by LENGTH inside windows of this many rows (0: 512 consecutive rows)
 }
 
@@ -122,7 +124,10 @@ def main(args):
     lap("index_build_s")
     stem = Path(args.resume).stem.split(".")[0] if args.resume else "random_init"
     index_path = os.path.join(args.index_dir, stem + (f".shard{rank}of{world}" if world > 1 else "") + ".index")
-    write_index(index, index_path)
+    if getattr(args, "index_fp16", False):
+        write_index(index, index_path, fp16=True)        # the encode loop delivered fp32 rows; they are centred and cast at write time
+    else:
+        write_index(index, index_path)
     lap("index_write_s")
     with open(os.path.join(args.index_dir, "meta.pkl" if world == 1 else f"meta.shard{rank}.pkl"), "wb") as f:
         pickle.dump({"text_ids": np.array(text_ids), "text_id_to_idx": text_id_to_idx}, f)

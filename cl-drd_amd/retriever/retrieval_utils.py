@@ -13,7 +13,8 @@ missing results id -1) whose ``search`` runs on the GPU, device resident from th
     3. select              : t^_q = k-th largest scan score; only rows with scan score >= t^_q - 2 eps_q can be in the exact
                              top-k, where eps_q >= |scan score - exact score| bounds the fp16 rounding of both operands
                              (2^-10 |q| max|p|), the fp32 accumulation and fp16 underflow (csrc/topk.hip: thresholds_kernel)
-    4. exact re-score      : fp32 dot products of those rows from the fp32 rows (what faiss would have computed)
+    4. exact re-score      : fp32 dot products of those rows from the fp32 rows (what faiss would have computed); in fp16-row mode
+                             (``useFloat16=True``, :class:`FlatIPIndex`) from the stored fp16 rows - there are no fp32 rows then
     5. sort + cut          : (score desc, row position asc) -> top-k
     6. proof of exactness  : per query ON THE DEVICE: the list is complete down to t^_q - 2 eps_q (thr_q <= that, >= k candidates,
                              no overflow, no dropped hit).  The host reads the flags once per search; a query that fails is
@@ -46,6 +47,10 @@ QUERY_TILE = 128             # the reference searches in batches of 128 (retriev
                              # share one pass over the index (FlatIPIndex.query_tile = 256: the index bytes are read once per 256 queries)
 EST_CHUNK = 1024             # queries per threshold-estimate GEMM
 MAX_ATTEMPTS = 12
+ATTACH_CHUNK_ROWS = 65536    # fp16-row mode: fp32 rows reach the GPU in chunks of this many rows (two staging buffers), never as a whole
+HOST_CHUNK_ROWS = 16384      # fp16-row file written from a host index: rows converted per numpy step
+FORMAT_F32 = "cldrd-flatip-v1"
+FORMAT_F16 = "cldrd-flatip-f16-v1"
 PROGRESS_HOOK = None         # tools: callable(timings dict) every 500 batches of get_embeddings_from_scratch
 
 
@@ -173,7 +178,20 @@ def get_embeddings_from_scratch(model, dataloader, use_fp16, is_query, show_prog
 
 
 class FlatIPIndex:
-    """Exact inner-product index over one shard of rows (faiss ``IndexIDMap(IndexFlatIP(d))`` semantics)."""
+    """Exact inner-product index over one shard of rows (faiss ``IndexIDMap(IndexFlatIP(d))`` semantics).
+
+    Two row modes.  Default (``row_dtype == "float32"``): the fp32 rows are resident next to the fp16 scan shadow and scores are exact fp32
+    inner products (6 B per element in HBM).  **fp16-row mode** (``to_gpu(dev, fp16_rows=True)``, ``convert_index_to_gpu(..., useFloat16=True)``,
+    or an index read from an fp16-row file; ``row_dtype == "float16"``): the shard keeps ``mu`` (fp32 [d], its mean row) and
+    ``R16 = fp16(p - mu)`` (round to nearest even) and nothing else of the rows - 2 B per element.  The stored row is ``mu + R16[r]`` and
+
+        s(q, r) = fp32( sum_j q_j mu_j + sum_j q_j R16[r, j] )          both sums in fp64, one rounding
+
+    i.e. the exact inner product with the stored row; ``search`` returns the top-k of s by (s desc, row position asc), everything else of the
+    contract is unchanged.  This differs from faiss' ``useFloat16``, which stores plain ``fp16(p)``: the centred array is the one the scan
+    reads anyway (one array serves scan and re-score), and its rounding error is relative to ``|p - mu|`` instead of ``|p|`` - on CLS-like
+    embeddings the stored rows are closer to the fp32 ones.  ``mu`` is the fp32 value of the fp64 column mean; a host-written file and a
+    device-attached index of the same rows may differ in the last bit of ``mu`` and therefore of a few ``R16`` values."""
 
     def __init__(self, d: int):
         self.d = d
@@ -183,13 +201,36 @@ class FlatIPIndex:
         self.id_offset = 0
         self.device = None
         self._p32 = self._p16 = self._sample = None
+        self._mu = None               # device fp32 [d]: mean row of the attached shard
+        self._fp16_rows = False       # attached in fp16-row mode (no fp32 rows in HBM)
+        self._r16_host = None         # np.float16 [n, d] = fp16(p - mu): an index read from an fp16-row file (no fp32 rows anywhere)
+        self._mu_host = None          # np.float32 [d] of such an index
+        self._cnorm = self._raw_max = None      # max |p - mu|, max |p| of the attached shard / the file
         self.last_stats = {}
         self.profile = False          # bench.py: time the search with HIP events and count candidates
         self.probe = True             # first pass of a long search sizes the kept-set buffer of the rest (test hook: False)
         self.query_tile_request = None
 
+    @property
+    def row_dtype(self) -> str:
+        """``"float16"``: fp16-row mode (attached with ``fp16_rows=True`` or read from an fp16-row file); ``"float32"`` otherwise."""
+        return "float16" if (self._fp16_rows or self._r16_host is not None) else "float32"
+
+    @property
+    def mu(self):
+        """The shard's mean row the fp16 rows are centred on: np.float32 [d], read-only (None before the index has one)."""
+        if self._mu_host is None and self._mu is not None:
+            self._mu_host = self._mu.cpu().numpy()
+        if self._mu_host is None:
+            return None
+        out = self._mu_host.view()
+        out.flags.writeable = False
+        return out
+
     # -- construction -----------------------------------------------------------------------------------------
     def add_with_ids(self, embeddings, ids):
+        if self._r16_host is not None:
+            raise ValueError("an index read from an fp16-row file holds no fp32 rows: rows cannot be added to it")
         emb = np.ascontiguousarray(embeddings, dtype=np.float32)
         if emb.ndim != 2 or emb.shape[1] != self.d:
             raise ValueError("embeddings must be [n, d]")
@@ -203,24 +244,44 @@ class FlatIPIndex:
             self.ids = None if self.ids is None or ids is None else np.concatenate([self.ids, ids])
         self.ntotal = self.embeddings.shape[0]
         self._p32 = self._p16 = self._sample = self._ids_dev = None
+        self._mu = self._mu_host = None
+        self._fp16_rows = False
         self._ws = None
 
     def add(self, embeddings):
         self.add_with_ids(embeddings, None)
 
     @classmethod
-    def from_device_rows(cls, rows32: torch.Tensor, id_offset: int = 0) -> "FlatIPIndex":
-        """Index over fp32 rows that already live in HBM (e.g. an encode shard that never left the GPU)."""
+    def from_device_rows(cls, rows32: torch.Tensor, id_offset: int = 0, fp16_rows: bool = False) -> "FlatIPIndex":
+        """Index over fp32 rows that already live in HBM (e.g. an encode shard that never left the GPU).  ``fp16_rows``: centre + cast on the
+        device and keep no reference to ``rows32`` (fp16-row mode, class docstring)."""
         idx = cls(rows32.shape[1])
         idx.ntotal, idx.id_offset = rows32.shape[0], id_offset
+        if fp16_rows:
+            rows32 = rows32.contiguous()
+            n = rows32.shape[0]
+            idx._attach16(rows32.device, n, lambda: ((lo, rows32[lo:min(n, lo + ATTACH_CHUNK_ROWS)]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
+            return idx
         idx._attach(rows32.contiguous())
         return idx
 
-    def to_gpu(self, device):
-        """Make the shard resident in HBM: fp32 rows (exact re-score), fp16 shadow (scan), bf16 row sample (threshold)."""
+    def to_gpu(self, device, fp16_rows: bool = False):
+        """Make the shard resident in HBM.  Default: fp32 rows (exact re-score), fp16 shadow (scan), bf16 row sample (threshold).
+        ``fp16_rows=True`` (or an index read from an fp16-row file, whatever the argument says): fp16-row mode - only ``mu``, the centred fp16
+        rows and the sample become resident; the fp32 rows pass through two staging buffers of ``ATTACH_CHUNK_ROWS`` rows."""
         device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("FlatIPIndex.search runs on the GPU only (no CPU path)")
+        if self._r16_host is not None:
+            with torch.cuda.device(device):
+                self._attach16_file(device)
+            return self
+        if fp16_rows:
+            if self.embeddings is None:
+                raise ValueError("FlatIPIndex.to_gpu: the index holds no rows")
+            with torch.cuda.device(device):
+                self._attach16(device, self.embeddings.shape[0], lambda: self._staged_chunks(device))
+            return self
         with torch.cuda.device(device):
             import warnings
             with warnings.catch_warnings():
@@ -230,10 +291,127 @@ class FlatIPIndex:
             self._attach(host.to(device))
         return self
 
+    def _staged_chunks(self, device):
+        """(first row, fp32 device tensor) for every ``ATTACH_CHUNK_ROWS`` rows of the host array (a numpy array or a memory-mapped file), through
+        two staging buffers: the H2D copy of chunk i + 1 (a side stream) runs under the kernels the consumer enqueued for chunk i."""
+        import warnings
+        emb = self.embeddings
+        n, d = emb.shape
+        m_max = min(n, ATTACH_CHUNK_ROWS)
+        cur, side = torch.cuda.current_stream(device), torch.cuda.Stream(device)
+        bufs = [torch.empty(m_max, d, dtype=torch.float32, device=device) for _ in range(2 if n > m_max else 1)]
+        consumed = [None] * len(bufs)
+        side.wait_stream(cur)
+        try:
+            for i, lo in enumerate(range(0, n, ATTACH_CHUNK_ROWS)):
+                hi = min(n, lo + ATTACH_CHUNK_ROWS)
+                b = i % len(bufs)
+                with warnings.catch_warnings():
+                    warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+                    host = torch.from_numpy(np.ascontiguousarray(emb[lo:hi], dtype=np.float32))
+                with torch.cuda.stream(side):
+                    if consumed[b] is not None:
+                        side.wait_event(consumed[b])
+                    bufs[b][:hi - lo].copy_(host, non_blocking=True)
+                    ready = torch.cuda.Event()
+                    ready.record(side)
+                cur.wait_event(ready)
+                yield lo, bufs[b][:hi - lo]
+                consumed[b] = torch.cuda.Event()
+                consumed[b].record(cur)
+        finally:
+            cur.wait_stream(side)
+            cur.synchronize()            # the staging buffers go back to the allocator only when nothing reads or writes them
+
+    def _plan_sample(self, n: int, d: int, device):
+        """the threshold sample of :meth:`_attach` (sizes explained there)"""
+        self._s_stride = max(1, n // min(max(SAMPLE_ROWS, n // 64), 1 << 18))
+        self._s_rows = min(n, (n + self._s_stride - 1) // self._s_stride)
+        self._sample = torch.zeros((self._s_rows + 7) // 8 * 8, d, dtype=torch.bfloat16, device=device)
+
+    def _attach16(self, device, n: int, chunks):
+        """fp16-row attach.  ``chunks()`` yields (first row, fp32 device tensor) over the shard in order; it is walked twice:
+        pass 1 - max |p|^2 and the mean row of every chunk (cldrd_row_sqnorm_max, cldrd_index_col_mean), the chunk means combined on the host in
+        fp64 weighted by chunk size (mu depends neither on the device nor on timing; it need not equal the fp32 mode's mu bit for bit);
+        pass 2 - centre + cast every chunk into its slice of P16 and of the sample, max centred norm and range flag accumulated
+        (cldrd_index_center_cast_chunk).  No fp32 row stays in HBM."""
+        d = self.d
+        if d % 4:
+            raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
+        if d > 2048:
+            raise ValueError(f"FlatIPIndex: fp16-row mode supports an embedding width of at most 2048 (the mean-row kernel's limit), got {d}")
+        if n <= 0:
+            raise ValueError("FlatIPIndex: no rows to attach")
+        self.device = device
+        self._ws = None
+        self._p32 = None
+        with torch.cuda.device(device):
+            raw = torch.zeros(1, dtype=torch.int32, device=device)
+            means, sizes = [], []
+            for lo, c in chunks():
+                ops.row_sqnorm_max_into(c, raw)
+                means.append(ops.index_col_mean(c))
+                sizes.append(c.shape[0])
+            del c                        # the last view of a staging buffer: pass 2 allocates its own
+            raw_max = math.sqrt(float(raw.view(torch.float32).item()))
+            if math.isfinite(raw_max):
+                w = np.asarray(sizes, dtype=np.float64)[:, None]
+                mu_h = ((torch.stack(means).cpu().numpy().astype(np.float64) * w).sum(axis=0) / float(n)).astype(np.float32)
+            else:
+                mu_h = np.zeros(d, dtype=np.float32)
+            del means
+            mu = torch.from_numpy(mu_h).to(device)
+            flag = torch.zeros(1, dtype=torch.int32, device=device)
+            cmax = torch.zeros(1, dtype=torch.int32, device=device)
+            self._p16 = torch.empty(n, d, dtype=torch.float16, device=device)
+            self._plan_sample(n, d, device)
+            for lo, c in chunks():
+                ops.index_center_cast_chunk(c, mu, lo, self._p16[lo:lo + c.shape[0]], self._sample, self._s_stride, self._s_rows, cmax, flag)
+            del c
+            self._mu, self._mu_host = mu, mu_h
+            self._cnorm, self._raw_max = math.sqrt(float(cmax.view(torch.float32).item())), raw_max
+            self._finish_attach16(int(flag.item()))
+
+    def _attach16_file(self, device):
+        """An index read from an fp16-row file: the fp16 rows go to HBM as they are (chunked H2D straight into P16), the sample is gathered on
+        the device, the norms come from the file - no statistics pass."""
+        import warnings
+        r16 = self._r16_host
+        n, d = r16.shape
+        if d % 4:
+            raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
+        self.device = device
+        self._ws = None
+        self._p32 = None
+        with torch.cuda.device(device):
+            self._p16 = torch.empty(n, d, dtype=torch.float16, device=device)
+            for lo in range(0, n, ATTACH_CHUNK_ROWS):
+                hi = min(n, lo + ATTACH_CHUNK_ROWS)
+                with warnings.catch_warnings():
+                    warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+                    self._p16[lo:hi].copy_(torch.from_numpy(np.ascontiguousarray(r16[lo:hi])))
+            self._plan_sample(n, d, device)
+            ops.gather_cast_rows16(self._p16, self._sample, self._s_rows, self._s_stride)
+            self._mu = torch.from_numpy(np.ascontiguousarray(self._mu_host, dtype=np.float32)).to(device)
+            self._finish_attach16(0)
+
+    def _finish_attach16(self, flag: int):
+        d = self.d
+        self._fp16_rows = True
+        # the bound of _attach: max |p - mu| plus 2^-12 max|p| for the rounding of the fp32 subtraction.  The scan's operand now IS the stored
+        # row, so the second term is slack here; the bound is kept as it is (cldrd_topk_thresholds unchanged)
+        self._max_norm = self._cnorm * (1.0 + 1e-6) + self._raw_max * 2.0 ** -12
+        self.query_tile = 256 if (d == 768 and self.query_tile_request != 128) else 128
+        if flag or not math.isfinite(self._max_norm):
+            self._p16 = self._sample = None
+            raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
+
     def _attach(self, p32: torch.Tensor):
         device = p32.device
         self.device = device
         self._ws = None
+        self._fp16_rows = False
+        self._mu_host = None
         with torch.cuda.device(device):
             self._p32 = p32
             n, d = self._p32.shape
@@ -263,7 +441,8 @@ class FlatIPIndex:
             cmax = ops.index_center_cast(self._p32, mu, self._p16, self._sample, self._s_stride, self._s_rows, flag)
             # max |p - mu| for the bound, plus 2^-12 max|p|: the fp32 subtraction p - mu itself rounds (2^-24 |p| per element), which moves a
             # centred score by up to |q| sqrt(d) 2^-24 max|p| < 2^-10 |q| (2^-12 max|p|) - folded into the norm the eps formula multiplies by 2^-10
-            self._max_norm = math.sqrt(float(cmax.view(torch.float32).item())) * (1.0 + 1e-6) + raw_max * 2.0 ** -12
+            self._cnorm, self._raw_max = math.sqrt(float(cmax.view(torch.float32).item())), raw_max
+            self._max_norm = self._cnorm * (1.0 + 1e-6) + raw_max * 2.0 ** -12
             # queries per pass over the index bytes: 256 at d = 768 (the streaming scan's two-batch form), else the reference's 128
             # (`query_tile_request`: a test hook that asks for 128 at d = 768)
             self.query_tile = 256 if (d == 768 and self.query_tile_request != 128) else 128
@@ -281,7 +460,7 @@ class FlatIPIndex:
 
     def search(self, queries, k: int):
         """(D np.float32 [nq, k] descending, I np.int64 [nq, k]); missing results: id -1, score -inf."""
-        if self._p32 is None:
+        if self._p16 is None:
             raise RuntimeError("index is not on a GPU: call convert_index_to_gpu(index, device) first (no CPU search path)")
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.d:
@@ -312,7 +491,7 @@ class FlatIPIndex:
         """Search with device-resident fp32 queries [nq, d]; returns device tensors (D fp32 [nq, k], I int32 row positions
         [nq, k], -1 = missing) and the statistics dict.  ONE host synchronisation (the proof flags) when nothing is redone."""
         dev = self.device
-        n, d = self._p32.shape
+        n, d = self._p16.shape
         nq = q32.shape[0]
         kk = min(k, n)
         exhaustive = n <= CAND_CAP
@@ -325,6 +504,7 @@ class FlatIPIndex:
         qb = torch.empty(nq, d, dtype=torch.bfloat16, device=dev)
         qnorm, flag = torch.empty(nq, **f32), torch.zeros(1, **i32)
         ops.topk_prep_queries(q32, qh, qb, qnorm, flag)
+        qmu = ops.query_dot64(q32, self._mu) if self._fp16_rows else None        # fp16-row mode: <q, mu> in fp64, added by the re-score
         thr, eps = torch.full((nq,), -float("inf"), **f32), torch.empty(nq, **f32)
         stats = dict(scans=0, rescans=0, candidates=0, rescored=0, unproven_first_pass=0, exhaustive=bool(exhaustive))
         if exhaustive:
@@ -356,7 +536,8 @@ class FlatIPIndex:
         # overflowing it query after query and scanning those a second time.
         probe = 0 if (exhaustive or nq <= 2 * QT or not self.probe) else QT
         if probe:
-            st_p, cnt_p, n2_p, kh_p = self._run(q32[:probe], qh[:probe], thr[:probe], eps[:probe], k, self._workspace(cap2), D[:probe], I[:probe], False)
+            st_p, cnt_p, n2_p, kh_p = self._run(q32[:probe], qh[:probe], thr[:probe], eps[:probe], k, self._workspace(cap2), D[:probe], I[:probe], False,
+                                             qmu=None if qmu is None else qmu[:probe])
             pr = torch.stack([st_p, n2_p]).cpu().numpy()
             ok = (pr[0] & 16) == 0
             need = int(pr[1].max()) if ok.all() else CAND_CAP
@@ -365,12 +546,13 @@ class FlatIPIndex:
                 cap2_rest *= 2
             cap2_rest = min(cap2_rest, CAND_CAP)
             stats["cap2"] = [cap2, cap2_rest]
-            st_r, cnt_r, n2_r, kh_r = self._run(q32[probe:], qh[probe:], thr[probe:], eps[probe:], k, self._workspace(cap2_rest), D[probe:], I[probe:], False)
+            st_r, cnt_r, n2_r, kh_r = self._run(q32[probe:], qh[probe:], thr[probe:], eps[probe:], k, self._workspace(cap2_rest), D[probe:], I[probe:], False,
+                                             qmu=None if qmu is None else qmu[probe:])
             st, n2, khat = torch.cat([st_p, st_r]), torch.cat([n2_p, n2_r]), torch.cat([kh_p, kh_r])
             counts = torch.cat([cnt_p, cnt_r])
             cap2 = cap2_rest
         else:
-            st, counts, n2, khat = self._run(q32, qh, thr, eps, k, self._workspace(cap2), D, I, exhaustive)
+            st, counts, n2, khat = self._run(q32, qh, thr, eps, k, self._workspace(cap2), D, I, exhaustive, qmu=qmu)
         if self.profile:
             e1.record()
         status = st.cpu().numpy()                       # the synchronisation of a search (plus the probe's)
@@ -435,7 +617,8 @@ class FlatIPIndex:
             thr_b = torch.from_numpy(t_b.astype(np.float32)).to(dev)
             eps_b = eps.index_select(0, idx)
             Db, Ib = torch.empty(bad.size, k, **f32), torch.empty(bad.size, k, **i32)
-            st2, _, _, khat2 = self._run(qb32, qbh, thr_b, eps_b, k, self._workspace(cap2_b), Db, Ib, False, tiled=tiled)
+            st2, _, _, khat2 = self._run(qb32, qbh, thr_b, eps_b, k, self._workspace(cap2_b), Db, Ib, False, tiled=tiled,
+                                             qmu=None if qmu is None else qmu.index_select(0, idx))
             status_b = st2.cpu().numpy()
             good = status_b == 0
             if good.any():
@@ -459,9 +642,11 @@ class FlatIPIndex:
     def _search_exhaustive_chunks(self, q32: torch.Tensor, k: int):
         """Exact top-k of a few queries with EVERY row re-scored in fp32, CAND_CAP rows at a time (the exhaustive form of
         cldrd_flatip_search on row slices), the running top-k merged with each chunk's by the same sort kernel (score desc, row position
-        asc).  The last resort of :meth:`search_device`: reads the fp32 rows once per 128/256 queries, needs no threshold, cannot fail."""
+        asc).  The last resort of :meth:`search_device`: reads the fp32 rows once per 128/256 queries, needs no threshold, cannot fail.
+        fp16-row mode: the same over slices of the fp16 rows (cldrd_flatip_search16, scores as the class docstring defines them)."""
         dev = self.device
-        n, d = self._p32.shape
+        n, d = self._p16.shape
+        qmu = ops.query_dot64(q32.contiguous(), self._mu) if self._fp16_rows else None
         nq = q32.shape[0]
         if 2 * k > CAND_CAP:
             raise ValueError(f"exact fallback: top_k = {k} > {CAND_CAP // 2}")
@@ -479,8 +664,12 @@ class FlatIPIndex:
             nb = (nq + QT - 1) // QT
             counts = torch.zeros(nb * (QT + 1), **i32)
             n2, st, khat = torch.empty(nq, **i32), torch.empty(nq, **i32), torch.empty(nq, **f32)
-            ops.flatip_search(q32, None, thr, eps, None, self._p32[lo:hi], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
-                              n2, st, khat, Dc, Ic, exhaustive=True, qtile=QT)
+            if qmu is not None:
+                ops.flatip_search16(q32, None, thr, eps, self._p16[lo:hi], qmu, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"],
+                                    ws["scores2"], n2, st, khat, Dc, Ic, exhaustive=True, qtile=QT)
+            else:
+                ops.flatip_search(q32, None, thr, eps, None, self._p32[lo:hi], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
+                                  n2, st, khat, Dc, Ic, exhaustive=True, qtile=QT)
             Ic = torch.where(Ic >= 0, Ic + lo, Ic)
             rows = torch.cat([I, Ic], dim=1).contiguous()
             scores = torch.cat([D, Dc], dim=1).contiguous()
@@ -502,7 +691,7 @@ class FlatIPIndex:
                            scores2=torch.empty(QT, cap2, dtype=torch.float32, device=dev))
         return ws[key]
 
-    def _run(self, q32, qh, thr, eps, k, ws, D, I, exhaustive, tiled=False):
+    def _run(self, q32, qh, thr, eps, k, ws, D, I, exhaustive, tiled=False, qmu=None):
         dev = self.device
         nq, QT = q32.shape[0], self.query_tile
         nb = (nq + QT - 1) // QT
@@ -510,32 +699,95 @@ class FlatIPIndex:
         n2 = torch.empty(nq, dtype=torch.int32, device=dev)
         status = torch.empty(nq, dtype=torch.int32, device=dev)
         khat = torch.empty(nq, dtype=torch.float32, device=dev)
+        if qmu is not None:
+            ops.flatip_search16(q32, qh, thr, eps, self._p16, qmu, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
+                                n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled)
+            return status, counts, n2, khat
         ops.flatip_search(q32, qh, thr, eps, self._p16, self._p32, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
                           n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled)
         return status, counts, n2, khat
 
     # -- persistence (own format; faiss' binary layout is not reproduced) ----------------
-    def write(self, path: str):
+    def write(self, path: str, fp16: bool = False):
+        """``path.emb.npy`` (fp32 rows) + ``path.meta.pkl``; ``fp16=True``: the fp16-row format - ``path.emb16.npy`` (``R16 = fp16(p - mu)``,
+        numpy float16, memory-mappable) and ``mu``, ``max_centred_norm``, ``raw_max_norm`` next to ``d / ids / id_offset`` in the meta file.  An
+        index that is on a GPU writes the ``mu`` / ``R16`` it searches with; a host index computes them with numpy in chunks (same definition:
+        ``mu`` = fp32 of the fp64 column mean - the last bit of ``mu``, and with it a few ``R16`` values, may differ between the two)."""
+        if fp16:
+            return self._write16(path)
+        if self.embeddings is None:
+            raise ValueError("this index holds fp16 rows only (read from an fp16-row file): write it with fp16=True")
         np.save(path + ".emb.npy", self.embeddings)
         with open(path + ".meta.pkl", "wb") as fh:
-            pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": "cldrd-flatip-v1"}, fh)
+            pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F32}, fh)
+
+    def _write16(self, path: str):
+        if self._p16 is not None:
+            # attached (either mode): the device's centred fp16 rows and statistics
+            r16, mu, cnorm, raw = self._p16.cpu().numpy(), np.array(self.mu), self._cnorm, self._raw_max
+            np.save(path + ".emb16.npy", r16)
+        elif self._r16_host is not None:
+            mu, cnorm, raw = np.array(self._mu_host), self._cnorm, self._raw_max
+            np.save(path + ".emb16.npy", self._r16_host)
+        else:
+            emb = self.embeddings
+            if emb is None or emb.shape[0] == 0:
+                raise ValueError("FlatIPIndex.write: the index holds no rows")
+            n, d = emb.shape
+            colsum, raw_sq = np.zeros(d, dtype=np.float64), 0.0
+            for lo in range(0, n, HOST_CHUNK_ROWS):
+                c = np.asarray(emb[lo:lo + HOST_CHUNK_ROWS], dtype=np.float32)
+                colsum += c.sum(axis=0, dtype=np.float64)
+                raw_sq = max(raw_sq, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max()))
+            if not (math.isfinite(raw_sq) and np.isfinite(colsum).all()):
+                raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
+            mu = (colsum / float(n)).astype(np.float32)
+            out = np.lib.format.open_memmap(path + ".emb16.npy", mode="w+", dtype=np.float16, shape=(n, d))
+            c_sq = 0.0
+            for lo in range(0, n, HOST_CHUNK_ROWS):
+                c = np.asarray(emb[lo:lo + HOST_CHUNK_ROWS], dtype=np.float32) - mu            # fp32 subtraction, as the device does it
+                if not (np.abs(c) <= 65504.0).all():
+                    del out
+                    raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
+                out[lo:lo + c.shape[0]] = c.astype(np.float16)                                 # round to nearest even
+                c_sq = max(c_sq, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max()))
+            out.flush()
+            del out
+            cnorm, raw = math.sqrt(float(np.float32(c_sq))), math.sqrt(float(np.float32(raw_sq)))
+        with open(path + ".meta.pkl", "wb") as fh:
+            pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F16, "mu": mu,
+                         "max_centred_norm": float(cnorm), "raw_max_norm": float(raw)}, fh)
 
     @classmethod
     def read(cls, path: str) -> "FlatIPIndex":
         with open(path + ".meta.pkl", "rb") as fh:
             meta = pickle.load(fh)
         idx = cls(meta["d"])
+        if meta.get("format") == FORMAT_F16:
+            idx._r16_host = np.load(path + ".emb16.npy", mmap_mode="r")
+            if idx._r16_host.dtype != np.float16 or idx._r16_host.ndim != 2 or idx._r16_host.shape[1] != idx.d:
+                raise ValueError(f"{path}.emb16.npy: expected float16 [n, {idx.d}]")
+            idx._mu_host = np.ascontiguousarray(meta["mu"], dtype=np.float32)
+            idx._cnorm, idx._raw_max = float(meta["max_centred_norm"]), float(meta["raw_max_norm"])
+            idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
+            idx.ntotal = idx._r16_host.shape[0]
+            return idx
         idx.embeddings = np.load(path + ".emb.npy", mmap_mode="r")
         idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
         idx.ntotal = idx.embeddings.shape[0]
         return idx
 
 
-def write_index(index: FlatIPIndex, path: str, faiss_format: bool = False):
+def write_index(index: FlatIPIndex, path: str, faiss_format: bool = False, fp16: bool = False):
     """``faiss.write_index`` of the reference (index_text.py:103).  Default: this package's memory-mappable pair of files;
-    ``faiss_format=True`` writes faiss' own ``IndexIDMap(IndexFlatIP)`` serialisation to ``path`` (see ``write_faiss_index``)."""
+    ``faiss_format=True`` writes faiss' own ``IndexIDMap(IndexFlatIP)`` serialisation to ``path`` (see ``write_faiss_index``);
+    ``fp16=True`` writes the fp16-row format (:meth:`FlatIPIndex.write`; not available in faiss' layout)."""
+    if faiss_format and fp16:
+        raise ValueError("write_index: the fp16-row format exists in this package's own layout only (faiss_format=True with fp16=True)")
     if faiss_format:
         write_faiss_index(index, path)
+    elif fp16:
+        index.write(path, fp16=True)
     else:
         index.write(path)
 
@@ -648,6 +900,7 @@ class ShardedFlatIPIndex:
 
     def __init__(self, local: FlatIPIndex, rank: int = 0, world: int = 1, group=None):
         self.local, self.rank, self.world, self.group = local, rank, world, group
+        self.row_dtype = getattr(local, "row_dtype", "float32")      # the local index searches in either row mode; the exchange does not care
         self.ntotal = local.ntotal
         self.last_merge = {}
         self.force_exchange = False        # tests / bench: run gather + merge with a process group of ONE rank too
@@ -730,12 +983,13 @@ class MultiDeviceFlatIPIndex:
     The production path for 8 GPUs stays one process per GPU (:class:`ShardedFlatIPIndex`, retrieve_top_passages.py under RANK /
     WORLD_SIZE): one Python thread enqueues for all devices here."""
 
-    def __init__(self, index: FlatIPIndex, devices):
+    def __init__(self, index: FlatIPIndex, devices, fp16_rows: bool = False):
         if not devices:
             raise ValueError("convert_index_to_gpu: empty device list")
         if index.embeddings is None:
             raise ValueError("convert_index_to_gpu(index, [devices...]): the index must still hold its rows on the host")
         self.d, self.ntotal = index.d, index.ntotal
+        self.row_dtype = "float16" if fp16_rows else "float32"       # fp16-row mode: every shard is centred on its OWN mean row
         self.devices = [torch.device("cuda", d) if isinstance(d, int) else torch.device(d) for d in devices]
         self.shards = []
         S = len(self.devices)
@@ -748,7 +1002,10 @@ class MultiDeviceFlatIPIndex:
                 else:
                     sh.add(index.embeddings[lo:hi])
                     sh.id_offset = index.id_offset + lo
-                sh.to_gpu(dev)
+                if fp16_rows:
+                    sh.to_gpu(dev, fp16_rows=True)
+                else:
+                    sh.to_gpu(dev)
             self.shards.append(sh)
         self.last_stats = {}
         self.last_merge = {}
@@ -794,13 +1051,17 @@ class MultiDeviceFlatIPIndex:
 def convert_index_to_gpu(index, faiss_gpu_index, useFloat16=False):
     """reference :155-184.  int (or 1-element list): whole index on that GPU.  list of several devices: the index is row-sharded over
     them inside THIS process (:class:`MultiDeviceFlatIPIndex`; the reference's branch, :164-182, is dead code - this is what it
-    intends); the 8-GPU production path is still one process per GPU (:class:`ShardedFlatIPIndex`).  ``useFloat16`` is ignored: the scan
-    always reads an fp16 shadow and the returned scores are exact fp32 either way."""
+    intends); the 8-GPU production path is still one process per GPU (:class:`ShardedFlatIPIndex`).  ``useFloat16=False``: fp32 rows and the
+    fp16 scan shadow are resident, scores are exact fp32.  ``useFloat16=True``: fp16-row mode (:class:`FlatIPIndex`) - as in faiss the vectors
+    live on the GPU in half precision only (a third of the default's bytes) and scores come from the half-precision vectors; unlike faiss the
+    stored vectors are the CENTRED rows ``fp16(p - mu)`` plus ``mu``.  An index read from an fp16-row file is in that mode whatever the flag."""
     if type(faiss_gpu_index) == list and len(faiss_gpu_index) == 1:
         faiss_gpu_index = faiss_gpu_index[0]
     if isinstance(faiss_gpu_index, int):
-        return index.to_gpu(faiss_gpu_index)
+        return index.to_gpu(faiss_gpu_index, fp16_rows=True) if useFloat16 else index.to_gpu(faiss_gpu_index)
     if isinstance(faiss_gpu_index, (list, tuple)):
+        if useFloat16:
+            return MultiDeviceFlatIPIndex(index, list(faiss_gpu_index), fp16_rows=True)
         return MultiDeviceFlatIPIndex(index, list(faiss_gpu_index))
     raise TypeError(f"convert_index_to_gpu: a device index or a list of them, got {type(faiss_gpu_index).__name__}")
 

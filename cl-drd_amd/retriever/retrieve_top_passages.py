@@ -1,7 +1,7 @@
 """``retriever/retrieve_top_passages.py`` of the reference (:28-109) on MI355X: encode the queries, load the index into HBM,
 search top-k in batches of 128 and write the run file ``qid\\tdocid\\trank\\tscore``.
 
-Same flags; extra: ``--synthetic_queries N``.  With WORLD_SIZE > 1 (one process per GPU) rank r loads index shard r, every
+Same flags; extra: ``--synthetic_queries N``, ``--use_float16`` (fp16-row mode: half-precision rows only in HBM).  With WORLD_SIZE > 1 (one process per GPU) rank r loads index shard r, every
 rank encodes all queries (they are 21 MB), and rank 0 merges the per-shard lists on the host and writes the file."""
 from __future__ import annotations
 
@@ -30,6 +30,7 @@ _FLAGS = {
     "share_weights": dict(action="store_true", default=False),
     "output_path": dict(default=""),
     "synthetic_queries": dict(type=int, default=0),       # ours: N generated queries instead of --queries_path
+    "use_float16": dict(action="store_true", default=False),      # ours: attach the index in fp16-row mode (convert_index_to_gpu(..., useFloat16=True))
 }
 
 
@@ -124,7 +125,9 @@ def main(args):
         path = path.replace(".index", f".shard{rank}of{world}.index") if ".shard" not in path else path
     index = read_index(path)
     lap("index_read_s")
-    index = convert_index_to_gpu(index, local_rank, False)
+    # --use_float16: only the centred fp16 rows of an fp32-format file become resident (a third of the bytes; scores from the stored fp16
+    # rows).  A file written by index_text --index_fp16 is searched in that mode with or without the flag.
+    index = convert_index_to_gpu(index, local_rank, bool(getattr(args, "use_float16", False)))
     lap("index_to_gpu_s")
     index = ShardedFlatIPIndex(index, rank, world)
     # the reference converts every 128-query slice to nested Python lists (retrieval_utils.py:145-146) and loops over 7 M scalars to

@@ -319,6 +319,25 @@ int cldrd_topk_rescore(const float* q, const float* P, int d, const int* counts,
                        int nq, int cap, void* stream);
 int cldrd_topk_sort(const int* counts, const int* cand_rows, const float* cand_scores, int nq, int cap, int k, float* D,
                     int* I, void* stream);
+/* fp16-row mode: an index that keeps per shard mu (fp32 [d], the mean row) and R16 = fp16(p - mu) and NO fp32 rows (half the resident bytes of
+ * the scan shadow + fp32 rows pair).  The stored row is mu + R16[r]; its score is fp32(<q, mu> + <q, R16[r]>), both sums in fp64, one rounding:
+ *   cldrd_query_dot64      out[q] = <q, mu> in fp64 (device double [nq], fixed summation order)
+ *   cldrd_topk_rescore16   cldrd_topk_rescore with the rows read from P16 (16-byte loads when d % 8 == 0) and qmu[query] added before the rounding
+ *   cldrd_flatip_search16  cldrd_flatip_search with P32 replaced by (P16, qmu): P16 is the scan's operand and the re-scored row; same passes,
+ *                          status bits and `exhaustive` mask (bit 0: no scan, every row re-scored from P16)
+ *   cldrd_gather_cast_rows16       dst[i] = bf16(src16[i * stride]): the threshold sample of an index uploaded as fp16 rows
+ *   cldrd_index_center_cast_chunk  cldrd_index_center_cast on rows [row0, row0 + rows) of a shard attached chunk by chunk (P, P16 point at row0;
+ *                          the sample is the whole shard's; *cmax_bits, *flag accumulate over the chunks) */
+int cldrd_query_dot64(const float* q, const float* mu, int d, double* out, int nq, void* stream);
+int cldrd_topk_rescore16(const float* q, const void* P16, const double* qmu, int d, const int* counts, const int* cand_rows,
+                         float* cand_scores, int nq, int cap, void* stream);
+int cldrd_flatip_search16(const float* q32, const void* q16, const float* thr, const float* eps, const void* P16, const double* qmu,
+                          long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
+                          int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
+                          int exhaustive, void* stream);
+int cldrd_gather_cast_rows16(const void* src16, void* dst, size_t n_out, size_t stride, int d, void* stream);
+int cldrd_index_center_cast_chunk(const float* P, const float* mu, size_t rows, size_t row0, int d, void* P16, void* sample_bf16,
+                                  size_t s_stride, size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream);
 int cldrd_row_sqnorm_max(const float* P, size_t rows, int d, unsigned int* out, void* stream);
 int cldrd_gather_cast_rows(const float* src, void* dst, size_t n_out, size_t stride, int d, void* stream);
 /* Attaching an index shard to a GPU (what faiss' index_cpu_to_gpu does behind retriever/retrieval_utils.py:155-162 - here: the scan shadow
