@@ -26,6 +26,7 @@ SIGNATURES = {
     "cldrd_wgrad_splits": (ci, [ci, ci, ci]),
     "cldrd_wgrad16": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, csz, ci, vp]),
     "cldrd_wgrad_group_workspace": (csz, [vp, vp, vp, ci]),
+    "cldrd_wgrad_plan": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "cldrd_wgrad_group": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, csz, ci, vp]),
     "cldrd_attention_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp]),
     "cldrd_attention_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, vp]),

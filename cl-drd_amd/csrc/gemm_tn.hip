@@ -12,8 +12,8 @@
 // Same software pipeline as gemm_nt_ring.hip: per 32-token k-step the A fragments are refilled in place as soon as
 // their last MFMA has issued, the B fragments are double-buffered, reads are threaded between the MFMAs
 // (sched_group_barrier), one raw s_barrier per K tile, the DMA of K tile t+2 is issued half-way through K tile t.
-// M = tokens is huge and N1 x N2 small, so the token range is split over `splits` workgroups per tile; each writes an
-// fp32 slab and a second pass sums the slabs in a fixed order (bitwise reproducible, no float atomics).
+// M = tokens is huge and N1 x N2 small, so the token range of a tile is cut into chunks, one workgroup each; each writes an fp32 slab
+// and a second pass sums the slabs in a fixed order (bitwise reproducible, no float atomics).
 // The bias gradient costs one extra MFMA per A fragment in the n2 == 0 tiles: B = all-ones.
 //
 // Rows >= M of the last 64-token K tile are fetched from a zero page instead of the operands (the LDS-DMA source address is per
@@ -21,36 +21,54 @@
 //
 // GROUPED launch (cldrd_wgrad_group): the weight gradients are not on the critical path of the backward (only the data gradients
 // are), so the trainer defers them and hands all of a tower's problems - 4 per layer - to ONE launch.  Work item = (problem, token
-// split, output tile), ordered tile-fastest so that the workgroups running at the same time on one XCD compute neighbouring tiles
-// of the same problem at the same token position (shared A / B panels in that XCD's L2).  With 700+ tiles in a group no token split
-// is needed any more (744 tiles = 2.9 rounds of 256 CUs for DistilBERT at cfg2): every workgroup sweeps ALL tokens of its tile and
-// writes dW once - no fp32 slabs through HBM, no reduction launches (round 1: 25 GEMM + 25 reduction launches and ~1 GB of slab
-// traffic per step).  Token splits + slabs remain for small groups (few tiles), chosen by the same cost model as before.
+// chunk, output tile), ordered tile-fastest so that the workgroups running at the same time on one XCD compute neighbouring tiles
+// of the same problem at the same token position (shared A / B panels in that XCD's L2).  Workgroups of an XCD stay together only for
+// about 256 K tiles (wgrad_splits_group), so long token ranges are cut even where the tiles alone would fill the CUs.  How they are cut is
+// a host-side PLAN per problem (wgrad_plan_group): n_long chunks of c_long K tiles, then n_short chunks of c_short, the long items of all
+// problems first in the launch, the short ones last, where they fill the round the long items leave part empty.  At cfg2 (25 problems,
+// 32 768 tokens) one split count for the launch meant 3 x 171 K tiles and a last round a third full; the plan is two chunks of 256 for
+// 18 problems, 256 + 2 x 128 or 4 x 128 for three small ones, one short item per tile of the CLS-only layer's four-K-tile problems: 1 305
+// items instead of 1 944, 342 MB written instead of 510, the launch 2.39 -> 2.25 ms and its reduction 117 -> 86 us
+// (profiles/wgrad_balanced_timing.txt).  A problem with one chunk writes dW directly; a group of ONE problem keeps the single split
+// count and the bits it always had.
+// Tried and dropped: adding the slabs up inside the launch (arrival counter per tile, agent-scope release / acquire, the last arriver
+// reads the slabs in chunk order).  Correct and reproducible, and the 86-us reduction launch goes away, but with a release at the end of
+// every workgroup and the slabs re-read inside it the launch grew from 2.25 to 2.44 ms: +0.05 ms per step (same file).
+#include <algorithm>
+#include <functional>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 
 namespace {
 
 constexpr int BK = 64;                 // tokens per LDS slot
-constexpr int MAXP = 32;               // problems per launch (kernel-argument block: 32 x 72 B)
+constexpr int MAXP = 32;               // problems per launch (kernel-argument block: 32 x 104 B + header, see the static_assert)
 
 struct TnProblem {
     const bf16_t* A; const bf16_t* B; float* dW; float* dbias;      // dbias may be null
     int M, N1, N2, lda, ldb;
     int tiles, nt2;                    // (N1 / T1) * (N2 / T2), N2 / T2
     int nt1, n1_fast;                  // N1 / T1; tile order inside a split: n2 fastest (0) or n1 fastest (1), see cldrd_wgrad_group
-    int first;                         // first work item of this problem; items of a problem: split-major, tile-minor
-    long long slab_off;                // splits > 1: float offset of this problem's slabs in the workspace
+    // Chunk plan (host: wgrad_plan_group).  The token range is cut into n_long chunks of clen[0] K tiles followed by chunks of clen[1]
+    // K tiles (the last chunk may be shorter).  A launch runs the long items of ALL its problems first, then the short ones: region
+    // r = 0 (long) / 1 (short), first[r] = this problem's first work item counted from the start of region r; items of a problem inside a
+    // region: chunk-major, tile-minor.
+    int first[2], clen[2];
+    int n_long, chunks;                // long chunks; all chunks = fp32 slabs of this problem (1: the tile is complete, dW is written directly)
+    long long slab_off;                // chunks > 1: float offset of this problem's slabs in the workspace
 };
 struct TnGroupArgs {
-    int n, splits, accumulate, stagger;
+    int n, items_long, accumulate, stagger;      // items_long: work items of region 0 (the grid holds items_long + the short items)
     float* slabs;
     const float* inv_scale;            // device scalar or null: every output (dW, dbias) is multiplied by it - the operands of the all-fp16
                                        // training mode carry the loss scale, parameter gradients do not (capi.hip: cldrd_set_loss_scale)
     float* sq_out;                     // slab reduction only: [gridDim.y][gridDim.x] sums of squares of what each workgroup wrote, or null
     TnProblem p[MAXP];
 };
+// the table travels in the kernel-argument block (the launch is captured in a graph: no device-side copy to keep alive)
+static_assert(sizeof(TnProblem) == 104 && sizeof(TnGroupArgs) <= 4096, "TnGroupArgs must fit the 4-KiB kernel-argument block");
 
 __device__ __attribute__((aligned(4096))) uint4 g_zero_page[256];     // 4 KiB of zeros: DMA source of token rows >= M
 
@@ -120,21 +138,25 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
     constexpr int G = APW + BPW;                        // LDS-DMA instructions per wave per K tile
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int id = xcd_remap(blockIdx.x, gridDim.x);
+    // Long items first, short items last; each region is spread over the XCDs on its own, so every XCD works through its share of the
+    // long items, then its share of the short ones, and neighbouring tiles of a (problem, chunk) still meet in one XCD's L2.
+    const int rg = (int)blockIdx.x >= ga.items_long ? 1 : 0;             // wave-uniform, like everything down to c1 / c2
+    const int id = rg ? xcd_remap(blockIdx.x - ga.items_long, gridDim.x - ga.items_long) : xcd_remap(blockIdx.x, ga.items_long);
     int pi = 0;
-    while (pi + 1 < ga.n && id >= ga.p[pi + 1].first) ++pi;               // wave-uniform: scalar loads from the argument block
+    while (pi + 1 < ga.n && id >= ga.p[pi + 1].first[rg]) ++pi;          // scalar loads from the argument block
     const TnProblem& P = ga.p[pi];
     const bf16_t* __restrict__ A = P.A;
     const bf16_t* __restrict__ B = P.B;
     const int M = P.M, N1 = P.N1, N2 = P.N2, lda = P.lda, ldb = P.ldb;
     const int nt2 = P.nt2, ntiles = P.tiles;
-    const int local = id - P.first;
-    const int split = local / ntiles, tile = local % ntiles;      // the tiles of one split are neighbours: they share A/B rows
+    const int local = id - P.first[rg];
+    const int chunk = local / ntiles, tile = local % ntiles;      // the tiles of one chunk are neighbours: they share A/B rows
     const int c1 = (P.n1_fast ? tile % P.nt1 : tile / nt2) * T1, c2 = (P.n1_fast ? tile / P.nt1 : tile % nt2) * T2;
     const int ktotal = (M + BK - 1) / BK;
-    const int ksteps_per_split = (ktotal + ga.splits - 1) / ga.splits;
-    const int kbeg = split * ksteps_per_split;
-    const int nk = min(ktotal, kbeg + ksteps_per_split) - kbeg;
+    const int clen = P.clen[rg];
+    const int kbeg = (rg ? P.n_long * P.clen[0] : 0) + chunk * clen;
+    const int nk = min(ktotal, kbeg + clen) - kbeg;
+    const int slab = (rg ? P.n_long : 0) + chunk;
     const int wm = wid / WGN, wn = wid % WGN;
     const bool do_bias = P.dbias != nullptr && c2 == 0 && wn == 0;
     const int stagger = ga.stagger;
@@ -369,9 +391,9 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
         else sweep(std::false_type{});
     }
 
-    // ---- output.  One split: the tile is complete, write (or add to) dW / dbias directly.  Several: this split's slab.
-    const bool direct = ga.splits == 1;
-    float* outW = direct ? P.dW : ga.slabs + P.slab_off + (size_t)split * ((size_t)N1 * N2 + (size_t)N1);
+    // ---- output.  One chunk: the tile is complete, write (or add to) dW / dbias directly.  Several: this chunk's slab.
+    const bool direct = P.chunks == 1;
+    float* outW = direct ? P.dW : ga.slabs + P.slab_off + (size_t)slab * ((size_t)N1 * N2 + (size_t)N1);
     float* outB = direct ? P.dbias : outW + (size_t)N1 * N2;
     const bool add = direct && ga.accumulate != 0;
     const float osc = (direct && ga.inv_scale) ? *ga.inv_scale : 1.0f;      // slabs stay raw: the reduction applies the factor
@@ -413,18 +435,27 @@ __global__ void reduce_slabs_kernel(const float* __restrict__ slabs, float* __re
     }
 }
 
-// the same for every problem of a group in one launch: blockIdx.y = problem
+// the same for every problem of a group in one launch: blockIdx.y = problem.  A problem with a single chunk has no slabs (the GEMM wrote
+// its dW); when the clip norm's partial sums are wanted it is read once more here, so that the sink sees everything the group wrote.
 __global__ __launch_bounds__(256) void reduce_slabs_group_kernel(TnGroupArgs ga) {
     const TnProblem& P = ga.p[blockIdx.y];
+    if (P.chunks == 1 && !ga.sq_out) return;            // written directly by the GEMM and nobody asks for its sum of squares
     const size_t n_main4 = (size_t)P.N1 * P.N2 / 4, n_all4 = n_main4 + (P.dbias ? (size_t)P.N1 / 4 : 0);
     const size_t stride4 = ((size_t)P.N1 * P.N2 + (size_t)P.N1) / 4;
     const float4* slabs = (const float4*)(ga.slabs + P.slab_off);
     const size_t step = (size_t)gridDim.x * blockDim.x;
     const float osc = ga.inv_scale ? *ga.inv_scale : 1.0f;
     float sq = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_all4; i += step) {
+    if (P.chunks == 1) {
+        // no slabs: the GEMM launch in front of this one wrote dW / dbias; only the clip norm's share is taken here (same slots, same order)
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_all4; i += step) {
+            const float4 s = i < n_main4 ? ((const float4*)P.dW)[i] : ((const float4*)P.dbias)[i - n_main4];
+            sq += s.x * s.x + s.y * s.y + s.z * s.z + s.w * s.w;
+        }
+    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; P.chunks > 1 && i < n_all4; i += step) {
         float4 s = slabs[i];
-        for (int k = 1; k < ga.splits; ++k) {
+        for (int k = 1; k < P.chunks; ++k) {
             const float4 t = slabs[i + k * stride4];
             s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
         }
@@ -523,6 +554,196 @@ static int wgrad_splits_group(const int* M, const int* N1, const int* N2, int n,
     return best;
 }
 
+
+// ---- chunk plan of a group launch -----------------------------------------------------------------------------------------------------
+// One split count for the whole launch leaves a tail: at cfg2 the passage tower's 25 problems become 1 674 items of 171 K tiles (+ the
+// CLS-only layer's four-K-tile ones), 6.5 items per CU, and the last round runs a third full.  A plan gives every problem its own cut -
+// n_long chunks of c_long K tiles, then n_short chunks of c_short - and the launch runs all long items first, the short ones last, so
+// the short items fill the tail.  The plan is a pure function of the shapes: a small candidate set (every uniform count, as before, and
+// c_long x c_short x the share of long ranges re-cut into short chunks) is scored by replaying the dispatch - 256 CUs, one workgroup
+// each (LDS), items handed out in launch order to whichever CU is free first, item cost = K tiles + OVERHEAD - plus the slab bytes
+// and the reduction launch in the same units as wgrad_splits_group.  Smallest modelled time wins among the candidates whose replay is
+// no longer than that of every uniform count up to 8; ties go to the earlier candidate (uniform, fewer chunks).
+struct WgradChunks { int n_long, c_long, n_short, c_short; };
+struct WgradPlan {
+    WgradChunks p[MAXP];
+    int items_long, items_short;
+    double makespan, cost;             // replayed dispatch; + slab traffic and reduction launch
+};
+
+static inline int wgrad_ktiles(int M) { return (M + BK - 1) / BK; }
+static inline int wgrad_chunks(const WgradChunks& c) { return c.n_long + c.n_short; }
+static inline int xcd_remap_host(int orig, int nwg) {          // common.h: xcd_remap
+    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
+
+// Fills items_*, makespan and cost of `pl` from its chunk table.  `beat` >= 0: the replay is skipped (false) when even perfectly balanced
+// work could not come in under `beat`.
+static bool wgrad_plan_score(const int* M, const int* N1, const int* N2, int n, WgradTile t, WgradPlan& pl, double beat = -1.0) {
+    const int overhead = 6, slots = 256;
+    double slab_bytes = 0.0, work = 0.0, longest = 0.0;
+    std::vector<float> cost[2];                                // per item, in item order of its region
+    for (int i = 0; i < n; ++i) {
+        const int tiles = (N1[i] / t.t1) * (N2[i] / t.t2), kt = wgrad_ktiles(M[i]);
+        const WgradChunks& c = pl.p[i];
+        if (wgrad_chunks(c) > 1) slab_bytes += 2.0 * wgrad_chunks(c) * 4.0 * N1[i] * N2[i];
+        for (int rg = 0; rg < 2; ++rg) {
+            const int clen = rg ? c.c_short : c.c_long;
+            for (int ch = 0; ch < (rg ? c.n_short : c.n_long); ++ch) {
+                const int kbeg = (rg ? c.n_long * c.c_long : 0) + ch * clen;
+                const int nk = std::max(0, std::min(kt, kbeg + clen) - kbeg);      // (a uniform split of a short problem has empty chunks)
+                cost[rg].insert(cost[rg].end(), (size_t)tiles, (float)(nk + overhead));
+                work += (double)tiles * (nk + overhead);
+                longest = std::max(longest, (double)(nk + overhead));
+            }
+        }
+    }
+    pl.items_long = (int)cost[0].size();
+    pl.items_short = (int)cost[1].size();
+    const double extra = slab_bytes > 0.0 ? slab_bytes / 5.0e12 / 1.5e-6 + 4.0 : 0.0;      // slabs written and read back, the reduction launch
+    if (beat >= 0.0 && std::max(work / slots, longest) + extra >= beat) return false;
+    std::vector<double> heap(slots, 0.0);                      // min-heap of the times at which the CUs fall free
+    double end = 0.0;
+    for (int rg = 0; rg < 2; ++rg) {
+        const int cnt = (int)cost[rg].size();
+        for (int s = 0; s < cnt; ++s) {                        // launch order: the kernel's xcd_remap per region
+            std::pop_heap(heap.begin(), heap.end(), std::greater<double>());
+            heap.back() += cost[rg][xcd_remap_host(s, cnt)];
+            end = std::max(end, heap.back());
+            std::push_heap(heap.begin(), heap.end(), std::greater<double>());
+        }
+    }
+    pl.makespan = end;
+    pl.cost = end + extra;
+    return true;
+}
+
+// `sp` chunks of ceil(ktotal / sp) K tiles for every problem, all in the long region: what a launch did before there was a plan (a short
+// problem then gets empty chunks too); `trim` drops those
+static void wgrad_plan_uniform(const int* M, int n, int sp, bool trim, WgradPlan& pl) {
+    for (int i = 0; i < n; ++i) {
+        const int kt = wgrad_ktiles(M[i]), per = (kt + sp - 1) / sp;
+        pl.p[i] = {trim ? (kt + per - 1) / per : sp, per, 0, 0};
+    }
+}
+
+static WgradPlan wgrad_plan_search(const int* M, const int* N1, const int* N2, int n, WgradTile t, int force_uniform) {
+    WgradPlan best;
+    int ktotal = 1;
+    for (int i = 0; i < n; ++i) ktotal = std::max(ktotal, wgrad_ktiles(M[i]));
+    const int force = force_uniform > 0 ? force_uniform : CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS", 0);
+    // one problem keeps the rule (and the bits) it had; CLDRD_WGRAD_PLAN=0 (development build): every group does
+    if (force > 0 || n == 1 || CLDRD_DEV_INT("CLDRD_WGRAD_PLAN", 1) == 0) {
+        wgrad_plan_uniform(M, n, force > 0 ? std::min(force, ktotal) : wgrad_splits_group(M, N1, N2, n, t), false, best);
+        wgrad_plan_score(M, N1, N2, n, t, best);
+        return best;
+    }
+    const int maxk = CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256) < 1 ? 256 : CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256);      // the drift cap, see wgrad_splits_group
+    // A plan must also replay no longer than the best of the uniform counts up to 8 does (slab bytes aside): that one is always eligible.
+    WgradPlan c;
+    double span_cap = -1.0;
+    for (int sp = (ktotal + maxk - 1) / maxk; sp <= 8 && sp <= ktotal; ++sp) {
+        wgrad_plan_uniform(M, n, sp, true, c);
+        wgrad_plan_score(M, N1, N2, n, t, c);
+        if (span_cap < 0.0 || c.makespan < span_cap) span_cap = c.makespan;
+    }
+    bool have = false;
+    auto consider = [&](WgradPlan& c) {
+        if (!wgrad_plan_score(M, N1, N2, n, t, c, have ? best.cost - 1e-9 : -1.0)) return;
+        if (span_cap >= 0.0 && c.makespan > span_cap + 1e-9) return;
+        if (!have || c.cost < best.cost - 1e-9) { best = c; have = true; }
+    };
+    for (int sp = (ktotal + maxk - 1) / maxk; sp <= 64 && sp <= ktotal; ++sp) {
+        wgrad_plan_uniform(M, n, sp, true, c);
+        consider(c);
+    }
+    static const int c_longs[] = {256, 171, 128}, c_shorts[] = {32, 64, 128};
+    static const double shares[] = {0.0, 1.0 / 16, 1.0 / 8, 3.0 / 16, 1.0 / 4, 3.0 / 8, 1.0 / 2};
+    for (int cl : c_longs) {
+        if (cl > maxk) continue;
+        for (int cs : c_shorts) {
+            if (cs >= cl) continue;
+            // long ranges of a problem: ceil(kt / cl); problems of at most cs K tiles are one short item.  `want` of all (tile, range)
+            // pairs are re-cut, taken from the end of the problem list, a problem's last range first: fixed shares, and what the long
+            // items have beyond whole rounds of 256 CUs (the short items then start on a level front).
+            long all = 0;
+            for (int i = 0; i < n; ++i)
+                if (wgrad_ktiles(M[i]) > cs) all += (long)(N1[i] / t.t1) * (N2[i] / t.t2) * ((wgrad_ktiles(M[i]) + cl - 1) / cl);
+            // (want, cover): cover = re-cut at least `want` (one more range of the smallest problem that still has one), else at most
+            std::vector<std::pair<long, bool>> wants;
+            for (double share : shares) wants.push_back({(long)(share * (double)all + 0.5), false});
+            for (long rounds = all / 256; rounds >= 0 && rounds + 2 > all / 256; --rounds) wants.push_back({all - 256 * rounds, true});
+            for (const auto& w : wants) {
+                int nl[MAXP];
+                long done = 0;
+                for (int i = n - 1; i >= 0; --i) {
+                    const int kt = wgrad_ktiles(M[i]);
+                    const long tiles = (long)(N1[i] / t.t1) * (N2[i] / t.t2);
+                    nl[i] = kt <= cs ? 0 : (kt + cl - 1) / cl;
+                    while (nl[i] > 0 && done + tiles <= w.first) { --nl[i]; done += tiles; }
+                }
+                if (w.second && done < w.first) {
+                    int pick = -1;
+                    for (int i = n - 1; i >= 0; --i)
+                        if (nl[i] > 0 && (pick < 0 || (N1[i] / t.t1) * (N2[i] / t.t2) < (N1[pick] / t.t1) * (N2[pick] / t.t2))) pick = i;
+                    if (pick >= 0) --nl[pick];
+                }
+                for (int i = 0; i < n; ++i) {
+                    const int kt = wgrad_ktiles(M[i]);
+                    if (kt <= cs) { c.p[i] = {0, cl, 1, kt}; continue; }
+                    const int rest = kt - std::min(kt, nl[i] * cl);
+                    c.p[i] = {nl[i], cl, (rest + cs - 1) / cs, cs};
+                }
+                consider(c);
+            }
+        }
+    }
+    return best;
+}
+
+// the search is repeated for every launch of an eager step: remember the last few answers (shapes, tile and knobs are the key)
+static WgradPlan wgrad_plan_group(const int* M, const int* N1, const int* N2, int n, WgradTile t, int force_uniform = 0) {
+    struct Entry { std::vector<int> key; WgradPlan plan; };
+    thread_local std::vector<Entry> cache;
+    std::vector<int> key = {n, t.t1, t.t2, force_uniform, CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS", 0), CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS_BIG", 0),
+                            CLDRD_DEV_INT("CLDRD_WGRAD_PLAN", 1), CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256)};
+    for (int i = 0; i < n; ++i) { key.push_back(M[i]); key.push_back(N1[i]); key.push_back(N2[i]); }
+    for (const Entry& e : cache)
+        if (e.key == key) return e.plan;
+    if (cache.size() >= 16) cache.erase(cache.begin());
+    cache.push_back({key, wgrad_plan_search(M, N1, N2, n, t, force_uniform)});
+    return cache.back().plan;
+}
+
+// The planner's answer for inspection (host only, no device call; tests/test_wgrad_plan.py).  Per problem: chunks[4 i ..] = n_long,
+// c_long, n_short, c_short (K tiles of 64 tokens).  info[0..7] = tile rows, tile columns, work items, launches, bytes of the kernel-argument
+// block, its limit, problems per launch, 0.  model[0] = replayed makespan, model[1] = modelled cost (K-tile times; summed over the launches).
+// uniform_splits > 0: that many token splits for every problem, the form every group launch had before, scored by the same model.
+extern "C" int cldrd_wgrad_plan(const int* M, const int* N1, const int* N2, int n, int uniform_splits, int* chunks, int* info, double* model) {
+    CLDRD_CHECK(n > 0, "wgrad_plan: no problems");
+    for (int i = 0; i < n; ++i)
+        CLDRD_CHECK(M[i] > 0 && N1[i] % 128 == 0 && (N2[i] % 128 == 0 || (N1[i] % 256 == 0 && N2[i] % 192 == 0)), "wgrad_plan: unsupported shape");
+    const WgradTile t = wgrad_tile_group(N1, N2, n);
+    int items = 0, launches = 0;
+    double makespan = 0.0, cost = 0.0;
+    for (int lo = 0; lo < n; lo += MAXP, ++launches) {
+        const int m = std::min(n - lo, MAXP);
+        const WgradPlan pl = wgrad_plan_group(M + lo, N1 + lo, N2 + lo, m, t, uniform_splits);
+        for (int i = 0; i < m; ++i) {
+            chunks[4 * (lo + i) + 0] = pl.p[i].n_long; chunks[4 * (lo + i) + 1] = pl.p[i].c_long;
+            chunks[4 * (lo + i) + 2] = pl.p[i].n_short; chunks[4 * (lo + i) + 3] = pl.p[i].c_short;
+        }
+        items += pl.items_long + pl.items_short;
+        makespan += pl.makespan;
+        cost += pl.cost;
+    }
+    info[0] = t.t1; info[1] = t.t2; info[2] = items; info[3] = launches;
+    info[4] = (int)sizeof(TnGroupArgs); info[5] = 4096; info[6] = MAXP; info[7] = 0;
+    model[0] = makespan; model[1] = cost;
+    return 0;
+}
+
 extern "C" int cldrd_wgrad_splits(int M, int N1, int N2) {
     if (N1 % 128 != 0 || !(N2 % 128 == 0 || (N1 % 256 == 0 && N2 % 192 == 0))) return 1;
     return wgrad_splits_group(&M, &N1, &N2, 1, wgrad_tile_group(&N1, &N2, 1));
@@ -548,10 +769,13 @@ static int launch_tn_group(const TnGroupArgs& g, int items, hipStream_t st) {
 extern "C" size_t cldrd_wgrad_group_workspace(const int* M, const int* N1, const int* N2, int n) {
     if (n <= 0) return 0;
     const WgradTile t = wgrad_tile_group(N1, N2, n);
-    const int splits = wgrad_splits_group(M, N1, N2, n, t);
-    if (splits == 1) return 0;
     size_t tot = 0;
-    for (int i = 0; i < n; ++i) tot += (size_t)splits * ((size_t)N1[i] * N2[i] + (size_t)N1[i]);
+    for (int lo = 0; lo < n; lo += MAXP) {
+        const int m = n - lo < MAXP ? n - lo : MAXP;
+        const WgradPlan pl = wgrad_plan_group(M + lo, N1 + lo, N2 + lo, m, t);
+        for (int i = 0; i < m; ++i)
+            if (wgrad_chunks(pl.p[i]) > 1) tot += (size_t)wgrad_chunks(pl.p[i]) * ((size_t)N1[lo + i] * N2[lo + i] + (size_t)N1[lo + i]);
+    }
     return tot;
 }
 
@@ -575,21 +799,19 @@ extern "C" int cldrd_wgrad_group(const void* const* A, const void* const* B, flo
     bool any128 = false;
     for (int i = 0; i < n; ++i) any128 = any128 || N2[i] % 128 != 0;
     CLDRD_CHECK(!(t.t2 != 192 && any128), "wgrad_group: problems with N2 % 128 != 0 need every problem to fit the 256 x 192 tile");
-    const int splits = wgrad_splits_group(M, N1, N2, n, t);
-    if (splits > 1) {
-        size_t need = 0;
-        for (int i = 0; i < n; ++i) need += (size_t)splits * ((size_t)N1[i] * N2[i] + (size_t)N1[i]);
-        CLDRD_CHECK(workspace != nullptr && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= need * sizeof(float), "wgrad: workspace too small");
-    }
+    const size_t need = cldrd_wgrad_group_workspace(M, N1, N2, n);
+    CLDRD_CHECK(need == 0 || (workspace != nullptr && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= need * sizeof(float)), "wgrad: workspace too small");
     const int env_order = CLDRD_DEV_INT("CLDRD_WGRAD_ORDER", -1);       // tile order per problem (below); development build: 0 / 1 force n2- / n1-fastest
     size_t slab_off = 0;
     for (int lo = 0; lo < n; lo += MAXP) {
         const int m = n - lo < MAXP ? n - lo : MAXP;
+        const WgradPlan pl = wgrad_plan_group(M + lo, N1 + lo, N2 + lo, m, t);
         TnGroupArgs g;
-        g.n = m; g.splits = splits; g.accumulate = accumulate & 1; g.stagger = wgrad_stagger(); g.slabs = workspace;
+        g.n = m; g.items_long = pl.items_long; g.accumulate = accumulate & 1; g.stagger = wgrad_stagger(); g.slabs = workspace;
         g.inv_scale = g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr;
         g.sq_out = nullptr;
-        int items = 0;
+        int first[2] = {0, 0};
+        bool reduce = false;
         for (int i = 0; i < m; ++i) {
             TnProblem& P = g.p[i];
             const int j = lo + i;
@@ -601,10 +823,14 @@ extern "C" int cldrd_wgrad_group(const void* const* A, const void* const* B, flo
             // 3 n1 tiles x 16 n2 tiles: n2 fastest covers 2 of the 3 rows, so every panel of h (the 200-MB operand) is fetched by 2 concurrent
             // tiles now and again by the third row later; n1 fastest puts all 3 tiles of an h panel side by side: h streams from HBM once.
             P.n1_fast = (env_order == 1 || (env_order < 0 && P.nt2 > P.nt1 && P.nt1 <= 32)) ? 1 : 0;
-            P.first = items; P.slab_off = (long long)slab_off;
-            items += P.tiles * splits;
-            if (splits > 1) slab_off += (size_t)splits * ((size_t)N1[j] * N2[j] + (size_t)N1[j]);
+            P.first[0] = first[0]; P.first[1] = first[1];
+            P.clen[0] = pl.p[i].c_long; P.clen[1] = pl.p[i].c_short;
+            P.n_long = pl.p[i].n_long; P.chunks = wgrad_chunks(pl.p[i]);
+            P.slab_off = (long long)slab_off;
+            first[0] += P.tiles * pl.p[i].n_long; first[1] += P.tiles * pl.p[i].n_short;
+            if (P.chunks > 1) { slab_off += (size_t)P.chunks * ((size_t)N1[j] * N2[j] + (size_t)N1[j]); reduce = true; }
         }
+        const int items = first[0] + first[1];
         int rc;
 #ifdef CLDRD_DEV_BUILD                                 // timing-only ablations (WRONG results): development build only
         const int abl = cldrd_dev_int("CLDRD_TN_ABLATE", 0);
@@ -626,8 +852,8 @@ extern "C" int cldrd_wgrad_group(const void* const* A, const void* const* B, flo
         else if (t.t1 == 256) rc = launch_tn_group<256, 128, 8>(g, items, st);
         else rc = launch_tn_group<128, 128, 4>(g, items, st);
         if (rc) return rc;
-        if (splits == 1) cldrd_norm_sink_miss();      // tiles written directly by the GEMM: no slab reduction to take the sums of squares from
-        if (splits > 1) {
+        if (!reduce) cldrd_norm_sink_miss();          // every tile written directly by the GEMM: no slab reduction to take the sums of squares from
+        if (reduce) {
             size_t biggest = 0;
             for (int i = 0; i < m; ++i) biggest = biggest > (size_t)g.p[i].N1 * g.p[i].N2 / 4 ? biggest : (size_t)g.p[i].N1 * g.p[i].N2 / 4;
             const int rb = (int)((biggest + 255) / 256 < 256 ? (biggest + 255) / 256 : 256);

@@ -85,12 +85,19 @@ int cldrd_gemm_nt16_ws(const void* A, const void* B, void* C, int M, int N, int 
  * cldrd_wgrad_group: n such problems in ONE launch (the pointer / shape arrays are HOST arrays).  The weight gradients are off the
  * critical path of the backward, so the trainer defers them: with a tower's 20+ problems in one launch every workgroup sweeps all
  * tokens of its output tile and writes dW once - no token split, no fp32 partial slabs, no reduction launches.
- * workspace (floats): cldrd_wgrad_group_workspace(...) for a group (0 when no token split is chosen),
+ * workspace (floats): cldrd_wgrad_group_workspace(...) for a group (fp32 slabs of the problems whose token range is cut; 0 when none is),
  * cldrd_wgrad_splits(M,N1,N2) * (N1 * N2 + N1) for the single-problem form. */
 int cldrd_wgrad_splits(int M, int N1, int N2);
 int cldrd_wgrad16(const void* A, const void* B, float* dW, float* dbias, int M, int N1, int N2, int lda, int ldb,
                      float* workspace, size_t workspace_bytes, int accumulate, void* stream);
 size_t cldrd_wgrad_group_workspace(const int* M, const int* N1, const int* N2, int n);
+/* The chunk plan a group launch of these shapes uses (host only, no device call): every problem's token range is cut into n_long chunks
+ * of c_long K tiles (64 tokens each) followed by n_short chunks of c_short, the launch runs all long items first, the short ones last.
+ * chunks[4 i ..] = n_long, c_long, n_short, c_short of problem i;  info[0..7] = tile rows, tile columns, work items, launches (32 problems
+ * each), bytes of the kernel-argument block, its limit, problems per launch, 0;  model[0] = makespan of the replayed dispatch (256 CUs,
+ * items in launch order, K tiles + 6 per item), model[1] = that plus the slab traffic and the reduction launch, in K-tile times.
+ * uniform_splits > 0: the same numbers for that many token splits of every problem instead of the planner's choice. */
+int cldrd_wgrad_plan(const int* M, const int* N1, const int* N2, int n, int uniform_splits, int* chunks, int* info, double* model);
 int cldrd_wgrad_group(const void* const* A, const void* const* B, float* const* dW, float* const* dbias, const int* M,
                       const int* N1, const int* N2, const int* lda, const int* ldb, int n, float* workspace,
                       size_t workspace_bytes, int accumulate, void* stream);
