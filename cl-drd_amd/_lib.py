@@ -6,8 +6,8 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# CLDRD_LIB selects another BUILD of the library (tools/build_dev.py: the development build with the experiments' knobs); the product
-# library itself reads no environment variable
+# CLDRD_LIB selects another BUILD of the library (e.g. the parent commit's, for A/B runs); the library itself reads no environment
+# variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
 
 _lib = None

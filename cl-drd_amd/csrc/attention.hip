@@ -115,11 +115,7 @@ __device__ __forceinline__ void mfma_drain() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-#if defined(CLDRD_DEV_BUILD) && defined(CLDRD_NO_BLOCK_SKIP)
-#define CLDRD_LIVE_BLOCKS(len, NKB) (NKB)                 // development build: compute every block (bisecting)
-#else
 #define CLDRD_LIVE_BLOCKS(len, NKB) (((len) + 31) >> 5)
-#endif
 // A launch may cover a LIST of sequences (seq_list, device int32; null: all of them in order): item i / H is then the list position and
 // seq_list[i / H] the sequence - how a packed batch with L > 128 sends its sequences of at most 128 tokens (most of an MS MARCO batch) to the
 // L <= 128 kernels (persistent, double-buffered) and only the long ones to the streaming / one-item kernels: `L` stays the stride of LSE and of

@@ -11,25 +11,14 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 // Streaming accesses for data touched once in a long while (the backward tape: written by the forward, read ~10 ms later): the
-// non-temporal hint keeps them from evicting what the NEXT kernel reads out of the 256-MB Infinity Cache.  CLDRD_TAPE_NT=0: A/B builds.
-#ifndef CLDRD_TAPE_NT
-#define CLDRD_TAPE_NT 1
-#endif
+// non-temporal hint keeps them from evicting what the NEXT kernel reads out of the 256-MB Infinity Cache.
 __device__ __forceinline__ uint4 ld16_stream(const void* p) {
-#if CLDRD_TAPE_NT
     const u32x4 t = __builtin_nontemporal_load((const u32x4*)p);
     return make_uint4(t.x, t.y, t.z, t.w);
-#else
-    return *(const uint4*)p;
-#endif
 }
 __device__ __forceinline__ void st16_stream(void* p, const uint4& v) {
-#if CLDRD_TAPE_NT
     const u32x4 t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, (u32x4*)p);
-#else
-    *(uint4*)p = v;
-#endif
 }
 
 #define CLDRD_WAVE 64
@@ -196,15 +185,7 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 
 int cldrd_set_error(const char* msg);
 
-// The PRODUCT library reads no environment variable: an inherited variable must not change what a run computes, or how.  Tuning and
-// ablation knobs of the experiments (tools/) exist only in the development build (tools/build_dev.py: -DCLDRD_DEV_BUILD ->
-// libcldrd_hip_dev.so, selected with CLDRD_LIB=...); in the product build CLDRD_DEV_INT(name, default) IS the default, at compile time.
-#ifdef CLDRD_DEV_BUILD
-int cldrd_dev_int(const char* name, int dflt);
-#define CLDRD_DEV_INT(name, dflt) cldrd_dev_int(name, dflt)
-#else
-#define CLDRD_DEV_INT(name, dflt) (dflt)
-#endif
+// The library reads no environment variable: an inherited variable must not change what a run computes, or how.
 // Kernel choices that tests flip IN PROCESS go through cldrd_set_tuning (capi.hip), never through the environment.
 extern int g_cldrd_tune_splitk;        // 0: heuristic, 1: never split K, n > 1: n splits (small-M NT GEMM)
 extern int g_cldrd_tune_attn_fwd2;     // 1: persistent attention forward where it applies, 0: one item per workgroup

@@ -220,7 +220,7 @@ __device__ __forceinline__ void gemm_nt_apply8(const GemmNtArgs& p, const EpiFla
 // after the last fragment read of the K loop (the patch aliases the staging buffers).
 template <int MT, int NT, int EPI>
 __device__ __forceinline__ void gemm_nt_epilogue(const GemmNtArgs& p, f32x4 (&acc)[MT][NT], int row0, int col0, int lane,
-                                                 float* patch, unsigned long long* dbg = nullptr) {
+                                                 float* patch) {
     constexpr int WCOLS = NT * 16, RS = WCOLS + 4, LPR = WCOLS / 8, RPP = 64 / LPR, NPASS = (32 + RPP - 1) / RPP;
     const EpiFlags<EPI> fl(p);
     const int frow = lane & 15, fq = lane >> 4;
@@ -231,7 +231,7 @@ __device__ __forceinline__ void gemm_nt_epilogue(const GemmNtArgs& p, f32x4 (&ac
     // behind such a region the compiler's wait-count pass must assume the path on which nothing was issued after the load, i.e. every later
     // use waits with `s_waitcnt vmcnt(0)` - and on CDNA4 vmcnt counts STORES too, so each of the 16 passes of a wave began by waiting for the
     // previous pass's stores to be acknowledged by L2 (~1 us under load; the per-column constants below were "pending" in every pass because a
-    // pass skipped by an empty exec mask does not wait for them).  tools/epi_ablate.py: 15-25 us per tile for the fused flavours against 3-4 us
+    // pass skipped by an empty exec mask does not wait for them).  Measured (profiles/r04_microbench.txt): 15-25 us per tile for the fused flavours against 3-4 us
     // for the plain one.  Now every load is unconditional on a clamped address, the arithmetic runs on all lanes, only the stores are
     // predicated (no branch around a single store), and the per-tile constants are consumed once, here, by an empty asm: one wait, in
     // dominating code.
@@ -254,7 +254,7 @@ __device__ __forceinline__ void gemm_nt_epilogue(const GemmNtArgs& p, f32x4 (&ac
     // The effective dropout seed, read ONCE: until round 4 `*p.seed_base` (a global load: the step's seed lives in device memory for the graph
     // replay) sat inside gemm_nt_apply8, behind the chunk loop's compiler barriers - reloaded in each of the 16 passes of a wave, every time
     // followed by `s_waitcnt vmcnt(0)`, which also waits for the previous pass's STORES and the next chunk's prefetches: ~1.2 us x 16 per tile
-    // (tools/epi_ablate.py: the dropout + residual flavours spent 24 us per tile in the epilogue, 20 of them here).
+    // (profiles/r04_microbench.txt: the dropout + residual flavours spent 24 us per tile in the epilogue, 20 of them here).
     unsigned long long seed_eff = 0;
     if (fl.dropout) seed_eff = p.seed_base ? p.seed + *p.seed_base : p.seed;
     if (fl.bias) asm volatile("" ::"v"(bias8[0]), "v"(bias8[1]), "v"(bias8[2]), "v"(bias8[3]), "v"(bias8[4]), "v"(bias8[5]), "v"(bias8[6]), "v"(bias8[7]));
@@ -339,9 +339,6 @@ __device__ __forceinline__ void gemm_nt_epilogue(const GemmNtArgs& p, f32x4 (&ac
             const int m = row0 + mh * 32 + r;
             gemm_nt_apply8<EPI>(p, fl, v[pass], m, nc, bias8, cres, cresh, cgp, seed_eff, lane_ok && r < 32 && m < p.M);
         }
-#ifdef CLDRD_DEV_BUILD
-        if (dbg) { const unsigned long long t = __builtin_readcyclecounter(); if (lane == 0) dbg[mh] = t; }      // tools/epi_stamps.py
-#endif
     }
 }
 
@@ -351,8 +348,7 @@ __device__ __forceinline__ void gemm_nt_epilogue(const GemmNtArgs& p, f32x4 (&ac
 // that pattern against 86-110 cycles and 5.7-7.3 TB/s for instructions that write whole row segments.  Here consecutive lanes own consecutive
 // 16-B pieces of a row: one load, one LDS read and one store per lane and pass, all of them contiguous row segments.
 template <int MT, int NT, int EPI>
-__device__ __forceinline__ void gemm_nt_epilogue_f32(const GemmNtArgs& p, f32x4 (&acc)[MT][NT], int row0, int col0, int lane, float* patch,
-                                                     unsigned long long* dbg = nullptr) {
+__device__ __forceinline__ void gemm_nt_epilogue_f32(const GemmNtArgs& p, f32x4 (&acc)[MT][NT], int row0, int col0, int lane, float* patch) {
     constexpr int WCOLS = NT * 16, RS = WCOLS + 4, LPR = WCOLS / 4, RPP = 64 / LPR, NPASS = (32 + RPP - 1) / RPP;
     const EpiFlags<EPI> fl(p);
     const int frow = lane & 15, fq = lane >> 4;
@@ -439,9 +435,6 @@ __device__ __forceinline__ void gemm_nt_epilogue_f32(const GemmNtArgs& p, f32x4 
             if (fl.residual && mh + 1 < MT / 2) prefetch_pass(mh + 1, pass);
             if (lane_ok && r < 32 && m < p.M) *(float4*)((float*)p.C + (size_t)m * p.ldc + nc) = make_float4(x[0], x[1], x[2], x[3]);
         }
-#ifdef CLDRD_DEV_BUILD
-        if (dbg) { const unsigned long long t = __builtin_readcyclecounter(); if (lane == 0) dbg[mh] = t; }      // tools/epi_stamps.py
-#endif
     }
 }
 

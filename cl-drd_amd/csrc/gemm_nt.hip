@@ -328,7 +328,7 @@ int launch_nt(const GemmNtArgs& a, hipStream_t st) {
 
 }  // namespace
 
-int cldrd_gemm_nt_ring_dispatch(const GemmNtArgs& a, int force_bn, hipStream_t st);   // gemm_nt_ring.hip
+int cldrd_gemm_nt_ring_dispatch(const GemmNtArgs& a, hipStream_t st);   // gemm_nt_ring.hip
 int cldrd_gemm_nt_ring_scan(const GemmNtArgs& a, hipStream_t st);                     // gemm_nt_ring.hip
 int cldrd_topk_scan_stream(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts, int* cand_rows,
                            float* cand_scores, int cap, int f16, hipStream_t st);   // topk.hip
@@ -469,7 +469,7 @@ extern "C" int cldrd_gemm_nt16_ws(const void* A, const void* B, void* C, int M, 
         CLDRD_CHECK(K % BK == 0, "gemm_nt: K must be a multiple of 64");
         CLDRD_CHECK(gelu_pre == nullptr || (io_f16 & 4), "gemm_nt: gelu_pre with fp16 operands needs the fp16 tape format (io_f16 = 5)");
         {
-            const int rc = cldrd_gemm_nt_ring_dispatch(a, 0, (hipStream_t)stream);      // large-M FFN forward flavours (gemm_nt_ring16.hip)
+            const int rc = cldrd_gemm_nt_ring_dispatch(a, (hipStream_t)stream);      // large-M FFN forward flavours (gemm_nt_ring16.hip)
             if (rc >= 0) return rc;
         }
         switch (epi_flavour(a)) {
@@ -493,10 +493,8 @@ extern "C" int cldrd_gemm_nt16_ws(const void* A, const void* B, void* C, int M, 
             default: return cldrd_set_error("gemm_nt: this epilogue combination is not built for the fp16 format");
         }
     }
-    // large-M shapes go to the 256-row ring kernel; development build: CLDRD_GEMM_TILE=128|192|256 forces a variant
-    const int force = CLDRD_DEV_INT("CLDRD_GEMM_TILE", 0);
-    if (force != 128) {
-        const int rc = cldrd_gemm_nt_ring_dispatch(a, force, (hipStream_t)stream);
+    {   // large-M shapes go to the 256-row ring kernel
+        const int rc = cldrd_gemm_nt_ring_dispatch(a, (hipStream_t)stream);
         if (rc >= 0) return rc;
     }
     CLDRD_CHECK(K % BK == 0, "gemm_nt: K must be a multiple of 64 for M < 1024 or N not a multiple of 192/256");
@@ -537,11 +535,11 @@ static int scan_filter_impl(const void* Q, const void* P, int nq, long long rows
     a.drop_thresh = 0; a.drop_scale = 1.0f; a.seed = 0; a.out_f32 = 0;
     a.thr = thr; a.counts = counts; a.cand_rows = cand_rows; a.cand_scores = cand_scores; a.cap = cap;
     a.in_f16 = f16 ? 1 : 0;
-    if (!tiled && !CLDRD_DEV_INT("CLDRD_SCAN_GEMM", 0)) {          // development build: 1 forces the tiled-GEMM scan (A/B experiments)
+    if (!tiled) {
         const int rc = cldrd_topk_scan_stream(Q, P, nq, rows, d, thr, counts, cand_rows, cand_scores, cap, f16, (hipStream_t)stream);
         if (rc >= 0) return rc;
     }
-    if (rows >= 4096 && nq <= 128 && CLDRD_DEV_INT("CLDRD_GEMM_TILE", 0) != 128 && (double)rows * d * 2.0 < 4.0e9) {
+    if (rows >= 4096 && nq <= 128 && (double)rows * d * 2.0 < 4.0e9) {
         // large shard: index rows are the M dimension of the 256-row ring kernel, the (<= 128) queries its N tile
         a.A = (const bf16_t*)P; a.B = (const bf16_t*)Q; a.M = (int)rows; a.N = nq;
         return cldrd_gemm_nt_ring_scan(a, (hipStream_t)stream);

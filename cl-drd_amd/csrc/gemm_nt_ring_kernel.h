@@ -31,21 +31,14 @@ constexpr int ring_lds_bytes() {
     return na * A_BYTES + nslot * b;
 }
 
-// ABL != 0: timing experiments only (tools/gemm_ablate.py; results are wrong): 1 no s_barrier, 2 no LDS-DMA inside the K loop,
-// 3 neither (and no vmcnt waits), 4 no fragment reads inside the K loop, 6 DMA issued but never waited for, 7 no epilogue (one
-// conditional store keeps the accumulators alive), 8 epilogue of every tile written to the output's first tile (no HBM write stream).
-// Measured at M = 32768, N = 768, K = 3072 (us): full 144 | 1: 139-144 | 2: 118 | 3: 112 | 4: 145 | 6: 140 -> the fragment reads are
-// free, barrier + waits cost ~4 %, the ISSUE of the LDS-DMA pieces ~16 % (spreading them one per MFMA row was worse: 157).
+// Where the K loop's time goes, measured at M = 32768, N = 768, K = 3072 by taking parts out (profiles/r01_microbench.txt; us): full 144 | no
+// s_barrier 139-144 | no LDS-DMA inside the K loop 118 | neither, no vmcnt waits 112 | no fragment reads 145 | DMA issued, never waited for 140
+// -> the fragment reads are free, barrier + waits cost ~4 %, the ISSUE of the LDS-DMA pieces ~16 % (spreading them one per MFMA row was worse: 157).
 // Tried in round 3 and dropped (profiles/r03_microbench.txt): the same wave tile in 128-row workgroups of 4 waves with 80 KiB of LDS, two of
 // them per CU, so that one runs its K loop while the other is in its epilogue (21 % of this kernel's time at K = 768).  Each then stages
 // its own B tile (40 instead of 28 KiB of LDS-DMA per 128 rows and K tile) and that costs more than the overlap returns: -14 % (QKV) to
 // -20 % (FFN1) at K = 768, -4..-8 % at K = 2304 / 3072, -2.7 % on the training step.
-#ifdef CLDRD_DEV_BUILD
-// ABL == 10 (tools/epi_stamps.py): wave 0 of the first 1024 workgroups leaves cycle-counter stamps: [0] kernel entry, [1] first K tile landed,
-// [2] K loop done, [3] epilogue barrier passed, [4..7] after each 32-row chunk of its epilogue
-__device__ unsigned long long g_ring_stamps[1024 * 8];
-#endif
-template <int BN, int EPI, int ABL = 0>
+template <int BN, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int B_BYTES = BN * BK * 2;
@@ -64,14 +57,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     constexpr int BRING = NA_MAX * A_BYTES;  // byte offset of the B ring
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef CLDRD_DEV_BUILD
-    unsigned long long* stamps = (ABL == 10 && blockIdx.x < 1024 && wid == 0) ? g_ring_stamps + blockIdx.x * 8 : nullptr;
-    auto stamp = [&](int k) { if (ABL == 10) { const unsigned long long t = __builtin_readcyclecounter(); if (stamps && lane == 0) stamps[k] = t; } };
-#else
-    auto stamp = [&](int) {};
-    unsigned long long* stamps = nullptr;
-#endif
-    stamp(0);
     if (p.phase_units > 0 && blockIdx.x < 256 && ((blockIdx.x >> 3) & 1)) {
         // first round of tiles only (later rounds inherit their CU's phase): every second workgroup of an XCD starts `phase_units` of the
         // s_memtime counter late (1 unit = 0.064 us), so that half of the chip is in its K loop while the other half is in its epilogue
@@ -173,25 +158,16 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
         if (sync) {
             // K tile kt+1 must have landed; what may stay in flight are the requests for later K tiles, which are the YOUNGEST ones of this
             // wave (recycle() order): with three slots each K tile kt+2 (G pieces), with the third A slot A(kt+2) (4 pieces)
-            if (ABL == 3 || ABL == 6) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            else if (NSLOT == 3 && kt + 2 < nk_) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
+            if (NSLOT == 3 && kt + 2 < nk_) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
             else if (NSLOT == 2 && na_ == 3 && kt + 2 < nk_) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            if (ABL != 1 && ABL != 3) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if (ABL != 2 && ABL != 3 && !late_wave) recycle(slot, slotB, kt);      // slots of K tile kt: its fragments are in registers everywhere
+            if (!late_wave) recycle(slot, slotB, kt);      // slots of K tile kt: its fragments are in registers everywhere
             __builtin_amdgcn_sched_barrier(0);
-        } else if (ABL != 2 && ABL != 3 && late_wave && slot >= 0) {
+        } else if (late_wave && slot >= 0) {
             recycle(slot, slotB, kt);                       // slots of the previous K tile, freed at its barrier
             __builtin_amdgcn_sched_barrier(0);
-        }
-        if (ABL == 4) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) bn[t] = bc[t];
-#pragma unroll
-            for (int mt = 2; mt < 8; ++mt) mfma_row(mt, bc);
-            __builtin_amdgcn_sched_barrier(0);
-            return;
         }
         af[0] = *(const bf16x8*)(na);
         af[1] = *(const bf16x8*)(na + 16 * 128);
@@ -237,7 +213,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    stamp(1);
     if (NSLOT == 3) { if (nk_ > 2) { stageB(2, 2); stageA(2, 2); } } else { if (nk_ > 1 && !early1) { stageB(1, 1); stageA(1, 1); } }
 #pragma unroll
     for (int t = 0; t < NT; ++t) b0[t] = *(const bf16x8*)(smem + b_off[0] + t * 16 * 128);
@@ -264,113 +239,18 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     if constexpr ((EPI & EPI_FILTER) != 0 && EPI != EPI_GENERIC) {
         gemm_nt_filter_epilogue_cols<8, NT>(p, acc, m0 + wm * 128, n0 + wn * WN, lane);
     } else {
-        stamp(2);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();     // last K tile fully consumed by every wave: the slots become epilogue scratch
         asm volatile("" ::: "memory");
-        stamp(3);
-        if constexpr (ABL == 10) {
-            if constexpr (epi_is_f32_only<EPI>()) gemm_nt_epilogue_f32<8, NT, EPI>(p, acc, m0 + wm * 128, n0 + wn * WN, lane, (float*)smem + wid * (32 * (WN + 4)), stamps ? stamps + 4 : nullptr);
-            else gemm_nt_epilogue<8, NT, EPI>(p, acc, m0 + wm * 128, n0 + wn * WN, lane, (float*)smem + wid * (32 * (WN + 4)), stamps ? stamps + 4 : nullptr);
-            return;
-        }
-        if constexpr (ABL == 7) {
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) s += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-            if (s == 123.456f) ((bf16_t*)p.C)[threadIdx.x] = 0;
-            return;
-        }
-        if constexpr (ABL == 8) {
-            gemm_nt_epilogue<8, NT, EPI>(p, acc, wm * 128, wn * WN, lane, (float*)smem + wid * (32 * (WN + 4)));
-            return;
-        }
-        if constexpr (ABL == 11) {      // every CU stores to (and reads the epilogue operands of) a place of its own: tile index folded onto the first 256 -> no HBM streaming beyond the first round, no shared lines
-            const int tf = tile & 255;
-            gemm_nt_epilogue<8, NT, EPI>(p, acc, (tf & 127) * BM + wm * 128, (tf >> 7) * BN + wn * WN, lane, (float*)smem + wid * (32 * (WN + 4)));
-            return;
-        }
-        if constexpr (ABL == 9) {       // the tile's own columns, M panel folded onto the first four: a cache-resident footprint without same-line conflicts
-            gemm_nt_epilogue<8, NT, EPI>(p, acc, (mt_ & 3) * BM + wm * 128, n0 + wn * WN, lane, (float*)smem + wid * (32 * (WN + 4)));
-            return;
-        }
         if constexpr (epi_is_f32_only<EPI>()) gemm_nt_epilogue_f32<8, NT, EPI>(p, acc, m0 + wm * 128, n0 + wn * WN, lane, (float*)smem + wid * (32 * (WN + 4)));
         else gemm_nt_epilogue<8, NT, EPI>(p, acc, m0 + wm * 128, n0 + wn * WN, lane, (float*)smem + wid * (32 * (WN + 4)));
     }
 }
 
-#ifdef CLDRD_DEV_BUILD
-extern "C" unsigned long long g_dev_stamps_host[1024 * 8];      // capi.hip (dev build): the last stamped launch's stamps, read with cldrd_dev_stamps()
-#endif
-template <int BN, int ABL>
-int launch_ring_abl(const GemmNtArgs& a, hipStream_t st) {
-    constexpr int lds = ring_lds_bytes<BN>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, 0, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    const int nblk = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    hipLaunchKernelGGL((gemm_nt_ring_kernel<BN, 0, ABL>), dim3(nblk), dim3(512), lds, st, a);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
 
 template <int BN, int EPI>
 int launch_ring_epi(const GemmNtArgs& a, hipStream_t st) {
-#ifdef CLDRD_DEV_BUILD                                 // timing-only ablations (WRONG results): development build only, never in the product library
-    if (EPI == 0 && BN == 192) {                       // ablations exist for the plain BN = 192 instance only
-        switch (cldrd_dev_int("CLDRD_GEMM_ABLATE", 0)) {
-            case 1: return launch_ring_abl<192, 1>(a, st);
-            case 2: return launch_ring_abl<192, 2>(a, st);
-            case 3: return launch_ring_abl<192, 3>(a, st);
-            case 4: return launch_ring_abl<192, 4>(a, st);
-            case 6: return launch_ring_abl<192, 6>(a, st);
-            case 7: return launch_ring_abl<192, 7>(a, st);
-            case 8: return launch_ring_abl<192, 8>(a, st);
-            default: break;
-        }
-    }
-#endif
     constexpr int lds = ring_lds_bytes<BN>();
-#ifdef CLDRD_DEV_BUILD
-    if constexpr (EPI != 0 && (EPI & EPI_FILTER) == 0 && EPI != EPI_GENERIC) {      // the epilogue ablations (7: none, 8: no HBM streams) for every fused flavour: tools/epi_ablate.py
-        const int abl = cldrd_dev_int("CLDRD_GEMM_ABLATE_EPI", 0);
-        if (abl == 10) {
-            static bool attr10 = false;
-            if (!attr10) { (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, EPI, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr10 = true; }
-            const int nb = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-            hipLaunchKernelGGL((gemm_nt_ring_kernel<BN, EPI, 10>), dim3(nb), dim3(512), lds, st, a);
-            CLDRD_LAUNCH_CHECK();
-            return hipMemcpyFromSymbolAsync(g_dev_stamps_host, HIP_SYMBOL(g_ring_stamps), sizeof(unsigned long long) * 1024 * 8, 0, hipMemcpyDeviceToHost, st) == hipSuccess ? 0 : 1;
-        }
-        if (abl == 11) {
-            static bool attr11 = false;
-            if (!attr11) { (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, EPI, 11>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr11 = true; }
-            const int nb = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-            hipLaunchKernelGGL((gemm_nt_ring_kernel<BN, EPI, 11>), dim3(nb), dim3(512), lds, st, a);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
-        if (abl == 7 || abl == 8 || abl == 9) {
-            static bool attr7 = false;
-            if (!attr7) {
-                (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, EPI, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, EPI, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, EPI, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                attr7 = true;
-            }
-            const int nb = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-            if (abl == 7) hipLaunchKernelGGL((gemm_nt_ring_kernel<BN, EPI, 7>), dim3(nb), dim3(512), lds, st, a);
-            else if (abl == 9) hipLaunchKernelGGL((gemm_nt_ring_kernel<BN, EPI, 9>), dim3(nb), dim3(512), lds, st, a);
-            else hipLaunchKernelGGL((gemm_nt_ring_kernel<BN, EPI, 8>), dim3(nb), dim3(512), lds, st, a);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-#endif
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);

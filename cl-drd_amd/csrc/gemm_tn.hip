@@ -116,8 +116,6 @@ __device__ __forceinline__ void tn_dma16_addr(uint32_t lds_addr, const void* src
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
 }
 
-// ABL != 0 (development build only, tools/tn_ablate.py; WRONG results): 1 no LDS-DMA inside the K loop, 2 no fragment reads inside the
-// K loop, 3 no barrier and no vmcnt wait inside the K loop.
 typedef _Float16 tn_f16x8 __attribute__((ext_vector_type(8)));
 template <bool F16>
 __device__ __forceinline__ f32x4 tn_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
@@ -125,7 +123,7 @@ __device__ __forceinline__ f32x4 tn_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 // F16: the operands are fp16 (round 4: the all-fp16 training mode), same MFMA rate, same tiles
-template <int T1, int T2, int NW, int ABL = 0, bool F16 = false>
+template <int T1, int T2, int NW, bool F16 = false>
 __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NBF = T2 == 192 ? 3 : 4;              // B fragments (16 n2 columns each) per wave
@@ -176,7 +174,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
         ob[i] = (uint32_t)r * (uint32_t)(ldb * 2) + (uint32_t)(c2 * 2) + (uint32_t)(chunk_pos<T2 * 2>(pos, r) * 16);
     }
     auto stage = [&](int slot, int kt) {
-        if (ABL == 1 && kt >= NSLOT) return;
         const char* pa = (const char*)A + (size_t)(kbeg + kt) * BK * lda * 2;
         const char* pb = (const char*)B + (size_t)(kbeg + kt) * BK * ldb * 2;
         if (mtail != 0 && kbeg + kt == ktotal - 1) {
@@ -243,10 +240,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
     auto sweep = [&](auto bias_tag) {
         constexpr bool WB = decltype(bias_tag)::value;
         Frag af[FA], b0[NBF], b1[NBF];
-        auto tr_issue_ = [&](auto off_tag, auto hi_tag, Frag& f, uint32_t addr) {
-            if constexpr (ABL == 2) { asm volatile("" : "+v"(f.lo), "+v"(f.hi)); }
-            else tr_issue<decltype(off_tag)::value, decltype(hi_tag)::value>(f, addr);
-        };
         auto mfma_row = [&](int t1, Frag (&bc)[NBF]) {
             const bf16x8 a = frag8(af[t1]);
 #pragma unroll
@@ -259,10 +252,9 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
         // tile's slot must be back before the slot is handed to the DMA: lgkmcnt(0) covers the compiler's reads, which are all issued
         // above this point (sched_barrier).
         auto sync_and_recycle = [&](int slot, int kt) {
-            if (ABL == 3) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            else if (NSLOT == 3 && kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
+            if (NSLOT == 3 && kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            if (ABL != 3) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (!late_wave && kt + NSLOT < nk) stage(slot, kt + NSLOT);  // slot of K tile kt: every wave holds its fragments in registers
             __builtin_amdgcn_sched_barrier(0);
@@ -280,15 +272,15 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
                 stage(slot, kt + NSLOT);                       // postponed from the previous K tile's barrier (see gemm_nt_ring.hip)
                 __builtin_amdgcn_sched_barrier(0);
             }
-            tr_issue_(std::integral_constant<int, OA>{}, std::integral_constant<int, 4 * T1 * 2>{}, af[0], ra[0] + noff);
+            tr_issue<OA, 4 * T1 * 2>(af[0], ra[0] + noff);
 #pragma unroll
-            for (int t = 0; t < NBF; ++t) tr_issue_(std::integral_constant<int, OB>{}, std::integral_constant<int, 4 * T2 * 2>{}, bn[t], rb[t] + noff);
+            for (int t = 0; t < NBF; ++t) tr_issue<OB, 4 * T2 * 2>(bn[t], rb[t] + noff);
 #pragma unroll
             for (int t1 = 1; t1 < FA; ++t1) {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_row(t1, bc);
                 __builtin_amdgcn_sched_barrier(0);
-                tr_issue_(std::integral_constant<int, OA>{}, std::integral_constant<int, 4 * T1 * 2>{}, af[t1], ra[t1] + noff);
+                tr_issue<OA, 4 * T1 * 2>(af[t1], ra[t1] + noff);
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -307,27 +299,27 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
                 stage(slot, kt + NSLOT);                       // postponed from the previous K tile's barrier (see gemm_nt_ring.hip)
                 __builtin_amdgcn_sched_barrier(0);
             }
-            tr_issue_(std::integral_constant<int, COA>{}, std::integral_constant<int, 4 * T1 * 2>{}, af[4], ra[4] + coff);
+            tr_issue<COA, 4 * T1 * 2>(af[4], ra[4] + coff);
 #pragma unroll
             for (int t1 = 1; t1 < 4; ++t1) {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_row(t1, bc);
                 __builtin_amdgcn_sched_barrier(0);
-                tr_issue_(std::integral_constant<int, COA>{}, std::integral_constant<int, 4 * T1 * 2>{}, af[t1 + 4], ra[t1 + 4] + coff);
+                tr_issue<COA, 4 * T1 * 2>(af[t1 + 4], ra[t1 + 4] + coff);
             }
             __builtin_amdgcn_sched_barrier(0);
             mfma_row(4, bc);
             __builtin_amdgcn_sched_barrier(0);
             if (sync) sync_and_recycle(slot, kt);
 #pragma unroll
-            for (int t = 0; t < NBF; ++t) tr_issue_(std::integral_constant<int, NOB>{}, std::integral_constant<int, 4 * T2 * 2>{}, bn[t], rb[t] + noff);
-            tr_issue_(std::integral_constant<int, NOA>{}, std::integral_constant<int, 4 * T1 * 2>{}, af[0], ra[0] + noff);
+            for (int t = 0; t < NBF; ++t) tr_issue<NOB, 4 * T2 * 2>(bn[t], rb[t] + noff);
+            tr_issue<NOA, 4 * T1 * 2>(af[0], ra[0] + noff);
 #pragma unroll
             for (int t1 = 5; t1 < 8; ++t1) {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_row(t1, bc);
                 __builtin_amdgcn_sched_barrier(0);
-                tr_issue_(std::integral_constant<int, NOA>{}, std::integral_constant<int, 4 * T1 * 2>{}, af[t1 - 4], ra[t1 - 4] + noff);
+                tr_issue<NOA, 4 * T1 * 2>(af[t1 - 4], ra[t1 - 4] + noff);
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -481,13 +473,12 @@ __global__ __launch_bounds__(256) void reduce_slabs_group_kernel(TnGroupArgs ga)
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 struct WgradTile { int t1, t2; };
+constexpr int WGRAD_MAXK = 256;      // longest item in K tiles: the drift cap, see wgrad_splits_group
 
 // One tile shape per launch: 256 x 192 (8 waves of 128 x 48: 7 LDS-DMA pieces per 48 MFMAs per wave, the ratio of the NT kernel's
 // BN = 192) when every problem allows it, else 256 x 128 (8 waves of 64 x 64), else 128 x 128 (4 waves).  The 256 x 256 tile of
 // round 1 (all 256 VGPRs, spills, two LDS slots: 430-480 TF/s against 690-810) came back in round 4 without the spills (below).
-// CLDRD_WGRAD_TILE=128|192|256 forces one (development build).
 static WgradTile wgrad_tile_group(const int* N1, const int* N2, int n) {
-    const int force = CLDRD_DEV_INT("CLDRD_WGRAD_TILE", 0);
     bool ok192 = true, ok128w = true;
     for (int i = 0; i < n; ++i) {
         ok192 = ok192 && N1[i] % 256 == 0 && N2[i] % 192 == 0;
@@ -497,11 +488,11 @@ static WgradTile wgrad_tile_group(const int* N1, const int* N2, int n) {
     for (int i = 0; i < n; ++i) ok256 = ok256 && N1[i] % 256 == 0 && N2[i] % 256 == 0;
     // Round 4: 256 x 256 (8 waves of 128 x 64; 256 VGPRs, no spills with the rewritten K sweep, two 64-KiB LDS slots) for GROUPS: 8 LDS-DMA
     // pieces per 64 MFMAs per wave instead of 7 per 48, and the passage tower's three-layer group becomes 324 tiles instead of 432.  Alone per
-    // problem it is +3..7 % on the FFN shapes, -2 % on QKV, -14 % at 4096^3 (tools/tn_ablate.py); in the step 11.70 -> 11.44 and 11.67 ->
+    // problem it is +3..7 % on the FFN shapes, -2 % on QKV, -14 % at 4096^3; in the step 11.70 -> 11.44 and 11.67 ->
     // 11.48 ms (profiles/r04_microbench.txt).  Single problems keep the measured per-shape choice below.
-    if (ok256 && force != 192 && force != 128 && (force == 256 || n > 1)) return {256, 256};
-    if (ok192 && force != 128 && (force == 192 || !ok128w || n > 1)) return {256, 192};
-    if (ok192 && force != 128) {
+    if (ok256 && n > 1) return {256, 256};
+    if (ok192 && (!ok128w || n > 1)) return {256, 192};
+    if (ok192) {
         // single problem: small outputs stay on 256 x 128 (measured at T = 32768: 768 x 768 -7 % on 256 x 192, the others +3..10 %)
         if ((N1[0] / 256) * (N2[0] / 192) >= 24) return {256, 192};
     }
@@ -526,16 +517,11 @@ static int wgrad_splits_group(const int* M, const int* N1, const int* N2, int n,
     }
     if (tiles_all <= 0) return 1;
     const int overhead = 6;
-    const int force = CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS", 0);
-    if (force > 0) return force < ktotal ? force : ktotal;
-    const int force_big = CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS_BIG", 0);          // long sweeps only (the passage tower's group)
-    if (force_big > 0 && ktotal >= 256) return force_big;
     // Workgroups of one XCD share A / B panels through its 4-MiB L2 only while they sweep the same token range at about the same
     // time; nothing synchronises them, so over a long sweep they drift apart and every one of them streams its operands from HBM
     // (measured at cfg2: 512 K tiles per item, no split: 3.2 ms for the passage tower's group; 2 splits of 256: 2.9 ms + 0.1 ms of
-    // slabs).  Items are therefore capped at MAXK K tiles.
-    const int maxk = CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256) < 1 ? 256 : CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256);
-    const int sp_min = (ktotal + maxk - 1) / maxk;
+    // slabs).  Items are therefore capped at WGRAD_MAXK K tiles.
+    const int sp_min = (ktotal + WGRAD_MAXK - 1) / WGRAD_MAXK;
     int best = sp_min;
     double best_cost = -1.0;
     for (int sp = sp_min; sp <= 64 && sp <= ktotal; ++sp) {
@@ -632,18 +618,16 @@ static WgradPlan wgrad_plan_search(const int* M, const int* N1, const int* N2, i
     WgradPlan best;
     int ktotal = 1;
     for (int i = 0; i < n; ++i) ktotal = std::max(ktotal, wgrad_ktiles(M[i]));
-    const int force = force_uniform > 0 ? force_uniform : CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS", 0);
-    // one problem keeps the rule (and the bits) it had; CLDRD_WGRAD_PLAN=0 (development build): every group does
-    if (force > 0 || n == 1 || CLDRD_DEV_INT("CLDRD_WGRAD_PLAN", 1) == 0) {
-        wgrad_plan_uniform(M, n, force > 0 ? std::min(force, ktotal) : wgrad_splits_group(M, N1, N2, n, t), false, best);
+    // one problem keeps the rule (and the bits) it had
+    if (force_uniform > 0 || n == 1) {
+        wgrad_plan_uniform(M, n, force_uniform > 0 ? std::min(force_uniform, ktotal) : wgrad_splits_group(M, N1, N2, n, t), false, best);
         wgrad_plan_score(M, N1, N2, n, t, best);
         return best;
     }
-    const int maxk = CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256) < 1 ? 256 : CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256);      // the drift cap, see wgrad_splits_group
     // A plan must also replay no longer than the best of the uniform counts up to 8 does (slab bytes aside): that one is always eligible.
     WgradPlan c;
     double span_cap = -1.0;
-    for (int sp = (ktotal + maxk - 1) / maxk; sp <= 8 && sp <= ktotal; ++sp) {
+    for (int sp = (ktotal + WGRAD_MAXK - 1) / WGRAD_MAXK; sp <= 8 && sp <= ktotal; ++sp) {
         wgrad_plan_uniform(M, n, sp, true, c);
         wgrad_plan_score(M, N1, N2, n, t, c);
         if (span_cap < 0.0 || c.makespan < span_cap) span_cap = c.makespan;
@@ -654,14 +638,13 @@ static WgradPlan wgrad_plan_search(const int* M, const int* N1, const int* N2, i
         if (span_cap >= 0.0 && c.makespan > span_cap + 1e-9) return;
         if (!have || c.cost < best.cost - 1e-9) { best = c; have = true; }
     };
-    for (int sp = (ktotal + maxk - 1) / maxk; sp <= 64 && sp <= ktotal; ++sp) {
+    for (int sp = (ktotal + WGRAD_MAXK - 1) / WGRAD_MAXK; sp <= 64 && sp <= ktotal; ++sp) {
         wgrad_plan_uniform(M, n, sp, true, c);
         consider(c);
     }
     static const int c_longs[] = {256, 171, 128}, c_shorts[] = {32, 64, 128};
     static const double shares[] = {0.0, 1.0 / 16, 1.0 / 8, 3.0 / 16, 1.0 / 4, 3.0 / 8, 1.0 / 2};
     for (int cl : c_longs) {
-        if (cl > maxk) continue;
         for (int cs : c_shorts) {
             if (cs >= cl) continue;
             // long ranges of a problem: ceil(kt / cl); problems of at most cs K tiles are one short item.  `want` of all (tile, range)
@@ -702,12 +685,11 @@ static WgradPlan wgrad_plan_search(const int* M, const int* N1, const int* N2, i
     return best;
 }
 
-// the search is repeated for every launch of an eager step: remember the last few answers (shapes, tile and knobs are the key)
+// the search is repeated for every launch of an eager step: remember the last few answers (shapes, tile and the forced split count are the key)
 static WgradPlan wgrad_plan_group(const int* M, const int* N1, const int* N2, int n, WgradTile t, int force_uniform = 0) {
     struct Entry { std::vector<int> key; WgradPlan plan; };
     thread_local std::vector<Entry> cache;
-    std::vector<int> key = {n, t.t1, t.t2, force_uniform, CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS", 0), CLDRD_DEV_INT("CLDRD_WGRAD_SPLITS_BIG", 0),
-                            CLDRD_DEV_INT("CLDRD_WGRAD_PLAN", 1), CLDRD_DEV_INT("CLDRD_WGRAD_MAXK", 256)};
+    std::vector<int> key = {n, t.t1, t.t2, force_uniform};
     for (int i = 0; i < n; ++i) { key.push_back(M[i]); key.push_back(N1[i]); key.push_back(N2[i]); }
     for (const Entry& e : cache)
         if (e.key == key) return e.plan;
@@ -749,18 +731,16 @@ extern "C" int cldrd_wgrad_splits(int M, int N1, int N2) {
     return wgrad_splits_group(&M, &N1, &N2, 1, wgrad_tile_group(&N1, &N2, 1));
 }
 
-static inline int wgrad_stagger() { return CLDRD_DEV_INT("CLDRD_WGRAD_STAGGER", 1); }
-
-template <int T1, int T2, int NW, int ABL = 0, bool F16 = false>
+template <int T1, int T2, int NW, bool F16 = false>
 static int launch_tn_group(const TnGroupArgs& g, int items, hipStream_t st) {
     constexpr int slot = BK * (T1 + T2) * 2;
     constexpr int lds = (3 * slot <= 160 * 1024 ? 3 : 2) * slot;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T1, T2, NW, ABL, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T1, T2, NW, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
-    hipLaunchKernelGGL((gemm_tn_kernel<T1, T2, NW, ABL, F16>), dim3(items), dim3(64 * NW), lds, st, g);
+    hipLaunchKernelGGL((gemm_tn_kernel<T1, T2, NW, F16>), dim3(items), dim3(64 * NW), lds, st, g);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
@@ -801,13 +781,12 @@ extern "C" int cldrd_wgrad_group(const void* const* A, const void* const* B, flo
     CLDRD_CHECK(!(t.t2 != 192 && any128), "wgrad_group: problems with N2 % 128 != 0 need every problem to fit the 256 x 192 tile");
     const size_t need = cldrd_wgrad_group_workspace(M, N1, N2, n);
     CLDRD_CHECK(need == 0 || (workspace != nullptr && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= need * sizeof(float)), "wgrad: workspace too small");
-    const int env_order = CLDRD_DEV_INT("CLDRD_WGRAD_ORDER", -1);       // tile order per problem (below); development build: 0 / 1 force n2- / n1-fastest
     size_t slab_off = 0;
     for (int lo = 0; lo < n; lo += MAXP) {
         const int m = n - lo < MAXP ? n - lo : MAXP;
         const WgradPlan pl = wgrad_plan_group(M + lo, N1 + lo, N2 + lo, m, t);
         TnGroupArgs g;
-        g.n = m; g.items_long = pl.items_long; g.accumulate = accumulate & 1; g.stagger = wgrad_stagger(); g.slabs = workspace;
+        g.n = m; g.items_long = pl.items_long; g.accumulate = accumulate & 1; g.stagger = 1; g.slabs = workspace;
         g.inv_scale = g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr;
         g.sq_out = nullptr;
         int first[2] = {0, 0};
@@ -822,7 +801,7 @@ extern "C" int cldrd_wgrad_group(const void* const* A, const void* const* B, flo
             // L2.  With n2 fastest they cover (32 / nt2) A panels x all nt2 B panels: fine while nt2 is small (QKV, FFN1: nt2 = 4).  FFN2 has
             // 3 n1 tiles x 16 n2 tiles: n2 fastest covers 2 of the 3 rows, so every panel of h (the 200-MB operand) is fetched by 2 concurrent
             // tiles now and again by the third row later; n1 fastest puts all 3 tiles of an h panel side by side: h streams from HBM once.
-            P.n1_fast = (env_order == 1 || (env_order < 0 && P.nt2 > P.nt1 && P.nt1 <= 32)) ? 1 : 0;
+            P.n1_fast = (P.nt2 > P.nt1 && P.nt1 <= 32) ? 1 : 0;
             P.first[0] = first[0]; P.first[1] = first[1];
             P.clen[0] = pl.p[i].c_long; P.clen[1] = pl.p[i].c_short;
             P.n_long = pl.p[i].n_long; P.chunks = wgrad_chunks(pl.p[i]);
@@ -832,22 +811,12 @@ extern "C" int cldrd_wgrad_group(const void* const* A, const void* const* B, flo
         }
         const int items = first[0] + first[1];
         int rc;
-#ifdef CLDRD_DEV_BUILD                                 // timing-only ablations (WRONG results): development build only
-        const int abl = cldrd_dev_int("CLDRD_TN_ABLATE", 0);
-        if (abl && t.t1 == 256 && t.t2 == 192) {
-            rc = abl == 1 ? launch_tn_group<256, 192, 8, 1>(g, items, st) : abl == 2 ? launch_tn_group<256, 192, 8, 2>(g, items, st)
-                                                                                      : launch_tn_group<256, 192, 8, 3>(g, items, st);
-        } else if (abl && t.t1 == 256) {
-            rc = abl == 1 ? launch_tn_group<256, 128, 8, 1>(g, items, st) : abl == 2 ? launch_tn_group<256, 128, 8, 2>(g, items, st)
-                                                                                      : launch_tn_group<256, 128, 8, 3>(g, items, st);
-        } else
-#endif
         if (t.t2 == 256) {
-            rc = (accumulate & 2) ? launch_tn_group<256, 256, 8, 0, true>(g, items, st) : launch_tn_group<256, 256, 8>(g, items, st);
+            rc = (accumulate & 2) ? launch_tn_group<256, 256, 8, true>(g, items, st) : launch_tn_group<256, 256, 8>(g, items, st);
         } else if (accumulate & 2) {             // bit 1 of `accumulate`: fp16 operands
-            if (t.t1 == 256 && t.t2 == 192) rc = launch_tn_group<256, 192, 8, 0, true>(g, items, st);
-            else if (t.t1 == 256) rc = launch_tn_group<256, 128, 8, 0, true>(g, items, st);
-            else rc = launch_tn_group<128, 128, 4, 0, true>(g, items, st);
+            if (t.t1 == 256 && t.t2 == 192) rc = launch_tn_group<256, 192, 8, true>(g, items, st);
+            else if (t.t1 == 256) rc = launch_tn_group<256, 128, 8, true>(g, items, st);
+            else rc = launch_tn_group<128, 128, 4, true>(g, items, st);
         } else if (t.t1 == 256 && t.t2 == 192) rc = launch_tn_group<256, 192, 8>(g, items, st);
         else if (t.t1 == 256) rc = launch_tn_group<256, 128, 8>(g, items, st);
         else rc = launch_tn_group<128, 128, 4>(g, items, st);

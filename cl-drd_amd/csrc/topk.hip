@@ -542,7 +542,7 @@ __device__ __forceinline__ f32x4 mfma16_bq(bf16x8 a, bf16x8 bq_agpr, f32x4 c) {
 }
 __device__ __forceinline__ void mfma_result_fence() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory"); }
 
-template <int KS, int ablate, bool F16, int NW = 8, int NQS = 1>     // d = 32 * KS; ablate != 0: timing experiments only (tools/scan_bench.py); F16: fp16 shadow
+template <int KS, bool F16, int NW = 8, int NQS = 1>     // d = 32 * KS; F16: fp16 shadow
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void scan_stream_kernel(const bf16_t* __restrict__ P, const bf16_t* __restrict__ Q, int nq,
                                                               long long rows, const float* __restrict__ thr,
                                                               int* __restrict__ counts, int* __restrict__ cand_rows,
@@ -629,7 +629,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void scan_stream_kernel(c
     // Move the LDS hit list to the per-query candidate lists: one global atomic per (block, query) reserves the block's range in
     // that query's list (per-hit atomics on 128 addresses serialise in L2).  Called by the whole workgroup (barriers inside).
     auto flush = [&]() {
-        if (ablate == 4) { wcnt = 0; return; }                                                          // timing experiment: hits vanish
         for (int i = threadIdx.x; i < 2 * NQ; i += blockDim.x) qcnt[i] = 0;
         if (lane == 0) lcount[wid] = wcnt;
         __syncthreads();
@@ -638,7 +637,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void scan_stream_kernel(c
             if (live(e)) lq[e] |= atomicAdd(qcnt + lq[e], 1) << 8;                                      // rank inside the block
         __syncthreads();
         for (int i = threadIdx.x; i < NQ; i += blockDim.x)
-            if (qcnt[i] > 0) qcnt[NQ + i] = ablate == 3 ? 0 : atomicAdd(counts + i, qcnt[i]);         // ablate 3: no global atomics (timing only)
+            if (qcnt[i] > 0) qcnt[NQ + i] = atomicAdd(counts + i, qcnt[i]);
         __syncthreads();
         for (int e = threadIdx.x; e < NW * WCAP; e += blockDim.x) {
             if (!live(e)) continue;
@@ -671,14 +670,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void scan_stream_kernel(c
         __builtin_amdgcn_s_barrier();                                       // ... for every wave; slot of tile t-step is free
         asm volatile("" ::: "memory");
         // Hit-list level check: `snap` was read at the top of this iteration (see there); the decision is workgroup-uniform.
-        if ((ablate == 0 || ablate >= 3) && __builtin_amdgcn_ballot_w64(snap > (uint32_t)(WCAP / 2)) != 0) flush();      // some wave's list is half full (rare)
+        if (__builtin_amdgcn_ballot_w64(snap > (uint32_t)(WCAP / 2)) != 0) flush();      // some wave's list is half full (rare)
         const int fs = cs == 0 ? NSLOT - 1 : cs - 1;                        // slot of tile t-step
         const char* sb = smem + cs * TILEB;
         cs = cs == NSLOT - 1 ? 0 : cs + 1;
-        if (ablate == 1) {                                                  // timing experiments only: DMA stream alone
-            if (t + 2 * step < ntiles) stage(fs, t + 2 * step);
-            continue;
-        }
         // Two half-row chunks of A fragments are kept in flight ahead of the MFMAs that consume them: with 2 waves per SIMD
         // nothing else hides the LDS latency (measured: reads alone and MFMAs alone both keep up with the DMA stream,
         // read -> wait -> MFMA in one chain does not).  sched_barrier pins the order, hipcc still counts the lgkmcnt waits.
@@ -698,7 +693,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void scan_stream_kernel(c
             }
         };
         auto emit = [&](f32x4 acc, int mt, int qn, float thr_q) {        // acc[j] = <P[row], Q[qn]> with row = 32 t + 16 mt + 4 (lane >> 4) + j
-            if (ablate == 2) { asm volatile("" ::"v"(acc)); return; }
             const int row0 = (int)(t * R) + mt * 16 + 4 * (lane >> 4);
             // one test for the four rows of every lane first: no hit in the whole 16 x 16 block is the common case.  Everything
             // below branches on ballots only, so the control flow - and with it wcnt - stays wave-uniform.
@@ -760,30 +754,29 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void scan_stream_kernel(c
                 for (int s = 0; s < NQS; ++s) emit(acc[s], c / NCM, qn0 + 16 * s, thr_lane[s]);
             }
         }
-        if (ablate == 0 || ablate >= 3) {           // snapshot of this wave's list length for the check two tiles on (hand-issued: see emit)
-            const uint32_t a = lcount_off + 4u * (8u + 8u * (uint32_t)(it % 3) + (uint32_t)wid);
-            if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(wcnt) : "memory");
-        }
+        // snapshot of this wave's list length for the check two tiles on (hand-issued: see emit)
+        const uint32_t snap_out = lcount_off + 4u * (8u + 8u * (uint32_t)(it % 3) + (uint32_t)wid);
+        if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(snap_out), "v"(wcnt) : "memory");
     }
     // ---- what is left in the list
     __syncthreads();
     flush();
 }
 
-template <int KS, int ABL, bool F16, int NW = 8, int NQS = 1>
-int launch_scan_stream_abl(const void* Q, const void* P, int nq, long long rows, const float* thr, int* counts, int* cand_rows,
-                           float* cand_scores, int cap, hipStream_t st) {
+template <int KS, bool F16, int NW = 8, int NQS = 1>
+int launch_scan_stream_instance(const void* Q, const void* P, int nq, long long rows, const float* thr, int* counts, int* cand_rows,
+                                float* cand_scores, int cap, hipStream_t st) {
     constexpr int tb = 3 * 32 * KS * 64, NQ = 16 * NQS * NW;
     constexpr int lcap = (160 * 1024 - tb - 128 - 8 * NQ) / 12 < 4096 ? (160 * 1024 - tb - 128 - 8 * NQ) / 12 : 4096;
     constexpr int lds = tb + 128 + 8 * NQ + lcap * 12;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)scan_stream_kernel<KS, ABL, F16, NW, NQS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute((const void*)scan_stream_kernel<KS, F16, NW, NQS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
     const long long ntiles = (rows + 31) / 32;
     const int grid = (int)(ntiles < 256 ? ntiles : 256);
-    hipLaunchKernelGGL((scan_stream_kernel<KS, ABL, F16, NW, NQS>), dim3(grid), dim3(64 * NW), lds, st, (const bf16_t*)P, (const bf16_t*)Q, nq, rows, thr,
+    hipLaunchKernelGGL((scan_stream_kernel<KS, F16, NW, NQS>), dim3(grid), dim3(64 * NW), lds, st, (const bf16_t*)P, (const bf16_t*)Q, nq, rows, thr,
                        counts, cand_rows, cand_scores, cap);
     CLDRD_LAUNCH_CHECK();
     return 0;
@@ -792,30 +785,12 @@ int launch_scan_stream_abl(const void* Q, const void* P, int nq, long long rows,
 template <int KS>
 int launch_scan_stream(const void* Q, const void* P, int nq, long long rows, const float* thr, int* counts, int* cand_rows,
                        float* cand_scores, int cap, bool f16, hipStream_t st) {
-#ifdef CLDRD_DEV_BUILD                                 // timing-only ablations (WRONG results): development build only, never in the product library
-    if (KS == 24 && !f16) {                            // ablations exist for the d = 768 bf16 instance only
-        switch (cldrd_dev_int("CLDRD_SCAN_ABLATE", 0)) {
-            case 1: return launch_scan_stream_abl<24, 1, false>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
-            case 2: return launch_scan_stream_abl<24, 2, false>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
-            default: break;
-        }
-    }
-#endif
     if (nq > 128) {                                    // 129..256 queries: the 8-wave x 32-query instance (fp16 shadow, d = 768 only)
-#ifdef CLDRD_DEV_BUILD
-        if (KS == 24 && f16) {
-            switch (cldrd_dev_int("CLDRD_SCAN_ABLATE", 0)) {
-                case 3: return launch_scan_stream_abl<24, 3, true, 8, 2>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
-                case 4: return launch_scan_stream_abl<24, 4, true, 8, 2>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
-                default: break;
-            }
-        }
-#endif
-        if (KS == 24 && f16) return launch_scan_stream_abl<24, 0, true, 8, 2>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
+        if (KS == 24 && f16) return launch_scan_stream_instance<24, true, 8, 2>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
         return -1;
     }
-    if (f16) return launch_scan_stream_abl<KS, 0, true>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
-    return launch_scan_stream_abl<KS, 0, false>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
+    if (f16) return launch_scan_stream_instance<KS, true>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
+    return launch_scan_stream_instance<KS, false>(Q, P, nq, rows, thr, counts, cand_rows, cand_scores, cap, st);
 }
 
 }  // namespace

@@ -16,7 +16,7 @@ import pytest
 from conftest import ROOT  # noqa: F401
 
 BK = 64
-MAXK = 256          # the drift cap: no item sweeps more K tiles (csrc/gemm_tn.hip: CLDRD_WGRAD_MAXK)
+MAXK = 256          # the drift cap: no item sweeps more K tiles (csrc/gemm_tn.hip: WGRAD_MAXK)
 
 
 @pytest.fixture(scope="module")

@@ -1,9 +1,7 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the NT GEMM variants on the encoder shapes (interleaved rounds in one process)."""
-import os, sys, time
+"""Micro-benchmark of the NT GEMM (the product dispatch) on the encoder shapes, and of the weight gradients."""
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _devlib  # noqa: F401  (development build: the knobs below do not exist in the product library)
 import torch
 from cldrd_amd import hip_ops as ops
 
@@ -15,9 +13,8 @@ def main():
               ("ffn1", T, 3072, 768, {"bias": 1, "pre": 1, "act": 3}), ("ffn1_old", T, 3072, 768, {"bias": 1, "pre": 1, "act": 1}), ("ffn2", T, 768, 3072, {"bias": 1, "res32": 1, "drop": 1}),
               ("dgrad_ffn2", T, 3072, 768, {"gp": 1, "act": 2}), ("dgrad_ffn2_old", T, 3072, 768, {"gp": 1}), ("dgrad_ffn1", T, 768, 3072, {"res": 1}),
               ("dgrad_out", T, 768, 768, {}), ("dgrad_qkv", T, 768, 2304, {"res": 1})]
-    variants = os.environ.get("VARIANTS", "ring,ring2s").split(",")      # ring | ring2s | ring128 | ring192 | ring256
     torch.manual_seed(0)
-    tot = {v: 0.0 for v in variants}
+    tot = 0.0
     for name, M, N, K, ep in shapes:
         # ROTATE=n: n sets of (A, output, residual, ...) used in turn, so that no call finds its operands in the 256-MB Infinity Cache
         # (as in the training step, where every activation is touched once per pass); 1 = the same buffers every call
@@ -35,28 +32,19 @@ def main():
         if ep.get("gp"): kw["gelu_pre"] = torch.randn(M, N, device=dev).bfloat16()
         if ep.get("drop"): kw.update(dropout_p=0.1, seed=1234)
         kws = [kw] + [{k: (v.clone() if torch.is_tensor(v) and v.dim() == 2 else v) for k, v in kw.items()} for _ in range(rot - 1)]
-        res = {}
+        ts = []
         for rnd in range(3):
-            for v in variants:
-                os.environ["CLDRD_GEMM_ASYM"] = "0" if v == "ring2s" else "1"          # ring2s: two A slots (the round-2 K-loop schedule)
-                if v.startswith("ring") and len(v) > 4 and v != "ring2s": os.environ["CLDRD_GEMM_TILE"] = v[4:]
-                else: os.environ.pop("CLDRD_GEMM_TILE", None)
-                for i in range(2): ops.gemm_nt(As[i % rot], B, outs[i % rot], **kws[i % rot])
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for i in range(10): ops.gemm_nt(As[i % rot], B, outs[i % rot], **kws[i % rot])
-                e1.record(); torch.cuda.synchronize()
-                res.setdefault(v, []).append(e0.elapsed_time(e1) / 10)
-        fl = 2.0 * M * N * K
-        line = f"{name:11s} M={M} N={N} K={K}: "
-        for v, ts in res.items():
-            t = min(ts)
-            if not name.endswith("_old"): tot[v] += t
-            line += f" {v}: {t*1e3:7.1f} us {fl/t/1e9:7.1f} TF/s |"
-        print(line, flush=True)
-    print("layer total (8 GEMMs): " + " | ".join(f"{v}: {t*1e3:7.1f} us" for v, t in tot.items()), flush=True)
-    os.environ.pop("CLDRD_GEMM_TILE", None)
+            for i in range(2): ops.gemm_nt(As[i % rot], B, outs[i % rot], **kws[i % rot])
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(10): ops.gemm_nt(As[i % rot], B, outs[i % rot], **kws[i % rot])
+            e1.record(); torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / 10)
+        t = min(ts)
+        if not name.endswith("_old"): tot += t
+        print(f"{name:11s} M={M} N={N} K={K}: {t*1e3:7.1f} us {2.0*M*N*K/t/1e9:7.1f} TF/s", flush=True)
+    print(f"layer total (8 GEMMs): {tot*1e3:7.1f} us", flush=True)
     # weight gradients: dW[N1,N2] = dY[T,N1]^T X[T,N2] (+ bias gradient), split-K slabs + reduction included
     for name, N1, N2 in [("w_qkv", 2304, 768), ("w_out", 768, 768), ("w_ffn1", 3072, 768), ("w_ffn2", 768, 3072)]:
         dY = (torch.randn(T, N1, device=dev) * 0.02).bfloat16()
