@@ -5,9 +5,11 @@
 // that scan would be matrix-bound.  Here the scan reads a bf16 shadow of the index (half the HBM bytes, bf16 MFMA) and
 // keeps only candidates above a per-query threshold (filter epilogue of the NT GEMM, gemm_nt.hip); the candidates are
 // re-scored in exact fp32 from the fp32 rows, sorted (score desc, row asc) and cut to k.  Exactness is PROVEN per
-// batch on the host: |scan - exact| <= eps_q = 2^-8 |q| max|p|, so if thr_q <= (k-th exact candidate score) - eps_q no
-// row outside the candidate list can belong to the top-k (retriever/retrieval_utils.py docstring); otherwise the host
-// lowers the threshold and rescans.
+// query on the device: |scan - exact| <= eps_q (thresholds_kernel: the fp16 rounding of both operands, 2^-10 |q| max|p - mu|,
+// plus the fp32 accumulation and the values below the fp16 normal range), so when the candidate list is complete down to
+// t^_q - 2 eps_q (t^_q = k-th largest scan score; select_compact_kernel) no row outside it can belong to the top-k;
+// otherwise a status bit tells the host, which corrects the threshold and rescans (retriever/retrieval_utils.py docstring).
+// The premise is MEASURED on corpora built to spend the bound (tests/test_gpu_search_proof.py, profiles/search_proof_ratios.txt).
 //
 // Kernels here: per-query k-th largest of the sample scores (threshold estimate, radix select), fp32 re-score,
 // bitonic sort + cut, max row norm; and the fp16-row mode's re-score from the centred fp16 rows (an index without fp32 rows).
