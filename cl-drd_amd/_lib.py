@@ -6,9 +6,11 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# CLDRD_LIB selects another BUILD of the library (e.g. the parent commit's, for A/B runs); the library itself reads no environment
-# variable
+# CLDRD_LIB selects another BUILD of the library for A/B runs; it must have the ABI version this table was written for (an A/B across a
+# change of ABI_VERSION uses two checkouts).  The library itself reads no environment variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
+
+ABI_VERSION = 101          # cldrd_version() of the build SIGNATURES describes
 
 _lib = None
 
@@ -19,30 +21,18 @@ SIGNATURES = {
     "cldrd_version": (ci, []),
     "cldrd_device_ok": (ci, []),
     "cldrd_set_tuning": (ci, [C.c_char_p, ci]),
-    "cldrd_gemm_nt16": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, cf, cf, cull, ci, ci, ci, vp]),
-    "cldrd_gemm_nt16_ln": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, cf, cf, cull, ci, ci, ci, vp, vp, vp, vp, vp]),
     "cldrd_gemm_nt_splitk_workspace": (csz, [ci, ci, ci]),
-    "cldrd_gemm_nt16_ws": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, cf, cf, cull, ci, ci, ci, vp, vp, vp, vp, vp, vp, csz, vp]),
+    "cldrd_gemm_nt16": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, cf, cf, cull, ci, ci, ci, vp, vp, vp, vp, vp, vp, csz, vp]),
     "cldrd_wgrad_splits": (ci, [ci, ci, ci]),
     "cldrd_wgrad16": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, csz, ci, vp]),
     "cldrd_wgrad_group_workspace": (csz, [vp, vp, vp, ci]),
     "cldrd_wgrad_plan": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "cldrd_wgrad_group": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, csz, ci, vp]),
-    "cldrd_attention_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp]),
-    "cldrd_attention_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, vp]),
+    "cldrd_attention_fwd": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp, vp]),
+    "cldrd_attention_bwd": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp]),
+    "cldrd_attention_cls_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp]),
+    "cldrd_attention_cls_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp]),
     "cldrd_attention_bits_words": (C.c_longlong, [ci, ci, ci, cf]),
-    "cldrd_attention_fwd_bits": (ci, [vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp, vp]),
-    "cldrd_attention_bwd_bits": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, vp, vp]),
-    "cldrd_attention_bwd_x": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, vp, ci, vp]),
-    "cldrd_attention_cls_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp]),
-    "cldrd_attention_cls_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, vp]),
-    "cldrd_attention_cls_bwd_x": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp]),
-    "cldrd_attention_fwd_varlen": (ci, [vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp, vp]),
-    "cldrd_attention_bwd_varlen": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, vp, ci, vp]),
-    "cldrd_attention_fwd_varlen_list": (ci, [vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp, vp, ci, ci, vp]),
-    "cldrd_attention_bwd_varlen_list": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, vp, ci, vp, ci, ci, vp]),
-    "cldrd_attention_cls_fwd_varlen": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp]),
-    "cldrd_attention_cls_bwd_varlen": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp]),
     "cldrd_add_rows_strided": (ci, [vp, vp, ci, ci, ci, ci, vp]),
     "cldrd_ln_partial_blocks": (ci, [ci]),
     "cldrd_embed_ln_fwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp, vp]),
@@ -129,6 +119,10 @@ def load():
         raise CldrdError(f"{LIB_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
                          "cldrd_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
+    lib.cldrd_version.restype = ci
+    if lib.cldrd_version() != ABI_VERSION:
+        raise CldrdError(f"{LIB_PATH} has ABI version {lib.cldrd_version()}, this binding was written for {ABI_VERSION}: rebuild it "
+                         "(or point CLDRD_LIB at a build of the same ABI version)")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -13,6 +13,8 @@
 // query-on-lane (dQ accumulates over all key blocks).  Probabilities and dS are rounded to bf16 only as
 // MFMA operands; softmax statistics, LSE and delta are fp32.
 #include "common.h"
+#include <cstdio>
+#include <type_traits>
 
 namespace {
 
@@ -1336,71 +1338,6 @@ __global__ __launch_bounds__(512) void attn_bwd2_kernel(const bf16_t* __restrict
     }
 }
 
-int attn_num_cus();
-bool attn_fwd2_enabled(int nseq, int L, int H);
-
-template <int NKB, bool DROP>
-int launch_fwd_f16(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H, float scale, float p,
-                   unsigned long long seed, hipStream_t st, const int* cu, const int* seq_list) {      // fp16 in, fp16 out: no second copy
-    const size_t lds = 3 * 32 * NKB * RSB + 32 * NKB * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_full_kernel<NKB, DROP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((attn_fwd_full_kernel<NKB, DROP, true>), dim3(nseq * H), dim3(256), lds, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                       (bf16_t*)ctx, lse, L, H, scale, DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), (bf16_t*)nullptr, cu, seq_list);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-template <int NKB>
-int launch_fwd_h(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H, float scale, float p,
-                 unsigned long long seed, hipStream_t st, const int* cu, const int* seq_list) {
-    return p > 0.f && dropout_thresh16(p) > 0 ? launch_fwd_f16<NKB, true>(qkv, mask, ctx, lse, nseq, L, H, scale, p, seed, st, cu, seq_list)
-                                              : launch_fwd_f16<NKB, false>(qkv, mask, ctx, lse, nseq, L, H, scale, 0.f, seed, st, cu, seq_list);
-}
-
-template <int NKB, bool DROP, bool F16 = false>
-int launch_fwd_d(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H, float scale, float p,
-                 unsigned long long seed, uint32_t* bits_out, void* ctx16, hipStream_t st, const int* cu, const int* seq_list) {
-    const size_t lds = 3 * 32 * NKB * RSB + 32 * NKB * sizeof(float);
-    if constexpr (NKB <= 4) {
-        // many items: the persistent loader / compute kernel (CLDRD_ATTN_FWD2=0 keeps the one-item-per-workgroup kernel: A/B runs and tests)
-        const int nitems = nseq * H, cus = attn_num_cus();
-        if (attn_fwd2_enabled(nseq, 32 * NKB, H)) {       // (the tile height, not L: a listed launch of short sequences has L > 128)
-            const size_t lds2 = 2 * (lds + (DROP ? 32 * NKB * NKB * sizeof(uint32_t) : 0));
-            (void)hipFuncSetAttribute((const void*)attn_fwd2_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            hipLaunchKernelGGL((attn_fwd2_kernel<NKB, DROP, F16>), dim3(cus), dim3(512), lds2, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                               (bf16_t*)ctx, lse, L, H, scale, DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), nitems,
-                               bits_out, (bf16_t*)ctx16, cu, seq_list);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
-        (void)hipFuncSetAttribute((const void*)attn_fwd_full_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((attn_fwd_full_kernel<NKB, DROP, F16>), dim3(nseq * H), dim3(256), lds, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                           (bf16_t*)ctx, lse, L, H, scale, DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), (bf16_t*)ctx16, cu, seq_list);
-    } else {
-        // many items at 128 < L <= 256: the persistent streaming kernel (K / V double-buffered, Q from global memory); cldrd_set_tuning("attn_fwd2", 0)
-        // keeps the one-item-per-workgroup kernel (tests: the two are bit-identical)
-        const int nitems = nseq * H, cus = attn_num_cus();
-        if (nitems >= 2 * cus && g_cldrd_tune_attn_fwd2 != 0) {
-            const size_t lds3 = 2 * (2 * 32 * NKB * RSB + 32 * NKB * sizeof(float));
-            (void)hipFuncSetAttribute((const void*)attn_fwd3_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            hipLaunchKernelGGL((attn_fwd3_kernel<NKB, DROP, F16>), dim3(cus), dim3(512), lds3, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                               (bf16_t*)ctx, lse, L, H, scale, DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), nitems,
-                               (bf16_t*)ctx16, cu, seq_list);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((attn_fwd_kernel<NKB, DROP, F16>), dim3(nseq * H), dim3(512), lds, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                           (bf16_t*)ctx, lse, L, H, scale, DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), (bf16_t*)ctx16, cu, seq_list);
-    }
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-template <int NKB, bool F16 = false>
-int launch_fwd(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H, float scale, float p,
-               unsigned long long seed, uint32_t* bits_out, void* ctx16, hipStream_t st, const int* cu, const int* seq_list) {
-    return p > 0.f && dropout_thresh16(p) > 0 ? launch_fwd_d<NKB, true, F16>(qkv, mask, ctx, lse, nseq, L, H, scale, p, seed, bits_out, ctx16, st, cu, seq_list)
-                                              : launch_fwd_d<NKB, false, F16>(qkv, mask, ctx, lse, nseq, L, H, scale, 0.f, seed, nullptr, ctx16, st, cu, seq_list);
-}
 int attn_num_cus() {
     static int n = 0;
     if (n == 0) {
@@ -1415,226 +1352,189 @@ bool attn_fwd2_enabled(int nseq, int L, int H) {
     return L <= 128 && nseq * H >= 2 * attn_num_cus() && g_cldrd_tune_attn_fwd2 != 0;
 }
 
-template <int NKB, bool DROP, bool F16 = false>
-int launch_bwd_d(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse, void* dqkv, int nseq,
-                 int L, int H, float scale, float p, unsigned long long seed, const uint32_t* drop_bits, hipStream_t st, const int* cu, const int* seq_list) {
+// One launch's arguments: the entry point fills them once, every launcher reads them.  nseq: the sequences of THIS launch (items = nseq x H);
+// L: the batch's row stride of lse / keep bits / dropout row keys (the tile height is the launcher's NKB); p, seed: as the caller gave them.
+struct AttnFwdArgs {
+    const void* qkv; const long long* mask; const int* cu; const int* seq_list;
+    void* ctx; float* lse; int nseq, L, H; float scale, p; unsigned long long seed; uint32_t* bits_out; void* ctx16; hipStream_t st;
+};
+struct AttnBwdArgs {
+    const void* qkv; const long long* mask; const int* cu; const int* seq_list;
+    const void* ctx; const void* dctx; const float* lse; void* dqkv; int nseq, L, H; float scale, p; unsigned long long seed;
+    const uint32_t* drop_bits; hipStream_t st;
+};
+
+// f(std::integral_constant<int, n>) for n = nkb clamped to 1 .. MAX: the runtime number of 32-key blocks as a template argument
+template <int MAX, class F>
+int with_nkb(int nkb, F&& f) {
+    if constexpr (MAX > 1) {
+        if (nkb < MAX) return with_nkb<MAX - 1>(nkb, f);
+    }
+    return f(std::integral_constant<int, MAX>{});
+}
+// f(std::true_type) when dropout is active for this p, else f(std::false_type); a DROP = false launcher passes the kernels p = 0 and no keep bits
+bool attn_drops(float p) { return p > 0.f && dropout_thresh16(p) > 0; }
+template <class F>
+int with_drop(float p, F&& f) { return attn_drops(p) ? f(std::true_type{}) : f(std::false_type{}); }
+
+template <int NKB, bool DROP>
+int launch_fwd_f16(const AttnFwdArgs& a) {      // fp16 in, fp16 out: no second copy; the all-scores-in-registers kernel only (L <= 128)
+    const float p = DROP ? a.p : 0.f;
+    const size_t lds = 3 * 32 * NKB * RSB + 32 * NKB * sizeof(float);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_full_kernel<NKB, DROP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((attn_fwd_full_kernel<NKB, DROP, true>), dim3(a.nseq * a.H), dim3(256), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                       (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(a.seed), (bf16_t*)nullptr,
+                       a.cu, a.seq_list);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int NKB, bool DROP, bool F16>
+int launch_fwd(const AttnFwdArgs& a) {
+    const float p = DROP ? a.p : 0.f;
+    const uint32_t thresh = DROP ? dropout_thresh16(p) : 0u;
+    const size_t lds = 3 * 32 * NKB * RSB + 32 * NKB * sizeof(float);
+    const int nitems = a.nseq * a.H, cus = attn_num_cus();
+    if constexpr (NKB <= 4) {
+        // many items: the persistent loader / compute kernel (cldrd_set_tuning("attn_fwd2", 0) keeps the one-item-per-workgroup kernel: A/B runs and tests)
+        if (attn_fwd2_enabled(a.nseq, 32 * NKB, a.H)) {       // (the tile height, not L: a listed launch of short sequences has L > 128)
+            const size_t lds2 = 2 * (lds + (DROP ? 32 * NKB * NKB * sizeof(uint32_t) : 0));
+            (void)hipFuncSetAttribute((const void*)attn_fwd2_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+            hipLaunchKernelGGL((attn_fwd2_kernel<NKB, DROP, F16>), dim3(cus), dim3(512), lds2, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                               (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems,
+                               DROP ? a.bits_out : nullptr, (bf16_t*)a.ctx16, a.cu, a.seq_list);
+            CLDRD_LAUNCH_CHECK();
+            return 0;
+        }
+        (void)hipFuncSetAttribute((const void*)attn_fwd_full_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((attn_fwd_full_kernel<NKB, DROP, F16>), dim3(nitems), dim3(256), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                           (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), (bf16_t*)a.ctx16, a.cu, a.seq_list);
+    } else {
+        // many items at 128 < L <= 256: the persistent streaming kernel (K / V double-buffered, Q from global memory); cldrd_set_tuning("attn_fwd2", 0)
+        // keeps the one-item-per-workgroup kernel (tests: the two are bit-identical)
+        if (nitems >= 2 * cus && g_cldrd_tune_attn_fwd2 != 0) {
+            const size_t lds3 = 2 * (2 * 32 * NKB * RSB + 32 * NKB * sizeof(float));
+            (void)hipFuncSetAttribute((const void*)attn_fwd3_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
+            hipLaunchKernelGGL((attn_fwd3_kernel<NKB, DROP, F16>), dim3(cus), dim3(512), lds3, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                               (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems,
+                               (bf16_t*)a.ctx16, a.cu, a.seq_list);
+            CLDRD_LAUNCH_CHECK();
+            return 0;
+        }
+        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((attn_fwd_kernel<NKB, DROP, F16>), dim3(nitems), dim3(512), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                           (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), (bf16_t*)a.ctx16, a.cu, a.seq_list);
+    }
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int NKB, bool DROP, bool F16>
+int launch_bwd(const AttnBwdArgs& a) {
+    const float p = DROP ? a.p : 0.f;
+    const uint32_t thresh = DROP ? dropout_thresh16(p) : 0u;
+    const int nitems = a.nseq * a.H;
+    const size_t lds = 4 * 32 * NKB * RSB + 4 * 32 * NKB * sizeof(float);
     if constexpr (NKB <= 4) {
         // many items: the persistent two-role kernel (cldrd_set_tuning("attn_bwd2", 0) keeps the one-item-per-workgroup kernel: tests)
-        const int nitems = nseq * H, cus = attn_num_cus();
+        const int cus = attn_num_cus();
         if (nitems >= 2 * cus && g_cldrd_tune_attn_bwd2 != 0) {
-            const size_t lds1 = 4 * 32 * NKB * RSB + 4 * 32 * NKB * sizeof(float);
-            if (DROP && drop_bits) {
-                const size_t lds2 = 2 * (lds1 + 32 * NKB * NKB * sizeof(uint32_t));
+            if (DROP && a.drop_bits) {
+                const size_t lds2 = 2 * (lds + 32 * NKB * NKB * sizeof(uint32_t));
                 (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<NKB, DROP, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                hipLaunchKernelGGL((attn_bwd2_kernel<NKB, DROP, DROP, F16>), dim3(cus), dim3(512), lds2, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                                   (const bf16_t*)ctx, (const bf16_t*)dctx, lse, (bf16_t*)dqkv, L, H, scale,
-                                   DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), nitems, drop_bits, cu, seq_list);
+                hipLaunchKernelGGL((attn_bwd2_kernel<NKB, DROP, DROP, F16>), dim3(cus), dim3(512), lds2, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                                   (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
+                                   thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems, a.drop_bits, a.cu, a.seq_list);
             } else {
-                (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<NKB, DROP, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds1));
-                hipLaunchKernelGGL((attn_bwd2_kernel<NKB, DROP, false, F16>), dim3(cus), dim3(512), 2 * lds1, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                                   (const bf16_t*)ctx, (const bf16_t*)dctx, lse, (bf16_t*)dqkv, L, H, scale,
-                                   DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), nitems, (const uint32_t*)nullptr, cu, seq_list);
+                (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<NKB, DROP, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds));
+                hipLaunchKernelGGL((attn_bwd2_kernel<NKB, DROP, false, F16>), dim3(cus), dim3(512), 2 * lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                                   (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
+                                   thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems, (const uint32_t*)nullptr, a.cu, a.seq_list);
             }
             CLDRD_LAUNCH_CHECK();
             return 0;
         }
     }
-    const size_t lds = 4 * 32 * NKB * RSB + 4 * 32 * NKB * sizeof(float);
-    if (cu != nullptr && NKB > 1) {       // a packed batch: the instantiation whose block loops stop at the sequence's last live block
+    if (a.cu != nullptr && NKB > 1) {       // a packed batch: the instantiation whose block loops stop at the sequence's last live block
         (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<NKB, DROP, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((attn_bwd_kernel<NKB, DROP, F16, true>), dim3(nseq * H), dim3(NKB > 4 ? 512 : 256), lds, st, (const bf16_t*)qkv,
-                           (const int64_t*)mask, (const bf16_t*)ctx, (const bf16_t*)dctx, lse, (bf16_t*)dqkv, L, H, scale,
-                           DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), cu, seq_list);
+        hipLaunchKernelGGL((attn_bwd_kernel<NKB, DROP, F16, true>), dim3(nitems), dim3(NKB > 4 ? 512 : 256), lds, a.st, (const bf16_t*)a.qkv,
+                           (const int64_t*)a.mask, (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
+                           thresh, 1.0f / (1.0f - p), seed_arg(a.seed), a.cu, a.seq_list);
         CLDRD_LAUNCH_CHECK();
         return 0;
     }
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((attn_bwd_kernel<NKB, DROP, F16>), dim3(nseq * H), dim3(NKB > 4 ? 512 : 256), lds, st, (const bf16_t*)qkv, (const int64_t*)mask,
-                       (const bf16_t*)ctx, (const bf16_t*)dctx, lse, (bf16_t*)dqkv, L, H, scale,
-                       DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(seed), cu, seq_list);
+    hipLaunchKernelGGL((attn_bwd_kernel<NKB, DROP, F16>), dim3(nitems), dim3(NKB > 4 ? 512 : 256), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
+                       (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
+                       thresh, 1.0f / (1.0f - p), seed_arg(a.seed), a.cu, a.seq_list);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
-template <int NKB, bool F16 = false>
-int launch_bwd(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse, void* dqkv, int nseq,
-               int L, int H, float scale, float p, unsigned long long seed, const uint32_t* drop_bits, hipStream_t st, const int* cu, const int* seq_list) {
-    return p > 0.f && dropout_thresh16(p) > 0
-               ? launch_bwd_d<NKB, true, F16>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, p, seed, drop_bits, st, cu, seq_list)
-               : launch_bwd_d<NKB, false, F16>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, 0.f, seed, nullptr, st, cu, seq_list);
+
+// The shape limits and the layout rule of include/cldrd_hip.h, checked here for all four entry points (`op` names the caller in the message)
+int attn_check(const char* op, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile, int nseq, int L, int H) {
+    const char* why = nullptr;
+    if (!(nseq > 0 && L > 0 && L <= 256 && H > 0)) why = "need 0 < L <= 256";
+    else if (cu_rows != nullptr && mask != nullptr) why = "a packed batch (cu_rows) takes no mask";
+    else if (seq_list != nullptr && !(cu_rows != nullptr && n_list > 0 && n_list <= nseq && Ltile > 0 && Ltile <= L))
+        why = "a sequence list goes with a packed batch, 0 < n_list <= nseq, 0 < Ltile <= L";
+    if (why == nullptr) return 0;
+    char msg[128];
+    snprintf(msg, sizeof(msg), "%s: %s", op, why);
+    return cldrd_set_error(msg);
 }
 
 }  // namespace
 
-// qkv: bf16 [nseq*L, 3*H*64] (Q | K | V, heads contiguous inside each); mask: int64 [nseq, L] (0 = padded key) or null;
-// ctx: bf16 [nseq*L, H*64]; lse: fp32 [nseq, H, L] (may be null for inference).
 // Does the forward for this shape run the persistent kernel that leaves the dropout keep bits behind?  Returns the number of 32-bit
 // words of the bit array (nseq*H items x [key block][query]), 0 when the bits are not produced (the backward then hashes itself).
 extern "C" long long cldrd_attention_bits_words(int nseq, int L, int H, float dropout_p) {
-    if (!(dropout_p > 0.f && dropout_thresh16(dropout_p) > 0) || nseq <= 0 || L <= 0 || H <= 0 || !attn_fwd2_enabled(nseq, L, H)) return 0;
+    if (!attn_drops(dropout_p) || nseq <= 0 || L <= 0 || H <= 0 || !attn_fwd2_enabled(nseq, L, H)) return 0;
     const long long nkb = (L + 31) / 32;
     return (long long)nseq * H * 32 * nkb * nkb;
 }
 
-extern "C" int cldrd_attention_fwd_bits(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H,
-                                        float dropout_p, unsigned long long seed, int io_f16, void* drop_bits_out, void* ctx_f16_copy,
-                                        void* stream);
-extern "C" int cldrd_attention_fwd(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H,
-                                   float dropout_p, unsigned long long seed, int io_f16, void* stream) {
-    return cldrd_attention_fwd_bits(qkv, mask, ctx, lse, nseq, L, H, dropout_p, seed, io_f16, nullptr, nullptr, stream);
-}
-// drop_bits_out (optional, cldrd_attention_bits_words() words): receives the dropout keep bits for cldrd_attention_bwd_bits.
+// qkv: 16-bit [rows, 3*H*64] (Q | K | V, heads contiguous inside each); ctx: [rows, H*64]; lse: fp32 [nseq, H, L] (may be null for inference).
+// Layouts (mask / cu_rows / seq_list, n_list, Ltile): include/cldrd_hip.h.  A packed batch gives bit for bit what cldrd_unpack_rows16 -> the
+// padded call -> cldrd_gather_rows give, without the two row moves and without loading padding rows.
+// drop_bits_out (optional, cldrd_attention_bits_words() words): receives the dropout keep bits for cldrd_attention_bwd (none for L > 128).
 // ctx_f16_copy (optional, bf16 pass only): the same context in fp16 - the operand of an fp16 out-projection GEMM; ctx itself may then be null
 // (an evaluation forward keeps no bf16 tape).
-static int attention_fwd_impl(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H, float dropout_p,
-                              unsigned long long seed, int io_f16, void* drop_bits_out, void* ctx_f16_copy, const int* cu, void* stream,
-                              const int* seq_list = nullptr, int n_list = 0, int Ltile = 0);
-extern "C" int cldrd_attention_fwd_bits(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H,
-                                        float dropout_p, unsigned long long seed, int io_f16, void* drop_bits_out, void* ctx_f16_copy,
-                                        void* stream) {
-    return attention_fwd_impl(qkv, mask, ctx, lse, nseq, L, H, dropout_p, seed, io_f16, drop_bits_out, ctx_f16_copy, nullptr, stream);
-}
-// The same on a PACKED batch (pack.hip): qkv [Tp, 3*H*64] and ctx [Tp, H*64] hold the rows cu_rows[m] .. cu_rows[m + 1] of sequence m
-// (cu_rows: int32 [nseq + 1] on the device, every length in 1 .. L); keys >= a sequence's length are masked (right padding, what an HF
-// tokenizer's attention mask says), no mask tensor is read.  lse [nseq, H, L] and the keep bits keep their padded shapes.  Bit for bit what
-// cldrd_unpack_rows16 -> cldrd_attention_fwd_bits -> cldrd_gather_rows give, without the two row moves and without loading padding rows.
-extern "C" int cldrd_attention_fwd_varlen(const void* qkv_packed, const int* cu_rows, void* ctx_packed, float* lse, int nseq, int L, int H,
-                                          float dropout_p, unsigned long long seed, int io_f16, void* drop_bits_out, void* ctx_f16_copy,
-                                          void* stream) {
-    CLDRD_CHECK(cu_rows != nullptr, "attention_fwd_varlen: cu_rows is required");
-    return attention_fwd_impl(qkv_packed, nullptr, ctx_packed, lse, nseq, L, H, dropout_p, seed, io_f16, drop_bits_out, ctx_f16_copy, cu_rows, stream);
-}
-// The same for a LIST of the batch's sequences (seq_list: device int32 [n_list], positions in 0 .. nseq - 1, each at most Ltile <= L tokens long):
-// the launch runs the kernels of tile height Ltile - a packed batch at L = 256 sends its sequences of at most 128 tokens through the persistent
-// L <= 128 kernels and the rest through a second call (round 6).  LSE rows and dropout row keys keep the stride L of the whole batch, so the
-// backward of a sequence must be given the same L (any list).  No keep bits are produced for L > 128 (cldrd_attention_bits_words).
-extern "C" int cldrd_attention_fwd_varlen_list(const void* qkv_packed, const int* cu_rows, void* ctx_packed, float* lse, int nseq, int L, int H,
-                                               float dropout_p, unsigned long long seed, int io_f16, void* drop_bits_out, void* ctx_f16_copy,
-                                               const int* seq_list, int n_list, int Ltile, void* stream) {
-    CLDRD_CHECK(cu_rows != nullptr && seq_list != nullptr, "attention_fwd_varlen_list: cu_rows and seq_list are required");
-    return attention_fwd_impl(qkv_packed, nullptr, ctx_packed, lse, nseq, L, H, dropout_p, seed, io_f16, drop_bits_out, ctx_f16_copy, cu_rows, stream,
-                              seq_list, n_list, Ltile);
-}
-static int attention_fwd_impl(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq_all, int L, int H, float dropout_p,
-                              unsigned long long seed, int io_f16, void* drop_bits_out, void* ctx_f16_copy, const int* cu, void* stream,
-                              const int* seq_list, int n_list, int Ltile) {
-    CLDRD_CHECK(nseq_all > 0 && L > 0 && L <= 256 && H > 0, "attention_fwd: need 0 < L <= 256");
-    CLDRD_CHECK(seq_list == nullptr || (cu != nullptr && n_list > 0 && n_list <= nseq_all && Ltile > 0 && Ltile <= L),
-                "attention_fwd: a sequence list goes with a packed batch, 0 < n_list <= nseq, 0 < Ltile <= L");
-    const int nseq = seq_list ? n_list : nseq_all;          // sequences of THIS launch (items = nseq x H)
-    const int Lt = seq_list ? Ltile : L;                    // rows a sequence of this launch can have: the kernels' tile height
+extern "C" int cldrd_attention_fwd(const void* qkv, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile,
+                                   void* ctx, float* lse, int nseq, int L, int H, float dropout_p, unsigned long long seed, int io_f16,
+                                   void* drop_bits_out, void* ctx_f16_copy, void* stream) {
+    if (attn_check("attention_fwd", mask, cu_rows, seq_list, n_list, Ltile, nseq, L, H)) return 1;
+    const int n = seq_list ? n_list : nseq;          // sequences of THIS launch (items = n x H)
+    const int Lt = seq_list ? Ltile : L;             // rows a sequence of this launch can have: the kernels' tile height
     CLDRD_CHECK(ctx != nullptr || ctx_f16_copy != nullptr, "attention_fwd: no output");
     CLDRD_CHECK(!(io_f16 && (ctx_f16_copy != nullptr || ctx == nullptr)), "attention_fwd: the fp16 pass writes ctx only");
     CLDRD_CHECK(io_f16 == 0 || io_f16 == 1 || io_f16 == 5, "attention_fwd: io_f16 is 0 (bf16), 1 (fp16, L <= 128, no keep bits) or 5 (fp16, every kernel of the bf16 path)");
-    const float scale = 0.125f;   // 1 / sqrt(64)
+    CLDRD_CHECK(io_f16 != 1 || Lt <= 128, "attention_fwd: the fp16 forward handles L <= 128");
+    const AttnFwdArgs a = {qkv, mask, cu_rows, seq_list, ctx, lse, n, L, H, 0.125f /* 1 / sqrt(64) */, dropout_p, seed,
+                           (uint32_t*)drop_bits_out, ctx_f16_copy, (hipStream_t)stream};
     const int nkb = (Lt + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
-    if (io_f16 == 5) {            // fp16 activations through the whole kernel family (round 4: the all-fp16 training mode)
-        switch (nkb) {
-            case 1: return launch_fwd<1, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-            case 2: return launch_fwd<2, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-            case 3: return launch_fwd<3, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-            case 4: return launch_fwd<4, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-            case 5: return launch_fwd<5, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-            case 6: return launch_fwd<6, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-            case 7: return launch_fwd<7, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-            default: return launch_fwd<8, true>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, nullptr, st, cu, seq_list);
-        }
-    }
-    if (io_f16) {                 // fp16 activations: the all-scores-in-registers kernel only (L <= 128)
-        CLDRD_CHECK(Lt <= 128, "attention_fwd: the fp16 forward handles L <= 128");
-        switch (nkb) {
-            case 1: return launch_fwd_h<1>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, st, cu, seq_list);
-            case 2: return launch_fwd_h<2>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, st, cu, seq_list);
-            case 3: return launch_fwd_h<3>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, st, cu, seq_list);
-            default: return launch_fwd_h<4>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, st, cu, seq_list);
-        }
-    }
-    switch (nkb) {
-        case 1: return launch_fwd<1>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-        case 2: return launch_fwd<2>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-        case 3: return launch_fwd<3>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-        case 4: return launch_fwd<4>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-        case 5: return launch_fwd<5>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-        case 6: return launch_fwd<6>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-        case 7: return launch_fwd<7>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-        default: return launch_fwd<8>(qkv, mask, ctx, lse, nseq, L, H, scale, dropout_p, seed, (uint32_t*)drop_bits_out, ctx_f16_copy, st, cu, seq_list);
-    }
+    if (io_f16 == 5)            // fp16 activations through the whole kernel family (round 4: the all-fp16 training mode)
+        return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_fwd<decltype(k)::value, decltype(d)::value, true>(a); }); });
+    if (io_f16 == 1)            // fp16 activations, evaluation passes: the all-scores-in-registers kernel only
+        return with_nkb<4>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_fwd_f16<decltype(k)::value, decltype(d)::value>(a); }); });
+    return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_fwd<decltype(k)::value, decltype(d)::value, false>(a); }); });
 }
 
-extern "C" int cldrd_attention_bwd_bits(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                                        void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits,
-                                        void* stream);
-extern "C" int cldrd_attention_bwd(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                                   void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, void* stream) {
-    return cldrd_attention_bwd_bits(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, dropout_p, seed, nullptr, stream);
-}
-extern "C" int cldrd_attention_bwd_x(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                                     void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits,
-                                     int io_f16, void* stream);
-// drop_bits (optional): what cldrd_attention_fwd_bits left for the same (nseq, L, H, dropout_p, seed); null: the mask is re-hashed.
-extern "C" int cldrd_attention_bwd_bits(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                                        void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits,
-                                        void* stream) {
-    return cldrd_attention_bwd_x(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, dropout_p, seed, drop_bits, 0, stream);
-}
-// io_f16 != 0: q / k / v, ctx, dctx and dqkv are fp16 (the all-fp16 training mode: gradients carry the loss scale)
-static int attention_bwd_impl(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse, void* dqkv, int nseq,
-                              int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits, int io_f16, const int* cu, void* stream,
-                              const int* seq_list = nullptr, int n_list = 0, int Ltile = 0);
-extern "C" int cldrd_attention_bwd_x(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                                     void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits,
-                                     int io_f16, void* stream) {
-    return attention_bwd_impl(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, dropout_p, seed, drop_bits, io_f16, nullptr, stream);
-}
-// The backward on a PACKED batch (see cldrd_attention_fwd_varlen): qkv, ctx, dctx, dqkv are [Tp, .]; rows of dqkv that do not exist in the
-// packed layout (padding) are not written - in the padded layout they receive zeros.
-extern "C" int cldrd_attention_bwd_varlen(const void* qkv_packed, const int* cu_rows, const void* ctx_packed, const void* dctx_packed,
-                                          const float* lse, void* dqkv_packed, int nseq, int L, int H, float dropout_p, unsigned long long seed,
-                                          const void* drop_bits, int io_f16, void* stream) {
-    CLDRD_CHECK(cu_rows != nullptr, "attention_bwd_varlen: cu_rows is required");
-    return attention_bwd_impl(qkv_packed, nullptr, ctx_packed, dctx_packed, lse, dqkv_packed, nseq, L, H, dropout_p, seed, drop_bits, io_f16, cu_rows, stream);
-}
-extern "C" int cldrd_attention_bwd_varlen_list(const void* qkv_packed, const int* cu_rows, const void* ctx_packed, const void* dctx_packed,
-                                               const float* lse, void* dqkv_packed, int nseq, int L, int H, float dropout_p, unsigned long long seed,
-                                               const void* drop_bits, int io_f16, const int* seq_list, int n_list, int Ltile, void* stream) {
-    CLDRD_CHECK(cu_rows != nullptr && seq_list != nullptr, "attention_bwd_varlen_list: cu_rows and seq_list are required");
-    return attention_bwd_impl(qkv_packed, nullptr, ctx_packed, dctx_packed, lse, dqkv_packed, nseq, L, H, dropout_p, seed, drop_bits, io_f16, cu_rows,
-                              stream, seq_list, n_list, Ltile);
-}
-static int attention_bwd_impl(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse, void* dqkv, int nseq_all,
-                              int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits, int io_f16, const int* cu, void* stream,
-                              const int* seq_list, int n_list, int Ltile) {
-    CLDRD_CHECK(nseq_all > 0 && L > 0 && L <= 256 && H > 0, "attention_bwd: need 0 < L <= 256");
-    CLDRD_CHECK(seq_list == nullptr || (cu != nullptr && n_list > 0 && n_list <= nseq_all && Ltile > 0 && Ltile <= L),
-                "attention_bwd: a sequence list goes with a packed batch, 0 < n_list <= nseq, 0 < Ltile <= L");
-    const int nseq = seq_list ? n_list : nseq_all;          // sequences of THIS launch; Lt: the rows one of them can have (tile height)
-    const int Lt = seq_list ? Ltile : L;
+// drop_bits (optional): what cldrd_attention_fwd left for the same (nseq, L, H, dropout_p, seed); null: the mask is re-hashed.
+// io_f16 != 0: q / k / v, ctx, dctx and dqkv are fp16 (the all-fp16 training mode: gradients carry the loss scale).
+// Packed batch: rows of dqkv that do not exist in the packed layout (padding) are not written - in the padded layout they receive zeros.
+extern "C" int cldrd_attention_bwd(const void* qkv, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile,
+                                   const void* ctx, const void* dctx, const float* lse, void* dqkv, int nseq, int L, int H, float dropout_p,
+                                   unsigned long long seed, int io_f16, const void* drop_bits, void* stream) {
+    if (attn_check("attention_bwd", mask, cu_rows, seq_list, n_list, Ltile, nseq, L, H)) return 1;
+    const int n = seq_list ? n_list : nseq, Lt = seq_list ? Ltile : L;          // as in cldrd_attention_fwd
     CLDRD_CHECK(lse != nullptr, "attention_bwd: lse is required");
-    const float scale = 0.125f;
+    const AttnBwdArgs a = {qkv, mask, cu_rows, seq_list, ctx, dctx, lse, dqkv, n, L, H, 0.125f, dropout_p, seed, (const uint32_t*)drop_bits,
+                           (hipStream_t)stream};
     const int nkb = (Lt + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
-    if (io_f16) {
-        switch (nkb) {
-            case 1: return launch_bwd<1, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-            case 2: return launch_bwd<2, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-            case 3: return launch_bwd<3, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-            case 4: return launch_bwd<4, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-            case 5: return launch_bwd<5, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-            case 6: return launch_bwd<6, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-            case 7: return launch_bwd<7, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-            default: return launch_bwd<8, true>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        }
-    }
-    switch (nkb) {
-        case 1: return launch_bwd<1>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        case 2: return launch_bwd<2>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        case 3: return launch_bwd<3>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        case 4: return launch_bwd<4>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        case 5: return launch_bwd<5>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        case 6: return launch_bwd<6>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        case 7: return launch_bwd<7>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-        default: return launch_bwd<8>(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, scale, dropout_p, seed, (const uint32_t*)drop_bits, st, cu, seq_list);
-    }
+    if (io_f16)
+        return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_bwd<decltype(k)::value, decltype(d)::value, true>(a); }); });
+    return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_bwd<decltype(k)::value, decltype(d)::value, false>(a); }); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1838,64 +1738,38 @@ __global__ __launch_bounds__(256) void add_rows_strided_kernel(void* __restrict_
 
 }  // namespace
 
-// qc: bf16 [nseq, H*64] (CLS queries); kv: bf16 [nseq*L, 2*H*64] = K | V; ctx: bf16 [nseq, H*64]; probs: fp32 [nseq, H, L]
-static int attention_cls_fwd_impl(const void* qc, const void* kv, const long long* mask, void* ctx, float* probs, int nseq, int L, int H,
-                                  float dropout_p, unsigned long long seed, int io_f16, void* ctx_f16_copy, const int* cu, void* stream);
-extern "C" int cldrd_attention_cls_fwd(const void* qc, const void* kv, const long long* mask, void* ctx, float* probs, int nseq, int L,
-                                       int H, float dropout_p, unsigned long long seed, int io_f16, void* ctx_f16_copy, void* stream) {
-    return attention_cls_fwd_impl(qc, kv, mask, ctx, probs, nseq, L, H, dropout_p, seed, io_f16, ctx_f16_copy, nullptr, stream);
-}
-// kv PACKED: [Tp, 2*H*64], rows cu_rows[m] .. cu_rows[m + 1] of sequence m (see cldrd_attention_fwd_varlen); probs stays [nseq, H, L]
-extern "C" int cldrd_attention_cls_fwd_varlen(const void* qc, const void* kv_packed, const int* cu_rows, void* ctx, float* probs, int nseq, int L,
-                                              int H, float dropout_p, unsigned long long seed, int io_f16, void* ctx_f16_copy, void* stream) {
-    CLDRD_CHECK(cu_rows != nullptr, "attention_cls_fwd_varlen: cu_rows is required");
-    return attention_cls_fwd_impl(qc, kv_packed, nullptr, ctx, probs, nseq, L, H, dropout_p, seed, io_f16, ctx_f16_copy, cu_rows, stream);
-}
-static int attention_cls_fwd_impl(const void* qc, const void* kv, const long long* mask, void* ctx, float* probs, int nseq, int L, int H,
-                                  float dropout_p, unsigned long long seed, int io_f16, void* ctx_f16_copy, const int* cu, void* stream) {
-    CLDRD_CHECK(nseq > 0 && L > 0 && L <= 256 && H > 0 && probs != nullptr, "attention_cls_fwd: need 0 < L <= 256 and a probs buffer");
+// qc: 16-bit [nseq, H*64] (CLS queries); kv: [rows, 2*H*64] = K | V (padded, or packed with cu_rows: include/cldrd_hip.h); ctx: [nseq, H*64];
+// probs: fp32 [nseq, H, L] in either layout
+extern "C" int cldrd_attention_cls_fwd(const void* qc, const void* kv, const long long* mask, const int* cu_rows, void* ctx, float* probs,
+                                       int nseq, int L, int H, float dropout_p, unsigned long long seed, int io_f16, void* ctx_f16_copy,
+                                       void* stream) {
+    if (attn_check("attention_cls_fwd", mask, cu_rows, nullptr, 0, 0, nseq, L, H)) return 1;
+    CLDRD_CHECK(probs != nullptr, "attention_cls_fwd: need a probs buffer");
     CLDRD_CHECK((ctx != nullptr || ctx_f16_copy != nullptr) && !(io_f16 && (ctx_f16_copy != nullptr || ctx == nullptr)), "attention_cls_fwd: outputs");
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
     if (io_f16)
         hipLaunchKernelGGL(attn_cls_fwd_kernel<true>, dim3(nseq * H), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)qc, (const bf16_t*)kv,
-                           (const int64_t*)mask, (bf16_t*)ctx, probs, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), (bf16_t*)nullptr, cu);
+                           (const int64_t*)mask, (bf16_t*)ctx, probs, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), (bf16_t*)nullptr, cu_rows);
     else
         hipLaunchKernelGGL(attn_cls_fwd_kernel<false>, dim3(nseq * H), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)qc, (const bf16_t*)kv,
-                           (const int64_t*)mask, (bf16_t*)ctx, probs, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), (bf16_t*)ctx_f16_copy, cu);
+                           (const int64_t*)mask, (bf16_t*)ctx, probs, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), (bf16_t*)ctx_f16_copy, cu_rows);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
 
-// dqc: bf16 [nseq, H*64]; dkv: bf16 [nseq*L, 2*H*64] (every row written)
-static int attention_cls_bwd_impl(const void* qc, const void* kv, const float* probs, const void* dctx, void* dqc, void* dkv, int nseq, int L,
-                                  int H, float dropout_p, unsigned long long seed, int io_f16, const int* cu, void* stream);
-extern "C" int cldrd_attention_cls_bwd_x(const void* qc, const void* kv, const float* probs, const void* dctx, void* dqc, void* dkv,
-                                         int nseq, int L, int H, float dropout_p, unsigned long long seed, int io_f16, void* stream) {
-    return attention_cls_bwd_impl(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p, seed, io_f16, nullptr, stream);
-}
-// kv and dkv PACKED: [Tp, 2*H*64] (every row of dkv written)
-extern "C" int cldrd_attention_cls_bwd_varlen(const void* qc, const void* kv_packed, const int* cu_rows, const float* probs, const void* dctx,
-                                              void* dqc, void* dkv_packed, int nseq, int L, int H, float dropout_p, unsigned long long seed,
-                                              int io_f16, void* stream) {
-    CLDRD_CHECK(cu_rows != nullptr, "attention_cls_bwd_varlen: cu_rows is required");
-    return attention_cls_bwd_impl(qc, kv_packed, probs, dctx, dqc, dkv_packed, nseq, L, H, dropout_p, seed, io_f16, cu_rows, stream);
-}
-static int attention_cls_bwd_impl(const void* qc, const void* kv, const float* probs, const void* dctx, void* dqc, void* dkv, int nseq, int L,
-                                  int H, float dropout_p, unsigned long long seed, int io_f16, const int* cu, void* stream) {
-    CLDRD_CHECK(nseq > 0 && L > 0 && L <= 256 && H > 0, "attention_cls_bwd: need 0 < L <= 256");
+// dqc: [nseq, H*64]; dkv: [rows, 2*H*64] in the layout of kv (every row written)
+extern "C" int cldrd_attention_cls_bwd(const void* qc, const void* kv, const int* cu_rows, const float* probs, const void* dctx, void* dqc,
+                                       void* dkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, int io_f16, void* stream) {
+    if (attn_check("attention_cls_bwd", nullptr, cu_rows, nullptr, 0, 0, nseq, L, H)) return 1;
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
     if (io_f16)
         hipLaunchKernelGGL(attn_cls_bwd_kernel<true>, dim3(nseq * H), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)qc, (const bf16_t*)kv, probs,
-                           (const bf16_t*)dctx, (bf16_t*)dqc, (bf16_t*)dkv, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), cu);
+                           (const bf16_t*)dctx, (bf16_t*)dqc, (bf16_t*)dkv, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), cu_rows);
     else
         hipLaunchKernelGGL(attn_cls_bwd_kernel<false>, dim3(nseq * H), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)qc, (const bf16_t*)kv, probs,
-                           (const bf16_t*)dctx, (bf16_t*)dqc, (bf16_t*)dkv, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), cu);
+                           (const bf16_t*)dctx, (bf16_t*)dqc, (bf16_t*)dkv, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), cu_rows);
     CLDRD_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int cldrd_attention_cls_bwd(const void* qc, const void* kv, const float* probs, const void* dctx, void* dqc, void* dkv,
-                                       int nseq, int L, int H, float dropout_p, unsigned long long seed, void* stream) {
-    return cldrd_attention_cls_bwd_x(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p, seed, 0, stream);
 }
 
 extern "C" int cldrd_add_rows_strided(void* dst, const void* src, int M, int d, int stride_rows, int f32, void* stream) {

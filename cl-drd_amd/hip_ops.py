@@ -266,7 +266,7 @@ def gemm_nt(A, B, out, M=None, *, bias=None, residual=None, preact=None, gelu_pr
             ws_bytes = _SPLITK_WS[key] = int(_lib.load().cldrd_gemm_nt_splitk_workspace(M, N, K))
         if ws_bytes:
             ws = torch.empty(ws_bytes // 4, dtype=F32, device=A.device)
-    call("cldrd_gemm_nt16_ws", _p(A), _p(B), _p(out), M, N, K, A.stride(0), B.stride(0), out.stride(0), _p(bias),
+    call("cldrd_gemm_nt16", _p(A), _p(B), _p(out), M, N, K, A.stride(0), B.stride(0), out.stride(0), _p(bias),
          _p(residual), residual.stride(0) if residual is not None else 0, _p(preact), _p(gelu_pre), act, alpha, dropout_p, seed,
          out_f32, res_f32, io_f16, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(out_copy), _p(ws), ws_bytes, _stream())
     return out
@@ -365,7 +365,7 @@ def _cu_rows(cu, nseq, mask, what):
 
 def _seq_list(seq_list, tile, cu, nseq, L, what):
     """``seq_list`` (int32 on the device) with ``tile``: the launch covers only these sequences of a packed batch, each at most ``tile`` <= L tokens
-    long, with the kernels of that tile height (cldrd_attention_*_varlen_list)."""
+    long, with the kernels of that tile height."""
     if cu is None:
         raise ValueError(f"{what}: a sequence list goes with a packed batch (cu)")
     _chk(seq_list, torch.int32, "seq_list", 1)
@@ -374,21 +374,20 @@ def _seq_list(seq_list, tile, cu, nseq, L, what):
     return (_p(seq_list), int(seq_list.numel()), int(tile))
 
 
+def _layout(mask, cu, seq_list, tile, nseq, L, what):
+    """The (mask, cu_rows, seq_list, n_list, Ltile) arguments of an attention entry point (layout rule: include/cldrd_hip.h)."""
+    lst = _seq_list(seq_list, tile, cu, nseq, L, what) if seq_list is not None else (None, 0, 0)
+    if cu is not None:
+        return (None, _p(_cu_rows(cu, nseq, mask, what)), *lst)
+    return (_p(mask), None, *lst)
+
+
 def attention_fwd(qkv, mask, ctx, lse, nseq, L, H, dropout_p=0.0, seed=0, drop_bits=None, ctx16=None, full_family=False, cu=None, seq_list=None, tile=0):
     """``ctx16`` (fp16, bf16 pass only): the same context in fp16, for an fp16-operand out-projection; ``ctx`` may then be None.
     ``cu``: qkv / ctx / ctx16 are packed [Tp, .] (see _cu_rows); ``lse`` and ``drop_bits`` keep their padded shapes.  ``seq_list`` / ``tile``:
     see _seq_list."""
     io_f16 = _fmt16(qkv, "qkv")
-    entry = "cldrd_attention_fwd_bits"
-    tail = ()
-    if cu is not None:
-        entry, mask_arg = "cldrd_attention_fwd_varlen", _p(_cu_rows(cu, nseq, mask, "attention_fwd"))
-        if seq_list is not None:
-            entry, tail = "cldrd_attention_fwd_varlen_list", _seq_list(seq_list, tile, cu, nseq, L, "attention_fwd")
-    else:
-        mask_arg = _p(mask)
-        if seq_list is not None:
-            raise ValueError("attention_fwd: a sequence list goes with a packed batch (cu)")
+    layout = _layout(mask, cu, seq_list, tile, nseq, L, "attention_fwd")
     _chk(qkv, F16 if io_f16 else BF16, "qkv", 2)
     if ctx16 is not None:
         if io_f16:
@@ -396,17 +395,13 @@ def attention_fwd(qkv, mask, ctx, lse, nseq, L, H, dropout_p=0.0, seed=0, drop_b
         _chk(ctx16, F16, "ctx16", 2)
         if ctx16.shape[1] != H * 64 or not ctx16.is_contiguous():
             raise ValueError("attention: ctx16 must be contiguous [T, H*64]")
-        if ctx is None:
-            if mask is not None:
-                _chk(mask, torch.int64, "mask", 2)
-            call(entry, _p(qkv), mask_arg, None, _p(lse), nseq, L, H, dropout_p, seed, 0, _p(drop_bits), _p(ctx16), *tail, _stream())
-            return ctx16
-    _chk(ctx, F16 if io_f16 else BF16, "ctx", 2)
+    if ctx is not None or ctx16 is None:
+        _chk(ctx, F16 if io_f16 else BF16, "ctx", 2)
     if mask is not None:
         _chk(mask, torch.int64, "mask", 2)
         if not mask.is_contiguous() or tuple(mask.shape) != (nseq, L):
             raise ValueError("attention: mask must be contiguous int64 [nseq, L]")
-    if qkv.shape[1] != 3 * H * 64 or ctx.shape[1] != H * 64 or not qkv.is_contiguous() or not ctx.is_contiguous():
+    if qkv.shape[1] != 3 * H * 64 or not qkv.is_contiguous() or (ctx is not None and (ctx.shape[1] != H * 64 or not ctx.is_contiguous())):
         raise ValueError("attention: qkv must be [T, 3*H*64], ctx [T, H*64], contiguous")
     if lse is not None:
         _chk(lse, F32, "lse")
@@ -416,8 +411,8 @@ def attention_fwd(qkv, mask, ctx, lse, nseq, L, H, dropout_p=0.0, seed=0, drop_b
             raise ValueError("attention_fwd: drop_bits must come from attention_drop_bits() for the same shape")
     if io_f16 and (drop_bits is not None or L > 128 or full_family):
         io_f16 = 5                    # fp16 through the whole kernel family of the bf16 path (persistent kernel, keep bits, L > 128)
-    call(entry, _p(qkv), mask_arg, _p(ctx), _p(lse), nseq, L, H, dropout_p, seed, io_f16, _p(drop_bits), _p(ctx16), *tail, _stream())
-    return ctx
+    call("cldrd_attention_fwd", _p(qkv), *layout, _p(ctx), _p(lse), nseq, L, H, dropout_p, seed, io_f16, _p(drop_bits), _p(ctx16), _stream())
+    return ctx16 if ctx is None else ctx
 
 
 def attention_bwd(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, dropout_p=0.0, seed=0, drop_bits=None, cu=None, seq_list=None, tile=0):
@@ -430,16 +425,8 @@ def attention_bwd(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, dropout_p=0.0, se
     _chk(lse, F32, "lse")
     if drop_bits is not None:
         _chk(drop_bits, torch.int32, "drop_bits", 1)
-    if seq_list is not None:
-        call("cldrd_attention_bwd_varlen_list", _p(qkv), _p(_cu_rows(cu, nseq, mask, "attention_bwd") if cu is not None else None), _p(ctx), _p(dctx),
-             _p(lse), _p(dqkv), nseq, L, H, dropout_p, seed, _p(drop_bits), io_f16, *_seq_list(seq_list, tile, cu, nseq, L, "attention_bwd"), _stream())
-        return dqkv
-    if cu is not None:
-        call("cldrd_attention_bwd_varlen", _p(qkv), _p(_cu_rows(cu, nseq, mask, "attention_bwd")), _p(ctx), _p(dctx), _p(lse), _p(dqkv), nseq, L, H,
-             dropout_p, seed, _p(drop_bits), io_f16, _stream())
-        return dqkv
-    call("cldrd_attention_bwd_x", _p(qkv), _p(mask), _p(ctx), _p(dctx), _p(lse), _p(dqkv), nseq, L, H, dropout_p, seed,
-         _p(drop_bits), io_f16, _stream())
+    call("cldrd_attention_bwd", _p(qkv), *_layout(mask, cu, seq_list, tile, nseq, L, "attention_bwd"), _p(ctx), _p(dctx), _p(lse), _p(dqkv),
+         nseq, L, H, dropout_p, seed, io_f16, _p(drop_bits), _stream())
     return dqkv
 
 
@@ -458,11 +445,8 @@ def attention_cls_fwd(qc, kv, mask, ctx, probs, nseq, L, H, dropout_p=0.0, seed=
         raise ValueError("attention_cls_fwd: no output")
     if kv.shape[1] != 2 * H * 64 or not kv.is_contiguous() or not qc.is_contiguous() or any(t is not None and not t.is_contiguous() for t in (ctx, ctx16)):
         raise ValueError("attention_cls: kv must be contiguous [T, 2*H*64]")
-    if cu is not None:
-        call("cldrd_attention_cls_fwd_varlen", _p(qc), _p(kv), _p(_cu_rows(cu, nseq, mask, "attention_cls_fwd")), _p(ctx), _p(probs), nseq, L, H,
-             dropout_p, seed, io_f16, _p(ctx16), _stream())
-        return
-    call("cldrd_attention_cls_fwd", _p(qc), _p(kv), _p(mask), _p(ctx), _p(probs), nseq, L, H, dropout_p, seed, io_f16, _p(ctx16), _stream())
+    call("cldrd_attention_cls_fwd", _p(qc), _p(kv), *_layout(mask, cu, None, 0, nseq, L, "attention_cls_fwd")[:2], _p(ctx), _p(probs), nseq, L, H,
+         dropout_p, seed, io_f16, _p(ctx16), _stream())
 
 
 def attention_cls_bwd(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p=0.0, seed=0, cu=None):
@@ -472,11 +456,8 @@ def attention_cls_bwd(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p=0.0, 
         _chk(t, F16 if io_f16 else BF16, n, 2)
         if not t.is_contiguous():
             raise ValueError(f"attention_cls_bwd: {n} must be contiguous")
-    if cu is not None:
-        call("cldrd_attention_cls_bwd_varlen", _p(qc), _p(kv), _p(_cu_rows(cu, nseq, None, "attention_cls_bwd")), _p(probs), _p(dctx), _p(dqc), _p(dkv),
-             nseq, L, H, dropout_p, seed, io_f16, _stream())
-        return
-    call("cldrd_attention_cls_bwd_x", _p(qc), _p(kv), _p(probs), _p(dctx), _p(dqc), _p(dkv), nseq, L, H, dropout_p, seed, io_f16, _stream())
+    call("cldrd_attention_cls_bwd", _p(qc), _p(kv), _layout(None, cu, None, 0, nseq, L, "attention_cls_bwd")[1], _p(probs), _p(dctx), _p(dqc), _p(dkv),
+         nseq, L, H, dropout_p, seed, io_f16, _stream())
 
 
 def add_rows_strided(dst, src, M, stride_rows):

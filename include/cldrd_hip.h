@@ -54,30 +54,20 @@ enum cldrd_fmt16 {
     CLDRD_FMT_F16_C_BF16 = 3,    /* fp16 A and B, bf16 C: the QKV projection of an evaluation pass whose attention kernels are bf16 */
     CLDRD_FMT_F16_TAPE = 5       /* fp16 everywhere incl. preact / gelu_pre: a training pass of the fp16 mode */
 };
-int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
-                       const float* bias, const void* residual, int ldr, void* preact, const void* gelu_pre,
-                       int act, float alpha, float dropout_p, unsigned long long seed, int out_f32, int res_f32, int fmt,
-                       void* stream);
-
-/* The same GEMM with the fp32 residual given as a LayerNorm still to be applied: `residual` holds the pre-LN sum s (fp32, res_f32 = 1) and
+/* ln_* (all four or none): the fp32 residual given as a LayerNorm still to be applied: `residual` holds the pre-LN sum s (fp32, res_f32 = 1) and
  * the epilogue adds (s - ln_mean[m]) * ln_rstd[m] * ln_gamma[n] + ln_beta[n] - exactly what cldrd_layernorm_fwd would have written
- * as its fp32 output, which it then need not write (HF: hidden = LayerNorm(...); out = dense(x) + hidden).  All four ln_* or none. */
-int cldrd_gemm_nt16_ln(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
-                          const float* bias, const void* residual, int ldr, void* preact, const void* gelu_pre,
-                          int act, float alpha, float dropout_p, unsigned long long seed, int out_f32, int res_f32, int fmt,
-                          const float* ln_mean, const float* ln_rstd, const float* ln_gamma, const float* ln_beta, void* stream);
-
-/* The same with a workspace: problems of fewer than 1024 rows whose one-pass grid would leave most CUs idle (CLS-only last layer, query
+ * as its fp32 output, which it then need not write (HF: hidden = LayerNorm(...); out = dense(x) + hidden).
+ * workspace (optional): problems of fewer than 1024 rows whose one-pass grid would leave most CUs idle (CLS-only last layer, query
  * tower) are split along K: fp32 partials in `workspace` (cldrd_gemm_nt_splitk_workspace() bytes; 0 = this shape is not split), summed in
- * a fixed order and finished with the same epilogue by a second launch.  workspace = NULL: cldrd_gemm_nt16_ln.
- * fmt != CLDRD_FMT_BF16 here also serves M >= 1024 (csrc/gemm_nt_ring16.hip).  c_copy_bf16: NULL (a bf16 copy of an fp16 C for the removed
+ * a fixed order and finished with the same epilogue by a second launch.  workspace = NULL: one pass.
+ * fmt != CLDRD_FMT_BF16 also serves M >= 1024 (csrc/gemm_nt_ring16.hip).  c_copy_bf16: NULL (a bf16 copy of an fp16 C for the removed
  * "bf16 tape under an fp16 forward" mode of rounds 3-5; kept in the signature, rejected when non-NULL with any format but CLDRD_FMT_F16). */
 size_t cldrd_gemm_nt_splitk_workspace(int M, int N, int K);
-int cldrd_gemm_nt16_ws(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
-                          const float* bias, const void* residual, int ldr, void* preact, const void* gelu_pre,
-                          int act, float alpha, float dropout_p, unsigned long long seed, int out_f32, int res_f32, int fmt,
-                          const float* ln_mean, const float* ln_rstd, const float* ln_gamma, const float* ln_beta,
-                          void* c_copy_bf16, float* workspace, size_t workspace_bytes, void* stream);
+int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                    const float* bias, const void* residual, int ldr, void* preact, const void* gelu_pre,
+                    int act, float alpha, float dropout_p, unsigned long long seed, int out_f32, int res_f32, int fmt,
+                    const float* ln_mean, const float* ln_rstd, const float* ln_gamma, const float* ln_beta,
+                    void* c_copy_bf16, float* workspace, size_t workspace_bytes, void* stream);
 
 /* Weight gradient dW[N1,N2] (+)= A[M,N1]^T . B[M,N2]   (A = dY, B = layer input; autograd's Linear backward), and,
  * when dbias != NULL, the bias gradient dbias[N1] (+)= column sums of A in the same pass.
@@ -103,67 +93,45 @@ int cldrd_wgrad_group(const void* const* A, const void* const* B, float* const* 
                       size_t workspace_bytes, int accumulate, void* stream);
 
 /* ---- attention (HF DistilBertSelfAttention / BertSelfAttention, head dim 64, L <= 256) --------------------
- * qkv: bf16 [nseq*L, 3*H*64] = Q | K | V;  mask: int64 [nseq, L], 0 = padded key, or NULL;
- * ctx: bf16 [nseq*L, H*64];  lse: fp32 [nseq, H, L] (NULL allowed in forward-only use). */
-int cldrd_attention_fwd(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H,
-                        float dropout_p, unsigned long long seed, int fmt, void* stream);
-int cldrd_attention_bwd(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                        void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, void* stream);
-
-/* Dropout keep bits.  For L <= 128 and at least two (sequence, head) items per CU the forward runs as a persistent loader / compute
- * kernel whose loader waves evaluate the dropout hash and leave the keep decisions behind as bits ([item][key block][query] dwords);
- * the backward for the same (nseq, L, H, dropout_p, seed) then reads them instead of hashing again.  cldrd_attention_bits_words()
- * says how many 32-bit words that is for a shape (0: this shape does not produce bits - pass null and the backward re-hashes). */
+ * One entry point per operation; the layout of the [rows, .] tensors (qkv, ctx, dctx, dqkv, kv, dkv) is said by the arguments behind them:
+ *   cu_rows == NULL  PADDED: rows = nseq * L, sequence m owns rows m * L .. m * L + L - 1; mask: int64 [nseq, L], 0 = padded key, or NULL.
+ *   cu_rows != NULL  PACKED (layout of "packed batches" below): sequence m owns rows cu_rows[m] .. cu_rows[m + 1], rows = cu_rows[nseq]; cu_rows:
+ *                    device int32 [nseq + 1], every length in 1 .. L.  mask must be NULL: keys beyond a sequence's length are masked (right padding:
+ *                    what the tokenizer's attention_mask says) and padding rows are neither loaded nor stored.  The reference pads every sequence of
+ *                    a batch to the longest (dataset/nway_dataset.py:105-106, dataset/sequence_dataset.py:50-51) and HF attention then computes on
+ *                    the padding.  Results are bit for bit those of cldrd_unpack_rows16 -> the padded call -> cldrd_gather_rows.
+ *   seq_list != NULL a LIST of a packed batch's sequences (needs cu_rows; device int32 [n_list], positions in 0 .. nseq - 1, 0 < n_list <= nseq, each
+ *                    listed sequence at most Ltile tokens long, 0 < Ltile <= L): the launch runs the kernels of tile height Ltile.  A packed batch at
+ *                    L = 256 sends its sequences of at most 128 tokens (most of an MS MARCO batch) through the persistent L <= 128 kernels and the
+ *                    others through a second call.  seq_list == NULL: n_list and Ltile are ignored.
+ * lse, probs and the keep bits are [nseq, H, L(, ..)] in every layout: LSE rows and dropout row keys keep the stride L of the batch, so forward and
+ * backward of a sequence must be given the same nseq and L (the lists may differ).
+ * qkv: [rows, 3*H*64] = Q | K | V;  ctx: [rows, H*64];  lse: fp32 [nseq, H, L] (NULL allowed in forward-only use, required by the backward).
+ * fmt: CLDRD_FMT_BF16; CLDRD_FMT_F16_TAPE: q / k / v, ctx, dctx and dqkv are fp16 (a training pass of the fp16 mode); forward only: CLDRD_FMT_F16
+ * (fp16, rows of at most 128 tokens, no keep bits: evaluation passes).  The backward takes any non-zero fmt as fp16.
+ * Dropout keep bits: for L <= 128 and at least two (sequence, head) items per CU the forward runs as a persistent loader / compute kernel whose
+ * loader waves evaluate the dropout hash and leave the keep decisions behind as bits in drop_bits_out ([item][key block][query] dwords, optional);
+ * the backward for the same (nseq, L, H, dropout_p, seed) then reads them (drop_bits) instead of hashing again.  cldrd_attention_bits_words() says
+ * how many 32-bit words that is for a shape (0: this shape does not produce bits - pass NULL and the backward re-hashes).
+ * ctx_f16_copy (optional, bf16 pass only): the same context vectors in fp16 - the A operand of an fp16-operand out-projection GEMM (round 3: the
+ * out-projection's operands carry most of the remaining logit drift of a 12-layer tower); ctx may then be NULL (no bf16 tape wanted). */
 long long cldrd_attention_bits_words(int nseq, int L, int H, float dropout_p);
-/* ctx_f16_copy (optional, bf16 pass only): the same context vectors in fp16 - the A operand of an fp16-operand out-projection GEMM (round 3:
- * the out-projection's operands carry most of the remaining logit drift of a 12-layer tower); ctx may then be NULL (no bf16 tape wanted). */
-int cldrd_attention_fwd_bits(const void* qkv, const long long* mask, void* ctx, float* lse, int nseq, int L, int H,
-                             float dropout_p, unsigned long long seed, int fmt, void* drop_bits_out, void* ctx_f16_copy, void* stream);
-int cldrd_attention_bwd_bits(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                             void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits,
-                             void* stream);
-/* the same with a format: fmt != CLDRD_FMT_BF16 - q / k / v, ctx, dctx and dqkv are fp16 (a training pass of the fp16 mode) */
-int cldrd_attention_bwd_x(const void* qkv, const long long* mask, const void* ctx, const void* dctx, const float* lse,
-                             void* dqkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits, int fmt,
-                             void* stream);
+int cldrd_attention_fwd(const void* qkv, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile,
+                        void* ctx, float* lse, int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt,
+                        void* drop_bits_out, void* ctx_f16_copy, void* stream);
+int cldrd_attention_bwd(const void* qkv, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile,
+                        const void* ctx, const void* dctx, const float* lse, void* dqkv, int nseq, int L, int H, float dropout_p,
+                        unsigned long long seed, int fmt, const void* drop_bits, void* stream);
 
 /* CLS-only attention of the LAST layer (the reference pools last_hidden_state[:, 0, :], models/nway_dual_encoder.py:52,56,64):
- * qc: bf16 [nseq, H*64] = queries of token 0; kv: bf16 [nseq*L, 2*H*64] = K | V of every token; ctx/dctx/dqc: bf16 [nseq, H*64];
- * probs: fp32 [nseq, H, L] (softmax row, saved for the backward); dkv: bf16 [nseq*L, 2*H*64] (every row written).
+ * qc: [nseq, H*64] = queries of token 0; kv: [rows, 2*H*64] = K | V of every token, padded or packed as above (no lists); ctx/dctx/dqc: [nseq, H*64];
+ * probs: fp32 [nseq, H, L] (softmax row, saved for the backward; required); dkv: [rows, 2*H*64] in the layout of kv (every row written).
  * cldrd_add_rows_strided: dst[m * stride_rows] += src[m] for bf16 rows of d elements (puts the CLS-row gradients back). */
-int cldrd_attention_cls_fwd(const void* qc, const void* kv, const long long* mask, void* ctx, float* probs, int nseq, int L,
-                            int H, float dropout_p, unsigned long long seed, int fmt, void* ctx_f16_copy, void* stream);
-int cldrd_attention_cls_bwd(const void* qc, const void* kv, const float* probs, const void* dctx, void* dqc, void* dkv,
-                            int nseq, int L, int H, float dropout_p, unsigned long long seed, void* stream);
-int cldrd_attention_cls_bwd_x(const void* qc, const void* kv, const float* probs, const void* dctx, void* dqc, void* dkv,
+int cldrd_attention_cls_fwd(const void* qc, const void* kv, const long long* mask, const int* cu_rows, void* ctx, float* probs,
+                            int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* ctx_f16_copy, void* stream);
+int cldrd_attention_cls_bwd(const void* qc, const void* kv, const int* cu_rows, const float* probs, const void* dctx, void* dqc, void* dkv,
                             int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* stream);
 int cldrd_add_rows_strided(void* dst, const void* src, int M, int d, int stride_rows, int f32, void* stream);   /* f32: fp32 rows (fp32 gradient stream) */
-
-/* The four attention calls on a PACKED batch (round 6; layout of "packed batches" below: sequence m owns rows cu_rows[m] .. cu_rows[m + 1] of every
- * [Tp, .] tensor, Tp = cu_rows[nseq]; cu_rows: int32 [nseq + 1] on the device, every length in 1 .. L).  The reference pads every sequence of a batch
- * to the longest (dataset/nway_dataset.py:105-106, dataset/sequence_dataset.py:50-51) and HF attention then computes on the padding; here keys
- * beyond a sequence's length are masked (right padding: what the tokenizer's attention_mask says; no mask tensor is read) and padding rows are
- * neither loaded nor stored.  qkv / ctx / dctx / dqkv / kv / dkv are [Tp, .]; lse, probs and the keep bits keep their [nseq, H, L(, ..)] shapes.
- * Results are bit for bit those of cldrd_unpack_rows16 -> the padded call -> cldrd_gather_rows. */
-int cldrd_attention_fwd_varlen(const void* qkv_packed, const int* cu_rows, void* ctx_packed, float* lse, int nseq, int L, int H,
-                               float dropout_p, unsigned long long seed, int fmt, void* drop_bits_out, void* ctx_f16_copy, void* stream);
-int cldrd_attention_bwd_varlen(const void* qkv_packed, const int* cu_rows, const void* ctx_packed, const void* dctx_packed, const float* lse,
-                               void* dqkv_packed, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits,
-                               int fmt, void* stream);
-/* ... for a LIST of the batch's sequences (seq_list: device int32 [n_list], positions in 0 .. nseq - 1, each sequence at most Ltile <= L tokens
- * long): the launch runs the kernels of tile height Ltile.  A packed batch at L = 256 sends its sequences of at most 128 tokens (most of an
- * MS MARCO batch) through the persistent L <= 128 kernels and the others through a second call; LSE rows and dropout row keys keep the stride L
- * of the batch, so forward and backward of a sequence must be given the same L (the lists may differ). */
-int cldrd_attention_fwd_varlen_list(const void* qkv_packed, const int* cu_rows, void* ctx_packed, float* lse, int nseq, int L, int H,
-                                    float dropout_p, unsigned long long seed, int fmt, void* drop_bits_out, void* ctx_f16_copy,
-                                    const int* seq_list, int n_list, int Ltile, void* stream);
-int cldrd_attention_bwd_varlen_list(const void* qkv_packed, const int* cu_rows, const void* ctx_packed, const void* dctx_packed, const float* lse,
-                                    void* dqkv_packed, int nseq, int L, int H, float dropout_p, unsigned long long seed, const void* drop_bits,
-                                    int fmt, const int* seq_list, int n_list, int Ltile, void* stream);
-int cldrd_attention_cls_fwd_varlen(const void* qc, const void* kv_packed, const int* cu_rows, void* ctx, float* probs, int nseq, int L, int H,
-                                   float dropout_p, unsigned long long seed, int fmt, void* ctx_f16_copy, void* stream);
-int cldrd_attention_cls_bwd_varlen(const void* qc, const void* kv_packed, const int* cu_rows, const float* probs, const void* dctx, void* dqc,
-                                   void* dkv_packed, int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* stream);
 
 /* ---- embeddings + LayerNorm (HF Embeddings.forward, sa_layer_norm / output_layer_norm) --------------------
  * d <= 1024, d % 4 == 0.  `partial` scratch: cldrd_ln_partial_blocks(T) * 3 * d floats. */
@@ -364,7 +332,7 @@ int cldrd_map_ids(const int* I, const long long* ids, long long id_offset, long 
  * The reference pads every sequence of a batch to the longest one (dataset/sequence_dataset.py:50-51, nway_dataset.py:103-107) and the
  * encoder computes on the padding.  Packed layout: tokens of sequence m = rows cu[m] .. cu[m+1] of a [Tp, features] matrix (cu: device
  * int32 [nseq + 1]); Linear / LayerNorm / weight gradients run on the Tp real rows, attention on the same rows through the
- * cldrd_attention_*_varlen calls above (until round 6: on the padded [nseq * L, .] layout, rows moved by the two calls below).
+ * cldrd_attention_* calls above given cu_rows (until round 6: on the padded [nseq * L, .] layout, rows moved by the two calls below).
  * cldrd_embed_ln_fwd / _bwd take pos_idx (device int32 [T], the position of every row inside its sequence; NULL: row % L).
  *   unpack_rows16: dst[m * L + j] = j < len[m] ? src[cu[m] + j] : 0  (16-bit rows of w elements);  gather_rows: dst[p] = src[idx[p]]
  *   (rows of row_bytes bytes: packing, CLS rows);  scatter_cls_grad_idx: g = 0, g[idx[r]] = bf16(dcls[r]);  add_rows_idx: dst[idx[m]] += src[m]. */

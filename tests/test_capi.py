@@ -73,6 +73,47 @@ def test_version_and_error_string_without_gpu():
     assert isinstance(lib.cldrd_last_error(), bytes)
 
 
+def test_attention_entry_points_reject_inconsistent_layouts():
+    """The layout rule of include/cldrd_hip.h (mask / cu_rows / seq_list, n_list, Ltile) and the other argument checks of the four attention entry
+    points, without a GPU: every call below is rejected by a check in front of any HIP call, so small integers stand in for the device pointers.
+    No call here may pass the checks - a fake pointer must never reach a launch."""
+    from cldrd_amd import _lib
+    lib = _lib.load()
+    P, nseq, L, H = 64, 4, 32, 2            # P: any non-null "pointer"
+
+    def fwd(mask=None, cu=None, sl=None, n_list=0, Ltile=0, ctx=P, lse=P, L=L, fmt=0, bits=None, ctx16=None):
+        return "attention_fwd", lib.cldrd_attention_fwd(P, mask, cu, sl, n_list, Ltile, ctx, lse, nseq, L, H, 0.1, 7, fmt, bits, ctx16, None)
+
+    def bwd(mask=None, cu=None, sl=None, n_list=0, Ltile=0, lse=P, L=L, fmt=0):
+        return "attention_bwd", lib.cldrd_attention_bwd(P, mask, cu, sl, n_list, Ltile, P, P, lse, P, nseq, L, H, 0.1, 7, fmt, None, None)
+
+    def cls_fwd(mask=None, cu=None, ctx=P, probs=P, L=L, fmt=0, ctx16=None):
+        return "attention_cls_fwd", lib.cldrd_attention_cls_fwd(P, P, mask, cu, ctx, probs, nseq, L, H, 0.1, 7, fmt, ctx16, None)
+
+    def cls_bwd(cu=None, L=L):
+        return "attention_cls_bwd", lib.cldrd_attention_cls_bwd(P, P, cu, P, P, P, P, nseq, L, H, 0.1, 7, 0, None)
+
+    cases = [
+        lambda: fwd(mask=P, cu=P), lambda: bwd(mask=P, cu=P), lambda: cls_fwd(mask=P, cu=P),              # mask together with cu_rows
+        lambda: fwd(sl=P, n_list=2, Ltile=L), lambda: bwd(sl=P, n_list=2, Ltile=L),                        # seq_list without cu_rows
+        lambda: fwd(cu=P, sl=P, n_list=0, Ltile=L), lambda: bwd(cu=P, sl=P, n_list=0, Ltile=L),            # n_list = 0
+        lambda: fwd(cu=P, sl=P, n_list=nseq + 1, Ltile=L), lambda: bwd(cu=P, sl=P, n_list=nseq + 1, Ltile=L),
+        lambda: fwd(cu=P, sl=P, n_list=2, Ltile=L + 1), lambda: bwd(cu=P, sl=P, n_list=2, Ltile=L + 1),
+        lambda: fwd(L=257), lambda: bwd(L=257), lambda: cls_fwd(L=257), lambda: cls_bwd(L=257), lambda: cls_bwd(cu=P, L=257),
+        lambda: fwd(ctx=None, ctx16=None),                                                                 # no output
+        lambda: fwd(fmt=1, ctx16=P), lambda: cls_fwd(fmt=1, ctx16=P),                                      # the fp16 pass writes ctx only
+        lambda: fwd(fmt=2),
+        lambda: bwd(lse=None),
+        lambda: cls_fwd(probs=None),
+    ]
+    for i, case in enumerate(cases):
+        lib.cldrd_set_tuning(None, 0)       # leaves "set_tuning: null key" behind: the message read below is this case's own
+        op, rc = case()
+        msg = lib.cldrd_last_error().decode()
+        assert rc != 0, f"case {i} ({op}) was not rejected"
+        assert msg.startswith(op + ":") and len(msg) > len(op) + 2, f"case {i}: {msg!r}"
+
+
 def test_no_cpu_fallback():
     """Ops refuse CPU tensors instead of silently computing on the host."""
     from cldrd_amd import hip_ops as ops

@@ -18,7 +18,7 @@ def stubbed(monkeypatch):
         _lib.load()
     except Exception as e:
         pytest.skip(f"libcldrd_hip.so not built: {e}")
-    calls = []
+    calls = _Calls()
 
     def chk(t, dtype, name, dim=None):
         if not isinstance(t, torch.Tensor):
@@ -31,11 +31,29 @@ def stubbed(monkeypatch):
             raise ValueError(f"{name}: last dim must be contiguous")
         return t
     monkeypatch.setattr(ops, "_chk", chk)
-    monkeypatch.setattr(ops, "call", lambda name, *a: calls.append(name))
+    monkeypatch.setattr(ops, "call", lambda name, *a: (calls.append(name), calls.args.append((name, a))))
     monkeypatch.setattr(ops, "_stream", lambda: 0)
     monkeypatch.setattr(HipEncoder, "refresh_shadows", lambda self, need_transposed=True, cast=True, cast16=None, h_stale=False: _cpu_shadows(self))
     monkeypatch.setattr(HipEncoder, "_shadows_ok", lambda self, need_t, need_h=True: self.flat_h is not None)
     return calls
+
+
+class _Calls(list):
+    """The entry-point names in call order (what most tests look at); ``args``: (name, argument tuple) of the same calls."""
+
+    def __init__(self):
+        super().__init__()
+        self.args = []
+
+
+# position of cu_rows (and, for the full-attention calls, of seq_list) in the C signatures of include/cldrd_hip.h
+_CU_ARG = {"cldrd_attention_fwd": 2, "cldrd_attention_bwd": 2, "cldrd_attention_cls_fwd": 3, "cldrd_attention_cls_bwd": 2}
+_LIST_ARG = 3
+
+
+def _cu_set(recorded, name):
+    """For every recorded call of ``name``: is its cu_rows argument non-null (the packed layout)?"""
+    return [a[_CU_ARG[name]] is not None for n, a in recorded if n == name]
 
 
 def _cpu_shadows(enc):
@@ -82,15 +100,17 @@ def test_forward_backward_walks_every_mode(stubbed, monkeypatch, arch, layers, p
         enc.backward_from_cls(tape, torch.zeros(M, 128), after_layer=hooks.append, accumulate=False)
         assert sorted(hooks) == list(range(-1, layers))        # every bucket reported once (the embedding block before the last weight-gradient group)
     kinds = set(stubbed)
-    assert "cldrd_gemm_nt16_ws" in kinds and "cldrd_wgrad_group" in kinds and "cldrd_embed_ln_bwd" in kinds
-    assert ("cldrd_attention_cls_fwd_varlen" in kinds) == packed and ("cldrd_attention_cls_bwd_varlen" in kinds) == packed
-    assert ("cldrd_attention_fwd_varlen" in kinds) == (packed and layers > 1) and ("cldrd_attention_bwd_varlen" in kinds) == (packed and layers > 1)
+    assert "cldrd_gemm_nt16" in kinds and "cldrd_wgrad_group" in kinds and "cldrd_embed_ln_bwd" in kinds
+    for name in ("cldrd_attention_cls_fwd", "cldrd_attention_cls_bwd"):       # the packed layout is said by the cu_rows argument
+        assert any(_cu_set(stubbed.args, name)) == packed, name
+    for name in ("cldrd_attention_fwd", "cldrd_attention_bwd"):              # (a one-layer tower has only the CLS-only last layer)
+        assert any(_cu_set(stubbed.args, name)) == (packed and layers > 1), name
     assert "cldrd_unpack_rows16" not in kinds                      # round 6: attention reads the packed rows through cu, no row moves
 
 
 @pytest.mark.parametrize("lens,want", [([200, 3, 10, 130, 5, 128], 2), ([100, 3, 10, 128, 5, 64], 1), ([200, 150, 129, 130, 131, 199], 0)])
 def test_packed_batches_above_128_tokens_split_their_attention_launches_by_length(stubbed, monkeypatch, lens, want):
-    """encoder._Pack at L > 128: the sequences of at most 128 tokens go through the L <= 128 kernels (cldrd_attention_*_varlen_list with tile 128),
+    """encoder._Pack at L > 128: the sequences of at most 128 tokens go through the L <= 128 kernels (cldrd_attention_fwd / _bwd with a seq_list and tile 128),
     the others through a second launch at tile L; all short: one listed launch; all long: the plain packed launch."""
     monkeypatch.setenv("CLDRD_AMP", "fp16")
     cfg = EncoderConfig(arch="distilbert", vocab_size=512, dim=128, n_heads=2, hidden_dim=256, n_layers=2, max_position_embeddings=256,
@@ -106,9 +126,11 @@ def test_packed_batches_above_128_tokens_split_their_attention_launches_by_lengt
     if want:
         assert sorted(int(i) for sl, _ in tape.pack.groups for i in sl.tolist()) == list(range(M))
     enc.backward_from_cls(tape, torch.randn(M, cfg.dim))
-    calls = stubbed[n0:]
-    fwd_l, bwd_l = calls.count("cldrd_attention_fwd_varlen_list"), calls.count("cldrd_attention_bwd_varlen_list")
-    assert fwd_l == bwd_l == want * 1 and calls.count("cldrd_attention_fwd_varlen") == calls.count("cldrd_attention_bwd_varlen") == (0 if want else 1)
+    for name in ("cldrd_attention_fwd", "cldrd_attention_bwd"):
+        calls = [a for n, a in stubbed.args[n0:] if n == name]
+        listed = sum(a[_LIST_ARG] is not None for a in calls)
+        plain_packed = sum(a[_CU_ARG[name]] is not None and a[_LIST_ARG] is None for a in calls)
+        assert listed == want * 1 and plain_packed == (0 if want else 1), name
 
 
 def test_trainer_step_walks_with_stubbed_kernels(stubbed, monkeypatch):
@@ -160,7 +182,7 @@ def test_window_scheduled_step_walks_and_interleaves_the_two_towers(stubbed, mon
     assert sorted(seqs[True]) == sorted(seqs[False]) and seqs[True] != seqs[False]
     # free-running: the query tower's whole forward (its embedding kernel first) is enqueued before the passage tower's first launch;
     # windowed: the passage tower's embedding kernel comes first and the two towers' attention launches alternate
-    first_attn = [i for i, n in enumerate(seqs[True]) if n.startswith("cldrd_attention_fwd")]
+    first_attn = [i for i, n in enumerate(seqs[True]) if n == "cldrd_attention_fwd"]
     assert len(first_attn) >= 4
     emb = [i for i, n in enumerate(seqs[True]) if n == "cldrd_embed_ln_fwd"]
     assert len(emb) == 2 and emb[1] - emb[0] <= 3           # both embedding launches at the very start of the windowed forward
