@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # change of ABI_VERSION uses two checkouts).  The library itself reads no environment variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
 
-ABI_VERSION = 101          # cldrd_version() of the build SIGNATURES describes
+ABI_VERSION = 102          # cldrd_version() of the build SIGNATURES describes
 
 _lib = None
 
@@ -33,16 +33,15 @@ SIGNATURES = {
     "cldrd_attention_cls_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp]),
     "cldrd_attention_cls_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp]),
     "cldrd_attention_bits_words": (C.c_longlong, [ci, ci, ci, cf]),
-    "cldrd_add_rows_strided": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+    "cldrd_add_rows": (ci, [vp, vp, ci, ci, ci, vp, ci, vp]),
     "cldrd_ln_partial_blocks": (ci, [ci]),
-    "cldrd_embed_ln_fwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp, vp]),
-    "cldrd_embed_ln_fwd_typed": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp, vp]),
-    "cldrd_embed_ln_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cull, ci, vp, ci, vp, vp]),
+    "cldrd_embed_ln_fwd": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp, vp]),
+    "cldrd_embed_ln_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cull, ci, vp, ci, ci, vp, vp]),
     "cldrd_layernorm_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, ci, vp, ci, vp, vp]),
-    "cldrd_layernorm_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cull, ci, ci, vp, vp]),
+    "cldrd_layernorm_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cull, ci, ci, ci, ci, vp, vp]),
     "cldrd_ln_reduce_group": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_colsum_bf16": (ci, [vp, vp, vp, ci, ci, ci, ci, vp]),
-    "cldrd_scatter_cls_grad": (ci, [vp, vp, ci, ci, ci, ci, ci, vp]),
+    "cldrd_scatter_cls_grad": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, vp]),
     "cldrd_score_fwd": (ci, [vp, vp, vp, ci, ci, ci, ci, vp]),
     "cldrd_score_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "cldrd_loss_fwd_bwd": (ci, [ci, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, ci, vp]),
@@ -55,37 +54,29 @@ SIGNATURES = {
     "cldrd_clip_coef": (ci, [vp, ci, cf, vp, vp]),
     "cldrd_copy_segments": (ci, [vp, vp, vp, ci, vp]),
     "cldrd_zero_segments": (ci, [vp, vp, ci, vp]),
-    "cldrd_adamw_step": (ci, [vp, vp, vp, vp, vp, vp, csz, cf, cf, cf, cf, cf, ci, vp, vp]),
-    "cldrd_adamw_step_h16": (ci, [vp, vp, vp, vp, vp, vp, csz, cf, cf, cf, cf, cf, ci, vp, vp, csz, csz, vp]),
+    "cldrd_adamw_step": (ci, [vp, vp, vp, vp, vp, vp, csz, cf, cf, cf, cf, cf, ci, vp, vp, csz, csz, vp]),
     "cldrd_cast_bf16": (ci, [vp, vp, csz, vp]),
     "cldrd_transpose_cast_batched": (ci, [vp, vp, vp, vp, ci, ci, vp]),
     "cldrd_transpose_bf16_batched": (ci, [vp, vp, vp, vp, ci, ci, vp]),
-    "cldrd_topk_scan_filter": (ci, [vp, vp, ci, C.c_longlong, ci, vp, vp, vp, vp, ci, ci, vp]),
-    "cldrd_topk_scan_filter_tiled": (ci, [vp, vp, ci, C.c_longlong, ci, vp, vp, vp, vp, ci, ci, vp]),
+    "cldrd_topk_scan_filter": (ci, [vp, vp, ci, C.c_longlong, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_cast_f16": (ci, [vp, vp, csz, vp, vp]),
     "cldrd_topk_prep_queries": (ci, [vp, vp, vp, vp, ci, ci, vp, vp]),
     "cldrd_topk_thresholds": (ci, [vp, vp, cf, ci, vp, vp, ci, vp]),
     "cldrd_topk_select": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
-    "cldrd_flatip_search": (ci, [vp, vp, vp, vp, vp, vp, C.c_longlong, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp]),
+    "cldrd_flatip_search": (ci, [vp, vp, vp, vp, vp, vp, vp, C.c_longlong, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp]),
     "cldrd_topk_kth_largest": (ci, [vp, ci, ci, ci, ci, vp, vp]),
-    "cldrd_topk_rescore": (ci, [vp, vp, ci, vp, vp, vp, ci, ci, vp]),
+    "cldrd_topk_rescore": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, vp]),
     "cldrd_topk_sort": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
     "cldrd_row_sqnorm_max": (ci, [vp, csz, ci, vp, vp]),
-    "cldrd_gather_cast_rows": (ci, [vp, vp, csz, csz, ci, vp]),
+    "cldrd_gather_cast_rows": (ci, [vp, ci, vp, csz, csz, ci, vp]),
     "cldrd_index_col_mean_workspace": (csz, [csz, ci]),
     "cldrd_index_col_mean": (ci, [vp, csz, ci, vp, vp, csz, vp]),
-    "cldrd_index_center_cast": (ci, [vp, vp, csz, ci, vp, vp, csz, csz, vp, vp, vp]),
+    "cldrd_index_center_cast": (ci, [vp, vp, csz, csz, ci, vp, vp, csz, csz, vp, vp, vp]),
     "cldrd_map_ids": (ci, [vp, vp, C.c_longlong, vp, csz, vp]),
     "cldrd_query_dot64": (ci, [vp, vp, ci, vp, ci, vp]),
-    "cldrd_topk_rescore16": (ci, [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp]),
-    "cldrd_flatip_search16": (ci, [vp, vp, vp, vp, vp, vp, C.c_longlong, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp]),
-    "cldrd_gather_cast_rows16": (ci, [vp, vp, csz, csz, ci, vp]),
-    "cldrd_index_center_cast_chunk": (ci, [vp, vp, csz, csz, ci, vp, vp, csz, csz, vp, vp, vp]),
     "cldrd_unpack_rows16": (ci, [vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_gather_rows": (ci, [vp, vp, vp, ci, ci, vp]),
     "cldrd_gather_i64": (ci, [vp, vp, vp, ci, vp]),
-    "cldrd_scatter_cls_grad_idx": (ci, [vp, vp, ci, ci, vp, ci, ci, vp]),
-    "cldrd_add_rows_idx": (ci, [vp, vp, ci, ci, vp, ci, vp]),
     "cldrd_set_seed_base": (None, [vp]),
     "cldrd_set_optim_hyper": (None, [vp]),
     "cldrd_set_loss_scale": (None, [vp, ci]),

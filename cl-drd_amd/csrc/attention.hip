@@ -1772,11 +1772,16 @@ extern "C" int cldrd_attention_cls_bwd(const void* qc, const void* kv, const int
     return 0;
 }
 
-extern "C" int cldrd_add_rows_strided(void* dst, const void* src, int M, int d, int stride_rows, int f32, void* stream) {
-    CLDRD_CHECK(M > 0 && d > 0 && stride_rows > 0, "add_rows_strided: bad shape");
-    if (f32 == 1) hipLaunchKernelGGL(add_rows_strided_kernel<1>, dim3(M), dim3(256), 0, (hipStream_t)stream, dst, src, M, d, stride_rows);
-    else if (f32 == 2) hipLaunchKernelGGL(add_rows_strided_kernel<2>, dim3(M), dim3(256), 0, (hipStream_t)stream, dst, src, M, d, stride_rows);
-    else hipLaunchKernelGGL(add_rows_strided_kernel<0>, dim3(M), dim3(256), 0, (hipStream_t)stream, dst, src, M, d, stride_rows);
+int cldrd_launch_add_rows_idx(void* dst, const void* src, int M, int d, const int* idx, int fmt, hipStream_t st);      // pack.hip
+// dst[idx ? idx[m] : m * stride_rows] += src[m]; fmt: enum cldrd_stream_fmt
+extern "C" int cldrd_add_rows(void* dst, const void* src, int M, int d, int stride_rows, const int* idx, int fmt, void* stream) {
+    CLDRD_CHECK(M > 0 && d > 0 && (idx || stride_rows > 0), "add_rows: bad shape");
+    if (idx) return cldrd_launch_add_rows_idx(dst, src, M, d, idx, fmt, (hipStream_t)stream);
+    decltype(&add_rows_strided_kernel<1>) kern;      // fmt: 0 bf16, 1 fp32, 2 fp16
+    if (fmt == 1) kern = add_rows_strided_kernel<1>;
+    else if (fmt == 2) kern = add_rows_strided_kernel<2>;
+    else kern = add_rows_strided_kernel<0>;
+    hipLaunchKernelGGL(kern, dim3(M), dim3(256), 0, (hipStream_t)stream, dst, src, M, d, stride_rows);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }

@@ -24,7 +24,7 @@ extern "C" int cldrd_set_tuning(const char* key, int value) {
     if (!strcmp(key, "gemm_nt64")) { g_cldrd_tune_nt64 = value != 0; return 0; }
     return cldrd_set_error("set_tuning: unknown key");
 }
-extern "C" int cldrd_version(void) { return 101; }
+extern "C" int cldrd_version(void) { return 102; }
 extern "C" int cldrd_device_ok(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return 0;
@@ -40,7 +40,7 @@ thread_local const float* g_cldrd_optim_hyper = nullptr;
 
 // Every launch made by this thread from now on adds *base (read on the device, at run time) to its dropout seed; null: off.
 extern "C" void cldrd_set_seed_base(const unsigned long long* base) { g_cldrd_seed_base = base; }
-// cldrd_adamw_step* launched by this thread from now on take {lr, step size = lr sqrt(1 - beta2^t) / (1 - beta1^t)} from this device
+// cldrd_adamw_step calls of this thread from now on take {lr, step size = lr sqrt(1 - beta2^t) / (1 - beta1^t)} from this device
 // float[2] instead of their by-value arguments; null: off.
 extern "C" void cldrd_set_optim_hyper(const float* hyper) { g_cldrd_optim_hyper = hyper; }
 // Loss scaling of the all-fp16 training mode (reference: torch.cuda.amp.GradScaler around nway_listwise_1.py:334-359).  scale = device

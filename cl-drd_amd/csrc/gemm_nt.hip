@@ -496,8 +496,9 @@ extern "C" int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int
 
 // Top-k scan over one index shard: scores = Q[nq,d] . P[rows,d]^T on bf16 MFMA; every (query, row) with score >= thr[query]
 // is appended to the query's candidate list (counts must be zeroed by the caller; counts[q] may exceed cap = overflow).
-static int scan_filter_impl(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
-                            int* cand_rows, float* cand_scores, int cap, int f16, void* stream, bool tiled) {
+// tiled != 0: always through the tiled kernels (hits go straight to the global lists: never sets counts[nq]).
+extern "C" int cldrd_topk_scan_filter(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
+                                      int* cand_rows, float* cand_scores, int cap, int f16, int tiled, void* stream) {
     CLDRD_CHECK(nq > 0 && rows > 0 && rows < 2147483647LL && d % BK == 0 && cap > 0, "topk_scan_filter: bad arguments");
     CLDRD_CHECK(((uintptr_t)Q % 16 == 0) && ((uintptr_t)P % 16 == 0), "topk_scan_filter: operands must be 16-byte aligned");
     GemmNtArgs a;
@@ -517,15 +518,4 @@ static int scan_filter_impl(const void* Q, const void* P, int nq, long long rows
         return cldrd_gemm_nt_ring_scan(a, (hipStream_t)stream);
     }
     return f16 ? launch_nt<EPI_FILTER | EPI_F16IN>(a, (hipStream_t)stream) : launch_nt<EPI_FILTER>(a, (hipStream_t)stream);
-}
-
-extern "C" int cldrd_topk_scan_filter(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
-                                      int* cand_rows, float* cand_scores, int cap, int f16, void* stream) {
-    return scan_filter_impl(Q, P, nq, rows, d, thr, counts, cand_rows, cand_scores, cap, f16, stream, false);
-}
-
-// Same contract, always through the tiled kernels (hits go straight to the global lists: never sets counts[nq]).
-extern "C" int cldrd_topk_scan_filter_tiled(const void* Q, const void* P, int nq, long long rows, int d, const float* thr,
-                                            int* counts, int* cand_rows, float* cand_scores, int cap, int f16, void* stream) {
-    return scan_filter_impl(Q, P, nq, rows, d, thr, counts, cand_rows, cand_scores, cap, f16, stream, true);
 }

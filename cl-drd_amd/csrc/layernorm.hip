@@ -594,6 +594,8 @@ static void ln_dispatch(int d, bool drop, F&& f) {
     else { if (drop) f(std::integral_constant<int, 0>{}, T_{}); else f(std::integral_constant<int, 0>{}, F_{}); }
 }
 
+enum { STREAM_BF16 = 0, STREAM_F32 = 1, STREAM_F16 = 2 };      // enum cldrd_stream_fmt of include/cldrd_hip.h: the format of gradient-stream rows
+
 static inline int ln_bwd_blocks(int T) {
     const int cap = 512;
     int b = (T + 7) / 8;
@@ -616,37 +618,26 @@ extern "C" int cldrd_layernorm_fwd(const void* x, const float* gamma, const floa
     return 0;
 }
 
-extern "C" int cldrd_embed_ln_fwd(const long long* ids, const float* word, const float* pos, const float* type0,
-                                  const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
+// Token types: type_ids == nullptr: every row takes row 0 of type_table (null for DistilBERT); else per row (cross-encoder pairs): type_table
+// [type_vocab, d] fp32, type_ids device int32 [T] (clamped to the table) - the same kernel body, a template flag
+extern "C" int cldrd_embed_ln_fwd(const long long* ids, const float* word, const float* pos, const float* type_table, const int* type_ids,
+                                  int type_vocab, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
                                   int d, int vocab, float eps, float dropout_p, unsigned long long seed, float* out32, int out_f16,
                                   const int* pos_idx, void* out_bf16_copy, void* stream) {
     CLDRD_CHECK(out_bf16_copy == nullptr || out_f16, "embed_ln_fwd: the bf16 copy goes with an fp16 output");
     CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0 && L > 0, "embed_ln_fwd: bad shape");
+    CLDRD_CHECK(type_ids == nullptr || (type_table != nullptr && type_vocab > 0), "embed_ln_fwd: type ids need the token-type table");
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
-    ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
-        hipLaunchKernelGGL((embed_ln_fwd_kernel<decltype(dc)::value, decltype(dr)::value>), dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                           (const int64_t*)ids, word, pos, type0, gamma, beta, (bf16_t*)out, out32, mean, rstd, T, L, d, vocab, eps, th,
-                           1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, (bf16_t*)out_bf16_copy, nullptr, 1);
-    });
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-
-// The same with per-row token types (cross-encoder pairs): type_table [type_vocab, d] fp32, type_ids device int32 [T] (clamped to the table)
-extern "C" int cldrd_embed_ln_fwd_typed(const long long* ids, const float* word, const float* pos, const float* type_table,
-                                        const int* type_ids, int type_vocab, const float* gamma, const float* beta, void* out, float* mean,
-                                        float* rstd, int T, int L, int d, int vocab, float eps, float dropout_p, unsigned long long seed,
-                                        float* out32, int out_f16, const int* pos_idx, void* out_bf16_copy, void* stream) {
-    CLDRD_CHECK(out_bf16_copy == nullptr || out_f16, "embed_ln_fwd_typed: the bf16 copy goes with an fp16 output");
-    CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0 && L > 0, "embed_ln_fwd_typed: bad shape");
-    CLDRD_CHECK(type_table != nullptr && type_ids != nullptr && type_vocab > 0, "embed_ln_fwd_typed: needs the token-type table and type ids");
-    const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
-    ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
-        hipLaunchKernelGGL((embed_ln_fwd_kernel<decltype(dc)::value, decltype(dr)::value, true>), dim3((T + 3) / 4), dim3(256), 0,
-                           (hipStream_t)stream, (const int64_t*)ids, word, pos, type_table, gamma, beta, (bf16_t*)out, out32, mean, rstd, T, L,
-                           d, vocab, eps, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, (bf16_t*)out_bf16_copy,
-                           type_ids, type_vocab);
-    });
+    auto launch = [&](auto typed) {
+        ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
+            hipLaunchKernelGGL((embed_ln_fwd_kernel<decltype(dc)::value, decltype(dr)::value, decltype(typed)::value>), dim3((T + 3) / 4), dim3(256), 0,
+                               (hipStream_t)stream, (const int64_t*)ids, word, pos, type_table, gamma, beta, (bf16_t*)out, out32, mean, rstd, T, L,
+                               d, vocab, eps, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, (bf16_t*)out_bf16_copy,
+                               type_ids, type_ids ? type_vocab : 1);
+        });
+    };
+    if (type_ids == nullptr) launch(std::false_type{});
+    else launch(std::true_type{});
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
@@ -702,40 +693,32 @@ static int launch_reduce(const float* partial, int nblk, int d, float* o0, float
 
 // partial must hold cldrd_ln_partial_blocks(T) * 3 * d floats.  dgamma/dbeta/dbias are accumulated (+=) when accumulate != 0.
 // All three null: the reduction is deferred - `partial` keeps the per-block sums for a later cldrd_ln_reduce_group call.
+// grad_fmt (enum cldrd_stream_fmt; the rule is in include/cldrd_hip.h): the format of dy and dx; operand_f16: dx_dropped / dy_branch of the fp32
+// stream are fp16, not bf16 (the fp16 stream's always are; its dx_dropped may be null - dx then serves as the MFMA operand too)
 extern "C" int cldrd_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                                    void* dx, void* dx_dropped, float* dgamma, float* dbeta, float* dbias, float* partial, int T,
-                                   int d, float dropout_p, unsigned long long seed, int accumulate, int x_f32, const void* dy_branch, void* stream) {
+                                   int d, float dropout_p, unsigned long long seed, int accumulate, int x_f32, int grad_fmt, int operand_f16,
+                                   const void* dy_branch, void* stream) {
     CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0, "layernorm_bwd: need 0 < d <= 1024, d % 4 == 0");
-    CLDRD_CHECK(dy_branch == nullptr || (x_f32 & (2 | 8)), "layernorm_bwd: dy_branch goes with the fp32 / fp16 gradient stream (x_f32 bit 1 / 3)");
-    // x_f32 bit 2 (round 4): dx_dropped and dy_branch are fp16, not bf16 (the all-fp16 training mode)
-    // x_f32 bit 3 (round 5): dy and dx are FP16 rows (the fp16 gradient stream; implies bit 2); dx_dropped may be null when no dropout
-    //   separates the stream from the MFMA operand - dx then serves as both
-    const bool g_f16 = (x_f32 & 8) != 0;
-    const int h16 = ((x_f32 & 4) || g_f16) ? 1 : 0;
+    CLDRD_CHECK(grad_fmt >= STREAM_BF16 && grad_fmt <= STREAM_F16, "layernorm_bwd: grad_fmt is one of enum cldrd_stream_fmt");
+    CLDRD_CHECK(dy_branch == nullptr || grad_fmt != STREAM_BF16, "layernorm_bwd: dy_branch goes with the fp32 / fp16 gradient stream");
+    CLDRD_CHECK(grad_fmt != STREAM_F32 || (x_f32 && dx_dropped != nullptr), "layernorm_bwd: the fp32 gradient stream needs fp32 x and the 16-bit operand copy (dx_dropped)");
+    CLDRD_CHECK(grad_fmt != STREAM_F16 || x_f32, "layernorm_bwd: the fp16 gradient stream needs fp32 x (the pre-LN sums of the fp32 residual stream)");
+    const int h16 = grad_fmt == STREAM_F16 || (grad_fmt == STREAM_F32 && operand_f16) ? 1 : 0;
     const float* inv_scale = g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr;
-    // x_f32: bit 0 = x holds fp32 pre-LN sums; bit 1 = dy and dx are fp32 rows (fp32 gradient stream; dx_dropped stays 16-bit and is required:
-    // it is the MFMA operand of the next data-gradient GEMM)
-    const bool g_f32 = (x_f32 & 2) != 0;
-    CLDRD_CHECK(!(g_f32 && g_f16), "layernorm_bwd: the gradient stream is fp32 or fp16, not both");
-    CLDRD_CHECK(!g_f32 || ((x_f32 & 1) && dx_dropped != nullptr), "layernorm_bwd: the fp32 gradient stream needs fp32 x and the 16-bit operand copy (dx_dropped)");
-    CLDRD_CHECK(!g_f16 || (x_f32 & 1), "layernorm_bwd: the fp16 gradient stream needs fp32 x (the pre-LN sums of the fp32 residual stream)");
     const int nb = ln_bwd_blocks(T);
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
     ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
         constexpr int DCV = decltype(dc)::value;
         constexpr bool DRV = decltype(dr)::value;
         const size_t lds = (512 / 128) * 3 * MAX_IT * 64 * sizeof(float4);
-        const float sc = 1.0f / (1.0f - dropout_p);
-        hipStream_t st = (hipStream_t)stream;
-        bf16_t* d2 = (bf16_t*)dx_dropped;
-        if (g_f16)
-            hipLaunchKernelGGL((ln_bwd_kernel<DCV, DRV, true, 2>), dim3(nb), dim3(512), lds, st, dy, x, mean, rstd, gamma, dx, d2, partial, T, d, th, sc, seed_arg(seed), (const bf16_t*)dy_branch, 1, inv_scale);
-        else if (g_f32)     // fp32 gradient stream: only with the fp32 pre-LN sums of the fp32 residual stream
-            hipLaunchKernelGGL((ln_bwd_kernel<DCV, DRV, true, 1>), dim3(nb), dim3(512), lds, st, dy, x, mean, rstd, gamma, dx, d2, partial, T, d, th, sc, seed_arg(seed), (const bf16_t*)dy_branch, h16, inv_scale);
-        else if (x_f32 & 1)
-            hipLaunchKernelGGL((ln_bwd_kernel<DCV, DRV, true>), dim3(nb), dim3(512), lds, st, dy, x, mean, rstd, gamma, dx, d2, partial, T, d, th, sc, seed_arg(seed), (const bf16_t*)nullptr, 0, inv_scale);
-        else
-            hipLaunchKernelGGL((ln_bwd_kernel<DCV, DRV, false>), dim3(nb), dim3(512), lds, st, dy, x, mean, rstd, gamma, dx, d2, partial, T, d, th, sc, seed_arg(seed), (const bf16_t*)nullptr, 0, inv_scale);
+        decltype(&ln_bwd_kernel<DCV, DRV, true, 2>) kern;
+        if (grad_fmt == STREAM_F16) kern = ln_bwd_kernel<DCV, DRV, true, 2>;
+        else if (grad_fmt == STREAM_F32) kern = ln_bwd_kernel<DCV, DRV, true, 1>;      // only with the fp32 pre-LN sums of the fp32 residual stream
+        else if (x_f32) kern = ln_bwd_kernel<DCV, DRV, true>;
+        else kern = ln_bwd_kernel<DCV, DRV, false>;
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, (hipStream_t)stream, dy, x, mean, rstd, gamma, dx, (bf16_t*)dx_dropped, partial, T, d, th,
+                           1.0f / (1.0f - dropout_p), seed_arg(seed), (const bf16_t*)dy_branch, h16, inv_scale);
     });
     CLDRD_LAUNCH_CHECK();
     return launch_reduce(partial, nb, d, dgamma, dbeta, dbias, accumulate, (hipStream_t)stream);
@@ -765,12 +748,13 @@ extern "C" int cldrd_ln_reduce_group(const float* const* partial, const int* T, 
 extern "C" int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
                                   const float* gamma, const float* mean, const float* rstd, float* dword, float* dpos,
                                   float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
-                                  float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int dy_f32, const void* dy_branch,
-                                  void* stream) {
+                                  float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16,
+                                  const void* dy_branch, void* stream) {
     CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0 && L > 0, "embed_ln_bwd: bad shape");
-    // dy_f32: bit 0 = dy is fp32; bit 2 = dy_branch is fp16; bit 3 (round 5) = dy is FP16 (the fp16 gradient stream; dy_branch fp16 then)
-    CLDRD_CHECK(dy_branch == nullptr || (dy_f32 & (1 | 8)), "embed_ln_bwd: dy_branch goes with an fp32 / fp16 dy");
-    CLDRD_CHECK((dy_f32 & 9) != 9, "embed_ln_bwd: dy is fp32 or fp16, not both");
+    // grad_fmt (enum cldrd_stream_fmt): the format of dy; branch_f16: the dy_branch of an fp32 dy is fp16, not bf16 (an fp16 dy's always is)
+    CLDRD_CHECK(grad_fmt >= STREAM_BF16 && grad_fmt <= STREAM_F16, "embed_ln_bwd: grad_fmt is one of enum cldrd_stream_fmt");
+    CLDRD_CHECK(dy_branch == nullptr || grad_fmt != STREAM_BF16, "embed_ln_bwd: dy_branch goes with an fp32 / fp16 dy");
+    const int h16 = grad_fmt == STREAM_F16 || (grad_fmt == STREAM_F32 && branch_f16) ? 1 : 0;
     int nb = ln_bwd_blocks(T);                      // the caller sized `partial` for this many blocks; fewer is fine
     int g4 = 4, r = L;                              // gcd(4, L)
     while (r) { const int t = g4 % r; g4 = r; r = t; }
@@ -780,21 +764,13 @@ extern "C" int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const fl
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
     ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
         const size_t lds = (256 / 128) * 3 * MAX_IT * 64 * sizeof(float4);
-        if (dy_f32 & 8)
-            hipLaunchKernelGGL((embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 2>), dim3(nb), dim3(256), lds,
-                               (hipStream_t)stream, dy, (const int64_t*)ids, word, pos, type0, gamma, mean, rstd, dword, dpos, partial,
-                               T, L, d, vocab, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), pos_uniform, pos_idx, (const bf16_t*)dy_branch,
-                               1, g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr);
-        else if (dy_f32 & 1)
-            hipLaunchKernelGGL((embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 1>), dim3(nb), dim3(256), lds,
-                               (hipStream_t)stream, dy, (const int64_t*)ids, word, pos, type0, gamma, mean, rstd, dword, dpos, partial,
-                               T, L, d, vocab, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), pos_uniform, pos_idx, (const bf16_t*)dy_branch,
-                               (dy_f32 & 4) ? 1 : 0, g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr);
-        else
-            hipLaunchKernelGGL((embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value>), dim3(nb), dim3(256), lds,
-                               (hipStream_t)stream, dy, (const int64_t*)ids, word, pos, type0, gamma, mean, rstd, dword, dpos, partial,
-                               T, L, d, vocab, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), pos_uniform, pos_idx, (const bf16_t*)nullptr, 0,
-                               g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr);
+        decltype(&embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 2>) kern;
+        if (grad_fmt == STREAM_F16) kern = embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 2>;
+        else if (grad_fmt == STREAM_F32) kern = embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 1>;
+        else kern = embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value>;
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, (hipStream_t)stream, dy, (const int64_t*)ids, word, pos, type0, gamma, mean, rstd, dword,
+                           dpos, partial, T, L, d, vocab, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), pos_uniform, pos_idx, (const bf16_t*)dy_branch,
+                           h16, g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr);
     });
     CLDRD_LAUNCH_CHECK();
     return launch_reduce(partial, nb, d, dgamma, dbeta, dtype0, accumulate, (hipStream_t)stream);
@@ -813,13 +789,17 @@ extern "C" int cldrd_colsum_bf16(const void* x, float* out, float* partial, int 
     return 0;
 }
 
-extern "C" int cldrd_scatter_cls_grad(const float* dcls, void* g, int R, int d, int stride, int T, int g_f32, void* stream) {
-    CLDRD_CHECK(R > 0 && d > 0 && stride > 0 && (long long)R * stride <= (long long)T + stride - 1, "scatter_cls_grad: bad shape");
-    // g_f32: 0 = bf16 rows, 1 = fp32, 2 = fp16
-    if (hipMemsetAsync(g, 0, (size_t)T * d * (g_f32 == 1 ? sizeof(float) : sizeof(bf16_t)), (hipStream_t)stream) != hipSuccess) return cldrd_set_error("scatter_cls_grad: memset failed");
-    if (g_f32 == 1) hipLaunchKernelGGL(scatter_cls_kernel<1>, dim3(R), dim3(256), 0, (hipStream_t)stream, dcls, g, R, d, stride);
-    else if (g_f32 == 2) hipLaunchKernelGGL(scatter_cls_kernel<2>, dim3(R), dim3(256), 0, (hipStream_t)stream, dcls, g, R, d, stride);
-    else hipLaunchKernelGGL(scatter_cls_kernel<0>, dim3(R), dim3(256), 0, (hipStream_t)stream, dcls, g, R, d, stride);
+int cldrd_launch_scatter_cls_idx(const float* dcls, void* g, int R, int d, const int* idx, int fmt, hipStream_t st);      // pack.hip
+// g = zeros [T, d] in the format fmt (enum cldrd_stream_fmt), then g[idx ? idx[r] : r * stride] = dcls[r]
+extern "C" int cldrd_scatter_cls_grad(const float* dcls, void* g, int R, int d, int stride, const int* idx, int T, int fmt, void* stream) {
+    CLDRD_CHECK(R > 0 && d > 0 && (idx ? T >= R : stride > 0 && (long long)R * stride <= (long long)T + stride - 1), "scatter_cls_grad: bad shape");
+    if (hipMemsetAsync(g, 0, (size_t)T * d * (fmt == STREAM_F32 ? sizeof(float) : sizeof(bf16_t)), (hipStream_t)stream) != hipSuccess) return cldrd_set_error("scatter_cls_grad: memset failed");
+    if (idx) return cldrd_launch_scatter_cls_idx(dcls, g, R, d, idx, fmt, (hipStream_t)stream);
+    decltype(&scatter_cls_kernel<1>) kern;
+    if (fmt == STREAM_F32) kern = scatter_cls_kernel<1>;
+    else if (fmt == STREAM_F16) kern = scatter_cls_kernel<2>;
+    else kern = scatter_cls_kernel<0>;
+    hipLaunchKernelGGL(kern, dim3(R), dim3(256), 0, (hipStream_t)stream, dcls, g, R, d, stride);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }

@@ -283,19 +283,11 @@ extern "C" int cldrd_clip_coef(const float* partial, int nblk_total, float max_n
 
 // Legacy transformers.AdamW (correct_bias=True), step is 1-based.  decay_flags: one byte per 64 parameters.
 // clip: device float[3] from cldrd_grad_clip_coef or null.  shadow: bf16 copy of the updated parameters or null.
-// shadow16 (optional): fp16 copy (RNE, as cldrd_cast_f16) of the updated parameters [h16_begin, h16_end) - the high-precision forward
+// shadow16 (null: none): fp16 copy (RNE, as cldrd_cast_f16) of the updated parameters [h16_begin, h16_end) - the high-precision forward
 // of the query tower reads it; both bounds multiples of 4, shadow16[0] = parameter h16_begin.
-extern "C" int cldrd_adamw_step_h16(float* p, const float* g, float* m, float* v, const unsigned char* decay_flags, void* shadow,
-                                    size_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                                    const float* clip, void* shadow16, size_t h16_begin, size_t h16_end, void* stream);
 extern "C" int cldrd_adamw_step(float* p, const float* g, float* m, float* v, const unsigned char* decay_flags, void* shadow,
                                 size_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                                const float* clip, void* stream) {
-    return cldrd_adamw_step_h16(p, g, m, v, decay_flags, shadow, n, lr, beta1, beta2, eps, weight_decay, step, clip, nullptr, 0, 0, stream);
-}
-extern "C" int cldrd_adamw_step_h16(float* p, const float* g, float* m, float* v, const unsigned char* decay_flags, void* shadow,
-                                    size_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                                    const float* clip, void* shadow16, size_t h16_begin, size_t h16_end, void* stream) {
+                                const float* clip, void* shadow16, size_t h16_begin, size_t h16_end, void* stream) {
     CLDRD_CHECK(n > 0 && n % 64 == 0, "adamw_step: n must be a multiple of 64");
     CLDRD_CHECK(step >= 1, "adamw_step: step is 1-based");
     CLDRD_CHECK(shadow16 == nullptr || (h16_begin % 4 == 0 && h16_end % 4 == 0 && h16_begin <= h16_end && h16_end <= n && (uintptr_t)shadow16 % 8 == 0),

@@ -94,21 +94,23 @@ extern "C" int cldrd_gather_i64(const long long* src, const int* idx, long long*
     return 0;
 }
 
-extern "C" int cldrd_scatter_cls_grad_idx(const float* dcls, void* g, int R, int d, const int* idx, int T, int g_f32, void* stream) {
-    CLDRD_CHECK(R > 0 && d > 0 && T >= R, "scatter_cls_grad_idx: bad shape");
-    if (hipMemsetAsync(g, 0, (size_t)T * d * (g_f32 == 1 ? sizeof(float) : sizeof(bf16_t)), (hipStream_t)stream) != hipSuccess) return cldrd_set_error("scatter_cls_grad_idx: memset failed");
-    if (g_f32 == 1) hipLaunchKernelGGL(scatter_cls_idx_kernel<1>, dim3(R), dim3(256), 0, (hipStream_t)stream, dcls, g, idx, d);
-    else if (g_f32 == 2) hipLaunchKernelGGL(scatter_cls_idx_kernel<2>, dim3(R), dim3(256), 0, (hipStream_t)stream, dcls, g, idx, d);
-    else hipLaunchKernelGGL(scatter_cls_idx_kernel<0>, dim3(R), dim3(256), 0, (hipStream_t)stream, dcls, g, idx, d);
+// The idx[r] forms of cldrd_scatter_cls_grad (layernorm.hip) and cldrd_add_rows (attention.hip), which check the arguments (and zero g)
+int cldrd_launch_scatter_cls_idx(const float* dcls, void* g, int R, int d, const int* idx, int fmt, hipStream_t st) {
+    decltype(&scatter_cls_idx_kernel<1>) kern;      // fmt: 0 bf16, 1 fp32, 2 fp16 (enum cldrd_stream_fmt)
+    if (fmt == 1) kern = scatter_cls_idx_kernel<1>;
+    else if (fmt == 2) kern = scatter_cls_idx_kernel<2>;
+    else kern = scatter_cls_idx_kernel<0>;
+    hipLaunchKernelGGL(kern, dim3(R), dim3(256), 0, st, dcls, g, idx, d);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int cldrd_add_rows_idx(void* dst, const void* src, int M, int d, const int* idx, int f32, void* stream) {
-    CLDRD_CHECK(M > 0 && d > 0, "add_rows_idx: bad shape");
-    if (f32 == 1) hipLaunchKernelGGL(add_rows_idx_kernel<1>, dim3(M), dim3(256), 0, (hipStream_t)stream, dst, src, idx, d);
-    else if (f32 == 2) hipLaunchKernelGGL(add_rows_idx_kernel<2>, dim3(M), dim3(256), 0, (hipStream_t)stream, dst, src, idx, d);
-    else hipLaunchKernelGGL(add_rows_idx_kernel<0>, dim3(M), dim3(256), 0, (hipStream_t)stream, dst, src, idx, d);
+int cldrd_launch_add_rows_idx(void* dst, const void* src, int M, int d, const int* idx, int fmt, hipStream_t st) {
+    decltype(&add_rows_idx_kernel<1>) kern;
+    if (fmt == 1) kern = add_rows_idx_kernel<1>;
+    else if (fmt == 2) kern = add_rows_idx_kernel<2>;
+    else kern = add_rows_idx_kernel<0>;
+    hipLaunchKernelGGL(kern, dim3(M), dim3(256), 0, st, dst, src, idx, d);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }

@@ -806,30 +806,29 @@ extern "C" int cldrd_topk_kth_largest(const float* scores, int ld, int nq, int S
     return 0;
 }
 
-extern "C" int cldrd_topk_rescore(const float* q, const float* P, int d, const int* counts, const int* cand_rows,
-                                  float* cand_scores, int nq, int cap, void* stream) {
+// cand_scores[q][c] = exact score of row cand_rows[q][c] for c < counts[q].  P32 != nullptr: fp32(<q, P32[row]>); else the fp16-row mode:
+// fp32(qmu[q] + <q, P16[row]>), qmu[q] = <q, mu> in fp64 (cldrd_query_dot64), sums in fp64, one rounding
+extern "C" int cldrd_topk_rescore(const float* q, const float* P32, const void* P16, const double* qmu, int d, const int* counts,
+                                  const int* cand_rows, float* cand_scores, int nq, int cap, void* stream) {
     CLDRD_CHECK(nq > 0 && d % 4 == 0 && cap > 0, "topk_rescore: bad arguments");
-    hipLaunchKernelGGL(rescore_kernel, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, P, d, counts, cand_rows, cand_scores, cap);
+    CLDRD_CHECK(P32 ? qmu == nullptr : (P16 != nullptr && qmu != nullptr), "topk_rescore: fp32 rows take no qmu, fp16 rows need P16 and qmu");
+    if (P32) {
+        hipLaunchKernelGGL(rescore_kernel, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, P32, d, counts, cand_rows, cand_scores, cap);
+    } else {
+        CLDRD_CHECK((uintptr_t)q % 16 == 0 && (uintptr_t)P16 % (d % 8 == 0 ? 16 : 8) == 0, "topk_rescore: aligned operands");
+        if (d % 8 == 0)
+            hipLaunchKernelGGL(rescore16_kernel<8>, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, (const uint16_t*)P16, qmu, d, counts, cand_rows, cand_scores, cap);
+        else
+            hipLaunchKernelGGL(rescore16_kernel<4>, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, (const uint16_t*)P16, qmu, d, counts, cand_rows, cand_scores, cap);
+    }
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
 
-// fp16-row mode: qmu[q] = <q, mu> in fp64 (device double [nq]); cand_scores = fp32(qmu[q] + <q, P16[row]>), sums in fp64, one rounding
+// qmu[q] = <q, mu> in fp64 (device double [nq]): the fp16-row mode of cldrd_topk_rescore / cldrd_flatip_search
 extern "C" int cldrd_query_dot64(const float* q, const float* mu, int d, double* out, int nq, void* stream) {
     CLDRD_CHECK(nq > 0 && d > 0 && d % 4 == 0 && (uintptr_t)q % 16 == 0 && (uintptr_t)mu % 16 == 0, "query_dot64: bad arguments");
     hipLaunchKernelGGL(query_dot64_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, mu, d, out, nq);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int cldrd_topk_rescore16(const float* q, const void* P16, const double* qmu, int d, const int* counts, const int* cand_rows,
-                                    float* cand_scores, int nq, int cap, void* stream) {
-    CLDRD_CHECK(nq > 0 && d % 4 == 0 && cap > 0 && qmu != nullptr, "topk_rescore16: bad arguments");
-    CLDRD_CHECK((uintptr_t)q % 16 == 0 && (uintptr_t)P16 % (d % 8 == 0 ? 16 : 8) == 0, "topk_rescore16: aligned operands");
-    if (d % 8 == 0)
-        hipLaunchKernelGGL(rescore16_kernel<8>, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, (const uint16_t*)P16, qmu, d, counts, cand_rows, cand_scores, cap);
-    else
-        hipLaunchKernelGGL(rescore16_kernel<4>, dim3(64, nq), dim3(256), 0, (hipStream_t)stream, q, (const uint16_t*)P16, qmu, d, counts, cand_rows, cand_scores, cap);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
@@ -859,22 +858,16 @@ extern "C" int cldrd_row_sqnorm_max(const float* P, size_t rows, int d, unsigned
     return 0;
 }
 
-extern "C" int cldrd_gather_cast_rows(const float* src, void* dst, size_t n_out, size_t stride, int d, void* stream) {
+// dst[i] = bf16(src[i * stride]) for i < n_out; src_f16 != 0: src holds fp16 rows (an index uploaded in fp16-row mode), else fp32
+extern "C" int cldrd_gather_cast_rows(const void* src, int src_f16, void* dst, size_t n_out, size_t stride, int d, void* stream) {
     CLDRD_CHECK(n_out > 0 && stride > 0 && d % 4 == 0, "gather_cast_rows: bad arguments");
+    CLDRD_CHECK(!src_f16 || ((uintptr_t)src % 8 == 0 && (uintptr_t)dst % 8 == 0), "gather_cast_rows: aligned operands");
     const int nb = (int)((n_out + 3) / 4 < 2048 ? (n_out + 3) / 4 : 2048);
-    hipLaunchKernelGGL(gather_cast_rows_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n_out, stride, d);
+    if (src_f16) hipLaunchKernelGGL(gather_cast_rows16_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, (bf16_t*)dst, n_out, stride, d);
+    else hipLaunchKernelGGL(gather_cast_rows_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const float*)src, (bf16_t*)dst, n_out, stride, d);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
-
-extern "C" int cldrd_gather_cast_rows16(const void* src16, void* dst, size_t n_out, size_t stride, int d, void* stream) {
-    CLDRD_CHECK(n_out > 0 && stride > 0 && d % 4 == 0 && (uintptr_t)src16 % 8 == 0 && (uintptr_t)dst % 8 == 0, "gather_cast_rows16: bad arguments");
-    const int nb = (int)((n_out + 3) / 4 < 2048 ? (n_out + 3) / 4 : 2048);
-    hipLaunchKernelGGL(gather_cast_rows16_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src16, (bf16_t*)dst, n_out, stride, d);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-
 
 extern "C" int cldrd_cast_f16(const float* src, void* dst, size_t n, unsigned int* flag, void* stream) {
     CLDRD_CHECK(n % 4 == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 8 == 0), "cast_f16: n % 4 == 0 and aligned operands");
@@ -904,25 +897,14 @@ extern "C" int cldrd_index_col_mean(const float* P, size_t rows, int d, float* m
 }
 // P16[r] = fp16(P[r] - mu); sample[i] = bf16(P[i * s_stride] - mu) for i < s_rows (sample may be null); *cmax_bits (zero it first) = bit pattern
 // of max_r |P[r] - mu|^2 as fp32; *flag |= 1 when a centred value does not fit fp16.
-extern "C" int cldrd_index_center_cast(const float* P, const float* mu, size_t rows, int d, void* P16, void* sample_bf16, size_t s_stride,
-                                       size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream) {
+// One chunk of a chunked attach (a whole shard: one chunk, row0 = 0): P / P16 point at row `row0` of the shard and hold `rows` rows; `sample_bf16` is the WHOLE shard's sample
+// (row i = shard row i * s_stride, so a chunk writes the sample rows that fall inside it); *cmax_bits and *flag accumulate over the chunks
+// (zero them before the first one).
+extern "C" int cldrd_index_center_cast(const float* P, const float* mu, size_t rows, size_t row0, int d, void* P16, void* sample_bf16,
+                                       size_t s_stride, size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream) {
     CLDRD_CHECK(rows > 0 && d > 0 && d % 4 == 0 && cmax_bits != nullptr, "index_center_cast: bad arguments");
     CLDRD_CHECK(sample_bf16 == nullptr || s_stride > 0, "index_center_cast: sample stride");
     CLDRD_CHECK((uintptr_t)P % 16 == 0 && (uintptr_t)mu % 16 == 0 && (uintptr_t)P16 % 8 == 0, "index_center_cast: aligned operands");
-    const int nb = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
-    hipLaunchKernelGGL(index_center_cast_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, P, mu, rows, (size_t)0, d, (uint16_t*)P16, (bf16_t*)sample_bf16, s_stride,
-                       s_rows, cmax_bits, flag);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-// One chunk of a chunked attach: P / P16 point at row `row0` of the shard and hold `rows` rows; `sample_bf16` is the WHOLE shard's sample
-// (row i = shard row i * s_stride, so a chunk writes the sample rows that fall inside it); *cmax_bits and *flag accumulate over the chunks
-// (zero them before the first one).
-extern "C" int cldrd_index_center_cast_chunk(const float* P, const float* mu, size_t rows, size_t row0, int d, void* P16, void* sample_bf16,
-                                             size_t s_stride, size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream) {
-    CLDRD_CHECK(rows > 0 && d > 0 && d % 4 == 0 && cmax_bits != nullptr, "index_center_cast_chunk: bad arguments");
-    CLDRD_CHECK(sample_bf16 == nullptr || s_stride > 0, "index_center_cast_chunk: sample stride");
-    CLDRD_CHECK((uintptr_t)P % 16 == 0 && (uintptr_t)mu % 16 == 0 && (uintptr_t)P16 % 8 == 0, "index_center_cast_chunk: aligned operands");
     const int nb = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
     hipLaunchKernelGGL(index_center_cast_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, P, mu, rows, row0, d, (uint16_t*)P16, (bf16_t*)sample_bf16, s_stride,
                        s_rows, cmax_bits, flag);
@@ -977,9 +959,7 @@ extern "C" int cldrd_topk_select(const int* counts, const int* cand_rows, const 
 int cldrd_topk_scan_stream(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts, int* cand_rows,
                            float* cand_scores, int cap, int f16, hipStream_t st);
 extern "C" int cldrd_topk_scan_filter(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
-                                      int* cand_rows, float* cand_scores, int cap, int f16, void* stream);
-extern "C" int cldrd_topk_scan_filter_tiled(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
-                                            int* cand_rows, float* cand_scores, int cap, int f16, void* stream);
+                                      int* cand_rows, float* cand_scores, int cap, int f16, int tiled, void* stream);
 
 // The whole search of one shard for nq queries (device resident, fp32 + fp16 copies), in batches of 128 as the reference searches
 // (retriever/retrieve_top_passages.py:88, retrieval_utils.py:131-153), enqueued back to back on `stream` with no host round trip:
@@ -992,12 +972,14 @@ extern "C" int cldrd_topk_scan_filter_tiled(const void* Q, const void* P, int nq
 // the global candidate lists - slower, but it has no on-chip hit list and so can never drop a hit (status bit 4): the retry form
 // for passes whose hit density overflowed the streaming scan's per-wave lists.  The caller reads `status` once at the end and
 // redoes the (rare) unproven queries with thresholds of its choice through this same entry point.
-// R16 != nullptr: fp16-row mode, the re-score reads the rows from R16 and adds qmu (cldrd_flatip_search16); else from P32.
-static int flatip_search_impl(const float* q32, const void* qh, const float* thr, const float* eps, const void* Ph, const float* P32,
-                              const void* R16, const double* qmu,
-                              long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
-                              int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
-                              int exhaustive, void* stream) {
+// P32 != nullptr: the re-score reads the fp32 rows; else the fp16-row mode (no fp32 rows anywhere): P16 = fp16(p - mu) is the scan's operand AND
+// the stored row, scores are fp32(qmu[q] + <q, P16[row]>) (cldrd_topk_rescore), qmu from cldrd_query_dot64; the scan's operand is then the exact
+// stored row, so eps (both operands rounded) still bounds |scan - exact|.
+extern "C" int cldrd_flatip_search(const float* q32, const void* qh, const float* thr, const float* eps, const void* P16, const float* P32,
+                                   const double* qmu, long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows,
+                                   float* cand_scores, int cap, int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat,
+                                   float* D, int* I, int exhaustive, void* stream) {
+    CLDRD_CHECK(P32 ? qmu == nullptr : (P16 != nullptr && qmu != nullptr), "flatip_search: fp32 rows take no qmu, fp16 rows need P16 and qmu");
     CLDRD_CHECK(nq > 0 && rows > 0 && k > 0 && cap > 0 && cap <= 8192 && cap2 > 0 && cap2 <= 8192 && d % 4 == 0, "flatip_search: bad arguments");
     CLDRD_CHECK(qtile == 128 || qtile == 256, "flatip_search: the query tile is 128 (the reference's batch) or 256 (two batches per pass over the index)");
     const int tiled = (exhaustive >> 1) & 1;
@@ -1016,44 +998,22 @@ static int flatip_search_impl(const float* q32, const void* qh, const float* thr
             // the tiled kernels take at most 128 queries per call; list lengths of query j of this pass stay at cb[j]
             for (int h = 0; h < m; h += 128) {
                 const int mh = m - h < 128 ? m - h : 128;
-                rc = cldrd_topk_scan_filter_tiled((const char*)qh + (size_t)(lo + h) * d * 2, Ph, mh, rows, d, thr + lo + h, cb + h,
-                                                  cand_rows + (size_t)h * cap, cand_scores + (size_t)h * cap, cap, 1, st);
+                rc = cldrd_topk_scan_filter((const char*)qh + (size_t)(lo + h) * d * 2, P16, mh, rows, d, thr + lo + h, cb + h,
+                                            cand_rows + (size_t)h * cap, cand_scores + (size_t)h * cap, cap, 1, 1, st);
                 if (rc) return rc;
             }
         } else {
-            rc = cldrd_topk_scan_filter(qh ? (const char*)qh + (size_t)lo * d * 2 : nullptr, Ph, m, rows, d, thr + lo, cb, cand_rows, cand_scores, cap, 1, st);
+            rc = cldrd_topk_scan_filter(qh ? (const char*)qh + (size_t)lo * d * 2 : nullptr, P16, m, rows, d, thr + lo, cb, cand_rows, cand_scores, cap, 1, 0, st);
             if (rc) return rc;
         }
         rc = launch_select(cb, cb + m, cand_rows, cand_scores, m, cap, kk, thr + lo, eps + lo, rows2, cap2, n2 + lo, status + lo, khat + lo, exhaustive, st);
         if (rc) return rc;
-        if (R16) rc = cldrd_topk_rescore16(q32 + (size_t)lo * d, R16, qmu + lo, d, n2 + lo, rows2, scores2, m, cap2, st);
-        else rc = cldrd_topk_rescore(q32 + (size_t)lo * d, P32, d, n2 + lo, rows2, scores2, m, cap2, st);
+        rc = cldrd_topk_rescore(q32 + (size_t)lo * d, P32, P16, qmu ? qmu + lo : nullptr, d, n2 + lo, rows2, scores2, m, cap2, st);
         if (rc) return rc;
         rc = cldrd_topk_sort(n2 + lo, rows2, scores2, m, cap2, k, D + (size_t)lo * k, I + (size_t)lo * k, st);
         if (rc) return rc;
     }
     return 0;
-}
-
-extern "C" int cldrd_flatip_search(const float* q32, const void* qh, const float* thr, const float* eps, const void* Ph, const float* P32,
-                                   long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
-                                   int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
-                                   int exhaustive, void* stream) {
-    CLDRD_CHECK(P32 != nullptr, "flatip_search: no fp32 rows");
-    return flatip_search_impl(q32, qh, thr, eps, Ph, P32, nullptr, nullptr, rows, d, nq, k, qtile, counts, cand_rows, cand_scores, cap, rows2, scores2,
-                              cap2, n2, status, khat, D, I, exhaustive, stream);
-}
-
-// cldrd_flatip_search on an index in fp16-row mode: P16 = fp16(p - mu) is the scan's operand AND the stored row (no fp32 rows anywhere);
-// scores are fp32(qmu[q] + <q, P16[row]>) (cldrd_topk_rescore16), qmu from cldrd_query_dot64.  Scan, select, sort and the status bits are
-// those of cldrd_flatip_search; the scan's operand is now the exact stored row, so eps (both operands rounded) still bounds |scan - exact|.
-extern "C" int cldrd_flatip_search16(const float* q32, const void* qh, const float* thr, const float* eps, const void* P16, const double* qmu,
-                                     long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
-                                     int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
-                                     int exhaustive, void* stream) {
-    CLDRD_CHECK(P16 != nullptr && qmu != nullptr, "flatip_search16: need the fp16 rows and qmu");
-    return flatip_search_impl(q32, qh, thr, eps, P16, nullptr, P16, qmu, rows, d, nq, k, qtile, counts, cand_rows, cand_scores, cap, rows2, scores2,
-                              cap2, n2, status, khat, D, I, exhaustive, stream);
 }
 
 // Streaming form of cldrd_topk_scan_filter for d in {128, 256, 768} and nq <= 128 (returns -1 when it does not apply).

@@ -783,19 +783,12 @@ class HipEncoder(nn.Module):
         xh = self._buf(T, d, dev, torch.float16) if QKV16 else None
         x32 = self._buf(T, d, dev, torch.float32)           # fp32 copy of the layer input: the residual operand
         mean0, rstd0 = torch.empty(T, **f32), torch.empty(T, **f32)
-        type0 = self.w("embeddings.token_type_embeddings.weight")[0] if cfg.arch == "bert" else None
         if window is not None:
             window("ln")
-        if tt is not None:
-            ops.embed_ln_fwd_typed(ids.view(-1), self.w("embeddings.word_embeddings.weight"), self.w("embeddings.position_embeddings.weight"),
-                                   self.w("embeddings.token_type_embeddings.weight"), tt.to(torch.int32), self.w("embeddings.LayerNorm.weight"),
-                                   self.w("embeddings.LayerNorm.bias"), xh if QKV16 else x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
-                                   pos_idx=pk.pos if pk is not None else None)
-        else:
-            ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"),
-                             self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
-                             self.w("embeddings.LayerNorm.bias"), xh if QKV16 else x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
-                             pos_idx=pk.pos if pk is not None else None)
+        ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"), self.w("embeddings.position_embeddings.weight"),
+                         self.w("embeddings.token_type_embeddings.weight") if cfg.arch == "bert" else None, self.w("embeddings.LayerNorm.weight"),
+                         self.w("embeddings.LayerNorm.bias"), xh if QKV16 else x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
+                         pos_idx=pk.pos if pk is not None else None, type_ids=tt.to(torch.int32) if tt is not None else None)
         if save:
             tape.mean0, tape.rstd0 = mean0, rstd0
         yield
@@ -1021,10 +1014,7 @@ class HipEncoder(nn.Module):
         ops.gemm_nt(dkv, wt[:, d:], g, T)                           # through K and V: every token
         gq = buf(M, d, dev, sdt)
         ops.gemm_nt(dqc, wt[:, :d], gq, M, residual=ds1)            # through Q and the residual: CLS rows only
-        if pk is None:
-            ops.add_rows_strided(g, gq, M, L)
-        else:
-            ops.add_rows_idx(g, gq, pk.cls_idx, M)
+        ops.add_rows(g, gq, M, stride=L, idx=pk.cls_idx if pk is not None else None)
         return g
 
     # ------------------------------------------------------------------ backward
@@ -1129,10 +1119,7 @@ class HipEncoder(nn.Module):
             buf = lambda r, c, dv, dt=None: self._buf(r, c, dv, bdt if dt is None else dt)
             if g is None:
                 g = buf(T, d, dev, sdt)
-                if tape.pack is None:
-                    ops.scatter_cls_grad(dcls.contiguous(), g, M, L, T)
-                else:
-                    ops.scatter_cls_grad_idx(dcls.contiguous(), g, tape.pack.cls_idx, T)
+                ops.scatter_cls_grad(dcls.contiguous(), g, M, T, stride=L, idx=tape.pack.cls_idx if tape.pack is not None else None)
             s_l, p_h, p_a, p_out = a["seed"], a["p_h"], a["p_a"], a["p_out"]
             # --- output LayerNorm + FFN ---
             ds2 = buf(T, d, dev, sdt)

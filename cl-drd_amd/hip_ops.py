@@ -460,45 +460,38 @@ def attention_cls_bwd(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p=0.0, 
          nseq, L, H, dropout_p, seed, io_f16, _stream())
 
 
-def add_rows_strided(dst, src, M, stride_rows):
-    """dst[m * stride_rows] += src[m]: bf16 rows (fp32 add, one rounding), or fp32 rows (fp32 gradient stream)."""
-    fmt = _stream_fmt(dst)           # fp16 dst (the fp16 gradient stream) takes an fp32 src
+def add_rows(dst, src, M, stride=0, idx=None):
+    """dst[row(m)] += src[m], row(m) = idx[m] (int32, the CLS rows of a packed batch) or m * stride: bf16 += bf16 (fp32 add, one rounding),
+    fp32 += fp32 (fp32 gradient stream), or fp16 dst += fp32 src (the fp16 gradient stream)."""
+    fmt = _stream_fmt(dst)
     _chk(dst, dst.dtype, "dst", 2), _chk(src, F32 if fmt else BF16, "src", 2)
-    call("cldrd_add_rows_strided", _p(dst), _p(src), M, src.shape[1], stride_rows, fmt, _stream())
+    if idx is not None:
+        _chk(idx, torch.int32, "idx", 1)
+    call("cldrd_add_rows", _p(dst), _p(src), M, src.shape[1], stride, _p(idx), fmt, _stream())
 
 
 def ln_partial_elems(T, d) -> int:
     return _lib.load().cldrd_ln_partial_blocks(T) * 3 * d
 
 
-def embed_ln_fwd(ids, word, pos, type0, gamma, beta, out, mean, rstd, T, L, eps, dropout_p=0.0, seed=0, out32=None, pos_idx=None, out_copy=None):
-    """``pos_idx`` (int32 [T], packed batches): the position of every row inside its sequence; None: row % L."""
+def embed_ln_fwd(ids, word, pos, type_table, gamma, beta, out, mean, rstd, T, L, eps, dropout_p=0.0, seed=0, out32=None, pos_idx=None, out_copy=None,
+                 type_ids=None):
+    """``pos_idx`` (int32 [T], packed batches): the position of every row inside its sequence; None: row % L.
+    ``type_ids`` None: every row takes row 0 of ``type_table`` (fp32 [d] or [type_vocab, d]; None for DistilBERT); int32 [>= T]: per-row token
+    types into the whole [type_vocab, d] table (cross-encoder pairs)."""
     _chk(ids, torch.int64, "ids")
     d = word.shape[1]
+    if type_ids is not None:
+        _chk(type_table, F32, "type_table", 2), _chk(type_ids, torch.int32, "type_ids", 1)
+        if type_table.shape[1] != d or type_ids.numel() < T:
+            raise ValueError("embed_ln_fwd: type_table must be [type_vocab, d], type_ids [>= T]")
     if out32 is not None:
         _chk(out32, F32, "out32", 2)
     if pos_idx is not None:
         _chk(pos_idx, torch.int32, "pos_idx", 1)
-    call("cldrd_embed_ln_fwd", _p(ids), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), _p(out), _p(mean), _p(rstd),
-         T, L, d, word.shape[0], eps, dropout_p, seed, _p(out32), _fmt16(out, "out"), _p(pos_idx), _p(out_copy), _stream())
-    return out
-
-
-def embed_ln_fwd_typed(ids, word, pos, type_table, type_ids, gamma, beta, out, mean, rstd, T, L, eps, dropout_p=0.0, seed=0, out32=None,
-                       pos_idx=None, out_copy=None):
-    """:func:`embed_ln_fwd` with per-row token types: ``type_table`` fp32 [type_vocab, d], ``type_ids`` int32 [>= T] (cross-encoder pairs)."""
-    _chk(ids, torch.int64, "ids")
-    _chk(type_table, F32, "type_table", 2), _chk(type_ids, torch.int32, "type_ids", 1)
-    d = word.shape[1]
-    if type_table.shape[1] != d or type_ids.numel() < T:
-        raise ValueError("embed_ln_fwd_typed: type_table must be [type_vocab, d], type_ids [>= T]")
-    if out32 is not None:
-        _chk(out32, F32, "out32", 2)
-    if pos_idx is not None:
-        _chk(pos_idx, torch.int32, "pos_idx", 1)
-    call("cldrd_embed_ln_fwd_typed", _p(ids), _p(word), _p(pos), _p(type_table), _p(type_ids), type_table.shape[0], _p(gamma), _p(beta),
-         _p(out), _p(mean), _p(rstd), T, L, d, word.shape[0], eps, dropout_p, seed, _p(out32), _fmt16(out, "out"), _p(pos_idx), _p(out_copy),
-         _stream())
+    call("cldrd_embed_ln_fwd", _p(ids), _p(word), _p(pos), _p(type_table), _p(type_ids), type_table.shape[0] if type_ids is not None else 0,
+         _p(gamma), _p(beta), _p(out), _p(mean), _p(rstd), T, L, d, word.shape[0], eps, dropout_p, seed, _p(out32), _fmt16(out, "out"),
+         _p(pos_idx), _p(out_copy), _stream())
     return out
 
 
@@ -553,8 +546,7 @@ def embed_ln_bwd(dy, ids, word, pos, type0, gamma, mean, rstd, dword, dpos, dtyp
         raise ValueError("embed_ln_bwd: dy_branch (bf16 or fp16 [>= T, d]) goes with an fp32 dy, an fp16 one with an fp16 dy")
     call("cldrd_embed_ln_bwd", _p(dy), _p(ids), _p(word), _p(pos), _p(type0), _p(gamma), _p(mean), _p(rstd), _p(dword),
          _p(dpos), _p(dtype0), _p(dgamma), _p(dbeta), _p(partial), T, L, d, word.shape[0], dropout_p, seed,
-         1 if accumulate else 0, _p(pos_idx), (1 if dy.dtype == F32 else 0) | (4 if (dy_branch is not None and dy_branch.dtype == F16) else 0)
-         | (8 if dy.dtype == F16 else 0), _p(dy_branch), _stream())
+         1 if accumulate else 0, _p(pos_idx), _stream_fmt(dy), 1 if (dy_branch is not None and dy_branch.dtype == F16) else 0, _p(dy_branch), _stream())
 
 
 # ---- variable-length packing (csrc/pack.hip) ---------------------------------------------------------------------------------------
@@ -598,18 +590,6 @@ def _stream_fmt(t):
     if t.dtype not in (BF16, F32, F16):
         raise TypeError(f"gradient stream tensor: expected bf16, fp32 or fp16, got {t.dtype}")
     return 1 if t.dtype == F32 else (2 if t.dtype == F16 else 0)
-
-
-def scatter_cls_grad_idx(dcls, g, idx, T):
-    _chk(dcls, F32, "dcls", 2), _chk(g, g.dtype, "g", 2), _chk(idx, torch.int32, "idx", 1)
-    call("cldrd_scatter_cls_grad_idx", _p(dcls), _p(g), dcls.shape[0], dcls.shape[1], _p(idx), T, _stream_fmt(g), _stream())
-
-
-def add_rows_idx(dst, src, idx, M):
-    """dst[idx[m]] += src[m]: bf16 += bf16, fp32 += fp32, or fp16 dst += fp32 src (the fp16 gradient stream)"""
-    fmt = _stream_fmt(dst)
-    _chk(dst, dst.dtype, "dst", 2), _chk(src, F32 if fmt else BF16, "src", 2), _chk(idx, torch.int32, "idx", 1)
-    call("cldrd_add_rows_idx", _p(dst), _p(src), M, src.shape[1], _p(idx), fmt, _stream())
 
 
 def layernorm_fwd(x, gamma, beta, out, mean, rstd, T, eps, cls_out=None, cls_stride=0, out32=None, out_copy=None):
@@ -664,47 +644,42 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dx_dropped, dgamma, dbeta, dbias
     fp32 ``dy`` = the fp32 gradient stream: ``dx`` fp32, ``dx_dropped`` (bf16, required) the MFMA operand copy; ``dy_branch`` (bf16,
     optional) is added to dy on load (the branch's data-gradient GEMM output, instead of a residual add in that GEMM's epilogue)."""
     x_f32 = 1 if x.dtype == F32 else 0
-    g_f32 = dy.dtype == F32               # fp32 gradient stream: dy and dx fp32, dx_dropped (the 16-bit MFMA operand) required
-    g_f16 = dy.dtype == F16               # fp16 gradient stream (round 5): dy, dx, dy_branch and dx_dropped fp16; dx_dropped optional
-    if g_f32:
+    fmt = _stream_fmt(dy)
+    h16 = False                           # the 16-bit MFMA operand copy (dx_dropped) and the branch term are fp16, not bf16
+    if fmt == 1:                          # fp32 gradient stream: dy and dx fp32, dx_dropped required
         if not x_f32 or dx_dropped is None:
             raise ValueError("layernorm_bwd: an fp32 dy needs fp32 x and the bf16 operand copy dx_dropped")
-        h16 = dx_dropped.dtype == F16        # the all-fp16 training mode: the operand copy and the branch term are fp16
+        h16 = dx_dropped.dtype == F16     # the all-fp16 training mode
         _chk(dx, F32, "dx", 2), _chk(dx_dropped, F16 if h16 else BF16, "dx_dropped", 2)
-        if dy_branch is not None:
-            _chk(dy_branch, F16 if h16 else BF16, "dy_branch", 2)
-            if dy_branch.shape[1] != dy.shape[1] or dy_branch.shape[0] < T:
-                raise ValueError("layernorm_bwd: dy_branch must be [>= T, d]")
-        x_f32 |= 2 | (4 if h16 else 0)
-    elif g_f16:
+    elif fmt == 2:                        # fp16 gradient stream (round 5): dy, dx, dy_branch and dx_dropped fp16; dx_dropped optional
         if not x_f32:
             raise ValueError("layernorm_bwd: an fp16 dy (the fp16 gradient stream) needs fp32 x")
+        h16 = True
         _chk(dx, F16, "dx", 2)
         if dx_dropped is not None:
             _chk(dx_dropped, F16, "dx_dropped", 2)
-        if dy_branch is not None:
-            _chk(dy_branch, F16, "dy_branch", 2)
-            if dy_branch.shape[1] != dy.shape[1] or dy_branch.shape[0] < T:
-                raise ValueError("layernorm_bwd: dy_branch must be [>= T, d]")
-        x_f32 |= 4 | 8
     else:
         if dy_branch is not None:
             raise ValueError("layernorm_bwd: dy_branch goes with an fp32 / fp16 dy")
         _chk(dy, BF16, "dy", 2), _chk(dx, BF16, "dx", 2)
-    _chk(x, F32 if (x_f32 & 1) else BF16, "x", 2)
+    if dy_branch is not None:
+        _chk(dy_branch, F16 if h16 else BF16, "dy_branch", 2)
+        if dy_branch.shape[1] != dy.shape[1] or dy_branch.shape[0] < T:
+            raise ValueError("layernorm_bwd: dy_branch must be [>= T, d]")
+    _chk(x, F32 if x_f32 else BF16, "x", 2)
     d = x.shape[1]
+    sums = (_p(dgamma), _p(dbeta), _p(dbias))
     if defer is not None:
         for t, nme in ((dgamma, "dgamma"), (dbeta, "dbeta"), (dbias, "dbias")):
             if t is not None:
                 _chk(t, F32, nme, 1)
         if partial.numel() < ln_partial_elems(T, d):
             raise ValueError("layernorm_bwd: deferred reduction needs a partial buffer of ln_partial_elems(T, d) floats")
-        call("cldrd_layernorm_bwd", _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(dx_dropped), None, None, None,
-             _p(partial), T, d, dropout_p, seed, 1 if accumulate else 0, x_f32, _p(dy_branch), _stream())
+        sums = (None, None, None)
+    call("cldrd_layernorm_bwd", _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(dx_dropped), *sums, _p(partial), T, d, dropout_p, seed,
+         1 if accumulate else 0, x_f32, fmt, 1 if h16 else 0, _p(dy_branch), _stream())
+    if defer is not None:
         defer.jobs.append((partial, dgamma, dbeta, dbias, int(T), int(d)))
-        return
-    call("cldrd_layernorm_bwd", _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(dx_dropped), _p(dgamma),
-         _p(dbeta), _p(dbias), _p(partial), T, d, dropout_p, seed, 1 if accumulate else 0, x_f32, _p(dy_branch), _stream())
 
 
 def colsum(x, out, partial, T, accumulate=True):
@@ -712,10 +687,13 @@ def colsum(x, out, partial, T, accumulate=True):
     call("cldrd_colsum_bf16", _p(x), _p(out), _p(partial), T, x.shape[1], x.stride(0), 1 if accumulate else 0, _stream())
 
 
-def scatter_cls_grad(dcls, g, R, stride, T):
-    """g[T, d] (bf16, or fp32 for the fp32 gradient stream) = 0 except rows r * stride <- dcls[r]."""
+def scatter_cls_grad(dcls, g, R, T, stride=0, idx=None):
+    """g[T, d] (bf16, fp32 or fp16: the format of the gradient stream) = 0 except rows idx[r] (int32, the CLS rows of a packed batch) or
+    r * stride <- dcls[r]."""
     _chk(dcls, F32, "dcls", 2), _chk(g, g.dtype, "g", 2)
-    call("cldrd_scatter_cls_grad", _p(dcls), _p(g), R, dcls.shape[1], stride, T, _stream_fmt(g), _stream())
+    if idx is not None:
+        _chk(idx, torch.int32, "idx", 1)
+    call("cldrd_scatter_cls_grad", _p(dcls), _p(g), R, dcls.shape[1], stride, _p(idx), T, _stream_fmt(g), _stream())
 
 
 def score_fwd(q, p, logits, B, N, mode=0):
@@ -834,15 +812,13 @@ def adamw_step(p, g, m, v, decay_flags, shadow, *, lr, beta1, beta2, eps, weight
     """``shadow16`` (fp16, optional) receives the updated parameters ``[h16_range[0], h16_range[1])`` (``shadow16[0]`` = the first of them)."""
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, F32, n, 1)
-    if shadow16 is None:
-        call("cldrd_adamw_step", _p(p), _p(g), _p(m), _p(v), _p(decay_flags), _p(shadow), p.numel(), float(lr), float(beta1),
-             float(beta2), float(eps), float(weight_decay), int(step), _p(clip), _stream())
-        return
-    _chk(shadow16, F16, "shadow16", 1)
-    lo, hi = int(h16_range[0]), int(h16_range[1])
-    if shadow16.numel() < hi - lo:
-        raise ValueError("adamw_step: shadow16 is smaller than its range")
-    call("cldrd_adamw_step_h16", _p(p), _p(g), _p(m), _p(v), _p(decay_flags), _p(shadow), p.numel(), float(lr), float(beta1),
+    lo = hi = 0
+    if shadow16 is not None:
+        _chk(shadow16, F16, "shadow16", 1)
+        lo, hi = int(h16_range[0]), int(h16_range[1])
+        if shadow16.numel() < hi - lo:
+            raise ValueError("adamw_step: shadow16 is smaller than its range")
+    call("cldrd_adamw_step", _p(p), _p(g), _p(m), _p(v), _p(decay_flags), _p(shadow), p.numel(), float(lr), float(beta1),
          float(beta2), float(eps), float(weight_decay), int(step), _p(clip), _p(shadow16), lo, hi, _stream())
 
 
@@ -875,8 +851,8 @@ def topk_scan_filter(Q, P, thr, counts, cand_rows, cand_scores, tiled=False):
     nq, d = Q.shape
     if P.shape[1] != d or not Q.is_contiguous() or not P.is_contiguous() or counts.numel() < nq + 1:
         raise ValueError("topk_scan_filter: shape mismatch (counts needs nq + 1 entries)")
-    call("cldrd_topk_scan_filter_tiled" if tiled else "cldrd_topk_scan_filter", _p(Q), _p(P), nq, P.shape[0], d, _p(thr), _p(counts), _p(cand_rows), _p(cand_scores),
-         cand_rows.shape[1], 1 if dt == F16 else 0, _stream())
+    call("cldrd_topk_scan_filter", _p(Q), _p(P), nq, P.shape[0], d, _p(thr), _p(counts), _p(cand_rows), _p(cand_scores),
+         cand_rows.shape[1], 1 if dt == F16 else 0, 1 if tiled else 0, _stream())
 
 
 def cast_f16(src, dst, flag=None):
@@ -906,47 +882,33 @@ def topk_select(counts, cand_rows, cand_scores, kk, thr, eps, rows2, n2, status,
          rows2.shape[1], _p(n2), _p(status), _p(khat), 1 if exhaustive else 0, _stream())
 
 
-def flatip_search(q32, qh, thr, eps, P16, P32, k, counts, cand_rows, cand_scores, rows2, scores2, n2, status, khat, D, I, exhaustive=False,
-                  qtile=128, tiled=False):
+def flatip_search(q32, qh, thr, eps, P16, k, counts, cand_rows, cand_scores, rows2, scores2, n2, status, khat, D, I, exhaustive=False,
+                  qtile=128, tiled=False, P32=None, qmu=None):
     """The whole search of one shard (include/cldrd_hip.h: cldrd_flatip_search); everything device resident, no host sync.
+    ``P32`` given: fp32-row mode, the re-score reads the fp32 rows (``P16`` is the scan shadow).  ``qmu`` given instead: fp16-row mode, ``P16`` =
+    fp16(p - mu) is the scan's operand and the row the re-score reads, ``qmu`` = <q, mu> (fp64 [nq], :func:`query_dot64`).
     ``tiled``: scan through the tiled kernels (cannot drop hits; the retry form for passes with status bit 4)."""
-    _chk(q32, F32, "q32", 2), _chk(P32, F32, "P32", 2), _chk(thr, F32, "thr", 1), _chk(eps, F32, "eps", 1)
-    _chk(D, F32, "D", 2), _chk(I, torch.int32, "I", 2)
+    if (P32 is None) == (qmu is None):
+        raise ValueError("flatip_search: give P32 (fp32-row mode) or qmu (fp16-row mode), not both")
+    P = P32 if P32 is not None else P16              # the rows the re-score reads
+    _chk(q32, F32, "q32", 2), _chk(thr, F32, "thr", 1), _chk(eps, F32, "eps", 1), _chk(D, F32, "D", 2), _chk(I, torch.int32, "I", 2)
+    if P32 is not None:
+        _chk(P32, F32, "P32", 2)
+    else:
+        _chk(P16, F16, "P16", 2), _chk(qmu, torch.float64, "qmu", 1)
     nq, d = q32.shape
-    rows = P32.shape[0]
     if not exhaustive:
         _chk(qh, F16, "qh", 2), _chk(P16, F16, "P16", 2)
+    if P.shape[1] != d or (qmu is not None and qmu.numel() < nq):
+        raise ValueError("flatip_search: the rows must be [rows, d] and qmu [nq]")
     if cand_rows.shape[0] < qtile or rows2.shape[0] < qtile:
         raise ValueError("flatip_search: the candidate buffers need qtile rows")
     if counts.numel() < ((nq + qtile - 1) // qtile) * (qtile + 1) or n2.numel() < nq or status.numel() < nq or khat.numel() < nq or D.shape != (nq, k) or I.shape != (nq, k):
         raise ValueError("flatip_search: buffer sizes do not match nq / k")
-    if not (q32.is_contiguous() and P32.is_contiguous() and D.is_contiguous() and I.is_contiguous()):
+    if not (q32.is_contiguous() and P.is_contiguous() and D.is_contiguous() and I.is_contiguous() and (qmu is None or qmu.is_contiguous())):
         raise ValueError("flatip_search: operands must be contiguous")
-    call("cldrd_flatip_search", _p(q32), _p(qh), _p(thr), _p(eps), _p(P16), _p(P32), rows, d, nq, int(k), int(qtile), _p(counts), _p(cand_rows),
-         _p(cand_scores), cand_rows.shape[1], _p(rows2), _p(scores2), rows2.shape[1], _p(n2), _p(status), _p(khat), _p(D), _p(I),
-         (1 if exhaustive else 0) | (2 if tiled else 0), _stream())
-
-
-def flatip_search16(q32, qh, thr, eps, P16, qmu, k, counts, cand_rows, cand_scores, rows2, scores2, n2, status, khat, D, I, exhaustive=False,
-                    qtile=128, tiled=False):
-    """:func:`flatip_search` on an index in fp16-row mode (cldrd_flatip_search16): ``P16`` = fp16(p - mu) is the scan's operand and the row
-    the re-score reads, ``qmu`` = <q, mu> (fp64 [nq], :func:`query_dot64`)."""
-    _chk(q32, F32, "q32", 2), _chk(P16, F16, "P16", 2), _chk(qmu, torch.float64, "qmu", 1), _chk(thr, F32, "thr", 1), _chk(eps, F32, "eps", 1)
-    _chk(D, F32, "D", 2), _chk(I, torch.int32, "I", 2)
-    nq, d = q32.shape
-    rows = P16.shape[0]
-    if not exhaustive:
-        _chk(qh, F16, "qh", 2)
-    if P16.shape[1] != d or qmu.numel() < nq:
-        raise ValueError("flatip_search16: P16 must be [rows, d] and qmu [nq]")
-    if cand_rows.shape[0] < qtile or rows2.shape[0] < qtile:
-        raise ValueError("flatip_search16: the candidate buffers need qtile rows")
-    if counts.numel() < ((nq + qtile - 1) // qtile) * (qtile + 1) or n2.numel() < nq or status.numel() < nq or khat.numel() < nq or D.shape != (nq, k) or I.shape != (nq, k):
-        raise ValueError("flatip_search16: buffer sizes do not match nq / k")
-    if not (q32.is_contiguous() and P16.is_contiguous() and qmu.is_contiguous() and D.is_contiguous() and I.is_contiguous()):
-        raise ValueError("flatip_search16: operands must be contiguous")
-    call("cldrd_flatip_search16", _p(q32), _p(qh), _p(thr), _p(eps), _p(P16), _p(qmu), rows, d, nq, int(k), int(qtile), _p(counts), _p(cand_rows),
-         _p(cand_scores), cand_rows.shape[1], _p(rows2), _p(scores2), rows2.shape[1], _p(n2), _p(status), _p(khat), _p(D), _p(I),
+    call("cldrd_flatip_search", _p(q32), _p(qh), _p(thr), _p(eps), _p(P16), _p(P32), _p(qmu), P.shape[0], d, nq, int(k), int(qtile), _p(counts),
+         _p(cand_rows), _p(cand_scores), cand_rows.shape[1], _p(rows2), _p(scores2), rows2.shape[1], _p(n2), _p(status), _p(khat), _p(D), _p(I),
          (1 if exhaustive else 0) | (2 if tiled else 0), _stream())
 
 
@@ -960,28 +922,28 @@ def query_dot64(q32, mu):
     return out
 
 
-def topk_rescore16(q32, P16, qmu, counts, cand_rows, cand_scores):
-    """cand_scores[q, c] = fp32(qmu[q] + <q32[q], P16[cand_rows[q, c]]>) for c < counts[q], sums in fp64 (cldrd_topk_rescore16)"""
-    _chk(q32, F32, "q32", 2), _chk(P16, F16, "P16", 2), _chk(qmu, torch.float64, "qmu", 1)
-    _chk(counts, torch.int32, "counts", 1), _chk(cand_rows, torch.int32, "cand_rows", 2), _chk(cand_scores, F32, "cand_scores", 2)
-    if not (q32.is_contiguous() and P16.is_contiguous() and cand_rows.is_contiguous() and cand_scores.is_contiguous()):
-        raise ValueError("topk_rescore16: operands must be contiguous")
-    if P16.shape[1] != q32.shape[1] or qmu.numel() < q32.shape[0] or counts.numel() < q32.shape[0] or cand_rows.shape != cand_scores.shape \
-            or cand_rows.shape[0] < q32.shape[0]:
-        raise ValueError("topk_rescore16: shape mismatch")
-    call("cldrd_topk_rescore16", _p(q32), _p(P16), _p(qmu), q32.shape[1], _p(counts), _p(cand_rows), _p(cand_scores), q32.shape[0],
-         cand_rows.shape[1], _stream())
-
-
 def topk_kth_largest(scores, S, kth, thr):
     _chk(scores, F32, "scores", 2), _chk(thr, F32, "thr", 1)
     call("cldrd_topk_kth_largest", _p(scores), scores.stride(0), scores.shape[0], S, int(kth), _p(thr), _stream())
 
 
-def topk_rescore(q32, P32, counts, cand_rows, cand_scores):
-    _chk(q32, F32, "q32", 2), _chk(P32, F32, "P32", 2)
-    call("cldrd_topk_rescore", _p(q32), _p(P32), q32.shape[1], _p(counts), _p(cand_rows), _p(cand_scores), q32.shape[0],
-         cand_rows.shape[1], _stream())
+def topk_rescore(q32, P, counts, cand_rows, cand_scores, qmu=None):
+    """cand_scores[q, c] = exact score of row cand_rows[q, c] for c < counts[q]: fp32(<q32[q], P[row]>) for fp32 rows ``P``; for fp16 rows (the
+    fp16-row mode) fp32(qmu[q] + <q32[q], P[row]>), sums in fp64, ``qmu`` = <q, mu> (fp64, :func:`query_dot64`)."""
+    f16 = P.dtype == F16
+    _chk(q32, F32, "q32", 2), _chk(P, F16 if f16 else F32, "P", 2)
+    _chk(counts, torch.int32, "counts", 1), _chk(cand_rows, torch.int32, "cand_rows", 2), _chk(cand_scores, F32, "cand_scores", 2)
+    if f16 != (qmu is not None):
+        raise ValueError("topk_rescore: qmu goes with fp16 rows")
+    if f16:
+        _chk(qmu, torch.float64, "qmu", 1)
+    if not (q32.is_contiguous() and P.is_contiguous() and cand_rows.is_contiguous() and cand_scores.is_contiguous()):
+        raise ValueError("topk_rescore: operands must be contiguous")
+    if P.shape[1] != q32.shape[1] or (f16 and qmu.numel() < q32.shape[0]) or counts.numel() < q32.shape[0] or cand_rows.shape != cand_scores.shape \
+            or cand_rows.shape[0] < q32.shape[0]:
+        raise ValueError("topk_rescore: shape mismatch")
+    call("cldrd_topk_rescore", _p(q32), None if f16 else _p(P), _p(P) if f16 else None, _p(qmu), q32.shape[1], _p(counts), _p(cand_rows),
+         _p(cand_scores), q32.shape[0], cand_rows.shape[1], _stream())
 
 
 def topk_sort(counts, cand_rows, cand_scores, k, D, I):
@@ -991,9 +953,8 @@ def topk_sort(counts, cand_rows, cand_scores, k, D, I):
 
 
 def row_sqnorm_max(P32) -> float:
-    _chk(P32, F32, "P32", 2)
     out = torch.zeros(1, dtype=torch.int32, device=P32.device)
-    call("cldrd_row_sqnorm_max", _p(P32), P32.shape[0], P32.shape[1], _p(out), _stream())
+    row_sqnorm_max_into(P32, out)
     return float(out.view(torch.float32).item())
 
 
@@ -1006,32 +967,14 @@ def row_sqnorm_max_into(P32, out):
     call("cldrd_row_sqnorm_max", _p(P32), P32.shape[0], P32.shape[1], _p(out), _stream())
 
 
-def gather_cast_rows(src32, dst_bf16, n_out, stride):
-    _chk(src32, F32, "src32", 2), _chk(dst_bf16, BF16, "dst_bf16", 2)
-    call("cldrd_gather_cast_rows", _p(src32), _p(dst_bf16), n_out, stride, src32.shape[1], _stream())
-
-
-def gather_cast_rows16(src16, dst_bf16, n_out, stride):
-    """dst[i] = bf16(src16[i * stride]) for i < n_out (cldrd_gather_cast_rows16)"""
-    _chk(src16, F16, "src16", 2), _chk(dst_bf16, BF16, "dst_bf16", 2)
-    if not (src16.is_contiguous() and dst_bf16.is_contiguous()) or dst_bf16.shape[1] != src16.shape[1] or n_out > dst_bf16.shape[0] \
-            or (n_out - 1) * stride >= src16.shape[0]:
-        raise ValueError("gather_cast_rows16: shape mismatch")
-    call("cldrd_gather_cast_rows16", _p(src16), _p(dst_bf16), n_out, stride, src16.shape[1], _stream())
-
-
-def index_center_cast_chunk(P32, mu, row0, P16, sample_bf16, s_stride, s_rows, cmax, flag):
-    """:func:`index_center_cast` for rows [row0, row0 + len(P32)) of a shard attached chunk by chunk: ``P16`` is that slice of the shard's
-    fp16 rows, ``sample_bf16`` the whole shard's sample; ``cmax`` (int32 [1], zeroed before the first chunk) and ``flag`` accumulate."""
-    _chk(P32, F32, "P32", 2), _chk(mu, F32, "mu", 1), _chk(P16, F16, "P16", 2), _chk(cmax, torch.int32, "cmax", 1)
-    if sample_bf16 is not None:
-        _chk(sample_bf16, BF16, "sample_bf16", 2)
-        if int(s_rows) > sample_bf16.shape[0] or sample_bf16.shape[1] != P32.shape[1] or not sample_bf16.is_contiguous():
-            raise ValueError("index_center_cast_chunk: the sample needs s_rows rows of width d")
-    if P16.shape != P32.shape or mu.numel() != P32.shape[1] or not (P32.is_contiguous() and P16.is_contiguous()):
-        raise ValueError("index_center_cast_chunk: P16 must be the contiguous [rows, d] slice that matches P32")
-    call("cldrd_index_center_cast_chunk", _p(P32), _p(mu), P32.shape[0], int(row0), P32.shape[1], _p(P16), _p(sample_bf16), int(s_stride), int(s_rows),
-         _p(cmax), _p(flag), _stream())
+def gather_cast_rows(src, dst_bf16, n_out, stride):
+    """dst[i] = bf16(src[i * stride]) for i < n_out; ``src`` fp32 rows, or fp16 rows (an index uploaded in fp16-row mode)"""
+    f16 = src.dtype == F16
+    _chk(src, F16 if f16 else F32, "src", 2), _chk(dst_bf16, BF16, "dst_bf16", 2)
+    if not (src.is_contiguous() and dst_bf16.is_contiguous()) or dst_bf16.shape[1] != src.shape[1] or n_out > dst_bf16.shape[0] \
+            or (n_out - 1) * stride >= src.shape[0]:
+        raise ValueError("gather_cast_rows: shape mismatch")
+    call("cldrd_gather_cast_rows", _p(src), 1 if f16 else 0, _p(dst_bf16), n_out, stride, src.shape[1], _stream())
 
 
 def index_col_mean(P32):
@@ -1045,15 +988,23 @@ def index_col_mean(P32):
     return mu
 
 
-def index_center_cast(P32, mu, P16, sample_bf16, s_stride, s_rows, flag):
+def index_center_cast(P32, mu, P16, sample_bf16, s_stride, s_rows, flag, row0=0, cmax=None):
     """P16 = fp16(P32 - mu), sample = bf16 of every s_stride-th centred row; returns the DEVICE int32 word holding the bit pattern of
-    max_r |P32[r] - mu|^2 as fp32 (cldrd_index_center_cast) - read it with ``.view(torch.float32).item()``"""
+    max_r |P32[r] - mu|^2 as fp32 (cldrd_index_center_cast) - read it with ``.view(torch.float32).item()``.
+    A shard attached chunk by chunk: ``P32`` / ``P16`` are rows [row0, row0 + len(P32)) of it, ``sample_bf16`` is the whole shard's sample;
+    ``cmax`` (int32 [1], zeroed before the first chunk; None: a fresh one) and ``flag`` accumulate over the chunks."""
     _chk(P32, F32, "P32", 2), _chk(mu, F32, "mu", 1), _chk(P16, F16, "P16", 2)
     if sample_bf16 is not None:
         _chk(sample_bf16, BF16, "sample_bf16", 2)
-    cmax = torch.zeros(1, dtype=torch.int32, device=P32.device)
-    call("cldrd_index_center_cast", _p(P32), _p(mu), P32.shape[0], P32.shape[1], _p(P16), _p(sample_bf16), int(s_stride), int(s_rows), _p(cmax),
-         _p(flag), _stream())
+        if int(s_rows) > sample_bf16.shape[0] or sample_bf16.shape[1] != P32.shape[1] or not sample_bf16.is_contiguous():
+            raise ValueError("index_center_cast: the sample needs s_rows rows of width d")
+    if P16.shape != P32.shape or mu.numel() != P32.shape[1] or not (P32.is_contiguous() and P16.is_contiguous()):
+        raise ValueError("index_center_cast: P16 must be the contiguous [rows, d] slice that matches P32")
+    if cmax is None:
+        cmax = torch.zeros(1, dtype=torch.int32, device=P32.device)
+    _chk(cmax, torch.int32, "cmax", 1)
+    call("cldrd_index_center_cast", _p(P32), _p(mu), P32.shape[0], int(row0), P32.shape[1], _p(P16), _p(sample_bf16), int(s_stride), int(s_rows),
+         _p(cmax), _p(flag), _stream())
     return cmax
 
 

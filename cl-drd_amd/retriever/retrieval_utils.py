@@ -327,6 +327,7 @@ class FlatIPIndex:
         """the threshold sample of :meth:`_attach` (sizes explained there)"""
         self._s_stride = max(1, n // min(max(SAMPLE_ROWS, n // 64), 1 << 18))
         self._s_rows = min(n, (n + self._s_stride - 1) // self._s_stride)
+        # the GEMM wants a column count that is a multiple of 8: zero rows pad the sample (never read by the select)
         self._sample = torch.zeros((self._s_rows + 7) // 8 * 8, d, dtype=torch.bfloat16, device=device)
 
     def _attach16(self, device, n: int, chunks):
@@ -334,7 +335,7 @@ class FlatIPIndex:
         pass 1 - max |p|^2 and the mean row of every chunk (cldrd_row_sqnorm_max, cldrd_index_col_mean), the chunk means combined on the host in
         fp64 weighted by chunk size (mu depends neither on the device nor on timing; it need not equal the fp32 mode's mu bit for bit);
         pass 2 - centre + cast every chunk into its slice of P16 and of the sample, max centred norm and range flag accumulated
-        (cldrd_index_center_cast_chunk).  No fp32 row stays in HBM."""
+        (cldrd_index_center_cast with row0).  No fp32 row stays in HBM."""
         d = self.d
         if d % 4:
             raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
@@ -366,7 +367,7 @@ class FlatIPIndex:
             self._p16 = torch.empty(n, d, dtype=torch.float16, device=device)
             self._plan_sample(n, d, device)
             for lo, c in chunks():
-                ops.index_center_cast_chunk(c, mu, lo, self._p16[lo:lo + c.shape[0]], self._sample, self._s_stride, self._s_rows, cmax, flag)
+                ops.index_center_cast(c, mu, self._p16[lo:lo + c.shape[0]], self._sample, self._s_stride, self._s_rows, flag, row0=lo, cmax=cmax)
             del c
             self._mu, self._mu_host = mu, mu_h
             self._cnorm, self._raw_max = math.sqrt(float(cmax.view(torch.float32).item())), raw_max
@@ -391,19 +392,29 @@ class FlatIPIndex:
                     warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
                     self._p16[lo:hi].copy_(torch.from_numpy(np.ascontiguousarray(r16[lo:hi])))
             self._plan_sample(n, d, device)
-            ops.gather_cast_rows16(self._p16, self._sample, self._s_rows, self._s_stride)
+            ops.gather_cast_rows(self._p16, self._sample, self._s_rows, self._s_stride)
             self._mu = torch.from_numpy(np.ascontiguousarray(self._mu_host, dtype=np.float32)).to(device)
             self._finish_attach16(0)
 
     def _finish_attach16(self, flag: int):
-        d = self.d
         self._fp16_rows = True
-        # the bound of _attach: max |p - mu| plus 2^-12 max|p| for the rounding of the fp32 subtraction.  The scan's operand now IS the stored
-        # row, so the second term is slack here; the bound is kept as it is (cldrd_topk_thresholds unchanged)
-        self._max_norm = self._cnorm * (1.0 + 1e-6) + self._raw_max * 2.0 ** -12
-        self.query_tile = 256 if (d == 768 and self.query_tile_request != 128) else 128
-        if flag or not math.isfinite(self._max_norm):
+        try:
+            # the scan's operand now IS the stored row, so the 2^-12 max|p| term of the bound is slack here; the bound is kept as it is
+            # (cldrd_topk_thresholds unchanged)
+            self._finish_attach(flag)
+        except ValueError:
             self._p16 = self._sample = None
+            raise
+
+    def _finish_attach(self, flag: int):
+        """the end of every attach, from ``_cnorm`` / ``_raw_max`` and the range flag of the centre + cast pass"""
+        # max |p - mu| for the bound, plus 2^-12 max|p|: the fp32 subtraction p - mu itself rounds (2^-24 |p| per element), which moves a
+        # centred score by up to |q| sqrt(d) 2^-24 max|p| < 2^-10 |q| (2^-12 max|p|) - folded into the norm the eps formula multiplies by 2^-10
+        self._max_norm = self._cnorm * (1.0 + 1e-6) + self._raw_max * 2.0 ** -12
+        # queries per pass over the index bytes: 256 at d = 768 (the streaming scan's two-batch form), else the reference's 128
+        # (`query_tile_request`: a test hook that asks for 128 at d = 768)
+        self.query_tile = 256 if (self.d == 768 and self.query_tile_request != 128) else 128
+        if flag or not math.isfinite(self._max_norm):
             raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
 
     def _attach(self, p32: torch.Tensor):
@@ -428,10 +439,7 @@ class FlatIPIndex:
             # sample size: SAMPLE_ROWS, or 1 / 64 of the rows on a larger index (the whole 8.84 M-row collection on one GPU: with 16 384 rows
             # the expected number of sample rows inside the top 1000 is 1.9, the estimate is the 9th largest sample score and the candidate
             # lists come out at ~6 300 +- 2 000 of their 8 192 slots: overflowing queries, one or two extra passes; with 138 k rows ~2 300)
-            self._s_stride = max(1, n // min(max(SAMPLE_ROWS, n // 64), 1 << 18))
-            self._s_rows = min(n, (n + self._s_stride - 1) // self._s_stride)
-            # the GEMM wants a column count that is a multiple of 8: zero rows pad the sample (never read by the select)
-            self._sample = torch.zeros((self._s_rows + 7) // 8 * 8, d, dtype=torch.bfloat16, device=device)
+            self._plan_sample(n, d, device)
             # three launches over the fp32 rows (cldrd_row_sqnorm_max, cldrd_index_col_mean, cldrd_index_center_cast: mean row in fp64, then
             # centre + fp16 shadow + max centred norm + bf16 sample + range flag in ONE pass); until round 5 this was 17 chunks of
             # at::native kernels per attach (mean, subtract, double-precision norms, casts, a strided gather)
@@ -439,15 +447,8 @@ class FlatIPIndex:
             mu = ops.index_col_mean(self._p32) if math.isfinite(raw_max) else torch.zeros(d, dtype=torch.float32, device=device)
             self._mu = mu
             cmax = ops.index_center_cast(self._p32, mu, self._p16, self._sample, self._s_stride, self._s_rows, flag)
-            # max |p - mu| for the bound, plus 2^-12 max|p|: the fp32 subtraction p - mu itself rounds (2^-24 |p| per element), which moves a
-            # centred score by up to |q| sqrt(d) 2^-24 max|p| < 2^-10 |q| (2^-12 max|p|) - folded into the norm the eps formula multiplies by 2^-10
             self._cnorm, self._raw_max = math.sqrt(float(cmax.view(torch.float32).item())), raw_max
-            self._max_norm = self._cnorm * (1.0 + 1e-6) + raw_max * 2.0 ** -12
-            # queries per pass over the index bytes: 256 at d = 768 (the streaming scan's two-batch form), else the reference's 128
-            # (`query_tile_request`: a test hook that asks for 128 at d = 768)
-            self.query_tile = 256 if (d == 768 and self.query_tile_request != 128) else 128
-            if int(flag.item()) or not math.isfinite(self._max_norm):
-                raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
+            self._finish_attach(int(flag.item()))
 
     # -- search -------------------------------------------------------------------------------------------------
     @staticmethod
@@ -643,7 +644,7 @@ class FlatIPIndex:
         """Exact top-k of a few queries with EVERY row re-scored in fp32, CAND_CAP rows at a time (the exhaustive form of
         cldrd_flatip_search on row slices), the running top-k merged with each chunk's by the same sort kernel (score desc, row position
         asc).  The last resort of :meth:`search_device`: reads the fp32 rows once per 128/256 queries, needs no threshold, cannot fail.
-        fp16-row mode: the same over slices of the fp16 rows (cldrd_flatip_search16, scores as the class docstring defines them)."""
+        fp16-row mode: the same over slices of the fp16 rows (scores as the class docstring defines them)."""
         dev = self.device
         n, d = self._p16.shape
         qmu = ops.query_dot64(q32.contiguous(), self._mu) if self._fp16_rows else None
@@ -664,12 +665,8 @@ class FlatIPIndex:
             nb = (nq + QT - 1) // QT
             counts = torch.zeros(nb * (QT + 1), **i32)
             n2, st, khat = torch.empty(nq, **i32), torch.empty(nq, **i32), torch.empty(nq, **f32)
-            if qmu is not None:
-                ops.flatip_search16(q32, None, thr, eps, self._p16[lo:hi], qmu, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"],
-                                    ws["scores2"], n2, st, khat, Dc, Ic, exhaustive=True, qtile=QT)
-            else:
-                ops.flatip_search(q32, None, thr, eps, None, self._p32[lo:hi], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
-                                  n2, st, khat, Dc, Ic, exhaustive=True, qtile=QT)
+            ops.flatip_search(q32, None, thr, eps, self._p16[lo:hi], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
+                              n2, st, khat, Dc, Ic, exhaustive=True, qtile=QT, P32=self._p32[lo:hi] if qmu is None else None, qmu=qmu)
             Ic = torch.where(Ic >= 0, Ic + lo, Ic)
             rows = torch.cat([I, Ic], dim=1).contiguous()
             scores = torch.cat([D, Dc], dim=1).contiguous()
@@ -699,12 +696,8 @@ class FlatIPIndex:
         n2 = torch.empty(nq, dtype=torch.int32, device=dev)
         status = torch.empty(nq, dtype=torch.int32, device=dev)
         khat = torch.empty(nq, dtype=torch.float32, device=dev)
-        if qmu is not None:
-            ops.flatip_search16(q32, qh, thr, eps, self._p16, qmu, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
-                                n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled)
-            return status, counts, n2, khat
-        ops.flatip_search(q32, qh, thr, eps, self._p16, self._p32, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
-                          n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled)
+        ops.flatip_search(q32, qh, thr, eps, self._p16, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
+                          n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled, P32=self._p32, qmu=qmu)      # _p32 is None in fp16-row mode
         return status, counts, n2, khat
 
     # -- persistence (own format; faiss' binary layout is not reproduced) ----------------

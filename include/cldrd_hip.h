@@ -126,31 +126,29 @@ int cldrd_attention_bwd(const void* qkv, const long long* mask, const int* cu_ro
 /* CLS-only attention of the LAST layer (the reference pools last_hidden_state[:, 0, :], models/nway_dual_encoder.py:52,56,64):
  * qc: [nseq, H*64] = queries of token 0; kv: [rows, 2*H*64] = K | V of every token, padded or packed as above (no lists); ctx/dctx/dqc: [nseq, H*64];
  * probs: fp32 [nseq, H, L] (softmax row, saved for the backward; required); dkv: [rows, 2*H*64] in the layout of kv (every row written).
- * cldrd_add_rows_strided: dst[m * stride_rows] += src[m] for bf16 rows of d elements (puts the CLS-row gradients back). */
+ * cldrd_add_rows: dst[row(m)] += src[m] for rows of d elements (puts the CLS-row gradients back); row(m) = idx ? idx[m] : m * stride_rows (idx: device
+ * int32 [M], the CLS rows of a packed batch; stride_rows is then ignored), fmt: enum cldrd_stream_fmt below. */
 int cldrd_attention_cls_fwd(const void* qc, const void* kv, const long long* mask, const int* cu_rows, void* ctx, float* probs,
                             int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* ctx_f16_copy, void* stream);
 int cldrd_attention_cls_bwd(const void* qc, const void* kv, const int* cu_rows, const float* probs, const void* dctx, void* dqc, void* dkv,
                             int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* stream);
-int cldrd_add_rows_strided(void* dst, const void* src, int M, int d, int stride_rows, int f32, void* stream);   /* f32: fp32 rows (fp32 gradient stream) */
+int cldrd_add_rows(void* dst, const void* src, int M, int d, int stride_rows, const int* idx, int fmt, void* stream);
 
 /* ---- embeddings + LayerNorm (HF Embeddings.forward, sa_layer_norm / output_layer_norm) --------------------
  * d <= 1024, d % 4 == 0.  `partial` scratch: cldrd_ln_partial_blocks(T) * 3 * d floats. */
 int cldrd_ln_partial_blocks(int T);
-int cldrd_embed_ln_fwd(const long long* ids, const float* word, const float* pos, const float* type0,
-                       const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
+/* Token types: type_ids == NULL: every row takes row 0 of type_table (NULL for DistilBERT, which has none); type_vocab is ignored.
+ * type_ids != NULL (cross-encoder pairs): device int32 [T] (clamped to 0 .. type_vocab - 1) into the whole [type_vocab, d] table, which is then
+ * required.  With all-zero type_ids it computes what type_ids == NULL does. */
+int cldrd_embed_ln_fwd(const long long* ids, const float* word, const float* pos, const float* type_table, const int* type_ids,
+                       int type_vocab, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
                        int d, int vocab, float eps, float dropout_p, unsigned long long seed, float* out32, int out_f16,
                        const int* pos_idx, void* out_bf16_copy, void* stream);
-/* cldrd_embed_ln_fwd with per-row token types (cross-encoder pairs): type_table = the whole [type_vocab, d] token-type table, type_ids
- * device int32 [T] (clamped to 0 .. type_vocab - 1).  With all-zero type_ids it computes what cldrd_embed_ln_fwd(type0 = table row 0) does. */
-int cldrd_embed_ln_fwd_typed(const long long* ids, const float* word, const float* pos, const float* type_table, const int* type_ids,
-                             int type_vocab, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
-                             int d, int vocab, float eps, float dropout_p, unsigned long long seed, float* out32, int out_f16,
-                             const int* pos_idx, void* out_bf16_copy, void* stream);
 int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
                        const float* gamma, const float* mean, const float* rstd, float* dword, float* dpos,
                        float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
-                       float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int dy_f32, const void* dy_branch,
-                       void* stream);
+                       float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16,
+                       const void* dy_branch, void* stream);
 /* out = LN(x)*gamma+beta (bf16); cls_out (fp32 [T/cls_stride, d], optional) receives rows r % cls_stride == 0:
  * the `[0][:, 0, :]` CLS pooling of models/nway_dual_encoder.py:52,56,64.
  * x_f32 != 0: x is fp32 (the pre-LN sum of the fp32 residual stream) and out32 (optional) receives the fp32 output next to
@@ -160,19 +158,23 @@ int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, 
 int cldrd_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* out, float* mean, float* rstd,
                         int T, int d, float eps, float* cls_out, int cls_stride, int x_f32, float* out32, int out_f16,
                         void* out_bf16_copy, void* stream);
+/* The format of the GRADIENT STREAM - the rows that carry dL/dx from one backward kernel to the next - is said by one code wherever such rows
+ * are passed (grad_fmt of cldrd_embed_ln_bwd and cldrd_layernorm_bwd, fmt of cldrd_scatter_cls_grad and cldrd_add_rows):
+ *   CLDRD_STREAM_BF16  dy is read and dx written as bf16 rows; no dy_branch.
+ *   CLDRD_STREAM_F32   dy and dx are fp32 rows; needs x_f32 (the pre-LN sums of the fp32 residual stream) and dx_dropped, the 16-bit MFMA operand
+ *                      of the next data-gradient GEMM (written without dropout too); dy_branch (16-bit, optional) is added to dy on load - the
+ *                      output of the data-gradient GEMM of the branch that joins the residual path here.  operand_f16 / branch_f16 != 0:
+ *                      dx_dropped and dy_branch are fp16, not bf16 (the all-fp16 training mode).
+ *   CLDRD_STREAM_F16   dy and dx are fp16 rows carrying the loss scale; needs x_f32; dx_dropped and dy_branch are fp16 whatever operand_f16 /
+ *                      branch_f16 say; dx_dropped may be NULL when no dropout separates the stream from the MFMA operand (dx then is that operand).
+ * cldrd_add_rows takes an fp32 src with the fp32 and fp16 streams (fp16 dst += fp32 src, one rounding), a bf16 src with the bf16 one. */
+enum cldrd_stream_fmt { CLDRD_STREAM_BF16 = 0, CLDRD_STREAM_F32 = 1, CLDRD_STREAM_F16 = 2 };
 /* dx = LN backward of dy; dx_dropped (optional) = dropout-masked dx for the branch that passed through dropout;
- * dgamma/dbeta/dbias (each optional) receive sum(dy*xhat), sum(dy), sum(dx_dropped or dx).
- * x_f32: bit 0 = x holds fp32 pre-LN sums; bit 1 = fp32 GRADIENT STREAM: dy is read and dx written as fp32 rows, dx_dropped (bf16, then
- * required and written without dropout too) is the MFMA operand of the next data-gradient GEMM, and dy_branch (bf16, optional) is added to dy
- * on load - the output of the data-gradient GEMM of the branch that joins the residual path here.  cldrd_embed_ln_bwd: dy_f32 / dy_branch
- * likewise.  bit 2 = dx_dropped / dy_branch are fp16, not bf16 (the all-fp16 training mode).  bit 3 = FP16 GRADIENT STREAM (round 5; implies
- * bit 2, needs bit 0, excludes bit 1): dy is read and dx written as fp16 rows carrying the loss scale; dx_dropped may be NULL when no dropout
- * separates the stream from the MFMA operand (dx then is that operand).  cldrd_embed_ln_bwd: dy_f32 bit 3 = dy is fp16.
- * cldrd_scatter_cls_grad(_idx) g_f32 / cldrd_add_rows_strided, cldrd_add_rows_idx f32: 0 = bf16 rows, 1 = fp32, 2 = fp16 (the add forms
- * then take an fp32 src: fp16 dst += fp32 src, one rounding). */
+ * dgamma/dbeta/dbias (each optional) receive sum(dy*xhat), sum(dy), sum(dx_dropped or dx).  x_f32 != 0: x holds fp32 pre-LN sums. */
 int cldrd_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                         void* dx, void* dx_dropped, float* dgamma, float* dbeta, float* dbias, float* partial, int T,
-                        int d, float dropout_p, unsigned long long seed, int accumulate, int x_f32, const void* dy_branch, void* stream);
+                        int d, float dropout_p, unsigned long long seed, int accumulate, int x_f32, int grad_fmt, int operand_f16,
+                        const void* dy_branch, void* stream);
 /* Deferred form: call cldrd_layernorm_bwd with dgamma = dbeta = dbias = NULL (its `partial` then keeps the per-block sums and must
  * stay untouched), and reduce the scratch buffers of n such calls in ONE launch afterwards.  T[i] = the T of call i; outputs as
  * above, bit-identical to the immediate form.  (The parameter gradients of a LayerNorm are not on the backward's critical path.) */
@@ -180,8 +182,8 @@ int cldrd_ln_reduce_group(const float* const* partial, const int* T, float* cons
                           float* const* dbias, int n, int d, int accumulate, void* stream);
 /* out[N] (+)= column sums of bf16 x[T,N] (bias gradients).  partial: ceil(T/128) * N floats. */
 int cldrd_colsum_bf16(const void* x, float* out, float* partial, int T, int N, int ld, int accumulate, void* stream);
-/* g = zeros(bf16 [T,d]); g[r*stride] = dcls[r]  (gradient of the CLS pooling). */
-int cldrd_scatter_cls_grad(const float* dcls, void* g, int R, int d, int stride, int T, int g_f32, void* stream);   /* g_f32: g holds fp32 rows */
+/* g = zeros([T,d] rows of format fmt); g[row(r)] = dcls[r]  (gradient of the CLS pooling); row(r) = idx ? idx[r] : r * stride, as in cldrd_add_rows. */
+int cldrd_scatter_cls_grad(const float* dcls, void* g, int R, int d, int stride, const int* idx, int T, int fmt, void* stream);
 
 /* ---- N-way scoring (models/nway_dual_encoder.py:30-47) ----------------------------------------------------
  * mode 0: logits[B,N]; 1: in-batch, all negatives [B,B*N]; 2: in-batch, next sample's N [B,2N]. fp32. */
@@ -239,14 +241,11 @@ int cldrd_sqnorm_partial(const float* g, size_t n, float* partial, int nblk, voi
 void cldrd_set_norm_sink(float* slots, int capacity);
 int cldrd_norm_sink_used(void);
 int cldrd_clip_coef(const float* partial, int nblk_total, float max_norm, float* out, void* stream);
+/* shadow16 (NULL: none): the step also leaves an fp16 copy (RNE, as cldrd_cast_f16) of the updated parameters [h16_begin, h16_end) there
+ * (shadow16[0] = parameter h16_begin; bounds multiples of 4): the query tower's high-precision forward reads fp16 weights. */
 int cldrd_adamw_step(float* p, const float* g, float* m, float* v, const unsigned char* decay_flags, void* shadow,
                      size_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                     const float* clip, void* stream);
-/* The same step that also leaves an fp16 copy (RNE, as cldrd_cast_f16) of the updated parameters [h16_begin, h16_end) in shadow16
- * (shadow16[0] = parameter h16_begin; bounds multiples of 4): the query tower's high-precision forward reads fp16 weights. */
-int cldrd_adamw_step_h16(float* p, const float* g, float* m, float* v, const unsigned char* decay_flags, void* shadow,
-                         size_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                         const float* clip, void* shadow16, size_t h16_begin, size_t h16_end, void* stream);
+                     const float* clip, void* shadow16, size_t h16_begin, size_t h16_end, void* stream);
 int cldrd_cast_bf16(const float* src, void* dst, size_t n, void* stream);
 int cldrd_transpose_cast_batched(const float* src, void* dst, const long long* desc, const int* tile_prefix, int ndesc,
                                  int total_tiles, void* stream);
@@ -271,60 +270,52 @@ int cldrd_transpose_bf16_batched(const void* src, void* dst, const long long* de
  *   sort:    (score desc, row asc), first k -> D[nq,k], I[nq,k] (row index, -1 / -inf = missing).
  * The caller reads `status` once per search and redoes unproven queries with thresholds of its choice (same entry point).
  * `exhaustive` is a bit mask: bit 0 (rows <= cap): no scan, every row is re-scored; bit 1: the scan runs through the tiled kernels
- * (cldrd_topk_scan_filter_tiled: no on-chip hit list, so status bit 4 cannot occur) - the retry form for passes that dropped hits.
+ * (cldrd_topk_scan_filter with tiled != 0: no on-chip hit list, so status bit 4 cannot occur) - the retry form for passes that dropped hits.
  * Pieces, also callable one by one: prep (fp16 + bf16 copies and norms of the queries; *flag |= 1 if a value exceeds the fp16
  * range), kth (thr estimate: kth largest of sample scores), thresholds (eps[q] = bound on |scan - exact|, thr = est - 2 eps). */
 int cldrd_cast_f16(const float* src, void* dst, size_t n, unsigned int* flag, void* stream);
 int cldrd_topk_prep_queries(const float* q, void* q_f16, void* q_bf16, float* qnorm, int nq, int d, unsigned int* flag, void* stream);
 int cldrd_topk_thresholds(const float* est, const float* qnorm, float pmax, int d, float* thr, float* eps, int nq, void* stream);
 int cldrd_flatip_search(const float* q32, const void* q16, const float* thr, const float* eps, const void* P16, const float* P32,
-                        long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
+                        const double* qmu, long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
                         int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
                         int exhaustive, void* stream);
+/* tiled != 0: the same contract through the tiled GEMM kernels (any d % 64 == 0; hits go straight to the global lists, nothing is dropped) */
 int cldrd_topk_scan_filter(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
-                           int* cand_rows, float* cand_scores, int cap, int f16, void* stream);
-/* same contract through the tiled GEMM kernels (any d % 64 == 0; hits go straight to the global lists, nothing is dropped) */
-int cldrd_topk_scan_filter_tiled(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
-                           int* cand_rows, float* cand_scores, int cap, int f16, void* stream);
+                           int* cand_rows, float* cand_scores, int cap, int f16, int tiled, void* stream);
 int cldrd_topk_kth_largest(const float* scores, int ld, int nq, int S, int kth, float* thr, void* stream);
 /* counts has nq + 1 entries (counts[nq] = dropped hits of the scan) */
 int cldrd_topk_select(const int* counts, const int* cand_rows, const float* cand_scores, int nq, int cap, int kk, const float* thr,
                       const float* eps, int* rows2, int cap2, int* n2, int* status, float* khat, int exhaustive, void* stream);
-int cldrd_topk_rescore(const float* q, const float* P, int d, const int* counts, const int* cand_rows, float* cand_scores,
-                       int nq, int cap, void* stream);
+int cldrd_topk_rescore(const float* q, const float* P32, const void* P16, const double* qmu, int d, const int* counts, const int* cand_rows,
+                       float* cand_scores, int nq, int cap, void* stream);
 int cldrd_topk_sort(const int* counts, const int* cand_rows, const float* cand_scores, int nq, int cap, int k, float* D,
                     int* I, void* stream);
-/* fp16-row mode: an index that keeps per shard mu (fp32 [d], the mean row) and R16 = fp16(p - mu) and NO fp32 rows (half the resident bytes of
- * the scan shadow + fp32 rows pair).  The stored row is mu + R16[r]; its score is fp32(<q, mu> + <q, R16[r]>), both sums in fp64, one rounding:
- *   cldrd_query_dot64      out[q] = <q, mu> in fp64 (device double [nq], fixed summation order)
- *   cldrd_topk_rescore16   cldrd_topk_rescore with the rows read from P16 (16-byte loads when d % 8 == 0) and qmu[query] added before the rounding
- *   cldrd_flatip_search16  cldrd_flatip_search with P32 replaced by (P16, qmu): P16 is the scan's operand and the re-scored row; same passes,
- *                          status bits and `exhaustive` mask (bit 0: no scan, every row re-scored from P16)
- *   cldrd_gather_cast_rows16       dst[i] = bf16(src16[i * stride]): the threshold sample of an index uploaded as fp16 rows
- *   cldrd_index_center_cast_chunk  cldrd_index_center_cast on rows [row0, row0 + rows) of a shard attached chunk by chunk (P, P16 point at row0;
- *                          the sample is the whole shard's; *cmax_bits, *flag accumulate over the chunks) */
+/* Row modes.  P32 != NULL: fp32-row mode, the re-score reads the fp32 rows (P16 is the scan shadow only; qmu must be NULL).  P32 == NULL: fp16-row
+ * mode, an index that keeps per shard mu (fp32 [d], the mean row) and P16 = fp16(p - mu) and NO fp32 rows (half the resident bytes of the scan
+ * shadow + fp32 rows pair); P16 and qmu are then required.  The stored row is mu + P16[r]; its score is fp32(<q, mu> + <q, P16[r]>), both sums
+ * in fp64, one rounding:
+ *   cldrd_query_dot64        out[q] = <q, mu> in fp64 (device double [nq], fixed summation order): the qmu argument
+ *   cldrd_topk_rescore       fp16-row mode: the rows are read from P16 (16-byte loads when d % 8 == 0) and qmu[query] is added before the rounding
+ *   cldrd_flatip_search      fp16-row mode: P16 is the scan's operand and the re-scored row; same passes, status bits and `exhaustive` mask (bit 0:
+ *                            no scan, every row re-scored from P16)
+ *   cldrd_gather_cast_rows   dst[i] = bf16(src[i * stride]) from fp32 rows, or (src_f16 != 0) from fp16 rows: the threshold sample of an index
+ *   cldrd_index_center_cast  rows [row0, row0 + rows) of a shard attached chunk by chunk (below; a whole shard is one chunk with row0 = 0) */
 int cldrd_query_dot64(const float* q, const float* mu, int d, double* out, int nq, void* stream);
-int cldrd_topk_rescore16(const float* q, const void* P16, const double* qmu, int d, const int* counts, const int* cand_rows,
-                         float* cand_scores, int nq, int cap, void* stream);
-int cldrd_flatip_search16(const float* q32, const void* q16, const float* thr, const float* eps, const void* P16, const double* qmu,
-                          long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
-                          int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I,
-                          int exhaustive, void* stream);
-int cldrd_gather_cast_rows16(const void* src16, void* dst, size_t n_out, size_t stride, int d, void* stream);
-int cldrd_index_center_cast_chunk(const float* P, const float* mu, size_t rows, size_t row0, int d, void* P16, void* sample_bf16,
-                                  size_t s_stride, size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream);
 int cldrd_row_sqnorm_max(const float* P, size_t rows, int d, unsigned int* out, void* stream);
-int cldrd_gather_cast_rows(const float* src, void* dst, size_t n_out, size_t stride, int d, void* stream);
+int cldrd_gather_cast_rows(const void* src, int src_f16, void* dst, size_t n_out, size_t stride, int d, void* stream);
 /* Attaching an index shard to a GPU (what faiss' index_cpu_to_gpu does behind retriever/retrieval_utils.py:155-162 - here: the scan shadow
  * and its error-bound statistics), three launches over the fp32 rows P[rows, d]:
  *   cldrd_index_col_mean    mu[d] = mean row (fp64 column sums, fixed order); workspace: cldrd_index_col_mean_workspace(rows, d) device bytes
  *   cldrd_index_center_cast P16[r] = fp16(P[r] - mu) (the scan's operand), sample[i] = bf16(P[i * s_stride] - mu) for i < s_rows (the threshold
  *                           sample; may be NULL), *cmax_bits = bit pattern of the fp32 value of max_r |P[r] - mu|^2 (fp64 row sums; zero it
- *                           first), *flag |= 1 when a centred value is outside the fp16 range
+ *                           first), *flag |= 1 when a centred value is outside the fp16 range.  P, P16 point at row `row0` of the shard and
+ *                           hold `rows` rows; the sample is the WHOLE shard's (a chunk writes the sample rows that fall inside it); *cmax_bits
+ *                           and *flag accumulate over the chunks
  *   cldrd_map_ids           out[i] = I[i] < 0 ? -1 : (ids ? ids[I[i]] : I[i] + id_offset): faiss IndexIDMap applied to a result list */
 size_t cldrd_index_col_mean_workspace(size_t rows, int d);
 int cldrd_index_col_mean(const float* P, size_t rows, int d, float* mu, void* workspace, size_t workspace_bytes, void* stream);
-int cldrd_index_center_cast(const float* P, const float* mu, size_t rows, int d, void* P16, void* sample_bf16, size_t s_stride,
+int cldrd_index_center_cast(const float* P, const float* mu, size_t rows, size_t row0, int d, void* P16, void* sample_bf16, size_t s_stride,
                             size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream);
 int cldrd_map_ids(const int* I, const long long* ids, long long id_offset, long long* out, size_t n, void* stream);
 
@@ -335,17 +326,15 @@ int cldrd_map_ids(const int* I, const long long* ids, long long id_offset, long 
  * cldrd_attention_* calls above given cu_rows (until round 6: on the padded [nseq * L, .] layout, rows moved by the two calls below).
  * cldrd_embed_ln_fwd / _bwd take pos_idx (device int32 [T], the position of every row inside its sequence; NULL: row % L).
  *   unpack_rows16: dst[m * L + j] = j < len[m] ? src[cu[m] + j] : 0  (16-bit rows of w elements);  gather_rows: dst[p] = src[idx[p]]
- *   (rows of row_bytes bytes: packing, CLS rows);  scatter_cls_grad_idx: g = 0, g[idx[r]] = bf16(dcls[r]);  add_rows_idx: dst[idx[m]] += src[m]. */
+ *   (rows of row_bytes bytes: packing, CLS rows);  the CLS rows of a packed batch go to cldrd_scatter_cls_grad / cldrd_add_rows as idx. */
 int cldrd_unpack_rows16(const void* src_packed, void* dst_padded, const int* cu, int nseq, int L, int w, void* stream);
 int cldrd_gather_rows(const void* src, const int* idx, void* dst, int n, int row_bytes, void* stream);
 int cldrd_gather_i64(const long long* src, const int* idx, long long* dst, int n, void* stream);      /* dst[p] = src[idx[p]]: token ids of the packed rows */
-int cldrd_scatter_cls_grad_idx(const float* dcls, void* g, int R, int d, const int* idx, int T, int g_f32, void* stream);
-int cldrd_add_rows_idx(void* dst, const void* src, int M, int d, const int* idx, int f32, void* stream);
 
 /* ---- per-step state in device memory: what lets a whole training step be captured into a HIP graph and replayed -------------------
  * Kernel arguments are frozen at capture; a dropout seed and the optimizer's lr / bias-corrected step size change every step.  With a
  * seed base installed, every launch of the calling thread passes its `seed` argument as an OFFSET and the kernels add the 64-bit word at
- * `base` (device memory) at run time; with the optimizer hyper-parameters installed, cldrd_adamw_step* read {lr, step size} from the
+ * `base` (device memory) at run time; with the optimizer hyper-parameters installed, cldrd_adamw_step reads {lr, step size} from the
  * device float[2].  cldrd_write_step_state writes both (seeds[0..1]: one word per tower) in stream order - the one launch the trainer
  * makes in front of each replay.  NULL uninstalls; nothing installed = the by-value arguments, as before (bit-identical results). */
 void cldrd_set_seed_base(const unsigned long long* base);

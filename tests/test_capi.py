@@ -114,6 +114,56 @@ def test_attention_entry_points_reject_inconsistent_layouts():
         assert msg.startswith(op + ":") and len(msg) > len(op) + 2, f"case {i}: {msg!r}"
 
 
+def test_merged_entry_points_reject_inconsistent_arguments():
+    """The row-mode rule of the search (P32 / P16 / qmu), the token-type rule of the embedding forward, the gradient-stream rule of the two
+    LayerNorm backwards (enum cldrd_stream_fmt), the fp16 shadow range of the optimizer step and the row rule of the CLS scatter
+    (include/cldrd_hip.h), without a GPU: as above, every call is rejected in front of any HIP call and none may pass the checks."""
+    from cldrd_amd import _lib
+    lib = _lib.load()
+    P = 64                                  # any non-null "pointer"
+    BF16, F32, F16 = 0, 1, 2                # enum cldrd_stream_fmt
+
+    def search(P16=P, P32=None, qmu=None):
+        return "flatip_search", lib.cldrd_flatip_search(P, P, P, P, P16, P32, qmu, 1000, 128, 4, 10, 128, P, P, P, 1024, P, P, 1024, P, P, P, P, P, 0, None)
+
+    def rescore(P16=P, P32=None, qmu=None):
+        return "topk_rescore", lib.cldrd_topk_rescore(P, P32, P16, qmu, 128, P, P, P, 4, 1024, None)
+
+    def embed_fwd(table=P, type_ids=P, type_vocab=2):
+        return "embed_ln_fwd", lib.cldrd_embed_ln_fwd(P, P, P, table, type_ids, type_vocab, P, P, P, P, P, 16, 8, 128, 300, 1e-12, 0.0, 7, None, 0, None, None, None)
+
+    def ln_bwd(x_f32=1, fmt=BF16, dx_dropped=P, branch=None):
+        return "layernorm_bwd", lib.cldrd_layernorm_bwd(P, P, P, P, P, P, dx_dropped, None, None, None, P, 16, 128, 0.0, 7, 0, x_f32, fmt, 0, branch, None)
+
+    def embed_bwd(fmt=BF16, branch=None):
+        return "embed_ln_bwd", lib.cldrd_embed_ln_bwd(P, P, P, P, None, P, P, P, P, P, None, None, None, P, 16, 8, 128, 300, 0.0, 7, 0, None, fmt, 0, branch, None)
+
+    def adamw(lo, hi, n=1024):
+        return "adamw_step", lib.cldrd_adamw_step(P, P, P, P, P, None, n, 1e-3, 0.9, 0.999, 1e-8, 0.01, 1, None, P, lo, hi, None)
+
+    def scatter(stride, idx=None):
+        return "scatter_cls_grad", lib.cldrd_scatter_cls_grad(P, P, 4, 128, stride, idx, 32, BF16, None)
+
+    cases = [
+        lambda: search(P32=P, qmu=P), lambda: rescore(P32=P, qmu=P),                    # fp32 rows take no qmu
+        lambda: search(), lambda: rescore(),                                            # neither P32 nor qmu
+        lambda: search(P16=None, qmu=P), lambda: rescore(P16=None, qmu=P),              # fp16-row mode without the fp16 rows
+        lambda: search(P16=None), lambda: rescore(P16=None),                            # no rows at all
+        lambda: embed_fwd(table=None), lambda: embed_fwd(type_vocab=0), lambda: embed_fwd(type_vocab=-1),
+        lambda: ln_bwd(x_f32=0, fmt=F32), lambda: ln_bwd(fmt=F32, dx_dropped=None), lambda: ln_bwd(x_f32=0, fmt=F16),
+        lambda: ln_bwd(fmt=BF16, branch=P), lambda: ln_bwd(fmt=3), lambda: ln_bwd(fmt=-1),
+        lambda: embed_bwd(fmt=BF16, branch=P), lambda: embed_bwd(fmt=3),
+        lambda: adamw(2, 64), lambda: adamw(0, 62), lambda: adamw(0, 1028), lambda: adamw(1024, 2048),
+        lambda: scatter(0), lambda: scatter(-8),
+    ]
+    for i, case in enumerate(cases):
+        lib.cldrd_set_tuning(None, 0)       # leaves "set_tuning: null key" behind: the message read below is this case's own
+        op, rc = case()
+        msg = lib.cldrd_last_error().decode()
+        assert rc != 0, f"case {i} ({op}) was not rejected"
+        assert msg.startswith(op + ":") and len(msg) > len(op) + 2, f"case {i}: {msg!r}"
+
+
 def test_no_cpu_fallback():
     """Ops refuse CPU tensors instead of silently computing on the host."""
     from cldrd_amd import hip_ops as ops

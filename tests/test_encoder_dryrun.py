@@ -49,6 +49,9 @@ class _Calls(list):
 # position of cu_rows (and, for the full-attention calls, of seq_list) in the C signatures of include/cldrd_hip.h
 _CU_ARG = {"cldrd_attention_fwd": 2, "cldrd_attention_bwd": 2, "cldrd_attention_cls_fwd": 3, "cldrd_attention_cls_bwd": 2}
 _LIST_ARG = 3
+# position of the arguments that select a branch of a merged entry point: type_ids of the embedding forward, idx of the CLS-row calls
+_TYPE_IDS_ARG = 4
+_IDX_ARG = {"cldrd_add_rows": 5, "cldrd_scatter_cls_grad": 5}
 
 
 def _cu_set(recorded, name):
@@ -106,6 +109,21 @@ def test_forward_backward_walks_every_mode(stubbed, monkeypatch, arch, layers, p
     for name in ("cldrd_attention_fwd", "cldrd_attention_bwd"):              # (a one-layer tower has only the CLS-only last layer)
         assert any(_cu_set(stubbed.args, name)) == (packed and layers > 1), name
     assert "cldrd_unpack_rows16" not in kinds                      # round 6: attention reads the packed rows through cu, no row moves
+    # the CLS rows are said by idx in a packed pass, by the stride L in a padded one; the full last layer (test hook; never packed) scatters dcls
+    if not packed:
+        enc.hp_forward, enc.cls_only_last = False, False
+        cls, tape = enc.encode(ids, mask, train=True, save=True)
+        enc.backward_from_cls(tape, torch.zeros(M, 128), accumulate=False)
+        enc.cls_only_last = True
+        assert "cldrd_scatter_cls_grad" in stubbed
+    assert "cldrd_add_rows" in stubbed
+    for name, pos in _IDX_ARG.items():
+        assert all((a[pos] is not None) == packed for n, a in stubbed.args if n == name), name
+    # token types: none of the passes above has any; a pass that is given some hands them to the same entry point - BERT only, DistilBERT has no table
+    assert not any(a[_TYPE_IDS_ARG] is not None for n, a in stubbed.args if n == "cldrd_embed_ln_fwd")
+    n0, enc.hp_forward = len(stubbed.args), False
+    enc.encode(ids, mask, train=False, save=False, lengths=lengths, token_type_ids=(torch.arange(L)[None, :] >= 5).long().expand(M, L))
+    assert [a[_TYPE_IDS_ARG] is not None for n, a in stubbed.args[n0:] if n == "cldrd_embed_ln_fwd"] == [arch == "bert"]
 
 
 @pytest.mark.parametrize("lens,want", [([200, 3, 10, 130, 5, 128], 2), ([100, 3, 10, 128, 5, 64], 1), ([200, 150, 129, 130, 131, 199], 0)])
@@ -150,7 +168,7 @@ def test_trainer_step_walks_with_stubbed_kernels(stubbed, monkeypatch):
     assert moved["nway_passages"]["lengths"].tolist() == batch["nway_passages"]["attention_mask"].sum(-1).reshape(-1).tolist()
     n0 = len(stubbed)
     tr.train_step(moved)
-    assert tr.global_step == 1 and "cldrd_adamw_step_h16" in stubbed[n0:] and "cldrd_loss_fwd_bwd" in stubbed[n0:]
+    assert tr.global_step == 1 and "cldrd_adamw_step" in stubbed[n0:] and "cldrd_loss_fwd_bwd" in stubbed[n0:]
 
 
 def test_window_scheduled_step_walks_and_interleaves_the_two_towers(stubbed, monkeypatch):

@@ -484,29 +484,29 @@ def test_layernorm_bwd_fp16_gradient_stream(T, d, p, branch):
 
 
 def test_fp16_stream_row_helpers():
-    """scatter_cls_grad(_idx) into an fp16 stream tensor; fp16 dst += fp32 src for the CLS rows (one rounding)."""
+    """scatter_cls_grad (stride and idx forms) into an fp16 stream tensor; fp16 dst += fp32 src for the CLS rows (one rounding)."""
     R, d, L = 6, 128, 5
     dcls = rnd(61, (R, d)).to(DEV)
     g = torch.full((R * L, d), float("nan"), dtype=torch.float16, device=DEV)
-    ops.scatter_cls_grad(dcls, g, R, L, R * L)
+    ops.scatter_cls_grad(dcls, g, R, R * L, stride=L)
     want = torch.zeros(R * L, d, dtype=torch.float16, device=DEV)
     want[::L] = dcls.half()
     assert torch.equal(g, want)
     idx = torch.tensor([0, 3, 4, 9, 17, 29], dtype=torch.int32, device=DEV)
     g2 = torch.full((R * L, d), float("nan"), dtype=torch.float16, device=DEV)
-    ops.scatter_cls_grad_idx(dcls, g2, idx, R * L)
+    ops.scatter_cls_grad(dcls, g2, R, R * L, idx=idx)
     want2 = torch.zeros(R * L, d, dtype=torch.float16, device=DEV)
     want2[idx.long()] = dcls.half()
     assert torch.equal(g2, want2)
     base = rnd(62, (R * L, d)).half().to(DEV)
     src = rnd(63, (R, d)).to(DEV)
     a = base.clone()
-    ops.add_rows_strided(a, src, R, L)
+    ops.add_rows(a, src, R, stride=L)
     w = base.clone()
     w[::L] = (base[::L].float() + src).half()
     assert torch.equal(a, w)
     b = base.clone()
-    ops.add_rows_idx(b, src, idx, R)
+    ops.add_rows(b, src, R, idx=idx)
     w2 = base.clone()
     w2[idx.long()] = (base[idx.long()].float() + src).half()
     assert torch.equal(b, w2)

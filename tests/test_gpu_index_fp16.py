@@ -65,7 +65,7 @@ def attach16(P, ids=None, id_offset=0, **hooks):
 # ---- 1. the re-score kernel alone -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("d", [64, 128, 768, 1024, 132])
 def test_rescore16_is_the_rounded_fp64_sum(d):
-    """cldrd_topk_rescore16 + cldrd_query_dot64 against fp32(q.mu + q.R16[row]) in numpy fp64 on ragged candidate lists (counts 0 and cap among
+    """cldrd_topk_rescore on fp16 rows + cldrd_query_dot64 against fp32(q.mu + q.R16[row]) in numpy fp64 on ragged candidate lists (counts 0 and cap among
     them), heavy-tailed row norms.  Equal BIT FOR BIT, except where the fp64 sum lies within 1e-9 relative of an fp32 rounding boundary (the
     device's summation order differs from numpy's): at most 1 in 10 000 such entries, each one ulp off.  d = 132 takes the 8-byte-load form."""
     rows, nq, cap = 6000, 9, 1500
@@ -81,7 +81,7 @@ def test_rescore16_is_the_rounded_fp64_sum(d):
     cand[1, 0], cand[1, 1] = rows - 1, 0
     scores = torch.full((nq, cap), 12345.0, device=DEV)
     qmu = ops.query_dot64(Q, mu)
-    ops.topk_rescore16(Q, R16, qmu, counts, cand, scores)
+    ops.topk_rescore(Q, R16, counts, cand, scores, qmu=qmu)
     torch.cuda.synchronize()
     q64, mu64, r64 = Q.cpu().numpy().astype(np.float64), mu.cpu().numpy().astype(np.float64), R16.cpu().numpy().astype(np.float64)
     qmu_ref = (q64 * mu64).sum(axis=1)

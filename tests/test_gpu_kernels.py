@@ -894,27 +894,47 @@ def test_layernorm_bwd_fp32_gradient_stream(T, d, p):
 
 
 def test_stream_row_ops_on_fp32_rows():
-    """scatter_cls_grad(_idx) / add_rows_strided / add_rows_idx with fp32 rows (fp32 gradient stream): exact."""
+    """scatter_cls_grad / add_rows (stride and idx forms) with fp32 rows (fp32 gradient stream): exact."""
     R, d, L = 5, 128, 16
     dcls = rnd(128, (R, d)).to(DEV)
     g = torch.full((ops.pad_rows(R * L), d), 3.0, dtype=torch.float32, device=DEV)
-    ops.scatter_cls_grad(dcls, g, R, L, R * L)
+    ops.scatter_cls_grad(dcls, g, R, R * L, stride=L)
     ref = torch.zeros(R * L, d, device=DEV)
     ref[::L] = dcls
     assert torch.equal(g[: R * L], ref)
     idx = torch.tensor([0, 7, 19, 30, 41], dtype=torch.int32, device=DEV)
     g2 = torch.full((64, d), 3.0, dtype=torch.float32, device=DEV)
-    ops.scatter_cls_grad_idx(dcls, g2, idx, 50)
+    ops.scatter_cls_grad(dcls, g2, R, 50, idx=idx)
     ref2 = torch.zeros(50, d, device=DEV)
     ref2[idx.long()] = dcls
     assert torch.equal(g2[:50], ref2)
     add = rnd(129, (R, d)).to(DEV)
-    ops.add_rows_strided(g, add, R, L)
+    ops.add_rows(g, add, R, stride=L)
     ref[::L] += add
     assert torch.equal(g[: R * L], ref)
-    ops.add_rows_idx(g2, add, idx, R)
+    ops.add_rows(g2, add, R, idx=idx)
     ref2[idx.long()] += add
     assert torch.equal(g2[:50], ref2)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32, torch.float16])
+def test_row_ops_idx_form_equals_stride_form(dt):
+    """scatter_cls_grad / add_rows: rows idx[r] = r * stride give bit for bit what the stride form gives, in every gradient-stream format."""
+    M, d, stride = 4, 128, 8
+    idx = torch.arange(M, dtype=torch.int32, device=DEV) * stride
+    dcls = rnd(140, (M, d)).to(DEV)
+    g1 = torch.full((M * stride, d), 3.0, dtype=dt, device=DEV)
+    g2 = g1.clone()
+    ops.scatter_cls_grad(dcls, g1, M, M * stride, stride=stride)
+    ops.scatter_cls_grad(dcls, g2, M, M * stride, idx=idx)
+    assert torch.equal(g1, g2) and g1[::stride].float().abs().sum().item() > 0 and not g1[1].any()
+    base = rnd(141, (M * stride, d)).to(dt).to(DEV)
+    src = rnd(142, (M, d)).to(DEV)
+    src = bf(src) if dt == torch.bfloat16 else src          # bf16 += bf16; the fp32 and fp16 streams take an fp32 src
+    a, b = base.clone(), base.clone()
+    ops.add_rows(a, src, M, stride=stride)
+    ops.add_rows(b, src, M, idx=idx)
+    assert torch.equal(a, b) and not torch.equal(a[::stride], base[::stride]) and torch.equal(a[1:stride], base[1:stride])
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 768, 3072), (2048, 768, 2304), (240, 768, 768), (256, 768, 3072)])
@@ -1013,7 +1033,7 @@ def test_colsum_and_scatter():
     R, d, L = 5, 128, 16
     dcls = rnd(28, (R, d))
     g = torch.full((ops.pad_rows(R * L), d), 3.0, dtype=torch.bfloat16, device=DEV)
-    ops.scatter_cls_grad(dcls.to(DEV), g, R, L, R * L)
+    ops.scatter_cls_grad(dcls.to(DEV), g, R, R * L, stride=L)
     ref = torch.zeros(R * L, d)
     ref[::L] = dcls
     close(g[: R * L], ref, 1 / 256, 0, "scatter_cls")

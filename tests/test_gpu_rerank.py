@@ -60,10 +60,7 @@ def test_embed_ln_fwd_typed(d):
     def run(types):
         out, o32 = torch.empty(T, d, dtype=torch.bfloat16, device=DEV), torch.empty(T, d, device=DEV)
         mean, rstd = torch.empty(T, device=DEV), torch.empty(T, device=DEV)
-        if types is None:
-            ops.embed_ln_fwd(ids, word, pos, typ[0], gam, bet, out, mean, rstd, T, L, 1e-12, out32=o32, pos_idx=posi)
-        else:
-            ops.embed_ln_fwd_typed(ids, word, pos, typ, types, gam, bet, out, mean, rstd, T, L, 1e-12, out32=o32, pos_idx=posi)
+        ops.embed_ln_fwd(ids, word, pos, typ, gam, bet, out, mean, rstd, T, L, 1e-12, out32=o32, pos_idx=posi, type_ids=types)
         return out, o32, mean, rstd
     zero = run(torch.zeros(T, dtype=torch.int32, device=DEV))
     base = run(None)
@@ -74,6 +71,27 @@ def test_embed_ln_fwd_typed(d):
     x = word.cpu()[ids.cpu()] + pos.cpu()[posi.cpu().long()] + typ.cpu()[tt.long()]
     ref = torch.nn.functional.layer_norm(x.double(), (d,), gam.cpu().double(), bet.cpu().double(), 1e-12)
     assert (o32.cpu().double() - ref).abs().max().item() < 1e-4
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_embed_ln_fwd_all_zero_type_ids_equal_no_type_ids(p):
+    """include/cldrd_hip.h: with all-zero type_ids the typed form computes what type_ids = NULL does - bit for bit, with and without dropout
+    (same seed); two sequences of 8 rows, a two-row token-type table."""
+    g = torch.Generator().manual_seed(5)
+    V, T, L, d = 50, 16, 8, 128
+    word, pos, typ = torch.randn(V, d, generator=g).to(DEV), torch.randn(L, d, generator=g).to(DEV), torch.randn(2, d, generator=g).to(DEV)
+    gam, bet = (1 + 0.1 * torch.randn(d, generator=g)).to(DEV), (0.1 * torch.randn(d, generator=g)).to(DEV)
+    ids = torch.randint(0, V, (T,), generator=g).to(DEV)
+
+    def run(types):
+        out, o32 = torch.empty(T, d, dtype=torch.bfloat16, device=DEV), torch.empty(T, d, device=DEV)
+        mean, rstd = torch.empty(T, device=DEV), torch.empty(T, device=DEV)
+        ops.embed_ln_fwd(ids, word, pos, typ, gam, bet, out, mean, rstd, T, L, 1e-12, dropout_p=p, seed=11, out32=o32, type_ids=types)
+        return out, o32, mean, rstd
+    for a, b in zip(run(torch.zeros(T, dtype=torch.int32, device=DEV)), run(None)):
+        assert torch.equal(a, b)
+    ones = run(torch.ones(T, dtype=torch.int32, device=DEV))
+    assert not torch.equal(ones[2], run(None)[2])           # the type ids are read: row 1 of the table moves the means
 
 
 # ---------------------------------------------------------------- CrossEncoder against HF

@@ -236,6 +236,29 @@ def test_attach_statistics_kernels_equal_the_numpy_restatement(rows, d, stride):
     assert np.array_equal(ops.map_ids(I, None, 1000).cpu().numpy(), np.where(In >= 0, In + 1000, -1))
 
 
+def test_index_center_cast_in_chunks_equals_one_call():
+    """cldrd_index_center_cast on rows [row0, row0 + rows): 104 rows as chunks of 64 + 40 leave the fp16 rows, the whole shard's sample (stride 3),
+    the largest centred norm and the range flag (raised by a row of the second chunk) bit for bit as one call with row0 = 0 does."""
+    rows, d, stride = 104, 128, 3
+    P = (np.random.default_rng(104).standard_normal((rows, d)) * 3.0 + 2.5).astype(np.float32)
+    P[70, 5] = 1e6                                          # outside the fp16 range
+    Pd = torch.from_numpy(P).to(DEV)
+    mu = ops.index_col_mean(Pd)
+    s_rows = (rows + stride - 1) // stride
+
+    def run(bounds):
+        P16 = torch.zeros(rows, d, dtype=torch.float16, device=DEV)
+        sample = torch.zeros((s_rows + 7) // 8 * 8, d, dtype=torch.bfloat16, device=DEV)
+        flag, cmax = torch.zeros(1, dtype=torch.int32, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+        for lo, hi in bounds:
+            ops.index_center_cast(Pd[lo:hi], mu, P16[lo:hi], sample, stride, s_rows, flag, row0=lo, cmax=cmax)
+        return P16.view(torch.int16), sample.view(torch.int16), cmax, flag
+    whole, chunked = run([(0, rows)]), run([(0, 64), (64, rows)])
+    for a, b in zip(whole, chunked):
+        assert torch.equal(a, b)
+    assert int(whole[3].item()) == 1 and whole[1][:s_rows].any(dim=1).all() and int(whole[2].item()) != 0
+
+
 @pytest.mark.parametrize("devices,with_ids", [([0, 0], True), ([0, 0, 0], False)])
 def test_convert_index_to_gpu_device_list_shards_in_one_process(devices, with_ids):
     """The reference's LIST form, ``convert_index_to_gpu(index, [d0, d1, ...])`` (retriever/retrieval_utils.py:164-182: sharded clone, dead
