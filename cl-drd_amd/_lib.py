@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # change of ABI_VERSION uses two checkouts).  The library itself reads no environment variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
 
-ABI_VERSION = 102          # cldrd_version() of the build SIGNATURES describes
+ABI_VERSION = 103          # cldrd_version() of the build SIGNATURES describes
 
 _lib = None
 
@@ -22,7 +22,7 @@ SIGNATURES = {
     "cldrd_device_ok": (ci, []),
     "cldrd_set_tuning": (ci, [C.c_char_p, ci]),
     "cldrd_gemm_nt_splitk_workspace": (csz, [ci, ci, ci]),
-    "cldrd_gemm_nt16": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, cf, cf, cull, ci, ci, ci, vp, vp, vp, vp, vp, vp, csz, vp]),
+    "cldrd_gemm_nt16": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, cf, cf, cull, ci, ci, ci, vp, vp, vp, vp, vp, csz, vp]),
     "cldrd_wgrad_splits": (ci, [ci, ci, ci]),
     "cldrd_wgrad16": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, csz, ci, vp]),
     "cldrd_wgrad_group_workspace": (csz, [vp, vp, vp, ci]),
@@ -35,9 +35,9 @@ SIGNATURES = {
     "cldrd_attention_bits_words": (C.c_longlong, [ci, ci, ci, cf]),
     "cldrd_add_rows": (ci, [vp, vp, ci, ci, ci, vp, ci, vp]),
     "cldrd_ln_partial_blocks": (ci, [ci]),
-    "cldrd_embed_ln_fwd": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp, vp]),
+    "cldrd_embed_ln_fwd": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp]),
     "cldrd_embed_ln_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cull, ci, vp, ci, ci, vp, vp]),
-    "cldrd_layernorm_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, ci, vp, ci, vp, vp]),
+    "cldrd_layernorm_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, ci, vp, ci, vp]),
     "cldrd_layernorm_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cull, ci, ci, ci, ci, vp, vp]),
     "cldrd_ln_reduce_group": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_colsum_bf16": (ci, [vp, vp, vp, ci, ci, ci, ci, vp]),

@@ -110,7 +110,12 @@ __device__ __forceinline__ uint4 widen_pair(const uint2& g0, const uint2& g1) {
 // a[48:63] - stale scores for keys 58, 59, 62, 63 of every sequence of 59 .. 64 tokens (tools/wgrad_attn_fuzz.py found it; the keys are masked
 // in shorter sequences, which is why nothing else noticed).  mfma_drain() ends every block iteration of such a loop, in front of the next
 // iteration's exit test: 24 wait states (more than the longest XDL result latency) on BOTH ways out of the branch, pinned against the schedulers;
-// they pass under the last MFMA of the block, which occupies the pipe for longer than that.
+// they pass under the last MFMA of the block, which occupies the pipe for longer than that.  Drained: the key-block loops of the forward kernels,
+// both block loops of attn_bwd_kernel when VARLEN, and both sweeps of attn_bwd2_kernel (its count nb is a run-time value in either layout).  In the
+// key-side sweep of attn_bwd2_kernel (dK, dV: four accumulators, the kernel's register peak) the drain stands BEHIND the loop instead of at the end of
+// its body: the loop's only exit falls through to it, so the wait states lie between the last MFMA and the first read of dK / dV all the same, and on the
+// back edge nothing reads dK / dV before the next iteration's last MFMAs, which take them as their own C operand a whole iteration later.  Inside the body
+// it put the L = 128 dropout instantiations at 256 VGPRs with 28 bytes of scratch (profiles/one_schedule_timing.txt).
 __device__ __forceinline__ void mfma_drain() {
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
@@ -1228,6 +1233,7 @@ __global__ __launch_bounds__(512) void attn_bwd2_kernel(const bf16_t* __restrict
                     // leaves in 8-byte stores (the other order gave 32 two-byte stores per lane)
                     dQ[dt] = mfma32<F16>(tr_frag(sK, kb * 32 + 16 * s2 + 4 * h, dt * 32, lane), sa, dQ[dt]);
             }
+            mfma_drain();
         }
         {                 // dQ[dt][t] = dQ[q][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
             bf16_t* oq = dqkv + ((size_t)sr.row0 + q) * ld + hd * 64;
@@ -1307,6 +1313,7 @@ __global__ __launch_bounds__(512) void attn_bwd2_kernel(const bf16_t* __restrict
                 }
             }
         }
+        mfma_drain();     // behind the loop (see mfma_drain): its only exit falls through to here, in front of the first read of dK / dV
         // dV[dt][t] = dV[key][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
         {
             bf16_t* ok = dqkv + ((size_t)sr.row0 + key) * ld + dm + hd * 64;

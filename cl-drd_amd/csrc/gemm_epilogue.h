@@ -28,15 +28,9 @@ struct GemmNtArgs {
     int in_f16 = 0;               // the operands (and a 16-bit C) are fp16, not bf16: top-k scan, high-precision forward flavours
     int c_bf16 = 0;               // with in_f16: a 16-bit C is bf16 all the same (fp16 operands, bf16 result: the QKV projection, whose
                                   // consumers - attention forward and backward - are bf16 kernels)
-    bf16_t* c_copy = nullptr;     // with in_f16 and a 16-bit C: a bf16 copy of C [M, ldc] (the backward's MFMAs read bf16: the tape of an
-                                  // fp16-operand forward GEMM), or null
     int ksplit = 1;               // small-M kernel: K range split over ksplit workgroups per tile, fp32 partials in `slabs` ([ksplit][M][N]),
     float* slabs = nullptr;       //   summed in a fixed order and finished (epilogue) by splitk_finish_kernel
     int gn = 0;                   // ring kernel: N tiles are walked in groups of gn inside an XCD's range (0: row-major)
-    int stagger = 1;              // ring kernel: waves 4..7 issue their LDS-DMA one k-step after waves 0..3 (0: A/B runs)
-    int asym = 1;                 // ring kernel, two whole slots: a third A slot, A requested two K tiles ahead (0: the round-2 schedule)
-    int early1 = 1;               // ring kernel, two LDS slots: K tile 1 is requested together with K tile 0 at tile start (0: after tile 0 landed)
-    int phase_units = 0;          // ring kernel: half of the first round's workgroups start this many s_memtime units late (0: off)
     int tape_f16 = 0;             // with in_f16 (the all-fp16 training mode): `preact` is written and `gelu_pre` is read as fp16, not bf16
 };
 
@@ -199,7 +193,6 @@ __device__ __forceinline__ void gemm_nt_apply8(const GemmNtArgs& p, const EpiFla
         if (h16) {
             const uint4 o = pack8h(v);
             if (ok) *(uint4*)((bf16_t*)p.C + crow) = o;
-            if (p.c_copy) { const uint4 o2 = pack8(v); if (ok) st16_stream(p.c_copy + crow, o2); }       // the tape copy: read ~10 ms later by the weight-gradient launch
         } else {
             const uint4 o = pack8(v);
             if (ok) *(uint4*)((bf16_t*)p.C + crow) = o;

@@ -349,11 +349,9 @@ extern "C" int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int
                                const float* bias, const void* residual, int ldr, void* preact, const void* gelu_pre,
                                int act, float alpha, float dropout_p, unsigned long long seed, int out_f32, int res_f32,
                                int io_f16, const float* ln_mean, const float* ln_rstd, const float* ln_gamma,
-                               const float* ln_beta, void* c_copy_bf16, float* workspace, size_t workspace_bytes, void* stream) {
+                               const float* ln_beta, float* workspace, size_t workspace_bytes, void* stream) {
     CLDRD_CHECK(io_f16 == 0 || io_f16 == 1 || io_f16 == 3 || io_f16 == 5,
                 "gemm_nt: io_f16 is 0 (bf16), 1 (fp16 operands and 16-bit C), 3 (fp16 operands, bf16 C) or 5 (1 + fp16 preact / gelu_pre: the all-fp16 training mode)");
-    CLDRD_CHECK(c_copy_bf16 == nullptr || (io_f16 == 1 && !out_f32 && (uintptr_t)c_copy_bf16 % 16 == 0),
-                "gemm_nt: the bf16 copy of C goes with fp16 operands and an fp16 C");
     {
         const int nln = (ln_mean != nullptr) + (ln_rstd != nullptr) + (ln_gamma != nullptr) + (ln_beta != nullptr);
         CLDRD_CHECK(nln == 0 || nln == 4, "gemm_nt: ln_mean / ln_rstd / ln_gamma / ln_beta go together");
@@ -382,7 +380,6 @@ extern "C" int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int
     a.in_f16 = io_f16 ? 1 : 0;
     a.c_bf16 = (io_f16 & 2) ? 1 : 0;
     a.tape_f16 = (io_f16 & 4) ? 1 : 0;
-    a.c_copy = (bf16_t*)c_copy_bf16;
     if (const int k64 = (io_f16 && gelu_pre && !(io_f16 & 4)) ? 0 : nt64_splits(M, N, K);
         k64 == 1 || (k64 > 1 && workspace != nullptr && workspace_bytes >= (size_t)k64 * M * N * sizeof(float) && (uintptr_t)workspace % 16 == 0)) {
         a.ksplit = k64;

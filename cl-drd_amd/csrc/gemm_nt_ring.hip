@@ -43,7 +43,6 @@ int cldrd_gemm_nt_ring16_launch(const GemmNtArgs& a, int bn, hipStream_t st);   
 // Returns -1 if this variant does not apply (caller falls back to the 128x128 kernel), else the launch status.
 int cldrd_gemm_nt_ring_dispatch(const GemmNtArgs& a_in, hipStream_t st) {
     GemmNtArgs a = a_in;
-    a.stagger = a.early1 = a.asym = 1;      // settled A/B pairs (profiles/r02, r03_microbench.txt)
     if (a.K % BK != 0) return -1;
     if ((double)a.M * a.lda * 2.0 >= 4.0e9 || (double)a.N * a.ldb * 2.0 >= 4.0e9) return -1;   // 32-bit DMA offsets
     if (a.M < 1024) return -1;
@@ -64,7 +63,6 @@ int cldrd_gemm_nt_ring_dispatch(const GemmNtArgs& a_in, hipStream_t st) {
     // group pass would re-read the A panels - PMC: 436 MB instead of 293 MB for N = 768, K = 2304 / 3072)
     a.gn = a.K <= 1024 ? (int)(2.0e6 / ((double)bn * a.K * 2.0) + 0.5) : 0;
     if (a.gn < 0) a.gn = 0;
-    a.phase_units = 0;      // no phase shift between the workgroups of the first round
     // (A persistent tile walk with a register epilogue - gemm_nt_pers.hip of rounds 2-3 - measured equal to this kernel within 1 % on
     // the encoder shapes and in the training step, profiles/r02_microbench.txt, and was removed in round 4.)
     if (a.in_f16) return cldrd_gemm_nt_ring16_launch(a, bn, st);       // fp16 operands: the forward FFN flavours, or -1

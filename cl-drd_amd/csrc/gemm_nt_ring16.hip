@@ -5,9 +5,8 @@
 // Why these two GEMMs: of all 16-bit rounding points of a layer the operands of the FFN GEMMs carry the logit drift (CPU emulation on the
 // cfg1 golden, DESIGN.md section 2: every operand bf16 0.234, FFN operands fp16 and the rest bf16 0.051, everything fp16 0.024, against
 // 0.036 for the reference's own fp16 autocast).  fp16 has the same MFMA rate as bf16 and 8x finer rounding, and forward activations of
-// a BERT encoder are far inside its range (the reference itself trains under fp16 autocast, nway_listwise_1.py:334).  The backward's
-// MFMAs multiply these activations with bf16 gradients, so the training forward leaves a bf16 copy of h (GemmNtArgs::c_copy) and of the
-// LayerNorm output next to the fp16 tensors.
+// a BERT encoder are far inside its range (the reference itself trains under fp16 autocast, nway_listwise_1.py:334).  The all-fp16
+// training mode reads the same fp16 tensors as its tape (GemmNtArgs::tape_f16): no second copy is written.
 #include "gemm_nt_ring_kernel.h"
 
 namespace {

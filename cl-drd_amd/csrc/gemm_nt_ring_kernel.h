@@ -50,19 +50,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     // Round 3: separate rings for the two operands.  LDS = [NA A slots | NB B slots].  Where only two whole K tiles fit (BN = 192 / 256:
     // every encoder shape) the A operand still gets a THIRD slot (3 x 32 KiB + 2 x 24 / 32 KiB = 144 / 160 KiB): A is the activation matrix
     // that streams in from HBM / the Infinity Cache (1.5-2 us per request under load, more than the 1.15 us of MFMA work per K tile), B the
-    // weight panel that lives in L2.  A is then requested TWO K tiles ahead (p.asym; 0 = two slots each, the round-2 schedule).
+    // weight panel that lives in L2.  A is then requested TWO K tiles ahead.
     constexpr int NB_ = NSLOT;
     constexpr int NA_MAX = (NSLOT == 2 && 3 * A_BYTES + 2 * B_BYTES <= 160 * 1024) ? 3 : NSLOT;
-    const int na_ = (NA_MAX > NSLOT && p.asym != 0) ? NA_MAX : NSLOT;        // A slots in use (uniform)
+    constexpr int na_ = NA_MAX;              // A slots in use
     constexpr int BRING = NA_MAX * A_BYTES;  // byte offset of the B ring
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (p.phase_units > 0 && blockIdx.x < 256 && ((blockIdx.x >> 3) & 1)) {
-        // first round of tiles only (later rounds inherit their CU's phase): every second workgroup of an XCD starts `phase_units` of the
-        // s_memtime counter late (1 unit = 0.064 us), so that half of the chip is in its K loop while the other half is in its epilogue
-        const unsigned long long t0 = __builtin_readcyclecounter();
-        while ((long long)(__builtin_readcyclecounter() - t0) < (long long)p.phase_units) __builtin_amdgcn_s_sleep(8);
-    }
     const int ntn = (p.N + BN - 1) / BN;
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     // Tile order inside an XCD's contiguous range.  Row-major (all N tiles of an M panel, then the next panel) streams the
@@ -150,7 +144,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     // they leave the MFMA pipe idle for that long.  Waves 4..7 therefore postpone their pieces to the following k-step
     // (`late`), so one wave of each SIMD feeds the MFMA pipe while the other one issues: +2..9 % on the encoder shapes
     // (a whole k-step later is too late for two LDS slots: -10 %).
-    const bool late_wave = wid >= 4 && p.stagger != 0;
+    const bool late_wave = wid >= 4;
     auto kstep = [&](bf16x8 (&bc)[NT], bf16x8 (&bn)[NT], const char* na, const char* nb, bool sync, int slot, int slotB, int kt) {
         mfma_row(0, bc);
         mfma_row(1, bc);
@@ -192,12 +186,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     };
 
     // Prologue: every slot is free at tile start, so K tiles 0 and 1 (and A of K tile 2 with the third A slot) are requested back to back and
-    // only tile 0 is waited for.  (Until round 3 the two-slot instances requested tile 1 only after tile 0 had landed: its whole HBM /
-    // Infinity-Cache latency sat in front of the first slot recycle of every tile; p.early1 = 0 restores that for A/B runs.)
+    // only tile 0 is waited for: the HBM / Infinity-Cache latency of tile 1 does not sit in front of the first slot recycle of every tile.
     // Request order = what the waits count on: A0 B0 | B1 A1 | A2.
     stageA(0, 0);
     stageB(0, 0);
-    const bool early1 = nk_ > 1 && (NSLOT == 3 || p.early1 != 0 || na_ == 3);
+    const bool early1 = nk_ > 1;
     const bool early2 = early1 && na_ == 3 && NSLOT == 2 && nk_ > 2;
     if (early1) {
         stageB(1, 1);
@@ -213,7 +206,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (NSLOT == 3) { if (nk_ > 2) { stageB(2, 2); stageA(2, 2); } } else { if (nk_ > 1 && !early1) { stageB(1, 1); stageA(1, 1); } }
+    if (NSLOT == 3 && nk_ > 2) { stageB(2, 2); stageA(2, 2); }
 #pragma unroll
     for (int t = 0; t < NT; ++t) b0[t] = *(const bf16x8*)(smem + b_off[0] + t * 16 * 128);
 #pragma unroll

@@ -60,7 +60,7 @@ struct TnProblem {
     long long slab_off;                // chunks > 1: float offset of this problem's slabs in the workspace
 };
 struct TnGroupArgs {
-    int n, items_long, accumulate, stagger;      // items_long: work items of region 0 (the grid holds items_long + the short items)
+    int n, items_long, accumulate;      // items_long: work items of region 0 (the grid holds items_long + the short items)
     float* slabs;
     const float* inv_scale;            // device scalar or null: every output (dW, dbias) is multiplied by it - the operands of the all-fp16
                                        // training mode carry the loss scale, parameter gradients do not (capi.hip: cldrd_set_loss_scale)
@@ -157,7 +157,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
     const int slab = (rg ? P.n_long : 0) + chunk;
     const int wm = wid / WGN, wn = wid % WGN;
     const bool do_bias = P.dbias != nullptr && c2 == 0 && wn == 0;
-    const int stagger = ga.stagger;
     const int mtail = M & (BK - 1);                    // valid rows of the last K tile (0: it is complete)
 
     // ---- LDS-DMA.  A piece = RA token rows x (T1*2) B; a B piece = 1 KiB of the row-major B image; wave w owns pieces APW*w.. / BPW*w..
@@ -230,7 +229,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_kernel(TnGroupArgs ga) {
 
     // waves w and w + NW/2 share a SIMD: the second half issues its LDS-DMA one k-step later, so the two do not stall the
     // MFMA pipe at the same time (measured on the NT kernel: +2..9 %)
-    const bool late_wave = NW == 8 && wid >= 4 && stagger;
+    const bool late_wave = NW == 8 && wid >= 4;
     using KS0 = std::integral_constant<int, 0>;
     using KS1 = std::integral_constant<int, 1>;
 
@@ -786,7 +785,7 @@ extern "C" int cldrd_wgrad_group(const void* const* A, const void* const* B, flo
         const int m = n - lo < MAXP ? n - lo : MAXP;
         const WgradPlan pl = wgrad_plan_group(M + lo, N1 + lo, N2 + lo, m, t);
         TnGroupArgs g;
-        g.n = m; g.items_long = pl.items_long; g.accumulate = accumulate & 1; g.stagger = 1; g.slabs = workspace;
+        g.n = m; g.items_long = pl.items_long; g.accumulate = accumulate & 1; g.slabs = workspace;
         g.inv_scale = g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr;
         g.sq_out = nullptr;
         int first[2] = {0, 0};

@@ -93,19 +93,6 @@ __device__ __forceinline__ void load_row_f32_i(const float* row, int d, int lane
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const int c = icol(it, j, lane); r.v[it][j] = c < d ? row[c] : 0.f; }
 }
-// the same with non-temporal stores: a tape copy nobody reads before the backward's weight-gradient launch (~10 ms later) should not
-// push the operands of the next GEMM out of the Infinity Cache
-__device__ __forceinline__ void store_row_bf16_stream(bf16_t* row, int d, int lane, const RowF& r) {
-#pragma unroll
-    for (int it = 0; it < MAX_IT; ++it) {
-        const int c = it * 256 + lane * 4;
-        if (c < d) {
-            typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-            const u32x2_t u = {pack2bf(r.v[it][0], r.v[it][1]), pack2bf(r.v[it][2], r.v[it][3])};
-            __builtin_nontemporal_store(u, (u32x2_t*)(row + c));
-        }
-    }
-}
 __device__ __forceinline__ void store_row_bf16(bf16_t* row, int d, int lane, const RowF& r) {
 #pragma unroll
     for (int it = 0; it < MAX_IT; ++it) {
@@ -163,8 +150,7 @@ template <int DC, bool X32>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, bf16_t* __restrict__ out, float* __restrict__ out32,
                                                       float* __restrict__ mean_o, float* __restrict__ rstd_o, int T, int d_rt,
-                                                      float eps, float* __restrict__ cls_out, int cls_stride, int out_f16,
-                                                      bf16_t* __restrict__ out_copy) {
+                                                      float eps, float* __restrict__ cls_out, int cls_stride, int out_f16) {
     const int d = DC ? DC : d_rt;      // compile-time row width: the `c < d` tests and the unused 4th column pass fold away
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -187,7 +173,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
     }
     if (out_f16) store_row_f16(out + (size_t)row * d, d, lane, r);
     else store_row_bf16(out + (size_t)row * d, d, lane, r);
-    if (out_copy) store_row_bf16_stream(out_copy + (size_t)row * d, d, lane, r);       // fp16 `out` for the forward GEMM + the bf16 tape copy
     if (X32 && out32) store_row_f32(out32 + (size_t)row * d, d, lane, r);
     if (lane == 0) { if (mean_o) mean_o[row] = mean; if (rstd_o) rstd_o[row] = rstd; }
 }
@@ -202,8 +187,8 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
                                                             bf16_t* __restrict__ out, float* __restrict__ out32, float* __restrict__ mean_o,
                                                             float* __restrict__ rstd_o, int T, int L, int d_rt, int vocab, float eps,
                                                             uint32_t drop_thresh, float drop_scale, SeedArg seed_a, int out_f16,
-                                                            const int* __restrict__ pos_idx, bf16_t* __restrict__ out_copy,
-                                                            const int* __restrict__ type_ids = nullptr, int type_vocab = 1) {
+                                                            const int* __restrict__ pos_idx, const int* __restrict__ type_ids = nullptr,
+                                                            int type_vocab = 1) {
     const uint64_t seed = seed_a.get();
     const int d = DC ? DC : d_rt;      // compile-time row width: the `c < d` tests and the unused 4th column pass fold away
     const int lane = threadIdx.x & 63;
@@ -254,7 +239,6 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
     }
     if (out_f16) store_row_f16(out + (size_t)row * d, d, lane, r);
     else store_row_bf16(out + (size_t)row * d, d, lane, r);
-    if (out_copy) store_row_bf16(out_copy + (size_t)row * d, d, lane, r);
     if (out32) store_row_f32(out32 + (size_t)row * d, d, lane, r);
     if (lane == 0) { mean_o[row] = mean; rstd_o[row] = rstd; }
 }
@@ -605,14 +589,12 @@ static inline int ln_bwd_blocks(int T) {
 extern "C" int cldrd_ln_partial_blocks(int T) { return ln_bwd_blocks(T); }
 
 extern "C" int cldrd_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* out, float* mean, float* rstd,
-                                   int T, int d, float eps, float* cls_out, int cls_stride, int x_f32, float* out32, int out_f16,
-                                   void* out_bf16_copy, void* stream) {
+                                   int T, int d, float eps, float* cls_out, int cls_stride, int x_f32, float* out32, int out_f16, void* stream) {
     CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0, "layernorm_fwd: need 0 < d <= 1024, d % 4 == 0");
-    CLDRD_CHECK(out_bf16_copy == nullptr || out_f16, "layernorm_fwd: the bf16 copy goes with an fp16 output");
     CLDRD_CHECK(x_f32 || out32 == nullptr, "layernorm_fwd: an fp32 output copy goes with an fp32 input (the fp32 residual stream)");
     ln_dispatch(d, x_f32 != 0, [&](auto dc, auto x32) {
         hipLaunchKernelGGL((ln_fwd_kernel<decltype(dc)::value, decltype(x32)::value>), dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,
-                           (bf16_t*)out, out32, mean, rstd, T, d, eps, cls_out, cls_stride > 0 ? cls_stride : 1, out_f16, (bf16_t*)out_bf16_copy);
+                           (bf16_t*)out, out32, mean, rstd, T, d, eps, cls_out, cls_stride > 0 ? cls_stride : 1, out_f16);
     });
     CLDRD_LAUNCH_CHECK();
     return 0;
@@ -623,8 +605,7 @@ extern "C" int cldrd_layernorm_fwd(const void* x, const float* gamma, const floa
 extern "C" int cldrd_embed_ln_fwd(const long long* ids, const float* word, const float* pos, const float* type_table, const int* type_ids,
                                   int type_vocab, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
                                   int d, int vocab, float eps, float dropout_p, unsigned long long seed, float* out32, int out_f16,
-                                  const int* pos_idx, void* out_bf16_copy, void* stream) {
-    CLDRD_CHECK(out_bf16_copy == nullptr || out_f16, "embed_ln_fwd: the bf16 copy goes with an fp16 output");
+                                  const int* pos_idx, void* stream) {
     CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0 && L > 0, "embed_ln_fwd: bad shape");
     CLDRD_CHECK(type_ids == nullptr || (type_table != nullptr && type_vocab > 0), "embed_ln_fwd: type ids need the token-type table");
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
@@ -632,8 +613,8 @@ extern "C" int cldrd_embed_ln_fwd(const long long* ids, const float* word, const
         ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
             hipLaunchKernelGGL((embed_ln_fwd_kernel<decltype(dc)::value, decltype(dr)::value, decltype(typed)::value>), dim3((T + 3) / 4), dim3(256), 0,
                                (hipStream_t)stream, (const int64_t*)ids, word, pos, type_table, gamma, beta, (bf16_t*)out, out32, mean, rstd, T, L,
-                               d, vocab, eps, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, (bf16_t*)out_bf16_copy,
-                               type_ids, type_ids ? type_vocab : 1);
+                               d, vocab, eps, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), out_f16, pos_idx, type_ids,
+                               type_ids ? type_vocab : 1);
         });
     };
     if (type_ids == nullptr) launch(std::false_type{});

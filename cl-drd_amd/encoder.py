@@ -249,15 +249,6 @@ class _Pack:
         return pk
 
 
-def _drain(gen):
-    """run a generator to its end; its return value"""
-    try:
-        while True:
-            next(gen)
-    except StopIteration as stop:
-        return stop.value
-
-
 class Stepper:
     """A forward or backward of one tower that is enqueued PIECE BY PIECE: ``step(n)`` enqueues the next n groups of launches (a group = a few
     dependent kernels: a projection + attention, an out-projection + LayerNorm, an FFN GEMM, ...), ``finish()`` the rest and returns the
@@ -331,8 +322,6 @@ class HipEncoder(nn.Module):
             raise ValueError(f"CLDRD_AMP must be fp16 or bf16, got {mode!r}")
         self.amp_mode = mode
         self._amp_fp16 = mode == "fp16"
-        self.stream32 = True                  # fp32 residual stream (pre-LN sums) in both modes
-        self.grad_stream32 = True             # fp32 arithmetic on the residual path of the backward in both modes
         self.ffn_fp16 = self._amp_fp16        # evaluation pass of the fp16 mode: FFN / out-projection (and deep towers' QKV) GEMMs on fp16 operands
         self._grad_stream16 = True            # fp16 mode: the gradient stream is stored in fp16 between kernels (test hook: False keeps it fp32)
         self.ln_defer = True                  # LayerNorm-parameter gradients reduced by one grouped launch per flush (test hook: False = immediately)
@@ -484,8 +473,8 @@ class HipEncoder(nn.Module):
 
     @property
     def amp16(self):
-        """the all-fp16 training mode (see __init__): needs the fp32 residual stream and the fp32 gradient stream"""
-        return self._amp_fp16 and self.stream32 and self.grad_stream32
+        """the all-fp16 training mode (see __init__)"""
+        return self._amp_fp16
 
     @property
     def grad_stream16(self):
@@ -713,9 +702,6 @@ class HipEncoder(nn.Module):
                 return self._encode_gen(input_ids, attention_mask, train=train, save=False, seed=seed, fp16=True, window=window)
         return self._encode_gen(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=False, lengths=lengths, window=window)
 
-    def _encode(self, input_ids, attention_mask, *, train, save, seed, fp16, lengths=None):
-        return _drain(self._encode_gen(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=fp16, lengths=lengths))
-
     def _encode_gen(self, input_ids, attention_mask, *, train, save, seed, fp16, lengths=None, window=None, token_type_ids=None, packed=None):
         """one forward pass as a generator: a ``yield`` behind every group of launches (:class:`Stepper`); returns cls or (cls, tape)"""
         cfg = self.cfg
@@ -772,7 +758,6 @@ class HipEncoder(nn.Module):
             tape.M, tape.L, tape.T, tape.ids, tape.mask, tape.seed, tape.layers = M, L, T, ids, mask, seed, []
             tape.p_embed, tape.pack, tape.device_seed = p_h, pk, False
         f32 = dict(dtype=torch.float32, device=dev)
-        sdt = torch.float32                                     # storage type of the pre-LN sums: the fp32 residual stream
         # QKV16 (evaluation pass of the fp16 mode, towers deeper than 6 layers): the QKV projection reads fp16 operands too (bf16 q / k / v
         # out: that pass's attention kernels are bf16).  With the FFN pair in fp16, x_in / Wqkv are the next largest source of logit drift
         # (BERT-base cfg4 golden: 0.190 -> 0.116); the 6-layer configs are at 2-3.5e-3 without it and would only pay for it.
@@ -833,7 +818,7 @@ class HipEncoder(nn.Module):
                 ops.attention_fwd(qkv, mask if pk is None else None, ctx, lse, M, L, H, p_a, s_l + 1, drop_bits=dbits, ctx16=ctx16,
                                   full_family=fp16 and self.amp16, cu=cu, seq_list=sl, tile=tile)
             yield
-            s1 = self._buf(T, d, dev, sdt)
+            s1 = self._buf(T, d, dev, torch.float32)      # pre-LN sums are stored in fp32: the fp32 residual stream
             ops.gemm_nt(ctx16 if OUT16 else ctx, (W16 if OUT16 else W)["Wo"], s1, T, bias=W["bo"], residual=x32, dropout_p=p_out,
                         seed=s_l + 2, residual_ln=res_ln)
             del ctx16
@@ -850,7 +835,7 @@ class HipEncoder(nn.Module):
                 hh = self._buf(T, f, dev, torch.float16)
                 ops.gemm_nt(x1h, W16["W1"], hh, T, bias=W["bf1"], act=1)
                 yield
-                s2 = self._buf(T, d, dev, sdt)
+                s2 = self._buf(T, d, dev, torch.float32)
                 ops.gemm_nt(hh, W16["W2"], s2, T, bias=W["bf2"], residual=s1, dropout_p=p_h, seed=s_l + 3, residual_ln=(mean1, rstd1, W["g1"], W["b1"]))
                 del x1h, hh
             else:
@@ -861,7 +846,7 @@ class HipEncoder(nn.Module):
                 pre = self._buf(T, f, dev, dt16) if save else None
                 ops.gemm_nt(x1, W["W1"], hbuf, T, bias=W["bf1"], preact=pre, act=3 if save else 1)     # the tape keeps gelu'(pre-activation)
                 yield
-                s2 = self._buf(T, d, dev, sdt)
+                s2 = self._buf(T, d, dev, torch.float32)
                 ops.gemm_nt(hbuf, W["W2"], s2, T, bias=W["bf2"], residual=s1, dropout_p=p_h, seed=s_l + 3, residual_ln=(mean1, rstd1, W["g1"], W["b1"]))
             xo = self._buf(T, d, dev, dt16) if not QKV16 else None
             xoh = self._buf(T, d, dev, torch.float16) if QKV16 else None
@@ -896,13 +881,12 @@ class HipEncoder(nn.Module):
         dev = (x if x is not None else xh).device
         f32 = dict(dtype=torch.float32, device=dev)
         kv = self._buf(T, 2 * d, dev, dt16)
-        Q16 = xh is not None and W16 is not None              # fp16 operands for the K / V / Q projections (bf16 results), see _encode
+        Q16 = xh is not None and W16 is not None              # fp16 operands for the K / V / Q projections (bf16 results), see _encode_gen
         if Q16:
             ops.gemm_nt(xh, W16["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
         else:
             ops.gemm_nt(x, W["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
         yield
-        sdt = torch.float32
         if pk is None:
             # the CLS rows are rows 0, L, 2L, ... of the layer input: STRIDED VIEWS (row pitch L * d), no copies - every consumer (the Q
             # projection's A operand, its weight gradient's X operand, the out-projection's fp32 residual) takes a row pitch.  Until round 5
@@ -932,7 +916,7 @@ class HipEncoder(nn.Module):
         ops.attention_cls_fwd(qc, kv, mask if pk is None else None, ctxc, probs, M, L, H, p_a, s_l + 1, ctx16=ctxc16,
                               cu=pk.cu if pk is not None else None)
         yield
-        s1 = self._buf(M, d, dev, sdt)
+        s1 = self._buf(M, d, dev, torch.float32)
         ops.gemm_nt(ctxc16 if out16 else ctxc, (W16 if out16 else W)["Wo"], s1, M, bias=W["bo"], residual=xc32, dropout_p=p_out, seed=s_l + 2)
         yield
         x1_32 = self._buf(M, d, dev, torch.float32)
@@ -943,7 +927,7 @@ class HipEncoder(nn.Module):
             ops.layernorm_fwd(s1, W["g1"], W["b1"], x1h, mean1, rstd1, M, cfg.eps, out32=x1_32)
             hh = self._buf(M, f, dev, torch.float16)
             ops.gemm_nt(x1h, W16["W1"], hh, M, bias=W["bf1"], act=1)
-            s2 = self._buf(M, d, dev, sdt)
+            s2 = self._buf(M, d, dev, torch.float32)
             ops.gemm_nt(hh, W16["W2"], s2, M, bias=W["bf2"], residual=x1_32, dropout_p=p_h, seed=s_l + 3)
         else:
             x1 = self._buf(M, d, dev, dt16)
@@ -951,7 +935,7 @@ class HipEncoder(nn.Module):
             hbuf = self._buf(M, f, dev, dt16)
             pre = self._buf(M, f, dev, dt16) if save else None
             ops.gemm_nt(x1, W["W1"], hbuf, M, bias=W["bf1"], preact=pre, act=3 if save else 1)
-            s2 = self._buf(M, d, dev, sdt)
+            s2 = self._buf(M, d, dev, torch.float32)
             ops.gemm_nt(hbuf, W["W2"], s2, M, bias=W["bf2"], residual=x1_32, dropout_p=p_h, seed=s_l + 3)
         yield
         xo = self._buf(M, d, dev, dt16)
@@ -971,11 +955,10 @@ class HipEncoder(nn.Module):
         dev = self.flat_p.device
         W, G = self._layer_weights(i), self._layer_grads(i)
         s_l, p_h, p_a, p_out = a["seed"], a["p_h"], a["p_a"], a["p_out"]
-        sdt = torch.float32                                             # this layer's M-row gradient stream stays fp32 in both modes
         bdt = a["h"].dtype                                              # the backward's 16-bit format = the tape's (fp16 or bf16)
         buf = lambda r, c, dv, dt=None: self._buf(r, c, dv, bdt if dt is None else dt)
         gc = dcls.contiguous()                                          # dL/dCLS is the stream's first tensor: no rounding at all
-        ds2 = buf(M, d, dev, sdt)
+        ds2 = buf(M, d, dev, torch.float32)      # this layer's M-row gradient stream stays fp32 in both modes
         ds2m = buf(M, d, dev)                                    # 16-bit MFMA operand of the next data-gradient GEMM
         lnq = getattr(self, "_lnq", None)
         f32 = dict(dtype=torch.float32, device=dev)
@@ -988,10 +971,10 @@ class HipEncoder(nn.Module):
         dpre = buf(M, f, dev)
         ops.gemm_nt(dF, self.ht(i, "f2"), dpre, M, gelu_pre=a["pre"], act=2)
         self._wq.add(dpre, a["x1"], G["W1"], M, dbias=G["bf1"])
-        dx1 = buf(M, d, dev, sdt)
+        dx1 = buf(M, d, dev, torch.float32)
         ops.gemm_nt(dpre, self.ht(i, "f1"), dx1, M, residual=ds2)
         yield
-        ds1 = buf(M, d, dev, sdt)
+        ds1 = buf(M, d, dev, torch.float32)
         ds1m = buf(M, d, dev)
         ops.layernorm_bwd(dx1, a["s1"], a["mean1"], a["rstd1"], W["g1"], ds1, ds1m, G["g1"], G["b1"], G["bo"], own(), M, p_out, s_l + 2,
                           accumulate=self._acc, defer=lnq)
@@ -1010,9 +993,9 @@ class HipEncoder(nn.Module):
         wt = self.ht(i, "qkv")                                      # [d, 3d] = Wqkv^T
         # the [T, d] gradient this layer hands down: fp32 - or fp16 with the fp16 gradient stream (the layer's own M-row stream stays fp32:
         # the CLS rows are added from the fp32 gq with one rounding)
-        g = buf(T, d, dev, torch.float16 if (self.grad_stream16 and bdt == torch.float16) else sdt)
+        g = buf(T, d, dev, torch.float16 if (self.grad_stream16 and bdt == torch.float16) else torch.float32)
         ops.gemm_nt(dkv, wt[:, d:], g, T)                           # through K and V: every token
-        gq = buf(M, d, dev, sdt)
+        gq = buf(M, d, dev, torch.float32)
         ops.gemm_nt(dqc, wt[:, :d], gq, M, residual=ds1)            # through Q and the residual: CLS rows only
         ops.add_rows(g, gq, M, stride=L, idx=pk.cls_idx if pk is not None else None)
         return g

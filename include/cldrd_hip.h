@@ -60,14 +60,13 @@ enum cldrd_fmt16 {
  * workspace (optional): problems of fewer than 1024 rows whose one-pass grid would leave most CUs idle (CLS-only last layer, query
  * tower) are split along K: fp32 partials in `workspace` (cldrd_gemm_nt_splitk_workspace() bytes; 0 = this shape is not split), summed in
  * a fixed order and finished with the same epilogue by a second launch.  workspace = NULL: one pass.
- * fmt != CLDRD_FMT_BF16 also serves M >= 1024 (csrc/gemm_nt_ring16.hip).  c_copy_bf16: NULL (a bf16 copy of an fp16 C for the removed
- * "bf16 tape under an fp16 forward" mode of rounds 3-5; kept in the signature, rejected when non-NULL with any format but CLDRD_FMT_F16). */
+ * fmt != CLDRD_FMT_BF16 also serves M >= 1024 (csrc/gemm_nt_ring16.hip). */
 size_t cldrd_gemm_nt_splitk_workspace(int M, int N, int K);
 int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
                     const float* bias, const void* residual, int ldr, void* preact, const void* gelu_pre,
                     int act, float alpha, float dropout_p, unsigned long long seed, int out_f32, int res_f32, int fmt,
                     const float* ln_mean, const float* ln_rstd, const float* ln_gamma, const float* ln_beta,
-                    void* c_copy_bf16, float* workspace, size_t workspace_bytes, void* stream);
+                    float* workspace, size_t workspace_bytes, void* stream);
 
 /* Weight gradient dW[N1,N2] (+)= A[M,N1]^T . B[M,N2]   (A = dY, B = layer input; autograd's Linear backward), and,
  * when dbias != NULL, the bias gradient dbias[N1] (+)= column sums of A in the same pass.
@@ -143,7 +142,7 @@ int cldrd_ln_partial_blocks(int T);
 int cldrd_embed_ln_fwd(const long long* ids, const float* word, const float* pos, const float* type_table, const int* type_ids,
                        int type_vocab, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int T, int L,
                        int d, int vocab, float eps, float dropout_p, unsigned long long seed, float* out32, int out_f16,
-                       const int* pos_idx, void* out_bf16_copy, void* stream);
+                       const int* pos_idx, void* stream);
 int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
                        const float* gamma, const float* mean, const float* rstd, float* dword, float* dpos,
                        float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
@@ -153,11 +152,10 @@ int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, 
  * the `[0][:, 0, :]` CLS pooling of models/nway_dual_encoder.py:52,56,64.
  * x_f32 != 0: x is fp32 (the pre-LN sum of the fp32 residual stream) and out32 (optional) receives the fp32 output next to
  * the bf16 copy the GEMMs read; cldrd_embed_ln_fwd has the same optional out32.
- * out_f16 != 0: `out` is fp16 (operand of an fp16 forward GEMM) and out_bf16_copy (optional) receives the same values in bf16: the
- * backward's MFMAs multiply the saved activations with bf16 gradients, so a training forward whose FFN GEMMs read fp16 keeps both. */
+ * out_f16 != 0: `out` is fp16 (operand of an fp16 forward GEMM; in the all-fp16 training mode also the backward's tape). */
 int cldrd_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* out, float* mean, float* rstd,
                         int T, int d, float eps, float* cls_out, int cls_stride, int x_f32, float* out32, int out_f16,
-                        void* out_bf16_copy, void* stream);
+                        void* stream);
 /* The format of the GRADIENT STREAM - the rows that carry dL/dx from one backward kernel to the next - is said by one code wherever such rows
  * are passed (grad_fmt of cldrd_embed_ln_bwd and cldrd_layernorm_bwd, fmt of cldrd_scatter_cls_grad and cldrd_add_rows):
  *   CLDRD_STREAM_BF16  dy is read and dx written as bf16 rows; no dy_branch.

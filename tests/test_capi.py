@@ -130,7 +130,7 @@ def test_merged_entry_points_reject_inconsistent_arguments():
         return "topk_rescore", lib.cldrd_topk_rescore(P, P32, P16, qmu, 128, P, P, P, 4, 1024, None)
 
     def embed_fwd(table=P, type_ids=P, type_vocab=2):
-        return "embed_ln_fwd", lib.cldrd_embed_ln_fwd(P, P, P, table, type_ids, type_vocab, P, P, P, P, P, 16, 8, 128, 300, 1e-12, 0.0, 7, None, 0, None, None, None)
+        return "embed_ln_fwd", lib.cldrd_embed_ln_fwd(P, P, P, table, type_ids, type_vocab, P, P, P, P, P, 16, 8, 128, 300, 1e-12, 0.0, 7, None, 0, None, None)
 
     def ln_bwd(x_f32=1, fmt=BF16, dx_dropped=P, branch=None):
         return "layernorm_bwd", lib.cldrd_layernorm_bwd(P, P, P, P, P, P, dx_dropped, None, None, None, P, 16, 128, 0.0, 7, 0, x_f32, fmt, 0, branch, None)

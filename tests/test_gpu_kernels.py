@@ -695,6 +695,59 @@ def test_attention_on_packed_rows_every_length(L, H, f16, p):
     assert torch.equal(out[True][2][lv], out[False][2][lv]) and bool(torch.isfinite(out[True][2]).all())
 
 
+@pytest.mark.parametrize("f16,p,use_bits", [(False, 0.0, False), (True, 0.0, False), (False, 0.1, True), (True, 0.1, False), (True, 0.1, True),
+                                            (False, 0.1, False)])
+def test_attention_bwd_persistent_kernel_at_block_boundaries(f16, p, use_bits):
+    """The persistent backward (attn_bwd2_kernel) runs its query- and key-block loops to the run-time count of live 32-row blocks and reads dQ / dK /
+    dV right behind the loop's exit: the edge on which hipcc miscounts the wait states behind an MFMA (attention.hip, mfma_drain()).  Lengths on both
+    sides of every block boundary - 59 .. 64 (the lengths that showed the forward's hazard), 91 .. 96, 1, 32, 33, 128 - in one launch of enough
+    (sequence, head) items for the dispatch to take the persistent kernel, against the one-item-per-workgroup kernel (set_tuning("attn_bwd2", 0)): the
+    live rows of dqkv bit for bit, packed and padded, bf16 and fp16 tapes, without dropout, with the forward's keep bits and with the re-hash."""
+    L, H = 128, 2
+    d = H * 64
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nseq = max(300, cus)
+    # Nothing here observes which kernel ran: the first run takes attn_bwd2_kernel only through launch_bwd's rule in csrc/attention.hip (L <= 128,
+    # nseq * H >= 2 * CUs, tuning "attn_bwd2" != 0).  If that rule changes, change this assert with it - otherwise both runs take the one-item kernel
+    # and the test compares it with itself.
+    assert nseq * H >= 2 * cus
+    dt = torch.float16 if f16 else torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(5900 + 2 * int(f16) + int(p > 0))
+    pool = torch.tensor(list(range(59, 65)) + list(range(91, 97)) + [1, 32, 33, 128], device=DEV)
+    lens = pool[torch.arange(nseq, device=DEV) % pool.numel()]
+    cu = torch.zeros(nseq + 1, dtype=torch.int32, device=DEV)
+    cu[1:] = torch.cumsum(lens, 0).to(torch.int32)
+    Tp = int(cu[-1])
+    mask = (torch.arange(L, device=DEV)[None, :] < lens[:, None]).to(torch.int64).contiguous()
+    tok = torch.nonzero(mask.reshape(-1)).reshape(-1)
+    qkv = torch.randn(nseq * L, 3 * d, device=DEV, generator=g).to(dt)            # real values in the padding rows (masked, not zero)
+    dctx = torch.randn(nseq * L, d, device=DEV, generator=g).to(dt) * mask.reshape(-1, 1).to(dt)
+    for pk in (True, False):
+        rows = Tp if pk else nseq * L
+        x, dy = (qkv[tok].contiguous(), dctx[tok].contiguous()) if pk else (qkv, dctx)
+        ctx = torch.full((rows, d), float("nan"), dtype=dt, device=DEV)
+        lse = torch.full((nseq, H, L), float("nan"), dtype=torch.float32, device=DEV)
+        bits = ops.attention_drop_bits(nseq, L, H, p, DEV) if use_bits else None
+        assert (bits is not None) == use_bits
+        ops.attention_fwd(x, None if pk else mask, ctx, lse, nseq, L, H, dropout_p=p, seed=59, drop_bits=bits, full_family=f16, cu=cu if pk else None)
+        outs = []
+        for bwd2 in (1, 0):
+            dqkv = torch.full((rows, 3 * d), float("nan"), dtype=dt, device=DEV)
+            ops.set_tuning("attn_bwd2", bwd2)
+            try:
+                ops.attention_bwd(x, None if pk else mask, ctx, dy, lse, dqkv, nseq, L, H, dropout_p=p, seed=59, drop_bits=bits, cu=cu if pk else None)
+                torch.cuda.synchronize()
+            finally:
+                ops.set_tuning("attn_bwd2", 1)
+            outs.append(dqkv if pk else dqkv[tok])
+        assert not torch.isnan(outs[0].float()).any()
+        same = (outs[0] == outs[1]).all(1)
+        seq_of = torch.repeat_interleave(torch.arange(nseq, device=DEV), lens)
+        bad = sorted(set(lens[seq_of[~same]].tolist()))
+        assert torch.equal(outs[0], outs[1]), \
+            f"{'packed' if pk else 'padded'}: the persistent kernel differs from the one-item kernel for sequences of {bad} tokens"
+
+
 @pytest.mark.parametrize("L,H,f16,p", [(256, 2, False, 0.0), (256, 4, True, 0.0), (200, 1, True, 0.0)])
 def test_attention_sequence_lists_send_short_sequences_through_the_short_kernels(L, H, f16, p):
     """cldrd_attention_{fwd,bwd}_varlen_list: a packed batch at 128 < L <= 256 in TWO launches - the sequences of at most 128 tokens through the

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised check of cldrd_gemm_nt16 against fp64 on the same rounded inputs: random M (1 .. 6000: both kernels, tails), N (multiples of 8),
 K (multiples of 64), operand format (bf16 / fp16), and every epilogue the encoder uses (bias, GELU with / without the tape, GELU gradient,
-bf16 / fp32 residual, LayerNorm on the fly, dropout, fp32 out, fp16 -> bf16 result, bf16 tape copy).  usage: tools/gemm_fuzz.py [cases] [seed]"""
+bf16 / fp32 residual, LayerNorm on the fly, dropout, fp32 out, fp16 -> bf16 result).  usage: tools/gemm_fuzz.py [cases] [seed]"""
 import os, sys, math
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,7 +37,6 @@ for c in range(cases):
         kw["bias"] = bias; kw["act"] = 1; ref = gelu(ref + bias.double())
     elif flav == "gelu_tape":
         kw["bias"] = bias; kw["act"] = 3; pre = torch.empty(M, N, dtype=torch.bfloat16, device=DEV); kw["preact"] = pre
-        if f16: kw["out_copy"] = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
         x = ref + bias.double(); ref = gelu(x); ref_pre = dgelu(x)
     elif flav == "gelugrad":
         gp = torch.randn(M, N, device=DEV, generator=g).to(torch.bfloat16); kw["gelu_pre"] = gp; kw["act"] = 2; ref = ref * gp.double()
@@ -66,8 +65,6 @@ for c in range(cases):
     ok = bool((err <= tol_r * ref.abs() + tol_a * max(scale, 1e-3) * (1 if out_dt != torch.float32 else 0.01)).all()) and bool(torch.isfinite(out.float()).all())
     if ok and flav == "gelu_tape":
         ok = bool(((pre.double() - ref_pre).abs() <= 2.0 ** -6 * ref_pre.abs() + 2e-2).all())
-        if ok and "out_copy" in kw:
-            ok = bool(torch.equal(kw["out_copy"].float(), out.float().to(torch.bfloat16).float())) or bool(((kw["out_copy"].double() - ref).abs() <= 2.0 ** -7 * ref.abs() + 2e-2 * scale).all())
     if not ok:
         bad += 1
         print(f"MISMATCH case {c}: M {M} N {N} K {K} f16 {f16} {flav} out {out_dt}: max err {err.max().item():.3e} (scale {scale:.3e})", flush=True)
