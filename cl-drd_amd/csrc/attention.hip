@@ -110,7 +110,7 @@ __device__ __forceinline__ uint4 widen_pair(const uint2& g0, const uint2& g1) {
 // a[48:63] - stale scores for keys 58, 59, 62, 63 of every sequence of 59 .. 64 tokens (tools/wgrad_attn_fuzz.py found it; the keys are masked
 // in shorter sequences, which is why nothing else noticed).  mfma_drain() ends every block iteration of such a loop, in front of the next
 // iteration's exit test: 24 wait states (more than the longest XDL result latency) on BOTH ways out of the branch, pinned against the schedulers;
-// they pass under the last MFMA of the block, which occupies the pipe for longer than that.  Drained: the key-block loops of the forward kernels,
+// they pass under the last MFMA of the block, which occupies the pipe for longer than that.  Drained: the key-block loops of the forward bodies (fwd_full_block, the two streaming kernels),
 // both block loops of attn_bwd_kernel when VARLEN, and both sweeps of attn_bwd2_kernel (its count nb is a run-time value in either layout).  In the
 // key-side sweep of attn_bwd2_kernel (dK, dV: four accumulators, the kernel's register peak) the drain stands BEHIND the loop instead of at the end of
 // its body: the loop's only exit falls through to it, so the wait states lie between the last MFMA and the first read of dK / dV all the same, and on the
@@ -122,7 +122,7 @@ __device__ __forceinline__ void mfma_drain() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-#define CLDRD_LIVE_BLOCKS(len, NKB) (((len) + 31) >> 5)
+__device__ __forceinline__ int live_blocks(int len) { return (len + 31) >> 5; }      // 32-row blocks that hold a row < len (see seq_rows)
 // A launch may cover a LIST of sequences (seq_list, device int32; null: all of them in order): item i / H is then the list position and
 // seq_list[i / H] the sequence - how a packed batch with L > 128 sends its sequences of at most 128 tokens (most of an MS MARCO batch) to the
 // L <= 128 kernels (persistent, double-buffered) and only the long ones to the streaming / one-item kernels: `L` stays the stride of LSE and of
@@ -144,9 +144,182 @@ __device__ __forceinline__ void load_tile(char* tile, const bf16_t* src, int ld,
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Every pass exists in two launch forms: ONE ITEM per workgroup (load -> barrier -> compute), and PERSISTENT (one workgroup per CU walks its items
+// and fetches the next one under the arithmetic of the current one).  The forms differ in how an item's tiles reach LDS and in nothing else: the
+// arithmetic of a block - and the stores behind it - is one function below, called by both kernels of a pair, which is why the pair gives the same
+// bits (the tests flip cldrd_set_tuning("attn_fwd2" / "attn_bwd2", 0) and compare).  One exception: the streaming forward pair (attn_fwd_kernel /
+// attn_fwd3_kernel) shares prologue and stores, but each kernel carries the block loop itself (see attn_fwd3_kernel).
+
+// Mask bias of key k: 0, or NEG_BIG for a key that is masked or beyond the sequence
+__device__ __forceinline__ float key_bias(const int64_t* __restrict__ mask, int seq, int L, int k, int len) {
+    return (k < len && (!mask || mask[(size_t)seq * L + k] != 0)) ? 0.f : NEG_BIG;
+}
+// Prologue of the one-item kernels: the item's Q, K, V head slices into their LDS tiles (rows >= its length zero).  With the bias fill below, the
+// caller's __syncthreads() completes it.
+__device__ __forceinline__ void load_item_tiles(char* sQ, char* sK, char* sV, const bf16_t* __restrict__ qkv, int hd, SeqRows sr, int H, int Lp) {
+    const int dm = H * 64, ld = 3 * dm;
+    const bf16_t* base = qkv + (size_t)sr.row0 * ld + hd * 64;
+    load_tile(sQ, base, ld, sr.len, Lp);
+    load_tile(sK, base + dm, ld, sr.len, Lp);
+    load_tile(sV, base + 2 * dm, ld, sr.len, Lp);
+}
+// The key bias of one item, as the forward kernels fill it (attn_bwd_kernel fills it in the loop that also converts the LSE and hashes the row keys)
+__device__ __forceinline__ void fill_key_bias(float* sBias, const int64_t* __restrict__ mask, int seq, int L, int Lp, int len) {
+    for (int k = threadIdx.x; k < Lp; k += blockDim.x) sBias[k] = key_bias(mask, seq, L, k, len);
+}
+
+// LSE of query q (log2 domain in, natural log out): lanes r and r + 32 hold the same value, the lower half stores it.  A query block beyond the
+// sequence passes (0, len): the closed form of its zero rows (see seq_rows).
+__device__ __forceinline__ void store_lse(float* __restrict__ lse, int seq, int hd, int H, int L, int q, int h, float m, float l) {
+    if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (m + __log2f(l)) * LN2;
+}
+
+// Context rows of a query block, at ctx / ctx16 + orow (the lane's query row).  O[dt][t] = ctx^T[d = 32 dt + rowmap(t, h)][q]: registers 4u .. 4u+3
+// are 4 consecutive head dimensions of the lane's query row; one v_permlane32_swap pair makes them 16 contiguous bytes (widen_pair): 4 (+ 4 for the
+// fp16 copy) 16-byte stores per lane instead of 32 (+ 32) two-byte ones.  (Round 2 tried the transposed form with 8-byte stores and found it 8 %
+// slower; round 5, with the widened stores: profiles/r05_microbench.txt section 6.)
+// ctx: the kernel's own format (may be absent); ctx16: an fp16 copy of a bf16 pass (out-projection operand).  SCALE: the streaming form's deferred
+// 1 / l (x 1 / (1 - p_drop)); the all-scores form has normalised its probabilities already and multiplies by nothing here.
+template <bool F16, bool SCALE>
+__device__ __forceinline__ void store_ctx_rows(const f32x16 (&O)[2], float inv, bf16_t* __restrict__ ctx, bf16_t* __restrict__ ctx16, size_t orow, int h,
+                                               bool live) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int u = 0; u < 4; u += 2) {
+            uint2 o[2], o16[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int b = 4 * (u + k);
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = SCALE ? O[dt][b + e] * inv : O[dt][b + e];
+                o[k].x = pack2x<F16>(v[0], v[1]);
+                o[k].y = pack2x<F16>(v[2], v[3]);
+                o16[k].x = (uint32_t)f2x<true>(v[0]) | ((uint32_t)f2x<true>(v[1]) << 16);
+                o16[k].y = (uint32_t)f2x<true>(v[2]) | ((uint32_t)f2x<true>(v[3]) << 16);
+            }
+            if (ctx) {
+                const uint4 w = widen_pair(o[0], o[1]);
+                if (live) *(uint4*)(ctx + orow + dt * 32 + 8 * (u + h)) = w;
+            }
+            if (ctx16) {
+                const uint4 w = widen_pair(o16[0], o16[1]);
+                if (live) *(uint4*)(ctx16 + orow + dt * 32 + 8 * (u + h)) = w;
+            }
+        }
+}
+
+// Where the all-scores forward takes its dropout keep decisions from.  row(rowidx, q) once per query: mask row rowidx = (seq*H + hd)*L + q;
+// pair(p, kb, t, h) zeroes the dropped ones of the two probabilities of keys 32 kb + rowmap(t, h) and + 1 (a column pair of the mask).
+struct KeepHash {                 // hashed on the spot (common.h): the one-item kernel
+    uint64_t seed; uint32_t thresh; uint32_t rk;
+    __device__ __forceinline__ void row(uint32_t rowidx, int) { rk = drop_rowkey(seed, rowidx); }
+    __device__ __forceinline__ void pair(cldrd_f32v2& p, int kb, int t, int h) const {
+        const uint32_t hh = drop_pair(rk, (uint32_t)(kb * 32 + rowmap(t, h)));
+        p.x = drop_keep_lo(hh, thresh) ? p.x : 0.f;
+        p.y = drop_keep_hi(hh, thresh) ? p.y : 0.f;
+    }
+};
+template <int Lp>
+struct KeepBits {                 // the loader waves' dword [kb][q] in LDS (attn_fwd2_kernel): two adjacent bits
+    const uint32_t* sBits; int q;
+    __device__ __forceinline__ void row(uint32_t, int q_) { q = q_; }
+    __device__ __forceinline__ void pair(cldrd_f32v2& p, int kb, int t, int h) const {
+        const uint32_t w = sBits[kb * Lp + q] >> (4 * h);
+        p.x = keep_bit(p.x, w, rowmap(t, 0));
+        p.y = keep_bit(p.y, w, rowmap(t, 0) + 1);
+    }
+};
+
 // DROP is a template parameter: as a run-time test hipcc branched on it per element (16 branches per MFMA tile, with the
 // accumulators re-read from AGPRs on both sides), which made these kernels VALU-bound.
 //
+// All-scores forward of one query block (L <= 128): Q fragments -> 16 NKB score accumulators -> softmax -> P.V -> LSE and context rows.  Called by one wave
+// with the item's tiles complete in LDS; shared by attn_fwd_full_kernel and attn_fwd2_kernel, which differ in `keep` only.
+template <int NKB, bool DROP, bool F16, class Keep>
+__device__ __forceinline__ void fwd_full_block(const char* sQ, const char* sK, const char* sV, const float* sBias, Keep keep, int qb, int nb, int lane,
+                                               int seq, int hd, SeqRows sr, int L, int H, float scale, float drop_scale, bf16_t* __restrict__ ctx,
+                                               bf16_t* __restrict__ ctx16, float* __restrict__ lse) {
+    const int r = lane & 31, h = lane >> 5;
+    bf16x8 qf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = row_frag(sQ, qb * 32 + r, s, h);
+    f32x16 S[NKB];
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+        if (kb >= nb) break;
+        S[kb] = (f32x16){0.f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            S[kb] = mfma32<F16>(row_frag(sK, kb * 32 + r, s, h), qf[s], S[kb]);
+        mfma_drain();
+    }
+    // S[kb][t] = <K[key], Q[q]> with key = 32 kb + rowmap(t, h), q = 32 qb + r
+    // softmax in the log2 domain (v_exp_f32 is 2^x): scores * scale * log2(e) + bias, bias read 4 keys at a time
+    // (keys rowmap(4u .. 4u+3, h) = 8u + 4h + 0..3 are consecutive)
+    const float scale2 = scale * LOG2E;
+    float mx = NEG_BIG * 4.f;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (kb >= nb) break;
+            const float4 b4 = *(const float4*)(sBias + kb * 32 + 8 * u + 4 * h);
+            const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+            for (int j = 0; j < 4; j += 2) {      // two keys per packed fp32 instruction (v_pk_fma_f32: same IEEE results as two v_fma_f32)
+                const cldrd_f32v2 v = fma2((cldrd_f32v2){S[kb][4 * u + j], S[kb][4 * u + j + 1]}, splat2(scale2), (cldrd_f32v2){bb[j], bb[j + 1]});
+                S[kb][4 * u + j] = v.x; S[kb][4 * u + j + 1] = v.y;
+                mx = fmaxf(mx, fmaxf(v.x, v.y));
+            }
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int t = 0; t < 16; t += 2) {
+            if (kb >= nb) break;
+            const cldrd_f32v2 d = (cldrd_f32v2){S[kb][t], S[kb][t + 1]} - splat2(mx);
+            const float e0 = __builtin_amdgcn_exp2f(d.x), e1 = __builtin_amdgcn_exp2f(d.y);
+            S[kb][t] = e0; S[kb][t + 1] = e1;
+            sum += e0;
+            sum += e1;
+        }
+    sum += __shfl_xor(sum, 32, 64);
+    const int q = qb * 32 + r;
+    store_lse(lse, seq, hd, H, L, q, h, mx, sum);
+    const float inv = 1.0f / sum;
+    // dropout mask element (row, col) = ((seq*H + hd)*L + q, key); keys rowmap(t, h), t even / odd, are a column pair
+    keep.row((uint32_t)((seq * H + hd) * L + q), q);
+    f32x16 O[2] = {(f32x16){0.f}, (f32x16){0.f}};
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+        if (kb >= nb) break;
+        float pv[16];
+#pragma unroll
+        for (int t = 0; t < 16; t += 2) {
+            cldrd_f32v2 p = (cldrd_f32v2){S[kb][t], S[kb][t + 1]} * splat2(inv);
+            if (DROP) {
+                p = p * splat2(drop_scale);
+                keep.pair(p, kb, t, h);
+            }
+            pv[t] = p.x; pv[t + 1] = p.y;
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            const bf16x8 pa = pack8x<F16>(pv + 8 * s2);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)      // operands swapped: O^T[d][q], so that a lane (= query) holds consecutive head dimensions
+                O[dt] = mfma32<F16>(tr_frag(sV, kb * 32 + 16 * s2 + 4 * h, dt * 32, lane), pa, O[dt]);
+        }
+        mfma_drain();
+    }
+    store_ctx_rows<F16, false>(O, 1.0f, ctx, ctx16, ((size_t)sr.row0 + q) * (H * 64) + hd * 64, h, q < sr.len);
+}
+
 // Forward with all the scores of a query block in registers (16 NKB accumulators): for L <= 128 this is ~7 % faster than the
 // streaming form below (16 score MFMAs back to back, one softmax pass, 16 P.V MFMAs) and is what the train step uses.
 template <int NKB, bool DROP, bool F16 = false>
@@ -162,140 +335,27 @@ __global__ __launch_bounds__(256) void attn_fwd_full_kernel(const bf16_t* __rest
     char* sV = sK + Lp * RSB;
     float* sBias = (float*)(sV + Lp * RSB);
     const int seq = seq_of(seq_list, blockIdx.x / H), hd = blockIdx.x % H;
-    const int dm = H * 64, ld = 3 * dm;
     const SeqRows sr = seq_rows(cu, seq, L);
-    const int len = sr.len;
-    const bf16_t* base = qkv + (size_t)sr.row0 * ld + hd * 64;
-    load_tile(sQ, base, ld, len, Lp);
-    load_tile(sK, base + dm, ld, len, Lp);
-    load_tile(sV, base + 2 * dm, ld, len, Lp);
-    for (int k = threadIdx.x; k < Lp; k += blockDim.x)
-        sBias[k] = (k < len && (!mask || mask[(size_t)seq * L + k] != 0)) ? 0.f : NEG_BIG;
+    load_item_tiles(sQ, sK, sV, qkv, hd, sr, H, Lp);
+    fill_key_bias(sBias, mask, seq, L, Lp, sr.len);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int nb = CLDRD_LIVE_BLOCKS(len, NKB);          // live blocks (see seq_rows)
+    const int nb = live_blocks(sr.len);
     for (int qb = wid; qb < NKB; qb += 4) {
-        if (qb >= nb) {       // a query block beyond the sequence: nothing to store but the LSE of its zero rows
-            const int q = qb * 32 + r;
-            if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (0.f + __log2f((float)len)) * LN2;
-            continue;
-        }
-        bf16x8 qf[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = row_frag(sQ, qb * 32 + r, s, h);
-        f32x16 S[NKB];
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            if (kb >= nb) break;
-            S[kb] = (f32x16){0.f};
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                S[kb] = mfma32<F16>(row_frag(sK, kb * 32 + r, s, h), qf[s], S[kb]);
-            mfma_drain();
-        }
-        // S[kb][t] = <K[key], Q[q]> with key = 32 kb + rowmap(t, h), q = 32 qb + r
-        // softmax in the log2 domain (v_exp_f32 is 2^x): scores * scale * log2(e) + bias, bias read 4 keys at a time
-        // (keys rowmap(4u .. 4u+3, h) = 8u + 4h + 0..3 are consecutive)
-        const float scale2 = scale * LOG2E;
-        float mx = NEG_BIG * 4.f;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (kb >= nb) break;
-                const float4 b4 = *(const float4*)(sBias + kb * 32 + 8 * u + 4 * h);
-                const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {      // two keys per packed fp32 instruction (v_pk_fma_f32: same IEEE results as two v_fma_f32)
-                    const cldrd_f32v2 v = fma2((cldrd_f32v2){S[kb][4 * u + j], S[kb][4 * u + j + 1]}, splat2(scale2), (cldrd_f32v2){bb[j], bb[j + 1]});
-                    S[kb][4 * u + j] = v.x; S[kb][4 * u + j + 1] = v.y;
-                    mx = fmaxf(mx, fmaxf(v.x, v.y));
-                }
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float sum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int t = 0; t < 16; t += 2) {
-                if (kb >= nb) break;
-                const cldrd_f32v2 d = (cldrd_f32v2){S[kb][t], S[kb][t + 1]} - splat2(mx);
-                const float e0 = __builtin_amdgcn_exp2f(d.x), e1 = __builtin_amdgcn_exp2f(d.y);
-                S[kb][t] = e0; S[kb][t + 1] = e1;
-                sum += e0;
-                sum += e1;
-            }
-        sum += __shfl_xor(sum, 32, 64);
-        const int q = qb * 32 + r;
-        if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (mx + __log2f(sum)) * LN2;
-        const float inv = 1.0f / sum;
-        // dropout mask element (row, col) = ((seq*H + hd)*L + q, key); keys rowmap(t, h), t even / odd, are a column pair
-        const uint32_t rk = drop_rowkey(seed, (uint32_t)((seq * H + hd) * L + q));
-        f32x16 O[2] = {(f32x16){0.f}, (f32x16){0.f}};
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            if (kb >= nb) break;
-            float pv[16];
-#pragma unroll
-            for (int t = 0; t < 16; t += 2) {
-                cldrd_f32v2 p = (cldrd_f32v2){S[kb][t], S[kb][t + 1]} * splat2(inv);
-                if (DROP) {
-                    const uint32_t hh = drop_pair(rk, (uint32_t)(kb * 32 + rowmap(t, h)));
-                    p = p * splat2(drop_scale);
-                    p.x = drop_keep_lo(hh, drop_thresh) ? p.x : 0.f;
-                    p.y = drop_keep_hi(hh, drop_thresh) ? p.y : 0.f;
-                }
-                pv[t] = p.x; pv[t + 1] = p.y;
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 pa = pack8x<F16>(pv + 8 * s2);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)      // operands swapped: O^T[d][q], so that a lane (= query) holds consecutive head dimensions
-                    O[dt] = mfma32<F16>(tr_frag(sV, kb * 32 + 16 * s2 + 4 * h, dt * 32, lane), pa, O[dt]);
-            }
-            mfma_drain();
-        }
-        // O[dt][t] = ctx^T[d = 32 dt + rowmap(t, h)][q = 32 qb + r]: registers 4u .. 4u+3 are 4 consecutive head dimensions of the lane's query row;
-        // one v_permlane32_swap pair makes them 16 contiguous bytes (widen_pair): 4 (+ 4 for the fp16 copy) 16-byte stores per lane instead of
-        // 32 (+ 32) two-byte ones.  (Round 2 tried the transposed form with 8-byte stores and found it 8 % slower; round 5, with the widened
-        // stores: profiles/r05_microbench.txt section 6.)
-        {
-            const size_t orow = ((size_t)sr.row0 + q) * dm + hd * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 o[2], o16[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int b = 4 * (u + k);
-                        o[k].x = pack2x<F16>(O[dt][b], O[dt][b + 1]);
-                        o[k].y = pack2x<F16>(O[dt][b + 2], O[dt][b + 3]);
-                        o16[k].x = (uint32_t)f2x<true>(O[dt][b]) | ((uint32_t)f2x<true>(O[dt][b + 1]) << 16);
-                        o16[k].y = (uint32_t)f2x<true>(O[dt][b + 2]) | ((uint32_t)f2x<true>(O[dt][b + 3]) << 16);
-                    }
-                    if (ctx) {       // ctx: the kernel's own format (may be absent); ctx16: an fp16 copy of a bf16 pass (out-projection operand)
-                        const uint4 w = widen_pair(o[0], o[1]);
-                        if (q < len) *(uint4*)(ctx + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                    if (ctx16) {
-                        const uint4 w = widen_pair(o16[0], o16[1]);
-                        if (q < len) *(uint4*)(ctx16 + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                }
-        }
+        if (qb >= nb)         // a query block beyond the sequence: nothing to store but the LSE of its zero rows
+            store_lse(lse, seq, hd, H, L, qb * 32 + (lane & 31), lane >> 5, 0.f, (float)sr.len);
+        else
+            fwd_full_block<NKB, DROP, F16>(sQ, sK, sV, sBias, KeepHash{seed, drop_thresh, 0u}, qb, nb, lane, seq, hd, sr, L, H, scale, drop_scale, ctx,
+                                           ctx16, lse);
     }
 }
 
-
-// Forward for L <= 128 and many (sequence, head) items: one persistent 8-wave workgroup per CU.  Waves 0..3 compute (the body of
-// attn_fwd_full_kernel, one query block each), waves 4..7 only move data: they issue the global loads of the NEXT item's Q, K, V into
-// registers, wait, and write them to the second LDS buffer - so an item's HBM latency sits under the previous item's arithmetic instead
-// of in front of its own (the kernel above does load -> barrier -> compute per workgroup and overlaps only across the two workgroups
-// a CU can hold).  One __syncthreads per item.
+// Forward for L <= 128 and many (sequence, head) items: one persistent 8-wave workgroup per CU.  Waves 0..3 compute (fwd_full_block, one
+// query block each; their keep decisions are the loader's bits in LDS), waves 4..7 only move data: they issue the global loads of the NEXT
+// item's Q, K, V into registers, wait, and write them to the second LDS buffer - so an item's HBM latency sits under the previous item's
+// arithmetic instead of in front of its own (the kernel above does load -> barrier -> compute per workgroup and overlaps only across the
+// two workgroups a CU can hold).  One __syncthreads per item.
 template <int NKB, bool DROP, bool F16 = false>
 __global__ __launch_bounds__(512) void attn_fwd2_kernel(const bf16_t* __restrict__ qkv, const int64_t* __restrict__ mask,
                                                          bf16_t* __restrict__ ctx, float* __restrict__ lse, int L, int H,
@@ -312,7 +372,7 @@ __global__ __launch_bounds__(512) void attn_fwd2_kernel(const bf16_t* __restrict
     const bool loader = wid >= 4;
     const int rw = wid & 3;
     const int dm = H * 64, ld = 3 * dm;
-    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };      // see attn_bwd2_kernel
+    auto opaque = [](int x) { asm volatile("" : "+v"(x)); return x; };      // keeps address halves from being hoisted out of the item loop: see attn_bwd2_kernel
     int tb = tid & 255;
     uint4 pq[NCH], pk[NCH], pv[NCH];
     float p_bias = 0.f;
@@ -380,123 +440,17 @@ __global__ __launch_bounds__(512) void attn_fwd2_kernel(const bf16_t* __restrict
         const uint32_t* sBits = (const uint32_t*)(sBias + Lp);
         const int seq = seq_of(seq_list, item / H), hd = item % H;
         const SeqRows sr = seq_rows(cu, seq, L);
-        const int len = sr.len, nb = CLDRD_LIVE_BLOCKS(len, NKB);
+        const int nb = live_blocks(sr.len);
         const int t_ = opaque(tid);
-        const int lane = t_ & 63, r = lane & 31, h = lane >> 5;
+        const int lane = t_ & 63;
         tb = t_ & 255;
         if (loader) {
             if (next < nitems) { issue(next); commit(cur ^ 1); make_bits(cur ^ 1, next); }
         } else if (rw < NKB && rw >= nb) {      // a query block beyond the sequence: nothing to store but the LSE of its zero rows
-            const int q = rw * 32 + r;
-            if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (0.f + __log2f((float)len)) * LN2;
+            store_lse(lse, seq, hd, H, L, rw * 32 + (lane & 31), lane >> 5, 0.f, (float)sr.len);
         } else if (rw < nb) {
-            const int qb = rw;
-        bf16x8 qf[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = row_frag(sQ, qb * 32 + r, s, h);
-        f32x16 S[NKB];
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            if (kb >= nb) break;
-            S[kb] = (f32x16){0.f};
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                S[kb] = mfma32<F16>(row_frag(sK, kb * 32 + r, s, h), qf[s], S[kb]);
-            mfma_drain();
+            fwd_full_block<NKB, DROP, F16>(sQ, sK, sV, sBias, KeepBits<Lp>{sBits, 0}, rw, nb, lane, seq, hd, sr, L, H, scale, drop_scale, ctx, ctx16, lse);
         }
-        // S[kb][t] = <K[key], Q[q]> with key = 32 kb + rowmap(t, h), q = 32 qb + r
-        // softmax in the log2 domain (v_exp_f32 is 2^x): scores * scale * log2(e) + bias, bias read 4 keys at a time
-        // (keys rowmap(4u .. 4u+3, h) = 8u + 4h + 0..3 are consecutive)
-        const float scale2 = scale * LOG2E;
-        float mx = NEG_BIG * 4.f;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (kb >= nb) break;
-                const float4 b4 = *(const float4*)(sBias + kb * 32 + 8 * u + 4 * h);
-                const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {      // two keys per packed fp32 instruction (v_pk_fma_f32: same IEEE results as two v_fma_f32)
-                    const cldrd_f32v2 v = fma2((cldrd_f32v2){S[kb][4 * u + j], S[kb][4 * u + j + 1]}, splat2(scale2), (cldrd_f32v2){bb[j], bb[j + 1]});
-                    S[kb][4 * u + j] = v.x; S[kb][4 * u + j + 1] = v.y;
-                    mx = fmaxf(mx, fmaxf(v.x, v.y));
-                }
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float sum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int t = 0; t < 16; t += 2) {
-                if (kb >= nb) break;
-                const cldrd_f32v2 d = (cldrd_f32v2){S[kb][t], S[kb][t + 1]} - splat2(mx);
-                const float e0 = __builtin_amdgcn_exp2f(d.x), e1 = __builtin_amdgcn_exp2f(d.y);
-                S[kb][t] = e0; S[kb][t + 1] = e1;
-                sum += e0;
-                sum += e1;
-            }
-        sum += __shfl_xor(sum, 32, 64);
-        const int q = qb * 32 + r;
-        if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (mx + __log2f(sum)) * LN2;
-        const float inv = 1.0f / sum;
-        // dropout mask element (row, col) = ((seq*H + hd)*L + q, key); keys rowmap(t, h), t even / odd, are a column pair
-        const uint32_t rk = drop_rowkey(seed, (uint32_t)((seq * H + hd) * L + q));
-        f32x16 O[2] = {(f32x16){0.f}, (f32x16){0.f}};
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            if (kb >= nb) break;
-            float pv[16];
-#pragma unroll
-            for (int t = 0; t < 16; t += 2) {
-                cldrd_f32v2 p = (cldrd_f32v2){S[kb][t], S[kb][t + 1]} * splat2(inv);
-                if (DROP) {       // keys rowmap(t, h), rowmap(t, h) + 1 of block kb: two adjacent bits of the loader's dword
-                    const uint32_t w = sBits[kb * Lp + q] >> (4 * h);
-                    p = p * splat2(drop_scale);
-                    p.x = keep_bit(p.x, w, rowmap(t, 0));
-                    p.y = keep_bit(p.y, w, rowmap(t, 0) + 1);
-                }
-                pv[t] = p.x; pv[t + 1] = p.y;
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 pa = pack8x<F16>(pv + 8 * s2);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)      // operands swapped: O^T[d][q], so that a lane (= query) holds consecutive head dimensions
-                    O[dt] = mfma32<F16>(tr_frag(sV, kb * 32 + 16 * s2 + 4 * h, dt * 32, lane), pa, O[dt]);
-            }
-            mfma_drain();
-        }
-        // O[dt][t] = ctx^T[d = 32 dt + rowmap(t, h)][q = 32 qb + r]: registers 4u .. 4u+3 are 4 consecutive head dimensions of the lane's query row;
-        // one v_permlane32_swap pair makes them 16 contiguous bytes (widen_pair): 4 (+ 4 for the fp16 copy) 16-byte stores per lane instead of
-        // 32 (+ 32) two-byte ones.  (Round 2 tried the transposed form with 8-byte stores and found it 8 % slower; round 5, with the widened
-        // stores: profiles/r05_microbench.txt section 6.)
-        {
-            const size_t orow = ((size_t)sr.row0 + q) * dm + hd * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 o[2], o16[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int b = 4 * (u + k);
-                        o[k].x = pack2x<F16>(O[dt][b], O[dt][b + 1]);
-                        o[k].y = pack2x<F16>(O[dt][b + 2], O[dt][b + 3]);
-                        o16[k].x = (uint32_t)f2x<true>(O[dt][b]) | ((uint32_t)f2x<true>(O[dt][b + 1]) << 16);
-                        o16[k].y = (uint32_t)f2x<true>(O[dt][b + 2]) | ((uint32_t)f2x<true>(O[dt][b + 3]) << 16);
-                    }
-                    if (ctx) {       // ctx: the kernel's own format (may be absent); ctx16: an fp16 copy of a bf16 pass (out-projection operand)
-                        const uint4 w = widen_pair(o[0], o[1]);
-                        if (q < len) *(uint4*)(ctx + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                    if (ctx16) {
-                        const uint4 w = widen_pair(o16[0], o16[1]);
-                        if (q < len) *(uint4*)(ctx16 + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                }
-        }
-            }
         __syncthreads();          // the other buffer is complete, and nobody reads this one any more
         cur ^= 1;
     }
@@ -509,6 +463,9 @@ __global__ __launch_bounds__(512) void attn_fwd2_kernel(const bf16_t* __restrict
 // output is accumulated TRANSPOSED (lane = query column, registers = head dimension): no cross-lane traffic but one
 // shuffle per block, and 16 + 32 accumulator registers whatever L is (the first version kept all of S in registers:
 // 16 NKB of them, which spilled from L = 192 up and ran 2x slower at L = 256).
+// The two streaming kernels share their prologue and stores with the rest of the file but each keeps this loop in its own text: as one function called
+// by both, attn_fwd3_kernel<8, false> (the index encode at L = 256) measured 1.3 % slower than before, several times its run-to-run spread
+// (profiles/attention_shared_bodies.txt).  A change to the loop goes into both; the tests hold the pair to bit equality.
 template <int NKB, bool DROP, bool F16 = false>
 __global__ __launch_bounds__(NKB > 4 ? 512 : 256) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, const int64_t* __restrict__ mask,
                                                         bf16_t* __restrict__ ctx, float* __restrict__ lse, int L, int H,
@@ -523,27 +480,21 @@ __global__ __launch_bounds__(NKB > 4 ? 512 : 256) void attn_fwd_kernel(const bf1
     char* sV = sK + Lp * RSB;
     float* sBias = (float*)(sV + Lp * RSB);
     const int seq = seq_of(seq_list, blockIdx.x / H), hd = blockIdx.x % H;
-    const int dm = H * 64, ld = 3 * dm;
     const SeqRows sr = seq_rows(cu, seq, L);
-    const int len = sr.len;
-    const bf16_t* base = qkv + (size_t)sr.row0 * ld + hd * 64;
-    load_tile(sQ, base, ld, len, Lp);
-    load_tile(sK, base + dm, ld, len, Lp);
-    load_tile(sV, base + 2 * dm, ld, len, Lp);
-    for (int k = threadIdx.x; k < Lp; k += blockDim.x)
-        sBias[k] = (k < len && (!mask || mask[(size_t)seq * L + k] != 0)) ? 0.f : NEG_BIG;
+    load_item_tiles(sQ, sK, sV, qkv, hd, sr, H, Lp);
+    fill_key_bias(sBias, mask, seq, L, Lp, sr.len);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     const float scale2 = scale * LOG2E;      // scores in the log2 domain (v_exp_f32 is 2^x)
-    const int nb = CLDRD_LIVE_BLOCKS(len, NKB);          // live blocks (see seq_rows)
+    const int nb = live_blocks(sr.len);
     for (int qb = wid; qb < NKB; qb += NWAVES) {
-        const int q = qb * 32 + r;
         if (qb >= nb) {       // a query block beyond the sequence: nothing to store but the LSE of its zero rows
-            if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (0.f + __log2f((float)len)) * LN2;
+            store_lse(lse, seq, hd, H, L, qb * 32 + r, h, 0.f, (float)sr.len);
             continue;
         }
+        const int q = qb * 32 + r;
         bf16x8 qf[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = row_frag(sQ, qb * 32 + r, s, h);
@@ -607,34 +558,9 @@ __global__ __launch_bounds__(NKB > 4 ? 512 : 256) void attn_fwd_kernel(const bf1
             mfma_drain();
         }
         const float l = lsum + __shfl_xor(lsum, 32, 64);
-        if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (m + __log2f(l)) * LN2;
+        store_lse(lse, seq, hd, H, L, q, h, m, l);
         const float inv = (DROP ? drop_scale : 1.0f) / l;
-        {
-            const size_t orow = ((size_t)sr.row0 + q) * dm + hd * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 o[2], o16[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int b = 4 * (u + k);
-                        const float v0 = O[dt][b] * inv, v1 = O[dt][b + 1] * inv, v2 = O[dt][b + 2] * inv, v3 = O[dt][b + 3] * inv;
-                        o[k].x = pack2x<F16>(v0, v1);
-                        o[k].y = pack2x<F16>(v2, v3);
-                        o16[k].x = (uint32_t)f2x<true>(v0) | ((uint32_t)f2x<true>(v1) << 16);
-                        o16[k].y = (uint32_t)f2x<true>(v2) | ((uint32_t)f2x<true>(v3) << 16);
-                    }
-                    if (ctx) {
-                        const uint4 w = widen_pair(o[0], o[1]);
-                        if (q < len) *(uint4*)(ctx + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                    if (ctx16) {       // fp16 copy (out-projection operand)
-                        const uint4 w = widen_pair(o16[0], o16[1]);
-                        if (q < len) *(uint4*)(ctx16 + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                }
-        }
+        store_ctx_rows<F16, true>(O, inv, ctx, ctx16, ((size_t)sr.row0 + q) * (H * 64) + hd * 64, h, q < sr.len);
     }
 }
 
@@ -646,7 +572,9 @@ __global__ __launch_bounds__(NKB > 4 ? 512 : 256) void attn_fwd_kernel(const bf1
 //   * K, V (+ the key bias) are double-buffered in LDS (2 x 74 KB): each thread requests its 16-byte pieces of the NEXT item into registers
 //     before it starts on the current item (issue early), and writes them to the other buffer when it is done (write late): an item's HBM
 //     latency sits under the previous item's arithmetic; one __syncthreads per item;
-//   * the body is attn_fwd_kernel's, instruction for instruction (same results bit for bit: tests flip cldrd_set_tuning("attn_fwd2", 0)).
+//   * the block loop is attn_fwd_kernel's, one query block per wave, its Q fragments taken from the prefetch registers.  It is written out here a
+//     second time: as one function called by both kernels it made this kernel 1.3 % slower at L = 256 without dropout (the index encode;
+//     profiles/attention_shared_bodies.txt).  Change the two loops together; test_attention_fwd_persistent_kernels_at_block_boundaries compares them.
 template <int NKB, bool DROP, bool F16 = false>
 __global__ __launch_bounds__(512) void attn_fwd3_kernel(const bf16_t* __restrict__ qkv, const int64_t* __restrict__ mask,
                                                          bf16_t* __restrict__ ctx, float* __restrict__ lse, int L, int H,
@@ -727,12 +655,11 @@ __global__ __launch_bounds__(512) void attn_fwd3_kernel(const bf16_t* __restrict
         const float* sBias = (const float*)(sV + TILE);
         const int seq = seq_of(seq_list, item / H), hd = item % H;
         const SeqRows sr = seq_rows(cu, seq, L);
-        const int len = sr.len, nb = CLDRD_LIVE_BLOCKS(len, NKB);
+        const int nb = live_blocks(sr.len);
         const int lane = tid & 63, wid = tid >> 6;
         const int r = lane & 31, h = lane >> 5;
         if (wid < NKB && wid >= nb) {          // a query block beyond the sequence: nothing to store but the LSE of its zero rows (see seq_rows)
-            const int q = wid * 32 + r;
-            if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (0.f + __log2f((float)len)) * LN2;
+            store_lse(lse, seq, hd, H, L, wid * 32 + r, h, 0.f, (float)sr.len);
         } else if (wid < nb) {
             const int qb = wid;
             const int q = qb * 32 + r;
@@ -795,32 +722,9 @@ __global__ __launch_bounds__(512) void attn_fwd3_kernel(const bf16_t* __restrict
                 mfma_drain();
             }
             const float l = lsum + __shfl_xor(lsum, 32, 64);
-            if (h == 0 && q < L && lse) lse[((size_t)seq * H + hd) * L + q] = (m + __log2f(l)) * LN2;
+            store_lse(lse, seq, hd, H, L, q, h, m, l);
             const float inv = (DROP ? drop_scale : 1.0f) / l;
-            const size_t orow = ((size_t)sr.row0 + q) * dm + hd * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 o[2], o16[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int b = 4 * (u + k);
-                        const float v0 = O[dt][b] * inv, v1 = O[dt][b + 1] * inv, v2 = O[dt][b + 2] * inv, v3 = O[dt][b + 3] * inv;
-                        o[k].x = pack2x<F16>(v0, v1);
-                        o[k].y = pack2x<F16>(v2, v3);
-                        o16[k].x = (uint32_t)f2x<true>(v0) | ((uint32_t)f2x<true>(v1) << 16);
-                        o16[k].y = (uint32_t)f2x<true>(v2) | ((uint32_t)f2x<true>(v3) << 16);
-                    }
-                    if (ctx) {
-                        const uint4 w = widen_pair(o[0], o[1]);
-                        if (q < len) *(uint4*)(ctx + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                    if (ctx16) {       // fp16 copy (out-projection operand)
-                        const uint4 w = widen_pair(o16[0], o16[1]);
-                        if (q < len) *(uint4*)(ctx16 + orow + dt * 32 + 8 * (u + h)) = w;
-                    }
-                }
+            store_ctx_rows<F16, true>(O, inv, ctx, ctx16, ((size_t)sr.row0 + q) * (H * 64) + hd * 64, h, q < sr.len);
         }
         commit(cur ^ 1);
 #pragma unroll
@@ -828,6 +732,188 @@ __global__ __launch_bounds__(512) void attn_fwd3_kernel(const bf16_t* __restrict
         __syncthreads();          // the other buffer is complete, and nobody reads this one any more
         cur ^= 1;
     }
+}
+
+// The backward's view of an item in LDS: Q, K, V, dO tiles; per key the mask bias; per query the LSE (log2 domain), delta = rowsum(dO . O) and the dropout
+// row key; sBits (BITS only): the forward's keep bits, dword [kb][q].
+struct BwdTiles {
+    const char *sQ, *sK, *sV, *sdO;
+    const float *sBias, *sLse, *sDelta;
+    const uint32_t *sRk, *sBits;
+};
+// What a wave holds for the whole of a sweep: its 32 keys (sweep A: K and V rows, mask bias) or its 32 queries (sweep B: Q and dO rows, LSE, delta, row key)
+struct BwdKeyRows { bf16x8 kf[4], vf[4]; float bias_k; };
+struct BwdQueryRows { bf16x8 qf[4], dof[4]; float lse_q, delta_q; uint32_t rk_q; };
+__device__ __forceinline__ void bwd_load_keys(const BwdTiles& T, int kb, int lane, BwdKeyRows& K) {
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) { K.kf[s] = row_frag(T.sK, kb * 32 + r, s, h); K.vf[s] = row_frag(T.sV, kb * 32 + r, s, h); }
+    K.bias_k = T.sBias[kb * 32 + r];
+}
+__device__ __forceinline__ void bwd_load_queries(const BwdTiles& T, int qb, int lane, BwdQueryRows& Q) {
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) { Q.qf[s] = row_frag(T.sQ, qb * 32 + r, s, h); Q.dof[s] = row_frag(T.sdO, qb * 32 + r, s, h); }
+    const int q = qb * 32 + r;
+    Q.lse_q = T.sLse[q]; Q.delta_q = T.sDelta[q];
+    Q.rk_q = T.sRk[q];
+}
+
+// Sweep A, one query block qb against the wave's key block kb (key on lane): S and dP, P / dP / dS per element, dV += P_drop^T dO, dK += dS^T Q.
+// The block loop, and the mfma_drain() that a loop with a run-time count needs, stay with the kernel: attn_bwd_kernel unrolls over NKB (padded)
+// or rolls to nb (VARLEN), attn_bwd2_kernel rolls to nb.  BITS: the keep decision is bit `r` of the forward's dword instead of the hash.
+template <int NKB, bool DROP, bool BITS, bool F16>
+__device__ __forceinline__ void bwd_key_step(const BwdTiles& T, const BwdKeyRows& K, int qb, int kb, int lane, float scale2, uint32_t drop_thresh,
+                                             float drop_scale, f32x16 (&dK)[2], f32x16 (&dV)[2]) {
+    constexpr int Lp = 32 * NKB;
+    const int r = lane & 31, h = lane >> 5, key = kb * 32 + r;
+    f32x16 S = (f32x16){0.f}, dP = (f32x16){0.f};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        S = mfma32<F16>(row_frag(T.sQ, qb * 32 + r, s, h), K.kf[s], S);
+        dP = mfma32<F16>(row_frag(T.sdO, qb * 32 + r, s, h), K.vf[s], dP);
+    }
+    // S[t], dP[t]: query q = 32 qb + rowmap(t, h), key = 32 kb + r
+    float pd[16], ds[16];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        // queries rowmap(4u .. 4u+3, h) are consecutive: their LSE / delta / dropout row keys come as 16-byte LDS reads
+        const int q4 = qb * 32 + 8 * u + 4 * h;
+        const float4 l4 = *(const float4*)(T.sLse + q4), d4 = *(const float4*)(T.sDelta + q4);
+        const float ll[4] = {l4.x, l4.y, l4.z, l4.w}, dd[4] = {d4.x, d4.y, d4.z, d4.w};
+        uint4 k4 = make_uint4(0, 0, 0, 0);
+        if (DROP) k4 = BITS ? *(const uint4*)(T.sBits + kb * Lp + q4) : *(const uint4*)(T.sRk + q4);      // BITS: dwords [kb][q4 .. q4+3], bit = key
+        const uint32_t kk[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {      // two queries per packed fp32 instruction (the same IEEE operations as the scalar form)
+            const int t = 4 * u + j;
+            const cldrd_f32v2 a2 = fma2((cldrd_f32v2){S[t], S[t + 1]}, splat2(scale2), splat2(K.bias_k)) - (cldrd_f32v2){ll[j], ll[j + 1]};
+            const cldrd_f32v2 p2 = {__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
+            cldrd_f32v2 pd2 = p2, dp2 = {dP[t], dP[t + 1]};
+            if (DROP) {
+                pd2 = p2 * splat2(drop_scale);
+                dp2 = dp2 * splat2(drop_scale);
+                if constexpr (BITS) {
+                    pd2.x = keep_bit(pd2.x, kk[j], r); pd2.y = keep_bit(pd2.y, kk[j + 1], r);
+                    dp2.x = keep_bit(dp2.x, kk[j], r); dp2.y = keep_bit(dp2.y, kk[j + 1], r);
+                } else {
+                    const bool keep0 = dropout_keep(kk[j], (uint32_t)key, drop_thresh), keep1 = dropout_keep(kk[j + 1], (uint32_t)key, drop_thresh);
+                    pd2.x = keep0 ? pd2.x : 0.f; pd2.y = keep1 ? pd2.y : 0.f;
+                    dp2.x = keep0 ? dp2.x : 0.f; dp2.y = keep1 ? dp2.y : 0.f;
+                }
+            }
+            pd[t] = pd2.x; pd[t + 1] = pd2.y;
+            const cldrd_f32v2 ds2 = p2 * (dp2 - (cldrd_f32v2){dd[j], dd[j + 1]});
+            ds[t] = ds2.x; ds[t + 1] = ds2.y;
+        }
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+        const bf16x8 pb = pack8x<F16>(pd + 8 * s2), sb = pack8x<F16>(ds + 8 * s2);
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+            dV[dt] = mfma32<F16>(tr_frag(T.sdO, qb * 32 + 16 * s2 + 4 * h, dt * 32, lane), pb, dV[dt]);
+            dK[dt] = mfma32<F16>(tr_frag(T.sQ, qb * 32 + 16 * s2 + 4 * h, dt * 32, lane), sb, dK[dt]);
+        }
+    }
+}
+
+// Sweep B, one key block kb against the wave's query block qb (query on lane): S^T and dP^T, dS per element, dQ += dS K.  Loop and drain: as for sweep A.
+// BITS: the keep decisions of the lane's query are the forward's dword [kb][q], shifted to the lane's half.
+template <int NKB, bool DROP, bool BITS, bool F16>
+__device__ __forceinline__ void bwd_query_step(const BwdTiles& T, const BwdQueryRows& Q, int kb, int qb, int lane, float scale2, uint32_t drop_thresh,
+                                               float drop_scale, f32x16 (&dQ)[2]) {
+    constexpr int Lp = 32 * NKB;
+    const int r = lane & 31, h = lane >> 5, q = qb * 32 + r;
+    f32x16 ST = (f32x16){0.f}, dPT = (f32x16){0.f};
+    uint32_t wbits = 0;
+    if constexpr (BITS) wbits = T.sBits[kb * Lp + q] >> (4 * h);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        ST = mfma32<F16>(row_frag(T.sK, kb * 32 + r, s, h), Q.qf[s], ST);
+        dPT = mfma32<F16>(row_frag(T.sV, kb * 32 + r, s, h), Q.dof[s], dPT);
+    }
+    float ds[16];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int key4 = kb * 32 + 8 * u + 4 * h;
+        const float4 b4 = *(const float4*)(T.sBias + key4);
+        const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {
+            const int t = 4 * u + j;
+            // packed fp32 (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32: two keys per instruction, the same IEEE operations as before)
+            const cldrd_f32v2 a2 = fma2((cldrd_f32v2){ST[t], ST[t + 1]}, splat2(scale2), (cldrd_f32v2){bb[j], bb[j + 1]}) - splat2(Q.lse_q);
+            const cldrd_f32v2 p2 = {__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
+            cldrd_f32v2 dp2 = {dPT[t], dPT[t + 1]};
+            if (DROP) dp2 = dp2 * splat2(drop_scale);
+            float dp0 = dp2.x, dp1 = dp2.y;
+            if (DROP) {
+                if constexpr (BITS) {       // keys key4 + j, key4 + j + 1: adjacent bits of the forward's dword [kb][q]
+                    dp0 = keep_bit(dp0, wbits, 8 * u + j);
+                    dp1 = keep_bit(dp1, wbits, 8 * u + j + 1);
+                } else {
+                    const uint32_t hh = drop_pair(Q.rk_q, (uint32_t)(key4 + j));
+                    dp0 = drop_keep_lo(hh, drop_thresh) ? dp0 : 0.f;
+                    dp1 = drop_keep_hi(hh, drop_thresh) ? dp1 : 0.f;
+                }
+            }
+            const cldrd_f32v2 ds2 = p2 * ((cldrd_f32v2){dp0, dp1} - splat2(Q.delta_q));
+            ds[t] = ds2.x; ds[t + 1] = ds2.y;
+        }
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+        const bf16x8 sa = pack8x<F16>(ds + 8 * s2);
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+            // operands swapped: D[d][q], so a lane (= query) ends up with 4 consecutive head dimensions per register quad and dQ
+            // leaves in 8-byte stores (the other order gave 32 two-byte stores per lane)
+            dQ[dt] = mfma32<F16>(tr_frag(T.sK, kb * 32 + 16 * s2 + 4 * h, dt * 32, lane), sa, dQ[dt]);
+    }
+}
+
+// dK (x scale) and dV rows of a key block, at ok / ov (the lane's key row).  dV[dt][t] = dV[key][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
+template <bool F16>
+__device__ __forceinline__ void store_dkdv(const f32x16 (&dK)[2], const f32x16 (&dV)[2], float scale, bf16_t* ok, bf16_t* ov, int h, bool live) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int u = 0; u < 4; u += 2) {
+            uint2 a[2], b[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int t = 4 * (u + k);
+                a[k].x = pack2x_scaled<F16>(dK[dt][t], dK[dt][t + 1], scale);
+                a[k].y = pack2x_scaled<F16>(dK[dt][t + 2], dK[dt][t + 3], scale);
+                b[k].x = pack2x<F16>(dV[dt][t], dV[dt][t + 1]);
+                b[k].y = pack2x<F16>(dV[dt][t + 2], dV[dt][t + 3]);
+            }
+            const uint4 wa = widen_pair(a[0], a[1]), wb = widen_pair(b[0], b[1]);      // 16 contiguous bytes per lane (see widen_pair)
+            const int d0 = dt * 32 + 8 * (u + h);
+            if (live) {
+                *(uint4*)(ok + d0) = wa;
+                *(uint4*)(ov + d0) = wb;
+            }
+        }
+}
+// dQ (x scale) rows of a query block, at oq (the lane's query row).  dQ[dt][t] = dQ[q][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
+template <bool F16>
+__device__ __forceinline__ void store_dq(const f32x16 (&dQ)[2], float scale, bf16_t* oq, int h, bool live) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int u = 0; u < 4; u += 2) {
+            uint2 a[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int t = 4 * (u + k);
+                a[k].x = pack2x_scaled<F16>(dQ[dt][t], dQ[dt][t + 1], scale);
+                a[k].y = pack2x_scaled<F16>(dQ[dt][t + 2], dQ[dt][t + 3], scale);
+            }
+            const uint4 w = widen_pair(a[0], a[1]);
+            if (live) *(uint4*)(oq + dt * 32 + 8 * (u + h)) = w;
+        }
 }
 
 // VARLEN (a packed batch, launch_bwd_d): the two block loops are ROLLED and run over the live blocks only - a sequence of 74 tokens at L = 256 does
@@ -855,10 +941,7 @@ __global__ __launch_bounds__(NKB > 4 ? 512 : 256) void attn_bwd_kernel(const bf1
     const int dm = H * 64, ld = 3 * dm;
     const SeqRows sr = seq_rows(cu, seq, L);
     const int len = sr.len;
-    const bf16_t* base = qkv + (size_t)sr.row0 * ld + hd * 64;
-    load_tile(sQ, base, ld, len, Lp);
-    load_tile(sK, base + dm, ld, len, Lp);
-    load_tile(sV, base + 2 * dm, ld, len, Lp);
+    load_item_tiles(sQ, sK, sV, qkv, hd, sr, H, Lp);
     {   // dO tile + delta[q] = sum_d dO[q][d] * O[q][d]
         const bf16_t* dob = dctx + (size_t)sr.row0 * dm + hd * 64;
         const bf16_t* ob = ctx + (size_t)sr.row0 * dm + hd * 64;
@@ -879,175 +962,51 @@ __global__ __launch_bounds__(NKB > 4 ? 512 : 256) void attn_bwd_kernel(const bf1
         }
     }
     for (int k = threadIdx.x; k < Lp; k += blockDim.x) {
-        sBias[k] = (k < len && (!mask || mask[(size_t)seq * L + k] != 0)) ? 0.f : NEG_BIG;
+        sBias[k] = key_bias(mask, seq, L, k, len);
         sLse[k] = k < L ? lse[((size_t)seq * H + hd) * L + k] * LOG2E : 1.0e30f;      // log2 domain; rows >= L: P = 2^-inf = 0
         sRk[k] = drop_rowkey(seed, (uint32_t)((seq * H + hd) * L + k));
     }
     __syncthreads();
+    const BwdTiles T = {sQ, sK, sV, sdO, sBias, sLse, sDelta, sRk, nullptr};
 
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
 
     const float scale2 = scale * LOG2E;      // scores, mask bias and LSE live in the log2 domain (v_exp_f32 is 2^x)
 
-    const int nb = CLDRD_LIVE_BLOCKS(len, NKB);          // live blocks (see seq_rows): whole waves are skipped; inside a live wave the padded
+    const int nb = live_blocks(len);          // live blocks (see seq_rows): whole waves are skipped; inside a live wave the padded
                                              // instantiation's block loops stay unrolled over all NKB blocks (an early exit from an unrolled
                                              // loop cost 40-90 VGPRs and spilled from NKB = 5 up), the VARLEN one's are rolled and stop at nb
     const int nbl = VARLEN ? nb : NKB;
     // ---------------- sweep A: key on lane; dK, dV for 32 keys accumulate over all query blocks ----------------
     for (int kb = wid; kb < NKB; kb += NWAVES) {
         if (kb >= nb) continue;
-        bf16x8 kf[4], vf[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { kf[s] = row_frag(sK, kb * 32 + r, s, h); vf[s] = row_frag(sV, kb * 32 + r, s, h); }
-        const int key = kb * 32 + r;
-        const float bias_k = sBias[key];
+        BwdKeyRows K;
+        bwd_load_keys(T, kb, lane, K);
         f32x16 dK[2] = {(f32x16){0.f}, (f32x16){0.f}}, dV[2] = {(f32x16){0.f}, (f32x16){0.f}};
 #pragma unroll (VARLEN ? 1 : NKB)
         for (int qb = 0; qb < nbl; ++qb) {
-            f32x16 S = (f32x16){0.f}, dP = (f32x16){0.f};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                S = mfma32<F16>(row_frag(sQ, qb * 32 + r, s, h), kf[s], S);
-                dP = mfma32<F16>(row_frag(sdO, qb * 32 + r, s, h), vf[s], dP);
-            }
-            // S[t], dP[t]: query q = 32 qb + rowmap(t, h), key = 32 kb + r
-            float pd[16], ds[16];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                // queries rowmap(4u .. 4u+3, h) are consecutive: their LSE / delta / dropout row keys come as 16-byte LDS reads
-                const int q4 = qb * 32 + 8 * u + 4 * h;
-                const float4 l4 = *(const float4*)(sLse + q4), d4 = *(const float4*)(sDelta + q4);
-                const float ll[4] = {l4.x, l4.y, l4.z, l4.w}, dd[4] = {d4.x, d4.y, d4.z, d4.w};
-                uint4 k4 = make_uint4(0, 0, 0, 0);
-                if (DROP) k4 = *(const uint4*)(sRk + q4);
-                const uint32_t kk[4] = {k4.x, k4.y, k4.z, k4.w};
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {      // two queries per packed fp32 instruction (the same IEEE operations as the scalar form)
-                    const int t = 4 * u + j;
-                    const cldrd_f32v2 a2 = fma2((cldrd_f32v2){S[t], S[t + 1]}, splat2(scale2), splat2(bias_k)) - (cldrd_f32v2){ll[j], ll[j + 1]};
-                    const cldrd_f32v2 p2 = {__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
-                    cldrd_f32v2 pd2 = p2, dp2 = {dP[t], dP[t + 1]};
-                    if (DROP) {
-                        const bool keep0 = dropout_keep(kk[j], (uint32_t)key, drop_thresh), keep1 = dropout_keep(kk[j + 1], (uint32_t)key, drop_thresh);
-                        pd2 = p2 * splat2(drop_scale);
-                        dp2 = dp2 * splat2(drop_scale);
-                        pd2.x = keep0 ? pd2.x : 0.f; pd2.y = keep1 ? pd2.y : 0.f;
-                        dp2.x = keep0 ? dp2.x : 0.f; dp2.y = keep1 ? dp2.y : 0.f;
-                    }
-                    pd[t] = pd2.x; pd[t + 1] = pd2.y;
-                    const cldrd_f32v2 ds2 = p2 * (dp2 - (cldrd_f32v2){dd[j], dd[j + 1]});
-                    ds[t] = ds2.x; ds[t + 1] = ds2.y;
-                }
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 pb = pack8x<F16>(pd + 8 * s2), sb = pack8x<F16>(ds + 8 * s2);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    dV[dt] = mfma32<F16>(tr_frag(sdO, qb * 32 + 16 * s2 + 4 * h, dt * 32, lane), pb, dV[dt]);
-                    dK[dt] = mfma32<F16>(tr_frag(sQ, qb * 32 + 16 * s2 + 4 * h, dt * 32, lane), sb, dK[dt]);
-                }
-            }
+            bwd_key_step<NKB, DROP, false, F16>(T, K, qb, kb, lane, scale2, drop_thresh, drop_scale, dK, dV);
             if (VARLEN) mfma_drain();
         }
-        // dV[dt][t] = dV[key][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
-        {
-            bf16_t* ok = dqkv + ((size_t)sr.row0 + key) * ld + dm + hd * 64;
-            bf16_t* ov = ok + dm;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 a[2], b[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int t = 4 * (u + k);
-                        a[k].x = pack2x_scaled<F16>(dK[dt][t], dK[dt][t + 1], scale);
-                        a[k].y = pack2x_scaled<F16>(dK[dt][t + 2], dK[dt][t + 3], scale);
-                        b[k].x = pack2x<F16>(dV[dt][t], dV[dt][t + 1]);
-                        b[k].y = pack2x<F16>(dV[dt][t + 2], dV[dt][t + 3]);
-                    }
-                    const uint4 wa = widen_pair(a[0], a[1]), wb = widen_pair(b[0], b[1]);      // 16 contiguous bytes per lane (see widen_pair)
-                    const int d0 = dt * 32 + 8 * (u + h);
-                    if (key < len) {
-                        *(uint4*)(ok + d0) = wa;
-                        *(uint4*)(ov + d0) = wb;
-                    }
-                }
-        }
+        const int key = kb * 32 + r;
+        bf16_t* ok = dqkv + ((size_t)sr.row0 + key) * ld + dm + hd * 64;
+        store_dkdv<F16>(dK, dV, scale, ok, ok + dm, h, key < len);
     }
 
     // ---------------- sweep B: query on lane; dQ for 32 queries accumulates over all key blocks ----------------
     for (int qb = wid; qb < NKB; qb += NWAVES) {
         if (qb >= nb) continue;
-        bf16x8 qf[4], dof[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { qf[s] = row_frag(sQ, qb * 32 + r, s, h); dof[s] = row_frag(sdO, qb * 32 + r, s, h); }
-        const int q = qb * 32 + r;
-        const float lse_q = sLse[q], delta_q = sDelta[q];
-        const uint32_t rk_q = sRk[q];
+        BwdQueryRows Q;
+        bwd_load_queries(T, qb, lane, Q);
         f32x16 dQ[2] = {(f32x16){0.f}, (f32x16){0.f}};
 #pragma unroll (VARLEN ? 1 : NKB)
         for (int kb = 0; kb < nbl; ++kb) {
-            f32x16 ST = (f32x16){0.f}, dPT = (f32x16){0.f};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                ST = mfma32<F16>(row_frag(sK, kb * 32 + r, s, h), qf[s], ST);
-                dPT = mfma32<F16>(row_frag(sV, kb * 32 + r, s, h), dof[s], dPT);
-            }
-            float ds[16];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int key4 = kb * 32 + 8 * u + 4 * h;
-                const float4 b4 = *(const float4*)(sBias + key4);
-                const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {
-                    const int t = 4 * u + j;
-                    // packed fp32 (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32: two keys per instruction, the same IEEE operations as before)
-                    const cldrd_f32v2 a2 = fma2((cldrd_f32v2){ST[t], ST[t + 1]}, splat2(scale2), (cldrd_f32v2){bb[j], bb[j + 1]}) - splat2(lse_q);
-                    const cldrd_f32v2 p2 = {__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
-                    cldrd_f32v2 dp2 = {dPT[t], dPT[t + 1]};
-                    if (DROP) dp2 = dp2 * splat2(drop_scale);
-                    float dp0 = dp2.x, dp1 = dp2.y;
-                    if (DROP) {
-                        const uint32_t hh = drop_pair(rk_q, (uint32_t)(key4 + j));
-                        dp0 = drop_keep_lo(hh, drop_thresh) ? dp0 : 0.f;
-                        dp1 = drop_keep_hi(hh, drop_thresh) ? dp1 : 0.f;
-                    }
-                    const cldrd_f32v2 ds2 = p2 * ((cldrd_f32v2){dp0, dp1} - splat2(delta_q));
-                    ds[t] = ds2.x; ds[t + 1] = ds2.y;
-                }
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 sa = pack8x<F16>(ds + 8 * s2);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)
-                    // operands swapped: D[d][q], so a lane (= query) ends up with 4 consecutive head dimensions per register quad and dQ
-                    // leaves in 8-byte stores (the other order gave 32 two-byte stores per lane)
-                    dQ[dt] = mfma32<F16>(tr_frag(sK, kb * 32 + 16 * s2 + 4 * h, dt * 32, lane), sa, dQ[dt]);
-            }
+            bwd_query_step<NKB, DROP, false, F16>(T, Q, kb, qb, lane, scale2, drop_thresh, drop_scale, dQ);
             if (VARLEN) mfma_drain();
         }
-        {                 // dQ[dt][t] = dQ[q][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
-            bf16_t* oq = dqkv + ((size_t)sr.row0 + q) * ld + hd * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 a[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int t = 4 * (u + k);
-                        a[k].x = pack2x_scaled<F16>(dQ[dt][t], dQ[dt][t + 1], scale);
-                        a[k].y = pack2x_scaled<F16>(dQ[dt][t + 2], dQ[dt][t + 3], scale);
-                    }
-                    const uint4 w = widen_pair(a[0], a[1]);
-                    if (q < len) *(uint4*)(oq + dt * 32 + 8 * (u + h)) = w;
-                }
-        }
+        const int q = qb * 32 + r;
+        store_dq<F16>(dQ, scale, dqkv + ((size_t)sr.row0 + q) * ld + hd * 64, h, q < len);
     }
 }
 
@@ -1061,7 +1020,8 @@ __global__ __launch_bounds__(NKB > 4 ? 512 : 256) void attn_bwd_kernel(const bf1
 //   * waves 4..7 first issue the global loads of the NEXT item into registers (Q, K, V, dO, O: 80 VGPRs), run their sweep, then
 //     write them to the other LDS buffer (with delta, mask bias, LSE, dropout row keys): issue-early / write-late, the HBM latency
 //     sits under the sweep;  one __syncthreads per item.
-// The sweeps are the code of attn_bwd_kernel with the block loops rolled (the prefetch registers need the room).
+// The sweeps are attn_bwd_kernel's (bwd_key_step / bwd_query_step and their loads and stores); this form adds the roles, the prefetch, the forward's
+// keep bits (BITS), and block loops that are always rolled and stop at the last live block (the prefetch registers need the room).
 template <int NKB, bool DROP, bool BITS, bool F16 = false>
 __global__ __launch_bounds__(512) void attn_bwd2_kernel(const bf16_t* __restrict__ qkv, const int64_t* __restrict__ mask,
                                                          const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx,
@@ -1160,18 +1120,13 @@ __global__ __launch_bounds__(512) void attn_bwd2_kernel(const bf16_t* __restrict
     for (; item < nitems; item += gridDim.x) {
         const int next = item + gridDim.x;
         const bool has_next = next < nitems;
-        const char* sQ = smem + cur * BUF;
-        const char* sK = sQ + TILE;
-        const char* sV = sK + TILE;
-        const char* sdO = sV + TILE;
-        const float* sBias = (const float*)(sdO + TILE);
-        const float* sLse = sBias + Lp;
-        const float* sDelta = sLse + Lp;
-        const uint32_t* sRk = (const uint32_t*)(sDelta + Lp);
-        const uint32_t* sBits = sRk + Lp;
+        const char* tiles = smem + cur * BUF;
+        const float* fl = (const float*)(tiles + 4 * TILE);
+        const BwdTiles T = {tiles, tiles + TILE, tiles + 2 * TILE, tiles + 3 * TILE, fl, fl + Lp, fl + 2 * Lp, (const uint32_t*)fl + 3 * Lp,
+                            (const uint32_t*)fl + 4 * Lp};
         const int seq = seq_of(seq_list, item / H), hd = item % H;
         const SeqRows sr = seq_rows(cu, seq, L);
-        const int len = sr.len, nb = CLDRD_LIVE_BLOCKS(len, NKB);
+        const int len = sr.len, nb = live_blocks(len);
         const int t_ = opaque(tid);
         const int lane = t_ & 63, r = lane & 31, h = lane >> 5;
         tb = t_ & 255;
@@ -1179,167 +1134,29 @@ __global__ __launch_bounds__(512) void attn_bwd2_kernel(const bf16_t* __restrict
             if (has_next) issue(next);
             if (rw < nb) {        // ---- sweep B: query on lane; dQ for 32 queries accumulates over all (live) key blocks
                 const int qb = rw;
-        bf16x8 qf[4], dof[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { qf[s] = row_frag(sQ, qb * 32 + r, s, h); dof[s] = row_frag(sdO, qb * 32 + r, s, h); }
-        const int q = qb * 32 + r;
-        const float lse_q = sLse[q], delta_q = sDelta[q];
-        const uint32_t rk_q = sRk[q];
-        f32x16 dQ[2] = {(f32x16){0.f}, (f32x16){0.f}};
-        for (int kb = 0; kb < nb; ++kb) {
-            f32x16 ST = (f32x16){0.f}, dPT = (f32x16){0.f};
-            uint32_t wbits = 0;
-            if constexpr (BITS) wbits = sBits[kb * Lp + q] >> (4 * h);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                ST = mfma32<F16>(row_frag(sK, kb * 32 + r, s, h), qf[s], ST);
-                dPT = mfma32<F16>(row_frag(sV, kb * 32 + r, s, h), dof[s], dPT);
-            }
-            float ds[16];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int key4 = kb * 32 + 8 * u + 4 * h;
-                const float4 b4 = *(const float4*)(sBias + key4);
-                const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {
-                    const int t = 4 * u + j;
-                    // packed fp32 (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32: two keys per instruction, the same IEEE operations as before)
-                    const cldrd_f32v2 a2 = fma2((cldrd_f32v2){ST[t], ST[t + 1]}, splat2(scale2), (cldrd_f32v2){bb[j], bb[j + 1]}) - splat2(lse_q);
-                    const cldrd_f32v2 p2 = {__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
-                    cldrd_f32v2 dp2 = {dPT[t], dPT[t + 1]};
-                    if (DROP) dp2 = dp2 * splat2(drop_scale);
-                    float dp0 = dp2.x, dp1 = dp2.y;
-                    if (DROP) {
-                        if constexpr (BITS) {       // keys key4 + j, key4 + j + 1: adjacent bits of the forward's dword [kb][q]
-                            dp0 = keep_bit(dp0, wbits, 8 * u + j);
-                            dp1 = keep_bit(dp1, wbits, 8 * u + j + 1);
-                        } else {
-                            const uint32_t hh = drop_pair(rk_q, (uint32_t)(key4 + j));
-                            dp0 = drop_keep_lo(hh, drop_thresh) ? dp0 : 0.f;
-                            dp1 = drop_keep_hi(hh, drop_thresh) ? dp1 : 0.f;
-                        }
-                    }
-                    const cldrd_f32v2 ds2 = p2 * ((cldrd_f32v2){dp0, dp1} - splat2(delta_q));
-                    ds[t] = ds2.x; ds[t + 1] = ds2.y;
+                BwdQueryRows Q;
+                bwd_load_queries(T, qb, lane, Q);
+                f32x16 dQ[2] = {(f32x16){0.f}, (f32x16){0.f}};
+                for (int kb = 0; kb < nb; ++kb) {
+                    bwd_query_step<NKB, DROP, BITS, F16>(T, Q, kb, qb, lane, scale2, drop_thresh, drop_scale, dQ);
+                    mfma_drain();
                 }
+                const int q = qb * 32 + r;
+                store_dq<F16>(dQ, scale, dqkv + ((size_t)sr.row0 + q) * ld + hd * 64, h, q < len);
             }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 sa = pack8x<F16>(ds + 8 * s2);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)
-                    // operands swapped: D[d][q], so a lane (= query) ends up with 4 consecutive head dimensions per register quad and dQ
-                    // leaves in 8-byte stores (the other order gave 32 two-byte stores per lane)
-                    dQ[dt] = mfma32<F16>(tr_frag(sK, kb * 32 + 16 * s2 + 4 * h, dt * 32, lane), sa, dQ[dt]);
-            }
-            mfma_drain();
-        }
-        {                 // dQ[dt][t] = dQ[q][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
-            bf16_t* oq = dqkv + ((size_t)sr.row0 + q) * ld + hd * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 a[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int t = 4 * (u + k);
-                        a[k].x = pack2x_scaled<F16>(dQ[dt][t], dQ[dt][t + 1], scale);
-                        a[k].y = pack2x_scaled<F16>(dQ[dt][t + 2], dQ[dt][t + 3], scale);
-                    }
-                    const uint4 w = widen_pair(a[0], a[1]);
-                    if (q < len) *(uint4*)(oq + dt * 32 + 8 * (u + h)) = w;
-                }
-        }
-                }
             if (has_next) commit(cur ^ 1, next);
         } else if (rw < nb) {     // ---- sweep A: key on lane; dK, dV for 32 keys accumulate over all (live) query blocks
             const int kb = rw;
-        bf16x8 kf[4], vf[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { kf[s] = row_frag(sK, kb * 32 + r, s, h); vf[s] = row_frag(sV, kb * 32 + r, s, h); }
-        const int key = kb * 32 + r;
-        const float bias_k = sBias[key];
-        f32x16 dK[2] = {(f32x16){0.f}, (f32x16){0.f}}, dV[2] = {(f32x16){0.f}, (f32x16){0.f}};
-        for (int qb = 0; qb < nb; ++qb) {
-            f32x16 S = (f32x16){0.f}, dP = (f32x16){0.f};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                S = mfma32<F16>(row_frag(sQ, qb * 32 + r, s, h), kf[s], S);
-                dP = mfma32<F16>(row_frag(sdO, qb * 32 + r, s, h), vf[s], dP);
-            }
-            // S[t], dP[t]: query q = 32 qb + rowmap(t, h), key = 32 kb + r
-            float pd[16], ds[16];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                // queries rowmap(4u .. 4u+3, h) are consecutive: their LSE / delta / dropout row keys come as 16-byte LDS reads
-                const int q4 = qb * 32 + 8 * u + 4 * h;
-                const float4 l4 = *(const float4*)(sLse + q4), d4 = *(const float4*)(sDelta + q4);
-                const float ll[4] = {l4.x, l4.y, l4.z, l4.w}, dd[4] = {d4.x, d4.y, d4.z, d4.w};
-                uint4 k4 = make_uint4(0, 0, 0, 0);
-                if (DROP) k4 = BITS ? *(const uint4*)(sBits + kb * Lp + q4) : *(const uint4*)(sRk + q4);      // BITS: dwords [kb][q4 .. q4+3], bit = key
-                const uint32_t kk[4] = {k4.x, k4.y, k4.z, k4.w};
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {      // two queries per packed fp32 instruction (the same IEEE operations as the scalar form)
-                    const int t = 4 * u + j;
-                    const cldrd_f32v2 a2 = fma2((cldrd_f32v2){S[t], S[t + 1]}, splat2(scale2), splat2(bias_k)) - (cldrd_f32v2){ll[j], ll[j + 1]};
-                    const cldrd_f32v2 p2 = {__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
-                    cldrd_f32v2 pd2 = p2, dp2 = {dP[t], dP[t + 1]};
-                    if (DROP) {
-                        pd2 = p2 * splat2(drop_scale);
-                        dp2 = dp2 * splat2(drop_scale);
-                        if constexpr (BITS) {
-                            pd2.x = keep_bit(pd2.x, kk[j], r); pd2.y = keep_bit(pd2.y, kk[j + 1], r);
-                            dp2.x = keep_bit(dp2.x, kk[j], r); dp2.y = keep_bit(dp2.y, kk[j + 1], r);
-                        } else {
-                            const bool keep0 = dropout_keep(kk[j], (uint32_t)key, drop_thresh), keep1 = dropout_keep(kk[j + 1], (uint32_t)key, drop_thresh);
-                            pd2.x = keep0 ? pd2.x : 0.f; pd2.y = keep1 ? pd2.y : 0.f;
-                            dp2.x = keep0 ? dp2.x : 0.f; dp2.y = keep1 ? dp2.y : 0.f;
-                        }
-                    }
-                    pd[t] = pd2.x; pd[t + 1] = pd2.y;
-                    const cldrd_f32v2 ds2 = p2 * (dp2 - (cldrd_f32v2){dd[j], dd[j + 1]});
-                    ds[t] = ds2.x; ds[t + 1] = ds2.y;
-                }
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 pb = pack8x<F16>(pd + 8 * s2), sb = pack8x<F16>(ds + 8 * s2);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    dV[dt] = mfma32<F16>(tr_frag(sdO, qb * 32 + 16 * s2 + 4 * h, dt * 32, lane), pb, dV[dt]);
-                    dK[dt] = mfma32<F16>(tr_frag(sQ, qb * 32 + 16 * s2 + 4 * h, dt * 32, lane), sb, dK[dt]);
-                }
-            }
-        }
-        mfma_drain();     // behind the loop (see mfma_drain): its only exit falls through to here, in front of the first read of dK / dV
-        // dV[dt][t] = dV[key][d = 32 dt + rowmap(t, h)]: regs 4u..4u+3 are 4 consecutive d
-        {
+            BwdKeyRows K;
+            bwd_load_keys(T, kb, lane, K);
+            f32x16 dK[2] = {(f32x16){0.f}, (f32x16){0.f}}, dV[2] = {(f32x16){0.f}, (f32x16){0.f}};
+            for (int qb = 0; qb < nb; ++qb)
+                bwd_key_step<NKB, DROP, BITS, F16>(T, K, qb, kb, lane, scale2, drop_thresh, drop_scale, dK, dV);
+            mfma_drain();     // behind the loop (see mfma_drain): its only exit falls through to here, in front of the first read of dK / dV
+            const int key = kb * 32 + r;
             bf16_t* ok = dqkv + ((size_t)sr.row0 + key) * ld + dm + hd * 64;
-            bf16_t* ov = ok + dm;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    uint2 a[2], b[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int t = 4 * (u + k);
-                        a[k].x = pack2x_scaled<F16>(dK[dt][t], dK[dt][t + 1], scale);
-                        a[k].y = pack2x_scaled<F16>(dK[dt][t + 2], dK[dt][t + 3], scale);
-                        b[k].x = pack2x<F16>(dV[dt][t], dV[dt][t + 1]);
-                        b[k].y = pack2x<F16>(dV[dt][t + 2], dV[dt][t + 3]);
-                    }
-                    const uint4 wa = widen_pair(a[0], a[1]), wb = widen_pair(b[0], b[1]);      // 16 contiguous bytes per lane (see widen_pair)
-                    const int d0 = dt * 32 + 8 * (u + h);
-                    if (key < len) {
-                        *(uint4*)(ok + d0) = wa;
-                        *(uint4*)(ov + d0) = wb;
-                    }
-                }
+            store_dkdv<F16>(dK, dV, scale, ok, ok + dm, h, key < len);
         }
-            }
         __syncthreads();          // the other buffer is complete, and nobody reads this one any more
         cur ^= 1;
     }
@@ -1362,12 +1179,12 @@ bool attn_fwd2_enabled(int nseq, int L, int H) {
 // One launch's arguments: the entry point fills them once, every launcher reads them.  nseq: the sequences of THIS launch (items = nseq x H);
 // L: the batch's row stride of lse / keep bits / dropout row keys (the tile height is the launcher's NKB); p, seed: as the caller gave them.
 struct AttnFwdArgs {
-    const void* qkv; const long long* mask; const int* cu; const int* seq_list;
-    void* ctx; float* lse; int nseq, L, H; float scale, p; unsigned long long seed; uint32_t* bits_out; void* ctx16; hipStream_t st;
+    const bf16_t* qkv; const int64_t* mask; const int* cu; const int* seq_list;
+    bf16_t* ctx; float* lse; int nseq, L, H; float scale, p; unsigned long long seed; uint32_t* bits_out; bf16_t* ctx16; hipStream_t st;
 };
 struct AttnBwdArgs {
-    const void* qkv; const long long* mask; const int* cu; const int* seq_list;
-    const void* ctx; const void* dctx; const float* lse; void* dqkv; int nseq, L, H; float scale, p; unsigned long long seed;
+    const bf16_t* qkv; const int64_t* mask; const int* cu; const int* seq_list;
+    const bf16_t* ctx; const bf16_t* dctx; const float* lse; bf16_t* dqkv; int nseq, L, H; float scale, p; unsigned long long seed;
     const uint32_t* drop_bits; hipStream_t st;
 };
 
@@ -1384,61 +1201,55 @@ bool attn_drops(float p) { return p > 0.f && dropout_thresh16(p) > 0; }
 template <class F>
 int with_drop(float p, F&& f) { return attn_drops(p) ? f(std::true_type{}) : f(std::false_type{}); }
 
-template <int NKB, bool DROP>
-int launch_fwd_f16(const AttnFwdArgs& a) {      // fp16 in, fp16 out: no second copy; the all-scores-in-registers kernel only (L <= 128)
-    const float p = DROP ? a.p : 0.f;
-    const size_t lds = 3 * 32 * NKB * RSB + 32 * NKB * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_full_kernel<NKB, DROP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((attn_fwd_full_kernel<NKB, DROP, true>), dim3(a.nseq * a.H), dim3(256), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                       (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(a.seed), (bf16_t*)nullptr,
-                       a.cu, a.seq_list);
+// Every launch of this family: the dynamic-LDS limit of the kernel, the launch, the launch check
+template <class... P, class... A>
+int attn_launch(void (*kern)(P...), int grid, int block, size_t lds, hipStream_t st, A... args) {
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, args...);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
 
 template <int NKB, bool DROP, bool F16>
-int launch_fwd(const AttnFwdArgs& a) {
+int launch_fwd_full(const AttnFwdArgs& a, bf16_t* ctx16) {      // the all-scores one-item kernel (L <= 128)
     const float p = DROP ? a.p : 0.f;
+    const size_t lds = 3 * 32 * NKB * RSB + 32 * NKB * sizeof(float);
+    return attn_launch(attn_fwd_full_kernel<NKB, DROP, F16>, a.nseq * a.H, 256, lds, a.st, a.qkv, a.mask, a.ctx, a.lse, a.L, a.H, a.scale,
+                       DROP ? dropout_thresh16(p) : 0u, 1.0f / (1.0f - p), seed_arg(a.seed), ctx16, a.cu, a.seq_list);
+}
+
+template <int NKB, bool DROP>
+int launch_fwd_f16(const AttnFwdArgs& a) {      // fp16 in, fp16 out: no second copy; the all-scores-in-registers kernel only (L <= 128)
+    return launch_fwd_full<NKB, DROP, true>(a, nullptr);
+}
+
+template <int NKB, bool DROP, bool F16>
+int launch_fwd(const AttnFwdArgs& a) {
+    const float p = DROP ? a.p : 0.f, drop_scale = 1.0f / (1.0f - p);
     const uint32_t thresh = DROP ? dropout_thresh16(p) : 0u;
     const size_t lds = 3 * 32 * NKB * RSB + 32 * NKB * sizeof(float);
     const int nitems = a.nseq * a.H, cus = attn_num_cus();
     if constexpr (NKB <= 4) {
         // many items: the persistent loader / compute kernel (cldrd_set_tuning("attn_fwd2", 0) keeps the one-item-per-workgroup kernel: A/B runs and tests)
-        if (attn_fwd2_enabled(a.nseq, 32 * NKB, a.H)) {       // (the tile height, not L: a listed launch of short sequences has L > 128)
-            const size_t lds2 = 2 * (lds + (DROP ? 32 * NKB * NKB * sizeof(uint32_t) : 0));
-            (void)hipFuncSetAttribute((const void*)attn_fwd2_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            hipLaunchKernelGGL((attn_fwd2_kernel<NKB, DROP, F16>), dim3(cus), dim3(512), lds2, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                               (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems,
-                               DROP ? a.bits_out : nullptr, (bf16_t*)a.ctx16, a.cu, a.seq_list);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
-        (void)hipFuncSetAttribute((const void*)attn_fwd_full_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((attn_fwd_full_kernel<NKB, DROP, F16>), dim3(nitems), dim3(256), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                           (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), (bf16_t*)a.ctx16, a.cu, a.seq_list);
+        if (attn_fwd2_enabled(a.nseq, 32 * NKB, a.H))         // (the tile height, not L: a listed launch of short sequences has L > 128)
+            return attn_launch(attn_fwd2_kernel<NKB, DROP, F16>, cus, 512, 2 * (lds + (DROP ? 32 * NKB * NKB * sizeof(uint32_t) : 0)), a.st, a.qkv, a.mask,
+                               a.ctx, a.lse, a.L, a.H, a.scale, thresh, drop_scale, seed_arg(a.seed), nitems, DROP ? a.bits_out : nullptr, a.ctx16, a.cu,
+                               a.seq_list);
+        return launch_fwd_full<NKB, DROP, F16>(a, a.ctx16);
     } else {
         // many items at 128 < L <= 256: the persistent streaming kernel (K / V double-buffered, Q from global memory); cldrd_set_tuning("attn_fwd2", 0)
         // keeps the one-item-per-workgroup kernel (tests: the two are bit-identical)
-        if (nitems >= 2 * cus && g_cldrd_tune_attn_fwd2 != 0) {
-            const size_t lds3 = 2 * (2 * 32 * NKB * RSB + 32 * NKB * sizeof(float));
-            (void)hipFuncSetAttribute((const void*)attn_fwd3_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            hipLaunchKernelGGL((attn_fwd3_kernel<NKB, DROP, F16>), dim3(cus), dim3(512), lds3, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                               (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems,
-                               (bf16_t*)a.ctx16, a.cu, a.seq_list);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((attn_fwd_kernel<NKB, DROP, F16>), dim3(nitems), dim3(512), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                           (bf16_t*)a.ctx, a.lse, a.L, a.H, a.scale, thresh, 1.0f / (1.0f - p), seed_arg(a.seed), (bf16_t*)a.ctx16, a.cu, a.seq_list);
+        if (nitems >= 2 * cus && g_cldrd_tune_attn_fwd2 != 0)
+            return attn_launch(attn_fwd3_kernel<NKB, DROP, F16>, cus, 512, 2 * (2 * 32 * NKB * RSB + 32 * NKB * sizeof(float)), a.st, a.qkv, a.mask, a.ctx,
+                               a.lse, a.L, a.H, a.scale, thresh, drop_scale, seed_arg(a.seed), nitems, a.ctx16, a.cu, a.seq_list);
+        return attn_launch(attn_fwd_kernel<NKB, DROP, F16>, nitems, 512, lds, a.st, a.qkv, a.mask, a.ctx, a.lse, a.L, a.H, a.scale, thresh, drop_scale,
+                           seed_arg(a.seed), a.ctx16, a.cu, a.seq_list);
     }
-    CLDRD_LAUNCH_CHECK();
-    return 0;
 }
 
 template <int NKB, bool DROP, bool F16>
 int launch_bwd(const AttnBwdArgs& a) {
-    const float p = DROP ? a.p : 0.f;
+    const float p = DROP ? a.p : 0.f, drop_scale = 1.0f / (1.0f - p);
     const uint32_t thresh = DROP ? dropout_thresh16(p) : 0u;
     const int nitems = a.nseq * a.H;
     const size_t lds = 4 * 32 * NKB * RSB + 4 * 32 * NKB * sizeof(float);
@@ -1446,36 +1257,21 @@ int launch_bwd(const AttnBwdArgs& a) {
         // many items: the persistent two-role kernel (cldrd_set_tuning("attn_bwd2", 0) keeps the one-item-per-workgroup kernel: tests)
         const int cus = attn_num_cus();
         if (nitems >= 2 * cus && g_cldrd_tune_attn_bwd2 != 0) {
-            if (DROP && a.drop_bits) {
-                const size_t lds2 = 2 * (lds + 32 * NKB * NKB * sizeof(uint32_t));
-                (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<NKB, DROP, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                hipLaunchKernelGGL((attn_bwd2_kernel<NKB, DROP, DROP, F16>), dim3(cus), dim3(512), lds2, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                                   (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
-                                   thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems, a.drop_bits, a.cu, a.seq_list);
-            } else {
-                (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<NKB, DROP, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds));
-                hipLaunchKernelGGL((attn_bwd2_kernel<NKB, DROP, false, F16>), dim3(cus), dim3(512), 2 * lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                                   (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
-                                   thresh, 1.0f / (1.0f - p), seed_arg(a.seed), nitems, (const uint32_t*)nullptr, a.cu, a.seq_list);
-            }
-            CLDRD_LAUNCH_CHECK();
-            return 0;
+            auto go = [&](auto bits) {       // bits: the forward left its keep bits (room for them behind each LDS buffer), else the kernel re-hashes
+                constexpr bool BITS = decltype(bits)::value;
+                return attn_launch(attn_bwd2_kernel<NKB, DROP, BITS, F16>, cus, 512, 2 * (lds + (BITS ? 32 * NKB * NKB * sizeof(uint32_t) : 0)), a.st, a.qkv,
+                                   a.mask, a.ctx, a.dctx, a.lse, a.dqkv, a.L, a.H, a.scale, thresh, drop_scale, seed_arg(a.seed), nitems,
+                                   BITS ? a.drop_bits : nullptr, a.cu, a.seq_list);
+            };
+            return DROP && a.drop_bits ? go(std::integral_constant<bool, DROP>{}) : go(std::false_type{});
         }
     }
-    if (a.cu != nullptr && NKB > 1) {       // a packed batch: the instantiation whose block loops stop at the sequence's last live block
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<NKB, DROP, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((attn_bwd_kernel<NKB, DROP, F16, true>), dim3(nitems), dim3(NKB > 4 ? 512 : 256), lds, a.st, (const bf16_t*)a.qkv,
-                           (const int64_t*)a.mask, (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
-                           thresh, 1.0f / (1.0f - p), seed_arg(a.seed), a.cu, a.seq_list);
-        CLDRD_LAUNCH_CHECK();
-        return 0;
-    }
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<NKB, DROP, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((attn_bwd_kernel<NKB, DROP, F16>), dim3(nitems), dim3(NKB > 4 ? 512 : 256), lds, a.st, (const bf16_t*)a.qkv, (const int64_t*)a.mask,
-                       (const bf16_t*)a.ctx, (const bf16_t*)a.dctx, a.lse, (bf16_t*)a.dqkv, a.L, a.H, a.scale,
-                       thresh, 1.0f / (1.0f - p), seed_arg(a.seed), a.cu, a.seq_list);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
+    auto go = [&](auto varlen) {
+        return attn_launch(attn_bwd_kernel<NKB, DROP, F16, decltype(varlen)::value>, nitems, NKB > 4 ? 512 : 256, lds, a.st, a.qkv, a.mask, a.ctx, a.dctx,
+                           a.lse, a.dqkv, a.L, a.H, a.scale, thresh, drop_scale, seed_arg(a.seed), a.cu, a.seq_list);
+    };
+    // a packed batch: the instantiation whose block loops stop at the sequence's last live block
+    return a.cu != nullptr && NKB > 1 ? go(std::true_type{}) : go(std::false_type{});
 }
 
 // The shape limits and the layout rule of include/cldrd_hip.h, checked here for all four entry points (`op` names the caller in the message)
@@ -1517,8 +1313,9 @@ extern "C" int cldrd_attention_fwd(const void* qkv, const long long* mask, const
     CLDRD_CHECK(!(io_f16 && (ctx_f16_copy != nullptr || ctx == nullptr)), "attention_fwd: the fp16 pass writes ctx only");
     CLDRD_CHECK(io_f16 == 0 || io_f16 == 1 || io_f16 == 5, "attention_fwd: io_f16 is 0 (bf16), 1 (fp16, L <= 128, no keep bits) or 5 (fp16, every kernel of the bf16 path)");
     CLDRD_CHECK(io_f16 != 1 || Lt <= 128, "attention_fwd: the fp16 forward handles L <= 128");
-    const AttnFwdArgs a = {qkv, mask, cu_rows, seq_list, ctx, lse, n, L, H, 0.125f /* 1 / sqrt(64) */, dropout_p, seed,
-                           (uint32_t*)drop_bits_out, ctx_f16_copy, (hipStream_t)stream};
+    const AttnFwdArgs a = {(const bf16_t*)qkv, (const int64_t*)mask, cu_rows, seq_list, (bf16_t*)ctx, lse,
+                           n, L, H, 0.125f /* 1 / sqrt(64) */, dropout_p, seed,
+                           (uint32_t*)drop_bits_out, (bf16_t*)ctx_f16_copy, (hipStream_t)stream};
     const int nkb = (Lt + 31) / 32;
     if (io_f16 == 5)            // fp16 activations through the whole kernel family (round 4: the all-fp16 training mode)
         return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_fwd<decltype(k)::value, decltype(d)::value, true>(a); }); });
@@ -1536,8 +1333,9 @@ extern "C" int cldrd_attention_bwd(const void* qkv, const long long* mask, const
     if (attn_check("attention_bwd", mask, cu_rows, seq_list, n_list, Ltile, nseq, L, H)) return 1;
     const int n = seq_list ? n_list : nseq, Lt = seq_list ? Ltile : L;          // as in cldrd_attention_fwd
     CLDRD_CHECK(lse != nullptr, "attention_bwd: lse is required");
-    const AttnBwdArgs a = {qkv, mask, cu_rows, seq_list, ctx, dctx, lse, dqkv, n, L, H, 0.125f, dropout_p, seed, (const uint32_t*)drop_bits,
-                           (hipStream_t)stream};
+    const AttnBwdArgs a = {(const bf16_t*)qkv, (const int64_t*)mask, cu_rows, seq_list, (const bf16_t*)ctx, (const bf16_t*)dctx, lse,
+                           (bf16_t*)dqkv, n, L, H, 0.125f, dropout_p, seed,
+                           (const uint32_t*)drop_bits, (hipStream_t)stream};
     const int nkb = (Lt + 31) / 32;
     if (io_f16)
         return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_bwd<decltype(k)::value, decltype(d)::value, true>(a); }); });

@@ -748,6 +748,69 @@ def test_attention_bwd_persistent_kernel_at_block_boundaries(f16, p, use_bits):
             f"{'packed' if pk else 'padded'}: the persistent kernel differs from the one-item kernel for sequences of {bad} tokens"
 
 
+@pytest.mark.parametrize("L,f16,p,use_bits", [(128, False, 0.0, False), (128, True, 0.0, False), (128, False, 0.1, True), (128, False, 0.1, False),
+                                              (128, True, 0.1, True), (128, True, 0.1, False), (256, False, 0.0, False), (256, True, 0.0, False),
+                                              (256, False, 0.1, False), (256, True, 0.1, False)])
+def test_attention_fwd_persistent_kernels_at_block_boundaries(L, f16, p, use_bits):
+    """The forward counterpart of the test above: the persistent forward kernels (attn_fwd2_kernel at L <= 128, attn_fwd3_kernel above) differ from
+    the one-item kernels in how an item reaches LDS, where the keep decisions come from (the loader's bits) and where Q comes from (the prefetch
+    registers).  At L <= 128 the pair calls one block function (fwd_full_block in attention.hip); above, attn_fwd3_kernel carries its own copy of
+    attn_fwd_kernel's block loop, and this test is what keeps the two copies in step.  Lengths on both sides of every 32-row block
+    boundary in ONE launch of enough (sequence, head) items for the dispatch to take the persistent kernel, against the one-item kernel
+    (set_tuning("attn_fwd2", 0)): context, LSE and the fp16 context copy (bf16 passes write one) of the live rows bit for bit and free of NaN, packed
+    and padded, bf16 and fp16, without and with dropout, and at L = 128 with and without the keep bits left for the backward."""
+    H = 2
+    d = H * 64
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nseq = max(300, cus)
+    # Nothing here observes which kernel ran: the first run takes the persistent kernel only through launch_fwd's rule in csrc/attention.hip
+    # (nseq * H >= 2 * CUs, tuning "attn_fwd2" != 0).  If that rule changes, change this assert with it - otherwise the one-item kernel meets itself.
+    assert nseq * H >= 2 * cus
+    dt = torch.float16 if f16 else torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(6100 + L + 2 * int(f16) + int(p > 0))
+    if L == 128:
+        pool = list(range(59, 65)) + list(range(91, 97)) + [1, 32, 33, 128]
+    else:
+        pool = [129, 159, 160, 161, 191, 192, 193, 223, 224, 225, 255, 256, 1, 32, 33]
+    pool = torch.tensor(pool, device=DEV)
+    lens = pool[torch.arange(nseq, device=DEV) % pool.numel()]
+    cu = torch.zeros(nseq + 1, dtype=torch.int32, device=DEV)
+    cu[1:] = torch.cumsum(lens, 0).to(torch.int32)
+    Tp = int(cu[-1])
+    mask = (torch.arange(L, device=DEV)[None, :] < lens[:, None]).to(torch.int64).contiguous()
+    tok = torch.nonzero(mask.reshape(-1)).reshape(-1)
+    lv = mask.bool()[:, None, :].expand(nseq, H, L)
+    seq_of = torch.repeat_interleave(torch.arange(nseq, device=DEV), lens)
+    qkv = torch.randn(nseq * L, 3 * d, device=DEV, generator=g).to(dt)            # real values in the padding rows (masked, not zero)
+    for pk in (True, False):
+        rows = Tp if pk else nseq * L
+        x = qkv[tok].contiguous() if pk else qkv
+        outs = []
+        for fwd2 in (1, 0):
+            ctx = torch.full((rows, d), float("nan"), dtype=dt, device=DEV)
+            ctx16 = None if f16 else torch.full((rows, d), float("nan"), dtype=torch.float16, device=DEV)
+            lse = torch.full((nseq, H, L), float("nan"), dtype=torch.float32, device=DEV)
+            ops.set_tuning("attn_fwd2", fwd2)
+            try:
+                bits = ops.attention_drop_bits(nseq, L, H, p, DEV) if use_bits and fwd2 else None      # only the persistent L <= 128 kernel leaves bits
+                assert (bits is not None) == bool(use_bits and fwd2)
+                ops.attention_fwd(x, None if pk else mask, ctx, lse, nseq, L, H, dropout_p=p, seed=61, drop_bits=bits, ctx16=ctx16, full_family=f16,
+                                  cu=cu if pk else None)
+                torch.cuda.synchronize()
+            finally:
+                ops.set_tuning("attn_fwd2", 1)
+            outs.append((ctx if pk else ctx[tok], lse[lv], None if f16 else (ctx16 if pk else ctx16[tok])))
+        where = "packed" if pk else "padded"
+        assert not torch.isnan(outs[0][0].float()).any() and not torch.isnan(outs[0][1]).any(), where
+        for i, name in ((0, "context"), (2, "fp16 context copy")):
+            if outs[0][i] is None:
+                continue
+            same = (outs[0][i] == outs[1][i]).all(1)
+            bad = sorted(set(lens[seq_of[~same]].tolist()))
+            assert torch.equal(outs[0][i], outs[1][i]), f"{where}, {name}: the persistent kernel differs from the one-item kernel for sequences of {bad} tokens"
+        assert torch.equal(outs[0][1], outs[1][1]), f"{where}: the LSE of the persistent kernel differs from the one-item kernel's"
+
+
 @pytest.mark.parametrize("L,H,f16,p", [(256, 2, False, 0.0), (256, 4, True, 0.0), (200, 1, True, 0.0)])
 def test_attention_sequence_lists_send_short_sequences_through_the_short_kernels(L, H, f16, p):
     """cldrd_attention_{fwd,bwd}_varlen_list: a packed batch at 128 < L <= 256 in TWO launches - the sequences of at most 128 tokens through the
