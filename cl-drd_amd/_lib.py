@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # change of ABI_VERSION uses two checkouts).  The library itself reads no environment variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
 
-ABI_VERSION = 103          # cldrd_version() of the build SIGNATURES describes
+ABI_VERSION = 104          # cldrd_version() of the build SIGNATURES describes
 
 _lib = None
 
@@ -32,6 +32,9 @@ SIGNATURES = {
     "cldrd_attention_bwd": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp]),
     "cldrd_attention_cls_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp, vp]),
     "cldrd_attention_cls_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, cull, ci, vp]),
+    "cldrd_gemm_nt_f32": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
+    "cldrd_attention_fwd_f32": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
+    "cldrd_attention_cls_fwd_f32": (ci, [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_attention_bits_words": (C.c_longlong, [ci, ci, ci, cf]),
     "cldrd_add_rows": (ci, [vp, vp, ci, ci, ci, vp, ci, vp]),
     "cldrd_ln_partial_blocks": (ci, [ci]),

@@ -610,7 +610,7 @@ class HipEncoder(nn.Module):
 
     def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None, *, train: bool | None = None,
                save: bool = False, seed: int | None = None, fp16: bool | None = None, lengths=None, device_seed: bool = False,
-               token_type_ids: torch.Tensor | None = None, packed=None):
+               token_type_ids: torch.Tensor | None = None, packed=None, fp32: bool = False):
         """CLS embeddings fp32 [M, d] (== HF ``model(**enc)[0][:, 0, :]``).  With ``save`` also returns the tape.
 
         ``fp16`` (default: ``self.hp_forward``, which NwayDualEncoder sets on the QUERY tower in the fp16 mode): the evaluation pass runs
@@ -629,15 +629,26 @@ class HipEncoder(nn.Module):
         int32 [T][, width]): rows already in the packed layout of ``lengths`` (``input_ids`` / ``attention_mask`` are then None; evaluation
         passes only) - what cldrd_build_pairs writes for the cross-encoder.  ``width`` (default: the longest sequence) is the L the attention
         kernels are chosen for: a caller that passes the same width for every batch gets each sequence's attention independent of the
-        batch.  Both run the evaluation pass of the tower's mode; ``fp16=True`` / ``hp_forward`` (the all-fp16 query-tower pass) is refused."""
+        batch.  Both run the evaluation pass of the tower's mode; ``fp16=True`` / ``hp_forward`` (the all-fp16 query-tower pass) is refused.
+
+        ``fp32=True``: the exact fp32 evaluation pass (:meth:`_encode_f32_gen`): every activation fp32, the weights read from ``flat_p`` in
+        place, every contraction on the f32-input MFMA - the reference's ``use_fp16=False`` encode.  It takes ``attention_mask``, ``lengths``
+        (the batch is then packed), ``token_type_ids`` and ``packed`` like the evaluation pass, and refuses ``save`` / ``train`` /
+        ``device_seed`` / ``fp16=True``: it keeps no tape and has no dropout.  A sequence's CLS vector does not depend on the rest of the
+        batch, bit for bit."""
         return self.encode_steps(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=fp16, lengths=lengths,
-                                 device_seed=device_seed, token_type_ids=token_type_ids, packed=packed).finish()
+                                 device_seed=device_seed, token_type_ids=token_type_ids, packed=packed, fp32=fp32).finish()
 
     def encode_steps(self, input_ids, attention_mask, *, train=None, save=False, seed=None, fp16=None, lengths=None, device_seed=False,
-                     window=None, token_type_ids=None, packed=None) -> Stepper:
+                     window=None, token_type_ids=None, packed=None, fp32=False) -> Stepper:
         """:meth:`encode` as a :class:`Stepper` (``.finish()`` -> what encode returns).  ``window(kind)`` (optional) is called right before
         each HBM-bound launch of the pass - kind "ln" (LayerNorm / embedding kernels) or "attn" - on the stream the pass is enqueued on: the
         hook at which a trainer releases a slice of the OTHER tower's stepper."""
+        if fp32:
+            if save or train or device_seed or fp16:
+                raise ValueError("encode(fp32=True) is an evaluation pass and nothing else: no save / train / device_seed / fp16")
+            return Stepper(self._encode_f32_gen(input_ids, attention_mask, lengths=lengths, window=window, token_type_ids=token_type_ids,
+                                                packed=packed))
         fp16 = self.hp_forward if fp16 is None else fp16
         base = getattr(self, "seed_base_ptr", None) if (device_seed and seed is None) else None
         if token_type_ids is not None or packed is not None:
@@ -869,6 +880,150 @@ class HipEncoder(nn.Module):
             src = x if x is not None else xh
             cls.copy_(src.view(ops.pad_rows(T), d)[:T].view(M, L, d)[:, 0].float())
         return (cls, tape) if save else cls
+
+    # ------------------------------------------------------------------ the fp32 evaluation pass (csrc/encoder_f32.hip)
+    def _layer_weights_f32(self, i):
+        """The fp32 master weights of layer ``i`` as views of ``flat_p`` (no shadows)."""
+        cfg, n = self.cfg, layer_param_names(self.cfg, i)
+        d = cfg.dim
+        oq = self.layout.entries[n["q"] + ".weight"][0]
+        ob = self.layout.entries[n["q"] + ".bias"][0]
+        return dict(Wqkv=self.flat_p[oq:oq + 3 * d * d].view(3 * d, d), bqkv=self.flat_p[ob:ob + 3 * d],
+                    Wo=self.w(n["o"] + ".weight"), bo=self.w(n["o"] + ".bias"),
+                    g1=self.w(n["ln1"] + ".weight"), b1=self.w(n["ln1"] + ".bias"),
+                    W1=self.w(n["f1"] + ".weight"), bf1=self.w(n["f1"] + ".bias"),
+                    W2=self.w(n["f2"] + ".weight"), bf2=self.w(n["f2"] + ".bias"),
+                    g2=self.w(n["ln2"] + ".weight"), b2=self.w(n["ln2"] + ".bias"))
+
+    def _encode_f32_gen(self, input_ids, attention_mask, *, lengths=None, window=None, token_type_ids=None, packed=None):
+        """The exact fp32 evaluation pass as a generator (a ``yield`` behind every group of launches): embedding + LayerNorm, ``n_layers - 1`` full
+        layers and the CLS-only last layer, fp32 activations only, weights from ``flat_p`` (``refresh_shadows`` is never reached).  Every kernel
+        of the pass treats a row independently of the launch it is in, so ``lengths`` always packs (no thresholds: packed == padded bit for
+        bit) - except on a tower built without the CLS-only last layer (test hook), which stays padded and refuses ``packed``."""
+        cfg = self.cfg
+        cls_last = self.cls_only_last and cfg.n_layers >= 1
+        if packed is not None:
+            if lengths is None or len(lengths) < 1 or not cls_last:
+                raise ValueError("packed rows need host lengths and the CLS-only last layer")
+            M, L = len(lengths), int(max(lengths))
+            if len(packed) > 3:
+                if int(packed[3]) < L:
+                    raise ValueError("packed rows: width must be at least the longest sequence")
+                L = int(packed[3])
+            if min(lengths) < 1:
+                raise ValueError("packed rows: every sequence has at least one token")
+        elif input_ids.dim() != 2:
+            raise ValueError("input_ids must be [M, L]")
+        else:
+            M, L = input_ids.shape
+        if L > 256 or L > cfg.max_position_embeddings:
+            raise ValueError("sequence length must be <= 256 (and <= max_position_embeddings)")
+        if lengths is not None and len(lengths) != M:
+            raise ValueError("lengths: one entry per sequence")
+        dev = self.flat_p.device
+        typed = token_type_ids is not None and cfg.arch == "bert"      # (DistilBERT has no token-type table)
+        T, d, f, H = M * L, cfg.dim, cfg.hidden_dim, cfg.n_heads
+        pk, mask = None, None
+        if packed is not None:
+            pk = _Pack.build(lengths, L, dev)
+            T = pk.Tp
+            ids, tt, pk.pos = packed[:3]
+            if ids.numel() != T or pk.pos.numel() != T or (tt is not None and tt.numel() != T):
+                raise ValueError("packed rows: ids / token types / positions must hold sum(lengths) rows")
+            tt = tt if cfg.arch == "bert" else None
+        else:
+            ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+            mask = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
+            tt = token_type_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous() if typed else None
+            if lengths is not None and cls_last and mask is not None and L > 1 and _env_flag("CLDRD_PACK", "1") != "0":
+                lens = [int(v) for v in (lengths.reshape(-1).tolist() if hasattr(lengths, "reshape") else lengths)]
+                if min(lens) >= 1 and max(lens) <= L:          # (an empty row stays on the padded path, which reads the mask)
+                    pk = _Pack.build(lens, L, dev)
+                    T = pk.Tp
+                    ids = ops.gather_i64(ids.reshape(-1), pk.tok_idx, T)
+                    if tt is not None:
+                        tt = ops.gather_i64(tt, pk.tok_idx, T)
+                    mask = None
+        f32 = dict(dtype=torch.float32, device=dev)
+        buf = lambda rows, cols: self._buf(rows, cols, dev, torch.float32)
+        # the embedding / LayerNorm kernels always write a 16-bit copy next to their fp32 output: it goes to one scratch buffer nobody reads
+        junk16 = self._buf(T, d, dev, torch.bfloat16)
+        stat = torch.empty(2, T, **f32)
+        x = buf(T, d)
+        if window is not None:
+            window("ln")
+        ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"), self.w("embeddings.position_embeddings.weight"),
+                         self.w("embeddings.token_type_embeddings.weight") if cfg.arch == "bert" else None, self.w("embeddings.LayerNorm.weight"),
+                         self.w("embeddings.LayerNorm.bias"), junk16, stat[0], stat[1], T, L, cfg.eps, 0.0, 0, out32=x,
+                         pos_idx=pk.pos if pk is not None else None, type_ids=tt.to(torch.int32) if tt is not None else None)
+        yield
+        cls = torch.empty(M, d, **f32)
+        cu = pk.cu if pk is not None else None
+        for i in range(cfg.n_layers):
+            W = self._layer_weights_f32(i)
+            last = i == cfg.n_layers - 1
+            if last and cls_last:
+                # K and V for every token; Q, attention, out-projection, FFN and both LayerNorms for token 0 only (as _last_layer_cls_fwd)
+                kv = buf(T, 2 * d)
+                ops.gemm_nt_f32(x, W["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
+                yield
+                if pk is None:
+                    xc = x[:T].view(M, L * d)[:, :d]              # rows 0, L, 2L, ...: a strided view (row pitch L * d)
+                else:
+                    xc = ops.gather_rows(x, pk.cls_idx, buf(M, d), M)
+                qc = buf(M, d)
+                ops.gemm_nt_f32(xc, W["Wqkv"][:d], qc, M, bias=W["bqkv"][:d])
+                ctxc = buf(M, d)
+                if window is not None:
+                    window("attn")
+                ops.attention_fwd_f32(kv, mask, ctxc, M, L, H, cu=cu, qc=qc)
+                yield
+                s1 = buf(M, d)
+                ops.gemm_nt_f32(ctxc, W["Wo"], s1, M, bias=W["bo"], residual=xc)
+                yield
+                x1 = buf(M, d)
+                ops.layernorm_fwd(s1, W["g1"], W["b1"], junk16, None, None, M, cfg.eps, out32=x1)
+                hb = buf(M, f)
+                ops.gemm_nt_f32(x1, W["W1"], hb, M, bias=W["bf1"], act=1)
+                s2 = buf(M, d)
+                ops.gemm_nt_f32(hb, W["W2"], s2, M, bias=W["bf2"], residual=x1)
+                yield
+                ops.layernorm_fwd(s2, W["g2"], W["b2"], junk16, None, None, M, cfg.eps, cls, 1)
+                yield
+                break
+            qkv = buf(T, 3 * d)
+            ops.gemm_nt_f32(x, W["Wqkv"], qkv, T, bias=W["bqkv"])
+            yield
+            ctx = buf(T, d)
+            if window is not None:
+                window("attn")
+            ops.attention_fwd_f32(qkv, mask, ctx, M, L, H, cu=cu)
+            yield
+            s1 = buf(T, d)
+            ops.gemm_nt_f32(ctx, W["Wo"], s1, T, bias=W["bo"], residual=x)
+            del qkv, ctx
+            yield
+            if window is not None:
+                window("ln")
+            x1 = buf(T, d)
+            ops.layernorm_fwd(s1, W["g1"], W["b1"], junk16, None, None, T, cfg.eps, out32=x1)
+            yield
+            hb = buf(T, f)
+            ops.gemm_nt_f32(x1, W["W1"], hb, T, bias=W["bf1"], act=1)
+            yield
+            s2 = buf(T, d)
+            ops.gemm_nt_f32(hb, W["W2"], s2, T, bias=W["bf2"], residual=x1)
+            del hb, s1
+            yield
+            if window is not None:
+                window("ln")
+            x = buf(T, d)
+            # a tower built without the CLS-only last layer (never packed): the last LayerNorm pools rows 0, L, 2L, ...
+            ops.layernorm_fwd(s2, W["g2"], W["b2"], junk16, None, None, T, cfg.eps, cls if last else None, L, out32=x)
+            yield
+        if cfg.n_layers == 0:
+            cls.copy_(x[:T].view(M, L, d)[:, 0])
+        return cls
 
     # ------------------------------------------------------------------ last layer, CLS row only (SURVEY.md K5)
     def _last_layer_cls_fwd(self, x, x32, W, mask, M, L, T, p_h, p_a, p_out, s_l, save, tape, cls, dt16=torch.bfloat16, W16=None, pk=None, xh=None,

@@ -265,6 +265,32 @@ def gemm_nt(A, B, out, M=None, *, bias=None, residual=None, preact=None, gelu_pr
     return out
 
 
+def gemm_nt_f32(A, W, out, M=None, *, bias=None, residual=None, act=0):
+    """out[M,N] = A[M,K] @ W[N,K]^T (+ bias) (act = 1: erf-GELU) (+ residual), every operand fp32, on the f32-input MFMA (the fp32 evaluation
+    pass, csrc/encoder_f32.hip).  A, out and residual take row pitches (``stride(0)``): the CLS rows of a padded batch are a strided view.
+    One schedule for every M: a row's result does not depend on the other rows of the launch."""
+    _chk(A, F32, "A", 2), _chk(W, F32, "W", 2), _chk(out, F32, "out", 2)
+    M = A.shape[0] if M is None else M
+    N, K = W.shape
+    if A.shape[1] != K or out.shape[1] != N or out.shape[0] < M or A.shape[0] < M or M < 1:
+        raise ValueError(f"gemm_nt_f32: shape mismatch A{tuple(A.shape)} W{tuple(W.shape)} out{tuple(out.shape)} M={M}")
+    if K % 32 or N % 8:
+        raise ValueError("gemm_nt_f32: K must be a multiple of 32, N of 8")
+    if bias is not None:
+        _chk(bias, F32, "bias", 1)
+        if bias.numel() != N:
+            raise ValueError("gemm_nt_f32: bias must be [N]")
+    if residual is not None:
+        _chk(residual, F32, "residual", 2)
+        if residual.shape[0] < M or residual.shape[1] != N:
+            raise ValueError("gemm_nt_f32: residual must be [>= M, N]")
+    if act not in (0, 1):
+        raise ValueError("gemm_nt_f32: act is 0 or 1 (erf-GELU)")
+    call("cldrd_gemm_nt_f32", _p(A), _p(W), _p(out), M, N, K, A.stride(0), W.stride(0), out.stride(0), _p(bias), _p(residual),
+         residual.stride(0) if residual is not None else 0, act, _stream())
+    return out
+
+
 _SPLITK_WS = {}
 _TUNING = {}
 
@@ -451,6 +477,36 @@ def attention_cls_bwd(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p=0.0, 
             raise ValueError(f"attention_cls_bwd: {n} must be contiguous")
     call("cldrd_attention_cls_bwd", _p(qc), _p(kv), _layout(None, cu, None, 0, nseq, L, "attention_cls_bwd")[1], _p(probs), _p(dctx), _p(dqc), _p(dkv),
          nseq, L, H, dropout_p, seed, io_f16, _stream())
+
+
+def attention_fwd_f32(qkv, mask, ctx, nseq, L, H, cu=None, qc=None):
+    """fp32 attention of the fp32 evaluation pass (csrc/encoder_f32.hip): ``ctx = softmax(Q K^T / 8 + key mask) V``, head dim 64, L <= 256.
+    Full form (``qc`` None): ``qkv`` fp32 [T, 3*H*64], ``ctx`` [T, H*64].  CLS form (``qc`` fp32 [nseq, H*64], a row pitch allowed): ``qkv`` is
+    K | V of every token, [T, 2*H*64], ``ctx`` [nseq, H*64] - bit for bit row 0 of the full form.  Layout: padded rows with ``mask`` (int64
+    [nseq, L] or None) or packed rows through ``cu`` (see _cu_rows), never both."""
+    what = "attention_fwd_f32"
+    d = H * 64
+    _chk(qkv, F32, "qkv", 2), _chk(ctx, F32, "ctx", 2)
+    if mask is not None:
+        _chk(mask, torch.int64, "mask", 2)
+        if not mask.is_contiguous() or tuple(mask.shape) != (nseq, L):
+            raise ValueError(f"{what}: mask must be contiguous int64 [nseq, L]")
+    mask_p, cu_p = _layout(mask, cu, None, 0, nseq, L, what)[:2]
+    if not (0 < L <= 256) or nseq < 1:
+        raise ValueError(f"{what}: need nseq > 0 and 0 < L <= 256")
+    rows = nseq * L if cu is None else 1
+    if qkv.shape[1] != (3 if qc is None else 2) * d or not qkv.is_contiguous() or qkv.shape[0] < rows:
+        raise ValueError(f"{what}: qkv must be contiguous [T, 3*H*64] (CLS form: K | V, [T, 2*H*64])")
+    if ctx.shape[1] != d or not ctx.is_contiguous() or ctx.shape[0] < (rows if qc is None else nseq):
+        raise ValueError(f"{what}: ctx must be contiguous [T, H*64] (CLS form: [nseq, H*64])")
+    if qc is None:
+        call("cldrd_attention_fwd_f32", _p(qkv), mask_p, cu_p, _p(ctx), nseq, L, H, _stream())
+    else:
+        _chk(qc, F32, "qc", 2)
+        if qc.shape[1] != d or qc.shape[0] < nseq:
+            raise ValueError(f"{what}: qc must be [nseq, H*64]")
+        call("cldrd_attention_cls_fwd_f32", _p(qc), qc.stride(0), _p(qkv), mask_p, cu_p, _p(ctx), nseq, L, H, _stream())
+    return ctx
 
 
 def add_rows(dst, src, M, stride=0, idx=None):

@@ -173,8 +173,9 @@ class CrossEncoder(nn.Module):
         return logits[:, 0] if self.num_labels == 1 else torch.log_softmax(logits, dim=-1)[:, 1]
 
     @torch.no_grad()
-    def forward(self, batch):
-        """``batch``: the reference collate's ``query_passage`` dict - padded ``input_ids`` / ``attention_mask`` (right padding) and, for
+    def forward(self, batch, fp32: bool = False):
+        """``fp32=True``: the body runs the exact fp32 evaluation pass (HipEncoder.encode(fp32=True)); the head is fp32 in both modes.
+        ``batch``: the reference collate's ``query_passage`` dict - padded ``input_ids`` / ``attention_mask`` (right padding) and, for
         BERT, ``token_type_ids`` - on the host or the device.  Returns fp32 logits [M, num_labels].  The encoder packs the batch (token
         counts from the mask)."""
         dev = self._device()
@@ -187,11 +188,11 @@ class CrossEncoder(nn.Module):
         lengths = mask.to("cpu").sum(1).tolist()
         tt = batch.get("token_type_ids") if self.cfg.arch == "bert" else None
         cls = self.encoder.encode(ids.to(dev), mask.to(dev), train=False, lengths=lengths,
-                                  token_type_ids=None if tt is None else tt.to(dev))
+                                  token_type_ids=None if tt is None else tt.to(dev), fp32=fp32)
         return self._head(cls)
 
     @torch.no_grad()
-    def score_cached(self, q_cache, p_cache, q_rows, p_rows, max_len: int | None = None):
+    def score_cached(self, q_cache, p_cache, q_rows, p_rows, max_len: int | None = None, fp32: bool = False):
         """Scores fp32 [n] of the pairs (query row q_rows[i] of ``q_cache``, passage row p_rows[i] of ``p_cache``); the caches are
         ``TokenCache`` / ``SequenceTokenCache`` tables (``[CLS] text [SEP]`` rows).  A cache built at a smaller max_length than the pairs'
         could have cut tokens a pair keeps: refused.  (Texts of more than max_length - 2 tokens on BOTH sides are seen at their cached
@@ -199,7 +200,10 @@ class CrossEncoder(nn.Module):
 
         A pair's score does not depend on the other pairs of the call (bit for bit, for a given max_len): the pass runs at least
         MIN_PASS_PAIRS pairs (large-M GEMM kernels only) and chooses its attention kernels for sequences of max_len tokens, so that every
-        pair's arithmetic depends on its own length only.  (``forward`` on a padded batch gives no such guarantee.)"""
+        pair's arithmetic depends on its own length only.  (``forward`` on a padded batch gives no such guarantee.)
+
+        ``fp32=True``: the body runs the exact fp32 evaluation pass.  Its kernels have one schedule for every shape, so the same guarantee
+        holds without padding pairs."""
         dev = self._device()
         max_len = self.max_len if max_len is None else int(max_len)
         if max_len > self.max_len:
@@ -217,7 +221,7 @@ class CrossEncoder(nn.Module):
         n = q_rows.shape[0]
         nq = np.asarray(q_cache.lens[q_rows], dtype=np.int64) - 2
         npp = np.asarray(p_cache.lens[p_rows], dtype=np.int64) - 2
-        if n < MIN_PASS_PAIRS:
+        if n < MIN_PASS_PAIRS and not fp32:
             fill = int(np.argmin(np.maximum(nq, 0) + np.maximum(npp, 0)))          # padding pairs: copies of the shortest one
             q_rows = np.concatenate([q_rows, np.full(MIN_PASS_PAIRS - n, q_rows[fill])])
             p_rows = np.concatenate([p_rows, np.full(MIN_PASS_PAIRS - n, p_rows[fill])])
@@ -230,5 +234,5 @@ class CrossEncoder(nn.Module):
         def i32(a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         ids, types, pos = ops.build_pairs(q_tok, q_lens, p_tok, p_lens, q_idx, p_idx, i32(keep_q), i32(keep_p), i32(cu), int(cu[-1]))
-        cls = self.encoder.encode(None, None, train=False, lengths=lengths.tolist(), packed=(ids, types, pos, max_len))
+        cls = self.encoder.encode(None, None, train=False, lengths=lengths.tolist(), packed=(ids, types, pos, max_len), fp32=fp32)
         return self.scores(self._head(cls))[:n]

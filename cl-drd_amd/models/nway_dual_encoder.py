@@ -50,6 +50,9 @@ class NwayDualEncoder(nn.Module):
         # bf16 like everything else.  With shared weights the one tower keeps an fp16 shadow too and only query calls use it.
         self.query_fp16 = self.query_encoder.amp_mode == "fp16"
         self.query_encoder.hp_forward = self.query_fp16
+        # True: query_embs / passage_embs / nway_passage_embs run the exact fp32 evaluation pass (HipEncoder.encode(fp32=True): the
+        # reference's use_fp16=False encode).  Evaluation only - there is no fp32 tape: with gradients enabled they raise.
+        self.eval_fp32 = False
 
     # -- reference call surface -------------------------------------------------------------------------------
     def forward(self, queries, nway_passages):
@@ -61,11 +64,20 @@ class NwayDualEncoder(nn.Module):
         mode = score_mode(self.in_batch_loss, self.all_in_batch_neg)
         return torch.ops.cldrd.nway_score(query_reps, nway_passage_reps.reshape(bz * nway, D), bz, nway, mode)
 
+    def _embs_fp32(self, enc, ids, mask, lengths=None):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in enc.parameters()):
+            raise RuntimeError("eval_fp32 is an evaluation mode (there is no fp32 tape): call under torch.no_grad(), or set eval_fp32 = False to train")
+        return enc.encode(ids, mask, train=False, lengths=lengths, fp32=True)
+
     def query_embs(self, queries):
+        if self.eval_fp32:
+            return self._embs_fp32(self.query_encoder, queries["input_ids"], queries.get("attention_mask"), _lengths(queries))
         return encode_autograd(self.query_encoder, queries["input_ids"], queries.get("attention_mask"), fp16=self.query_fp16)
 
     def passage_embs(self, passages):
         # "lengths" (ours, optional: host-side token counts, one per sequence): the batch is packed (encoder.HipEncoder.encode)
+        if self.eval_fp32:
+            return self._embs_fp32(self.passage_encoder, passages["input_ids"], passages.get("attention_mask"), _lengths(passages))
         return encode_autograd(self.passage_encoder, passages["input_ids"], passages.get("attention_mask"), fp16=False,
                                lengths=_lengths(passages))
 
@@ -73,7 +85,10 @@ class NwayDualEncoder(nn.Module):
         input_ids, attention_mask = nway_passages["input_ids"], nway_passages["attention_mask"]
         bz, nway, seq_len = input_ids.shape
         input_ids, attention_mask = input_ids.reshape(bz * nway, seq_len), attention_mask.reshape(bz * nway, seq_len)
-        passage_reps = encode_autograd(self.passage_encoder, input_ids, attention_mask, fp16=False, lengths=_lengths(nway_passages))
+        if self.eval_fp32:
+            passage_reps = self._embs_fp32(self.passage_encoder, input_ids, attention_mask, _lengths(nway_passages))
+        else:
+            passage_reps = encode_autograd(self.passage_encoder, input_ids, attention_mask, fp16=False, lengths=_lengths(nway_passages))
         return passage_reps.view(bz, nway, -1)
 
     # -- MI355X-specific ----------------------------------------------------------------------------------------

@@ -37,6 +37,7 @@ _FLAGS = {
     "token_cache_stem": dict(default=""),                 # ours: memory-map an EXISTING token cache by its file stem (no collection / tokenizer opened)
     "loader_workers": dict(type=int, default=2),          # ours: DataLoader workers of the token-cache path
     "index_fp16": dict(action="store_true", default=False),      # ours: write the fp16-row index format (mean row + centred fp16 rows: half the file)
+    "fp32_encode": dict(action="store_true", default=False),     # ours: encode with the exact fp32 evaluation pass (get_embeddings_from_scratch(use_fp16=False))
     "bucket_window": dict(type=int, default=16384),       # ours (token-cache path): rows are batched by LENGTH inside windows of this many rows (0: 512 consecutive rows)
 }
 
@@ -116,7 +117,7 @@ def main(args):
                                         bucket_window=int(getattr(args, "bucket_window", 0)))
 
     lap("open_collection_s")
-    text_embs, text_ids = get_embeddings_from_scratch(model, text_loader, use_fp16=True, is_query=args.is_query, show_progress_bar=True)
+    text_embs, text_ids = get_embeddings_from_scratch(model, text_loader, use_fp16=not getattr(args, "fp32_encode", False), is_query=args.is_query, show_progress_bar=True)
     lap("encode_s")
     text_id_to_idx = {tid: idx for idx, tid in enumerate(text_ids)}
     print("embs dtype: ", text_embs.dtype)

@@ -42,6 +42,8 @@ def get_args(argv=None):
                     help="pairs per encoder batch (2048: profiles/rerank_teacher_timing.txt; fewer than 1024 are padded to 1024)")
     ap.add_argument("--token_cache_dir", default="")
     ap.add_argument("--output_path", required=True)
+    ap.add_argument("--fp32_encode", action="store_true", default=False,
+                    help="run the cross-encoder body in the exact fp32 evaluation pass (CrossEncoder.score_cached(fp32=True))")
     return ap.parse_args(argv)
 
 
@@ -112,7 +114,8 @@ def main(args):
         _, _, lengths, _ = pair_lengths(np.asarray(q_cache.lens)[q_rows] - 2, np.asarray(p_cache.lens)[p_rows] - 2, args.max_len)
         scores = np.empty(q_rows.shape[0], dtype=np.float32)
         for b in length_batches(lengths, args.batch_size):
-            scores[b] = model.score_cached(q_cache, p_cache, q_rows[b], p_rows[b], args.max_len).cpu().numpy()
+            scores[b] = model.score_cached(q_cache, p_cache, q_rows[b], p_rows[b], args.max_len,
+                                            **({"fp32": True} if getattr(args, "fp32_encode", False) else {})).cpu().numpy()
     # within a query: score descending, ties in run order (the pairs are already grouped by query, in run order)
     order = np.lexsort((np.arange(scores.shape[0]), -scores.astype(np.float64), group))
     pids, scores = pids[order], scores[order]

@@ -88,15 +88,31 @@ def batch_to_device(batch, target_device: torch.device):
 
 def get_embeddings_from_scratch(model, dataloader, use_fp16, is_query, show_progress_bar=False):
     """Encode every batch of ``dataloader`` ({"seq": {input_ids, attention_mask}, "id": list[int]}) with the query or
-    passage tower in eval mode -> (np.float32 [n, D], list[int]).  ``use_fp16`` is accepted for signature compatibility:
-    the towers always run 16-bit MFMA compute (evaluation: fp16 operands in the FFN / out-projection GEMMs, bf16 QKV / attention) with fp32
-    accumulate, fp32 residual stream and fp32 CLS output (the reference's output is fp32 too, :56).
+    passage tower in eval mode -> (np.float32 [n, D], list[int]).
+
+    ``use_fp16`` is the reference's flag (:30-58: autocast only when it is set).  True: the towers' 16-bit evaluation pass (fp16 operands in
+    the FFN / out-projection GEMMs, bf16 QKV / attention, fp32 accumulate, fp32 residual stream, fp32 CLS output).  False: the exact fp32
+    evaluation pass (``HipEncoder.encode(fp32=True)``: fp32 operands on the f32-input MFMA, weights read from the fp32 master copy) - the
+    model's ``eval_fp32`` is set for the duration of the call and restored afterwards, also when the loader raises; a model without that
+    attribute is left alone.  The output is fp32 in both modes (the reference's too, :56).
 
     The host side of the loop is timed (``get_embeddings_from_scratch.last_timings``, seconds): ``load_s`` waiting for the loader (tokens
     from the cache / tokeniser), ``h2d_enqueue_s`` moving the batch and enqueuing the encode, ``d2h_wait_s`` waiting for the PREVIOUS
     batch's embeddings (the GPU's encode of it, as far as the host sees it: one batch of D2H stays in flight), ``gather_s`` collecting the
     rows.  When the loader knows its row count (``dataset.n_rows``: the token-cache and synthetic datasets) the [n, D] result is allocated
     once and filled in place; the reference appends per-batch arrays and concatenates 27 GB at the end (:51)."""
+    if use_fp16 or not hasattr(model, "eval_fp32"):
+        return _embeddings_from_scratch(model, dataloader, is_query)
+    before = model.eval_fp32
+    model.eval_fp32 = True
+    try:
+        return _embeddings_from_scratch(model, dataloader, is_query)
+    finally:
+        model.eval_fp32 = before
+
+
+def _embeddings_from_scratch(model, dataloader, is_query):
+    """The loop of :func:`get_embeddings_from_scratch` in whichever arithmetic mode the model is in."""
     import time
     tm = {"load_s": 0.0, "h2d_enqueue_s": 0.0, "d2h_wait_s": 0.0, "gather_s": 0.0, "batches": 0}
     embeddings, embeddings_ids = [], []

@@ -30,6 +30,7 @@ _FLAGS = {
     "share_weights": dict(action="store_true", default=False),
     "output_path": dict(default=""),
     "synthetic_queries": dict(type=int, default=0),       # ours: N generated queries instead of --queries_path
+    "fp32_encode": dict(action="store_true", default=False),     # ours: encode the queries with the exact fp32 evaluation pass (use_fp16=False)
     "use_float16": dict(action="store_true", default=False),      # ours: attach the index in fp16-row mode (convert_index_to_gpu(..., useFloat16=True))
 }
 
@@ -117,7 +118,7 @@ def main(args):
         tokenizer = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path)
         dataset = SequenceDataset.create_from_seqs_file(args.queries_path, tokenizer, args.max_length, is_query=True)
         loader = torch.utils.data.DataLoader(dataset, batch_size=512, shuffle=False, num_workers=4, collate_fn=dataset.collate_fn)
-    query_embs, query_ids = get_embeddings_from_scratch(model, loader, use_fp16=True, is_query=True, show_progress_bar=True)
+    query_embs, query_ids = get_embeddings_from_scratch(model, loader, use_fp16=not getattr(args, "fp32_encode", False), is_query=True, show_progress_bar=True)
     lap("encode_queries_s")
 
     path = args.index_path

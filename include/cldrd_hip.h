@@ -133,6 +133,22 @@ int cldrd_attention_cls_bwd(const void* qc, const void* kv, const int* cu_rows, 
                             int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* stream);
 int cldrd_add_rows(void* dst, const void* src, int M, int d, int stride_rows, const int* idx, int fmt, void* stream);
 
+/* ---- the fp32 evaluation pass (csrc/encoder_f32.hip): the reference's `use_fp16=False` encode, retriever/retrieval_utils.py:30-58 ----------
+ * Every operand fp32, accumulation on the f32-input MFMA (bit for bit a k-ordered fmaf chain).  Each op has ONE schedule, whatever the shape:
+ * a row's result does not depend on which other rows share the launch, so packed == padded and a batch == its sequences alone, bit for bit.
+ * Evaluation only: no dropout, no LSE, no keep bits, no tape.
+ * cldrd_gemm_nt_f32: C[M,N] = A[M,K] . W[N,K]^T -> + bias[N] (optional) -> erf-GELU (act = 1, erff) -> + residual[M,N] (optional, pitch ldr).
+ *   K % 32 == 0, N % 8 == 0, any M > 0; A and W 16-byte aligned, lda and ldw multiples of 4; W is the fp32 master weight, read in place.
+ * cldrd_attention_fwd_f32: ctx[rows, H*64] = softmax(Q K^T / 8 + key mask) V from qkv fp32 [rows, 3*H*64]; layouts as cldrd_attention_fwd
+ *   (padded rows + int64 mask or NULL, or packed rows through cu_rows - never both; no lists); L <= 256.  A masked key contributes exactly zero.
+ * cldrd_attention_cls_fwd_f32: the CLS form - qc: [nseq, H*64] queries of token 0 with row pitch ldq; kv: [rows, 2*H*64] = K | V of every token,
+ *   padded or packed as above; ctx: [nseq, H*64].  Bit for bit row 0 of the full form. */
+int cldrd_gemm_nt_f32(const float* A, const float* W, float* C, int M, int N, int K, int lda, int ldw, int ldc, const float* bias,
+                      const float* residual, int ldr, int act, void* stream);
+int cldrd_attention_fwd_f32(const float* qkv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L, int H, void* stream);
+int cldrd_attention_cls_fwd_f32(const float* qc, int ldq, const float* kv, const long long* mask, const int* cu_rows, float* ctx, int nseq,
+                                int L, int H, void* stream);
+
 /* ---- embeddings + LayerNorm (HF Embeddings.forward, sa_layer_norm / output_layer_norm) --------------------
  * d <= 1024, d % 4 == 0.  `partial` scratch: cldrd_ln_partial_blocks(T) * 3 * d floats. */
 int cldrd_ln_partial_blocks(int T);
