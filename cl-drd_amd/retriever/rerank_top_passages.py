@@ -5,6 +5,9 @@ training data: every training query's top-k student candidates re-scored by the 
         --model_name_or_path DIR --tokenizer_name_or_path TOK --output_path OUT [--max_len 256] [--top_k K] [--batch_size B]
         [--token_cache_dir DIR]
 
+``--dual_encoder [--resume CKPT] [--share_weights] [--query_max_len 30] [--passage_max_len 256]`` is the student mode: the same run, files,
+``--top_k``, ``--token_cache_dir``, ``--fp32_encode`` and output rules, scored by the dual encoder through ``evaluation.DevPool``.
+
 ``RUN``: ``qid pid [rank] [score]`` lines; ``Q.tsv`` / ``C.tsv``: ``id\\ttext``; ``DIR``: an HF BertForSequenceClassification /
 DistilBertForSequenceClassification directory.  Both tables are tokenised once into token caches built at ``--max_len`` (kept in
 ``--token_cache_dir`` when given), pairs are assembled on the GPU from the cache rows and scored in batches of similar length.
@@ -38,13 +41,23 @@ def get_args(argv=None):
     ap.add_argument("--tokenizer_name_or_path", default=None, help="default: --model_name_or_path")
     ap.add_argument("--max_len", type=int, default=256)
     ap.add_argument("--top_k", type=int, default=0, help="candidates per query, in run order (0: all)")
-    ap.add_argument("--batch_size", type=int, default=2048,
-                    help="pairs per encoder batch (2048: profiles/rerank_teacher_timing.txt; fewer than 1024 are padded to 1024)")
+    ap.add_argument("--batch_size", type=int, default=None,
+                    help="pairs per encoder batch (default 2048: profiles/rerank_teacher_timing.txt; fewer than 1024 are padded to 1024); "
+                         "--dual_encoder: sequences per encoder batch (default 512)")
     ap.add_argument("--token_cache_dir", default="")
     ap.add_argument("--output_path", required=True)
     ap.add_argument("--fp32_encode", action="store_true", default=False,
                     help="run the cross-encoder body in the exact fp32 evaluation pass (CrossEncoder.score_cached(fp32=True))")
-    return ap.parse_args(argv)
+    ap.add_argument("--dual_encoder", action="store_true", default=False,
+                    help="student mode: re-score with the dual encoder --model_name_or_path [--resume CKPT] instead of a cross-encoder")
+    ap.add_argument("--resume", default="", help="--dual_encoder: trainer checkpoint (checkpoint_<step>.pth.tar) loaded into the student")
+    ap.add_argument("--share_weights", action="store_true", default=False)
+    ap.add_argument("--query_max_len", type=int, default=30)
+    ap.add_argument("--passage_max_len", type=int, default=256)
+    args = ap.parse_args(argv)
+    if args.batch_size is None:
+        args.batch_size = 512 if args.dual_encoder else 2048
+    return args
 
 
 def query_groups(qid):
@@ -63,24 +76,30 @@ def read_run(path, top_k=0):
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")                         # (an empty file)
         a = np.loadtxt(path, dtype=np.int64, usecols=(0, 1), ndmin=2)
-    qid, pid = a[:, 0], a[:, 1]
+    return group_pairs(a[:, 0], a[:, 1], top_k)[:4]
+
+
+def group_pairs(qid, pid, top_k=0):
+    """:func:`read_run` on the two id columns (int64 arrays, one entry per line): (qids, pids, group, starts, src), ``src[i]`` = the line pair
+    i came from."""
+    qid, pid = np.asarray(qid, dtype=np.int64), np.asarray(pid, dtype=np.int64)
     # one entry per distinct pair, the first occurrence
     _, first = np.unique(np.stack([qid, pid], 1), axis=0, return_index=True)
-    keep = np.sort(first)
-    qid, pid = qid[keep], pid[keep]
+    src = np.sort(first)
+    qid, pid = qid[src], pid[src]
     # queries by first appearance; pairs grouped by query, run order inside
     group, n_q = query_groups(qid)
     order = np.argsort(group, kind="stable")
-    qid, pid, group = qid[order], pid[order], group[order]
+    qid, pid, group, src = qid[order], pid[order], group[order], src[order]
     counts = np.bincount(group, minlength=n_q)
     starts = np.zeros(n_q + 1, dtype=np.int64)
     np.cumsum(counts, out=starts[1:])
     if top_k > 0:
         sel = np.arange(qid.shape[0]) - starts[group] < top_k
-        qid, pid, group = qid[sel], pid[sel], group[sel]
+        qid, pid, group, src = qid[sel], pid[sel], group[sel], src[sel]
         counts = np.minimum(counts, top_k)
         np.cumsum(counts, out=starts[1:])
-    return qid, pid, group, starts
+    return qid, pid, group, starts, src
 
 
 def length_batches(lengths, batch_size):
@@ -89,7 +108,35 @@ def length_batches(lengths, batch_size):
     return [order[i:i + batch_size] for i in range(0, order.shape[0], batch_size)]
 
 
+def main_dual_encoder(args):
+    """``--dual_encoder``: the run re-scored by the student through an evaluation.DevPool (every distinct query and passage encoded once,
+    score = the flat search's exact re-score of the two CLS embeddings); output format and ordering rules as the teacher mode's."""
+    from ..evaluation.dev_pool import DevPool
+    from ..evaluation.reranking_evaluator import evaluation_state
+    from ..models.nway_dual_encoder import NwayDualEncoder
+    from .index_text import load_checkpoint_into
+    if max(args.query_max_len, args.passage_max_len) > 256 or args.batch_size < 1:
+        raise ValueError("--query_max_len / --passage_max_len are at most 256, --batch_size at least 1")
+    torch.cuda.set_device(0)
+    from transformers import AutoTokenizer
+    tokenizer = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path or args.model_name_or_path)
+    model = NwayDualEncoder(args.model_name_or_path, share_weights=args.share_weights)
+    if args.resume:
+        load_checkpoint_into(model, args.resume)
+    model.cuda()
+    model.eval_fp32 = bool(args.fp32_encode)
+    pool = DevPool(args.run_path, args.queries_path, args.collection_path, tokenizer, args.query_max_len, args.passage_max_len,
+                   top_k=args.top_k, token_cache_dir=args.token_cache_dir)
+    with evaluation_state(model):
+        scores = pool.score(model, args.batch_size)
+    total = write_ranked_run(args.output_path, pool.qids, pool.pids, pool.group, pool.starts, scores)
+    print(f"re-scored {total} pairs of {pool.n_queries} queries")
+    return total
+
+
 def main(args):
+    if getattr(args, "dual_encoder", False):
+        return main_dual_encoder(args)
     if args.max_len > 256 or args.batch_size < 1:
         raise ValueError("--max_len is at most 256, --batch_size at least 1")
     torch.cuda.set_device(0)
@@ -116,18 +163,29 @@ def main(args):
         for b in length_batches(lengths, args.batch_size):
             scores[b] = model.score_cached(q_cache, p_cache, q_rows[b], p_rows[b], args.max_len,
                                             **({"fp32": True} if getattr(args, "fp32_encode", False) else {})).cpu().numpy()
-    # within a query: score descending, ties in run order (the pairs are already grouped by query, in run order)
-    order = np.lexsort((np.arange(scores.shape[0]), -scores.astype(np.float64), group))
-    pids, scores = pids[order], scores[order]
+    total = write_ranked_run(args.output_path, qids, pids, group, starts, scores)
+    print(f"re-scored {total} pairs of {starts.shape[0] - 1} queries")
+    return total
+
+
+def rank_order(group, scores):
+    """Positions of the pairs in output order: queries as they are, inside a query score descending, ties in run order (the pairs arrive
+    grouped by query in run order) - what the reference's stable sort does."""
+    scores = np.asarray(scores)
+    return np.lexsort((np.arange(scores.shape[0]), -scores.astype(np.float64), group))
+
+
+def write_ranked_run(path, qids, pids, group, starts, scores):
+    """``qid\\tpid\\trank\\tscore`` of the pairs of :func:`read_run` ranked by :func:`rank_order`: the native writer when every query has the
+    same number of candidates (the usual top-k run), the writer's Python loop for a ragged run."""
+    order = rank_order(group, scores)
+    pids, scores = pids[order], np.ascontiguousarray(np.asarray(scores)[order], dtype=np.float32)
     q_out = qids[starts[:-1]]
     counts = np.diff(starts)
     if counts.shape[0] and (counts == counts[0]).all() and counts[0] > 0:
-        total = write_run_file(args.output_path, q_out.tolist(), pids.reshape(-1, counts[0]), scores.reshape(-1, counts[0]))
-    else:
-        total = write_run_file(args.output_path, q_out.tolist(), [pids[a:b].tolist() for a, b in zip(starts[:-1], starts[1:])],
-                               [scores[a:b].tolist() for a, b in zip(starts[:-1], starts[1:])])
-    print(f"re-scored {total} pairs of {q_out.shape[0]} queries")
-    return total
+        return write_run_file(path, q_out.tolist(), pids.reshape(-1, counts[0]), scores.reshape(-1, counts[0]))
+    return write_run_file(path, q_out.tolist(), [pids[a:b].tolist() for a, b in zip(starts[:-1], starts[1:])],
+                          [scores[a:b].tolist() for a, b in zip(starts[:-1], starts[1:])])
 
 
 if __name__ == "__main__":

@@ -19,7 +19,10 @@ Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
     (default ``lambda_mrr`` as in the reference);
   * ``--distill_loss kl_div | margin_mse`` adds ``distill_alpha * kd(logits[:, :nway], batch["teacher_scores"])`` to that loss (one more
     launch on the loss stream, ``cldrd_distill_term``): the role of the knowledge-distillation trainers the reference's scripts name
-    (``scripts/unity/kd_nway_listwise.sh``, ``logit_reg_nway_listwise.sh``) but never published.
+    (``scripts/unity/kd_nway_listwise.sh``, ``logit_reg_nway_listwise.sh``) but never published;
+  * ``--dev_path / --dev_queries_path / --dev_qrels_path`` (the reference's flags): at every saved checkpoint rank 0 re-ranks the dev run with
+    the student (``NwayTrainer.validate``: evaluation.DevPool + RerankingEvaluator) and writes ``dev_logs.log`` / ``dev_best.json``; the
+    reference tokenises and encodes every (query, passage) pair of the run per validation, here each distinct text once.
 """
 from __future__ import annotations
 
@@ -789,6 +792,17 @@ class NwayTrainer:
             return 0.0, 0.0
         return float(np.sum(1.0 / (keep + 1.0)) / len(first)), float(len(keep) / len(first))
 
+    # ---- validation on a dev run (the reference's launch scripts pass --dev_path ...; its trainers import RerankingEvaluator) --
+    def validate(self, pool, evaluator, batch_size: int = 512) -> dict:
+        """The metrics of ``evaluator`` (evaluation.RerankingEvaluator) for the student as it stands, re-ranking the dev run ``pool``
+        (evaluation.DevPool).  Training goes on as if it had not been called: an evaluation pass writes no parameter, moment or gradient
+        and no step state; the evaluator puts ``model.training`` and the towers' dropout step counters back; the evaluation forward
+        launches eagerly from the ordinary allocator, so the captured graphs (their private memory pool, their static inputs) stay as they
+        are and the next step of a captured shape is a replay.  The weight shadows need nothing new: an evaluation forward casts what is
+        stale before it reads it (HipEncoder._shadows_ok), and the next step - `_adamw_launches`, or the replay site of
+        `_train_step_graph` - marks the bf16 shadow stale again."""
+        return evaluator.compute_metrics_pool(self.model, pool, batch_size=batch_size)
+
     # ---- checkpoint payload (reference nway_listwise_1.py:418-426 / :300-304) --------------------------------------------
     def _optimizer_names(self):
         return optimizer_param_groups(self.model)
@@ -943,7 +957,21 @@ def get_args(argv=None):
     ap.add_argument("--synthetic_fixed", action="store_true", default=False, help="every synthetic passage passage_max_len tokens long (default: MS MARCO-shaped lengths)")
     ap.add_argument("--synthetic_model", default="distilbert", choices=("distilbert", "tiny"),
                     help="random-init architecture for --synthetic_steps runs without a model directory (tiny: encoder.tiny_config)")
+    # validation while training (the reference scripts' names, scripts/unity/*.sh): at every checkpoint rank 0 re-ranks the dev run with the student
+    ap.add_argument("--dev_path", default=None, help="dev run file (qid pid [rank] [score]) the student re-ranks at every evaluate_steps")
+    ap.add_argument("--dev_queries_path", default=None)
+    ap.add_argument("--dev_qrels_path", default=None)
+    ap.add_argument("--dev_top_k", default=0, type=int, help="candidates per dev query, in run order (0: all)")
+    ap.add_argument("--dev_batch_size", default=512, type=int, help="sequences per encoder batch of a validation")
+    ap.add_argument("--dev_qrels_trec", action="store_true", default=False, help="--dev_qrels_path is space separated (TREC)")
     args = ap.parse_args(argv)
+    dev_flags = [args.dev_path, args.dev_queries_path, args.dev_qrels_path]
+    if any(v is not None for v in dev_flags) and not all(v is not None for v in dev_flags):
+        ap.error("--dev_path, --dev_queries_path and --dev_qrels_path go together: all three or none")
+    if args.dev_path is not None and args.synthetic_steps > 0:
+        ap.error("--dev_path needs --collection_path for the passage texts; --synthetic_steps runs have no collection file")
+    if args.dev_path is not None and (args.dev_batch_size < 1 or args.dev_top_k < 0):
+        ap.error("--dev_batch_size must be >= 1 and --dev_top_k >= 0")
     if args.distill_loss is None and args.distill_only:
         ap.error("--distill_only needs --distill_loss")
     if args.distill_loss is not None and args.label_mode == "1" and args.synthetic_steps <= 0:
@@ -1105,6 +1133,40 @@ def batch_to_device(batch, dev):
     return out
 
 
+class _DevValidation:
+    """``--dev_path`` / ``--dev_queries_path`` / ``--dev_qrels_path`` of a training run (rank 0): the dev pool built once, then one
+    ``NwayTrainer.validate`` per saved checkpoint - a line of ``<log_dir>/dev_logs.log`` and ``<run_folder>/dev_best.json`` rewritten."""
+
+    def __init__(self, args):
+        from transformers import AutoTokenizer
+        from ..evaluation import DevPool, RerankingEvaluator
+        tok = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path)
+        self.pool = DevPool(args.dev_path, args.dev_queries_path, args.collection_path, tok, args.query_max_len, args.passage_max_len,
+                            top_k=args.dev_top_k, token_cache_dir=args.token_cache_dir)
+        self.evaluator = RerankingEvaluator(args.dev_qrels_path, is_trec=args.dev_qrels_trec)
+        self.batch_size = args.dev_batch_size
+        self.log_file = os.path.join(args.log_dir, "dev_logs.log")
+        self.best_file = os.path.join(args.run_folder, "dev_best.json")
+        self.best = None
+        if args.resume and os.path.exists(self.best_file):        # a resumed run goes on from the best it had
+            import json
+            with open(self.best_file) as fh:
+                self.best = json.load(fh)
+
+    def validate(self, trainer, epoch, ckpt_path):
+        import time
+        from ..evaluation.reranking_evaluator import update_dev_best, write_dev_logs
+        t0 = time.perf_counter()
+        metrics = trainer.validate(self.pool, self.evaluator, batch_size=self.batch_size)
+        write_dev_logs(self.log_file, epoch, trainer.global_step, metrics, time.perf_counter() - t0)
+        self.best = update_dev_best(self.best_file, self.best, metrics, trainer.global_step, epoch, ckpt_path)
+        return metrics
+
+
+def _dev_validation(args):
+    return _DevValidation(args) if getattr(args, "dev_path", None) else None
+
+
 def train(args):
     """Epoch / step loop of reference :328-426 on top of NwayTrainer.train_step."""
     import random
@@ -1154,6 +1216,7 @@ def train(args):
     if main_rank:
         os.makedirs(args.log_dir, exist_ok=True)
         os.makedirs(args.model_save_dir, exist_ok=True)
+    dev_run = _dev_validation(args) if main_rank else None      # None without --dev_path: nothing below changes
     loss_m, mrr_m, rec_m, reg_m, ratio_m, kd_m = _Avg(), _Avg(), _Avg(), _Avg(), _Avg(), _Avg()
     topk = 10
     log_file = os.path.join(args.log_dir, "train_logs.log")
@@ -1190,7 +1253,11 @@ def train(args):
             if main_rank and trainer.global_step % args.evaluate_steps == 0:
                 ckpt = trainer.state_dict()
                 ckpt["epoch"] = epoch + 1
-                torch.save(ckpt, os.path.join(args.model_save_dir, f"checkpoint_{trainer.global_step}.pth.tar"))
+                ckpt_path = os.path.join(args.model_save_dir, f"checkpoint_{trainer.global_step}.pth.tar")
+                torch.save(ckpt, ckpt_path)
+                if dev_run is not None:
+                    # rank 0 alone, no collective: the other ranks meet it at the next step's first all-reduce
+                    dev_run.validate(trainer, epoch + 1, ckpt_path)
     if args.distributed:
         dist.barrier()
     return trainer
