@@ -295,8 +295,18 @@ class HipEncoder(nn.Module):
         self.flat_h16 = None        # fp16 shadow (same layout): only towers that run the high-precision forward keep one
         self.hp_forward = False     # set by NwayDualEncoder on the query tower (see encode)
         self.flat_t = None          # transposed bf16 shadows
-        self._t_desc = None
+        self._t_desc = self._t_desc64 = None        # the batched transposes' descriptors (_build_t_desc)
         self._shadow_version = -1
+        self._h_stale = False       # the optimizer step left the bf16 shadow unwritten (refresh_shadows(h_stale=True))
+        self._t_fresh = False       # flat_t holds the transposes of the current shadows
+        self._view_cache = {}       # _cached
+        self._own_scale = None      # loss-scale state of a backward outside the trainer (backward_steps)
+        self._anchor = None         # encode_autograd's graph anchor
+        # set by the trainer:
+        self.seed_base_ptr = None           # device address of this tower's per-step dropout seed word (`device_seed` passes)
+        self.wgrad_flush_layers = 0         # launch the deferred weight gradients every so many layers (0: once, at the end of the backward)
+        self.norm_sink = None               # fp32 slots for the clip norm's partial sums of the one flush that writes every layer gradient
+        self.norm_sink_used = -1            # ... slots that flush of the last backward wrote (-1: it had no sink)
         self._names = list(self.layout.order)
         for name in self._names:
             off, shape = self.layout.entries[name]
@@ -315,8 +325,7 @@ class HipEncoder(nn.Module):
         #       gradient cosines 0.99+ (tests/test_gpu_model.py states the bars of each mode).
         # Both modes keep what the reference's autocast keeps in fp32: master weights, the residual stream (pre-LN sums, LayerNorm statistics),
         # softmax, the CLS output; the gradient of the residual path is fp32 in bf16 mode (fp16 + loss scale in fp16 mode) and every
-        # parameter gradient is fp32.  The operand-format sub-switches of rounds 3-5 (CLDRD_FFN_FP16, _OUT_FP16, _QKV_FP16, _QUERY_FP16,
-        # _RESIDUAL, _GRAD_STREAM, _LN_ON_THE_FLY) are gone: the hybrid "bf16 tape, fp16 forward" mode they spanned is not a supported mode.
+        # parameter gradient is fp32.  There is no hybrid "bf16 tape, fp16 forward" mode and no per-operand switch.
         mode = os.environ.get("CLDRD_AMP", "fp16")
         if mode not in ("fp16", "bf16"):
             raise ValueError(f"CLDRD_AMP must be fp16 or bf16, got {mode!r}")
@@ -353,7 +362,7 @@ class HipEncoder(nn.Module):
         from a view shares the base tensor's version counter, so ``optimizer.step()`` / ``load_state_dict`` / any in-place
         write through a parameter bumps ``flat_p._version`` and the bf16 shadows are known to be stale.  (Rebinding with
         ``param.data = view`` would give each parameter a private counter: torch 2.10.)"""
-        self.__dict__.pop("_view_cache", None)         # cached parameter views belong to the buffers being replaced
+        self._view_cache = {}                          # cached parameter views belong to the buffers being replaced
         old = dict(self.named_parameters())
         for n in self._names:
             off, shape = self.layout.entries[n]
@@ -378,7 +387,6 @@ class HipEncoder(nn.Module):
     def adopt_flat(self, flat_p: torch.Tensor, flat_g: torch.Tensor | None = None):
         """Move this tower's parameters into a slice of a model-level flat buffer (same device)."""
         assert flat_p.numel() == self.layout.total and flat_p.dtype == torch.float32
-        self.__dict__.pop("_view_cache", None)
         flat_p.copy_(self.flat_p.to(flat_p.device))
         self._rebind(flat_p)
         self.flat_g = flat_g
@@ -422,19 +430,24 @@ class HipEncoder(nn.Module):
             self._bind_grads()
 
     # Views of one parameter inside the flat buffers.  They are looked up ~250 times per training step; slicing + reshaping a tensor
-    # costs ~2.5 us, so the views are cached per (buffer identity, name) - a flat buffer that is replaced (`.to()`, adopt_flat,
-    # a new shadow) has another data_ptr and simply misses.
-    def _view(self, flat, tag, name):
-        cache = self.__dict__.setdefault("_view_cache", {})
-        key = (tag, name)
-        hit = cache.get(key)
-        ptr = flat.data_ptr()
-        if hit is not None and hit[0] == ptr:
-            return hit[1]
-        off, shape = self.layout.entries[name]
-        v = flat[off:off + _numel(shape)].view(shape)
-        cache[key] = (ptr, v)
+    # costs ~2.5 us, so the views (and the per-layer tables of them) are cached per (key, buffer identity) - a flat buffer that is
+    # replaced (`.to()`, adopt_flat, a new shadow) has another data_ptr and simply misses.
+    def _cached(self, key, build, mat, vec, what):
+        """``build(mat, vec, what)``, built again only when ``mat`` or ``vec`` (a flat buffer, or None) is not the buffer it was built from"""
+        hit = self._view_cache.get(key)
+        pm, pv = mat.data_ptr(), (0 if vec is None else vec.data_ptr())
+        if hit is not None and hit[0] == pm and hit[1] == pv:
+            return hit[2]
+        v = build(mat, vec, what)
+        self._view_cache[key] = (pm, pv, v)
         return v
+
+    def _param_view(self, flat, _, name):
+        off, shape = self.layout.entries[name]
+        return flat[off:off + _numel(shape)].view(shape)
+
+    def _view(self, flat, tag, name):
+        return self._cached((tag, name), self._param_view, flat, None, name)
 
     def g(self, name):
         return self._view(self.flat_g, "g", name)
@@ -478,7 +491,7 @@ class HipEncoder(nn.Module):
 
     @property
     def grad_stream16(self):
-        """the gradient stream is fp16 between kernels (round 5; only in the all-fp16 training mode, see __init__)"""
+        """the gradient stream is fp16 between kernels (only in the all-fp16 training mode, see __init__)"""
         return self.amp16 and self._grad_stream16
 
     @property
@@ -544,68 +557,43 @@ class HipEncoder(nn.Module):
 
     def _shadows_ok(self, need_t, need_h=True):
         return (self.flat_h is not None and self._shadow_version == self.flat_p._version and (not self.needs_h16 or self.flat_h16 is not None) and
-                (not need_h or not getattr(self, "_h_stale", False)) and
-                (not need_t or (self.flat_t is not None and getattr(self, "_t_fresh", False))))
+                (not need_h or not self._h_stale) and (not need_t or (self.flat_t is not None and self._t_fresh)))
 
     def ht(self, layer, key):
         off, shp = self.layout.t_entries[layer][key]
         return self.flat_t[off:off + shp[0] * shp[1]].view(shp)
 
     # ------------------------------------------------------------------ forward
+    def _layer_views(self, mat, vec, i):
+        """The parameters of layer ``i`` as views of two flat buffers: the four matrices from ``mat``, biases and LayerNorm parameters from ``vec``"""
+        n, d, entries = layer_param_names(self.cfg, i), self.cfg.dim, self.layout.entries
+        oq, ob = entries[n["q"] + ".weight"][0], entries[n["q"] + ".bias"][0]
+
+        def v(flat, name):
+            off, shape = entries[name]
+            return flat[off:off + _numel(shape)].view(shape)
+        return dict(Wqkv=mat[oq:oq + 3 * d * d].view(3 * d, d), bqkv=vec[ob:ob + 3 * d],
+                    Wo=v(mat, n["o"] + ".weight"), bo=v(vec, n["o"] + ".bias"),
+                    g1=v(vec, n["ln1"] + ".weight"), b1=v(vec, n["ln1"] + ".bias"),
+                    W1=v(mat, n["f1"] + ".weight"), bf1=v(vec, n["f1"] + ".bias"),
+                    W2=v(mat, n["f2"] + ".weight"), bf2=v(vec, n["f2"] + ".bias"),
+                    g2=v(vec, n["ln2"] + ".weight"), b2=v(vec, n["ln2"] + ".bias"))
+
     def _layer_weights(self, i, fp16=False):
-        sh0 = self.flat_h16 if fp16 else self.flat_h
-        ck = ("W", i, bool(fp16))
-        cache = self.__dict__.setdefault("_view_cache", {})
-        hit = cache.get(ck)
-        if hit is not None and hit[0] == (sh0.data_ptr(), self.flat_p.data_ptr()):
-            return hit[1]
-        W = self._layer_weights_build(i, fp16)
-        cache[ck] = ((sh0.data_ptr(), self.flat_p.data_ptr()), W)
-        return W
-
-    def _layer_weights_build(self, i, fp16=False):
-        cfg, n = self.cfg, layer_param_names(self.cfg, i)
-        d = cfg.dim
-        oq = self.layout.entries[n["q"] + ".weight"][0]
-        ob = self.layout.entries[n["q"] + ".bias"][0]
-        sh = self.flat_h16 if fp16 else self.flat_h
-
-        def h(name):
-            off, shape = self.layout.entries[name]
-            return sh[off:off + _numel(shape)].view(shape)
-        return dict(Wqkv=sh[oq:oq + 3 * d * d].view(3 * d, d), bqkv=self.flat_p[ob:ob + 3 * d],
-                    Wo=h(n["o"] + ".weight"), bo=self.w(n["o"] + ".bias"),
-                    g1=self.w(n["ln1"] + ".weight"), b1=self.w(n["ln1"] + ".bias"),
-                    W1=h(n["f1"] + ".weight"), bf1=self.w(n["f1"] + ".bias"),
-                    W2=h(n["f2"] + ".weight"), bf2=self.w(n["f2"] + ".bias"),
-                    g2=self.w(n["ln2"] + ".weight"), b2=self.w(n["ln2"] + ".bias"))
+        """16-bit shadows of the matrices (fp16 or bf16), fp32 biases and LayerNorm parameters"""
+        return self._cached(("W", i, bool(fp16)), self._layer_views, self.flat_h16 if fp16 else self.flat_h, self.flat_p, i)
 
     def _layer_grads(self, i):
-        ck = ("G", i)
-        cache = self.__dict__.setdefault("_view_cache", {})
-        hit = cache.get(ck)
-        if hit is not None and hit[0] == self.flat_g.data_ptr():
-            return hit[1]
-        G = self._layer_grads_build(i)
-        cache[ck] = (self.flat_g.data_ptr(), G)
-        return G
+        return self._cached(("G", i), self._layer_views, self.flat_g, self.flat_g, i)
 
-    def _layer_grads_build(self, i):
-        cfg, n = self.cfg, layer_param_names(self.cfg, i)
-        d = cfg.dim
-        oq = self.layout.entries[n["q"] + ".weight"][0]
-        ob = self.layout.entries[n["q"] + ".bias"][0]
-        return dict(Wqkv=self.flat_g[oq:oq + 3 * d * d].view(3 * d, d), bqkv=self.flat_g[ob:ob + 3 * d],
-                    Wo=self.g(n["o"] + ".weight"), bo=self.g(n["o"] + ".bias"),
-                    g1=self.g(n["ln1"] + ".weight"), b1=self.g(n["ln1"] + ".bias"),
-                    W1=self.g(n["f1"] + ".weight"), bf1=self.g(n["f1"] + ".bias"),
-                    W2=self.g(n["f2"] + ".weight"), bf2=self.g(n["f2"] + ".bias"),
-                    g2=self.g(n["ln2"] + ".weight"), b2=self.g(n["ln2"] + ".bias"))
+    def _layer_weights_f32(self, i):
+        """The fp32 master weights as views of ``flat_p`` (no shadows): the fp32 evaluation pass"""
+        return self._cached(("W32", i), self._layer_views, self.flat_p, self.flat_p, i)
 
     @staticmethod
     def _buf(rows, cols, dev, dtype=torch.bfloat16):
         # rows rounded up to 64: allocation granularity only (no kernel reads past `rows`; the weight-gradient kernel takes the
-        # missing token rows of its last K tile from a zero page, so nothing is zero-filled here - round 1 spent 102 fills a step)
+        # missing token rows of its last K tile from a zero page, so nothing is zero-filled here)
         return torch.empty(ops.pad_rows(rows), cols, dtype=dtype, device=dev)
 
     def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None, *, train: bool | None = None,
@@ -650,36 +638,40 @@ class HipEncoder(nn.Module):
             return Stepper(self._encode_f32_gen(input_ids, attention_mask, lengths=lengths, window=window, token_type_ids=token_type_ids,
                                                 packed=packed))
         fp16 = self.hp_forward if fp16 is None else fp16
-        base = getattr(self, "seed_base_ptr", None) if (device_seed and seed is None) else None
-        if token_type_ids is not None or packed is not None:
+        # `device_seed` (NwayTrainer only): the per-step part of the seed lives in device memory at `seed_base_ptr` (the trainer advances
+        # step_seed and writes next_seed() there before each step); the launches carry offsets only.  Any other caller (encode_autograd,
+        # an explicit seed) gets a by-value seed - the device word is only advanced by the trainer.
+        base = self.seed_base_ptr if (device_seed and seed is None) else None
+        plain = token_type_ids is None and packed is None
+        if not plain:
             if save or base:
                 raise ValueError("token_type_ids / packed rows: evaluation passes only (no tape, no device seed)")
             if fp16 and self.amp16:
                 raise ValueError("token_type_ids / packed rows run the tower's evaluation pass; the all-fp16 pass (fp16=True / hp_forward) is not supported there")
-            if seed is None:
-                seed = self.next_seed()
-            return Stepper(self._encode_gen(input_ids, attention_mask, train=train, save=False, seed=seed, fp16=False, lengths=lengths,
-                                            window=window, token_type_ids=token_type_ids, packed=packed))
+        all_fp16 = self._is_all_fp16_pass(save, fp16, input_ids, plain)
+        if all_fp16 and not save:
+            lengths = None                      # the query tower's evaluation pass stays padded
         if base:
-            # graph mode, NwayTrainer only (`device_seed`): the per-step part of the seed lives in device memory at `seed_base_ptr` (the
-            # trainer advances step_seed and writes next_seed() there before each step); the launches carry offsets only.  Any other
-            # caller (encode_autograd, an explicit seed) gets a by-value seed as before - the device word is only advanced by the trainer.
-            gen = self._encode_pair(input_ids, attention_mask, train=train, save=save, seed=0, fp16=fp16, lengths=lengths, window=window)
-
-            def mark(gen=gen):
-                out = yield from gen
-                if save:
-                    out[1].device_seed = True           # the backward adds the same device word
-                return out
-            return Stepper(mark(), [lambda: ops.seed_base(base)])
-        if seed is None:
+            seed = 0
+        elif seed is None:
             seed = self.next_seed()
-        return Stepper(self._encode_pair(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=fp16, lengths=lengths, window=window))
+        gen = self._encode_gen(input_ids, attention_mask, train=train, save=save, seed=seed, all_fp16=all_fp16, lengths=lengths, window=window,
+                               token_type_ids=token_type_ids, packed=packed)
+        if not base:
+            return Stepper(gen)
 
-    def would_pack(self, lengths, M, L, has_mask=True, fp16=False, train=True) -> bool:
+        def mark():
+            out = yield from gen
+            if save:
+                out[1].device_seed = True           # the backward adds the same device word
+            return out
+        return Stepper(mark(), [lambda: ops.seed_base(base)])
+
+    def would_pack(self, lengths, M, L, has_mask=True, fp16=False, train=True, always=False) -> bool:
         """Whether encode() packs a batch with these host-side token counts (CLDRD_PACK=0 turns packing off; thresholds at the
         end: a training batch with less than 8 % padding keeps its graph replay, an evaluation batch packs from 3 % padding).  The trainer asks BEFORE choosing between the replayed graph and the
-        eager step: only a batch that really is packed changes its row count from step to step."""
+        eager step: only a batch that really is packed changes its row count from step to step.  ``always``: the rule of the fp32 evaluation
+        pass, whose kernels treat a row independently of the launch it is in (packed == padded bit for bit at any size): no thresholds."""
         if (lengths is None or not has_mask or (fp16 and not self.amp16) or not self.cls_only_last or self.cfg.n_layers < 1 or L <= 1
                 or _env_flag("CLDRD_PACK", "1") == "0"):
             return False
@@ -688,6 +680,8 @@ class HipEncoder(nn.Module):
             # the packed kernels take every sequence to own 1 .. L rows (cldrd_attention_*_varlen, CLS row = first row): anything else - an empty
             # row of a partially filled batch, counts that do not belong to this batch - stays on the padded path, which reads the mask
             return False
+        if always:
+            return True
         n_tok = sum(lens)
         if n_tok < 1024 <= M * L:
             # packing would move the Linear layers from the large-M GEMM kernel to the small-M one (split along K: another summation order), and
@@ -702,23 +696,21 @@ class HipEncoder(nn.Module):
         self.step_seed += 1
         return (self.step_seed * 0x9E3779B1) & 0x7FFFFFFFFFFF
 
-    def _encode_pair(self, input_ids, attention_mask, *, train, save, seed, fp16, lengths=None, window=None):
-        """The generator of the pass that runs (see __init__, CLDRD_AMP).  fp16 mode: a pass that keeps a tape is the all-fp16 pass; an
-        evaluation pass of the query tower (``fp16``: hp_forward) is the all-fp16 pass too, any other evaluation pass reads fp16 operands in
-        the FFN / out-projection GEMMs and bf16 in QKV / attention.  bf16 mode: one pass, every operand bf16 (``fp16`` is ignored)."""
-        if self.amp16:
-            if save:
-                return self._encode_gen(input_ids, attention_mask, train=train, save=True, seed=seed, fp16=True, lengths=lengths, window=window)
-            if fp16 and self.hp_forward and input_ids.dim() == 2 and input_ids.shape[1] <= 128:
-                return self._encode_gen(input_ids, attention_mask, train=train, save=False, seed=seed, fp16=True, window=window)
-        return self._encode_gen(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=False, lengths=lengths, window=window)
+    def _is_all_fp16_pass(self, save, fp16, input_ids, plain=True) -> bool:
+        """Which of the two 16-bit passes runs (see __init__, CLDRD_AMP).  fp16 mode: a pass that keeps a tape is the all-fp16 pass; an
+        evaluation pass of the query tower (``fp16`` asked for on a tower with hp_forward; a plain [M, L <= 128] batch without token types or
+        packed rows) is the all-fp16 pass too; any other evaluation pass reads fp16 operands in the FFN / out-projection GEMMs and bf16 in QKV /
+        attention.  bf16 mode: one pass, every operand bf16 (``fp16`` is ignored)."""
+        if not self.amp16:
+            return False
+        return bool(save or (fp16 and self.hp_forward and plain and input_ids.dim() == 2 and input_ids.shape[1] <= 128))
 
-    def _encode_gen(self, input_ids, attention_mask, *, train, save, seed, fp16, lengths=None, window=None, token_type_ids=None, packed=None):
-        """one forward pass as a generator: a ``yield`` behind every group of launches (:class:`Stepper`); returns cls or (cls, tape)"""
-        cfg = self.cfg
-        train = self.training if train is None else train
+    def _prepare_batch(self, input_ids, attention_mask, lengths, token_type_ids, packed, **pack_rule):
+        """What every pass does with its batch before the first layer: check it, move ids / mask / token types to the device and pack the rows -
+        always for ``packed`` rows, else where ``would_pack(..., **pack_rule)`` says so.  -> M, L, T (rows of the activations), ids, mask, tt, pk"""
+        cfg, dev = self.cfg, self.flat_p.device
         if packed is not None:
-            if lengths is None or len(lengths) < 1 or not self.cls_only_last or cfg.n_layers < 1 or save:
+            if lengths is None or len(lengths) < 1 or not self.cls_only_last or cfg.n_layers < 1:
                 raise ValueError("packed rows need host lengths, an evaluation pass and the CLS-only last layer")
             M, L = len(lengths), int(max(lengths))
             if len(packed) > 3:
@@ -733,57 +725,66 @@ class HipEncoder(nn.Module):
             M, L = input_ids.shape
         if L > 256 or L > cfg.max_position_embeddings:
             raise ValueError("sequence length must be <= 256 (and <= max_position_embeddings)")
-        dev = self.flat_p.device
-        if not self._shadows_ok(save, need_h=not (self.amp16 and save)):      # (the all-fp16 training pass reads the fp16 shadow only)
-            self.refresh_shadows(need_transposed=save)
-        typed = token_type_ids is not None and cfg.arch == "bert"      # (DistilBERT has no token-type table)
-        if packed is None:
-            ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-            mask = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
-            tt = token_type_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous() if typed else None
-        else:
-            mask = None
-        T, d, f, H = M * L, cfg.dim, cfg.hidden_dim, cfg.n_heads
-        p_h = cfg.dropout if train else 0.0
-        p_a = cfg.attention_dropout if train else 0.0
-        dt16 = torch.float16 if fp16 else torch.bfloat16         # 16-bit activation format of this pass
-        pk = None
         if lengths is not None and len(lengths) != M:
             raise ValueError("lengths: one entry per sequence")
         if packed is not None:
             pk = _Pack.build(lengths, L, dev)
-            T = pk.Tp
             ids, tt, pk.pos = packed[:3]
-            if ids.numel() != T or pk.pos.numel() != T or (tt is not None and tt.numel() != T):
+            if ids.numel() != pk.Tp or pk.pos.numel() != pk.Tp or (tt is not None and tt.numel() != pk.Tp):
                 raise ValueError("packed rows: ids / token types / positions must hold sum(lengths) rows")
-            tt = tt if cfg.arch == "bert" else None
-        elif self.would_pack(lengths, M, L, has_mask=mask is not None, fp16=fp16, train=save):
-            pk = _Pack.build(lengths, L, dev)
-            T = pk.Tp
-            ids_padded, ids = ids, ops.gather_i64(ids.reshape(-1), pk.tok_idx, T)
-            if tt is not None:
-                tt = ops.gather_i64(tt, pk.tok_idx, T)          # the same row index as the ids
+            return M, L, pk.Tp, ids, None, (tt if cfg.arch == "bert" else None), pk
+        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+        mask = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
+        typed = token_type_ids is not None and cfg.arch == "bert"      # (DistilBERT has no token-type table)
+        tt = token_type_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous() if typed else None
+        if not self.would_pack(lengths, M, L, has_mask=mask is not None, **pack_rule):
+            return M, L, M * L, ids, mask, tt, None
+        pk = _Pack.build(lengths, L, dev)
+        ids = ops.gather_i64(ids.reshape(-1), pk.tok_idx, pk.Tp)
+        if tt is not None:
+            tt = ops.gather_i64(tt, pk.tok_idx, pk.Tp)          # the same row index as the ids
+        return M, L, pk.Tp, ids, mask, tt, pk
+
+    def _encode_gen(self, input_ids, attention_mask, *, train, save, seed, all_fp16, lengths=None, window=None, token_type_ids=None, packed=None):
+        """One 16-bit forward pass as a generator: a ``yield`` behind every group of launches (:class:`Stepper`); returns cls or (cls, tape).
+        ``all_fp16``: the all-fp16 pass (:meth:`_is_all_fp16_pass`), else the evaluation pass of the tower's mode or the bf16 training pass."""
+        cfg = self.cfg
+        train = self.training if train is None else train
+        dev = self.flat_p.device
+        if not self._shadows_ok(save, need_h=not (self.amp16 and save)):      # (the all-fp16 training pass reads the fp16 shadow only)
+            self.refresh_shadows(need_transposed=save)
+        M, L, T, ids, mask, tt, pk = self._prepare_batch(input_ids, attention_mask, lengths, token_type_ids, packed, fp16=all_fp16, train=save)
+        d, f, H = cfg.dim, cfg.hidden_dim, cfg.n_heads
+        p_h = cfg.dropout if train else 0.0
+        p_a = cfg.attention_dropout if train else 0.0
+        dt16 = torch.float16 if all_fp16 else torch.bfloat16         # 16-bit activation format of this pass
         tape = None
         if save:
             tape = _Tape()
             tape.M, tape.L, tape.T, tape.ids, tape.mask, tape.seed, tape.layers = M, L, T, ids, mask, seed, []
             tape.p_embed, tape.pack, tape.device_seed = p_h, pk, False
         f32 = dict(dtype=torch.float32, device=dev)
-        # QKV16 (evaluation pass of the fp16 mode, towers deeper than 6 layers): the QKV projection reads fp16 operands too (bf16 q / k / v
-        # out: that pass's attention kernels are bf16).  With the FFN pair in fp16, x_in / Wqkv are the next largest source of logit drift
-        # (BERT-base cfg4 golden: 0.190 -> 0.116); the 6-layer configs are at 2-3.5e-3 without it and would only pay for it.
-        QKV16 = self.ffn_fp16 and not fp16 and cfg.n_layers > 6
-        if QKV16 and save:
+        # FFN16 (fp16 mode, evaluation pass): the FFN and out-projection GEMMs read fp16 operands - the LayerNorm in front of the FFN writes
+        # fp16, FFN1 leaves h in fp16, and the attention kernel leaves its context in fp16 instead of bf16.  With the FFN pair on fp16
+        # operands the out-projection is the rounding point that carries most of what is left of the logit drift (CPU emulation on the
+        # goldens, DESIGN.md section 2: BERT-base 5.25e-3 -> 2.08e-3 of the logit scale, DistilBERT 2.98e-3 -> 2.05e-3).
+        # QKV16 (the same pass on towers deeper than 6 layers): the QKV projection reads fp16 operands too - the layer input is fp16; q / k / v
+        # come out in bf16, that pass's attention kernels are bf16.  x_in / Wqkv are the next largest source of logit drift (BERT-base cfg4
+        # golden: 0.190 -> 0.116); the 6-layer configs are at 2-3.5e-3 without it and would only pay for it.
+        FFN16 = self.ffn_fp16 and not all_fp16
+        QKV16 = FFN16 and cfg.n_layers > 6
+        if FFN16 and save:
             raise RuntimeError("a pass that keeps a tape runs one operand format (fp16 or bf16), never the evaluation pass's mixed one")
-        x = self._buf(T, d, dev, dt16) if not QKV16 else None
-        xh = self._buf(T, d, dev, torch.float16) if QKV16 else None
+        fdt = torch.float16 if FFN16 else dt16                # format of the FFN pair's and the out-projection's activation operands
+        xdt = torch.float16 if QKV16 else dt16                # format of the 16-bit layer input
+        x = self._buf(T, d, dev, xdt)
         x32 = self._buf(T, d, dev, torch.float32)           # fp32 copy of the layer input: the residual operand
         mean0, rstd0 = torch.empty(T, **f32), torch.empty(T, **f32)
         if window is not None:
             window("ln")
         ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"), self.w("embeddings.position_embeddings.weight"),
                          self.w("embeddings.token_type_embeddings.weight") if cfg.arch == "bert" else None, self.w("embeddings.LayerNorm.weight"),
-                         self.w("embeddings.LayerNorm.bias"), xh if QKV16 else x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
+                         self.w("embeddings.LayerNorm.bias"), x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
                          pos_idx=pk.pos if pk is not None else None, type_ids=tt.to(torch.int32) if tt is not None else None)
         if save:
             tape.mean0, tape.rstd0 = mean0, rstd0
@@ -794,73 +795,49 @@ class HipEncoder(nn.Module):
         # FFN2 epilogue.  It is not stored: that epilogue reads the pre-LN sum (which the backward keeps anyway) and applies mean / rstd /
         # gamma / beta on the fly (`residual_ln`) - 100 MB less written per LayerNorm at cfg2, the same bytes read.
         res_ln = None                                        # LayerNorm still to be applied to x32 (None: x32 is the value itself)
-        FFN16 = self.ffn_fp16 and not fp16              # fp16 mode, evaluation pass: the FFN and out-projection GEMMs read fp16 operands (the
-        OUT16 = FFN16                                   # attention kernel leaves its context in fp16 for the out-projection)
-        if FFN16 and save:
-            raise RuntimeError("a pass that keeps a tape runs one operand format (fp16 or bf16), never the evaluation pass's mixed one")
         for i in range(cfg.n_layers):
-            W = self._layer_weights(i, fp16)
+            W = self._layer_weights(i, all_fp16)
             W16 = self._layer_weights(i, True) if FFN16 else None
+            Wf = W16 if FFN16 else W                         # the matrices the FFN pair and the out-projection read
             s_l = seed + 7919 * (i + 1)
             if i == cfg.n_layers - 1 and self.cls_only_last:
-                yield from self._last_layer_cls_fwd(x, x32, W, mask, M, L, T, p_h, p_a, p_out, s_l, save, tape, cls, dt16, W16, pk, xh, out16=OUT16)
+                yield from self._last_layer_cls_fwd(x, x32, W, mask, M, L, T, p_h, p_a, p_out, s_l, save, tape, cls, dt16, W16, pk)
                 break
             qkv = self._buf(T, 3 * d, dev, dt16)
-            if QKV16:
-                ops.gemm_nt(xh, W16["Wqkv"], qkv, T, bias=W["bqkv"])          # fp16 operands, bf16 q / k / v
-            else:
-                ops.gemm_nt(x, W["Wqkv"], qkv, T, bias=W["bqkv"])
+            ops.gemm_nt(x, (W16 if QKV16 else W)["Wqkv"], qkv, T, bias=W["bqkv"])
             lse = torch.empty(M, H, L, **f32) if save else None
-            dbits = ops.attention_drop_bits(M, L, H, p_a, dev) if (save and (dt16 == torch.bfloat16 or self.amp16)) else None      # dropout keep bits for the backward
-            # OUT16: the out-projection on fp16 operands too - the attention kernel leaves its context in fp16 next to (training) or
-            # instead of (evaluation) the bf16 tensor the backward's MFMAs read.  With the FFN pair already on fp16 operands this is the
-            # rounding point that carries most of what is left of the logit drift (CPU emulation on the goldens, DESIGN.md section 2:
-            # BERT-base 5.25e-3 -> 2.08e-3 of the logit scale, DistilBERT 2.98e-3 -> 2.05e-3).
-            ctx16 = self._buf(T, d, dev, torch.float16) if OUT16 else None
+            dbits = ops.attention_drop_bits(M, L, H, p_a, dev) if save else None      # dropout keep bits for the backward
+            ctx16 = self._buf(T, d, dev, torch.float16) if FFN16 else None
             # packed batch: the attention kernels find a sequence's rows through cu (keys beyond its length masked, padding rows neither
-            # loaded nor stored: cldrd_attention_*_varlen) - bit for bit what moving the rows to the padded [M * L, .] layout and back
-            # gave until round 6 (two row moves per layer and pass, 0.56 ms of an 8.3-ms MS MARCO-shaped training step)
+            # loaded nor stored: cldrd_attention_*_varlen) - bit for bit what moving the rows to the padded [M * L, .] layout and back gives
             cu = pk.cu if pk is not None else None
-            ctx = self._buf(T, d, dev, dt16) if (save or not OUT16) else None
+            ctx = self._buf(T, d, dev, dt16) if not FFN16 else None
             yield
             if window is not None:
                 window("attn")
             for sl, tile in (pk.groups if pk is not None else [(None, 0)]):
                 ops.attention_fwd(qkv, mask if pk is None else None, ctx, lse, M, L, H, p_a, s_l + 1, drop_bits=dbits, ctx16=ctx16,
-                                  full_family=fp16 and self.amp16, cu=cu, seq_list=sl, tile=tile)
+                                  full_family=all_fp16, cu=cu, seq_list=sl, tile=tile)
             yield
             s1 = self._buf(T, d, dev, torch.float32)      # pre-LN sums are stored in fp32: the fp32 residual stream
-            ops.gemm_nt(ctx16 if OUT16 else ctx, (W16 if OUT16 else W)["Wo"], s1, T, bias=W["bo"], residual=x32, dropout_p=p_out,
-                        seed=s_l + 2, residual_ln=res_ln)
+            ops.gemm_nt(ctx16 if FFN16 else ctx, Wf["Wo"], s1, T, bias=W["bo"], residual=x32, dropout_p=p_out, seed=s_l + 2, residual_ln=res_ln)
             del ctx16
             yield
             if window is not None:
                 window("ln")
             mean1, rstd1 = torch.empty(T, **f32), torch.empty(T, **f32)
-            if FFN16:
-                # evaluation pass of the fp16 mode: LayerNorm -> fp16 (FFN1's operand); FFN1 -> h in fp16 (FFN2's operand); no tape
-                x1 = hbuf = pre = None
-                x1h = self._buf(T, d, dev, torch.float16)
-                ops.layernorm_fwd(s1, W["g1"], W["b1"], x1h, mean1, rstd1, T, cfg.eps)
-                yield
-                hh = self._buf(T, f, dev, torch.float16)
-                ops.gemm_nt(x1h, W16["W1"], hh, T, bias=W["bf1"], act=1)
-                yield
-                s2 = self._buf(T, d, dev, torch.float32)
-                ops.gemm_nt(hh, W16["W2"], s2, T, bias=W["bf2"], residual=s1, dropout_p=p_h, seed=s_l + 3, residual_ln=(mean1, rstd1, W["g1"], W["b1"]))
-                del x1h, hh
-            else:
-                x1 = self._buf(T, d, dev, dt16)
-                ops.layernorm_fwd(s1, W["g1"], W["b1"], x1, mean1, rstd1, T, cfg.eps)
-                yield
-                hbuf = self._buf(T, f, dev, dt16)
-                pre = self._buf(T, f, dev, dt16) if save else None
-                ops.gemm_nt(x1, W["W1"], hbuf, T, bias=W["bf1"], preact=pre, act=3 if save else 1)     # the tape keeps gelu'(pre-activation)
-                yield
-                s2 = self._buf(T, d, dev, torch.float32)
-                ops.gemm_nt(hbuf, W["W2"], s2, T, bias=W["bf2"], residual=s1, dropout_p=p_h, seed=s_l + 3, residual_ln=(mean1, rstd1, W["g1"], W["b1"]))
-            xo = self._buf(T, d, dev, dt16) if not QKV16 else None
-            xoh = self._buf(T, d, dev, torch.float16) if QKV16 else None
+            x1 = self._buf(T, d, dev, fdt)
+            ops.layernorm_fwd(s1, W["g1"], W["b1"], x1, mean1, rstd1, T, cfg.eps)
+            yield
+            hbuf = self._buf(T, f, dev, fdt)
+            pre = self._buf(T, f, dev, dt16) if save else None
+            ops.gemm_nt(x1, Wf["W1"], hbuf, T, bias=W["bf1"], preact=pre, act=3 if save else 1)     # the tape keeps gelu'(pre-activation)
+            yield
+            s2 = self._buf(T, d, dev, torch.float32)
+            ops.gemm_nt(hbuf, Wf["W2"], s2, T, bias=W["bf2"], residual=s1, dropout_p=p_h, seed=s_l + 3, residual_ln=(mean1, rstd1, W["g1"], W["b1"]))
+            if not save:
+                del x1, hbuf                                 # (only a tape still needs them)
+            xo = self._buf(T, d, dev, xdt)
             last = i == cfg.n_layers - 1
             # the CLS-only last layer gathers its fp32 residual rows from a stored copy: the layer before it still writes one
             need32 = not last and i + 1 == cfg.n_layers - 1 and self.cls_only_last
@@ -869,32 +846,18 @@ class HipEncoder(nn.Module):
             yield
             if window is not None:
                 window("ln")
-            ops.layernorm_fwd(s2, W["g2"], W["b2"], xoh if QKV16 else xo, mean2, rstd2, T, cfg.eps, cls if last else None, L, out32=xo32)
+            ops.layernorm_fwd(s2, W["g2"], W["b2"], xo, mean2, rstd2, T, cfg.eps, cls if last else None, L, out32=xo32)
             if save:
                 tape.layers.append(dict(x_in=x, qkv=qkv, ctx=ctx, lse=lse, dbits=dbits, s1=s1, mean1=mean1, rstd1=rstd1, x1=x1, pre=pre,
                                         h=hbuf, s2=s2, mean2=mean2, rstd2=rstd2, seed=s_l, p_h=p_h, p_a=p_a, p_out=p_out))
-            x, xh = xo, xoh
+            x = xo
             x32, res_ln = (xo32, None) if need32 else (s2, (mean2, rstd2, W["g2"], W["b2"]))
             yield
         if cfg.n_layers == 0:
-            src = x if x is not None else xh
-            cls.copy_(src.view(ops.pad_rows(T), d)[:T].view(M, L, d)[:, 0].float())
+            cls.copy_(x.view(ops.pad_rows(T), d)[:T].view(M, L, d)[:, 0].float())
         return (cls, tape) if save else cls
 
     # ------------------------------------------------------------------ the fp32 evaluation pass (csrc/encoder_f32.hip)
-    def _layer_weights_f32(self, i):
-        """The fp32 master weights of layer ``i`` as views of ``flat_p`` (no shadows)."""
-        cfg, n = self.cfg, layer_param_names(self.cfg, i)
-        d = cfg.dim
-        oq = self.layout.entries[n["q"] + ".weight"][0]
-        ob = self.layout.entries[n["q"] + ".bias"][0]
-        return dict(Wqkv=self.flat_p[oq:oq + 3 * d * d].view(3 * d, d), bqkv=self.flat_p[ob:ob + 3 * d],
-                    Wo=self.w(n["o"] + ".weight"), bo=self.w(n["o"] + ".bias"),
-                    g1=self.w(n["ln1"] + ".weight"), b1=self.w(n["ln1"] + ".bias"),
-                    W1=self.w(n["f1"] + ".weight"), bf1=self.w(n["f1"] + ".bias"),
-                    W2=self.w(n["f2"] + ".weight"), bf2=self.w(n["f2"] + ".bias"),
-                    g2=self.w(n["ln2"] + ".weight"), b2=self.w(n["ln2"] + ".bias"))
-
     def _encode_f32_gen(self, input_ids, attention_mask, *, lengths=None, window=None, token_type_ids=None, packed=None):
         """The exact fp32 evaluation pass as a generator (a ``yield`` behind every group of launches): embedding + LayerNorm, ``n_layers - 1`` full
         layers and the CLS-only last layer, fp32 activations only, weights from ``flat_p`` (``refresh_shadows`` is never reached).  Every kernel
@@ -902,48 +865,10 @@ class HipEncoder(nn.Module):
         bit) - except on a tower built without the CLS-only last layer (test hook), which stays padded and refuses ``packed``."""
         cfg = self.cfg
         cls_last = self.cls_only_last and cfg.n_layers >= 1
-        if packed is not None:
-            if lengths is None or len(lengths) < 1 or not cls_last:
-                raise ValueError("packed rows need host lengths and the CLS-only last layer")
-            M, L = len(lengths), int(max(lengths))
-            if len(packed) > 3:
-                if int(packed[3]) < L:
-                    raise ValueError("packed rows: width must be at least the longest sequence")
-                L = int(packed[3])
-            if min(lengths) < 1:
-                raise ValueError("packed rows: every sequence has at least one token")
-        elif input_ids.dim() != 2:
-            raise ValueError("input_ids must be [M, L]")
-        else:
-            M, L = input_ids.shape
-        if L > 256 or L > cfg.max_position_embeddings:
-            raise ValueError("sequence length must be <= 256 (and <= max_position_embeddings)")
-        if lengths is not None and len(lengths) != M:
-            raise ValueError("lengths: one entry per sequence")
-        dev = self.flat_p.device
-        typed = token_type_ids is not None and cfg.arch == "bert"      # (DistilBERT has no token-type table)
-        T, d, f, H = M * L, cfg.dim, cfg.hidden_dim, cfg.n_heads
-        pk, mask = None, None
-        if packed is not None:
-            pk = _Pack.build(lengths, L, dev)
-            T = pk.Tp
-            ids, tt, pk.pos = packed[:3]
-            if ids.numel() != T or pk.pos.numel() != T or (tt is not None and tt.numel() != T):
-                raise ValueError("packed rows: ids / token types / positions must hold sum(lengths) rows")
-            tt = tt if cfg.arch == "bert" else None
-        else:
-            ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-            mask = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
-            tt = token_type_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous() if typed else None
-            if lengths is not None and cls_last and mask is not None and L > 1 and _env_flag("CLDRD_PACK", "1") != "0":
-                lens = [int(v) for v in (lengths.reshape(-1).tolist() if hasattr(lengths, "reshape") else lengths)]
-                if min(lens) >= 1 and max(lens) <= L:          # (an empty row stays on the padded path, which reads the mask)
-                    pk = _Pack.build(lens, L, dev)
-                    T = pk.Tp
-                    ids = ops.gather_i64(ids.reshape(-1), pk.tok_idx, T)
-                    if tt is not None:
-                        tt = ops.gather_i64(tt, pk.tok_idx, T)
-                    mask = None
+        M, L, T, ids, mask, tt, pk = self._prepare_batch(input_ids, attention_mask, lengths, token_type_ids, packed, always=True)
+        if pk is not None:
+            mask = None
+        dev, d, f, H = self.flat_p.device, cfg.dim, cfg.hidden_dim, cfg.n_heads
         f32 = dict(dtype=torch.float32, device=dev)
         buf = lambda rows, cols: self._buf(rows, cols, dev, torch.float32)
         # the embedding / LayerNorm kernels always write a 16-bit copy next to their fp32 output: it goes to one scratch buffer nobody reads
@@ -1026,72 +951,53 @@ class HipEncoder(nn.Module):
         return cls
 
     # ------------------------------------------------------------------ last layer, CLS row only
-    def _last_layer_cls_fwd(self, x, x32, W, mask, M, L, T, p_h, p_a, p_out, s_l, save, tape, cls, dt16=torch.bfloat16, W16=None, pk=None, xh=None,
-                            out16=False):
+    def _last_layer_cls_fwd(self, x, x32, W, mask, M, L, T, p_h, p_a, p_out, s_l, save, tape, cls, dt16=torch.bfloat16, W16=None, pk=None):
         """Only ``last_hidden_state[:, 0, :]`` is consumed (reference models/nway_dual_encoder.py:52,56,64), so the last
         layer projects K and V for every token but Q, attention, out-proj, FFN and both LayerNorms for token 0 only:
-        identical CLS output, ~1/6 of the layer's FLOPs."""
+        identical CLS output, ~1/6 of the layer's FLOPs.  ``W16`` (the fp16 matrices): the evaluation pass of the fp16 mode - out-projection
+        and FFN pair on fp16 operands; where the layer input ``x`` is fp16 as well, so are the K / V / Q projections' operands (bf16
+        results), see _encode_gen."""
         cfg = self.cfg
         d, f, H = cfg.dim, cfg.hidden_dim, cfg.n_heads
-        dev = (x if x is not None else xh).device
+        dev = x.device
         f32 = dict(dtype=torch.float32, device=dev)
+        FFN16 = W16 is not None
+        Wq = W16 if (FFN16 and x.dtype != dt16) else W           # the matrices the K / V / Q projections read
+        Wf = W16 if FFN16 else W                                 # ... and the out-projection and the FFN pair
+        fdt = torch.float16 if FFN16 else dt16
         kv = self._buf(T, 2 * d, dev, dt16)
-        Q16 = xh is not None and W16 is not None              # fp16 operands for the K / V / Q projections (bf16 results), see _encode_gen
-        if Q16:
-            ops.gemm_nt(xh, W16["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
-        else:
-            ops.gemm_nt(x, W["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
+        ops.gemm_nt(x, Wq["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
         yield
         if pk is None:
             # the CLS rows are rows 0, L, 2L, ... of the layer input: STRIDED VIEWS (row pitch L * d), no copies - every consumer (the Q
-            # projection's A operand, its weight gradient's X operand, the out-projection's fp32 residual) takes a row pitch.  Until round 5
-            # two or three 6-us gather launches sat here, on the critical path between the towers' forward and the loss
-            xc = x[:T].view(M, L * d)[:, :d] if x is not None else None
-            xch = xh[:T].view(M, L * d)[:, :d] if Q16 else None
+            # projection's A operand, its weight gradient's X operand, the out-projection's fp32 residual) takes a row pitch, and no
+            # gather launch sits on the critical path between the towers' forward and the loss
+            xc = x[:T].view(M, L * d)[:, :d]
             xc32 = x32[:T].view(M, L * d)[:, :d]
         else:
-            xc = self._buf(M, d, dev, dt16) if x is not None else None          # 16-bit CLS rows: the weight gradient's operand (and, without Q16, the GEMM's)
-            xch = self._buf(M, d, dev, torch.float16) if Q16 else None
-            xc32 = self._buf(M, d, dev, torch.float32)
             # packed batch: the CLS token of sequence m is row cu[m]; the CLS attention kernel reads the packed K / V rows through cu
-            if xc is not None:
-                ops.gather_rows(x, pk.cls_idx, xc, M)
-            if Q16:
-                ops.gather_rows(xh, pk.cls_idx, xch, M)
-            ops.gather_rows(x32, pk.cls_idx, xc32, M)
+            xc = ops.gather_rows(x, pk.cls_idx, self._buf(M, d, dev, x.dtype), M)          # the Q projection's and its weight gradient's operand
+            xc32 = ops.gather_rows(x32, pk.cls_idx, self._buf(M, d, dev, torch.float32), M)
         qc = self._buf(M, d, dev, dt16)
-        if Q16:
-            ops.gemm_nt(xch, W16["Wqkv"][:d], qc, M, bias=W["bqkv"][:d])
-        else:
-            ops.gemm_nt(xc, W["Wqkv"][:d], qc, M, bias=W["bqkv"][:d])
-        out16 = out16 and W16 is not None                    # out-projection on fp16 operands (see _encode_gen)
-        ctxc = self._buf(M, d, dev, dt16) if (save or not out16) else None
-        ctxc16 = self._buf(M, d, dev, torch.float16) if out16 else None
+        ops.gemm_nt(xc, Wq["Wqkv"][:d], qc, M, bias=W["bqkv"][:d])
+        ctxc = self._buf(M, d, dev, dt16) if not FFN16 else None
+        ctxc16 = self._buf(M, d, dev, torch.float16) if FFN16 else None
         probs = torch.empty(M, H, L, **f32)
         ops.attention_cls_fwd(qc, kv, mask if pk is None else None, ctxc, probs, M, L, H, p_a, s_l + 1, ctx16=ctxc16,
                               cu=pk.cu if pk is not None else None)
         yield
         s1 = self._buf(M, d, dev, torch.float32)
-        ops.gemm_nt(ctxc16 if out16 else ctxc, (W16 if out16 else W)["Wo"], s1, M, bias=W["bo"], residual=xc32, dropout_p=p_out, seed=s_l + 2)
+        ops.gemm_nt(ctxc16 if FFN16 else ctxc, Wf["Wo"], s1, M, bias=W["bo"], residual=xc32, dropout_p=p_out, seed=s_l + 2)
         yield
         x1_32 = self._buf(M, d, dev, torch.float32)
         mean1, rstd1 = (torch.empty(M, **f32), torch.empty(M, **f32)) if save else (None, None)
-        if W16 is not None:                 # evaluation pass of the fp16 mode: the FFN pair on fp16 operands, as in the full layers (no tape)
-            x1 = hbuf = pre = None
-            x1h = self._buf(M, d, dev, torch.float16)
-            ops.layernorm_fwd(s1, W["g1"], W["b1"], x1h, mean1, rstd1, M, cfg.eps, out32=x1_32)
-            hh = self._buf(M, f, dev, torch.float16)
-            ops.gemm_nt(x1h, W16["W1"], hh, M, bias=W["bf1"], act=1)
-            s2 = self._buf(M, d, dev, torch.float32)
-            ops.gemm_nt(hh, W16["W2"], s2, M, bias=W["bf2"], residual=x1_32, dropout_p=p_h, seed=s_l + 3)
-        else:
-            x1 = self._buf(M, d, dev, dt16)
-            ops.layernorm_fwd(s1, W["g1"], W["b1"], x1, mean1, rstd1, M, cfg.eps, out32=x1_32)
-            hbuf = self._buf(M, f, dev, dt16)
-            pre = self._buf(M, f, dev, dt16) if save else None
-            ops.gemm_nt(x1, W["W1"], hbuf, M, bias=W["bf1"], preact=pre, act=3 if save else 1)
-            s2 = self._buf(M, d, dev, torch.float32)
-            ops.gemm_nt(hbuf, W["W2"], s2, M, bias=W["bf2"], residual=x1_32, dropout_p=p_h, seed=s_l + 3)
+        x1 = self._buf(M, d, dev, fdt)
+        ops.layernorm_fwd(s1, W["g1"], W["b1"], x1, mean1, rstd1, M, cfg.eps, out32=x1_32)
+        hbuf = self._buf(M, f, dev, fdt)
+        pre = self._buf(M, f, dev, dt16) if save else None
+        ops.gemm_nt(x1, Wf["W1"], hbuf, M, bias=W["bf1"], preact=pre, act=3 if save else 1)
+        s2 = self._buf(M, d, dev, torch.float32)
+        ops.gemm_nt(hbuf, Wf["W2"], s2, M, bias=W["bf2"], residual=x1_32, dropout_p=p_h, seed=s_l + 3)
         yield
         xo = self._buf(M, d, dev, dt16)
         mean2, rstd2 = (torch.empty(M, **f32), torch.empty(M, **f32)) if save else (None, None)
@@ -1101,9 +1007,9 @@ class HipEncoder(nn.Module):
                                     rstd1=rstd1, x1=x1, pre=pre, h=hbuf, s2=s2, mean2=mean2, rstd2=rstd2, seed=s_l, p_h=p_h,
                                     p_a=p_a, p_out=p_out))
 
-    def _last_layer_cls_bwd(self, i, a, tape, dcls, partial):
+    def _last_layer_cls_bwd(self, i, a, tape, dcls, partial, acc, wq, lnq):
         """Backward of :meth:`_last_layer_cls_fwd`; returns dL/d(layer input) as a full [T, d] tensor (fp32 with the fp32 gradient
-        stream, else bf16)."""
+        stream, else bf16).  ``acc``, ``wq``, ``lnq``: the accumulate flag and the two queues of the backward this is a part of (_backward_gen)."""
         cfg = self.cfg
         d, f, H = cfg.dim, cfg.hidden_dim, cfg.n_heads
         M, L, T = tape.M, tape.L, tape.T
@@ -1115,26 +1021,25 @@ class HipEncoder(nn.Module):
         gc = dcls.contiguous()                                          # dL/dCLS is the stream's first tensor: no rounding at all
         ds2 = buf(M, d, dev, torch.float32)      # this layer's M-row gradient stream stays fp32 in both modes
         ds2m = buf(M, d, dev)                                    # 16-bit MFMA operand of the next data-gradient GEMM
-        lnq = getattr(self, "_lnq", None)
         f32 = dict(dtype=torch.float32, device=dev)
         own = (lambda: torch.empty(ops.ln_partial_elems(M, d), **f32)) if lnq is not None else (lambda: partial)
         ops.layernorm_bwd(gc, a["s2"], a["mean2"], a["rstd2"], W["g2"], ds2, ds2m, G["g2"], G["b2"], G["bf2"], own(), M, p_h, s_l + 3,
-                          accumulate=self._acc, defer=lnq)
+                          accumulate=acc, defer=lnq)
         yield
         dF = ds2m if ds2m is not None else ds2
-        self._wq.add(dF, a["h"], G["W2"], M)
+        wq.add(dF, a["h"], G["W2"], M)
         dpre = buf(M, f, dev)
         ops.gemm_nt(dF, self.ht(i, "f2"), dpre, M, gelu_pre=a["pre"], act=2)
-        self._wq.add(dpre, a["x1"], G["W1"], M, dbias=G["bf1"])
+        wq.add(dpre, a["x1"], G["W1"], M, dbias=G["bf1"])
         dx1 = buf(M, d, dev, torch.float32)
         ops.gemm_nt(dpre, self.ht(i, "f1"), dx1, M, residual=ds2)
         yield
         ds1 = buf(M, d, dev, torch.float32)
         ds1m = buf(M, d, dev)
         ops.layernorm_bwd(dx1, a["s1"], a["mean1"], a["rstd1"], W["g1"], ds1, ds1m, G["g1"], G["b1"], G["bo"], own(), M, p_out, s_l + 2,
-                          accumulate=self._acc, defer=lnq)
+                          accumulate=acc, defer=lnq)
         dA = ds1m if ds1m is not None else ds1
-        self._wq.add(dA, a["ctx"], G["Wo"], M)
+        wq.add(dA, a["ctx"], G["Wo"], M)
         dctx = buf(M, d, dev)
         ops.gemm_nt(dA, self.ht(i, "o"), dctx, M)
         yield
@@ -1142,8 +1047,8 @@ class HipEncoder(nn.Module):
         pk = tape.pack
         dkv = buf(T, 2 * d, dev)                                    # (T = the packed row count of a packed batch)
         ops.attention_cls_bwd(a["qc"], a["kv"], a["probs"], dctx, dqc, dkv, M, L, H, p_a, s_l + 1, cu=pk.cu if pk is not None else None)
-        self._wq.add(dqc, a["xc"], G["Wqkv"][:d], M, dbias=G["bqkv"][:d])
-        self._wq.add(dkv, a["x_in"], G["Wqkv"][d:], T, dbias=G["bqkv"][d:])
+        wq.add(dqc, a["xc"], G["Wqkv"][:d], M, dbias=G["bqkv"][:d])
+        wq.add(dkv, a["x_in"], G["Wqkv"][d:], T, dbias=G["bqkv"][d:])
         yield
         wt = self.ht(i, "qkv")                                      # [d, 3d] = Wqkv^T
         # the [T, d] gradient this layer hands down: fp32 - or fp16 with the fp16 gradient stream (the layer's own M-row stream stays fp32:
@@ -1176,36 +1081,36 @@ class HipEncoder(nn.Module):
         """:meth:`backward_from_cls` as a :class:`Stepper`; ``window(kind)`` as in :meth:`encode_steps` (before LayerNorm / attention backward
         launches)."""
         contexts = []
-        base = getattr(self, "seed_base_ptr", None) if getattr(tape, "device_seed", False) else None
+        base = self.seed_base_ptr if tape.device_seed else None
         if base:
             contexts.append(lambda: ops.seed_base(base))
         if (self.amp16 and getattr(ops._TLS, "loss_scale", None) is None and tape.layers and tape.layers[-1] is not None
                 and tape.layers[-1]["h"].dtype == torch.float16):
             # an fp16 tape outside the trainer (the autograd bridge of the reference-style loop: dL/dCLS arrives unscaled): this tower scales
             # it by its own data-derived power of two (ops.loss_scale_adapt); parameter gradients come out unscaled
-            st = self.__dict__.get("_own_scale")
+            st = self._own_scale
             if st is None or st.device != self.flat_p.device:
-                st = self.__dict__["_own_scale"] = ops.new_loss_scale_state(self.flat_p.device)
+                st = self._own_scale = ops.new_loss_scale_state(self.flat_p.device)
             dcls = dcls.contiguous().clone()
             ops.loss_scale_adapt(dcls, None, st)
             contexts.append(lambda: ops.loss_scale(st.data_ptr()))
         return Stepper(self._backward_gen(tape, dcls, after_layer, accumulate, check_grads, before_last_wgrad, window), contexts)
 
     def _backward_gen(self, tape, dcls, after_layer, accumulate, check_grads, before_last_wgrad, window):
-        self._acc = bool(accumulate)
+        # `acc`, `wq` and `lnq` belong to THIS backward: a tower may have two of them alive at once (two tapes of a shared tower, two steppers)
+        acc = bool(accumulate)
         cfg = self.cfg
         self.ensure_grads(check_all=check_grads)
         # Weight gradients are deferred (hip_ops.WgradQueue): only the data gradients are on the critical path.  They are launched
         # as one group at the end of the backward, or every `wgrad_flush_layers` layers when somebody (the trainer's all-reduce
         # hooks) wants layers to complete early; `after_layer(i)` is only called once layer i's weight gradients have been launched.
-        self._wq = ops.WgradQueue()
-        # LayerNorm gamma / beta (and the preceding Linear's bias) gradients can be deferred likewise (CLDRD_LN_DEFER=1): each
-        # layernorm_bwd leaves its per-block sums in a scratch buffer of its own and one launch next to the weight-gradient group reduces
-        # them all.  Bit-identical and 22 launches fewer per step.  Round 2 kept it off (±0 at cfg2, slower on the then enqueue-bound
-        # cfg1); measured again in round 3 with the step replayed as a HIP graph: -1.0 % step time at cfg2, twice on one box
-        # (profiles/r03_microbench.txt): on by default, CLDRD_LN_DEFER=0 restores the immediate reductions.
-        self._lnq = ops.LnReduceQueue() if self.ln_defer else None
-        flush_every = int(getattr(self, "wgrad_flush_layers", 0) or 0)
+        wq = ops.WgradQueue()
+        # LayerNorm gamma / beta (and the preceding Linear's bias) gradients are deferred likewise (`ln_defer`): each layernorm_bwd
+        # leaves its per-block sums in a scratch buffer of its own and one launch next to the weight-gradient group reduces them all.
+        # Bit-identical and 22 launches fewer per step; with the step replayed as a HIP graph -1.0 % step time at cfg2, twice on one box
+        # (profiles/r03_microbench.txt).  `ln_defer = False` (test hook) restores the immediate reductions.
+        lnq = ops.LnReduceQueue() if self.ln_defer else None
+        flush_every = int(self.wgrad_flush_layers or 0)
         waiting = []
 
         def layer_done(i, force=False):
@@ -1217,19 +1122,19 @@ class HipEncoder(nn.Module):
             else:
                 waiting.append(i)
             # (layer 0 never triggers an early flush: its group waits for the forced one behind embed_ln_bwd, so that the embedding block's
-            # hook - the tower's largest all-reduce bucket - is issued IN FRONT of a weight-gradient group it can travel under.  Until round 5
-            # a layer count that `wgrad_flush_layers` divides (6 / 3, 12 / 6: every shipped config) launched the last group at layer 0 and the
-            # embedding bucket went out with nothing left to overlap it: tools/bucket_plan.py)
+            # hook - the tower's largest all-reduce bucket - is issued IN FRONT of a weight-gradient group it can travel under.  Otherwise
+            # a layer count that `wgrad_flush_layers` divides (6 / 3, 12 / 6: every shipped config) would launch the last group at layer 0 and
+            # the embedding bucket would go out with nothing left to overlap it: tools/bucket_plan.py)
             if force or (flush_every > 0 and len(waiting) >= flush_every and i != 0):
                 if force and before_last_wgrad is not None:
                     before_last_wgrad()
                 # `norm_sink` (the trainer's, one GPU): when this ONE flush produces every layer gradient of the tower - LayerNorm reductions
                 # deferred, no early flushes - the two launches also leave the clip norm's partial sums of what they write (hip_ops.norm_sink)
-                sink = getattr(self, "norm_sink", None) if (force and flush_every == 0 and self._lnq is not None and not self._acc) else None
+                sink = self.norm_sink if (force and flush_every == 0 and lnq is not None and not acc) else None
                 with ops.norm_sink(sink) as ns:
-                    if self._lnq is not None:
-                        self._lnq.flush(accumulate=self._acc)
-                    self._wq.flush(accumulate=self._acc)
+                    if lnq is not None:
+                        lnq.flush(accumulate=acc)
+                    wq.flush(accumulate=acc)
                 self.norm_sink_used = ns.used if sink is not None else -1
                 if after_layer is not None:
                     for j in waiting:
@@ -1244,14 +1149,14 @@ class HipEncoder(nn.Module):
         for i in reversed(range(cfg.n_layers)):
             W, G, a = self._layer_weights(i), self._layer_grads(i), tape.layers[i]
             if a.get("cls_only"):
-                g = yield from self._last_layer_cls_bwd(i, a, tape, dcls, partial)
+                g = yield from self._last_layer_cls_bwd(i, a, tape, dcls, partial, acc, wq, lnq)
                 tape.layers[i] = None
                 layer_done(i)
                 yield
                 continue
             bdt = a["h"].dtype                                          # 16-bit format of this backward = the tape's (fp16 in amp16)
             # the gradient stream (residual path): its arithmetic is fp32 inside the LayerNorm backward, where stream and branch are added;
-            # BETWEEN kernels it is stored in fp16 in the fp16 mode (round 5, see __init__), in fp32 in the bf16 mode
+            # BETWEEN kernels it is stored in fp16 in the fp16 mode (see __init__), in fp32 in the bf16 mode
             G16 = self.grad_stream16 and bdt == torch.float16
             sdt = torch.float16 if G16 else torch.float32
             buf = lambda r, c, dv, dt=None: self._buf(r, c, dv, bdt if dt is None else dt)
@@ -1264,21 +1169,20 @@ class HipEncoder(nn.Module):
             # the 16-bit MFMA operand of the FFN2 data / weight gradients: a tensor of its own when dropout separates it from the stream, or
             # when the stream is fp32; with the fp16 stream and no dropout the stream tensor serves
             ds2m = buf(T, d, dev) if (p_h > 0 or not G16) else None
-            lnq = self._lnq
-            own = (lambda: torch.empty(ops.ln_partial_elems(T, d), **f32)) if lnq is not None else (lambda: partial)
+            own =(lambda: torch.empty(ops.ln_partial_elems(T, d), **f32)) if lnq is not None else (lambda: partial)
             # fp32 stream: the gradient of a LayerNorm output is `g` (fp32: the residual path) + `gb` (bf16: the plain output of the
             # branch's last data-gradient GEMM), added inside layernorm_bwd - not in that GEMM's epilogue (200 MB less per GEMM)
             if window is not None:
                 window("ln")
             ops.layernorm_bwd(g, a["s2"], a["mean2"], a["rstd2"], W["g2"], ds2, ds2m, G["g2"], G["b2"], G["bf2"], own(), T,
-                              p_h, s_l + 3, accumulate=self._acc, defer=lnq, dy_branch=gb)
+                              p_h, s_l + 3, accumulate=acc, defer=lnq, dy_branch=gb)
             yield
             dF = ds2m if ds2m is not None else ds2
-            self._wq.add(dF, a["h"], G["W2"], T)
+            wq.add(dF, a["h"], G["W2"], T)
             dpre = buf(T, f, dev)
             ops.gemm_nt(dF, self.ht(i, "f2"), dpre, T, gelu_pre=a["pre"], act=2)
             yield
-            self._wq.add(dpre, a["x1"], G["W1"], T, dbias=G["bf1"])
+            wq.add(dpre, a["x1"], G["W1"], T, dbias=G["bf1"])
             dx1 = buf(T, d, dev)
             ops.gemm_nt(dpre, self.ht(i, "f1"), dx1, T)                 # the FFN branch alone; the residual path is ds2
             # --- attention-output LayerNorm + attention ---
@@ -1288,9 +1192,9 @@ class HipEncoder(nn.Module):
             if window is not None:
                 window("ln")
             ops.layernorm_bwd(ds2, a["s1"], a["mean1"], a["rstd1"], W["g1"], ds1, ds1m, G["g1"], G["b1"], G["bo"], own(), T,
-                              p_out, s_l + 2, accumulate=self._acc, defer=lnq, dy_branch=dx1)
+                              p_out, s_l + 2, accumulate=acc, defer=lnq, dy_branch=dx1)
             dA = ds1m if ds1m is not None else ds1
-            self._wq.add(dA, a["ctx"], G["Wo"], T)
+            wq.add(dA, a["ctx"], G["Wo"], T)
             dctx = buf(T, d, dev)
             yield
             ops.gemm_nt(dA, self.ht(i, "o"), dctx, T)
@@ -1302,7 +1206,7 @@ class HipEncoder(nn.Module):
             for sl, tile in (pk.groups if pk is not None else [(None, 0)]):
                 ops.attention_bwd(a["qkv"], tape.mask if pk is None else None, a["ctx"], dctx, a["lse"], dqkv, M, L, H, p_a, s_l + 1,
                                   drop_bits=a.get("dbits"), cu=pk.cu if pk is not None else None, seq_list=sl, tile=tile)
-            self._wq.add(dqkv, a["x_in"], G["Wqkv"], T, dbias=G["bqkv"])
+            wq.add(dqkv, a["x_in"], G["Wqkv"], T, dbias=G["bqkv"])
             yield
             gb = buf(T, d, dev)
             ops.gemm_nt(dqkv, self.ht(i, "qkv"), gb, T)                 # the attention branch alone
@@ -1318,7 +1222,7 @@ class HipEncoder(nn.Module):
                          self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
                          tape.mean0, tape.rstd0, self.g("embeddings.word_embeddings.weight"),
                          self.g("embeddings.position_embeddings.weight"), dtype0, self.g("embeddings.LayerNorm.weight"),
-                         self.g("embeddings.LayerNorm.bias"), partial, T, L, tape.p_embed, tape.seed, accumulate=self._acc,
+                         self.g("embeddings.LayerNorm.bias"), partial, T, L, tape.p_embed, tape.seed, accumulate=acc,
                          pos_idx=tape.pack.pos if tape.pack is not None else None, dy_branch=gb)
         yield
         layer_done(-1, force=True)
@@ -1421,7 +1325,7 @@ class _EncodeFn(torch.autograd.Function):
 
 def encode_autograd(enc: HipEncoder, ids, mask, fp16=None, lengths=None):
     if torch.is_grad_enabled() and any(p.requires_grad for p in enc.parameters()):
-        if getattr(enc, "_anchor", None) is None or enc._anchor.device != enc.flat_p.device:
+        if enc._anchor is None or enc._anchor.device != enc.flat_p.device:
             enc._anchor = torch.zeros(1, device=enc.flat_p.device, requires_grad=True)
         return _EncodeFn.apply(enc._anchor, enc, ids, mask, fp16, lengths)
     return enc.encode(ids, mask, save=False, fp16=fp16, lengths=lengths)

@@ -162,6 +162,10 @@ class NwayTrainer:
         self.l_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
         self._pending = []
         self._sink_on = False
+        self._windows_on = False           # this step's forward ran the window schedule (its backward then does too)
+        self._graph_broken = False         # a capture of the step failed: every later step runs eagerly
+        self._norm_split = None            # the clip norm's early piece covers flat_g[:_norm_split] (_early_norm_hook)
+        self._norm_deferred = None
         # test hooks (tests/test_gpu_model.py, test_gpu_amp16.py prove the default path equal to the plain one they select; not configuration):
         self.zero_all_grads = False        # True: zero the whole gradient buffer and accumulate instead of writing every gradient once
         self.use_norm_sink = True          # False: the late clip-norm piece by a separate pass over the gradients
@@ -259,7 +263,7 @@ class NwayTrainer:
         return window
 
     def _finish_early_norm(self, side):
-        d = getattr(self, "_norm_deferred", None)
+        d = self._norm_deferred
         self._norm_deferred = None
         if d is None:
             return
@@ -310,7 +314,7 @@ class NwayTrainer:
                 ops.zero_segments([self.flat_g[toff + t.layout.embed_range[0]:toff + t.layout.embed_range[1]]
                                    for t, toff in zip(model.towers(), model._tower_offsets)])      # one launch for both towers' tables
             for tower in model.towers():
-                if not getattr(tower, "_t_fresh", False):
+                if not tower._t_fresh:
                     tower.refresh_transposed()
         # Round 6 experiment, OFF by default (`window_schedule`): the query tower enqueued in SLICES, each released by an event the main stream
         # records at the start of one of the passage tower's HBM-bound kernels (LayerNorm, attention), instead of running free next to everything -
@@ -421,7 +425,7 @@ class NwayTrainer:
             # (the critical path) sat idle for 0.62 ms behind the loss in every replayed step (kernel trace, profiles/r04_microbench.txt
             # section 14).  So a captured step enqueues the passage tower first; the query tower's chain is released ~1.8 ms behind the loss
             # and still ends 4 ms before the join.
-            windows = side is not main and getattr(self, "_windows_on", False)
+            windows = side is not main and self._windows_on
             q_late = side is not main and (torch.cuda.is_current_stream_capturing() or windows)
             q_bstep = None
             if windows:
@@ -486,13 +490,13 @@ class NwayTrainer:
         self._adamw_launches(lr, adam_step, towers, hyper)
 
     def _norm_launches(self):
-        split = getattr(self, "_norm_split", None)
+        split = self._norm_split
         if split:
             # [0, split) was summed on the second stream during the backward (`_early_norm_hook`; the main stream has joined it since).  The rest -
             # the passage tower's layer gradients - is final only behind its last weight-gradient group; when that group's slab reduction
             # and the LayerNorm-parameter reduction left their sums of squares (norm sink), nothing is re-read; else one more pass over them
             half = ops.sqnorm_blocks() // 2
-            used = int(getattr(self.model.passage_encoder, "norm_sink_used", -1))
+            used = int(self.model.passage_encoder.norm_sink_used)
             if used > 0 and self._sink_on:
                 ops.clip_coef(self.norm_partial, half + used, self.max_grad_norm, self.clip)
             else:
@@ -629,7 +633,7 @@ class NwayTrainer:
             # a one-rank process group (CLDRD_FORCE_DDP: the bench's ddp leg, tests) captures by default.
             if _env_flag("CLDRD_DDP_GRAPH", "1" if self.world == 1 else "0") != "1" or dist.get_backend() != "nccl":
                 return False
-        return (not self.model.share_weights and not getattr(self, "_graph_broken", False)
+        return (not self.model.share_weights and not self._graph_broken
                 and _env_flag("CLDRD_GRAPH", "1") != "0" and self.flat_p.is_cuda)
 
     def _batch_key(self, batch):

@@ -18,6 +18,11 @@ def stubbed(monkeypatch):
         _lib.load()
     except Exception as e:
         pytest.skip(f"libcldrd_hip.so not built: {e}")
+    return _install_stubs(monkeypatch)
+
+
+def _install_stubs(monkeypatch):
+    """Stub every launch; returns the recorder (the launch-trace generator next to the goldens installs the same stubs)."""
     calls = _Calls()
 
     def chk(t, dtype, name, dim=None):
@@ -29,6 +34,7 @@ def stubbed(monkeypatch):
             raise ValueError(f"{name}: expected {dim} dims, got {t.dim()}")
         if t.stride(-1) != 1:
             raise ValueError(f"{name}: last dim must be contiguous")
+        calls.keep.append(t)
         return t
     monkeypatch.setattr(ops, "_chk", chk)
     monkeypatch.setattr(ops, "call", lambda name, *a: (calls.append(name), calls.args.append((name, a))))
@@ -44,6 +50,7 @@ class _Calls(list):
     def __init__(self):
         super().__init__()
         self.args = []
+        self.keep = []          # every tensor a wrapper validated (the launch trace needs them alive: no address is reused)
 
 
 # position of cu_rows (and, for the full-attention calls, of seq_list) in the C signatures of include/cldrd_hip.h
@@ -207,6 +214,35 @@ def test_window_scheduled_step_walks_and_interleaves_the_two_towers(stubbed, mon
 
 
 
+@pytest.mark.parametrize("ln_defer", [True, False])
+def test_two_backward_steppers_on_one_tower_keep_their_own_queues(stubbed, monkeypatch, ln_defer):
+    """backward_steps is public and a shared-weights tower has two tapes: two steppers alive at once, advanced alternately, must each launch
+    exactly the weight-gradient / LayerNorm-reduction groups they launch when the two backwards run one after the other - the same number of
+    jobs per launch and the same token-row counts (6 x 24 rows on one tape, 4 x 12 on the other)."""
+    monkeypatch.setenv("CLDRD_AMP", "fp16")
+    enc = HipEncoder(cfg_of("distilbert", 3), seed=1)
+    enc.ln_defer = ln_defer
+    shapes = ((6, 24), (4, 12))
+
+    def groups(alternate):
+        tapes = [enc.encode(torch.randint(3, 500, s), torch.ones(s, dtype=torch.long), train=True, save=True, seed=11)[1] for s in shapes]
+        n0 = len(stubbed.args)
+        steppers = [enc.backward_steps(t, torch.zeros(t.M, 128), accumulate=True) for t in tapes]
+        if alternate:
+            while not all([st.step(1) for st in steppers]):
+                pass
+        else:
+            for st in steppers:
+                st.finish()
+        rows = {"cldrd_wgrad_group": 4, "cldrd_ln_reduce_group": 1}       # position of the per-job row counts (int array) in the C signature
+        count = {"cldrd_wgrad_group": 9, "cldrd_ln_reduce_group": 5}      # ... and of the job count
+        return sorted((n, a[count[n]], list(a[rows[n]])) for n, a in stubbed.args[n0:] if n in rows)
+
+    want = groups(alternate=False)
+    assert [g[0] for g in want].count("cldrd_wgrad_group") == 2 and all(len(set(g[2])) <= 2 for g in want)       # (T and M rows of ONE tape each)
+    assert groups(alternate=True) == want
+
+
 class _FakeEvent:
     def record(self, stream=None):
         pass
@@ -248,3 +284,235 @@ def test_would_pack_rules():
 
 
 _MAIN = _FakeStream()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Launch trace: what the tower hands to the C ABI, launch by launch, in a canonical form that two walks of one case reproduce exactly.
+# tests/golden/encoder_launch_trace.json holds the trace of every case below as taken at the commit it names (make_encoder_launch_trace.py,
+# next to it, imports the cases from here); a host-side change of the tower that is meant to change no behaviour must reproduce it.
+# Canonical form of a launch: the entry-point name and every argument in order - floats as repr, every address (an int >= 2^32, also inside
+# the ctypes pointer arrays of the grouped launches) as p<k>, k = order of first appearance within the case.  Addresses are comparable
+# because nothing is freed during a case (`_KeepAlive` + the stubbed _chk hold every tensor) and the seeds are explicit and small (a drawn
+# seed is a 47-bit number and would read as an address; where the trainer draws them they are still the same number in every walk).
+
+class _KeepAlive(torch.utils._python_dispatch.TorchDispatchMode):
+    def __init__(self, keep):
+        super().__init__()
+        self.keep = keep
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        out = func(*args, **(kwargs or {}))
+        self.keep.extend(t for t in torch.utils._pytree.tree_leaves(out) if isinstance(t, torch.Tensor))
+        return out
+
+
+def _canonical(recorded):
+    """[(name, argument tuple)] -> [(name, canonical argument string)]"""
+    import ctypes
+    seen = {}
+
+    def one(v):
+        if isinstance(v, ctypes.Array):
+            return "[" + ",".join(one(e) for e in v) + "]"
+        if isinstance(v, int) and not isinstance(v, bool):
+            return f"p{seen.setdefault(v, len(seen))}" if v >= 1 << 32 else str(v)
+        if isinstance(v, (float, bool, bytes, str)) or v is None:
+            return repr(v)
+        raise TypeError(f"launch trace: unexpected argument type {type(v)}")
+    return [(name, ",".join(one(v) for v in a)) for name, a in recorded]
+
+
+_LENS = [24, 3, 10, 17, 5, 8]
+
+
+def _trace_batch(lens=_LENS, L=24):
+    return torch.randint(3, 500, (len(lens), L)), (torch.arange(L)[None, :] < torch.tensor(lens)[:, None]).long()
+
+
+def _mark(calls, what):
+    """a hook whose calls appear in the trace between the launches"""
+    return lambda *a: calls.args.append((what, a))
+
+
+def _tower_case(amp, arch, layers, lengths, tweak=None, cls_only=True):
+    """evaluation pass with hp_forward off and on, then a training pass + backward, writing and accumulating"""
+    def run(calls, monkeypatch):
+        monkeypatch.setenv("CLDRD_AMP", amp)
+        enc = HipEncoder(cfg_of(arch, layers), seed=1)
+        enc.cls_only_last = cls_only
+        if tweak is not None:
+            setattr(enc, *tweak)
+        ids, mask = _trace_batch()
+        lens = _LENS if lengths else None
+        for hp in (False, True):
+            enc.hp_forward = hp
+            enc.encode(ids, mask, train=False, seed=11, lengths=lens)
+        enc.hp_forward = False
+        for acc in (False, True):
+            cls, tape = enc.encode(ids, mask, train=True, save=True, seed=11, lengths=lens)
+            enc.backward_from_cls(tape, torch.zeros(len(_LENS), 128), after_layer=_mark(calls, "after_layer"), accumulate=acc,
+                                  before_last_wgrad=_mark(calls, "before_last_wgrad"))
+    return run
+
+
+def _empty_tower_case(amp):
+    """no transformer layer at all: the CLS rows of the embedding LayerNorm (forward only: there is nothing to send a gradient through)"""
+    def run(calls, monkeypatch):
+        monkeypatch.setenv("CLDRD_AMP", amp)
+        enc = HipEncoder(cfg_of("distilbert", 0), seed=1)
+        ids, mask = _trace_batch()
+        enc.encode(ids, mask, train=False, seed=11)
+        enc.encode(ids, mask, train=False, seed=11, lengths=_LENS)
+        enc.encode(ids, mask, train=True, save=True, seed=11)
+        enc.encode(ids, mask, fp32=True)
+    return run
+
+
+def _typed_case(amp, arch, layers, lengths):
+    def run(calls, monkeypatch):
+        monkeypatch.setenv("CLDRD_AMP", amp)
+        enc = HipEncoder(cfg_of(arch, layers), seed=1)
+        ids, mask = _trace_batch()
+        enc.encode(ids, mask, train=False, seed=11, lengths=_LENS if lengths else None,
+                   token_type_ids=(torch.arange(24)[None, :] >= 5).long().expand(len(_LENS), 24))
+    return run
+
+
+def _packed_rows(typed=True):
+    T = sum(_LENS)
+    pos = torch.cat([torch.arange(n, dtype=torch.int32) for n in _LENS])
+    return torch.randint(3, 500, (T,)), ((pos >= 2).to(torch.int32) if typed else None), pos
+
+
+def _packed_case(amp, arch, layers, width):
+    def run(calls, monkeypatch):
+        monkeypatch.setenv("CLDRD_AMP", amp)
+        enc = HipEncoder(cfg_of(arch, layers), seed=1)
+        rows = _packed_rows()
+        enc.encode(None, None, train=False, seed=11, lengths=_LENS, packed=rows + ((width,) if width else ()))
+    return run
+
+
+def _fp32_case(arch, layers, form):
+    def run(calls, monkeypatch):
+        monkeypatch.setenv("CLDRD_AMP", "fp16")
+        enc = HipEncoder(cfg_of(arch, layers), seed=1)
+        ids, mask = _trace_batch()
+        types = (torch.arange(24)[None, :] >= 5).long().expand(len(_LENS), 24)
+        if form == "padded":
+            enc.encode(ids, mask, fp32=True, token_type_ids=types)
+        elif form == "lengths":
+            enc.encode(ids, mask, fp32=True, lengths=_LENS, token_type_ids=types)
+        elif form == "packed":
+            enc.encode(None, None, fp32=True, lengths=_LENS, packed=_packed_rows())
+            enc.encode(None, None, fp32=True, lengths=_LENS, packed=_packed_rows(typed=False) + (32,))
+        else:
+            enc.cls_only_last = False
+            enc.encode(ids, mask, fp32=True)
+            enc.encode(ids, mask, fp32=True, lengths=_LENS)          # (stays padded)
+    return run
+
+
+def _long_case(lens):
+    """the batches of test_packed_batches_above_128_tokens_...: 2, 1 and 0 listed attention launches"""
+    def run(calls, monkeypatch):
+        monkeypatch.setenv("CLDRD_AMP", "fp16")
+        cfg = EncoderConfig(arch="distilbert", vocab_size=512, dim=128, n_heads=2, hidden_dim=256, n_layers=2, max_position_embeddings=256,
+                            dropout=0.1, attention_dropout=0.1)
+        enc = HipEncoder(cfg, seed=1)
+        ids, mask = _trace_batch(lens * 4, 200)
+        cls, tape = enc.encode(ids, mask, train=True, save=True, seed=11, lengths=lens * 4)
+        enc.backward_from_cls(tape, torch.zeros(len(lens) * 4, cfg.dim))
+    return run
+
+
+def _trainer_case(windows):
+    """one NwayTrainer.train_step on fake streams (the optimizer launches included)"""
+    def run(calls, monkeypatch):
+        from cldrd_amd.trainer import nway_listwise as TL
+        monkeypatch.setattr(TL.NwayTrainer, "_require_gpu", staticmethod(lambda dev: None))
+        monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _MAIN)
+        monkeypatch.setattr(torch.cuda, "stream", lambda s_: _Null())
+        monkeypatch.setattr(torch.cuda, "Stream", lambda *a, **k: _FakeStream())
+        monkeypatch.setattr(torch.cuda, "Event", lambda *a, **k: _FakeEvent())
+        monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+        monkeypatch.setattr(torch.Tensor, "record_stream", lambda self, s_: None)
+        monkeypatch.setenv("CLDRD_GRAPH", "0")
+        monkeypatch.setenv("CLDRD_AMP", "fp16")
+        torch.manual_seed(0)
+        model = NwayDualEncoder(cfg_of("distilbert", 3), share_weights=False)
+        tr = TL.NwayTrainer(model, loss="kl_div")
+        tr.q_stream, tr.l_stream = _FakeStream(), _FakeStream()
+        tr.window_schedule = windows
+        batch = syn.nway_batch(5, 2, 3, 6, 20, vocab=512, ragged=not windows, label_kind="teacher")
+        tr.train_step(batch if windows else TL.batch_to_device(batch, torch.device("cpu")))      # (the ragged batch with host lengths)
+        return model, tr
+    return run
+
+
+def _trace_cases():
+    cases = {}
+    for amp in ("fp16", "bf16"):
+        for lengths in (False, True):
+            lay = "lengths" if lengths else "padded"
+            for arch, layers in (("distilbert", 3), ("bert", 2), ("bert", 7), ("distilbert", 1)):
+                cases[f"tower-{amp}-{lay}-{arch}{layers}"] = _tower_case(amp, arch, layers, lengths)
+            for tag, tweak in (("stream32", ("_grad_stream16", False)), ("ln_now", ("ln_defer", False)), ("flush2", ("wgrad_flush_layers", 2))):
+                if tag != "stream32" or amp == "fp16":
+                    cases[f"tower-{amp}-{lay}-distilbert3-{tag}"] = _tower_case(amp, "distilbert", 3, lengths, tweak)
+            cases[f"typed-{amp}-{lay}-bert2"] = _typed_case(amp, "bert", 2, lengths)
+            cases[f"typed-{amp}-{lay}-distilbert3"] = _typed_case(amp, "distilbert", 3, lengths)
+        cases[f"tower-{amp}-lengths-bert7-flush2"] = _tower_case(amp, "bert", 7, True, ("wgrad_flush_layers", 2))
+        cases[f"tower-{amp}-padded-distilbert0"] = _empty_tower_case(amp)
+        cases[f"full_last-{amp}-padded-distilbert3"] = _tower_case(amp, "distilbert", 3, False, cls_only=False)
+        for width in (0, 32):
+            cases[f"packed_rows-{amp}-bert2-width{width}"] = _packed_case(amp, "bert", 2, width)
+            cases[f"packed_rows-{amp}-bert7-width{width}"] = _packed_case(amp, "bert", 7, width)
+    for form in ("padded", "lengths", "packed", "full_last"):
+        cases[f"fp32-{form}-bert2"] = _fp32_case("bert", 2, form)
+        cases[f"fp32-{form}-distilbert3"] = _fp32_case("distilbert", 3, form)
+    for lens, want in (([200, 3, 10, 130, 5, 128], 2), ([100, 3, 10, 128, 5, 64], 1), ([200, 150, 129, 130, 131, 199], 0)):
+        cases[f"long-listed{want}"] = _long_case(lens)
+    cases["trainer-free_running"] = _trainer_case(False)
+    cases["trainer-windows"] = _trainer_case(True)
+    return cases
+
+
+TRACE_CASES = _trace_cases()
+
+
+def walk_trace(case, calls, monkeypatch):
+    """Run one case under the stubs of ``_install_stubs``; -> [(entry point, 8-hex-digit hash of its canonical arguments)]"""
+    import hashlib
+    monkeypatch.delenv("CLDRD_PACK", raising=False)
+    n0 = len(calls.args)
+    with _KeepAlive(calls.keep):
+        calls.keep.append(TRACE_CASES[case](calls, monkeypatch))
+    return [(name, hashlib.sha1(a.encode()).hexdigest()[:8]) for name, a in _canonical(calls.args[n0:])]
+
+
+_TRACE_GOLDEN = None
+
+
+def _trace_golden():
+    global _TRACE_GOLDEN
+    if _TRACE_GOLDEN is None:
+        import json
+        import os
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "encoder_launch_trace.json")) as fh:
+            _TRACE_GOLDEN = json.load(fh)["cases"]
+    return _TRACE_GOLDEN
+
+
+def test_launch_trace_golden_lists_every_case():
+    assert sorted(_trace_golden()) == sorted(TRACE_CASES)
+
+
+@pytest.mark.parametrize("case", sorted(TRACE_CASES))
+def test_launch_trace_matches_golden(stubbed, monkeypatch, case):
+    """Every launch of the case - entry point, argument values, which buffer goes where - is the one the golden's commit made."""
+    want = _trace_golden()[case]
+    got = walk_trace(case, stubbed, monkeypatch)
+    for k, ((name, digest), wname, wdigest) in enumerate(zip(got, want["names"], want["hashes"])):
+        assert (name, digest) == (wname, wdigest), f"{case}: launch {k} differs: {name} (golden: {wname})"
+    assert len(got) == len(want["names"]), f"{case}: {len(got)} launches, golden {len(want['names'])}"
