@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # change of ABI_VERSION uses two checkouts).  The library itself reads no environment variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
 
-ABI_VERSION = 104          # cldrd_version() of the build SIGNATURES describes
+ABI_VERSION = 105          # cldrd_version() of the build SIGNATURES describes
 
 _lib = None
 
@@ -40,6 +40,10 @@ SIGNATURES = {
     "cldrd_ln_partial_blocks": (ci, [ci]),
     "cldrd_embed_ln_fwd": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cull, vp, ci, vp, vp]),
     "cldrd_embed_ln_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cull, ci, vp, ci, ci, vp, vp]),
+    "cldrd_embed_ln_bwd_rows": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cull, ci, vp, ci, ci, vp, vp]),
+    "cldrd_key_order_workspace": (csz, [ci, ci]),
+    "cldrd_key_order": (ci, [vp, ci, ci, vp, vp, vp, csz, vp]),
+    "cldrd_segment_sum_rows": (ci, [vp, vp, vp, ci, ci, ci, vp, ci, vp]),
     "cldrd_layernorm_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, ci, vp, ci, vp]),
     "cldrd_layernorm_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cull, ci, ci, ci, ci, vp, vp]),
     "cldrd_ln_reduce_group": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp]),

@@ -30,6 +30,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers.append(os.path.join(os.path.dirname(HERE), "include", "cldrd_hip.h"))      # segsum.hip takes CLDRD_SEGMENT_CHUNK from the C ABI header
     jobs = []
     objs = []
     for src in sources():

@@ -6,7 +6,8 @@
 // are HBM-bound: one wavefront owns one token row (d <= 1024), 8-byte bf16 loads per lane, two-pass
 // mean/variance in registers, wave-level shuffles for the reductions; LN statistics and all parameter
 // gradients are fp32.  Parameter gradients are reduced deterministically: per-block partial rows, then
-// one column-sum pass (no float atomics) - except the embedding-table scatter, which uses fp32 atomics.
+// one column-sum pass (no float atomics) - except the embedding-table scatter, which uses fp32 atomics
+// unless the deterministic mode stores rows instead (cldrd_embed_ln_bwd_rows + segsum.hip).
 #include <type_traits>
 
 #include "common.h"
@@ -398,12 +399,16 @@ __global__ __launch_bounds__(512) void ln_bwd_kernel(const void* __restrict__ dy
 // Embedding backward: dy -> (dropout) -> LN backward (statistics saved, input recomputed from the tables)
 // -> scatter-add into the word / position tables (fp32 atomics); LN-parameter and token-type gradients go
 // through per-block partials {dgamma, dbeta, dtype}.
+// dx_rows != null (the deterministic mode): the value the atomics would add for row r is stored once to dx_rows[r] instead - every row,
+// zeros for a row whose dy is zero - and cldrd_segment_sum_rows (segsum.hip) sums the rows per table row in a fixed order.  A run-time
+// switch behind the arithmetic, not a second instance of the kernel: the rows and the LayerNorm-parameter partials then come from the very
+// instructions of the atomic form (as a template flag the two instances contracted their multiply-adds differently: 1 ulp apart at d = 1024).
 template <int DC, bool DROP, int GS = 0>      // GS: format of dy, as in ln_bwd_kernel (0 bf16, 1 fp32, 2 fp16)
 __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restrict__ dy_v, const int64_t* __restrict__ ids,
                                                             const float* __restrict__ word, const float* __restrict__ pos,
                                                             const float* __restrict__ type0, const float* __restrict__ gamma,
                                                             const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
-                                                            float* __restrict__ dword, float* __restrict__ dpos,
+                                                            float* __restrict__ dword, float* __restrict__ dpos, float* __restrict__ dx_rows,
                                                             float* __restrict__ partial, int T, int L, int d_rt, int vocab,
                                                             uint32_t drop_thresh, float drop_scale, SeedArg seed_a, int pos_uniform,
                                                             const int* __restrict__ pos_idx, const bf16_t* __restrict__ dy_branch, int h16,
@@ -448,7 +453,15 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restric
             for (int it = 0; it < MAX_IT; ++it)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(g.v[it][j]));
-            if (wave_max(amax) == 0.f) continue;
+            if (wave_max(amax) == 0.f) {
+                if (dx_rows) {
+#pragma unroll
+                    for (int it = 0; it < MAX_IT; ++it)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { const int c = icol(it, j, lane); if (c < d) dx_rows[(size_t)row * d + c] = 0.f; }
+                }
+                continue;
+            }
         }
         load_row_f32_i(word + (size_t)id * d, d, lane, xr);
         load_row_f32_i(pos + (size_t)l * d, d, lane, p);
@@ -490,13 +503,33 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restric
                 if (c < d) {
                     const float v = rstd * (g.v[it][j] - s1 - xr.v[it][j] * s2) * is;
                     dt.v[it][j] += v;
+                    g.v[it][j] = v;
+                }
+            }
+        if (dx_rows) {
+#pragma unroll
+            for (int it = 0; it < MAX_IT; ++it)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c = icol(it, j, lane);
+                    if (c < d) dx_rows[(size_t)row * d + c] = g.v[it][j];          // 64 lanes x 4 B contiguous per instruction, like the atomics
+                }
+            continue;
+        }
+#pragma unroll
+        for (int it = 0; it < MAX_IT; ++it)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = icol(it, j, lane);
+                if (c < d) {
+                    const float v = g.v[it][j];
                     atomicAdd(dword + (size_t)id * d + c, v);          // 64 lanes x 4 B contiguous per instruction
                     if (pos_uniform) dp.v[it][j] += v;
                     else atomicAdd(dpos + (size_t)l * d + c, v);
                 }
             }
     }
-    if (pos_uniform) {
+    if (!dx_rows && pos_uniform) {
         const int l = (blockIdx.x * 4 + (threadIdx.x >> 6)) % L;
 #pragma unroll
         for (int it = 0; it < MAX_IT; ++it)
@@ -726,15 +759,22 @@ extern "C" int cldrd_ln_reduce_group(const float* const* partial, const int* T, 
     return 0;
 }
 
-extern "C" int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
-                                  const float* gamma, const float* mean, const float* rstd, float* dword, float* dpos,
-                                  float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
-                                  float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16,
-                                  const void* dy_branch, void* stream) {
-    CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0 && L > 0, "embed_ln_bwd: bad shape");
+// The two forms of the embedding backward: tables written with float atomics (dx_rows null), or one row per token stored to dx_rows (the
+// deterministic mode; the tables are then summed by cldrd_segment_sum_rows).  Same kernel body, same grid, same partials.
+static int embed_ln_bwd_launch(bool rows, const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
+                               const float* gamma, const float* mean, const float* rstd, float* dword, float* dpos, float* dx_rows,
+                               float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab, float dropout_p,
+                               unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16, const void* dy_branch,
+                               void* stream) {
+    CLDRD_CHECK(T > 0 && d > 0 && d <= 1024 && d % 4 == 0 && L > 0, rows ? "embed_ln_bwd_rows: bad shape" : "embed_ln_bwd: bad shape");
     // grad_fmt (enum cldrd_stream_fmt): the format of dy; branch_f16: the dy_branch of an fp32 dy is fp16, not bf16 (an fp16 dy's always is)
-    CLDRD_CHECK(grad_fmt >= STREAM_BF16 && grad_fmt <= STREAM_F16, "embed_ln_bwd: grad_fmt is one of enum cldrd_stream_fmt");
-    CLDRD_CHECK(dy_branch == nullptr || grad_fmt != STREAM_BF16, "embed_ln_bwd: dy_branch goes with an fp32 / fp16 dy");
+    CLDRD_CHECK(grad_fmt >= STREAM_BF16 && grad_fmt <= STREAM_F16,
+                rows ? "embed_ln_bwd_rows: grad_fmt is one of enum cldrd_stream_fmt" : "embed_ln_bwd: grad_fmt is one of enum cldrd_stream_fmt");
+    CLDRD_CHECK(dy_branch == nullptr || grad_fmt != STREAM_BF16,
+                rows ? "embed_ln_bwd_rows: dy_branch goes with an fp32 / fp16 dy" : "embed_ln_bwd: dy_branch goes with an fp32 / fp16 dy");
+    if (rows) {          // (the kernel tells the two forms apart by dx_rows)
+        CLDRD_CHECK(dy && ids && word && pos && gamma && mean && rstd && dx_rows && partial && vocab > 0, "embed_ln_bwd_rows: null operand or empty vocabulary");
+    }
     const int h16 = grad_fmt == STREAM_F16 || (grad_fmt == STREAM_F32 && branch_f16) ? 1 : 0;
     int nb = ln_bwd_blocks(T);                      // the caller sized `partial` for this many blocks; fewer is fine
     int g4 = 4, r = L;                              // gcd(4, L)
@@ -744,17 +784,39 @@ extern "C" int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const fl
     if (pos_uniform) nb = (nb / step) * step;
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
     ln_dispatch(d, th != 0, [&](auto dc, auto dr) {
+        constexpr int DCV = decltype(dc)::value;
+        constexpr bool DRV = decltype(dr)::value;
         const size_t lds = (256 / 128) * 3 * MAX_IT * 64 * sizeof(float4);
-        decltype(&embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 2>) kern;
-        if (grad_fmt == STREAM_F16) kern = embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 2>;
-        else if (grad_fmt == STREAM_F32) kern = embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value, 1>;
-        else kern = embed_ln_bwd_kernel<decltype(dc)::value, decltype(dr)::value>;
+        decltype(&embed_ln_bwd_kernel<DCV, DRV, 2>) kern;
+        if (grad_fmt == STREAM_F16) kern = embed_ln_bwd_kernel<DCV, DRV, 2>;
+        else if (grad_fmt == STREAM_F32) kern = embed_ln_bwd_kernel<DCV, DRV, 1>;
+        else kern = embed_ln_bwd_kernel<DCV, DRV>;
         hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, (hipStream_t)stream, dy, (const int64_t*)ids, word, pos, type0, gamma, mean, rstd, dword,
-                           dpos, partial, T, L, d, vocab, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), pos_uniform, pos_idx, (const bf16_t*)dy_branch,
-                           h16, g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr);
+                           dpos, dx_rows, partial, T, L, d, vocab, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), pos_uniform, pos_idx,
+                           (const bf16_t*)dy_branch, h16, g_cldrd_loss_scale ? g_cldrd_loss_scale + 1 : nullptr);
     });
     CLDRD_LAUNCH_CHECK();
     return launch_reduce(partial, nb, d, dgamma, dbeta, dtype0, accumulate, (hipStream_t)stream);
+}
+
+extern "C" int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
+                                  const float* gamma, const float* mean, const float* rstd, float* dword, float* dpos,
+                                  float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
+                                  float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16,
+                                  const void* dy_branch, void* stream) {
+    return embed_ln_bwd_launch(false, dy, ids, word, pos, type0, gamma, mean, rstd, dword, dpos, nullptr, dtype0, dgamma, dbeta, partial, T, L, d,
+                               vocab, dropout_p, seed, accumulate, pos_idx, grad_fmt, branch_f16, dy_branch, stream);
+}
+
+// dx_rows fp32 [T, d] takes the place of dword / dpos: row r receives what cldrd_embed_ln_bwd adds into both tables for token r (zeros for a
+// token whose dy is zero); plain stores, every row written.  dgamma / dbeta / dtype0 come out bit for bit as from cldrd_embed_ln_bwd.
+extern "C" int cldrd_embed_ln_bwd_rows(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
+                                       const float* gamma, const float* mean, const float* rstd, float* dx_rows,
+                                       float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
+                                       float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16,
+                                       const void* dy_branch, void* stream) {
+    return embed_ln_bwd_launch(true, dy, ids, word, pos, type0, gamma, mean, rstd, nullptr, nullptr, dx_rows, dtype0, dgamma, dbeta, partial, T, L, d,
+                               vocab, dropout_p, seed, accumulate, pos_idx, grad_fmt, branch_f16, dy_branch, stream);
 }
 
 // bias gradient: out[N] (+)= column sums of x[T, N].  partial must hold ceil(T/128) * N floats.

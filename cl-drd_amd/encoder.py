@@ -213,7 +213,7 @@ def _attach(root: nn.Module, dotted: str, param: nn.Parameter):
 
 class _Tape:
     """Activations saved by one training forward of one tower."""
-    __slots__ = ("M", "L", "T", "ids", "mask", "seed", "mean0", "rstd0", "layers", "p_embed", "pack", "device_seed")
+    __slots__ = ("M", "L", "T", "ids", "mask", "seed", "mean0", "rstd0", "layers", "p_embed", "pack", "device_seed", "word_order", "pos_order")
 
 
 class _Pack:
@@ -333,6 +333,7 @@ class HipEncoder(nn.Module):
         self._amp_fp16 = mode == "fp16"
         self.ffn_fp16 = self._amp_fp16        # evaluation pass of the fp16 mode: FFN / out-projection (and deep towers' QKV) GEMMs on fp16 operands
         self._grad_stream16 = True            # fp16 mode: the gradient stream is stored in fp16 between kernels (test hook: False keeps it fp32)
+        self.deterministic_embed = False      # embedding-table gradients as fixed-order per-row sums instead of float atomics (README: --deterministic)
         self.ln_defer = True                  # LayerNorm-parameter gradients reduced by one grouped launch per flush (test hook: False = immediately)
 
     # ------------------------------------------------------------------ parameters
@@ -763,6 +764,13 @@ class HipEncoder(nn.Module):
             tape = _Tape()
             tape.M, tape.L, tape.T, tape.ids, tape.mask, tape.seed, tape.layers = M, L, T, ids, mask, seed, []
             tape.p_embed, tape.pack, tape.device_seed = p_h, pk, False
+            tape.word_order = tape.pos_order = None
+            if self.deterministic_embed:
+                # the inverted indices of the embedding backward's per-row sums, built here from THIS batch's ids (inside a captured step:
+                # from the per-step id buffers, on every replay); a padded batch needs no position order (row r sits at position r % L)
+                tape.word_order = ops.key_order(ids.view(-1), cfg.vocab_size)
+                if pk is not None:
+                    tape.pos_order = ops.key_order(pk.pos.to(torch.int64), L)
         f32 = dict(dtype=torch.float32, device=dev)
         # FFN16 (fp16 mode, evaluation pass): the FFN and out-projection GEMMs read fp16 operands - the LayerNorm in front of the FFN writes
         # fp16, FFN1 leaves h in fp16, and the attention kernel leaves its context in fp16 instead of bf16.  With the FFN pair on fp16
@@ -1218,12 +1226,16 @@ class HipEncoder(nn.Module):
         dtype0 = self.g("embeddings.token_type_embeddings.weight")[0] if cfg.arch == "bert" else None
         if window is not None:
             window("ln")
-        ops.embed_ln_bwd(g, tape.ids.view(-1), self.w("embeddings.word_embeddings.weight"),
-                         self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
-                         tape.mean0, tape.rstd0, self.g("embeddings.word_embeddings.weight"),
-                         self.g("embeddings.position_embeddings.weight"), dtype0, self.g("embeddings.LayerNorm.weight"),
-                         self.g("embeddings.LayerNorm.bias"), partial, T, L, tape.p_embed, tape.seed, accumulate=acc,
-                         pos_idx=tape.pack.pos if tape.pack is not None else None, dy_branch=gb)
+        # deterministic_embed: one fp32 row per token, then the two table sums in a fixed order (three launches, the tables finished behind
+        # the last one) instead of the float atomics; the orders were built by the forward that kept this tape
+        det = dict(word_order=tape.word_order, pos_order=tape.pos_order, rows=self._buf(T, d, dev, torch.float32)) if tape.word_order is not None else {}
+        (ops.embed_ln_bwd_det if det else ops.embed_ln_bwd)(
+            g, tape.ids.view(-1), self.w("embeddings.word_embeddings.weight"),
+            self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
+            tape.mean0, tape.rstd0, self.g("embeddings.word_embeddings.weight"),
+            self.g("embeddings.position_embeddings.weight"), dtype0, self.g("embeddings.LayerNorm.weight"),
+            self.g("embeddings.LayerNorm.bias"), partial, T, L, tape.p_embed, tape.seed, accumulate=acc,
+            pos_idx=tape.pack.pos if tape.pack is not None else None, dy_branch=gb, **det)
         yield
         layer_done(-1, force=True)
 

@@ -597,6 +597,87 @@ def embed_ln_bwd(dy, ids, word, pos, type0, gamma, mean, rstd, dword, dpos, dtyp
          1 if accumulate else 0, _p(pos_idx), _stream_fmt(dy), 1 if (dy_branch is not None and dy_branch.dtype == F16) else 0, _p(dy_branch), _stream())
 
 
+# ---- the deterministic mode of the embedding backward (csrc/segsum.hip): rows stored once, summed per table row in a fixed order ------
+SEGMENT_CHUNK = 64          # CLDRD_SEGMENT_CHUNK of include/cldrd_hip.h: list entries per chunk of segment_sum_rows
+
+
+def key_order(keys, n_keys):
+    """keys int64 [T] (clamped to 0 .. n_keys - 1) -> (order int32 [T]: the stable ascending permutation of the rows by key, offsets int32
+    [n_keys + 1]: the CSR starts).  Device only, no read-back, a launch sequence that depends on n_keys alone (cldrd_key_order)."""
+    _chk(keys, torch.int64, "keys", 1)
+    T, n_keys = keys.numel(), int(n_keys)
+    if not 0 < T <= 1 << 22 or not 0 < n_keys <= 1 << 20:
+        raise ValueError("key_order: 0 < T <= 2^22 keys, 0 < n_keys <= 2^20")
+    dev = keys.device
+    order = torch.empty(T, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n_keys + 1, dtype=torch.int32, device=dev)
+    nbytes = int(_lib.load().cldrd_key_order_workspace(T, n_keys))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("cldrd_key_order", _p(keys), T, n_keys, _p(order), _p(offsets), _p(ws), nbytes, _stream())
+    return order, offsets
+
+
+def segment_sum_rows(rows, order, offsets, out, accumulate=False):
+    """out[k] (+)= the sum of rows[r] over key k's list in the fixed order of cldrd_segment_sum_rows (chunks of SEGMENT_CHUNK entries summed left
+    to right, chunk sums added left to right); keys without rows are left untouched.  rows fp32 [>= T, d], out fp32 [n_keys, d];
+    (order, offsets) from key_order - T = order.numel() - or both None: the strided form, row r of all rows.shape[0] has key r % n_keys."""
+    _chk(rows, F32, "rows", 2), _chk(out, F32, "out", 2)
+    if (order is None) != (offsets is None):
+        raise ValueError("segment_sum_rows: order and offsets go together")
+    d, n_keys = rows.shape[1], out.shape[0]
+    if out.shape[1] != d or not (rows.is_contiguous() and out.is_contiguous()):
+        raise ValueError("segment_sum_rows: contiguous rows [T, d] and out [n_keys, d]")
+    T = rows.shape[0]
+    if order is not None:
+        _chk(order, torch.int32, "order", 1), _chk(offsets, torch.int32, "offsets", 1)
+        T = order.numel()
+        if T > rows.shape[0] or offsets.numel() != n_keys + 1:
+            raise ValueError("segment_sum_rows: order [T <= rows], offsets [n_keys + 1]")
+    call("cldrd_segment_sum_rows", _p(rows), _p(order), _p(offsets), T, d, n_keys, _p(out), 1 if accumulate else 0, _stream())
+    return out
+
+
+def embed_ln_bwd_rows(dy, ids, word, pos, type0, gamma, mean, rstd, dx_rows, dtype0, dgamma, dbeta, partial, T, L,
+                      dropout_p=0.0, seed=0, accumulate=True, pos_idx=None, dy_branch=None):
+    """embed_ln_bwd with ``dx_rows`` (fp32 [>= T, d]) in place of the two table gradients: row r receives what embed_ln_bwd adds into both
+    tables for token r, every row written with plain stores; dgamma / dbeta / dtype0 as there, bit for bit."""
+    d = word.shape[1]
+    _chk(dx_rows, F32, "dx_rows", 2)
+    if dx_rows.shape[1] != d or dx_rows.shape[0] < T or not dx_rows.is_contiguous():
+        raise ValueError("embed_ln_bwd_rows: dx_rows is a contiguous fp32 [>= T, d]")
+    if pos_idx is not None:
+        _chk(pos_idx, torch.int32, "pos_idx", 1)
+    if dy.dtype not in (BF16, F32, F16):
+        raise TypeError("embed_ln_bwd_rows: dy must be bf16, fp32 (fp32 gradient stream) or fp16 (fp16 gradient stream)")
+    if dy_branch is not None and (dy.dtype not in (F32, F16) or dy_branch.dtype not in (BF16, F16) or dy_branch.shape[1] != dy.shape[1] or dy_branch.shape[0] < T
+                                  or (dy.dtype == F16 and dy_branch.dtype != F16)):
+        raise ValueError("embed_ln_bwd_rows: dy_branch (bf16 or fp16 [>= T, d]) goes with an fp32 dy, an fp16 one with an fp16 dy")
+    call("cldrd_embed_ln_bwd_rows", _p(dy), _p(ids), _p(word), _p(pos), _p(type0), _p(gamma), _p(mean), _p(rstd), _p(dx_rows),
+         _p(dtype0), _p(dgamma), _p(dbeta), _p(partial), T, L, d, word.shape[0], dropout_p, seed,
+         1 if accumulate else 0, _p(pos_idx), _stream_fmt(dy), 1 if (dy_branch is not None and dy_branch.dtype == F16) else 0, _p(dy_branch), _stream())
+
+
+def embed_ln_bwd_det(dy, ids, word, pos, type0, gamma, mean, rstd, dword, dpos, dtype0, dgamma, dbeta, partial, T, L,
+                     dropout_p=0.0, seed=0, accumulate=True, pos_idx=None, dy_branch=None, *, word_order, pos_order, rows):
+    """The deterministic form of embed_ln_bwd: the rows kernel, then the word-table sum, then the position-table sum - no float atomic, the same
+    bits on every run.  ``word_order`` = key_order(ids, vocab); ``pos_order`` = key_order(positions, L) for a packed batch (``pos_idx``), None for
+    a padded one (the strided form: row r sits at position r % L); ``rows``: fp32 scratch [>= T, d].  Like the atomics, the table sums are
+    ADDED onto dword / dpos (zeroed by the caller, or holding the other tape of a shared tower); ``accumulate`` speaks of dgamma / dbeta / dtype0."""
+    if (pos_order is None) != (pos_idx is None):
+        raise ValueError("embed_ln_bwd_det: a packed batch (pos_idx) brings its position order, a padded one none")
+    if word_order[0].numel() != T or (pos_order is not None and pos_order[0].numel() != T):
+        raise ValueError("embed_ln_bwd_det: the orders cover the T rows of this batch")
+    if dpos.shape[0] < L:
+        raise ValueError("embed_ln_bwd_det: dpos holds at least L rows")
+    embed_ln_bwd_rows(dy, ids, word, pos, type0, gamma, mean, rstd, rows, dtype0, dgamma, dbeta, partial, T, L, dropout_p, seed,
+                      accumulate=accumulate, pos_idx=pos_idx, dy_branch=dy_branch)
+    segment_sum_rows(rows, word_order[0], word_order[1], dword, accumulate=True)
+    if pos_order is not None:
+        segment_sum_rows(rows, pos_order[0], pos_order[1], dpos[:pos_order[1].numel() - 1], accumulate=True)
+    else:
+        segment_sum_rows(rows[:T], None, None, dpos[:L], accumulate=True)
+
+
 # ---- variable-length packing (csrc/pack.hip) ---------------------------------------------------------------------------------------
 def unpack_rows16(src_packed, dst_padded, cu, nseq, L):
     """dst[m * L + j] = j < len[m] ? src[cu[m] + j] : 0 for 16-bit rows (cu: int32 [nseq + 1] on the device)."""

@@ -88,7 +88,8 @@ class NwayTrainer:
     def __init__(self, model: NwayDualEncoder, *, loss: str = "lambda_mrr", T: float = 1.0, learning_rate: float = 7e-6,
                  weight_decay: float = 0.01, adam_epsilon: float = 1e-8, max_grad_norm: float = 1.0, warmup_steps: int = 4000,
                  total_steps: int = 100000, betas=(0.9, 0.999), bucket_layers: int = 1, reg_lambda: float = 0.0,
-                 distill=None, distill_alpha: float = 1.0, distill_T: float = 1.0, distill_only: bool = False):
+                 distill=None, distill_alpha: float = 1.0, distill_T: float = 1.0, distill_only: bool = False,
+                 deterministic: bool = False):
         if loss not in LOSS_KINDS:
             raise ValueError(f"loss must be one of {LOSS_KINDS}")
         if distill is not None and distill not in DISTILL_KINDS:
@@ -115,6 +116,11 @@ class NwayTrainer:
         self.distributed = dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or _env_flag("CLDRD_FORCE_DDP", "0") == "1")
         self.world = dist.get_world_size() if self.distributed else 1
         self.flat_p, self.flat_g = model.fuse_flat()
+        # --deterministic: the embedding-table gradients - the one part of the step summed by float atomics - become fixed-order per-row sums
+        # (encoder.HipEncoder.deterministic_embed): the same batches then give the same bits, run after run, eager or replayed
+        self.deterministic = bool(deterministic)
+        for t in model.towers():
+            t.deterministic_embed = self.deterministic
         # deferred weight gradients: one group launch per tower at the end of the backward on one GPU; with RCCL every
         # ceil(layers / 2) layers, so the first half of the buckets is all-reduced while the rest of the backward still runs
         for t in model.towers():
@@ -953,6 +959,8 @@ def get_args(argv=None):
     ap.add_argument("--distill_alpha", default=1.0, type=float, help="weight of the --distill_loss term")
     ap.add_argument("--distill_T", default=1.0, type=float, help="temperature of --distill_loss kl_div")
     ap.add_argument("--distill_only", action="store_true", default=False, help="drop the --loss term: total = distill_alpha * distill loss")
+    ap.add_argument("--deterministic", action="store_true", default=False,
+                    help="bit-reproducible steps: embedding-table gradients as fixed-order per-row sums instead of float atomics (README: cost)")
     ap.add_argument("--token_cache_dir", default=None)
     ap.add_argument("--loader_workers", default=4, type=int, help="collate (tokenise / gather from the token cache) worker processes; "
                     "batches arrive in pinned memory, a few steps ahead of the GPU")
@@ -1202,7 +1210,7 @@ def train(args):
                           adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm, warmup_steps=args.warmup_steps,
                           total_steps=t_total, reg_lambda=args.reg_lambda, distill=getattr(args, "distill_loss", None),
                           distill_alpha=getattr(args, "distill_alpha", 1.0), distill_T=getattr(args, "distill_T", 1.0),
-                          distill_only=getattr(args, "distill_only", False))
+                          distill_only=getattr(args, "distill_only", False), deterministic=getattr(args, "deterministic", False))
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)            # after model / loader construction, as the reference does (:282)

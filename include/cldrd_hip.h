@@ -164,6 +164,31 @@ int cldrd_embed_ln_bwd(const void* dy, const long long* ids, const float* word, 
                        float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
                        float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16,
                        const void* dy_branch, void* stream);
+/* ---- the deterministic mode of the embedding backward: rows stored once, summed per table row in a fixed order, no float atomics ----
+ * cldrd_embed_ln_bwd_rows: cldrd_embed_ln_bwd with dx_rows (fp32 [T, d]) in place of dword / dpos: row r receives the value cldrd_embed_ln_bwd
+ *   adds into both tables for token r (the same arithmetic, bit for bit); every row is written, zeros for a token whose dy is zero.
+ *   dgamma / dbeta / dtype0 as there.
+ * cldrd_key_order: keys int64 [T] (clamped to 0 .. n_keys - 1, as the kernels clamp ids) -> order int32 [T], the STABLE ascending permutation of
+ *   the rows by key, and offsets int32 [n_keys + 1], the CSR starts (rows of key k: order[offsets[k] .. offsets[k + 1])).  Device only, no
+ *   read-back; the launch sequence depends on n_keys alone.  0 < T <= 2^22, 0 < n_keys <= 2^20; workspace: cldrd_key_order_workspace bytes.
+ * cldrd_segment_sum_rows: for every key k with a non-empty list r_0 < r_1 < ... : the list is cut into chunks of CLDRD_SEGMENT_CHUNK consecutive
+ *   entries, each chunk is summed in fp32 left to right, the chunk sums are added left to right in chunk order -> s;
+ *   out[k] = accumulate ? out[k] + s : s (out fp32 [n_keys, d]).  Keys without rows are left untouched.  order == offsets == NULL: the strided
+ *   form, row r has key r % n_keys (the position table of a padded batch: no sort).  d % 4 == 0, d <= 1024; rows / out 16-byte aligned.
+ * CLDRD_SEGMENT_CHUNK = 64: the guide's rule is a quarter of one wave's share of the rows, and a training batch of 16 K .. 64 K token rows over the
+ *   4 K waves the kernel keeps in flight gives a share of 4 .. 16 rows - the 512 measured there belongs to a problem a hundred times larger.  64 is
+ *   the smallest chunk whose row numbers are still one full wave-wide load, and it cuts the one long list of a padded batch ([PAD], half the
+ *   rows) into hundreds of chunks that 16 waves x d / 256 workgroups take in parallel. */
+#define CLDRD_SEGMENT_CHUNK 64
+int cldrd_embed_ln_bwd_rows(const void* dy, const long long* ids, const float* word, const float* pos, const float* type0,
+                            const float* gamma, const float* mean, const float* rstd, float* dx_rows,
+                            float* dtype0, float* dgamma, float* dbeta, float* partial, int T, int L, int d, int vocab,
+                            float dropout_p, unsigned long long seed, int accumulate, const int* pos_idx, int grad_fmt, int branch_f16,
+                            const void* dy_branch, void* stream);
+size_t cldrd_key_order_workspace(int T, int n_keys);          /* bytes; 0 outside the supported range */
+int cldrd_key_order(const long long* keys, int T, int n_keys, int* order, int* offsets, void* workspace, size_t workspace_bytes, void* stream);
+int cldrd_segment_sum_rows(const float* rows, const int* order, const int* offsets, int T, int d, int n_keys, float* out, int accumulate,
+                           void* stream);
 /* out = LN(x)*gamma+beta (bf16); cls_out (fp32 [T/cls_stride, d], optional) receives rows r % cls_stride == 0:
  * the `[0][:, 0, :]` CLS pooling of models/nway_dual_encoder.py:52,56,64.
  * x_f32 != 0: x is fp32 (the pre-LN sum of the fp32 residual stream) and out32 (optional) receives the fp32 output next to
