@@ -249,38 +249,6 @@ class _Pack:
         return pk
 
 
-class Stepper:
-    """A forward or backward of one tower that is enqueued PIECE BY PIECE: ``step(n)`` enqueues the next n groups of launches (a group = a few
-    dependent kernels: a projection + attention, an out-projection + LayerNorm, an FFN GEMM, ...), ``finish()`` the rest and returns the
-    result.  The trainer uses it to enqueue the query tower's ~130 small launches in slices, each slice released by an event of the passage
-    tower's stream at the start of one of ITS HBM-bound kernels (LayerNorm, attention): next to those the small GEMMs cost nothing, next
-    to a large GEMM - whose grid is sized to whole rounds of 256 CUs - each of them delays a round (training step).
-    ``contexts``: factories of the thread-local launch contexts (hip_ops.seed_base / loss_scale) the launches need; every step re-enters them,
-    so two towers' steppers can be advanced alternately from one thread."""
-
-    def __init__(self, gen, contexts=()):
-        self._gen, self._contexts, self.done, self.result = gen, tuple(contexts), False, None
-
-    def step(self, n: int = 1) -> bool:
-        if self.done:
-            return True
-        from contextlib import ExitStack
-        with ExitStack() as stack:
-            for make in self._contexts:
-                stack.enter_context(make())
-            try:
-                for _ in range(n):
-                    next(self._gen)
-            except StopIteration as stop:
-                self.done, self.result = True, stop.value
-        return self.done
-
-    def finish(self):
-        while not self.step(1 << 20):
-            pass
-        return self.result
-
-
 class HipEncoder(nn.Module):
     """One encoder tower.  ``encode(ids, mask)`` -> CLS embeddings fp32 [M, d]."""
 
@@ -300,7 +268,7 @@ class HipEncoder(nn.Module):
         self._h_stale = False       # the optimizer step left the bf16 shadow unwritten (refresh_shadows(h_stale=True))
         self._t_fresh = False       # flat_t holds the transposes of the current shadows
         self._view_cache = {}       # _cached
-        self._own_scale = None      # loss-scale state of a backward outside the trainer (backward_steps)
+        self._own_scale = None      # loss-scale state of a backward outside the trainer (backward_from_cls)
         self._anchor = None         # encode_autograd's graph anchor
         # set by the trainer:
         self.seed_base_ptr = None           # device address of this tower's per-step dropout seed word (`device_seed` passes)
@@ -620,24 +588,15 @@ class HipEncoder(nn.Module):
         kernels are chosen for: a caller that passes the same width for every batch gets each sequence's attention independent of the
         batch.  Both run the evaluation pass of the tower's mode; ``fp16=True`` / ``hp_forward`` (the all-fp16 query-tower pass) is refused.
 
-        ``fp32=True``: the exact fp32 evaluation pass (:meth:`_encode_f32_gen`): every activation fp32, the weights read from ``flat_p`` in
+        ``fp32=True``: the exact fp32 evaluation pass (:meth:`_encode_f32`): every activation fp32, the weights read from ``flat_p`` in
         place, every contraction on the f32-input MFMA - the reference's ``use_fp16=False`` encode.  It takes ``attention_mask``, ``lengths``
         (the batch is then packed), ``token_type_ids`` and ``packed`` like the evaluation pass, and refuses ``save`` / ``train`` /
         ``device_seed`` / ``fp16=True``: it keeps no tape and has no dropout.  A sequence's CLS vector does not depend on the rest of the
         batch, bit for bit."""
-        return self.encode_steps(input_ids, attention_mask, train=train, save=save, seed=seed, fp16=fp16, lengths=lengths,
-                                 device_seed=device_seed, token_type_ids=token_type_ids, packed=packed, fp32=fp32).finish()
-
-    def encode_steps(self, input_ids, attention_mask, *, train=None, save=False, seed=None, fp16=None, lengths=None, device_seed=False,
-                     window=None, token_type_ids=None, packed=None, fp32=False) -> Stepper:
-        """:meth:`encode` as a :class:`Stepper` (``.finish()`` -> what encode returns).  ``window(kind)`` (optional) is called right before
-        each HBM-bound launch of the pass - kind "ln" (LayerNorm / embedding kernels) or "attn" - on the stream the pass is enqueued on: the
-        hook at which a trainer releases a slice of the OTHER tower's stepper."""
         if fp32:
             if save or train or device_seed or fp16:
                 raise ValueError("encode(fp32=True) is an evaluation pass and nothing else: no save / train / device_seed / fp16")
-            return Stepper(self._encode_f32_gen(input_ids, attention_mask, lengths=lengths, window=window, token_type_ids=token_type_ids,
-                                                packed=packed))
+            return self._encode_f32(input_ids, attention_mask, lengths=lengths, token_type_ids=token_type_ids, packed=packed)
         fp16 = self.hp_forward if fp16 is None else fp16
         # `device_seed` (NwayTrainer only): the per-step part of the seed lives in device memory at `seed_base_ptr` (the trainer advances
         # step_seed and writes next_seed() there before each step); the launches carry offsets only.  Any other caller (encode_autograd,
@@ -656,17 +615,12 @@ class HipEncoder(nn.Module):
             seed = 0
         elif seed is None:
             seed = self.next_seed()
-        gen = self._encode_gen(input_ids, attention_mask, train=train, save=save, seed=seed, all_fp16=all_fp16, lengths=lengths, window=window,
+        with ops.seed_base(base):                   # (no device seed: a no-op context)
+            out = self._encode(input_ids, attention_mask, train=train, save=save, seed=seed, all_fp16=all_fp16, lengths=lengths,
                                token_type_ids=token_type_ids, packed=packed)
-        if not base:
-            return Stepper(gen)
-
-        def mark():
-            out = yield from gen
-            if save:
-                out[1].device_seed = True           # the backward adds the same device word
-            return out
-        return Stepper(mark(), [lambda: ops.seed_base(base)])
+        if base and save:
+            out[1].device_seed = True               # the backward adds the same device word
+        return out
 
     def would_pack(self, lengths, M, L, has_mask=True, fp16=False, train=True, always=False) -> bool:
         """Whether encode() packs a batch with these host-side token counts (CLDRD_PACK=0 turns packing off; thresholds at the
@@ -746,8 +700,8 @@ class HipEncoder(nn.Module):
             tt = ops.gather_i64(tt, pk.tok_idx, pk.Tp)          # the same row index as the ids
         return M, L, pk.Tp, ids, mask, tt, pk
 
-    def _encode_gen(self, input_ids, attention_mask, *, train, save, seed, all_fp16, lengths=None, window=None, token_type_ids=None, packed=None):
-        """One 16-bit forward pass as a generator: a ``yield`` behind every group of launches (:class:`Stepper`); returns cls or (cls, tape).
+    def _encode(self, input_ids, attention_mask, *, train, save, seed, all_fp16, lengths=None, token_type_ids=None, packed=None):
+        """One 16-bit forward pass; returns cls or (cls, tape).
         ``all_fp16``: the all-fp16 pass (:meth:`_is_all_fp16_pass`), else the evaluation pass of the tower's mode or the bf16 training pass."""
         cfg = self.cfg
         train = self.training if train is None else train
@@ -788,15 +742,12 @@ class HipEncoder(nn.Module):
         x = self._buf(T, d, dev, xdt)
         x32 = self._buf(T, d, dev, torch.float32)           # fp32 copy of the layer input: the residual operand
         mean0, rstd0 = torch.empty(T, **f32), torch.empty(T, **f32)
-        if window is not None:
-            window("ln")
         ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"), self.w("embeddings.position_embeddings.weight"),
                          self.w("embeddings.token_type_embeddings.weight") if cfg.arch == "bert" else None, self.w("embeddings.LayerNorm.weight"),
                          self.w("embeddings.LayerNorm.bias"), x, mean0, rstd0, T, L, cfg.eps, p_h, seed, out32=x32,
                          pos_idx=pk.pos if pk is not None else None, type_ids=tt.to(torch.int32) if tt is not None else None)
         if save:
             tape.mean0, tape.rstd0 = mean0, rstd0
-        yield
         cls = torch.empty(M, d, **f32)
         p_out = p_h if cfg.arch == "bert" else 0.0          # DistilBERT has no dropout after out_lin
         # fp32 residual stream: a LayerNorm's fp32 output is consumed exactly once, as the residual operand of the next out-projection /
@@ -809,7 +760,7 @@ class HipEncoder(nn.Module):
             Wf = W16 if FFN16 else W                         # the matrices the FFN pair and the out-projection read
             s_l = seed + 7919 * (i + 1)
             if i == cfg.n_layers - 1 and self.cls_only_last:
-                yield from self._last_layer_cls_fwd(x, x32, W, mask, M, L, T, p_h, p_a, p_out, s_l, save, tape, cls, dt16, W16, pk)
+                self._last_layer_cls_fwd(x, x32, W, mask, M, L, T, p_h, p_a, p_out, s_l, save, tape, cls, dt16, W16, pk)
                 break
             qkv = self._buf(T, 3 * d, dev, dt16)
             ops.gemm_nt(x, (W16 if QKV16 else W)["Wqkv"], qkv, T, bias=W["bqkv"])
@@ -820,27 +771,18 @@ class HipEncoder(nn.Module):
             # loaded nor stored: cldrd_attention_*_varlen) - bit for bit what moving the rows to the padded [M * L, .] layout and back gives
             cu = pk.cu if pk is not None else None
             ctx = self._buf(T, d, dev, dt16) if not FFN16 else None
-            yield
-            if window is not None:
-                window("attn")
             for sl, tile in (pk.groups if pk is not None else [(None, 0)]):
                 ops.attention_fwd(qkv, mask if pk is None else None, ctx, lse, M, L, H, p_a, s_l + 1, drop_bits=dbits, ctx16=ctx16,
                                   full_family=all_fp16, cu=cu, seq_list=sl, tile=tile)
-            yield
             s1 = self._buf(T, d, dev, torch.float32)      # pre-LN sums are stored in fp32: the fp32 residual stream
             ops.gemm_nt(ctx16 if FFN16 else ctx, Wf["Wo"], s1, T, bias=W["bo"], residual=x32, dropout_p=p_out, seed=s_l + 2, residual_ln=res_ln)
             del ctx16
-            yield
-            if window is not None:
-                window("ln")
             mean1, rstd1 = torch.empty(T, **f32), torch.empty(T, **f32)
             x1 = self._buf(T, d, dev, fdt)
             ops.layernorm_fwd(s1, W["g1"], W["b1"], x1, mean1, rstd1, T, cfg.eps)
-            yield
             hbuf = self._buf(T, f, dev, fdt)
             pre = self._buf(T, f, dev, dt16) if save else None
             ops.gemm_nt(x1, Wf["W1"], hbuf, T, bias=W["bf1"], preact=pre, act=3 if save else 1)     # the tape keeps gelu'(pre-activation)
-            yield
             s2 = self._buf(T, d, dev, torch.float32)
             ops.gemm_nt(hbuf, Wf["W2"], s2, T, bias=W["bf2"], residual=s1, dropout_p=p_h, seed=s_l + 3, residual_ln=(mean1, rstd1, W["g1"], W["b1"]))
             if not save:
@@ -851,23 +793,19 @@ class HipEncoder(nn.Module):
             need32 = not last and i + 1 == cfg.n_layers - 1 and self.cls_only_last
             xo32 = self._buf(T, d, dev, torch.float32) if need32 else None
             mean2, rstd2 = torch.empty(T, **f32), torch.empty(T, **f32)
-            yield
-            if window is not None:
-                window("ln")
             ops.layernorm_fwd(s2, W["g2"], W["b2"], xo, mean2, rstd2, T, cfg.eps, cls if last else None, L, out32=xo32)
             if save:
                 tape.layers.append(dict(x_in=x, qkv=qkv, ctx=ctx, lse=lse, dbits=dbits, s1=s1, mean1=mean1, rstd1=rstd1, x1=x1, pre=pre,
                                         h=hbuf, s2=s2, mean2=mean2, rstd2=rstd2, seed=s_l, p_h=p_h, p_a=p_a, p_out=p_out))
             x = xo
             x32, res_ln = (xo32, None) if need32 else (s2, (mean2, rstd2, W["g2"], W["b2"]))
-            yield
         if cfg.n_layers == 0:
             cls.copy_(x.view(ops.pad_rows(T), d)[:T].view(M, L, d)[:, 0].float())
         return (cls, tape) if save else cls
 
     # ------------------------------------------------------------------ the fp32 evaluation pass (csrc/encoder_f32.hip)
-    def _encode_f32_gen(self, input_ids, attention_mask, *, lengths=None, window=None, token_type_ids=None, packed=None):
-        """The exact fp32 evaluation pass as a generator (a ``yield`` behind every group of launches): embedding + LayerNorm, ``n_layers - 1`` full
+    def _encode_f32(self, input_ids, attention_mask, *, lengths=None, token_type_ids=None, packed=None):
+        """The exact fp32 evaluation pass: embedding + LayerNorm, ``n_layers - 1`` full
         layers and the CLS-only last layer, fp32 activations only, weights from ``flat_p`` (``refresh_shadows`` is never reached).  Every kernel
         of the pass treats a row independently of the launch it is in, so ``lengths`` always packs (no thresholds: packed == padded bit for
         bit) - except on a tower built without the CLS-only last layer (test hook), which stays padded and refuses ``packed``."""
@@ -883,13 +821,10 @@ class HipEncoder(nn.Module):
         junk16 = self._buf(T, d, dev, torch.bfloat16)
         stat = torch.empty(2, T, **f32)
         x = buf(T, d)
-        if window is not None:
-            window("ln")
         ops.embed_ln_fwd(ids.view(-1), self.w("embeddings.word_embeddings.weight"), self.w("embeddings.position_embeddings.weight"),
                          self.w("embeddings.token_type_embeddings.weight") if cfg.arch == "bert" else None, self.w("embeddings.LayerNorm.weight"),
                          self.w("embeddings.LayerNorm.bias"), junk16, stat[0], stat[1], T, L, cfg.eps, 0.0, 0, out32=x,
                          pos_idx=pk.pos if pk is not None else None, type_ids=tt.to(torch.int32) if tt is not None else None)
-        yield
         cls = torch.empty(M, d, **f32)
         cu = pk.cu if pk is not None else None
         for i in range(cfg.n_layers):
@@ -899,7 +834,6 @@ class HipEncoder(nn.Module):
                 # K and V for every token; Q, attention, out-projection, FFN and both LayerNorms for token 0 only (as _last_layer_cls_fwd)
                 kv = buf(T, 2 * d)
                 ops.gemm_nt_f32(x, W["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
-                yield
                 if pk is None:
                     xc = x[:T].view(M, L * d)[:, :d]              # rows 0, L, 2L, ...: a strided view (row pitch L * d)
                 else:
@@ -907,53 +841,34 @@ class HipEncoder(nn.Module):
                 qc = buf(M, d)
                 ops.gemm_nt_f32(xc, W["Wqkv"][:d], qc, M, bias=W["bqkv"][:d])
                 ctxc = buf(M, d)
-                if window is not None:
-                    window("attn")
                 ops.attention_fwd_f32(kv, mask, ctxc, M, L, H, cu=cu, qc=qc)
-                yield
                 s1 = buf(M, d)
                 ops.gemm_nt_f32(ctxc, W["Wo"], s1, M, bias=W["bo"], residual=xc)
-                yield
                 x1 = buf(M, d)
                 ops.layernorm_fwd(s1, W["g1"], W["b1"], junk16, None, None, M, cfg.eps, out32=x1)
                 hb = buf(M, f)
                 ops.gemm_nt_f32(x1, W["W1"], hb, M, bias=W["bf1"], act=1)
                 s2 = buf(M, d)
                 ops.gemm_nt_f32(hb, W["W2"], s2, M, bias=W["bf2"], residual=x1)
-                yield
                 ops.layernorm_fwd(s2, W["g2"], W["b2"], junk16, None, None, M, cfg.eps, cls, 1)
-                yield
                 break
             qkv = buf(T, 3 * d)
             ops.gemm_nt_f32(x, W["Wqkv"], qkv, T, bias=W["bqkv"])
-            yield
             ctx = buf(T, d)
-            if window is not None:
-                window("attn")
             ops.attention_fwd_f32(qkv, mask, ctx, M, L, H, cu=cu)
-            yield
             s1 = buf(T, d)
             ops.gemm_nt_f32(ctx, W["Wo"], s1, T, bias=W["bo"], residual=x)
             del qkv, ctx
-            yield
-            if window is not None:
-                window("ln")
             x1 = buf(T, d)
             ops.layernorm_fwd(s1, W["g1"], W["b1"], junk16, None, None, T, cfg.eps, out32=x1)
-            yield
             hb = buf(T, f)
             ops.gemm_nt_f32(x1, W["W1"], hb, T, bias=W["bf1"], act=1)
-            yield
             s2 = buf(T, d)
             ops.gemm_nt_f32(hb, W["W2"], s2, T, bias=W["bf2"], residual=x1)
             del hb, s1
-            yield
-            if window is not None:
-                window("ln")
             x = buf(T, d)
             # a tower built without the CLS-only last layer (never packed): the last LayerNorm pools rows 0, L, 2L, ...
             ops.layernorm_fwd(s2, W["g2"], W["b2"], junk16, None, None, T, cfg.eps, cls if last else None, L, out32=x)
-            yield
         if cfg.n_layers == 0:
             cls.copy_(x[:T].view(M, L, d)[:, 0])
         return cls
@@ -964,7 +879,7 @@ class HipEncoder(nn.Module):
         layer projects K and V for every token but Q, attention, out-proj, FFN and both LayerNorms for token 0 only:
         identical CLS output, ~1/6 of the layer's FLOPs.  ``W16`` (the fp16 matrices): the evaluation pass of the fp16 mode - out-projection
         and FFN pair on fp16 operands; where the layer input ``x`` is fp16 as well, so are the K / V / Q projections' operands (bf16
-        results), see _encode_gen."""
+        results), see _encode."""
         cfg = self.cfg
         d, f, H = cfg.dim, cfg.hidden_dim, cfg.n_heads
         dev = x.device
@@ -975,7 +890,6 @@ class HipEncoder(nn.Module):
         fdt = torch.float16 if FFN16 else dt16
         kv = self._buf(T, 2 * d, dev, dt16)
         ops.gemm_nt(x, Wq["Wqkv"][d:], kv, T, bias=W["bqkv"][d:])
-        yield
         if pk is None:
             # the CLS rows are rows 0, L, 2L, ... of the layer input: STRIDED VIEWS (row pitch L * d), no copies - every consumer (the Q
             # projection's A operand, its weight gradient's X operand, the out-projection's fp32 residual) takes a row pitch, and no
@@ -993,10 +907,8 @@ class HipEncoder(nn.Module):
         probs = torch.empty(M, H, L, **f32)
         ops.attention_cls_fwd(qc, kv, mask if pk is None else None, ctxc, probs, M, L, H, p_a, s_l + 1, ctx16=ctxc16,
                               cu=pk.cu if pk is not None else None)
-        yield
         s1 = self._buf(M, d, dev, torch.float32)
         ops.gemm_nt(ctxc16 if FFN16 else ctxc, Wf["Wo"], s1, M, bias=W["bo"], residual=xc32, dropout_p=p_out, seed=s_l + 2)
-        yield
         x1_32 = self._buf(M, d, dev, torch.float32)
         mean1, rstd1 = (torch.empty(M, **f32), torch.empty(M, **f32)) if save else (None, None)
         x1 = self._buf(M, d, dev, fdt)
@@ -1006,7 +918,6 @@ class HipEncoder(nn.Module):
         ops.gemm_nt(x1, Wf["W1"], hbuf, M, bias=W["bf1"], preact=pre, act=3 if save else 1)
         s2 = self._buf(M, d, dev, torch.float32)
         ops.gemm_nt(hbuf, Wf["W2"], s2, M, bias=W["bf2"], residual=x1_32, dropout_p=p_h, seed=s_l + 3)
-        yield
         xo = self._buf(M, d, dev, dt16)
         mean2, rstd2 = (torch.empty(M, **f32), torch.empty(M, **f32)) if save else (None, None)
         ops.layernorm_fwd(s2, W["g2"], W["b2"], xo, mean2, rstd2, M, cfg.eps, cls, 1)
@@ -1017,7 +928,7 @@ class HipEncoder(nn.Module):
 
     def _last_layer_cls_bwd(self, i, a, tape, dcls, partial, acc, wq, lnq):
         """Backward of :meth:`_last_layer_cls_fwd`; returns dL/d(layer input) as a full [T, d] tensor (fp32 with the fp32 gradient
-        stream, else bf16).  ``acc``, ``wq``, ``lnq``: the accumulate flag and the two queues of the backward this is a part of (_backward_gen)."""
+        stream, else bf16).  ``acc``, ``wq``, ``lnq``: the accumulate flag and the two queues of the backward this is a part of (backward_from_cls)."""
         cfg = self.cfg
         d, f, H = cfg.dim, cfg.hidden_dim, cfg.n_heads
         M, L, T = tape.M, tape.L, tape.T
@@ -1033,7 +944,6 @@ class HipEncoder(nn.Module):
         own = (lambda: torch.empty(ops.ln_partial_elems(M, d), **f32)) if lnq is not None else (lambda: partial)
         ops.layernorm_bwd(gc, a["s2"], a["mean2"], a["rstd2"], W["g2"], ds2, ds2m, G["g2"], G["b2"], G["bf2"], own(), M, p_h, s_l + 3,
                           accumulate=acc, defer=lnq)
-        yield
         dF = ds2m if ds2m is not None else ds2
         wq.add(dF, a["h"], G["W2"], M)
         dpre = buf(M, f, dev)
@@ -1041,7 +951,6 @@ class HipEncoder(nn.Module):
         wq.add(dpre, a["x1"], G["W1"], M, dbias=G["bf1"])
         dx1 = buf(M, d, dev, torch.float32)
         ops.gemm_nt(dpre, self.ht(i, "f1"), dx1, M, residual=ds2)
-        yield
         ds1 = buf(M, d, dev, torch.float32)
         ds1m = buf(M, d, dev)
         ops.layernorm_bwd(dx1, a["s1"], a["mean1"], a["rstd1"], W["g1"], ds1, ds1m, G["g1"], G["b1"], G["bo"], own(), M, p_out, s_l + 2,
@@ -1050,14 +959,12 @@ class HipEncoder(nn.Module):
         wq.add(dA, a["ctx"], G["Wo"], M)
         dctx = buf(M, d, dev)
         ops.gemm_nt(dA, self.ht(i, "o"), dctx, M)
-        yield
         dqc = buf(M, d, dev)
         pk = tape.pack
         dkv = buf(T, 2 * d, dev)                                    # (T = the packed row count of a packed batch)
         ops.attention_cls_bwd(a["qc"], a["kv"], a["probs"], dctx, dqc, dkv, M, L, H, p_a, s_l + 1, cu=pk.cu if pk is not None else None)
         wq.add(dqc, a["xc"], G["Wqkv"][:d], M, dbias=G["bqkv"][:d])
         wq.add(dkv, a["x_in"], G["Wqkv"][d:], T, dbias=G["bqkv"][d:])
-        yield
         wt = self.ht(i, "qkv")                                      # [d, 3d] = Wqkv^T
         # the [T, d] gradient this layer hands down: fp32 - or fp16 with the fp16 gradient stream (the layer's own M-row stream stays fp32:
         # the CLS rows are added from the fp32 gq with one rounding)
@@ -1081,17 +988,7 @@ class HipEncoder(nn.Module):
 
         ``before_last_wgrad()`` (optional) is called once, right before the LAST group of deferred weight gradients is launched:
         from there on this stream runs one long launch that is on nobody's critical path."""
-        return self.backward_steps(tape, dcls, after_layer=after_layer, accumulate=accumulate, check_grads=check_grads,
-                                   before_last_wgrad=before_last_wgrad).finish()
-
-    def backward_steps(self, tape: _Tape, dcls: torch.Tensor, after_layer=None, accumulate: bool = True, check_grads: bool = False,
-                       before_last_wgrad=None, window=None) -> Stepper:
-        """:meth:`backward_from_cls` as a :class:`Stepper`; ``window(kind)`` as in :meth:`encode_steps` (before LayerNorm / attention backward
-        launches)."""
-        contexts = []
-        base = self.seed_base_ptr if tape.device_seed else None
-        if base:
-            contexts.append(lambda: ops.seed_base(base))
+        own_scale = None
         if (self.amp16 and getattr(ops._TLS, "loss_scale", None) is None and tape.layers and tape.layers[-1] is not None
                 and tape.layers[-1]["h"].dtype == torch.float16):
             # an fp16 tape outside the trainer (the autograd bridge of the reference-style loop: dL/dCLS arrives unscaled): this tower scales
@@ -1101,143 +998,124 @@ class HipEncoder(nn.Module):
                 st = self._own_scale = ops.new_loss_scale_state(self.flat_p.device)
             dcls = dcls.contiguous().clone()
             ops.loss_scale_adapt(dcls, None, st)
-            contexts.append(lambda: ops.loss_scale(st.data_ptr()))
-        return Stepper(self._backward_gen(tape, dcls, after_layer, accumulate, check_grads, before_last_wgrad, window), contexts)
+            own_scale = st.data_ptr()
+        # the launch contexts of the pass (no-ops where they do not apply): the device seed word of a `device_seed` tape, the tower's own scale
+        with ops.seed_base(self.seed_base_ptr if tape.device_seed else None), ops.loss_scale(own_scale):
+            acc = bool(accumulate)
+            cfg = self.cfg
+            self.ensure_grads(check_all=check_grads)
+            # Weight gradients are deferred (hip_ops.WgradQueue): only the data gradients are on the critical path.  They are launched
+            # as one group at the end of the backward, or every `wgrad_flush_layers` layers when somebody (the trainer's all-reduce
+            # hooks) wants layers to complete early; `after_layer(i)` is only called once layer i's weight gradients have been launched.
+            wq = ops.WgradQueue()
+            # LayerNorm gamma / beta (and the preceding Linear's bias) gradients are deferred likewise (`ln_defer`): each layernorm_bwd
+            # leaves its per-block sums in a scratch buffer of its own and one launch next to the weight-gradient group reduces them all.
+            # Bit-identical and 22 launches fewer per step; with the step replayed as a HIP graph -1.0 % step time at cfg2, twice on one box
+            # (profiles/r03_microbench.txt).  `ln_defer = False` (test hook) restores the immediate reductions.
+            lnq = ops.LnReduceQueue() if self.ln_defer else None
+            flush_every = int(self.wgrad_flush_layers or 0)
+            waiting = []
 
-    def _backward_gen(self, tape, dcls, after_layer, accumulate, check_grads, before_last_wgrad, window):
-        # `acc`, `wq` and `lnq` belong to THIS backward: a tower may have two of them alive at once (two tapes of a shared tower, two steppers)
-        acc = bool(accumulate)
-        cfg = self.cfg
-        self.ensure_grads(check_all=check_grads)
-        # Weight gradients are deferred (hip_ops.WgradQueue): only the data gradients are on the critical path.  They are launched
-        # as one group at the end of the backward, or every `wgrad_flush_layers` layers when somebody (the trainer's all-reduce
-        # hooks) wants layers to complete early; `after_layer(i)` is only called once layer i's weight gradients have been launched.
-        wq = ops.WgradQueue()
-        # LayerNorm gamma / beta (and the preceding Linear's bias) gradients are deferred likewise (`ln_defer`): each layernorm_bwd
-        # leaves its per-block sums in a scratch buffer of its own and one launch next to the weight-gradient group reduces them all.
-        # Bit-identical and 22 launches fewer per step; with the step replayed as a HIP graph -1.0 % step time at cfg2, twice on one box
-        # (profiles/r03_microbench.txt).  `ln_defer = False` (test hook) restores the immediate reductions.
-        lnq = ops.LnReduceQueue() if self.ln_defer else None
-        flush_every = int(self.wgrad_flush_layers or 0)
-        waiting = []
-
-        def layer_done(i, force=False):
-            if i == -1 and after_layer is not None:
-                # The embedding block (i = -1) is complete as soon as embed_ln_bwd has been launched - it has no deferred weight
-                # gradient - so its hook runs BEFORE the last weight-gradient group is launched: the largest all-reduce bucket of the
-                # tower (94 MB at DistilBERT) then travels under that group instead of after it.
-                after_layer(-1)
-            else:
-                waiting.append(i)
-            # (layer 0 never triggers an early flush: its group waits for the forced one behind embed_ln_bwd, so that the embedding block's
-            # hook - the tower's largest all-reduce bucket - is issued IN FRONT of a weight-gradient group it can travel under.  Otherwise
-            # a layer count that `wgrad_flush_layers` divides (6 / 3, 12 / 6: every shipped config) would launch the last group at layer 0 and
-            # the embedding bucket would go out with nothing left to overlap it: tools/bucket_plan.py)
-            if force or (flush_every > 0 and len(waiting) >= flush_every and i != 0):
-                if force and before_last_wgrad is not None:
-                    before_last_wgrad()
-                # `norm_sink` (the trainer's, one GPU): when this ONE flush produces every layer gradient of the tower - LayerNorm reductions
-                # deferred, no early flushes - the two launches also leave the clip norm's partial sums of what they write (hip_ops.norm_sink)
-                sink = self.norm_sink if (force and flush_every == 0 and lnq is not None and not acc) else None
-                with ops.norm_sink(sink) as ns:
-                    if lnq is not None:
-                        lnq.flush(accumulate=acc)
-                    wq.flush(accumulate=acc)
-                self.norm_sink_used = ns.used if sink is not None else -1
-                if after_layer is not None:
-                    for j in waiting:
-                        after_layer(j)
-                waiting.clear()
-        M, L, T = tape.M, tape.L, tape.T
-        d, f, H = cfg.dim, cfg.hidden_dim, cfg.n_heads
-        dev = self.flat_p.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        partial = torch.empty(max(ops.ln_partial_elems(T, d), ((T + 127) // 128) * max(3 * d, f)), **f32)
-        g = gb = None         # gradient of the current layer's output: g (+ gb, a bf16 branch term, with the fp32 gradient stream)
-        for i in reversed(range(cfg.n_layers)):
-            W, G, a = self._layer_weights(i), self._layer_grads(i), tape.layers[i]
-            if a.get("cls_only"):
-                g = yield from self._last_layer_cls_bwd(i, a, tape, dcls, partial, acc, wq, lnq)
-                tape.layers[i] = None
+            def layer_done(i, force=False):
+                if i == -1 and after_layer is not None:
+                    # The embedding block (i = -1) is complete as soon as embed_ln_bwd has been launched - it has no deferred weight
+                    # gradient - so its hook runs BEFORE the last weight-gradient group is launched: the largest all-reduce bucket of the
+                    # tower (94 MB at DistilBERT) then travels under that group instead of after it.
+                    after_layer(-1)
+                else:
+                    waiting.append(i)
+                # (layer 0 never triggers an early flush: its group waits for the forced one behind embed_ln_bwd, so that the embedding block's
+                # hook - the tower's largest all-reduce bucket - is issued IN FRONT of a weight-gradient group it can travel under.  Otherwise
+                # a layer count that `wgrad_flush_layers` divides (6 / 3, 12 / 6: every shipped config) would launch the last group at layer 0 and
+                # the embedding bucket would go out with nothing left to overlap it: tools/bucket_plan.py)
+                if force or (flush_every > 0 and len(waiting) >= flush_every and i != 0):
+                    if force and before_last_wgrad is not None:
+                        before_last_wgrad()
+                    # `norm_sink` (the trainer's, one GPU): when this ONE flush produces every layer gradient of the tower - LayerNorm reductions
+                    # deferred, no early flushes - the two launches also leave the clip norm's partial sums of what they write (hip_ops.norm_sink)
+                    sink = self.norm_sink if (force and flush_every == 0 and lnq is not None and not acc) else None
+                    with ops.norm_sink(sink) as ns:
+                        if lnq is not None:
+                            lnq.flush(accumulate=acc)
+                        wq.flush(accumulate=acc)
+                    self.norm_sink_used = ns.used if sink is not None else -1
+                    if after_layer is not None:
+                        for j in waiting:
+                            after_layer(j)
+                    waiting.clear()
+            M, L, T = tape.M, tape.L, tape.T
+            d, f, H = cfg.dim, cfg.hidden_dim, cfg.n_heads
+            dev = self.flat_p.device
+            f32 = dict(dtype=torch.float32, device=dev)
+            partial = torch.empty(max(ops.ln_partial_elems(T, d), ((T + 127) // 128) * max(3 * d, f)), **f32)
+            g = gb = None         # gradient of the current layer's output: g (+ gb, a bf16 branch term, with the fp32 gradient stream)
+            for i in reversed(range(cfg.n_layers)):
+                W, G, a = self._layer_weights(i), self._layer_grads(i), tape.layers[i]
+                if a.get("cls_only"):
+                    g = self._last_layer_cls_bwd(i, a, tape, dcls, partial, acc, wq, lnq)
+                    tape.layers[i] = None
+                    layer_done(i)
+                    continue
+                bdt = a["h"].dtype                                          # 16-bit format of this backward = the tape's (fp16 in amp16)
+                # the gradient stream (residual path): its arithmetic is fp32 inside the LayerNorm backward, where stream and branch are added;
+                # BETWEEN kernels it is stored in fp16 in the fp16 mode (see __init__), in fp32 in the bf16 mode
+                G16 = self.grad_stream16 and bdt == torch.float16
+                sdt = torch.float16 if G16 else torch.float32
+                buf = lambda r, c, dv, dt=None: self._buf(r, c, dv, bdt if dt is None else dt)
+                if g is None:
+                    g = buf(T, d, dev, sdt)
+                    ops.scatter_cls_grad(dcls.contiguous(), g, M, T, stride=L, idx=tape.pack.cls_idx if tape.pack is not None else None)
+                s_l, p_h, p_a, p_out = a["seed"], a["p_h"], a["p_a"], a["p_out"]
+                # --- output LayerNorm + FFN ---
+                ds2 = buf(T, d, dev, sdt)
+                # the 16-bit MFMA operand of the FFN2 data / weight gradients: a tensor of its own when dropout separates it from the stream, or
+                # when the stream is fp32; with the fp16 stream and no dropout the stream tensor serves
+                ds2m = buf(T, d, dev) if (p_h > 0 or not G16) else None
+                own =(lambda: torch.empty(ops.ln_partial_elems(T, d), **f32)) if lnq is not None else (lambda: partial)
+                # fp32 stream: the gradient of a LayerNorm output is `g` (fp32: the residual path) + `gb` (bf16: the plain output of the
+                # branch's last data-gradient GEMM), added inside layernorm_bwd - not in that GEMM's epilogue (200 MB less per GEMM)
+                ops.layernorm_bwd(g, a["s2"], a["mean2"], a["rstd2"], W["g2"], ds2, ds2m, G["g2"], G["b2"], G["bf2"], own(), T,
+                                  p_h, s_l + 3, accumulate=acc, defer=lnq, dy_branch=gb)
+                dF = ds2m if ds2m is not None else ds2
+                wq.add(dF, a["h"], G["W2"], T)
+                dpre = buf(T, f, dev)
+                ops.gemm_nt(dF, self.ht(i, "f2"), dpre, T, gelu_pre=a["pre"], act=2)
+                wq.add(dpre, a["x1"], G["W1"], T, dbias=G["bf1"])
+                dx1 = buf(T, d, dev)
+                ops.gemm_nt(dpre, self.ht(i, "f1"), dx1, T)                 # the FFN branch alone; the residual path is ds2
+                # --- attention-output LayerNorm + attention ---
+                ds1 = buf(T, d, dev, sdt)
+                ds1m = buf(T, d, dev) if (p_out > 0 or not G16) else None
+                ops.layernorm_bwd(ds2, a["s1"], a["mean1"], a["rstd1"], W["g1"], ds1, ds1m, G["g1"], G["b1"], G["bo"], own(), T,
+                                  p_out, s_l + 2, accumulate=acc, defer=lnq, dy_branch=dx1)
+                dA = ds1m if ds1m is not None else ds1
+                wq.add(dA, a["ctx"], G["Wo"], T)
+                dctx = buf(T, d, dev)
+                ops.gemm_nt(dA, self.ht(i, "o"), dctx, T)
+                pk = tape.pack
+                dqkv = buf(T, 3 * d, dev)
+                for sl, tile in (pk.groups if pk is not None else [(None, 0)]):
+                    ops.attention_bwd(a["qkv"], tape.mask if pk is None else None, a["ctx"], dctx, a["lse"], dqkv, M, L, H, p_a, s_l + 1,
+                                      drop_bits=a.get("dbits"), cu=pk.cu if pk is not None else None, seq_list=sl, tile=tile)
+                wq.add(dqkv, a["x_in"], G["Wqkv"], T, dbias=G["bqkv"])
+                gb = buf(T, d, dev)
+                ops.gemm_nt(dqkv, self.ht(i, "qkv"), gb, T)                 # the attention branch alone
+                g = ds1                                                     # the residual path
+                tape.layers[i] = None        # this layer's activations: the deferred weight-gradient jobs keep what they still need
                 layer_done(i)
-                yield
-                continue
-            bdt = a["h"].dtype                                          # 16-bit format of this backward = the tape's (fp16 in amp16)
-            # the gradient stream (residual path): its arithmetic is fp32 inside the LayerNorm backward, where stream and branch are added;
-            # BETWEEN kernels it is stored in fp16 in the fp16 mode (see __init__), in fp32 in the bf16 mode
-            G16 = self.grad_stream16 and bdt == torch.float16
-            sdt = torch.float16 if G16 else torch.float32
-            buf = lambda r, c, dv, dt=None: self._buf(r, c, dv, bdt if dt is None else dt)
-            if g is None:
-                g = buf(T, d, dev, sdt)
-                ops.scatter_cls_grad(dcls.contiguous(), g, M, T, stride=L, idx=tape.pack.cls_idx if tape.pack is not None else None)
-            s_l, p_h, p_a, p_out = a["seed"], a["p_h"], a["p_a"], a["p_out"]
-            # --- output LayerNorm + FFN ---
-            ds2 = buf(T, d, dev, sdt)
-            # the 16-bit MFMA operand of the FFN2 data / weight gradients: a tensor of its own when dropout separates it from the stream, or
-            # when the stream is fp32; with the fp16 stream and no dropout the stream tensor serves
-            ds2m = buf(T, d, dev) if (p_h > 0 or not G16) else None
-            own =(lambda: torch.empty(ops.ln_partial_elems(T, d), **f32)) if lnq is not None else (lambda: partial)
-            # fp32 stream: the gradient of a LayerNorm output is `g` (fp32: the residual path) + `gb` (bf16: the plain output of the
-            # branch's last data-gradient GEMM), added inside layernorm_bwd - not in that GEMM's epilogue (200 MB less per GEMM)
-            if window is not None:
-                window("ln")
-            ops.layernorm_bwd(g, a["s2"], a["mean2"], a["rstd2"], W["g2"], ds2, ds2m, G["g2"], G["b2"], G["bf2"], own(), T,
-                              p_h, s_l + 3, accumulate=acc, defer=lnq, dy_branch=gb)
-            yield
-            dF = ds2m if ds2m is not None else ds2
-            wq.add(dF, a["h"], G["W2"], T)
-            dpre = buf(T, f, dev)
-            ops.gemm_nt(dF, self.ht(i, "f2"), dpre, T, gelu_pre=a["pre"], act=2)
-            yield
-            wq.add(dpre, a["x1"], G["W1"], T, dbias=G["bf1"])
-            dx1 = buf(T, d, dev)
-            ops.gemm_nt(dpre, self.ht(i, "f1"), dx1, T)                 # the FFN branch alone; the residual path is ds2
-            # --- attention-output LayerNorm + attention ---
-            ds1 = buf(T, d, dev, sdt)
-            ds1m = buf(T, d, dev) if (p_out > 0 or not G16) else None
-            yield
-            if window is not None:
-                window("ln")
-            ops.layernorm_bwd(ds2, a["s1"], a["mean1"], a["rstd1"], W["g1"], ds1, ds1m, G["g1"], G["b1"], G["bo"], own(), T,
-                              p_out, s_l + 2, accumulate=acc, defer=lnq, dy_branch=dx1)
-            dA = ds1m if ds1m is not None else ds1
-            wq.add(dA, a["ctx"], G["Wo"], T)
-            dctx = buf(T, d, dev)
-            yield
-            ops.gemm_nt(dA, self.ht(i, "o"), dctx, T)
-            pk = tape.pack
-            yield
-            if window is not None:
-                window("attn")
-            dqkv = buf(T, 3 * d, dev)
-            for sl, tile in (pk.groups if pk is not None else [(None, 0)]):
-                ops.attention_bwd(a["qkv"], tape.mask if pk is None else None, a["ctx"], dctx, a["lse"], dqkv, M, L, H, p_a, s_l + 1,
-                                  drop_bits=a.get("dbits"), cu=pk.cu if pk is not None else None, seq_list=sl, tile=tile)
-            wq.add(dqkv, a["x_in"], G["Wqkv"], T, dbias=G["bqkv"])
-            yield
-            gb = buf(T, d, dev)
-            ops.gemm_nt(dqkv, self.ht(i, "qkv"), gb, T)                 # the attention branch alone
-            g = ds1                                                     # the residual path
-            tape.layers[i] = None        # this layer's activations: the deferred weight-gradient jobs keep what they still need
-            layer_done(i)
-            yield
-        type0 = self.w("embeddings.token_type_embeddings.weight")[0] if cfg.arch == "bert" else None
-        dtype0 = self.g("embeddings.token_type_embeddings.weight")[0] if cfg.arch == "bert" else None
-        if window is not None:
-            window("ln")
-        # deterministic_embed: one fp32 row per token, then the two table sums in a fixed order (three launches, the tables finished behind
-        # the last one) instead of the float atomics; the orders were built by the forward that kept this tape
-        det = dict(word_order=tape.word_order, pos_order=tape.pos_order, rows=self._buf(T, d, dev, torch.float32)) if tape.word_order is not None else {}
-        (ops.embed_ln_bwd_det if det else ops.embed_ln_bwd)(
-            g, tape.ids.view(-1), self.w("embeddings.word_embeddings.weight"),
-            self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
-            tape.mean0, tape.rstd0, self.g("embeddings.word_embeddings.weight"),
-            self.g("embeddings.position_embeddings.weight"), dtype0, self.g("embeddings.LayerNorm.weight"),
-            self.g("embeddings.LayerNorm.bias"), partial, T, L, tape.p_embed, tape.seed, accumulate=acc,
-            pos_idx=tape.pack.pos if tape.pack is not None else None, dy_branch=gb, **det)
-        yield
-        layer_done(-1, force=True)
+            type0 = self.w("embeddings.token_type_embeddings.weight")[0] if cfg.arch == "bert" else None
+            dtype0 = self.g("embeddings.token_type_embeddings.weight")[0] if cfg.arch == "bert" else None
+            # deterministic_embed: one fp32 row per token, then the two table sums in a fixed order (three launches, the tables finished behind
+            # the last one) instead of the float atomics; the orders were built by the forward that kept this tape
+            det = dict(word_order=tape.word_order, pos_order=tape.pos_order, rows=self._buf(T, d, dev, torch.float32)) if tape.word_order is not None else {}
+            (ops.embed_ln_bwd_det if det else ops.embed_ln_bwd)(
+                g, tape.ids.view(-1), self.w("embeddings.word_embeddings.weight"),
+                self.w("embeddings.position_embeddings.weight"), type0, self.w("embeddings.LayerNorm.weight"),
+                tape.mean0, tape.rstd0, self.g("embeddings.word_embeddings.weight"),
+                self.g("embeddings.position_embeddings.weight"), dtype0, self.g("embeddings.LayerNorm.weight"),
+                self.g("embeddings.LayerNorm.bias"), partial, T, L, tape.p_embed, tape.seed, accumulate=acc,
+                pos_idx=tape.pack.pos if tape.pack is not None else None, dy_branch=gb, **det)
+            layer_done(-1, force=True)
 
     # ------------------------------------------------------------------ HF-style call surface
     def forward(self, input_ids=None, attention_mask=None, **_):

@@ -168,15 +168,12 @@ class NwayTrainer:
         self.l_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
         self._pending = []
         self._sink_on = False
-        self._windows_on = False           # this step's forward ran the window schedule (its backward then does too)
         self._graph_broken = False         # a capture of the step failed: every later step runs eagerly
         self._norm_split = None            # the clip norm's early piece covers flat_g[:_norm_split] (_early_norm_hook)
         self._norm_deferred = None
         # test hooks (tests/test_gpu_model.py, test_gpu_amp16.py prove the default path equal to the plain one they select; not configuration):
         self.zero_all_grads = False        # True: zero the whole gradient buffer and accumulate instead of writing every gradient once
         self.use_norm_sink = True          # False: the late clip-norm piece by a separate pass over the gradients
-        self.window_schedule = False       # True: the query tower enqueued in slices released at the passage tower's LayerNorm / attention launches
-                                           # (round 6, measured and NOT adopted: 11.58-11.92 ms per cfg2 step against 11.01 free-running, see forward_backward)
         # CLDRD_AMP=fp16 towers (encoder.py: amp16): the loss scale lives in device memory (hip_ops.new_loss_scale_state).  It is set every
         # step from dL/dCLS (ops.loss_scale_adapt: a power of two that puts the largest entering gradient at 2^11..2^12); what is kept of
         # torch.cuda.amp.GradScaler (the reference: nway_listwise_1.py:355-359) is its safety net: a non-finite gradient norm skips the step
@@ -250,24 +247,6 @@ class NwayTrainer:
             self._norm_split = split
         return hook
 
-    # groups of the query tower's stepper (encoder.Stepper: one group = one GEMM / attention / LayerNorm launch, plus its split-K finish) released
-    # per window of the passage tower: an attention kernel lasts ~55 us forward / ~107 us backward at cfg2, a LayerNorm kernel 29-50 us, a small
-    # query-tower launch 7-10 us; one passage layer then releases seven groups = one query layer
-    FWD_SLICE = {"attn": 3, "ln": 2}
-    BWD_SLICE = {"attn": 3, "ln": 2}
-
-    @staticmethod
-    def _window(main, side, stepper, slices):
-        def window(kind):
-            if stepper.done:
-                return
-            ev = torch.cuda.Event()
-            ev.record(main)                  # fires when the main stream reaches the HBM-bound kernel enqueued right after this call
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                stepper.step(slices[kind])
-        return window
-
     def _finish_early_norm(self, side):
         d = self._norm_deferred
         self._norm_deferred = None
@@ -322,29 +301,12 @@ class NwayTrainer:
             for tower in model.towers():
                 if not tower._t_fresh:
                     tower.refresh_transposed()
-        # Round 6 experiment, OFF by default (`window_schedule`): the query tower enqueued in SLICES, each released by an event the main stream
-        # records at the start of one of the passage tower's HBM-bound kernels (LayerNorm, attention), instead of running free next to everything -
-        # the idea being that a 64 x 64-tile GEMM next to a kernel that waits for HBM costs nothing, while next to a large GEMM (a grid sized to
-        # whole rounds of 256 CUs) it delays a round (0.32 ms of interference per step, profiles/r05_microbench.txt section 14).  Measured on one
-        # box, interleaved rounds (profiles/r06_microbench.txt section 1): free-running 11.01 ms per step; slices of 3 / 2 groups per attention /
-        # LayerNorm window 11.66; 2 / 1: 11.92; 4 / 3: 11.72; 7 / 7: 11.58.  The tighter the gating the slower: a gated chain of ~130 dependent
-        # small launches finishes late (every release waits for the main stream to REACH a window, and the chain then still needs its own
-        # 7-10 us per launch), so the join in front of the loss / the last weight-gradient group waits for it - that costs more than the
-        # interference it avoids.  The stepping API (encoder.Stepper) stays: encode / backward are built on it.
-        windows = side is not main and self.window_schedule
-        self._windows_on = windows
+        # (The query tower enqueued in slices, each released at one of the passage tower's HBM-bound kernels, was measured 5-8 % slower than
+        # this free-running schedule and removed: profiles/r06_microbench.txt section 1.)
         p_ids, p_mask = nw["input_ids"].reshape(bz * nway, L), nw["attention_mask"].reshape(bz * nway, L)
-        if windows:
-            with torch.cuda.stream(side):
-                q_step = qe.encode_steps(q["input_ids"], q.get("attention_mask"), train=True, save=True, fp16=model.query_fp16, device_seed=True)
-            p_cls, p_tape = pe.encode_steps(p_ids, p_mask, train=True, save=True, fp16=False, lengths=_lengths(nw), device_seed=True,
-                                            window=self._window(main, side, q_step, self.FWD_SLICE)).finish()
-            with torch.cuda.stream(side):
-                q_cls, q_tape = q_step.finish()          # whatever is left (nothing, when the slices kept pace)
-        else:
-            with torch.cuda.stream(side):
-                q_cls, q_tape = qe.encode(q["input_ids"], q.get("attention_mask"), train=True, save=True, fp16=model.query_fp16, device_seed=True)
-            p_cls, p_tape = pe.encode(p_ids, p_mask, train=True, save=True, fp16=False, lengths=_lengths(nw), device_seed=True)      # "lengths" given: a packed batch
+        with torch.cuda.stream(side):
+            q_cls, q_tape = qe.encode(q["input_ids"], q.get("attention_mask"), train=True, save=True, fp16=model.query_fp16, device_seed=True)
+        p_cls, p_tape = pe.encode(p_ids, p_mask, train=True, save=True, fp16=False, lengths=_lengths(nw), device_seed=True)      # "lengths" given: a packed batch
         if side is not main:
             main.wait_stream(side)
             q_cls.record_stream(main)
@@ -390,8 +352,8 @@ class NwayTrainer:
             q_cls.record_stream(lst)
             p_cls.record_stream(lst)
         with ops.loss_scale(self._scale_state.data_ptr() if self.amp16 else None, self.scale_growth_interval):
-            return self._backward(batch, model, qe, pe, q_cls, p_cls, q_tape, p_tape, dlogits, dq, dp, bz, nway, mode, main, side, write_once, loss_out, logits,
-                                  lst)
+            self._backward(q_tape, p_tape, dq, dp, main, side, lst, write_once)
+        return loss_out, logits
 
     def _teacher_scores(self, batch, bz, nway):
         """batch["teacher_scores"] of a distilling trainer ([B, nway], checked); None for a trainer without ``distill`` (the key is ignored)."""
@@ -405,10 +367,11 @@ class NwayTrainer:
             raise ValueError(f"batch['teacher_scores'] must be [{bz}, {nway}] like the passages, got {tuple(t.shape)}")
         return t
 
-    def _backward(self, batch, model, qe, pe, q_cls, p_cls, q_tape, p_tape, dlogits, dq, dp, bz, nway, mode, main, side, write_once, loss_out, logits,
-                  lst=None):
-        """both towers' backward from dq / dp (scaled by the loss scale in the amp16 mode) + the bucket all-reduces"""
-        if model.share_weights:
+    def _backward(self, q_tape, p_tape, dq, dp, main, side, lst, write_once):
+        """both towers' backward from dq / dp (scaled by the loss scale in the amp16 mode) + the bucket all-reduces.  ``main``, ``side``, ``lst``:
+        the streams of the passage tower, the query tower and the loss (forward_backward; any of the last two may be ``main`` itself)."""
+        qe, pe = self.model.query_encoder, self.model.passage_encoder
+        if self.model.share_weights:
             # one tower, two tapes: gradients accumulate; all-reduce once everything is in
             pe.backward_from_cls(p_tape, dp)
             qe.backward_from_cls(q_tape, dq)
@@ -417,7 +380,7 @@ class NwayTrainer:
         else:
             def query_backward():
                 if side is not main:
-                    side.wait_stream(lst if (lst is not None and lst is not main) else main)
+                    side.wait_stream(lst)
                     dq.record_stream(side)
                 with torch.cuda.stream(side):
                     qe.backward_from_cls(q_tape, dq, after_layer=self._bucket_hook(0), accumulate=not write_once)
@@ -431,17 +394,8 @@ class NwayTrainer:
             # (the critical path) sat idle for 0.62 ms behind the loss in every replayed step (kernel trace, profiles/r04_microbench.txt
             # section 14).  So a captured step enqueues the passage tower first; the query tower's chain is released ~1.8 ms behind the loss
             # and still ends 4 ms before the join.
-            windows = side is not main and self._windows_on
-            q_late = side is not main and (torch.cuda.is_current_stream_capturing() or windows)
-            q_bstep = None
-            if windows:
-                # sliced like the forward: the query tower's backward is created here (inside the loss-scale context) and enqueued by the
-                # passage tower's backward windows; what is left follows the passage tower's last weight-gradient group
-                side.wait_stream(lst if (lst is not None and lst is not main) else main)
-                dq.record_stream(side)
-                with torch.cuda.stream(side):
-                    q_bstep = qe.backward_steps(q_tape, dq, after_layer=self._bucket_hook(0), accumulate=not write_once)
-            elif not q_late:
+            q_late = side is not main and torch.cuda.is_current_stream_capturing()
+            if not q_late:
                 query_backward()
             self._norm_split = None
             self._norm_deferred = None
@@ -453,22 +407,14 @@ class NwayTrainer:
                 if self.use_norm_sink:      # (test hook: False takes the late piece by a separate pass)
                     self._sink_on = True
                     pe.norm_sink = self.norm_partial[ops.sqnorm_blocks() // 2:ops.sqnorm_blocks() // 2 + self._sink_cap]
-            if q_bstep is not None:
-                pe.backward_steps(p_tape, dp, after_layer=p_hook, accumulate=not write_once,
-                                  window=self._window(main, side, q_bstep, self.BWD_SLICE)).finish()
-                with torch.cuda.stream(side):
-                    q_bstep.finish()
+            pe.backward_from_cls(p_tape, dp, after_layer=p_hook, accumulate=not write_once)
+            if q_late:
+                # (released together with the passage tower's last weight-gradient group instead: +1.4 %, as in round 3's eager measurement)
+                query_backward()
                 self._finish_early_norm(side)
-            else:
-                pe.backward_from_cls(p_tape, dp, after_layer=p_hook, accumulate=not write_once)
-                if q_late:
-                    # (released together with the passage tower's last weight-gradient group instead: +1.4 %, as in round 3's eager measurement)
-                    query_backward()
-                    self._finish_early_norm(side)
             main.wait_stream(side)
             if self.distributed:
                 self._wait_pending()
-        return loss_out, logits
 
     def optimizer_step(self):
         """clip_grad_norm_ + AdamW + scheduler.step of reference nway_listwise_1.py:355-367 (bf16: no GradScaler)."""

@@ -178,69 +178,50 @@ def test_trainer_step_walks_with_stubbed_kernels(stubbed, monkeypatch):
     assert tr.global_step == 1 and "cldrd_adamw_step" in stubbed[n0:] and "cldrd_loss_fwd_bwd" in stubbed[n0:]
 
 
-def test_window_scheduled_step_walks_and_interleaves_the_two_towers(stubbed, monkeypatch):
-    """Round 6: the query tower is enqueued in slices released at the passage tower's LayerNorm / attention launches (encoder.Stepper,
-    NwayTrainer._window).  With stubbed kernels and fake streams: the launch sequence of a step must contain every launch of the free-running
-    schedule exactly once (same multiset), the query tower's launches must be INTERLEAVED with the passage tower's (not all in front), and
-    forward and backward must each have drained their stepper."""
-    from cldrd_amd.trainer import nway_listwise as TL
-    monkeypatch.setattr(TL.NwayTrainer, "_require_gpu", staticmethod(lambda dev: None))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _MAIN)
-    monkeypatch.setattr(torch.cuda, "stream", lambda s_: _Null())
-    monkeypatch.setattr(torch.cuda, "Stream", lambda *a, **k: _FakeStream())
-    monkeypatch.setattr(torch.cuda, "Event", lambda *a, **k: _FakeEvent())
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    monkeypatch.setattr(torch.Tensor, "record_stream", lambda self, s_: None)
-    monkeypatch.setenv("CLDRD_GRAPH", "0")
-    seqs = {}
-    for windows in (False, True):
-        torch.manual_seed(0)
-        model = NwayDualEncoder(cfg_of("distilbert", 3), share_weights=False)
-        tr = TL.NwayTrainer(model, loss="kl_div")
-        tr.q_stream, tr.l_stream = _FakeStream(), _FakeStream()
-        tr.window_schedule = windows
-        batch = syn.nway_batch(5, 2, 3, 6, 20, vocab=512, ragged=False, label_kind="teacher")
-        n0 = len(stubbed)
-        tr.train_step(batch)
-        seqs[windows] = list(stubbed[n0:])
-        assert tr.global_step == 1
-    assert sorted(seqs[True]) == sorted(seqs[False]) and seqs[True] != seqs[False]
-    # free-running: the query tower's whole forward (its embedding kernel first) is enqueued before the passage tower's first launch;
-    # windowed: the passage tower's embedding kernel comes first and the two towers' attention launches alternate
-    first_attn = [i for i, n in enumerate(seqs[True]) if n == "cldrd_attention_fwd"]
-    assert len(first_attn) >= 4
-    emb = [i for i, n in enumerate(seqs[True]) if n == "cldrd_embed_ln_fwd"]
-    assert len(emb) == 2 and emb[1] - emb[0] <= 3           # both embedding launches at the very start of the windowed forward
-
-
-
 @pytest.mark.parametrize("ln_defer", [True, False])
-def test_two_backward_steppers_on_one_tower_keep_their_own_queues(stubbed, monkeypatch, ln_defer):
-    """backward_steps is public and a shared-weights tower has two tapes: two steppers alive at once, advanced alternately, must each launch
-    exactly the weight-gradient / LayerNorm-reduction groups they launch when the two backwards run one after the other - the same number of
-    jobs per launch and the same token-row counts (6 x 24 rows on one tape, 4 x 12 on the other)."""
+def test_two_backwards_on_one_tower_keep_their_own_queues(stubbed, monkeypatch, ln_defer):
+    """A shared-weights tower has two tapes: their backwards, run one after the other with ``accumulate=True``, each launch their own
+    weight-gradient / LayerNorm-reduction groups - one weight-gradient launch per tape, and no launch mixes the token-row counts of the two
+    tapes (6 x 24 rows on one, 4 x 12 on the other): the queues are locals of one backward_from_cls call."""
     monkeypatch.setenv("CLDRD_AMP", "fp16")
     enc = HipEncoder(cfg_of("distilbert", 3), seed=1)
     enc.ln_defer = ln_defer
     shapes = ((6, 24), (4, 12))
-
-    def groups(alternate):
-        tapes = [enc.encode(torch.randint(3, 500, s), torch.ones(s, dtype=torch.long), train=True, save=True, seed=11)[1] for s in shapes]
-        n0 = len(stubbed.args)
-        steppers = [enc.backward_steps(t, torch.zeros(t.M, 128), accumulate=True) for t in tapes]
-        if alternate:
-            while not all([st.step(1) for st in steppers]):
-                pass
-        else:
-            for st in steppers:
-                st.finish()
-        rows = {"cldrd_wgrad_group": 4, "cldrd_ln_reduce_group": 1}       # position of the per-job row counts (int array) in the C signature
-        count = {"cldrd_wgrad_group": 9, "cldrd_ln_reduce_group": 5}      # ... and of the job count
-        return sorted((n, a[count[n]], list(a[rows[n]])) for n, a in stubbed.args[n0:] if n in rows)
-
-    want = groups(alternate=False)
+    tapes = [enc.encode(torch.randint(3, 500, s), torch.ones(s, dtype=torch.long), train=True, save=True, seed=11)[1] for s in shapes]
+    n0 = len(stubbed.args)
+    for t in tapes:
+        enc.backward_from_cls(t, torch.zeros(t.M, 128), accumulate=True)
+    rows = {"cldrd_wgrad_group": 4, "cldrd_ln_reduce_group": 1}       # position of the per-job row counts (int array) in the C signature
+    count = {"cldrd_wgrad_group": 9, "cldrd_ln_reduce_group": 5}      # ... and of the job count
+    want = sorted((n, a[count[n]], list(a[rows[n]])) for n, a in stubbed.args[n0:] if n in rows)
     assert [g[0] for g in want].count("cldrd_wgrad_group") == 2 and all(len(set(g[2])) <= 2 for g in want)       # (T and M rows of ONE tape each)
-    assert groups(alternate=True) == want
+
+
+@pytest.mark.parametrize("kind", ["device_seed", "own_scale"])
+def test_a_failing_launch_in_the_backward_restores_the_launch_contexts(stubbed, monkeypatch, kind):
+    """backward_from_cls runs under up to two thread-local launch contexts - the device seed word of a ``device_seed`` tape, and the tower's own
+    loss scale for an fp16 tape outside a trainer.  A launch that raises in the middle of the pass must leave ``ops._TLS.seed_base`` /
+    ``ops._TLS.loss_scale`` at what they were before the call."""
+    monkeypatch.setenv("CLDRD_AMP", "fp16" if kind == "own_scale" else "bf16")
+    enc = HipEncoder(cfg_of("distilbert", 3), seed=1)
+    word = torch.zeros(2, dtype=torch.int64)                # stands in for the trainer's device seed word
+    enc.seed_base_ptr = word.data_ptr()
+    ids, mask = _trace_batch()
+    cls, tape = enc.encode(ids, mask, train=True, save=True, device_seed=kind == "device_seed")
+    assert tape.device_seed == (kind == "device_seed") and (tape.layers[-1]["h"].dtype == torch.float16) == (kind == "own_scale")
+    inside = []
+
+    def failing(name, *a):
+        if name == "cldrd_attention_bwd":                   # layer 1's attention backward: the last layer is behind it, two layers ahead
+            inside.append((getattr(ops._TLS, "seed_base", None), getattr(ops._TLS, "loss_scale", None)))
+            raise RuntimeError("launch failed")
+    monkeypatch.setattr(ops, "call", failing)
+    before = (getattr(ops._TLS, "seed_base", None), getattr(ops._TLS, "loss_scale", None))
+    with pytest.raises(RuntimeError, match="launch failed"):
+        enc.backward_from_cls(tape, torch.zeros(len(_LENS), 128))
+    seed_in, scale_in = inside[0]                           # the context under test really was entered when the launch failed
+    assert (seed_in == word.data_ptr()) if kind == "device_seed" else (scale_in is not None and scale_in[0] == enc._own_scale.data_ptr())
+    assert (getattr(ops._TLS, "seed_base", None), getattr(ops._TLS, "loss_scale", None)) == before
 
 
 class _FakeEvent:
@@ -426,7 +407,7 @@ def _long_case(lens):
     return run
 
 
-def _trainer_case(windows):
+def _trainer_case():
     """one NwayTrainer.train_step on fake streams (the optimizer launches included)"""
     def run(calls, monkeypatch):
         from cldrd_amd.trainer import nway_listwise as TL
@@ -443,9 +424,8 @@ def _trainer_case(windows):
         model = NwayDualEncoder(cfg_of("distilbert", 3), share_weights=False)
         tr = TL.NwayTrainer(model, loss="kl_div")
         tr.q_stream, tr.l_stream = _FakeStream(), _FakeStream()
-        tr.window_schedule = windows
-        batch = syn.nway_batch(5, 2, 3, 6, 20, vocab=512, ragged=not windows, label_kind="teacher")
-        tr.train_step(batch if windows else TL.batch_to_device(batch, torch.device("cpu")))      # (the ragged batch with host lengths)
+        batch = syn.nway_batch(5, 2, 3, 6, 20, vocab=512, ragged=True, label_kind="teacher")
+        tr.train_step(TL.batch_to_device(batch, torch.device("cpu")))      # (the ragged batch with host lengths)
         return model, tr
     return run
 
@@ -473,8 +453,7 @@ def _trace_cases():
         cases[f"fp32-{form}-distilbert3"] = _fp32_case("distilbert", 3, form)
     for lens, want in (([200, 3, 10, 130, 5, 128], 2), ([100, 3, 10, 128, 5, 64], 1), ([200, 150, 129, 130, 131, 199], 0)):
         cases[f"long-listed{want}"] = _long_case(lens)
-    cases["trainer-free_running"] = _trainer_case(False)
-    cases["trainer-windows"] = _trainer_case(True)
+    cases["trainer-free_running"] = _trainer_case()
     return cases
 
 

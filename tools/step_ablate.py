@@ -2,8 +2,7 @@
 """What parts of the training step cost on the critical path: the cfg2 step (graph replay) with parts SKIPPED (timing only, wrong
 results): the query tower's forward / backward (side stream), the AdamW + norm tail.  One process, interleaved rounds.
 
-Modes: full (the default step: the query tower runs free on the second stream) | win<a><l> (round-6 experiment: the query tower in slices of
-a / l groups released at the passage tower's attention / LayerNorm launches, e.g. win32, win21, win43, win77) | no_q_bwd | no_q | no_opt
+Modes: full (the default step: the query tower runs free on the second stream) | no_q_bwd | no_q | no_opt
 (parts skipped) | opt_side (AdamW moved to the head of the next step on
 the second stream: timing only)."""
 import os, sys, time
@@ -27,9 +26,6 @@ def build(mode):
         # the second (query tower) stream at another HIP stream priority: qprio-1 high, qprio1 low (round 3 tried high: no change)
         tr.q_stream = torch.cuda.Stream(device=dev, priority=int(mode[5:]))
         tr.flat_g.record_stream(tr.q_stream)
-    if mode.startswith("win") and len(mode) == 5:
-        tr.window_schedule = True
-        tr.FWD_SLICE = tr.BWD_SLICE = {"attn": int(mode[3]), "ln": int(mode[4])}
     if mode in ("no_q", "no_q_bwd"):
         real_enc, real_bwd = qe.encode, qe.backward_from_cls
         cache = {}
