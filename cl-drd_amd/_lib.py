@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # change of ABI_VERSION uses two checkouts).  The library itself reads no environment variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
 
-ABI_VERSION = 105          # cldrd_version() of the build SIGNATURES describes
+ABI_VERSION = 106         # cldrd_version() of the build SIGNATURES describes
 
 _lib = None
 
@@ -93,6 +93,7 @@ SIGNATURES = {
     "cldrd_write_step_state": (ci, [vp, cull, cull, vp, cf, cf, cf, ci, vp, vp]),
     "cldrd_build_pairs": (ci, [vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
     "cldrd_cls_head_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "cldrd_curriculum_select": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cull, vp, vp, vp, vp, vp]),
     "cldrd_write_run_file": (C.c_longlong, [C.c_char_p, vp, vp, vp, C.c_longlong, ci, ci]),
     "cldrd_py_float_repr": (ci, [C.c_double, C.c_char_p]),
     "cldrd_merge_topk": (ci, [vp, vp, ci, C.c_longlong, ci, ci, vp, vp, ci]),

@@ -24,7 +24,7 @@ extern "C" int cldrd_set_tuning(const char* key, int value) {
     if (!strcmp(key, "gemm_nt64")) { g_cldrd_tune_nt64 = value != 0; return 0; }
     return cldrd_set_error("set_tuning: unknown key");
 }
-extern "C" int cldrd_version(void) { return 105; }
+extern "C" int cldrd_version(void) { return 106; }
 extern "C" int cldrd_device_ok(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return 0;

@@ -37,6 +37,10 @@ built from the whole run, and shards can be built apart and concatenated.
 Host work at training-set scale (503 k queries x top-200, ~100 M pairs): numpy arrays throughout - the run is parsed by ``np.loadtxt``,
 grouped and ordered by sorts over the whole array, every window is gathered as one ``[queries, window]`` matrix; only the JSON lines are
 formatted per query.  ``tools/time_curriculum_file.py`` times the three phases (profiles/curriculum_file_timing.txt).
+
+:func:`select_examples_device` is the same selection on the search's ids and the teacher's scores while they are still ``[queries, K]``
+arrays in HBM (one kernel launch, ``cldrd_curriculum_select``; same examples, bit for bit): what ``retriever.build_stage_file`` uses instead
+of a run file (profiles/stage_file_timing.txt).
 """
 from __future__ import annotations
 
@@ -213,6 +217,80 @@ def select_examples(run: TeacherRun, spec: CurriculumSpec, seed: int = 0, with_s
     if bad.any():
         raise ValueError(f"qid {int(q_ids[np.argmax(bad)])}: the run has a non-finite teacher score for a selected passage")
     return CurriculumExamples(q_ids, relT, most, semi, int(n_q - first.shape[0]), relT_s, most_s, semi_s)
+
+
+DEVICE_MAX_K = 1024                     # candidates per query the selection kernel holds in LDS (cldrd_curriculum_select)
+
+
+def select_examples_device(qid, pid, score, count, spec: CurriculumSpec, seed: int = 0, with_scores: bool = False):
+    """:func:`select_examples` on what the GPU already holds: ``qid`` int64 [nq], ``pid`` int64 [nq, K] (candidates in run order), ``score``
+    fp32 [nq, K] (the teacher's) and ``count`` int32 [nq] (live candidates per row; entries behind them are never read), all device tensors.
+
+    Returns ``(examples, order)``.  ``examples`` is what :func:`select_examples` returns for the equivalent :class:`TeacherRun` - row q
+    contributes the lines ``qid[q]  pid[q, j]  j + 1  float64(score[q, j])`` for j < count[q], rows in order: queries in row order, int64 /
+    float64 arrays, scores the float64 of the fp32 values, ``n_skipped`` the rows with at least one and fewer than
+    ``spec.min_candidates`` candidates (a row without a candidate has no line in that run and is not counted there either).
+    ``order`` (device int32 [nq, K]): ``order[q, r]`` = run position of the candidate at teacher rank r, -1 at r >= count[q] - the host
+    lexsort of that run, row by row.
+
+    One kernel launch (``cldrd_curriculum_select``: one workgroup per query) and one device-to-host copy of the kept rows.  ``K > 1024``
+    does not fit the kernel: the run is built from the arrays and goes through :func:`select_examples` (slow, no limit).
+
+    The rows must have distinct qids and each row's live pids must be distinct (:func:`select_examples` raises on a repeated pair; this
+    function does not look).  ``ValueError`` naming the first such qid when a live score is not finite."""
+    import torch
+    from .. import hip_ops as ops
+    for t, name in ((qid, "qid"), (pid, "pid"), (score, "score"), (count, "count")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"select_examples_device: {name} must be a tensor on the GPU (select_examples is the host path)")
+    if pid.dim() != 2 or score.shape != pid.shape or qid.shape != pid.shape[:1] or count.shape != pid.shape[:1]:
+        raise ValueError("select_examples_device: qid [nq], pid [nq, K], score [nq, K], count [nq]")
+    nq, K = pid.shape
+    e, f = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64)
+    widths = (spec.n_rel, spec.n_most_hard, spec.n_semi_hard)
+    if nq == 0 or K == 0:
+        sc = tuple(f.reshape(0, w) for w in widths) if with_scores else ()
+        return (CurriculumExamples(e, *(e.reshape(0, w) for w in widths), 0, *sc),
+                torch.full((nq, K), -1, dtype=torch.int32, device=pid.device))
+    live = torch.arange(K, device=pid.device)[None, :] < count[:, None]
+    bad = ((~torch.isfinite(score)) & live).any(dim=1)
+    if bool(bad.any().item()):
+        raise ValueError(f"qid {int(qid[torch.nonzero(bad)[0, 0]].item())}: a non-finite teacher score among the query's candidates")
+    if K > DEVICE_MAX_K:
+        return _select_examples_arrays(qid, pid, score, count, live, spec, seed, with_scores)
+    order, keep, sel_pid, sel_score = ops.curriculum_select(qid, pid, score, count, spec.n_rel, spec.n_most_hard, spec.most_hard_ranks,
+                                                            spec.n_semi_hard, spec.semi_hard_ranks, seed)
+    rows = torch.nonzero(keep).reshape(-1)
+    q_ids = qid.index_select(0, rows).cpu().numpy()
+    pids = sel_pid.index_select(0, rows).cpu().numpy()
+    n_skipped = int(((count > 0) & (keep == 0)).sum().item())
+    cut = np.cumsum(widths)[:2]
+    relT, most, semi = (np.ascontiguousarray(a) for a in np.split(pids, cut, axis=1))
+    if not with_scores:
+        return CurriculumExamples(q_ids, relT, most, semi, n_skipped), order
+    scores = sel_score.index_select(0, rows).cpu().numpy().astype(np.float64)
+    relT_s, most_s, semi_s = (np.ascontiguousarray(a) for a in np.split(scores, cut, axis=1))
+    return CurriculumExamples(q_ids, relT, most, semi, n_skipped, relT_s, most_s, semi_s), order
+
+
+def _select_examples_arrays(qid, pid, score, count, live, spec, seed, with_scores):
+    """The ``K > DEVICE_MAX_K`` path of :func:`select_examples_device`: the equivalent :class:`TeacherRun` on the host."""
+    import torch
+    nq, K = pid.shape
+    live_h = live.cpu().numpy()
+    counts = live_h.sum(axis=1)
+    at_q, at_j = np.nonzero(live_h)                                                # row-major: rows in order, run order inside
+    run = TeacherRun(np.repeat(qid.cpu().numpy(), counts), pid.cpu().numpy()[at_q, at_j], at_j.astype(np.int64) + 1,
+                     score.cpu().numpy()[at_q, at_j].astype(np.float64))
+    if np.unique(run.qid).shape[0] != int((counts > 0).sum()):
+        raise ValueError("select_examples_device: the rows must have distinct qids")
+    ex = select_examples(run, spec, seed, with_scores=with_scores)
+    starts = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum(counts, out=starts[1:])
+    line = np.lexsort((run.rank, -run.score, at_q))                                # the teacher order select_examples used
+    order = np.full((nq, K), -1, dtype=np.int32)
+    order[at_q, at_j] = (line - starts[at_q]).astype(np.int32)                     # lines of a row stay inside the row's span
+    return ex, torch.from_numpy(order).to(pid.device)
 
 
 def write_examples(path, ex: CurriculumExamples, chunk: int = 65536, with_scores: bool = False) -> int:

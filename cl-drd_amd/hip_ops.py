@@ -1142,6 +1142,43 @@ def map_ids(I32, ids_table, id_offset):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- curriculum selection
+
+def curriculum_select(qid, pid, score, count, n_rel, n_most_hard, most_hard_ranks, n_semi_hard, semi_hard_ranks, seed=0, sel_pid=None,
+                      sel_score=None):
+    """cldrd_curriculum_select (include/cldrd_hip.h): qid int64 [nq], pid int64 [nq, K], score fp32 [nq, K], count int32 [nq] in HBM; the
+    windows are (lo, hi) pairs of 1-based inclusive teacher ranks -> (order int32 [nq, K], keep int32 [nq], sel_pid int64, sel_score fp32
+    [nq, n_rel + n_most_hard + n_semi_hard]) in HBM.  ``sel_pid`` / ``sel_score``: buffers to write into (rows with keep == 0 stay as they
+    are); fresh zeroed ones when not given."""
+    _chk(qid, torch.int64, "qid", 1), _chk(pid, torch.int64, "pid", 2), _chk(score, F32, "score", 2), _chk(count, torch.int32, "count", 1)
+    nq, K = pid.shape
+    if score.shape != pid.shape or qid.shape[0] != nq or count.shape[0] != nq:
+        raise ValueError("curriculum_select: qid [nq], pid [nq, K], score [nq, K], count [nq]")
+    n_sel = int(n_rel) + int(n_most_hard) + int(n_semi_hard)
+    if sel_pid is None:
+        sel_pid = torch.zeros(nq, n_sel, dtype=torch.int64, device=pid.device)
+    if sel_score is None:
+        sel_score = torch.zeros(nq, n_sel, dtype=F32, device=pid.device)
+    _chk(sel_pid, torch.int64, "sel_pid", 2), _chk(sel_score, F32, "sel_score", 2)
+    if tuple(sel_pid.shape) != (nq, n_sel) or tuple(sel_score.shape) != (nq, n_sel):
+        raise ValueError(f"curriculum_select: sel_pid / sel_score must be [{nq}, {n_sel}]")
+    for t, name in ((qid, "qid"), (pid, "pid"), (score, "score"), (count, "count"), (sel_pid, "sel_pid"), (sel_score, "sel_score")):
+        if not t.is_contiguous():
+            raise ValueError(f"curriculum_select: {name} must be contiguous")
+        if t.device != pid.device:
+            raise ValueError(f"curriculum_select: {name} is on {t.device}, pid on {pid.device}")
+    order = torch.empty(nq, K, dtype=torch.int32, device=pid.device)
+    keep = torch.empty(nq, dtype=torch.int32, device=pid.device)
+    if nq == 0:
+        return order, keep, sel_pid, sel_score
+    (most_lo, most_hi), (semi_lo, semi_hi) = most_hard_ranks, semi_hard_ranks
+    with torch.cuda.device(pid.device):
+        call("cldrd_curriculum_select", _p(qid), _p(pid), _p(score), _p(count), nq, K, int(n_rel), int(n_most_hard), int(most_lo),
+             int(most_hi), int(n_semi_hard), int(semi_lo), int(semi_hi), int(seed) & ((1 << 64) - 1), _p(order), _p(keep), _p(sel_pid),
+             _p(sel_score), _stream())
+    return order, keep, sel_pid, sel_score
+
+
 # ---------------------------------------------------------------------------------------------------- merge of shard lists
 
 def merge_topk_host(shard_D, shard_I, k, nthreads=0):

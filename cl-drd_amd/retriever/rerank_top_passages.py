@@ -108,6 +108,21 @@ def length_batches(lengths, batch_size):
     return [order[i:i + batch_size] for i in range(0, order.shape[0], batch_size)]
 
 
+def score_pairs(model, q_cache, p_cache, q_rows, p_rows, max_len, batch_size, fp32=False):
+    """Teacher scores of the pairs (query cache row ``q_rows[i]``, passage cache row ``p_rows[i]``; host int64 arrays) as ONE fp32 device
+    tensor [n]: scored in batches of similar pair length (:func:`length_batches`), each batch's scores scattered to the pairs' positions on
+    the device - nothing comes to the host per batch.  The batching of this program and of ``retriever.build_stage_file``."""
+    q_rows, p_rows = np.asarray(q_rows, dtype=np.int64).reshape(-1), np.asarray(p_rows, dtype=np.int64).reshape(-1)
+    _, _, lengths, _ = pair_lengths(np.asarray(q_cache.lens)[q_rows] - 2, np.asarray(p_cache.lens)[p_rows] - 2, max_len)
+    scores = None
+    for b in length_batches(lengths, batch_size):
+        s = model.score_cached(q_cache, p_cache, q_rows[b], p_rows[b], max_len, **({"fp32": True} if fp32 else {}))
+        if scores is None:
+            scores = torch.empty(q_rows.shape[0], dtype=torch.float32, device=s.device)
+        scores.index_copy_(0, torch.from_numpy(b).to(s.device), s)
+    return scores if scores is not None else torch.empty(0, dtype=torch.float32, device=next(model.parameters()).device)
+
+
 def main_dual_encoder(args):
     """``--dual_encoder``: the run re-scored by the student through an evaluation.DevPool (every distinct query and passage encoded once,
     score = the flat search's exact re-score of the two CLS embeddings); output format and ordering rules as the teacher mode's."""
@@ -158,11 +173,8 @@ def main(args):
             p_rows = np.array([p_row[int(p)] for p in up], dtype=np.int64)[p_inv.reshape(-1)]
         except KeyError as exc:
             raise KeyError(f"id {exc.args[0]} of {args.run_path} is not in the query / passage table") from exc
-        _, _, lengths, _ = pair_lengths(np.asarray(q_cache.lens)[q_rows] - 2, np.asarray(p_cache.lens)[p_rows] - 2, args.max_len)
-        scores = np.empty(q_rows.shape[0], dtype=np.float32)
-        for b in length_batches(lengths, args.batch_size):
-            scores[b] = model.score_cached(q_cache, p_cache, q_rows[b], p_rows[b], args.max_len,
-                                            **({"fp32": True} if getattr(args, "fp32_encode", False) else {})).cpu().numpy()
+        scores = score_pairs(model, q_cache, p_cache, q_rows, p_rows, args.max_len, args.batch_size,
+                             fp32=bool(getattr(args, "fp32_encode", False))).cpu().numpy()
     total = write_ranked_run(args.output_path, qids, pids, group, starts, scores)
     print(f"re-scored {total} pairs of {starts.shape[0] - 1} queries")
     return total
@@ -175,10 +187,12 @@ def rank_order(group, scores):
     return np.lexsort((np.arange(scores.shape[0]), -scores.astype(np.float64), group))
 
 
-def write_ranked_run(path, qids, pids, group, starts, scores):
+def write_ranked_run(path, qids, pids, group, starts, scores, order=None):
     """``qid\\tpid\\trank\\tscore`` of the pairs of :func:`read_run` ranked by :func:`rank_order`: the native writer when every query has the
-    same number of candidates (the usual top-k run), the writer's Python loop for a ragged run."""
-    order = rank_order(group, scores)
+    same number of candidates (the usual top-k run), the writer's Python loop for a ragged run.  ``order``: the pairs' positions in output
+    order when the caller already has them (``build_stage_file``: from the selection kernel) - what :func:`rank_order` would return."""
+    if order is None:
+        order = rank_order(group, scores)
     pids, scores = pids[order], np.ascontiguousarray(np.asarray(scores)[order], dtype=np.float32)
     q_out = qids[starts[:-1]]
     counts = np.diff(starts)

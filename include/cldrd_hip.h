@@ -412,6 +412,25 @@ int cldrd_build_pairs(const void* q_tok, const int* q_lens, int q_stride, int q_
 int cldrd_cls_head_fwd(const float* cls, const float* w1, const float* b1, const float* w2, const float* b2, float* out, int M, int d,
                        int num_labels, int act, void* stream);
 
+/* ---- curriculum selection (csrc/curriculum.hip; the device form of dataset/curriculum_file.py select_examples) ---------------------
+ * From the search's ids and the teacher's scores as they lie in HBM to a curriculum stage's training examples, one workgroup per query.
+ * In (device): qid int64 [nq]; pid int64 [nq, K], candidates in run order; score fp32 [nq, K]; count int32 [nq], the live candidates of
+ * the row (clamped to 0 .. K; entries at positions >= count are never read).  The spec as dataset.curriculum_file.CurriculumSpec: n_rel,
+ * and per window the number drawn and its 1-based inclusive teacher ranks lo .. hi (a window that draws nothing is ignored; one that
+ * draws must start after n_rel and hold at least as many ranks as it draws, and the two must not overlap: refused otherwise).
+ * Out (device):
+ *   order int32 [nq, K]   order[q, r] = run position of the candidate at teacher rank r: score descending, ties by run position
+ *                         ascending (-0.0 == 0.0); -1 at r >= count
+ *   keep int32 [nq]       1 where count >= min_candidates = max(n_rel, hi of every window that draws), else 0
+ *   sel_pid int64, sel_score fp32 [nq, n_rel + n_most_hard + n_semi_hard]: the top n_rel in teacher order, then from each window the
+ *                         n candidates with the smallest key splitmix64(splitmix64(splitmix64(seed) ^ qid) ^ pid) (uint64 wrap-around,
+ *                         ids as two's complement, ties by pid), written in teacher order.  Rows with keep == 0 are left untouched.
+ * K <= 1024 (refused above).  Preconditions: the live scores are finite and the live pids of a row are distinct; a row that breaks
+ * them gets an unspecified (never out-of-bounds) result. */
+int cldrd_curriculum_select(const long long* qid, const long long* pid, const float* score, const int* count, int nq, int K,
+                            int n_rel, int n_most_hard, int most_lo, int most_hi, int n_semi_hard, int semi_lo, int semi_hi,
+                            unsigned long long seed, int* order, int* keep, long long* sel_pid, float* sel_score, void* stream);
+
 /* ---- run file (retriever/retrieve_top_passages.py:98-105), HOST side: no GPU work -----------------------------------------
  * Writes `qid\tdocid\trank\tscore\n` for nq queries x k hits (rank 1..k) to `path`; the score text is Python's repr of the fp32
  * value widened to a double, which is what the reference's f-string prints.  All pointers are HOST pointers.  Formatted by nthreads
