@@ -30,9 +30,11 @@ The faiss sharding code of the reference (:164-182) is dead (undefined ``gpu_res
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 import pickle
+import warnings
 from timeit import default_timer as timer
 
 import numpy as np
@@ -52,6 +54,7 @@ HOST_CHUNK_ROWS = 16384      # fp16-row file written from a host index: rows con
 FORMAT_F32 = "cldrd-flatip-v1"
 FORMAT_F16 = "cldrd-flatip-f16-v1"
 PROGRESS_HOOK = None         # tools: callable(timings dict) every 500 batches of get_embeddings_from_scratch
+_MERGE_DEVICE, _MERGE_HOST = "device (cldrd_merge_topk_device)", "host (cldrd_merge_topk)"       # last_merge["path"] of a sharded search
 
 
 def cap_host_threads(limit: int = 8):
@@ -193,6 +196,90 @@ def _embeddings_from_scratch(model, dataloader, is_query):
     return embeddings, embeddings_ids
 
 
+@dataclasses.dataclass
+class _Resident:
+    """What an attached shard keeps in HBM and what the search needs to know about it.  Built completely by ``FlatIPIndex._attach`` and
+    never changed afterwards, except for the lazily filled members at the end."""
+    device: torch.device
+    p16: torch.Tensor            # fp16 [n, d] = fp16(p - mu): what the scan reads; in fp16-row mode also the stored rows
+    p32: object                  # fp32 [n, d], the rows the re-score reads; None = fp16-row mode
+    mu: torch.Tensor             # fp32 [d]: mean row of the shard
+    sample: torch.Tensor         # bf16 [s_rows rounded up to 8, d]: every s_stride-th centred row (threshold estimate)
+    s_stride: int
+    s_rows: int
+    cnorm: float                 # max |p - mu|
+    raw_max: float               # max |p|
+    max_norm: float              # the norm the eps bound multiplies (FlatIPIndex._attach)
+    query_tile: int              # queries per pass over the index bytes
+    ids_dev: object = None       # int64 [n]: the id table, uploaded by the first search that maps ids
+    mu_host: object = None       # np.float32 [d]: the host copy of mu, made when first asked for
+    ws: dict = dataclasses.field(default_factory=dict)       # cap2 -> per-batch scratch of the search
+
+
+def _host_tensor(a: np.ndarray) -> torch.Tensor:
+    """torch view of a host array that is only the source of an upload and never written through (a memory-mapped index file is read-only)"""
+    with warnings.catch_warnings():
+        warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+        return torch.from_numpy(a)
+
+
+def _sel(t, sel):
+    """the entries ``sel`` (a slice or an index tensor) of a per-query tensor that may be None"""
+    return None if t is None else (t[sel] if isinstance(sel, slice) else t.index_select(0, sel))
+
+
+def _all_missing(nq: int, k: int):
+    return np.full((nq, k), -np.inf, dtype=np.float32), np.full((nq, k), -1, dtype=np.int64)
+
+
+def _check_queries(queries, d: int, k):
+    """-> (fp32 contiguous queries [nq, d], int k, the (empty) result of an empty query set or None)"""
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    if q.ndim != 2 or q.shape[1] != d:
+        raise ValueError("queries must be [nq, d]")
+    k = int(k)
+    if k <= 0:
+        raise ValueError("k must be positive")
+    return q, k, (_all_missing(0, k) if q.shape[0] == 0 else None)
+
+
+def _cap2_after_probe(cap2: int, status: np.ndarray, kept: np.ndarray) -> int:
+    """Slots of the kept-set buffer for the passes after the probe pass, from the probe's status words and kept-set sizes: the smallest
+    power-of-two multiple of ``cap2`` with 25 % + 64 slots of headroom over the largest kept set (``CAND_CAP`` at most, and ``CAND_CAP``
+    when a probe query's kept set did not fit: status bit 16)."""
+    need = int(kept.max()) if ((status & 16) == 0).all() else CAND_CAP
+    cap2_rest = cap2
+    while cap2_rest < min(CAND_CAP, int(1.25 * need) + 64):
+        cap2_rest *= 2
+    return min(cap2_rest, CAND_CAP)
+
+
+def _retry_step(status: np.ndarray, thr: np.ndarray, eps: np.ndarray, khat: np.ndarray, attempt: int):
+    """What a failed proof does to the thresholds of the unproven queries: their status words (bits of cldrd_flatip_search: 1 too few
+    candidates, 2 candidate list overflowed, 4 the scan dropped hits, 8 threshold above t^ - 2 eps, 16 the kept set does not fit its
+    buffer), thresholds, eps and k-th scan scores (float64) and the attempt number (1, 2, ...) -> (new thresholds float64, scan with the
+    tiled kernels, use the full ``CAND_CAP`` kept-set buffer)."""
+    t = thr.copy()
+    has_k = np.isfinite(khat)
+    over = (status & 2) != 0
+    few = ((status & 1) != 0) & ~over
+    high = ((status & 8) != 0) & ~over & ~few
+    # proven bound: the list was complete and long enough, only the threshold sat above t^ - 2 eps
+    t[high] = khat[high] - 2.0 * eps[high] * (1.0 + 1e-3) - 1e-6 * np.abs(khat[high]) - 1e-30
+    # too few candidates: the estimate was too high; lower it, faster every attempt (but never by more than 8 eps + 20 % at once:
+    # a threshold far below t^ only fills the lists)
+    t[few] = t[few] - np.minimum(np.maximum(4.0 * eps[few], 0.05 * np.abs(t[few]) + 1e-3) * (2.0 ** (attempt - 1)),
+                                 8.0 * eps[few] * attempt + 0.2 * np.abs(t[few]) + 1e-3)
+    # overflow: the list holds an arbitrary `cap` of the c rows above thr; its k-th largest score is a (low) estimate of t^
+    up = np.where(has_k, khat - 2.0 * eps, -np.inf)
+    t[over] = np.maximum(t[over] + np.maximum(eps[over], 1e-3 * np.abs(t[over])) * (2.0 ** (attempt - 1)), up[over])
+    # status bit 4: the streaming scan dropped hits (its per-wave on-chip lists overflowed inside one tile: hit density above
+    # ~5 % of a tile, e.g. k = 1000 on an index of a few 10k rows).  Every query of such a pass carries the bit and the same
+    # kernel would drop the same hits again: the retry scans with the tiled kernels, which have no on-chip list.  Queries with
+    # ONLY that bit (or bit 16: a larger buffer, not another threshold) keep their threshold.
+    return t, bool(((status & 4) != 0).any()), bool(((status & 16) != 0).any())
+
+
 class FlatIPIndex:
     """Exact inner-product index over one shard of rows (faiss ``IndexIDMap(IndexFlatIP(d))`` semantics).
 
@@ -207,7 +294,12 @@ class FlatIPIndex:
     contract is unchanged.  This differs from faiss' ``useFloat16``, which stores plain ``fp16(p)``: the centred array is the one the scan
     reads anyway (one array serves scan and re-score), and its rounding error is relative to ``|p - mu|`` instead of ``|p|`` - on CLS-like
     embeddings the stored rows are closer to the fp32 ones.  ``mu`` is the fp32 value of the fp64 column mean; a host-written file and a
-    device-attached index of the same rows may differ in the last bit of ``mu`` and therefore of a few ``R16`` values."""
+    device-attached index of the same rows may differ in the last bit of ``mu`` and therefore of a few ``R16`` values.
+
+    State.  Host side: ``embeddings`` / ``ids`` / ``id_offset``, or - an index read from an fp16-row file - ``_file16`` (its rows, ``mu`` and
+    norms).  Device side: ONE :class:`_Resident` in ``_res``, None until an attach has succeeded: :meth:`_attach` assigns it as its last
+    statement, :meth:`add_with_ids` drops it.  ``device``, ``query_tile``, ``_p16``, ``_p32``, ``_sample`` and
+    ``_max_norm`` are read-only views of it (what bench.py, the tools and the tests read)."""
 
     def __init__(self, d: int):
         self.d = d
@@ -215,37 +307,44 @@ class FlatIPIndex:
         self.embeddings = None       # np.float32 [n, d] on the host until moved to a GPU
         self.ids = None              # np.int64 [n] or None (ids = row positions + id_offset)
         self.id_offset = 0
-        self.device = None
-        self._p32 = self._p16 = self._sample = None
-        self._mu = None               # device fp32 [d]: mean row of the attached shard
-        self._fp16_rows = False       # attached in fp16-row mode (no fp32 rows in HBM)
-        self._r16_host = None         # np.float16 [n, d] = fp16(p - mu): an index read from an fp16-row file (no fp32 rows anywhere)
-        self._mu_host = None          # np.float32 [d] of such an index
-        self._cnorm = self._raw_max = None      # max |p - mu|, max |p| of the attached shard / the file
+        self._file16 = None          # an index read from an fp16-row file (no fp32 rows anywhere): (np.float16 [n, d] = fp16(p - mu),
+                                     # np.float32 mu [d], max |p - mu|, max |p|) as the file holds them
+        self._res = None             # _Resident: the attached shard
         self.last_stats = {}
         self.profile = False          # bench.py: time the search with HIP events and count candidates
         self.probe = True             # first pass of a long search sizes the kept-set buffer of the rest (test hook: False)
         self.query_tile_request = None
 
+    device = property(lambda self: None if self._res is None else self._res.device, doc="the GPU the shard is attached to, or None")
+    query_tile = property(lambda self: self._res.query_tile, doc="queries per pass over the index bytes (attached index)")
+    _p16 = property(lambda self: None if self._res is None else self._res.p16, doc="the resident fp16 rows [n, d], or None")
+    _p32 = property(lambda self: None if self._res is None else self._res.p32, doc="the resident fp32 rows, or None (fp16-row mode)")
+    _sample = property(lambda self: None if self._res is None else self._res.sample, doc="the resident bf16 threshold sample, or None")
+    _max_norm = property(lambda self: self._res.max_norm, doc="the norm the eps bound multiplies (attached index)")
+
     @property
     def row_dtype(self) -> str:
         """``"float16"``: fp16-row mode (attached with ``fp16_rows=True`` or read from an fp16-row file); ``"float32"`` otherwise."""
-        return "float16" if (self._fp16_rows or self._r16_host is not None) else "float32"
+        return "float16" if (self._file16 is not None or (self._res is not None and self._res.p32 is None)) else "float32"
 
     @property
     def mu(self):
         """The shard's mean row the fp16 rows are centred on: np.float32 [d], read-only (None before the index has one)."""
-        if self._mu_host is None and self._mu is not None:
-            self._mu_host = self._mu.cpu().numpy()
-        if self._mu_host is None:
+        if self._res is not None:
+            if self._res.mu_host is None:
+                self._res.mu_host = self._res.mu.cpu().numpy()
+            mu = self._res.mu_host
+        elif self._file16 is not None:
+            mu = self._file16[1]
+        else:
             return None
-        out = self._mu_host.view()
+        out = mu.view()
         out.flags.writeable = False
         return out
 
     # -- construction -----------------------------------------------------------------------------------------
     def add_with_ids(self, embeddings, ids):
-        if self._r16_host is not None:
+        if self._file16 is not None:
             raise ValueError("an index read from an fp16-row file holds no fp32 rows: rows cannot be added to it")
         emb = np.ascontiguousarray(embeddings, dtype=np.float32)
         if emb.ndim != 2 or emb.shape[1] != self.d:
@@ -259,10 +358,7 @@ class FlatIPIndex:
             self.embeddings = np.concatenate([self.embeddings, emb])
             self.ids = None if self.ids is None or ids is None else np.concatenate([self.ids, ids])
         self.ntotal = self.embeddings.shape[0]
-        self._p32 = self._p16 = self._sample = self._ids_dev = None
-        self._mu = self._mu_host = None
-        self._fp16_rows = False
-        self._ws = None
+        self._res = None             # the attached shard is not these rows any more
 
     def add(self, embeddings):
         self.add_with_ids(embeddings, None)
@@ -272,13 +368,13 @@ class FlatIPIndex:
         """Index over fp32 rows that already live in HBM (e.g. an encode shard that never left the GPU).  ``fp16_rows``: centre + cast on the
         device and keep no reference to ``rows32`` (fp16-row mode, class docstring)."""
         idx = cls(rows32.shape[1])
-        idx.ntotal, idx.id_offset = rows32.shape[0], id_offset
+        n = idx.ntotal = rows32.shape[0]
+        idx.id_offset = id_offset
+        rows32 = rows32.contiguous()
         if fp16_rows:
-            rows32 = rows32.contiguous()
-            n = rows32.shape[0]
-            idx._attach16(rows32.device, n, lambda: ((lo, rows32[lo:min(n, lo + ATTACH_CHUNK_ROWS)]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
-            return idx
-        idx._attach(rows32.contiguous())
+            idx._attach(rows32.device, n, lambda: ((lo, rows32[lo:lo + ATTACH_CHUNK_ROWS]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
+        else:
+            idx._attach(rows32.device, n, lambda: ((0, rows32),), keep32=rows32)
         return idx
 
     def to_gpu(self, device, fp16_rows: bool = False):
@@ -288,29 +384,20 @@ class FlatIPIndex:
         device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("FlatIPIndex.search runs on the GPU only (no CPU path)")
-        if self._r16_host is not None:
-            with torch.cuda.device(device):
-                self._attach16_file(device)
-            return self
-        if fp16_rows:
+        if self._file16 is not None:
+            self._attach(device, self._file16[0].shape[0], None)
+        elif fp16_rows:
             if self.embeddings is None:
                 raise ValueError("FlatIPIndex.to_gpu: the index holds no rows")
-            with torch.cuda.device(device):
-                self._attach16(device, self.embeddings.shape[0], lambda: self._staged_chunks(device))
-            return self
-        with torch.cuda.device(device):
-            import warnings
-            with warnings.catch_warnings():
-                # a memory-mapped index file is read-only; the host tensor is only the source of this one upload and is never written through
-                warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
-                host = torch.from_numpy(np.ascontiguousarray(self.embeddings))
-            self._attach(host.to(device))
+            self._attach(device, self.embeddings.shape[0], lambda: self._staged_chunks(device))
+        else:
+            rows32 = _host_tensor(np.ascontiguousarray(self.embeddings)).to(device)        # the fp32 form uploads once
+            self._attach(device, rows32.shape[0], lambda: ((0, rows32),), keep32=rows32)
         return self
 
     def _staged_chunks(self, device):
         """(first row, fp32 device tensor) for every ``ATTACH_CHUNK_ROWS`` rows of the host array (a numpy array or a memory-mapped file), through
         two staging buffers: the H2D copy of chunk i + 1 (a side stream) runs under the kernels the consumer enqueued for chunk i."""
-        import warnings
         emb = self.embeddings
         n, d = emb.shape
         m_max = min(n, ATTACH_CHUNK_ROWS)
@@ -322,9 +409,7 @@ class FlatIPIndex:
             for i, lo in enumerate(range(0, n, ATTACH_CHUNK_ROWS)):
                 hi = min(n, lo + ATTACH_CHUNK_ROWS)
                 b = i % len(bufs)
-                with warnings.catch_warnings():
-                    warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
-                    host = torch.from_numpy(np.ascontiguousarray(emb[lo:hi], dtype=np.float32))
+                host = _host_tensor(np.ascontiguousarray(emb[lo:hi], dtype=np.float32))
                 with torch.cuda.stream(side):
                     if consumed[b] is not None:
                         side.wait_event(consumed[b])
@@ -339,132 +424,85 @@ class FlatIPIndex:
             cur.wait_stream(side)
             cur.synchronize()            # the staging buffers go back to the allocator only when nothing reads or writes them
 
-    def _plan_sample(self, n: int, d: int, device):
-        """the threshold sample of :meth:`_attach` (sizes explained there)"""
-        self._s_stride = max(1, n // min(max(SAMPLE_ROWS, n // 64), 1 << 18))
-        self._s_rows = min(n, (n + self._s_stride - 1) // self._s_stride)
-        # the GEMM wants a column count that is a multiple of 8: zero rows pad the sample (never read by the select)
-        self._sample = torch.zeros((self._s_rows + 7) // 8 * 8, d, dtype=torch.bfloat16, device=device)
+    def _attach(self, device, n: int, chunks, keep32=None):
+        """Every attach.  ``chunks()`` yields (first row, fp32 device tensor) over the shard in order and is walked twice (statistics, then
+        centre + cast); the fp32 form is the one-chunk case over the whole tensor, which ``keep32`` keeps resident for the re-score.
+        ``keep32=None``: fp16-row mode, no fp32 row stays in HBM.  ``chunks=None``: an index read from an fp16-row file - the fp16 rows go
+        to HBM as they are (chunked H2D straight into P16), the sample is gathered on the device, ``mu`` and the norms come from the file:
+        no statistics pass.
 
-    def _attach16(self, device, n: int, chunks):
-        """fp16-row attach.  ``chunks()`` yields (first row, fp32 device tensor) over the shard in order; it is walked twice:
-        pass 1 - max |p|^2 and the mean row of every chunk (cldrd_row_sqnorm_max, cldrd_index_col_mean), the chunk means combined on the host in
-        fp64 weighted by chunk size (mu depends neither on the device nor on timing; it need not equal the fp32 mode's mu bit for bit);
-        pass 2 - centre + cast every chunk into its slice of P16 and of the sample, max centred norm and range flag accumulated
-        (cldrd_index_center_cast with row0).  No fp32 row stays in HBM."""
-        d = self.d
+        The 16-bit rows are CENTRED on the shard's mean row mu.  <q, p - mu> = <q, p> - <q, mu> moves every score of a query by the same
+        constant, so the ranking - all the scan decides - is unchanged, while the rounding bound of the scan, eps ~ 2^-10 |q| max|p - mu|,
+        shrinks with the rows' common component.  Dual-encoder CLS embeddings are dominated by one (reference model: q . p = 17 +- 2 over a
+        corpus): on the CLS-like shard of the tests eps goes from 0.042 to 0.007 and the 2 eps band under the k-th score from ~1 250 rows to
+        ~200, i.e. the re-score gathers about half the rows and the scan emits half the hits; on an isotropic corpus mu ~ 0 and nothing
+        changes.  In fp32 mode the exact scores still come from the untouched fp32 rows (re-score)."""
+        d, file16 = self.d, self._file16 if chunks is None else None
         if d % 4:
             raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
-        if d > 2048:
-            raise ValueError(f"FlatIPIndex: fp16-row mode supports an embedding width of at most 2048 (the mean-row kernel's limit), got {d}")
-        if n <= 0:
-            raise ValueError("FlatIPIndex: no rows to attach")
-        self.device = device
-        self._ws = None
-        self._p32 = None
+        if keep32 is None and file16 is None:
+            if d > 2048:
+                raise ValueError(f"FlatIPIndex: fp16-row mode supports an embedding width of at most 2048 (the mean-row kernel's limit), got {d}")
+            if n <= 0:
+                raise ValueError("FlatIPIndex: no rows to attach")
+        i32 = dict(dtype=torch.int32, device=device)
         with torch.cuda.device(device):
-            raw = torch.zeros(1, dtype=torch.int32, device=device)
-            means, sizes = [], []
-            for lo, c in chunks():
-                ops.row_sqnorm_max_into(c, raw)
-                means.append(ops.index_col_mean(c))
-                sizes.append(c.shape[0])
-            del c                        # the last view of a staging buffer: pass 2 allocates its own
-            raw_max = math.sqrt(float(raw.view(torch.float32).item()))
-            if math.isfinite(raw_max):
-                w = np.asarray(sizes, dtype=np.float64)[:, None]
-                mu_h = ((torch.stack(means).cpu().numpy().astype(np.float64) * w).sum(axis=0) / float(n)).astype(np.float32)
+            # statistics: max |p|^2 and the mean row of every chunk (cldrd_row_sqnorm_max, cldrd_index_col_mean: fp64 column sums)
+            mu_h = None
+            if file16 is not None:
+                mu_h, cnorm, raw_max = file16[1], file16[2], file16[3]
+                mu = torch.from_numpy(np.ascontiguousarray(mu_h, dtype=np.float32)).to(device)
             else:
-                mu_h = np.zeros(d, dtype=np.float32)
-            del means
-            mu = torch.from_numpy(mu_h).to(device)
-            flag = torch.zeros(1, dtype=torch.int32, device=device)
-            cmax = torch.zeros(1, dtype=torch.int32, device=device)
-            self._p16 = torch.empty(n, d, dtype=torch.float16, device=device)
-            self._plan_sample(n, d, device)
-            for lo, c in chunks():
-                ops.index_center_cast(c, mu, self._p16[lo:lo + c.shape[0]], self._sample, self._s_stride, self._s_rows, flag, row0=lo, cmax=cmax)
-            del c
-            self._mu, self._mu_host = mu, mu_h
-            self._cnorm, self._raw_max = math.sqrt(float(cmax.view(torch.float32).item())), raw_max
-            self._finish_attach16(int(flag.item()))
-
-    def _attach16_file(self, device):
-        """An index read from an fp16-row file: the fp16 rows go to HBM as they are (chunked H2D straight into P16), the sample is gathered on
-        the device, the norms come from the file - no statistics pass."""
-        import warnings
-        r16 = self._r16_host
-        n, d = r16.shape
-        if d % 4:
-            raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
-        self.device = device
-        self._ws = None
-        self._p32 = None
-        with torch.cuda.device(device):
-            self._p16 = torch.empty(n, d, dtype=torch.float16, device=device)
-            for lo in range(0, n, ATTACH_CHUNK_ROWS):
-                hi = min(n, lo + ATTACH_CHUNK_ROWS)
-                with warnings.catch_warnings():
-                    warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
-                    self._p16[lo:hi].copy_(torch.from_numpy(np.ascontiguousarray(r16[lo:hi])))
-            self._plan_sample(n, d, device)
-            ops.gather_cast_rows(self._p16, self._sample, self._s_rows, self._s_stride)
-            self._mu = torch.from_numpy(np.ascontiguousarray(self._mu_host, dtype=np.float32)).to(device)
-            self._finish_attach16(0)
-
-    def _finish_attach16(self, flag: int):
-        self._fp16_rows = True
-        try:
-            # the scan's operand now IS the stored row, so the 2^-12 max|p| term of the bound is slack here; the bound is kept as it is
-            # (cldrd_topk_thresholds unchanged)
-            self._finish_attach(flag)
-        except ValueError:
-            self._p16 = self._sample = None
-            raise
-
-    def _finish_attach(self, flag: int):
-        """the end of every attach, from ``_cnorm`` / ``_raw_max`` and the range flag of the centre + cast pass"""
+                raw = torch.zeros(1, **i32)
+                means, sizes = [], []
+                for lo, c in chunks():
+                    ops.row_sqnorm_max_into(c, raw)
+                    means.append(ops.index_col_mean(c))
+                    sizes.append(c.shape[0])
+                del c                        # the last view of a staging buffer: the second walk allocates its own
+                raw_max = math.sqrt(float(raw.view(torch.float32).item()))
+                if not math.isfinite(raw_max):
+                    mu = torch.zeros(d, dtype=torch.float32, device=device)
+                elif keep32 is not None:
+                    mu = means[0]            # one chunk: the device's mean row as it is
+                else:
+                    # the chunk means combined on the host in fp64 weighted by chunk size (mu depends neither on the device nor on timing;
+                    # it need not equal the fp32 mode's mu bit for bit)
+                    w = np.asarray(sizes, dtype=np.float64)[:, None]
+                    mu_h = ((torch.stack(means).cpu().numpy().astype(np.float64) * w).sum(axis=0) / float(n)).astype(np.float32)
+                    mu = torch.from_numpy(mu_h).to(device)
+                del means
+            # the threshold sample: SAMPLE_ROWS rows, or 1 / 64 of the rows on a larger index (the whole 8.84 M-row collection on one GPU:
+            # with 16 384 rows the expected number of sample rows inside the top 1000 is 1.9, the estimate is the 9th largest sample score
+            # and the candidate lists come out at ~6 300 +- 2 000 of their 8 192 slots: overflowing queries, one or two extra passes; with
+            # 138 k rows ~2 300).  The GEMM wants a column count that is a multiple of 8: zero rows pad the sample (never read by the select)
+            s_stride = max(1, n // min(max(SAMPLE_ROWS, n // 64), 1 << 18))
+            s_rows = min(n, (n + s_stride - 1) // s_stride)
+            sample = torch.zeros((s_rows + 7) // 8 * 8, d, dtype=torch.bfloat16, device=device)
+            p16 = torch.empty(n, d, dtype=torch.float16, device=device)
+            # centre + cast: fp16 rows + max centred norm + bf16 sample + range flag in ONE pass per chunk (cldrd_index_center_cast)
+            flag = 0
+            if file16 is not None:
+                for lo in range(0, n, ATTACH_CHUNK_ROWS):
+                    p16[lo:lo + ATTACH_CHUNK_ROWS].copy_(_host_tensor(np.ascontiguousarray(file16[0][lo:lo + ATTACH_CHUNK_ROWS])))
+                ops.gather_cast_rows(p16, sample, s_rows, s_stride)
+            else:
+                flag_d, cmax = torch.zeros(1, **i32), torch.zeros(1, **i32)
+                for lo, c in chunks():
+                    ops.index_center_cast(c, mu, p16[lo:lo + c.shape[0]], sample, s_stride, s_rows, flag_d, row0=lo, cmax=cmax)
+                del c
+                cnorm, flag = math.sqrt(float(cmax.view(torch.float32).item())), int(flag_d.item())
         # max |p - mu| for the bound, plus 2^-12 max|p|: the fp32 subtraction p - mu itself rounds (2^-24 |p| per element), which moves a
         # centred score by up to |q| sqrt(d) 2^-24 max|p| < 2^-10 |q| (2^-12 max|p|) - folded into the norm the eps formula multiplies by 2^-10
-        self._max_norm = self._cnorm * (1.0 + 1e-6) + self._raw_max * 2.0 ** -12
+        # (fp16-row mode: the scan's operand IS the stored row, so that term is slack there; the bound is kept as it is)
+        max_norm = cnorm * (1.0 + 1e-6) + raw_max * 2.0 ** -12
+        if flag or not math.isfinite(max_norm):
+            raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
         # queries per pass over the index bytes: 256 at d = 768 (the streaming scan's two-batch form), else the reference's 128
         # (`query_tile_request`: a test hook that asks for 128 at d = 768)
-        self.query_tile = 256 if (self.d == 768 and self.query_tile_request != 128) else 128
-        if flag or not math.isfinite(self._max_norm):
-            raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
-
-    def _attach(self, p32: torch.Tensor):
-        device = p32.device
-        self.device = device
-        self._ws = None
-        self._fp16_rows = False
-        self._mu_host = None
-        with torch.cuda.device(device):
-            self._p32 = p32
-            n, d = self._p32.shape
-            if d % 4:
-                raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
-            flag = torch.zeros(1, dtype=torch.int32, device=device)
-            self._p16 = torch.empty(n, d, dtype=torch.float16, device=device)
-            # Round 4: the 16-bit scan shadow holds the rows CENTRED on the shard's mean row mu.  <q, p - mu> = <q, p> - <q, mu> moves every score
-            # of a query by the same constant, so the ranking - all the scan decides - is unchanged, while the rounding bound of the scan,
-            # eps ~ 2^-10 |q| max|p - mu|, shrinks with the rows' common component.  Dual-encoder CLS embeddings are dominated by one (reference
-            # model: q . p = 17 +- 2 over a corpus): on the CLS-like shard of the tests eps goes from 0.042 to 0.007 and the 2 eps band under the
-            # k-th score from ~1 250 rows to ~200, i.e. the re-score gathers about half the rows and the scan emits half the hits; on an isotropic
-            # corpus mu ~ 0 and nothing changes.  Exact scores still come from the untouched fp32 rows (re-score), so D / I are what they were.
-            # sample size: SAMPLE_ROWS, or 1 / 64 of the rows on a larger index (the whole 8.84 M-row collection on one GPU: with 16 384 rows
-            # the expected number of sample rows inside the top 1000 is 1.9, the estimate is the 9th largest sample score and the candidate
-            # lists come out at ~6 300 +- 2 000 of their 8 192 slots: overflowing queries, one or two extra passes; with 138 k rows ~2 300)
-            self._plan_sample(n, d, device)
-            # three launches over the fp32 rows (cldrd_row_sqnorm_max, cldrd_index_col_mean, cldrd_index_center_cast: mean row in fp64, then
-            # centre + fp16 shadow + max centred norm + bf16 sample + range flag in ONE pass); until round 5 this was 17 chunks of
-            # at::native kernels per attach (mean, subtract, double-precision norms, casts, a strided gather)
-            raw_max = math.sqrt(ops.row_sqnorm_max(self._p32))
-            mu = ops.index_col_mean(self._p32) if math.isfinite(raw_max) else torch.zeros(d, dtype=torch.float32, device=device)
-            self._mu = mu
-            cmax = ops.index_center_cast(self._p32, mu, self._p16, self._sample, self._s_stride, self._s_rows, flag)
-            self._cnorm, self._raw_max = math.sqrt(float(cmax.view(torch.float32).item())), raw_max
-            self._finish_attach(int(flag.item()))
+        self._res = _Resident(device=device, p16=p16, p32=keep32, mu=mu, sample=sample, s_stride=s_stride, s_rows=s_rows, cnorm=cnorm,
+                              raw_max=raw_max, max_norm=max_norm, query_tile=256 if (d == 768 and self.query_tile_request != 128) else 128,
+                              mu_host=mu_h)
 
     # -- search -------------------------------------------------------------------------------------------------
     @staticmethod
@@ -477,38 +515,33 @@ class FlatIPIndex:
 
     def search(self, queries, k: int):
         """(D np.float32 [nq, k] descending, I np.int64 [nq, k]); missing results: id -1, score -inf."""
-        if self._p16 is None:
+        if self._res is None:
             raise RuntimeError("index is not on a GPU: call convert_index_to_gpu(index, device) first (no CPU search path)")
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError("queries must be [nq, d]")
-        k = int(k)
-        if k <= 0:
-            raise ValueError("k must be positive")
-        nq = q.shape[0]
-        if nq == 0:
-            return np.full((0, k), -np.inf, dtype=np.float32), np.full((0, k), -1, dtype=np.int64)
+        q, k, empty = _check_queries(queries, self.d, k)
+        if empty is not None:
+            return empty
         with torch.cuda.device(self.device):
             Dd, ids64 = self.search_ids_device(torch.from_numpy(q).to(self.device), k)
-            D, I = Dd.cpu().numpy(), ids64.cpu().numpy()
-        return D, I
+            return Dd.cpu().numpy(), ids64.cpu().numpy()
 
     def search_ids_device(self, q32: torch.Tensor, k: int):
         """:meth:`search` without the two PCIe copies: fp32 queries [nq, d] in HBM -> (D fp32 [nq, k], ids int64 [nq, k]) in HBM
         (row position -> id on the device: IndexIDMap).  What a sharded search gathers over RCCL."""
-        with torch.cuda.device(self.device):
+        res = self._res
+        with torch.cuda.device(res.device):
             Dd, Id, stats = self.search_device(q32, int(k))
-            if self.ids is not None and (getattr(self, "_ids_dev", None) is None or self._ids_dev.device != self.device):
-                self._ids_dev = torch.from_numpy(np.ascontiguousarray(self.ids, dtype=np.int64)).to(self.device)
-            ids64 = ops.map_ids(Id, self._ids_dev if self.ids is not None else None, int(self.id_offset))     # one launch (cldrd_map_ids)
+            if self.ids is not None and res.ids_dev is None:
+                res.ids_dev = torch.from_numpy(np.ascontiguousarray(self.ids, dtype=np.int64)).to(res.device)
+            ids64 = ops.map_ids(Id, res.ids_dev if self.ids is not None else None, int(self.id_offset))     # one launch (cldrd_map_ids)
         self.last_stats = stats
         return Dd, ids64
 
     def search_device(self, q32: torch.Tensor, k: int):
         """Search with device-resident fp32 queries [nq, d]; returns device tensors (D fp32 [nq, k], I int32 row positions
         [nq, k], -1 = missing) and the statistics dict.  ONE host synchronisation (the proof flags) when nothing is redone."""
-        dev = self.device
-        n, d = self._p16.shape
+        res = self._res
+        dev, QT = res.device, res.query_tile
+        n, d = res.p16.shape
         nq = q32.shape[0]
         kk = min(k, n)
         exhaustive = n <= CAND_CAP
@@ -516,33 +549,19 @@ class FlatIPIndex:
             raise ValueError(f"top_k = {k} is not supported on an index of {n} rows: the candidate lists hold {CAND_CAP} entries "
                              f"(top_k <= {CAND_CAP // 2}, or an index of at most {CAND_CAP} rows)")
         i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        # 0. queries: 16-bit copies, norms, range flag; fp16-row mode: <q, mu> in fp64, added by the re-score
         q32 = q32.contiguous()
         qh = torch.empty(nq, d, dtype=torch.float16, device=dev)
         qb = torch.empty(nq, d, dtype=torch.bfloat16, device=dev)
         qnorm, flag = torch.empty(nq, **f32), torch.zeros(1, **i32)
         ops.topk_prep_queries(q32, qh, qb, qnorm, flag)
-        qmu = ops.query_dot64(q32, self._mu) if self._fp16_rows else None        # fp16-row mode: <q, mu> in fp64, added by the re-score
-        thr, eps = torch.full((nq,), -float("inf"), **f32), torch.empty(nq, **f32)
+        qmu = ops.query_dot64(q32, res.mu) if res.p32 is None else None
+        # 1. thresholds
+        thr, eps = self._estimate_thresholds(qb, qnorm, kk, exhaustive)
+        # 2. the first pass over every query
         stats = dict(scans=0, rescans=0, candidates=0, rescored=0, unproven_first_pass=0, exhaustive=bool(exhaustive))
-        if exhaustive:
-            ops.topk_thresholds(None, qnorm, self._max_norm, d, None, eps)
-        else:
-            # 1. threshold estimate from the row sample.  lam = expected number of sample rows inside the global top-kk; +4.5 sigma
-            # makes a too-high estimate (-> that query is searched again) a ~1e-5 event per query
-            S = self._s_rows
-            lam = kk * S / n
-            kth = int(min(S, math.ceil(lam + 4.5 * math.sqrt(lam) + 1.0))) if S < n else kk
-            est = torch.empty(nq, **f32)
-            samp = torch.empty(min(nq, EST_CHUNK), self._sample.shape[0], **f32)
-            for lo in range(0, nq, EST_CHUNK):
-                m = min(EST_CHUNK, nq - lo)
-                ops.gemm_nt(qb[lo:lo + m], self._sample, samp[:m], m)
-                ops.topk_kth_largest(samp[:m], S, kth, est[lo:lo + m])
-            del samp
-            ops.topk_thresholds(est, qnorm, self._max_norm, d, thr, eps)
         cap2 = CAND_CAP if exhaustive else self._cap2(kk)
         D, I = torch.empty(nq, k, **f32), torch.empty(nq, k, **i32)
-        QT = self.query_tile
         if self.profile:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -553,25 +572,19 @@ class FlatIPIndex:
         # overflowing it query after query and scanning those a second time.
         probe = 0 if (exhaustive or nq <= 2 * QT or not self.probe) else QT
         if probe:
-            st_p, cnt_p, n2_p, kh_p = self._run(q32[:probe], qh[:probe], thr[:probe], eps[:probe], k, self._workspace(cap2), D[:probe], I[:probe], False,
-                                             qmu=None if qmu is None else qmu[:probe])
-            pr = torch.stack([st_p, n2_p]).cpu().numpy()
-            ok = (pr[0] & 16) == 0
-            need = int(pr[1].max()) if ok.all() else CAND_CAP
-            cap2_rest = cap2
-            while cap2_rest < min(CAND_CAP, int(1.25 * need) + 64):
-                cap2_rest *= 2
-            cap2_rest = min(cap2_rest, CAND_CAP)
+            head, tail = slice(0, probe), slice(probe, nq)
+            first = self._run(q32[head], qh[head], thr[head], eps[head], _sel(qmu, head), k, cap2, D[head], I[head])
+            pr = torch.stack([first[0], first[2]]).cpu().numpy()
+            cap2_rest = _cap2_after_probe(cap2, pr[0], pr[1])
             stats["cap2"] = [cap2, cap2_rest]
-            st_r, cnt_r, n2_r, kh_r = self._run(q32[probe:], qh[probe:], thr[probe:], eps[probe:], k, self._workspace(cap2_rest), D[probe:], I[probe:], False,
-                                             qmu=None if qmu is None else qmu[probe:])
-            st, n2, khat = torch.cat([st_p, st_r]), torch.cat([n2_p, n2_r]), torch.cat([kh_p, kh_r])
-            counts = torch.cat([cnt_p, cnt_r])
+            rest = self._run(q32[tail], qh[tail], thr[tail], eps[tail], _sel(qmu, tail), k, cap2_rest, D[tail], I[tail])
+            st, counts, n2, khat = (torch.cat(pair) for pair in zip(first, rest))
             cap2 = cap2_rest
         else:
-            st, counts, n2, khat = self._run(q32, qh, thr, eps, k, self._workspace(cap2), D, I, exhaustive, qmu=qmu)
+            st, counts, n2, khat = self._run(q32, qh, thr, eps, qmu, k, cap2, D, I, exhaustive=exhaustive)
         if self.profile:
             e1.record()
+        # 3. the proof flags
         status = st.cpu().numpy()                       # the synchronisation of a search (plus the probe's)
         if int(flag.item()):
             raise ValueError("queries must be finite and inside the fp16 range (|x| <= 65504)")
@@ -587,20 +600,19 @@ class FlatIPIndex:
             stats["candidates"] = int(c_all.clamp(max=CAND_CAP).sum().item())
         bad = np.nonzero(status)[0]
         stats["unproven_first_pass"] = int(bad.size)
-        # why (status bits of cldrd_flatip_search): 1 too few candidates, 2 candidate list overflowed, 4 the scan dropped hits, 8 threshold above
-        # t^ - 2 eps, 16 the kept set (k + the 2 eps band) does not fit its buffer
         stats["status_bits_first_pass"] = {int(b): int(((status & b) != 0).sum()) for b in (1, 2, 4, 8, 16) if ((status & b) != 0).any()}
         stats["fallback_queries"] = 0
+        # 4. the proof loop: unproven queries are searched again as :func:`_retry_step` says
         attempt = 0
         thr_h = eps_h = None
         while bad.size:
             attempt += 1
             if exhaustive:
                 raise RuntimeError(f"exhaustive top-k left queries unproven (status bits {sorted(set(status[bad].tolist()))}): a bug")
+            idx = torch.from_numpy(bad).to(dev)
             if attempt > MAX_ATTEMPTS:
                 # More ties / near-ties around the k-th score than the candidate buffers hold (or a threshold that would not settle):
                 # the remaining queries are searched EXACTLY, chunk by chunk, with every row re-scored in fp32 - slow, cannot fail.
-                idx = torch.from_numpy(bad).to(dev)
                 Db, Ib = self._search_exhaustive_chunks(q32.index_select(0, idx), k)
                 D.index_copy_(0, idx, Db)
                 I.index_copy_(0, idx, Ib)
@@ -608,34 +620,11 @@ class FlatIPIndex:
                 break
             if thr_h is None:
                 thr_h, eps_h = thr.cpu().numpy().astype(np.float64), eps.cpu().numpy().astype(np.float64)
-            khat_h = khat.cpu().numpy().astype(np.float64)
-            st_b, t_b, e_b, kh_b = status[bad], thr_h[bad].copy(), eps_h[bad], khat_h[bad]
-            has_k = np.isfinite(kh_b)
-            over = (st_b & 2) != 0
-            few = ((st_b & 1) != 0) & ~over
-            high = ((st_b & 8) != 0) & ~over & ~few
-            # proven bound: the list was complete and long enough, only the threshold sat above t^ - 2 eps
-            t_b[high] = kh_b[high] - 2.0 * e_b[high] * (1.0 + 1e-3) - 1e-6 * np.abs(kh_b[high]) - 1e-30
-            # too few candidates: the estimate was too high; lower it, faster every attempt (but never by more than 8 eps + 20 % at once:
-            # a threshold far below t^ only fills the lists)
-            t_b[few] = t_b[few] - np.minimum(np.maximum(4.0 * e_b[few], 0.05 * np.abs(t_b[few]) + 1e-3) * (2.0 ** (attempt - 1)),
-                                             8.0 * e_b[few] * attempt + 0.2 * np.abs(t_b[few]) + 1e-3)
-            # overflow: the list holds an arbitrary `cap` of the c rows above thr; its k-th largest score is a (low) estimate of t^
-            up = np.where(has_k, kh_b - 2.0 * e_b, -np.inf)
-            t_b[over] = np.maximum(t_b[over] + np.maximum(e_b[over], 1e-3 * np.abs(t_b[over])) * (2.0 ** (attempt - 1)), up[over])
-            # status bit 4: the streaming scan dropped hits (its per-wave on-chip lists overflowed inside one tile: hit density above
-            # ~5 % of a tile, e.g. k = 1000 on an index of a few 10k rows).  Every query of such a pass carries the bit and the same
-            # kernel would drop the same hits again: the retry scans with the tiled kernels, which have no on-chip list.  Queries with
-            # ONLY that bit keep their threshold.
-            tiled = bool(((st_b & 4) != 0).any())
-            cap2_b = CAND_CAP if ((st_b & 16) != 0).any() else cap2
-            idx = torch.from_numpy(bad).to(dev)
-            qb32, qbh = q32.index_select(0, idx), qh.index_select(0, idx)
-            thr_b = torch.from_numpy(t_b.astype(np.float32)).to(dev)
-            eps_b = eps.index_select(0, idx)
+            t_b, tiled, full = _retry_step(status[bad], thr_h[bad], eps_h[bad], khat.cpu().numpy().astype(np.float64)[bad], attempt)
+            cap2_b = CAND_CAP if full else cap2
             Db, Ib = torch.empty(bad.size, k, **f32), torch.empty(bad.size, k, **i32)
-            st2, _, _, khat2 = self._run(qb32, qbh, thr_b, eps_b, k, self._workspace(cap2_b), Db, Ib, False, tiled=tiled,
-                                             qmu=None if qmu is None else qmu.index_select(0, idx))
+            st2, _, _, khat2 = self._run(q32.index_select(0, idx), qh.index_select(0, idx), torch.from_numpy(t_b.astype(np.float32)).to(dev),
+                                         eps.index_select(0, idx), _sel(qmu, idx), k, cap2_b, Db, Ib, tiled=tiled)
             status_b = st2.cpu().numpy()
             good = status_b == 0
             if good.any():
@@ -656,33 +645,48 @@ class FlatIPIndex:
             bad = bad[~good]
         return D, I, stats
 
+    def _estimate_thresholds(self, qb, qnorm, kk: int, exhaustive: bool):
+        """-> (thr, eps) fp32 [nq] on the device: eps_q bounds |scan score - exact score|, thr_q = est_q - 2 eps_q with est_q the kth largest
+        bf16 score of query q against the row sample (-inf, i.e. every row, on an exhaustive search)."""
+        res, nq = self._res, qb.shape[0]
+        f32 = dict(dtype=torch.float32, device=res.device)
+        thr, eps = torch.full((nq,), -float("inf"), **f32), torch.empty(nq, **f32)
+        if exhaustive:
+            ops.topk_thresholds(None, qnorm, res.max_norm, self.d, None, eps)
+            return thr, eps
+        # lam = expected number of sample rows inside the global top-kk; +4.5 sigma makes a too-high estimate (-> that query is searched
+        # again) a ~1e-5 event per query
+        S, n = res.s_rows, res.p16.shape[0]
+        lam = kk * S / n
+        kth = int(min(S, math.ceil(lam + 4.5 * math.sqrt(lam) + 1.0))) if S < n else kk
+        est = torch.empty(nq, **f32)
+        samp = torch.empty(min(nq, EST_CHUNK), res.sample.shape[0], **f32)
+        for lo in range(0, nq, EST_CHUNK):
+            m = min(EST_CHUNK, nq - lo)
+            ops.gemm_nt(qb[lo:lo + m], res.sample, samp[:m], m)
+            ops.topk_kth_largest(samp[:m], S, kth, est[lo:lo + m])
+        ops.topk_thresholds(est, qnorm, res.max_norm, self.d, thr, eps)
+        return thr, eps
+
     def _search_exhaustive_chunks(self, q32: torch.Tensor, k: int):
         """Exact top-k of a few queries with EVERY row re-scored in fp32, CAND_CAP rows at a time (the exhaustive form of
         cldrd_flatip_search on row slices), the running top-k merged with each chunk's by the same sort kernel (score desc, row position
         asc).  The last resort of :meth:`search_device`: reads the fp32 rows once per 128/256 queries, needs no threshold, cannot fail.
         fp16-row mode: the same over slices of the fp16 rows (scores as the class docstring defines them)."""
-        dev = self.device
-        n, d = self._p16.shape
-        qmu = ops.query_dot64(q32.contiguous(), self._mu) if self._fp16_rows else None
-        nq = q32.shape[0]
+        res = self._res
+        n, nq = res.p16.shape[0], q32.shape[0]
+        qmu = ops.query_dot64(q32.contiguous(), res.mu) if res.p32 is None else None
         if 2 * k > CAND_CAP:
             raise ValueError(f"exact fallback: top_k = {k} > {CAND_CAP // 2}")
-        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        i32, f32 = dict(dtype=torch.int32, device=res.device), dict(dtype=torch.float32, device=res.device)
         D = torch.full((nq, k), -float("inf"), **f32)
         I = torch.full((nq, k), -1, **i32)
         eps = torch.zeros(nq, **f32)
         thr = torch.full((nq,), -float("inf"), **f32)
-        ws = self._workspace(CAND_CAP)
         two = torch.full((nq,), 2 * k, **i32)
         for lo in range(0, n, CAND_CAP):
-            hi = min(n, lo + CAND_CAP)
             Dc, Ic = torch.empty(nq, k, **f32), torch.empty(nq, k, **i32)
-            QT = self.query_tile
-            nb = (nq + QT - 1) // QT
-            counts = torch.zeros(nb * (QT + 1), **i32)
-            n2, st, khat = torch.empty(nq, **i32), torch.empty(nq, **i32), torch.empty(nq, **f32)
-            ops.flatip_search(q32, None, thr, eps, self._p16[lo:hi], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
-                              n2, st, khat, Dc, Ic, exhaustive=True, qtile=QT, P32=self._p32[lo:hi] if qmu is None else None, qmu=qmu)
+            self._run(q32, None, thr, eps, qmu, k, CAND_CAP, Dc, Ic, exhaustive=True, rows=slice(lo, lo + CAND_CAP))
             Ic = torch.where(Ic >= 0, Ic + lo, Ic)
             rows = torch.cat([I, Ic], dim=1).contiguous()
             scores = torch.cat([D, Dc], dim=1).contiguous()
@@ -690,30 +694,24 @@ class FlatIPIndex:
             ops.topk_sort(two, rows, scores, k, D, I)          # missing entries (row -1, score -inf) sort last and come out as missing
         return D, I
 
-    def _workspace(self, cap2: int):
-        """Per-batch scratch of the search (reused by every 128-query batch of every search: same stream, so no hazard)."""
-        key = (int(cap2), str(self.device), int(self.query_tile))      # moving / refilling the index must not hand out stale buffers
-        ws = getattr(self, "_ws", None)
-        if ws is None:
-            ws = self._ws = {}
-        if key not in ws:
-            dev, QT = self.device, self.query_tile
-            ws[key] = dict(cand_rows=torch.empty(QT, CAND_CAP, dtype=torch.int32, device=dev),
-                           cand_scores=torch.empty(QT, CAND_CAP, dtype=torch.float32, device=dev),
-                           rows2=torch.empty(QT, cap2, dtype=torch.int32, device=dev),
-                           scores2=torch.empty(QT, cap2, dtype=torch.float32, device=dev))
-        return ws[key]
-
-    def _run(self, q32, qh, thr, eps, k, ws, D, I, exhaustive, tiled=False, qmu=None):
-        dev = self.device
-        nq, QT = q32.shape[0], self.query_tile
-        nb = (nq + QT - 1) // QT
-        counts = torch.zeros(nb * (QT + 1), dtype=torch.int32, device=dev)
+    def _run(self, q32, qh, thr, eps, qmu, k, cap2, D, I, exhaustive=False, tiled=False, rows=slice(None)):
+        """One ``cldrd_flatip_search`` over the queries given and the rows ``rows`` of the shard, kept sets in buffers of ``cap2`` slots ->
+        (status, counts, n2, khat) on the device.  The per-batch scratch is reused by every batch of every search (same stream: no hazard)."""
+        res = self._res
+        dev, QT, nq = res.device, res.query_tile, q32.shape[0]
+        if cap2 not in res.ws:
+            res.ws[cap2] = dict(cand_rows=torch.empty(QT, CAND_CAP, dtype=torch.int32, device=dev),
+                                cand_scores=torch.empty(QT, CAND_CAP, dtype=torch.float32, device=dev),
+                                rows2=torch.empty(QT, cap2, dtype=torch.int32, device=dev),
+                                scores2=torch.empty(QT, cap2, dtype=torch.float32, device=dev))
+        ws = res.ws[cap2]
+        counts = torch.zeros((nq + QT - 1) // QT * (QT + 1), dtype=torch.int32, device=dev)
         n2 = torch.empty(nq, dtype=torch.int32, device=dev)
         status = torch.empty(nq, dtype=torch.int32, device=dev)
         khat = torch.empty(nq, dtype=torch.float32, device=dev)
-        ops.flatip_search(q32, qh, thr, eps, self._p16, k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
-                          n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled, P32=self._p32, qmu=qmu)      # _p32 is None in fp16-row mode
+        ops.flatip_search(q32, qh, thr, eps, res.p16[rows], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
+                          n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled,
+                          P32=None if res.p32 is None else res.p32[rows], qmu=qmu)
         return status, counts, n2, khat
 
     # -- persistence (own format; faiss' binary layout is not reproduced, SURVEY.md section 8b) ----------------
@@ -731,13 +729,13 @@ class FlatIPIndex:
             pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F32}, fh)
 
     def _write16(self, path: str):
-        if self._p16 is not None:
+        if self._res is not None:
             # attached (either mode): the device's centred fp16 rows and statistics
-            r16, mu, cnorm, raw = self._p16.cpu().numpy(), np.array(self.mu), self._cnorm, self._raw_max
+            mu, cnorm, raw = np.array(self.mu), self._res.cnorm, self._res.raw_max
+            np.save(path + ".emb16.npy", self._res.p16.cpu().numpy())
+        elif self._file16 is not None:
+            r16, mu, cnorm, raw = self._file16
             np.save(path + ".emb16.npy", r16)
-        elif self._r16_host is not None:
-            mu, cnorm, raw = np.array(self._mu_host), self._cnorm, self._raw_max
-            np.save(path + ".emb16.npy", self._r16_host)
         else:
             emb = self.embeddings
             if emb is None or emb.shape[0] == 0:
@@ -773,13 +771,12 @@ class FlatIPIndex:
             meta = pickle.load(fh)
         idx = cls(meta["d"])
         if meta.get("format") == FORMAT_F16:
-            idx._r16_host = np.load(path + ".emb16.npy", mmap_mode="r")
-            if idx._r16_host.dtype != np.float16 or idx._r16_host.ndim != 2 or idx._r16_host.shape[1] != idx.d:
+            r16 = np.load(path + ".emb16.npy", mmap_mode="r")
+            if r16.dtype != np.float16 or r16.ndim != 2 or r16.shape[1] != idx.d:
                 raise ValueError(f"{path}.emb16.npy: expected float16 [n, {idx.d}]")
-            idx._mu_host = np.ascontiguousarray(meta["mu"], dtype=np.float32)
-            idx._cnorm, idx._raw_max = float(meta["max_centred_norm"]), float(meta["raw_max_norm"])
+            idx._file16 = (r16, np.ascontiguousarray(meta["mu"], dtype=np.float32), float(meta["max_centred_norm"]), float(meta["raw_max_norm"]))
             idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
-            idx.ntotal = idx._r16_host.shape[0]
+            idx.ntotal = r16.shape[0]
             return idx
         idx.embeddings = np.load(path + ".emb.npy", mmap_mode="r")
         idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
@@ -946,7 +943,7 @@ class ShardedFlatIPIndex:
             return D, I
         t0 = timer()
         out = merge_shard_results([g.numpy() for g in gD], [g.numpy() for g in gI], k)
-        self.last_merge = {"path": "host (cldrd_merge_topk)", "merge_s": timer() - t0}
+        self.last_merge = {"path": _MERGE_HOST, "merge_s": timer() - t0}
         return out
 
     def gather_merge_device(self, Dd: torch.Tensor, Id: torch.Tensor, k: int):
@@ -965,13 +962,9 @@ class ShardedFlatIPIndex:
         dist.gather(Id, gI, dst=0, group=self.group)
         if self.rank != 0:
             return Dd, Id
-        if self.world * k <= CAND_CAP:
-            self.last_merge = {"path": "device (cldrd_merge_topk_device)"}
-            return ops.merge_topk_device(allD, allI, k)
-        # more candidates per query than one sort launch holds: the native host merge
-        D, I = ops.merge_topk_host(list(allD.cpu().numpy()), list(allI.cpu().numpy()), k)
-        self.last_merge = {"path": "host (cldrd_merge_topk)"}
-        return torch.from_numpy(D).to(Dd.device), torch.from_numpy(I).to(Dd.device)
+        D, I, path = _merge_lists(allD, allI, k, as_tensors=True)
+        self.last_merge = {"path": path}
+        return D, I
 
 
 def merge_shard_results(shard_D, shard_I, k):
@@ -980,17 +973,30 @@ def merge_shard_results(shard_D, shard_I, k):
     return ops.merge_topk_host(shard_D, shard_I, k)
 
 
+def _merge_lists(allD: torch.Tensor, allI: torch.Tensor, k: int, as_tensors: bool):
+    """The lists of W shards gathered on one device (scores fp32 [W, nq, k], ids int64 [W, nq, k]) -> (D, I, the path taken, for
+    ``last_merge``): one sort launch when its LDS holds W * k candidates per query, else - more candidates than one launch holds - the
+    native host merge.  ``as_tensors``: the result as tensors on that device, else as numpy arrays; only the path whose own output is of
+    the other kind converts."""
+    if allD.shape[0] * k <= CAND_CAP:
+        D, I = ops.merge_topk_device(allD, allI, k)
+        return (D, I, _MERGE_DEVICE) if as_tensors else (D.cpu().numpy(), I.cpu().numpy(), _MERGE_DEVICE)
+    D, I = ops.merge_topk_host(list(allD.cpu().numpy()), list(allI.cpu().numpy()), k)
+    return (torch.from_numpy(D).to(allD.device), torch.from_numpy(I).to(allD.device), _MERGE_HOST) if as_tensors else (D, I, _MERGE_HOST)
+
+
 class MultiDeviceFlatIPIndex:
     """ONE process, several row shards on the devices of a list: what the reference's list branch of ``convert_index_to_gpu`` intends
     (retriever/retrieval_utils.py:164-182: ``index_cpu_to_gpu_multiple(..., shard=True)``; dead code there - ``gpu_resources`` is undefined).
     Shard s holds the contiguous row range ``ShardedFlatIPIndex.shard_bounds(n, S, s)`` of the index on ``devices[s]`` (a device may appear
     more than once: two shards on one GPU, which is how a one-GPU box tests this path).  ``search``: the queries are uploaded to every
-    device, each shard is searched there (its launches are enqueued before any result is awaited, so shards on different GPUs run side by
-    side), the per-shard lists - scores fp32 [nq, k], ids int64 [nq, k], already mapped - are copied device to device onto ``devices[0]``
-    and merged by the same launch a multi-process search uses on rank 0 (``cldrd_merge_topk_device``; more than 8192 candidates per query:
-    the native host merge).  Order: score desc, ties -> shard asc, then list position asc = global row position asc, the single-index rule.
+    device and the shards are searched ONE AFTER ANOTHER (every search reads its proof flags back to the host before it returns, so shards
+    on different GPUs do not overlap), the per-shard lists - scores fp32 [nq, k], ids int64 [nq, k], already mapped - are copied device to
+    device onto the first live shard's device and merged by the same launch a multi-process search uses on rank 0
+    (``cldrd_merge_topk_device``; more than 8192 candidates per query: the native host merge).  Order: score desc, ties -> shard asc, then
+    list position asc = global row position asc, the single-index rule.  An index without rows answers with all-missing lists.
     The production path for 8 GPUs stays one process per GPU (:class:`ShardedFlatIPIndex`, retrieve_top_passages.py under RANK /
-    WORLD_SIZE): one Python thread enqueues for all devices here."""
+    WORLD_SIZE): one Python thread drives all devices here."""
 
     def __init__(self, index: FlatIPIndex, devices, fp16_rows: bool = False):
         if not devices:
@@ -1011,25 +1017,19 @@ class MultiDeviceFlatIPIndex:
                 else:
                     sh.add(index.embeddings[lo:hi])
                     sh.id_offset = index.id_offset + lo
-                if fp16_rows:
-                    sh.to_gpu(dev, fp16_rows=True)
-                else:
-                    sh.to_gpu(dev)
+                sh.to_gpu(dev, fp16_rows=fp16_rows)
             self.shards.append(sh)
         self.last_stats = {}
         self.last_merge = {}
 
     def search(self, queries, k):
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError("queries must be [nq, d]")
-        k = int(k)
-        if k <= 0:
-            raise ValueError("k must be positive")
+        q, k, empty = _check_queries(queries, self.d, k)
+        if empty is not None:
+            return empty
         nq = q.shape[0]
-        if nq == 0:
-            return np.full((0, k), -np.inf, dtype=np.float32), np.full((0, k), -1, dtype=np.int64)
         live = [sh for sh in self.shards if sh.ntotal > 0]
+        if not live:
+            return _all_missing(nq, k)
         dev0 = live[0].device
         qh = torch.from_numpy(q)
         lists = []
@@ -1049,12 +1049,9 @@ class MultiDeviceFlatIPIndex:
                     torch.cuda.current_stream(dev0).wait_stream(torch.cuda.current_stream(Dd.device))      # the shard's search is done
                 allD[w].copy_(Dd, non_blocking=True)        # device to device (xGMI between GPUs of one node)
                 allI[w].copy_(Id, non_blocking=True)
-            if W * k <= CAND_CAP:
-                Dm, Im = ops.merge_topk_device(allD, allI, k)
-                self.last_merge = {"path": "device (cldrd_merge_topk_device)", "shards": W}
-                return Dm.cpu().numpy(), Im.cpu().numpy()
-            self.last_merge = {"path": "host (cldrd_merge_topk)", "shards": W}
-            return ops.merge_topk_host(list(allD.cpu().numpy()), list(allI.cpu().numpy()), k)
+            D, I, path = _merge_lists(allD, allI, k, as_tensors=False)
+            self.last_merge = {"path": path, "shards": W}
+            return D, I
 
 
 def convert_index_to_gpu(index, faiss_gpu_index, useFloat16=False):
@@ -1067,11 +1064,9 @@ def convert_index_to_gpu(index, faiss_gpu_index, useFloat16=False):
     if type(faiss_gpu_index) == list and len(faiss_gpu_index) == 1:
         faiss_gpu_index = faiss_gpu_index[0]
     if isinstance(faiss_gpu_index, int):
-        return index.to_gpu(faiss_gpu_index, fp16_rows=True) if useFloat16 else index.to_gpu(faiss_gpu_index)
+        return index.to_gpu(faiss_gpu_index, fp16_rows=bool(useFloat16))
     if isinstance(faiss_gpu_index, (list, tuple)):
-        if useFloat16:
-            return MultiDeviceFlatIPIndex(index, list(faiss_gpu_index), fp16_rows=True)
-        return MultiDeviceFlatIPIndex(index, list(faiss_gpu_index))
+        return MultiDeviceFlatIPIndex(index, list(faiss_gpu_index), fp16_rows=bool(useFloat16))
     raise TypeError(f"convert_index_to_gpu: a device index or a list of them, got {type(faiss_gpu_index).__name__}")
 
 

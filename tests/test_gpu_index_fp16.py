@@ -353,7 +353,7 @@ def test_default_mode_is_untouched():
             RU.convert_index_to_gpu(index, 0)
         else:
             RU.convert_index_to_gpu(index, [0], False)
-        assert index.row_dtype == "float32" and index._p32 is not None and not index._fp16_rows
+        assert index.row_dtype == "float32" and index._p32 is not None
         outs.append(index.search(q, k))
     for D, I in outs[1:]:
         assert np.array_equal(D, outs[0][0]) and np.array_equal(I, outs[0][1])

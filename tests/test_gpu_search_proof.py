@@ -283,6 +283,8 @@ def test_range_flag_of_queries_and_index_rows(value, flagged):
         if flagged:
             with pytest.raises(ValueError, match="65504"):
                 RU.convert_index_to_gpu(index, 0, fp16_rows)
+            with pytest.raises(RuntimeError, match="not on a GPU"):        # the refused shard is not searched
+                index.search(q, 3)
         else:
             RU.convert_index_to_gpu(index, 0, fp16_rows)
             assert np.all(index.mu == 0) and float(index._p16[34, 5].item()) == value
