@@ -5,12 +5,14 @@ One process per GPU (``torch.distributed`` backend "nccl" == RCCL over xGMI).  P
 
     forward (query tower, passage tower) -> scoring -> loss value + dlogits (one kernel) -> hand-written backward
     -> per-layer gradient buckets all-reduced on a side stream while the backward of earlier layers still runs
-    -> clip_grad_norm_(max_grad_norm) as one norm pass -> legacy-HF AdamW + bf16 shadows in one pass -> linear schedule
+    -> clip_grad_norm_(max_grad_norm): its sums of squares taken in two pieces under the backward on one GPU (`_ClipNormPlan`), one pass otherwise
+    -> legacy-HF AdamW, which also writes the 16-bit weight shadows the next step reads (fp16 in the default mode, where no training pass
+    reads the bf16 one and it is left stale; bf16 under ``CLDRD_AMP=bf16``) -> linear schedule
 
 Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
   * mixed precision is hand-placed instead of autocast: every MFMA operand of a training pass is fp16 (the reference's own
-    ``use_fp16`` mode; ``CLDRD_AMP=bf16`` runs the backward / tape on bf16 operands instead - there is NO all-bf16 mode: its forward FFN /
-    out-projection / query tower stay fp16), fp32 accumulate, residual stream, gradient stream and master weights;
+    ``use_fp16`` mode, loss-scaled backward); ``CLDRD_AMP=bf16`` is the all-bf16 mode - every operand of the forward, the tape and the
+    backward bf16, no loss scale (DESIGN.md section 3); fp32 accumulate, residual stream, gradient stream and master weights in both;
   * the loss scale is a power of two recomputed from dL/dCLS every step (``cldrd_loss_scale_adapt``), where ``GradScaler`` starts at
     65 536 and searches by overflowing: no early skipped steps here; what is kept is the safety net (a non-finite gradient norm skips the
     step, which - as in ``scaler.step`` - does not advance Adam's bias-correction step);
@@ -84,6 +86,145 @@ def optimizer_param_groups(model):
     return [[e for e in names if not no_decay(e[0])], [e for e in names if no_decay(e[0])]]
 
 
+class _ClipNormPlan:
+    """The sums of squares behind ``clip_grad_norm_``: the partial-sum buffer and what one step decides about it.
+
+    One GPU: the norm is taken in two pieces.  When the passage tower's embedding block is complete (hook -1, called BEFORE its last
+    weight-gradient group is launched) every gradient of the query tower (whose backward is already queued on the second stream) and of that
+    block is final: [0, split) of the joint buffer, two thirds of it.  Their sums of squares are taken on the second stream UNDER the 3-ms
+    weight-gradient launch (HBM reads next to an MFMA-bound kernel); after it only the passage tower's layers are left (`launch`).  Same fp64
+    reduction of fp32 partial sums as the one-piece norm.
+
+    ``partial``: [0, half) the early piece (sqnorm_partial on the second stream), [half, 2 half) the late piece when it is taken by
+    sqnorm_partial, or [half, half + used) when the kernels that write the passage tower's layer gradients leave them (norm sink, round 5).
+    Sink capacity from the layout: a weight-gradient group's slab reduction takes <= 256 slots per problem (4 per layer + the CLS-only
+    layer's split projections), a LayerNorm-parameter reduction ceil(3 d / 64) per LayerNorm (2 per layer + embeddings): 12-layer towers
+    (cfg4) need 13.4 k slots - a fixed 12 288 silently sent them back to the separate norm pass."""
+
+    def __init__(self, model, flat_g):
+        self.flat_g, self.tower = flat_g, model.passage_encoder       # the tower that is handed the sink and reports the slots it used
+        pt = model.towers()[-1]
+        self.early_end = model._tower_offsets[-1] + pt.layout.embed_range[1]          # where the early piece ends when there is one
+        self.half = ops.sqnorm_blocks() // 2
+        self.sink_cap = 256 * (4 * pt.cfg.n_layers + 4) + ((3 * pt.cfg.dim + 63) // 64) * (2 * pt.cfg.n_layers + 2)
+        self.partial = torch.empty(self.half + self.sink_cap, dtype=torch.float32, device=flat_g.device)
+        self.sink = self.partial[self.half:self.half + self.sink_cap]
+        self.warned = False                # the "sink too small" warning is given once per trainer
+        self.begin_step()
+
+    def begin_step(self):
+        """A backward starts (or a capture was abandoned): one-piece norm and no sink until this step says otherwise."""
+        self.split = None                  # the early piece covers flat_g[:split]
+        self.deferred = None               # (event on the main stream, second stream) of an early piece that is still to be enqueued
+        self.sink_on = False
+        self.tower.norm_sink, self.tower.norm_sink_used = None, -1
+
+    def early_hook(self, main, side, defer, use_sink):
+        """This step takes the norm in two pieces: -> the passage tower's ``after_layer`` hook; the tower is handed the sink if ``use_sink``."""
+        self.sink_on = bool(use_sink)
+        if use_sink:
+            self.tower.norm_sink = self.sink
+
+        def hook(layer):
+            if layer != -1 or self.early_end % 4 != 0 or self.early_end >= self.flat_g.numel():
+                return
+            ev = torch.cuda.Event()
+            ev.record(main)
+            self.deferred = (ev, side)
+            # defer: the query tower's backward is enqueued BEHIND the passage tower's (graph capture, see _backward): the partial norm has to
+            # follow it on the second stream - `_backward` calls enqueue_early then - and still only waits for THIS point of the main stream
+            if not defer:
+                self.enqueue_early()
+        return hook
+
+    def enqueue_early(self):
+        if self.deferred is None:
+            return
+        (ev, side), self.deferred = self.deferred, None
+        side.wait_event(ev)
+        with torch.cuda.stream(side):
+            ops.sqnorm_partial(self.flat_g[:self.early_end], self.partial, self.half)
+        self.split = self.early_end
+
+    def launch(self, flat_g, max_norm, clip_out):
+        """The rest of the norm and the clip coefficient, on the current stream (which has joined the second one since the early piece)."""
+        split, half = self.split, self.half
+        if not split:
+            ops.grad_clip_coef(flat_g, max_norm, self.partial, clip_out)
+            return
+        # [0, split) was summed on the second stream during the backward.  The rest - the passage tower's layer gradients - is final only
+        # behind its last weight-gradient group; when that group's slab reduction and the LayerNorm-parameter reduction left their sums of
+        # squares (norm sink), nothing is re-read; else one more pass over them
+        used = int(self.tower.norm_sink_used)
+        if self.sink_on and used > 0:
+            ops.clip_coef(self.partial, half + used, max_norm, clip_out)
+            return
+        if self.sink_on and used == -2 and not self.warned:
+            self.warned = True
+            import warnings
+            warnings.warn(f"clip norm: the norm sink ({self.sink_cap} slots) is too small for this tower's gradient launches; "
+                          "taking the late piece with a separate pass")
+        ops.sqnorm_partial(flat_g[split:], self.partial[half:2 * half], half)
+        ops.clip_coef(self.partial, 2 * half, max_norm, clip_out)
+
+
+class _CapturePolicy:
+    """Which steps are captured into a HIP graph and which are replayed: counts and batch keys only, nothing of torch.
+
+    ``decide(key, eligible)`` is asked once per train_step that wants a graph at all (``eligible``: the batch is padded - a packed batch
+    changes its row count every step) and answers EAGER, VOTE_NO (eager, after a "no" in the ranks' agreement), CAPTURE (capture, then replay)
+    or REPLAY; ``record(key, ok)`` takes the agreed outcome of a CAPTURE or VOTE_NO.
+
+    One GPU: a shape runs eager for its first ``warm`` eligible calls (allocator warm-up, one-time kernel attributes), is captured on the
+    next and replayed from then on; ``max_shapes`` shapes at most are followed (the last partial batch is dropped, drop_last: a few shapes)
+    - a shape first seen when that many are known stays eager for good; one failed capture leaves everything eager for good.
+
+    Data parallel: ranks that replay captured collectives must all do so for the SAME steps, or the collectives of one rank's replay meet
+    another rank's eager launches in another order / never (a hang no capture-time check can see).  So: (a) the decision is taken ONCE, at
+    call number ``warm`` + 1 on every rank - the count advances for EVERY call, eligible or not (whether a rank's batch is packed depends on
+    its own token fill: a count of eligible calls would reach the agreement at different global steps on different ranks, or never, and the
+    one-off all-reduce would meet another rank's bucket all-reduces); there a rank captures its batch shape if it is eligible and the only
+    one seen so far, ``warm`` times, else it votes "no"; one all_reduce(MIN) of the outcomes: a single failure anywhere leaves every rank
+    eager for good; (b) afterwards only that ONE shape replays - an eager step of another shape issues the same bucket all-reduces in the
+    same order as a replay does, so mixing the two across ranks is safe; a second capture (another agreement collective at a rank-dependent
+    step) would not be."""
+    EAGER, VOTE_NO, CAPTURE, REPLAY = "eager", "vote-no", "capture", "replay"
+
+    def __init__(self, warm, ddp, max_shapes=4):
+        self.warm, self.ddp, self.max_shapes = warm, ddp, max_shapes
+        self.calls = 0              # decide() calls under ``ddp``
+        self.seen = {}              # batch key -> eligible eager calls so far
+        self.captured = set()
+        self.broken = False
+
+    def decide(self, key, eligible):
+        if self.broken:
+            return self.EAGER
+        vote = False
+        if self.ddp:
+            self.calls += 1
+            vote = self.calls == self.warm + 1
+        if not eligible:
+            return self.VOTE_NO if vote else self.EAGER
+        if key in self.captured:
+            return self.REPLAY
+        if (self.ddp and self.calls > self.warm + 1) or (key not in self.seen and len(self.seen) >= self.max_shapes):
+            return self.EAGER
+        n = self.seen.setdefault(key, 0)
+        if vote:
+            return self.CAPTURE if (len(self.seen) == 1 and n >= self.warm) else self.VOTE_NO
+        if n < self.warm or self.ddp:
+            self.seen[key] = n + 1
+            return self.EAGER
+        return self.CAPTURE
+
+    def record(self, key, ok):
+        if ok:
+            self.captured.add(key)
+        else:
+            self.broken = True
+
+
 class NwayTrainer:
     def __init__(self, model: NwayDualEncoder, *, loss: str = "lambda_mrr", T: float = 1.0, learning_rate: float = 7e-6,
                  weight_decay: float = 0.01, adam_epsilon: float = 1e-8, max_grad_norm: float = 1.0, warmup_steps: int = 4000,
@@ -136,9 +277,7 @@ class NwayTrainer:
         for ti, (tower, toff) in enumerate(zip(model.towers(), model._tower_offsets)):
             for name in tower.layout.order:
                 off, shape = tower.layout.entries[name]
-                numel = 1
-                for s in shape:
-                    numel *= s
+                numel = math.prod(shape)
                 prefix = "query_encoder." if ti == 0 else "passage_encoder."
                 if not no_decay(prefix + name):
                     flags[(toff + off) // 64:(toff + off + numel + 63) // 64] |= 1
@@ -151,14 +290,8 @@ class NwayTrainer:
             self.buckets.append((ti, -1, toff + a, toff + b))
         self.decay_flags = flags.to(dev)
         self.clip = torch.zeros(3, dtype=torch.float32, device=dev)
-        # clip-norm partial sums: [0, half) the early piece (sqnorm_partial on the second stream), [half, 2 half) the late piece when it is taken by
-        # sqnorm_partial, or [half, half + used) when the kernels that write the passage tower's layer gradients leave them (norm sink, round 5)
-        # sink capacity from the layout: a weight-gradient group's slab reduction takes <= 256 slots per problem (4 per layer + the CLS-only
-        # layer's split projections), a LayerNorm-parameter reduction ceil(3 d / 64) per LayerNorm (2 per layer + embeddings): 12-layer
-        # towers (cfg4) need 13.4 k slots - a fixed 12 288 silently sent them back to the separate norm pass
-        pt = model.towers()[-1].cfg
-        self._sink_cap = 256 * (4 * pt.n_layers + 4) + ((3 * pt.dim + 63) // 64) * (2 * pt.n_layers + 2)
-        self.norm_partial = torch.empty(ops.sqnorm_blocks() // 2 + self._sink_cap, dtype=torch.float32, device=dev)
+        self._norm = _ClipNormPlan(model, self.flat_g)
+        self.norm_partial = self._norm.partial
         self.comm_stream = torch.cuda.Stream(device=dev) if self.distributed else None
         if self.comm_stream is not None:
             self.flat_g.record_stream(self.comm_stream)        # the bucket slices are used on it (the buffer lives as long as the trainer)
@@ -167,10 +300,13 @@ class NwayTrainer:
         # third stream: scoring + loss + score backward between the towers' forward and backward (see forward_backward)
         self.l_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
         self._pending = []
-        self._sink_on = False
-        self._graph_broken = False         # a capture of the step failed: every later step runs eagerly
-        self._norm_split = None            # the clip norm's early piece covers flat_g[:_norm_split] (_early_norm_hook)
-        self._norm_deferred = None
+        # HIP-graph replay of the step (see train_step).  `_state`: None, or the device words a captured step reads - {"seeds": int64[2], the
+        # towers' dropout seeds, "hyper": float32[2], {lr, Adam step size}} - from the first capture on; `_graphs`: batch key -> what `_capture`
+        # returned for that shape; `_policy`: which step is captured / replayed (a failed capture: every later step runs eagerly)
+        self._state = None
+        self._graphs = {}
+        self._policy = _CapturePolicy(self._DDP_WARM, self.distributed)
+        self.last_logits = None
         # test hooks (tests/test_gpu_model.py, test_gpu_amp16.py prove the default path equal to the plain one they select; not configuration):
         self.zero_all_grads = False        # True: zero the whole gradient buffer and accumulate instead of writing every gradient once
         self.use_norm_sink = True          # False: the late clip-norm piece by a separate pass over the gradients
@@ -181,16 +317,14 @@ class NwayTrainer:
         self.amp16 = any(getattr(t, "amp16", False) for t in model.towers())
         self.scale_growth_interval = 2000
         self._scale_state = ops.new_loss_scale_state(dev) if self.amp16 else None
-        self._hyper = None          # device {lr, Adam step size} of the eager loss-scaled step (see _optimizer_launches)
-        self._last_skip_h = False
-        self._ddp_steps = 0         # train_step calls under torch.distributed (the captured-graph agreement happens at a fixed count)
-        self._ddp_graph_key = None
+        # device {lr, Adam step size} of the eager loss-scaled step (see _optimizer_launches)
+        self._hyper = torch.zeros(2, dtype=torch.float32, device=dev) if self.amp16 else None
+        self._opt_step_loaded = None       # Adam's step count of the optimizer state loaded last (load_state_dict)
         if self.distributed:
             # DDP constructor semantics (reference :250-255): rank 0's parameters win
             dist.broadcast(self.flat_p, src=0)
             dist.barrier()
-        self._shadow = None
-        self._joint_shadow()
+        self._build_shadows()
 
     @staticmethod
     def _require_gpu(dev):
@@ -221,43 +355,6 @@ class NwayTrainer:
             self._pending.append(work)
         return hook
 
-    def _early_norm_hook(self, main, side, defer=False):
-        """One GPU: the clip norm is taken in two pieces.  When the passage tower's embedding block is complete (hook -1, called BEFORE
-        its last weight-gradient group is launched) every gradient of the query tower (whose backward is already queued on the second
-        stream) and of that block is final: [0, split) of the joint buffer, two thirds of it.  Their sums of squares are taken on the
-        second stream UNDER the 3-ms weight-gradient launch (HBM reads next to an MFMA-bound kernel); after it only the passage
-        tower's layers are left (`_optimizer_launches`).  Same fp64 reduction of fp32 partial sums as the one-piece norm."""
-        toff = self.model._tower_offsets[-1]
-        split = toff + self.model.towers()[-1].layout.embed_range[1]
-        half = ops.sqnorm_blocks() // 2
-
-        def hook(layer):
-            if layer != -1 or split % 4 != 0 or split >= self.flat_g.numel():
-                return
-            ev = torch.cuda.Event()
-            ev.record(main)
-            if defer:
-                # the query tower's backward is enqueued BEHIND the passage tower's (graph capture, see _backward): the partial norm has to
-                # follow it on the second stream - `_finish_early_norm` - and still only waits for THIS point of the main stream
-                self._norm_deferred = (ev, split, half)
-                return
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                ops.sqnorm_partial(self.flat_g[:split], self.norm_partial, half)
-            self._norm_split = split
-        return hook
-
-    def _finish_early_norm(self, side):
-        d = self._norm_deferred
-        self._norm_deferred = None
-        if d is None:
-            return
-        ev, split, half = d
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            ops.sqnorm_partial(self.flat_g[:split], self.norm_partial, half)
-        self._norm_split = split
-
     def _wait_pending(self):
         """Order every outstanding bucket all-reduce before whatever the CURRENT stream runs next (the gradient norm / optimizer):
         ``Work.wait()`` makes the current stream wait for the collective under ProcessGroupNCCL (no host block) and blocks the host
@@ -273,8 +370,7 @@ class NwayTrainer:
         model = self.model
         if self._state is not None and not _state_written and not torch.cuda.is_current_stream_capturing():
             # called on its own (tests, custom loops) while the towers read their dropout seeds from device memory: fresh seeds first
-            seeds = [t.next_seed() for t in model.towers()]
-            ops.write_step_state(self._state["seeds"], seeds[0], seeds[1] if len(seeds) > 1 else 0, None, 0.0, self.betas[0], self.betas[1], 1)
+            self._write_step_state()
         qe, pe = model.query_encoder, model.passage_encoder
         q, nw = batch["query"], batch["nway_passages"]
         bz, nway, L = nw["input_ids"].shape
@@ -351,7 +447,7 @@ class NwayTrainer:
                 t_.record_stream(main)
             q_cls.record_stream(lst)
             p_cls.record_stream(lst)
-        with ops.loss_scale(self._scale_state.data_ptr() if self.amp16 else None, self.scale_growth_interval):
+        with self._loss_scale():
             self._backward(q_tape, p_tape, dq, dp, main, side, lst, write_once)
         return loss_out, logits
 
@@ -371,6 +467,7 @@ class NwayTrainer:
         """both towers' backward from dq / dp (scaled by the loss scale in the amp16 mode) + the bucket all-reduces.  ``main``, ``side``, ``lst``:
         the streams of the passage tower, the query tower and the loss (forward_backward; any of the last two may be ``main`` itself)."""
         qe, pe = self.model.query_encoder, self.model.passage_encoder
+        self._norm.begin_step()
         if self.model.share_weights:
             # one tower, two tapes: gradients accumulate; all-reduce once everything is in
             pe.backward_from_cls(p_tape, dp)
@@ -397,37 +494,57 @@ class NwayTrainer:
             q_late = side is not main and torch.cuda.is_current_stream_capturing()
             if not q_late:
                 query_backward()
-            self._norm_split = None
-            self._norm_deferred = None
             p_hook = self._bucket_hook(1)
-            self._sink_on = False
-            pe.norm_sink, pe.norm_sink_used = None, -1
             if p_hook is None and side is not main and write_once:
-                p_hook = self._early_norm_hook(main, side, defer=q_late)
-                if self.use_norm_sink:      # (test hook: False takes the late piece by a separate pass)
-                    self._sink_on = True
-                    pe.norm_sink = self.norm_partial[ops.sqnorm_blocks() // 2:ops.sqnorm_blocks() // 2 + self._sink_cap]
+                # one GPU: the clip norm in two pieces (_ClipNormPlan; test hook: use_norm_sink = False takes the late piece by a separate pass)
+                p_hook = self._norm.early_hook(main, side, defer=q_late, use_sink=self.use_norm_sink)
             pe.backward_from_cls(p_tape, dp, after_layer=p_hook, accumulate=not write_once)
             if q_late:
                 # (released together with the passage tower's last weight-gradient group instead: +1.4 %, as in round 3's eager measurement)
                 query_backward()
-                self._finish_early_norm(side)
+                self._norm.enqueue_early()
             main.wait_stream(side)
             if self.distributed:
                 self._wait_pending()
 
-    def optimizer_step(self):
-        """clip_grad_norm_ + AdamW + scheduler.step of reference nway_listwise_1.py:355-367 (bf16: no GradScaler)."""
+    # ---- the step's host bookkeeping: ONE place advances the counters, ONE draws and writes the device-side step state -------------
+    def _advance_counters(self):
+        """global_step / adam_step of the step that is about to be applied; -> the lr in effect during it (the scheduler steps afterwards)."""
         self.global_step += 1
         self.adam_step += 1
-        lr = self.lr(self.global_step - 1)          # the lr in effect during this step (scheduler steps afterwards)
+        return self.lr(self.global_step - 1)
+
+    def _write_step_state(self, lr=None):
+        """Draw the towers' dropout seeds of this step and write them to device memory (`_state`), in stream order in front of the launches
+        that read them; with ``lr`` also {lr, Adam step size} of step ``adam_step`` (less the steps the loss-scale safety net skipped)."""
+        seeds = [t.next_seed() for t in self.model.towers()]
+        hyper = lr is not None
+        ops.write_step_state(self._state["seeds"], seeds[0], seeds[1] if len(seeds) > 1 else 0, self._state["hyper"] if hyper else None,
+                             lr if hyper else 0.0, self.betas[0], self.betas[1], self.adam_step if hyper else 1,
+                             scale_state=self._scale_state if hyper else None)
+
+    def _advance_step_state(self):
+        """A step whose launches read their seeds, lr and Adam step size from device memory (a replay, or an eager step while a captured
+        shape exists): the counters, then the one small launch that writes this step's values.  Returns lr."""
+        lr = self._advance_counters()
+        self._write_step_state(lr)
+        return lr
+
+    def optimizer_step(self):
+        """clip_grad_norm_ + AdamW + scheduler.step of reference nway_listwise_1.py:355-367.  What is kept of its GradScaler (fp16 mode; the
+        bf16 mode has no loss scale) is the safety net: a non-finite gradient norm skips the step on the device."""
+        lr = self._advance_counters()
         self._optimizer_launches(lr, self.adam_step)
         return lr
+
+    def _loss_scale(self):
+        """Launch context of the loss-scaled (fp16) mode: the backward unscales by, and the clip coefficient updates, the device scale."""
+        return ops.loss_scale(self._scale_state.data_ptr() if self.amp16 else None, self.scale_growth_interval)
 
     def _optimizer_launches(self, lr, adam_step):
         """The device work of one optimizer step.  Under a captured step (`_state` installed) lr and the bias-corrected step size are
         read from device memory at replay time and the by-value arguments given here are ignored by the kernel."""
-        with ops.loss_scale(self._scale_state.data_ptr() if self.amp16 else None, self.scale_growth_interval):     # clip_coef updates the scale
+        with self._loss_scale():     # clip_coef updates the scale
             self._norm_launches()
         towers = self.model.towers()
         hyper = self._state["hyper"] if self._state else None
@@ -435,93 +552,63 @@ class NwayTrainer:
             # eager step of the loss-scaled mode: {lr, step size} go through device memory too, because the bias-correction exponent
             # is adam_step MINUS the steps the safety net skipped, and that count lives on the device (`_scale_state[3]`, updated by the
             # clip_coef launch just above; a skipped step leaves p / m / v untouched, so its own step size does not matter)
-            if self._hyper is None:
-                self._hyper = torch.zeros(2, dtype=torch.float32, device=self.flat_p.device)
             hyper = self._hyper
             ops.write_step_state(None, 0, 0, hyper, lr, self.betas[0], self.betas[1], adam_step, scale_state=self._scale_state)
         self._adamw_launches(lr, adam_step, towers, hyper)
 
+    @property
+    def _sink_on(self):
+        return self._norm.sink_on
+
     def _norm_launches(self):
-        split = self._norm_split
-        if split:
-            # [0, split) was summed on the second stream during the backward (`_early_norm_hook`; the main stream has joined it since).  The rest -
-            # the passage tower's layer gradients - is final only behind its last weight-gradient group; when that group's slab reduction
-            # and the LayerNorm-parameter reduction left their sums of squares (norm sink), nothing is re-read; else one more pass over them
-            half = ops.sqnorm_blocks() // 2
-            used = int(self.model.passage_encoder.norm_sink_used)
-            if used > 0 and self._sink_on:
-                ops.clip_coef(self.norm_partial, half + used, self.max_grad_norm, self.clip)
-            else:
-                if self._sink_on and used == -2 and not getattr(self, "_sink_warned", False):
-                    self._sink_warned = True
-                    import warnings
-                    warnings.warn(f"clip norm: the norm sink ({self._sink_cap} slots) is too small for this tower's gradient launches; "
-                                  "taking the late piece with a separate pass")
-                ops.sqnorm_partial(self.flat_g[split:], self.norm_partial[half:2 * half], half)
-                ops.clip_coef(self.norm_partial, 2 * half, self.max_grad_norm, self.clip)
-            self._norm_split = None
-        else:
-            ops.grad_clip_coef(self.flat_g, self.max_grad_norm, self.norm_partial, self.clip)
+        self._norm.launch(self.flat_g, self.max_grad_norm, self.clip)
 
     def _adamw_launches(self, lr, adam_step, towers, hyper=None):
-        # one AdamW launch over the joint buffer; it also writes the bf16 shadow of every tower
-        shadow = self._joint_shadow()
-        # all-fp16 training: no pass of a training step reads the bf16 shadow (forward, backward and the transposed copies come from the fp16
-        # one), so AdamW does not write it; the towers remember it is stale and an evaluation forward casts it first
-        skip_h = self.amp16 and all(t.amp16 for t in towers)
-        # ... and the fp16 shadow of the towers whose forward reads fp16 weights (the FFN GEMMs of every tower by default, the whole
-        # high-precision pass of the query tower): one contiguous range of the joint buffer
-        s16, r16 = self._joint_shadow16()
+        # one AdamW launch over the joint buffer; it also writes the 16-bit weight shadows: the fp16 one of the towers whose forward reads fp16
+        # weights (one contiguous range of the joint buffer) and the bf16 one - unless no pass of a training step reads it (`_skip_h`)
+        s16, r16, skip_h = self._shadow16, self._shadow16_range, self._skip_h
         fused16 = s16 is not None
-        self._last_skip_h = bool(skip_h and fused16)
         with ops.optim_hyper(hyper.data_ptr() if hyper is not None else None):
-            ops.adamw_step(self.flat_p, self.flat_g, self.m, self.v, self.decay_flags, None if (skip_h and fused16) else shadow, lr=lr, beta1=self.betas[0],
+            ops.adamw_step(self.flat_p, self.flat_g, self.m, self.v, self.decay_flags, None if skip_h else self._shadow, lr=lr, beta1=self.betas[0],
                            beta2=self.betas[1], eps=self.eps, weight_decay=self.wd, step=adam_step, clip=self.clip,
                            shadow16=s16[r16[0]:r16[1]] if fused16 else None, h16_range=r16 if fused16 else None)
         # the transposed copies wait for the next step's preamble on the second stream (forward_backward) when there is one
         defer_t = not self.model.share_weights and self.q_stream is not None
         for t in towers:
-            t.refresh_shadows(need_transposed=not defer_t, cast=False, cast16=not fused16, h_stale=skip_h and fused16)
+            t.refresh_shadows(need_transposed=not defer_t, cast=False, cast16=not fused16, h_stale=skip_h)
 
-    def _joint_shadow(self):
-        if getattr(self, "_shadow", None) is None:
-            towers = self.model.towers()
-            self._shadow = torch.empty(self.flat_p.numel(), dtype=torch.bfloat16, device=self.flat_p.device)
-            self._joint_shadow16()
-            for t, off in zip(towers, self.model._tower_offsets):
-                t.flat_h = self._shadow[off:off + t.layout.total]
-                t.refresh_shadows(need_transposed=True)
-        return self._shadow
-
-    def _joint_shadow16(self):
-        """(joint fp16 shadow or None, (begin, end) of the parameters it mirrors): the towers that need fp16 weights are adjacent in the
-        joint buffer, so one range covers them; each such tower's ``flat_h16`` is a slice of the joint tensor."""
-        if getattr(self, "_shadow16", None) is None:
-            towers, offs = self.model.towers(), self.model._tower_offsets
-            need = [(t, off) for t, off in zip(towers, offs) if t.needs_h16]
-            if not need:
-                self._shadow16 = (None, None)
-            else:
-                lo, hi = need[0][1], need[-1][1] + need[-1][0].layout.total
-                if sum(t.layout.total for t, _ in need) != hi - lo:
-                    raise RuntimeError("towers with fp16 weights are not adjacent in the joint buffer")
-                buf = torch.empty(self.flat_p.numel(), dtype=torch.float16, device=self.flat_p.device)
-                for t, off in need:
-                    t.flat_h16 = buf[off:off + t.layout.total]
-                    t._shadow_version = -1
-                self._shadow16 = (buf, (lo, hi))
-        return self._shadow16
+    def _build_shadows(self):
+        """The joint 16-bit weight shadows AdamW writes, once per trainer: bf16 over the whole joint buffer (each tower's ``flat_h`` a slice) and
+        fp16 over the towers that read fp16 weights - adjacent in the joint buffer, so one range covers them (``flat_h16`` a slice each)."""
+        towers, offs = self.model.towers(), self.model._tower_offsets
+        n, dev = self.flat_p.numel(), self.flat_p.device
+        self._shadow = torch.empty(n, dtype=torch.bfloat16, device=dev)
+        self._shadow16, self._shadow16_range = None, None
+        need = [(t, off) for t, off in zip(towers, offs) if t.needs_h16]
+        if need:
+            lo, hi = need[0][1], need[-1][1] + need[-1][0].layout.total
+            if sum(t.layout.total for t, _ in need) != hi - lo:
+                raise RuntimeError("towers with fp16 weights are not adjacent in the joint buffer")
+            self._shadow16, self._shadow16_range = torch.empty(n, dtype=torch.float16, device=dev), (lo, hi)
+            for t, off in need:
+                t.flat_h16 = self._shadow16[off:off + t.layout.total]
+                t._shadow_version = -1
+        # all-fp16 training: no pass of a training step reads the bf16 shadow (forward, backward and the transposed copies come from the fp16
+        # one), so AdamW does not write it; the towers remember it is stale and an evaluation forward casts it first
+        self._skip_h = bool(self.amp16 and all(t.amp16 for t in towers) and self._shadow16 is not None)
+        for t, off in zip(towers, offs):
+            t.flat_h = self._shadow[off:off + t.layout.total]
+            t.refresh_shadows(need_transposed=True)
 
     def train_step(self, batch):
         """One full step; returns the device tensor {loss, pair count} (no host sync).
 
-        After ``CLDRD_GRAPH_WARMUP`` (3) eager steps on one batch shape the step - forward, loss, backward, clip, AdamW, shadows, both
-        streams: ~370 kernel launches - is captured into a HIP graph and replayed (``CLDRD_GRAPH=0``: always eager; never under
-        torch.distributed: the bucket all-reduces are issued from hooks).  The host then spends ~0.1 ms per step instead of ~3.7 ms,
+        After `_DDP_WARM` (3) eager steps on one batch shape the step - forward, loss, backward, clip, AdamW, shadows, all three
+        streams: ~370 kernel launches - is captured into a HIP graph and replayed (``CLDRD_GRAPH=0``: always eager; `_CapturePolicy`: which
+        steps, on one GPU and under torch.distributed).  The host then spends ~0.1 ms per step instead of ~3.7 ms,
         which is what an enqueue-bound shape (cfg1: B = 4, N = 8) and eight rank processes sharing one host need.  What changes
         from step to step - the two towers' dropout seeds, lr, Adam's bias-corrected step size - lives in device memory and is
         written by one small launch in front of each replay (``ops.write_step_state``); results are bit-identical to the eager path."""
-        self._joint_shadow()
         nw = batch["nway_passages"]
         lens = _lengths(nw)
         if lens is not None:
@@ -532,19 +619,10 @@ class NwayTrainer:
                 batch = dict(batch.items())
                 batch["nway_passages"] = {k: v for k, v in nw.items() if k != "lengths"}
                 lens = None
-        # Data-parallel ranks that may replay captured collectives agree on it ONCE, at call number _DDP_WARM + 1 of EVERY rank: the count
-        # advances here, in front of the per-batch gates below (whether THIS rank's batch is packed depends on its own token fill, so a
-        # count taken behind the gate would reach the agreement step at different global steps on different ranks, or never: the one-off
-        # all-reduce would then meet another rank's bucket all-reduces - a hang).  A rank whose batch is not eligible at that step votes "no".
-        ddp_graph = self.distributed and self._graph_wanted()
-        if ddp_graph:
-            self._ddp_steps += 1
-        if self._graph_wanted() and lens is None:      # a packed batch changes its row count every step: eager
-            out = self._train_step_graph(batch)
+        if self._graph_wanted():
+            out = self._train_step_graph(batch, padded=lens is None)       # a packed batch changes its row count every step: eager
             if out is not None:
                 return out
-        elif ddp_graph and self._ddp_steps == self._DDP_WARM + 1:
-            self._agree_on_capture(False)              # packed batch at the agreement step: every rank stays eager for good
         if self._state is not None:
             # a captured shape exists, so the towers read their seeds (and AdamW its lr) from device memory: an eager step (another
             # batch shape) writes this step's values there first, exactly as a replay does
@@ -552,29 +630,27 @@ class NwayTrainer:
             loss_out, logits = self.forward_backward(batch, _state_written=True)
             self._optimizer_launches(lr, self.adam_step)
         else:
+            # the plain eager step: the towers draw their own seeds, the hyper-parameters go by value, the counters advance after the backward
             loss_out, logits = self.forward_backward(batch)
             self.optimizer_step()
         self.last_logits = logits
         return loss_out
-
-    def _advance_step_state(self):
-        """Host bookkeeping of one step (what optimizer_step / encode do in the eager path) + the launch that writes the step's seeds, lr
-        and Adam step size to device memory, in stream order in front of the launches that read them.  Returns lr."""
-        self.global_step += 1
-        self.adam_step += 1
-        lr = self.lr(self.global_step - 1)
-        seeds = [t.next_seed() for t in self.model.towers()]
-        ops.write_step_state(self._state["seeds"], seeds[0], seeds[1] if len(seeds) > 1 else 0, self._state["hyper"], lr, self.betas[0],
-                             self.betas[1], self.adam_step, scale_state=self._scale_state)
-        return lr
 
     def skipped_steps(self) -> int:
         """Steps the loss-scale safety net skipped so far (a device -> host read: logging / checkpoint time only)."""
         return int(self._scale_state[3].item()) if self._scale_state is not None else 0
 
     # ---- HIP-graph replay of the step --------------------------------------------------------------------------------------
-    _state = None
     _DDP_WARM = 3               # eager steps in front of the capture (and, under torch.distributed, in front of the agreement step)
+
+    @property
+    def _ddp_steps(self):
+        """train_step calls under torch.distributed while a graph was wanted (the agreement happens at a fixed count)"""
+        return self._policy.calls
+
+    @property
+    def _graph_broken(self):
+        return self._policy.broken
 
     def _graph_wanted(self):
         if self.distributed:
@@ -588,77 +664,62 @@ class NwayTrainer:
         return (not self.model.share_weights and not self._graph_broken
                 and _env_flag("CLDRD_GRAPH", "1") != "0" and self.flat_p.is_cuda)
 
-    def _batch_key(self, batch):
+    def _step_inputs(self, batch):
+        """The per-step inputs of the captured step: [(where it sits in the batch dict, tensor, dtype the static batch holds it in - None: its
+        own)], in ONE order for the batch key, the static batch and every incoming one (at most 6 segments; cldrd_copy_segments takes 8).
+        The teacher scores are one of them: a distilling step reads this step's scores, like its labels."""
         q, nw = batch["query"], batch["nway_passages"]
-        key = (tuple(q["input_ids"].shape), q.get("attention_mask") is not None, tuple(nw["input_ids"].shape), tuple(batch["labels"].shape))
+        items = [(("query", "input_ids"), q["input_ids"], None), (("nway_passages", "input_ids"), nw["input_ids"], None),
+                 (("nway_passages", "attention_mask"), nw["attention_mask"], None), (("labels",), batch["labels"], torch.float32)]
+        if q.get("attention_mask") is not None:
+            items.append((("query", "attention_mask"), q["attention_mask"], None))
         if self.distill is not None:
             bz, nway, _ = nw["input_ids"].shape
-            key += (tuple(self._teacher_scores(batch, bz, nway).shape),)
-        return key
+            items.append((("teacher_scores",), self._teacher_scores(batch, bz, nway), torch.float32))
+        return items
 
-    def _train_step_graph(self, batch):
-        key = self._batch_key(batch)
-        graphs = self.__dict__.setdefault("_graphs", {})
-        entry = graphs.get(key)
-        if entry is None:
-            entry = graphs[key] = {"seen": 0, "graph": None}
-        warm = self._DDP_WARM
-        ddp = self.distributed        # (a one-rank forced group, CLDRD_FORCE_DDP, takes the same path: the agreement is then a one-rank all-reduce)
-        if ddp:
-            # Ranks that replay captured collectives must all do so for the SAME steps, or the collectives of one rank's replay meet another
-            # rank's eager launches in another order / never (a hang no capture-time check can see).  So: (a) the decision is taken ONCE, at
-            # train_step call number `warm` + 1 on every rank (a count, not a per-shape condition: ranks with dynamic padding see different
-            # shapes); there each rank tries to capture its current batch shape if it has seen nothing else so far, and the ranks agree with
-            # one all_reduce(MIN) of the outcome: a single failure anywhere leaves every rank eager for good; (b) afterwards only that ONE
-            # shape replays - an eager step of another shape issues the same bucket all-reduces in the same order as a replay does, so
-            # mixing the two across ranks is safe, a second capture (another agreement collective at a rank-dependent step) would not be.
-            # (`_ddp_steps` is advanced by train_step for every call, eligible for the graph path or not)
-            if self._ddp_steps <= warm:
-                entry["seen"] += 1
-                return None
-            if self._ddp_steps > warm + 1:
-                if entry["graph"] is None:
-                    return None
-            elif len(graphs) > 1 or entry["seen"] < warm:
-                self._agree_on_capture(False)
-                return None
-        if entry["graph"] is None and entry["seen"] < warm:
-            entry["seen"] += 1              # eager: allocator warm-up, one-time kernel attributes
+    def _batch_key(self, batch):
+        return tuple((where, tuple(t.shape)) for where, t, _ in self._step_inputs(batch))
+
+    def _train_step_graph(self, batch, padded=True):
+        """Ask the policy what this step is and carry the answer out; -> the step's loss tensor, or None: the caller runs it eagerly."""
+        P = _CapturePolicy
+        key = self._batch_key(batch) if padded else None
+        action = self._policy.decide(key, padded)
+        if action == P.VOTE_NO:
+            self._policy.record(key, self._agree_on_capture(False))       # (not eligible at the agreement step: every rank stays eager for good)
+        if action in (P.EAGER, P.VOTE_NO):
             return None
-        dev = self.flat_p.device
-        if self._state is None:
-            self._state = {"seeds": torch.zeros(2, dtype=torch.int64, device=dev), "hyper": torch.zeros(2, dtype=torch.float32, device=dev)}
         towers = self.model.towers()
-        if entry["graph"] is None:
-            if len(graphs) > 4:            # a few shapes at most (the last partial batch is dropped: drop_last): anything else stays eager
-                return None
-            ok = True
+        if action == P.CAPTURE:
+            if self._state is None:
+                dev = self.flat_p.device
+                self._state = {"seeds": torch.zeros(2, dtype=torch.int64, device=dev), "hyper": torch.zeros(2, dtype=torch.float32, device=dev)}
+            entry = None
             try:
-                entry.update(self._capture(batch))
-                entry["h_stale"] = self._last_skip_h        # the captured AdamW does not write the bf16 shadow (see the replay below)
+                entry = self._capture(batch)
             except Exception as exc:       # a capture problem must never take training down: fall back to the eager step for good
                 import warnings
                 first = exc
                 while first.__context__ is not None:          # what went wrong INSIDE the capture (the capture's own exit error hides it)
                     first = first.__context__
                 warnings.warn(f"HIP-graph capture of the training step failed ({type(first).__name__}: {first}); staying eager")
-                ok = False
-            if ddp:
+            ok = entry is not None
+            if self.distributed:    # (a one-rank forced group, CLDRD_FORCE_DDP, takes the same path: the agreement is then a one-rank all-reduce)
                 ok = self._agree_on_capture(ok)
-                if not ok:
-                    entry["graph"] = None
+            self._policy.record(key, ok)
             if not ok:
-                self._graph_broken = True
                 for t in towers:
                     t.seed_base_ptr = None
                     t._t_fresh = False       # refresh_transposed() inside the failed capture set the flag without executing a kernel
                 self._state = None
-                self._norm_split = None
-                self._norm_deferred = None
+                self._norm.begin_step()
                 torch.cuda.synchronize()
                 return None
+            self._graphs[key] = entry
+        entry = self._graphs[key]
         # this step's inputs and state, in stream order in front of the replay
-        dsts, srcs = entry["inputs"], self._flat_inputs(batch)
+        dsts, srcs = entry["inputs"], [t for _, t, _ in self._step_inputs(batch)]
         if all(s_.is_cuda and s_.is_contiguous() and s_.dtype == d_.dtype and s_.shape == d_.shape for d_, s_ in zip(dsts, srcs)):
             ops.copy_segments(dsts, srcs)           # one launch instead of five
         else:
@@ -666,7 +727,7 @@ class NwayTrainer:
                 dst.copy_(src, non_blocking=True)
         self._advance_step_state()
         entry["graph"].replay()
-        if entry.get("h_stale"):
+        if self._skip_h:
             # The captured AdamW skipped the bf16 weight shadow (all-fp16 training reads none of it).  The Python call that records this
             # (refresh_shadows(h_stale=True)) ran at capture time only; a replay changes the weights again, so every replay has to leave the
             # towers marked - or an evaluation forward after further replays would encode with the bf16 matrices of the LAST evaluation.
@@ -685,33 +746,17 @@ class NwayTrainer:
         if not agreed and ok:
             import warnings
             warnings.warn("HIP-graph capture of the training step failed on another rank; every rank stays eager")
-        if not agreed:
-            self._graph_broken = True
         return agreed
-
-    def _flat_inputs(self, batch):
-        """The per-step inputs of the captured step, in one order for the static batch and every incoming one (at most 6 segments;
-        cldrd_copy_segments takes 8).  The teacher scores are one of them: a distilling step reads this step's scores, like its labels."""
-        q, nw = batch["query"], batch["nway_passages"]
-        t = [q["input_ids"], nw["input_ids"], nw["attention_mask"], batch["labels"]]
-        if q.get("attention_mask") is not None:
-            t.append(q["attention_mask"])
-        if self.distill is not None:
-            t.append(batch["teacher_scores"])
-        return t
 
     def _capture(self, batch):
         dev = self.flat_p.device
-        towers = self.model.towers()
-        q, nw = batch["query"], batch["nway_passages"]
-        static = {"query": {"input_ids": q["input_ids"].to(dev).clone()},
-                  "nway_passages": {"input_ids": nw["input_ids"].to(dev).clone(), "attention_mask": nw["attention_mask"].to(dev).clone()},
-                  "labels": batch["labels"].to(device=dev, dtype=torch.float32).clone()}
-        if q.get("attention_mask") is not None:
-            static["query"]["attention_mask"] = q["attention_mask"].to(dev).clone()
-        if self.distill is not None:
-            static["teacher_scores"] = batch["teacher_scores"].to(device=dev, dtype=torch.float32).contiguous().clone()
-        for i, t in enumerate(towers):
+        static = {}
+        for where, t, dtype in self._step_inputs(batch):
+            d = static
+            for k in where[:-1]:
+                d = d.setdefault(k, {})
+            d[where[-1]] = t.to(device=dev, dtype=dtype or t.dtype).contiguous().clone()
+        for i, t in enumerate(self.model.towers()):
             t.seed_base_ptr = self._state["seeds"].data_ptr() + 8 * i
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -732,7 +777,7 @@ class NwayTrainer:
                     if s_ is not None:
                         cur.wait_stream(s_)
                 raise
-        return {"graph": g, "inputs": self._flat_inputs(static), "loss_out": loss_out, "logits": logits, "static": static,
+        return {"graph": g, "inputs": [t for _, t, _ in self._step_inputs(static)], "loss_out": loss_out, "logits": logits, "static": static,
                 "last_kd": self.last_kd}
 
     # ---------------------------------------------------------------------------------------------------------
@@ -766,10 +811,7 @@ class NwayTrainer:
     def _slice(self, buf, ti, hf_name):
         tower, toff = self.model.towers()[ti], self.model._tower_offsets[ti]
         off, shape = tower.layout.entries[hf_name]
-        numel = 1
-        for d in shape:
-            numel *= d
-        return buf[toff + off:toff + off + numel].view(shape)
+        return buf[toff + off:toff + off + math.prod(shape)].view(shape)
 
     def optimizer_state_dict(self):
         """``torch.optim.Optimizer.state_dict()`` layout of the reference's AdamW (state: step / exp_avg / exp_avg_sq per parameter
@@ -890,7 +932,8 @@ def get_args(argv=None):
     ap.add_argument("--reg_lambda", default=0.0, type=float)
     ap.add_argument("--query_max_len", default=30, type=int)
     ap.add_argument("--passage_max_len", default=256, type=int)
-    ap.add_argument("--use_fp16", default=True, type=bool, help="accepted for compatibility: MFMA operands are fp16 (loss-scaled backward) with fp32 master weights; CLDRD_AMP=bf16 for a bf16 backward")
+    ap.add_argument("--use_fp16", default=True, type=bool, help="accepted for compatibility: MFMA operands are fp16 (loss-scaled backward) with fp32 master weights; CLDRD_AMP=bf16 selects the "
+                    "all-bf16 mode (every operand bf16, no loss scale)")
     ap.add_argument("--train_batch_size", default=8, type=int)
     ap.add_argument("--share_weights", action="store_true", default=False)
     ap.add_argument("--label_mode", default="8", type=str)

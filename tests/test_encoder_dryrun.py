@@ -460,26 +460,31 @@ def _trace_cases():
 TRACE_CASES = _trace_cases()
 
 
-def walk_trace(case, calls, monkeypatch):
-    """Run one case under the stubs of ``_install_stubs``; -> [(entry point, 8-hex-digit hash of its canonical arguments)]"""
+def walk_trace(case, calls, monkeypatch, cases=None):
+    """Run one case (of ``cases``, default TRACE_CASES) under the stubs of ``_install_stubs``; -> [(entry point, 8-hex-digit hash of its
+    canonical arguments)]"""
     import hashlib
     monkeypatch.delenv("CLDRD_PACK", raising=False)
     n0 = len(calls.args)
     with _KeepAlive(calls.keep):
-        calls.keep.append(TRACE_CASES[case](calls, monkeypatch))
+        calls.keep.append((TRACE_CASES if cases is None else cases)[case](calls, monkeypatch))
     return [(name, hashlib.sha1(a.encode()).hexdigest()[:8]) for name, a in _canonical(calls.args[n0:])]
 
 
 _TRACE_GOLDEN = None
 
 
+def _load_golden(name):
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name)) as fh:
+        return json.load(fh)["cases"]
+
+
 def _trace_golden():
     global _TRACE_GOLDEN
     if _TRACE_GOLDEN is None:
-        import json
-        import os
-        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "encoder_launch_trace.json")) as fh:
-            _TRACE_GOLDEN = json.load(fh)["cases"]
+        _TRACE_GOLDEN = _load_golden("encoder_launch_trace.json")
     return _TRACE_GOLDEN
 
 
@@ -495,3 +500,216 @@ def test_launch_trace_matches_golden(stubbed, monkeypatch, case):
     for k, ((name, digest), wname, wdigest) in enumerate(zip(got, want["names"], want["hashes"])):
         assert (name, digest) == (wname, wdigest), f"{case}: launch {k} differs: {name} (golden: {wname})"
     assert len(got) == len(want["names"]), f"{case}: {len(got)} launches, golden {len(want['names'])}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Launch trace of the training step (tests/golden/trainer_launch_trace.json, written by make_encoder_launch_trace.py --trainer at the commit
+# it names): the same canonical form, with the stream in it.  `torch.cuda.stream(s)` is a real context over a stack of fake streams, every
+# launch's stream argument is the small index of the stack's top, and the cross-stream edges (wait_stream, wait_event, Event.record) and
+# the graph calls (capture begin / end, replay) are marks between the launches - so a change of NwayTrainer's host code that is meant to
+# leave every launch on its stream, in its order, behind its waits must reproduce the golden.
+
+class _TraceStream:
+    def __init__(self, rig, idx):
+        self.rig, self.idx, self.cuda_stream = rig, idx, idx
+
+    def wait_stream(self, s):
+        self.rig.mark("wait_stream", self.idx, s.idx)
+
+    def wait_event(self, e):
+        self.rig.mark("wait_event", self.idx, e.idx)
+
+
+class _TraceEvent:
+    def __init__(self, rig, idx):
+        self.rig, self.idx = rig, idx
+
+    def record(self, stream=None):
+        self.rig.mark("event_record", self.idx, (stream or self.rig.stack[-1]).idx)
+
+
+class _TraceGraph:
+    def __init__(self, rig, idx):
+        self.rig, self.idx = rig, idx
+
+    def replay(self):
+        self.rig.mark("graph_replay", self.idx)
+
+
+class _StreamRig:
+    """torch.cuda's stream / event / graph surface as the trainer uses it, on the host: stream 0 is the main one."""
+
+    def __init__(self, calls, monkeypatch):
+        import contextlib
+        self.calls, self.n_streams, self.n_events, self.n_graphs, self.capturing = calls, 0, 0, 0, False
+        self.stack = [self.new_stream()]
+
+        @contextlib.contextmanager
+        def on(s):
+            self.stack.append(s)
+            try:
+                yield
+            finally:
+                self.stack.pop()
+
+        @contextlib.contextmanager
+        def capture(g, **kw):
+            self.mark("capture_begin", g.idx)
+            self.capturing = True
+            try:
+                yield
+            finally:
+                self.capturing = False
+                self.mark("capture_end", g.idx)
+        monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: self.stack[-1])
+        monkeypatch.setattr(torch.cuda, "stream", on)
+        monkeypatch.setattr(torch.cuda, "Stream", lambda *a, **k: self.new_stream())
+        monkeypatch.setattr(torch.cuda, "Event", lambda *a, **k: self.new_event())
+        monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: self.capturing)
+        monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+        monkeypatch.setattr(torch.cuda, "CUDAGraph", lambda *a, **k: self.new_graph())
+        monkeypatch.setattr(torch.cuda, "graph", capture)
+        monkeypatch.setattr(torch.Tensor, "record_stream", lambda t, s_: None)
+        monkeypatch.setattr(ops, "_stream", lambda: self.stack[-1].idx)
+
+    def mark(self, what, *a):
+        self.calls.args.append((what, a))
+
+    def new_stream(self):
+        self.n_streams += 1
+        return _TraceStream(self, self.n_streams - 1)
+
+    def new_event(self):
+        self.n_events += 1
+        return _TraceEvent(self, self.n_events - 1)
+
+    def new_graph(self):
+        self.n_graphs += 1
+        return _TraceGraph(self, self.n_graphs - 1)
+
+
+def _step_batch(TL, ragged, batch=2, teacher=False):
+    """``ragged``: the packed batch.  (At 20 tokens the generator's MS MARCO-shaped lengths are all 20 - its floor is 16 - so the padding that
+    makes the encoder pack the batch is cut here: 63 of 120 token rows.)"""
+    b = syn.nway_batch(5, batch, 3, 6, 20, vocab=512, ragged=ragged, label_kind="teacher", with_teacher_scores=teacher)
+    if ragged:
+        nw = b["nway_passages"]
+        mask = (torch.arange(20)[None, :] < torch.tensor([20, 3, 10, 17, 5, 8] * batch)[:3 * batch, None]).long().view(batch, 3, 20)
+        nw["attention_mask"], nw["input_ids"] = mask, nw["input_ids"] * mask
+    return TL.batch_to_device(b, torch.device("cpu"))
+
+
+def _step_trainer(calls, monkeypatch, amp, model_kw, trainer_kw, hooks=()):
+    from cldrd_amd.trainer import nway_listwise as TL
+    rig = _StreamRig(calls, monkeypatch)
+    monkeypatch.setattr(TL.NwayTrainer, "_require_gpu", staticmethod(lambda dev: None))
+    monkeypatch.setenv("CLDRD_AMP", amp)
+    torch.manual_seed(0)
+    model = NwayDualEncoder(cfg_of("distilbert", 3), **{"share_weights": False, **model_kw})
+    tr = TL.NwayTrainer(model, **{"loss": "kl_div", **trainer_kw})
+    tr.q_stream, tr.l_stream = rig.new_stream(), rig.new_stream()       # (the constructor makes none for a host model)
+    for name, value in hooks:
+        setattr(tr, name, value)
+    return TL, rig, model, tr
+
+
+def _step_case(amp="fp16", ragged=(True, False), model_kw=None, trainer_kw=None, hooks=(), standalone=False, sink_used=None):
+    """one eager step per entry of ``ragged`` (True: the packed batch, False: the padded one) on one trainer.  ``sink_used``: what the
+    library reports for a norm sink after the passage tower's gradient launches (stubbed launches write nothing: 0, the separate late
+    pass); a positive count walks the sink's own branch, -2 (the sink overflowed) the separate pass behind ONE warning."""
+    def run(calls, monkeypatch):
+        import warnings
+        monkeypatch.setenv("CLDRD_GRAPH", "0")
+        TL, rig, model, tr = _step_trainer(calls, monkeypatch, amp, model_kw or {}, trainer_kw or {}, hooks)
+        if sink_used is not None:
+            class reported(ops.norm_sink):
+                def __exit__(self, *exc):
+                    super().__exit__(*exc)
+                    if self.slots is not None:
+                        self.used = sink_used
+            monkeypatch.setattr(ops, "norm_sink", reported)
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            for r in ragged:
+                batch = _step_batch(TL, r, teacher=tr.distill is not None)
+                nw = batch["nway_passages"]
+                assert model.passage_encoder.would_pack(nw["lengths"], 6, 20) == r
+                if standalone:
+                    tr.forward_backward(batch)
+                    tr.optimizer_step()
+                else:
+                    tr.train_step(batch)
+        assert tr.global_step == len(ragged) and len([w for w in caught if "norm sink" in str(w.message)]) == (1 if sink_used == -2 else 0)
+        return model, tr
+    return run
+
+
+def _graph_case():
+    """the graph path: six steps of one padded shape (three eager, the capture + first replay, two replays), one eager step of a second
+    shape while the step state lives in device memory, then a stand-alone forward_backward + optimizer_step in that state.  A host tensor
+    is never ``is_cuda``, so `_graph_wanted` is its one-GPU rule without the device test."""
+    def run(calls, monkeypatch):
+        import warnings
+        from cldrd_amd.encoder import _env_flag
+        monkeypatch.delenv("CLDRD_GRAPH", raising=False)
+        TL, rig, model, tr = _step_trainer(calls, monkeypatch, "fp16", {}, {})
+        monkeypatch.setattr(TL.NwayTrainer, "_graph_wanted", lambda self: (not self.model.share_weights and not self._graph_broken
+                                                                            and _env_flag("CLDRD_GRAPH", "1") != "0"))
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")          # a failed capture is a warning and an eager step: not what this case walks
+            for _ in range(6):
+                tr.train_step(_step_batch(TL, False))
+            assert rig.n_graphs == 1 and [e["graph"] is not None for e in tr._graphs.values()] == [True]
+            other = _step_batch(TL, False, batch=3)
+            tr.train_step(other)
+            tr.forward_backward(other)
+            tr.optimizer_step()
+        assert rig.n_graphs == 1 and tr.global_step == 8 and tr._state is not None
+        return model, tr
+    return run
+
+
+def _trainer_trace_cases():
+    cases = {}
+    for amp in ("fp16", "bf16"):
+        cases[f"step-{amp}-packed"] = _step_case(amp, ragged=(True,))
+        cases[f"step-{amp}-padded"] = _step_case(amp, ragged=(False,))
+    cases["step-distill_kl_div"] = _step_case(trainer_kw=dict(distill="kl_div", distill_alpha=0.5, distill_T=2.0))
+    cases["step-distill_only"] = _step_case(trainer_kw=dict(loss="lambda_mrr", distill="kl_div", distill_only=True))
+    cases["step-reg_lambda"] = _step_case(trainer_kw=dict(reg_lambda=0.25))
+    cases["step-share_weights"] = _step_case(model_kw=dict(share_weights=True))
+    cases["step-zero_all_grads"] = _step_case(hooks=(("zero_all_grads", True),))
+    cases["step-no_norm_sink"] = _step_case(hooks=(("use_norm_sink", False),))
+    cases["step-sink_used"] = _step_case(sink_used=7)
+    cases["step-sink_overflow"] = _step_case(sink_used=-2)
+    cases["step-in_batch"] =_step_case(model_kw=dict(in_batch_loss=True, all_in_batch_neg=False))
+    cases["step-all_in_batch"] = _step_case(model_kw=dict(in_batch_loss=True, all_in_batch_neg=True))
+    cases["step-standalone"] = _step_case(standalone=True)
+    cases["graph-six_steps_then_second_shape"] = _graph_case()
+    return cases
+
+
+TRAINER_TRACE_CASES = _trainer_trace_cases()
+_TRAINER_GOLDEN = None
+
+
+def _trainer_golden():
+    global _TRAINER_GOLDEN
+    if _TRAINER_GOLDEN is None:
+        _TRAINER_GOLDEN = _load_golden("trainer_launch_trace.json")
+    return _TRAINER_GOLDEN
+
+
+def test_trainer_launch_trace_golden_lists_every_case():
+    assert sorted(_trainer_golden()) == sorted(TRAINER_TRACE_CASES)
+
+
+@pytest.mark.parametrize("case", sorted(TRAINER_TRACE_CASES))
+def test_trainer_launch_trace_matches_golden(stubbed, monkeypatch, case):
+    """Every launch of the training step - entry point, arguments, stream - and every cross-stream wait between them is the one the golden's
+    commit made."""
+    want = _trainer_golden()[case]
+    got = walk_trace(case, stubbed, monkeypatch, TRAINER_TRACE_CASES)
+    for k, ((name, digest), wname, wdigest) in enumerate(zip(got, want["names"], want["hashes"])):
+        assert (name, digest) == (wname, wdigest), f"{case}: entry {k} differs: {name} (golden: {wname})"
+    assert len(got) == len(want["names"]), f"{case}: {len(got)} entries, golden {len(want['names'])}"

@@ -42,7 +42,6 @@ def build(mode):
         # VERDICT r05 item 1c, as a timing experiment (WRONG results: the forward reads weights while they are updated): AdamW of step t - 1 at the
         # HEAD of step t on the second stream, free to overlap the whole forward (no per-layer waits: the most optimistic schedule); the clip
         # norm stays at the tail, where it has to be.  What this mode gains over `full` is the ceiling of what a deferred optimizer can return.
-        from cldrd_amd import hip_ops as ops
         real_fb = tr.forward_backward
 
         def fb(b, **k):
@@ -53,7 +52,7 @@ def build(mode):
             return real_fb(b, **k)
 
         def tail(lr, step):
-            with ops.loss_scale(tr._scale_state.data_ptr() if tr.amp16 else None, tr.scale_growth_interval):
+            with tr._loss_scale():
                 tr._norm_launches()
         tr.forward_backward, tr._optimizer_launches = fb, tail
     return tr
