@@ -7,7 +7,8 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CLDRD_LIB selects another BUILD of the library for A/B runs; it must have the ABI version this table was written for (an A/B across a
-# change of ABI_VERSION uses two checkouts).  The library itself reads no environment variable
+# change of ABI_VERSION uses two checkouts) and export every entry point of SIGNATURES (load() names the first one it lacks).  The library
+# itself reads no environment variable
 LIB_PATH = os.environ.get("CLDRD_LIB") or os.path.join(_HERE, "libcldrd_hip.so")
 
 ABI_VERSION = 106         # cldrd_version() of the build SIGNATURES describes
@@ -94,6 +95,8 @@ SIGNATURES = {
     "cldrd_build_pairs": (ci, [vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
     "cldrd_cls_head_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "cldrd_curriculum_select": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cull, vp, vp, vp, vp, vp]),
+    "cldrd_pair_lookup": (ci, [vp, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp, vp]),
+    "cldrd_pair_merge": (ci, [vp, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]),
     "cldrd_write_run_file": (C.c_longlong, [C.c_char_p, vp, vp, vp, C.c_longlong, ci, ci]),
     "cldrd_py_float_repr": (ci, [C.c_double, C.c_char_p]),
     "cldrd_merge_topk": (ci, [vp, vp, ci, C.c_longlong, ci, ci, vp, vp, ci]),
@@ -123,7 +126,10 @@ def load():
         raise CldrdError(f"{LIB_PATH} has ABI version {lib.cldrd_version()}, this binding was written for {ABI_VERSION}: rebuild it "
                          "(or point CLDRD_LIB at a build of the same ABI version)")
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:          # entry points are added without a new ABI version: an older CLDRD_LIB build of the same version lacks them
+            raise CldrdError(f"{LIB_PATH} does not export {name}: it is a build of an older source tree; rebuild it "
+                             "(or point CLDRD_LIB at a build of this tree)")
         fn.restype = res
         fn.argtypes = args
     _lib = lib

@@ -1179,6 +1179,86 @@ def curriculum_select(qid, pid, score, count, n_rel, n_most_hard, most_hard_rank
     return order, keep, sel_pid, sel_score
 
 
+# ---------------------------------------------------------------------------------------------------- teacher score store
+
+PAIR_SEGMENT_MAX = 2 ** 31 - 1      # entries per segment (include/cldrd_hip.h)
+
+
+def _chk_flat(t, dtype, name):
+    """_chk for a 1-D array by ``is_contiguous`` (an empty or one-entry tensor is contiguous whatever stride it carries)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tensor must be on the GPU (cldrd_amd has no CPU path)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous 1-D tensor")
+    return t
+
+
+def _pair_segment(q, p, s, op, what):
+    _chk_flat(q, torch.int64, f"{what}_q"), _chk_flat(p, torch.int64, f"{what}_p"), _chk_flat(s, F32, f"{what}_s")
+    if not (q.shape == p.shape == s.shape) or not (p.device == s.device == q.device):
+        raise ValueError(f"{op}: {what}_q / {what}_p / {what}_s are one segment: one length, one device")
+    if q.numel() > PAIR_SEGMENT_MAX:
+        raise ValueError(f"{op}: a segment holds at most 2^31 - 1 entries")
+
+
+def pair_lookup(seg_q, seg_p, seg_s, qid, starts, pid, score_out=None, hit=None):
+    """cldrd_pair_lookup (include/cldrd_hip.h): the pairs of the CSR batch qid int64 [nq] / starts int64 [nq + 1] / pid int64 [total]
+    searched in the segment (seg_q, seg_p, seg_s) -> (score_out fp32 [total], hit uint8 [total]).  A found pair gets the stored score bits
+    and hit 1, a missed one leaves both as they were: pass the outputs of one call to the next to search several segments (fresh zeroed ones
+    when not given).  Everything in HBM."""
+    _pair_segment(seg_q, seg_p, seg_s, "pair_lookup", "seg")
+    _chk_flat(qid, torch.int64, "qid"), _chk_flat(starts, torch.int64, "starts"), _chk_flat(pid, torch.int64, "pid")
+    nq, total = qid.shape[0], pid.shape[0]
+    if starts.shape[0] != nq + 1:
+        raise ValueError("pair_lookup: qid [nq], starts [nq + 1], pid [total]")
+    if score_out is None:
+        score_out = torch.zeros(total, dtype=F32, device=pid.device)
+    if hit is None:
+        hit = torch.zeros(total, dtype=torch.uint8, device=pid.device)
+    _chk_flat(score_out, F32, "score_out"), _chk_flat(hit, torch.uint8, "hit")
+    if score_out.shape[0] != total or hit.shape[0] != total:
+        raise ValueError(f"pair_lookup: score_out / hit must be [{total}]")
+    for t, name in ((seg_q, "seg"), (qid, "qid"), (starts, "starts"), (score_out, "score_out"), (hit, "hit")):
+        if t.device != pid.device:
+            raise ValueError(f"pair_lookup: {name} is on {t.device}, pid on {pid.device}")
+    if nq == 0 or total == 0 or seg_q.shape[0] == 0:
+        return score_out, hit
+    with torch.cuda.device(pid.device):
+        call("cldrd_pair_lookup", _p(seg_q), _p(seg_p), _p(seg_s), seg_q.shape[0], _p(qid), _p(starts), _p(pid), nq, total, _p(score_out),
+             _p(hit), _stream())
+    return score_out, hit
+
+
+def pair_merge(a_q, a_p, a_s, b_q, b_p, b_s):
+    """cldrd_pair_merge (include/cldrd_hip.h): two segments with no key in common -> the merged segment (q, p, s) of na + nb entries, in
+    HBM.  ``ValueError`` when a key occurs in both (the flag is read here: one synchronisation).  An empty side: a copy of the other,
+    no launch."""
+    _pair_segment(a_q, a_p, a_s, "pair_merge", "a"), _pair_segment(b_q, b_p, b_s, "pair_merge", "b")
+    if a_q.device != b_q.device:
+        raise ValueError(f"pair_merge: a is on {a_q.device}, b on {b_q.device}")
+    na, nb = a_q.shape[0], b_q.shape[0]
+    if na + nb > PAIR_SEGMENT_MAX:
+        raise ValueError("pair_merge: a segment holds at most 2^31 - 1 entries (na + nb)")
+    if na == 0 or nb == 0:
+        q, p, s = (b_q, b_p, b_s) if na == 0 else (a_q, a_p, a_s)
+        return q.clone(), p.clone(), s.clone()
+    dev = a_q.device
+    out_q = torch.empty(na + nb, dtype=torch.int64, device=dev)
+    out_p = torch.empty(na + nb, dtype=torch.int64, device=dev)
+    out_s = torch.empty(na + nb, dtype=F32, device=dev)
+    dup = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("cldrd_pair_merge", _p(a_q), _p(a_p), _p(a_s), na, _p(b_q), _p(b_p), _p(b_s), nb, _p(out_q), _p(out_p), _p(out_s), _p(dup),
+             _stream())
+    if int(dup.item()):
+        raise ValueError("pair_merge: a key occurs in both inputs")
+    return out_q, out_p, out_s
+
+
 # ---------------------------------------------------------------------------------------------------- merge of shard lists
 
 def merge_topk_host(shard_D, shard_I, k, nthreads=0):

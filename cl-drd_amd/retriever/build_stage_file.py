@@ -6,7 +6,11 @@ other run files (100.6 M lines each at 503 k queries x top-200).
         --index_path IDX [--use_float16] --queries_path Q.tsv --collection_path C.tsv [--query_max_len 30] [--top_k 200] \\
         --teacher_name_or_path DIR [--teacher_tokenizer_name_or_path TOK] [--teacher_max_len 256] [--teacher_batch_size 2048] \\
         [--token_cache_dir DIR] --label_mode M [--most_hard_ranks LO:HI] [--semi_hard_ranks LO:HI] [--n_most_hard N] [--seed S] \\
-        [--with_scores] --output_path train.json [--student_run_path RUN] [--teacher_run_path RUN]
+        [--with_scores] --output_path train.json [--student_run_path RUN] [--teacher_run_path RUN] \\
+        [--score_store DIR [--score_store_flush_pairs N]]
+
+``--score_store DIR``: teacher scores are taken from the store ``DIR`` (``retriever.score_store``, shared with ``rerank_top_passages``) where
+it holds the pair; only the others are scored, and added to it.  Every file written is the same, byte for byte.
 
 The search's ids and the teacher's scores stay dense ``[queries, top_k]`` arrays in HBM from the search to the selection
 (``dataset.curriculum_file.select_examples_device``, one kernel launch); the host sees the ids once (to find the passages' token-cache rows,
@@ -59,6 +63,8 @@ def get_args(argv=None):
     ap.add_argument("--output_path", required=True)
     ap.add_argument("--student_run_path", default="", help="also write the student's run (what retrieve_top_passages writes)")
     ap.add_argument("--teacher_run_path", default="", help="also write the teacher-ranked run (what rerank_top_passages writes)")
+    from .score_store import add_arguments
+    add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -104,7 +110,7 @@ def main(args):
     from ..models.cross_encoder import CrossEncoder
     from ..models.nway_dual_encoder import NwayDualEncoder
     from .index_text import load_checkpoint_into
-    from .rerank_top_passages import score_pairs, write_ranked_run
+    from .rerank_top_passages import score_pairs, score_pairs_stored, write_ranked_run
     from .retrieval_utils import cap_host_threads, convert_index_to_gpu, get_embeddings_from_scratch, read_index
     from .retrieve_top_passages import write_run_file
     from transformers import AutoTokenizer
@@ -165,7 +171,17 @@ def main(args):
         q_rows = np.repeat(cache_rows(q_cache.keys, file_qids, "query"), k)
         p_rows = cache_rows(p_cache.keys, pid_h, "passage").reshape(-1)
         lap("map_rows_s")
-        score = score_pairs(teacher, q_cache, p_cache, q_rows, p_rows, args.teacher_max_len, args.teacher_batch_size).view(nq, k)
+        if args.score_store:
+            from .score_store import TeacherScoreStore, teacher_identity
+            with TeacherScoreStore(args.score_store, teacher_identity(teacher, args.teacher_max_len, False, q_cache, p_cache), dev) as store:
+                score, st = score_pairs_stored(store, teacher, q_cache, p_cache, torch.from_numpy(file_qids).to(dev),
+                                               torch.arange(nq + 1, dtype=torch.int64, device=dev) * k, pid.view(-1), q_rows, p_rows,
+                                               args.teacher_max_len, args.teacher_batch_size, args.score_store_flush_pairs)
+            score = score.view(nq, k)
+            timings["score_store_lookup_s"], timings["score_store_append_s"] = st["lookup_s"], st["append_s"]      # (parts of teacher_score_s)
+            print(f"score store {args.score_store}: {st['pairs']} pairs, {st['hits']} hits, {st['scored']} scored, {st['segments']} segments")
+        else:
+            score = score_pairs(teacher, q_cache, p_cache, q_rows, p_rows, args.teacher_max_len, args.teacher_batch_size).view(nq, k)
         del q_rows, p_rows
     del teacher
     lap("teacher_score_s")

@@ -3,7 +3,10 @@ training data: every training query's top-k student candidates re-scored by the 
 
     python -m cldrd_amd.retriever.rerank_top_passages --run_path RUN --queries_path Q.tsv --collection_path C.tsv \\
         --model_name_or_path DIR --tokenizer_name_or_path TOK --output_path OUT [--max_len 256] [--top_k K] [--batch_size B]
-        [--token_cache_dir DIR]
+        [--token_cache_dir DIR] [--score_store DIR [--score_store_flush_pairs N]]
+
+``--score_store DIR`` (teacher mode only): pairs that the teacher score store ``DIR`` (``retriever.score_store``) holds are not scored again,
+the others are scored and added to it - after every N of them, so a killed job has lost at most N; the output file is the same, byte for byte.
 
 ``--dual_encoder [--resume CKPT] [--share_weights] [--query_max_len 30] [--passage_max_len 256]`` is the student mode: the same run, files,
 ``--top_k``, ``--token_cache_dir``, ``--fp32_encode`` and output rules, scored by the dual encoder through ``evaluation.DevPool``.
@@ -54,7 +57,11 @@ def get_args(argv=None):
     ap.add_argument("--share_weights", action="store_true", default=False)
     ap.add_argument("--query_max_len", type=int, default=30)
     ap.add_argument("--passage_max_len", type=int, default=256)
+    from .score_store import add_arguments
+    add_arguments(ap)
     args = ap.parse_args(argv)
+    if args.score_store and args.dual_encoder:
+        ap.error("--score_store keeps teacher scores: it cannot be used with --dual_encoder (a student's scores change with every checkpoint)")
     if args.batch_size is None:
         args.batch_size = 512 if args.dual_encoder else 2048
     return args
@@ -108,10 +115,12 @@ def length_batches(lengths, batch_size):
     return [order[i:i + batch_size] for i in range(0, order.shape[0], batch_size)]
 
 
-def score_pairs(model, q_cache, p_cache, q_rows, p_rows, max_len, batch_size, fp32=False):
+def score_pairs(model, q_cache, p_cache, q_rows, p_rows, max_len, batch_size, fp32=False, on_batch=None):
     """Teacher scores of the pairs (query cache row ``q_rows[i]``, passage cache row ``p_rows[i]``; host int64 arrays) as ONE fp32 device
     tensor [n]: scored in batches of similar pair length (:func:`length_batches`), each batch's scores scattered to the pairs' positions on
-    the device - nothing comes to the host per batch.  The batching of this program and of ``retriever.build_stage_file``."""
+    the device - nothing comes to the host per batch.  The batching of this program and of ``retriever.build_stage_file``.
+    ``on_batch`` (a test hook): called on the host with the batch's pair count after each batch; a test stops a run between two batches by
+    raising from it."""
     q_rows, p_rows = np.asarray(q_rows, dtype=np.int64).reshape(-1), np.asarray(p_rows, dtype=np.int64).reshape(-1)
     _, _, lengths, _ = pair_lengths(np.asarray(q_cache.lens)[q_rows] - 2, np.asarray(p_cache.lens)[p_rows] - 2, max_len)
     scores = None
@@ -120,6 +129,8 @@ def score_pairs(model, q_cache, p_cache, q_rows, p_rows, max_len, batch_size, fp
         if scores is None:
             scores = torch.empty(q_rows.shape[0], dtype=torch.float32, device=s.device)
         scores.index_copy_(0, torch.from_numpy(b).to(s.device), s)
+        if on_batch is not None:
+            on_batch(int(b.shape[0]))
     return scores if scores is not None else torch.empty(0, dtype=torch.float32, device=next(model.parameters()).device)
 
 
@@ -149,8 +160,25 @@ def main_dual_encoder(args):
     return total
 
 
-def main(args):
+def score_pairs_stored(store, model, q_cache, p_cache, row_qid, starts, pid, q_rows, p_rows, max_len, batch_size, flush_pairs, fp32=False,
+                       on_batch=None):
+    """:func:`score_pairs` through a ``score_store.TeacherScoreStore``: the pairs of the CSR batch (``row_qid`` int64 [nq], ``starts`` int64
+    [nq + 1], ``pid`` int64 [n], on the device; ``q_rows`` / ``p_rows`` their cache rows, host arrays) that the store holds are not scored,
+    the others are scored in global pair-length order and added to it.  Returns (scores fp32 [n] on the device, stats)."""
+    from .score_store import score_through_store
+    q_rows, p_rows = np.asarray(q_rows, dtype=np.int64).reshape(-1), np.asarray(p_rows, dtype=np.int64).reshape(-1)
+    _, _, lengths, _ = pair_lengths(np.asarray(q_cache.lens)[q_rows] - 2, np.asarray(p_cache.lens)[p_rows] - 2, max_len)
+
+    def score_chunk(at):
+        return score_pairs(model, q_cache, p_cache, q_rows[at], p_rows[at], max_len, batch_size, fp32=fp32, on_batch=on_batch)
+    return score_through_store(store, row_qid, starts, pid, lengths, score_chunk, flush_pairs)
+
+
+def main(args, on_batch=None):
+    """``on_batch`` (a test hook): handed to :func:`score_pairs`."""
     if getattr(args, "dual_encoder", False):
+        if getattr(args, "score_store", ""):
+            raise ValueError("--score_store cannot be used with --dual_encoder")
         return main_dual_encoder(args)
     if args.max_len > 256 or args.batch_size < 1:
         raise ValueError("--max_len is at most 256, --batch_size at least 1")
@@ -173,8 +201,19 @@ def main(args):
             p_rows = np.array([p_row[int(p)] for p in up], dtype=np.int64)[p_inv.reshape(-1)]
         except KeyError as exc:
             raise KeyError(f"id {exc.args[0]} of {args.run_path} is not in the query / passage table") from exc
-        scores = score_pairs(model, q_cache, p_cache, q_rows, p_rows, args.max_len, args.batch_size,
-                             fp32=bool(getattr(args, "fp32_encode", False))).cpu().numpy()
+        fp32 = bool(getattr(args, "fp32_encode", False))
+        if getattr(args, "score_store", ""):
+            from .score_store import TeacherScoreStore, teacher_identity
+            dev = torch.device("cuda", torch.cuda.current_device())
+            with TeacherScoreStore(args.score_store, teacher_identity(model, args.max_len, fp32, q_cache, p_cache), dev) as store:
+                scores, st = score_pairs_stored(store, model, q_cache, p_cache, torch.from_numpy(qids[starts[:-1]]).to(dev),
+                                                torch.from_numpy(starts).to(dev), torch.from_numpy(pids).to(dev), q_rows, p_rows,
+                                                args.max_len, args.batch_size, args.score_store_flush_pairs, fp32=fp32, on_batch=on_batch)
+                scores = scores.cpu().numpy()
+            print(f"score store {args.score_store}: {st['pairs']} pairs, {st['hits']} hits, {st['scored']} scored, {st['segments']} segments")
+        else:
+            scores = score_pairs(model, q_cache, p_cache, q_rows, p_rows, args.max_len, args.batch_size, fp32=fp32,
+                                 on_batch=on_batch).cpu().numpy()
     total = write_ranked_run(args.output_path, qids, pids, group, starts, scores)
     print(f"re-scored {total} pairs of {starts.shape[0] - 1} queries")
     return total

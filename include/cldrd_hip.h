@@ -431,6 +431,22 @@ int cldrd_curriculum_select(const long long* qid, const long long* pid, const fl
                             int n_rel, int n_most_hard, int most_lo, int most_hi, int n_semi_hard, int semi_lo, int semi_hi,
                             unsigned long long seed, int* order, int* keep, long long* sel_pid, float* sel_score, void* stream);
 
+/* ---- teacher score store (csrc/pairstore.hip; retriever/score_store.py) --------------------------------------------------------------
+ * A segment is three parallel device arrays, q int64 / p int64 / s fp32, of 1 .. 2^31 - 1 entries strictly ascending in the key (q, p):
+ * lexicographic, q major, signed 64-bit compares.
+ * cldrd_pair_lookup: the pairs of a CSR batch - qid int64 [nq], starts int64 [nq + 1] (row r's pairs are starts[r] .. starts[r + 1],
+ *   clamped to 0 .. total), pid int64 [total] - searched in ONE segment, one workgroup per row (rows of any length, 0 included).  A pair
+ *   found at entry j gets score_out[i] = seg_s[j] (the stored bits) and hit[i] = 1 (uint8); a pair not found leaves both untouched, so
+ *   calls over several segments accumulate.  nq >= 1 (refused otherwise).
+ * cldrd_pair_merge: two segments with no key in common, na >= 1 and nb >= 1 entries, na + nb <= 2^31 - 1, merged into out_* of exactly
+ *   na + nb entries.  *dup_flag (int32, device, zeroed by the caller) is set to 1 when a key occurs in both inputs (the output then
+ *   holds it twice and is not a segment). */
+int cldrd_pair_lookup(const long long* seg_q, const long long* seg_p, const float* seg_s, long long n, const long long* qid,
+                      const long long* starts, const long long* pid, long long nq, long long total, float* score_out, unsigned char* hit,
+                      void* stream);
+int cldrd_pair_merge(const long long* a_q, const long long* a_p, const float* a_s, long long na, const long long* b_q, const long long* b_p,
+                     const float* b_s, long long nb, long long* out_q, long long* out_p, float* out_s, int* dup_flag, void* stream);
+
 /* ---- run file (retriever/retrieve_top_passages.py:98-105), HOST side: no GPU work -----------------------------------------
  * Writes `qid\tdocid\trank\tscore\n` for nq queries x k hits (rank 1..k) to `path`; the score text is Python's repr of the fp32
  * value widened to a double, which is what the reference's f-string prints.  All pointers are HOST pointers.  Formatted by nthreads
