@@ -13,6 +13,7 @@
 // query-on-lane (dQ accumulates over all key blocks).  Probabilities and dS are rounded to bf16 only as
 // MFMA operands; softmax statistics, LSE and delta are fp32.
 #include "common.h"
+#include "../../include/cldrd_hip.h"      // enum cldrd_fmt16
 #include <cstdio>
 #include <type_traits>
 
@@ -1304,32 +1305,32 @@ extern "C" long long cldrd_attention_bits_words(int nseq, int L, int H, float dr
 // ctx_f16_copy (optional, bf16 pass only): the same context in fp16 - the operand of an fp16 out-projection GEMM; ctx itself may then be null
 // (an evaluation forward keeps no bf16 tape).
 extern "C" int cldrd_attention_fwd(const void* qkv, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile,
-                                   void* ctx, float* lse, int nseq, int L, int H, float dropout_p, unsigned long long seed, int io_f16,
+                                   void* ctx, float* lse, int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt,
                                    void* drop_bits_out, void* ctx_f16_copy, void* stream) {
     if (attn_check("attention_fwd", mask, cu_rows, seq_list, n_list, Ltile, nseq, L, H)) return 1;
     const int n = seq_list ? n_list : nseq;          // sequences of THIS launch (items = n x H)
     const int Lt = seq_list ? Ltile : L;             // rows a sequence of this launch can have: the kernels' tile height
     CLDRD_CHECK(ctx != nullptr || ctx_f16_copy != nullptr, "attention_fwd: no output");
-    CLDRD_CHECK(!(io_f16 && (ctx_f16_copy != nullptr || ctx == nullptr)), "attention_fwd: the fp16 pass writes ctx only");
-    CLDRD_CHECK(io_f16 == 0 || io_f16 == 1 || io_f16 == 5, "attention_fwd: io_f16 is 0 (bf16), 1 (fp16, L <= 128, no keep bits) or 5 (fp16, every kernel of the bf16 path)");
-    CLDRD_CHECK(io_f16 != 1 || Lt <= 128, "attention_fwd: the fp16 forward handles L <= 128");
+    CLDRD_CHECK(!(fmt != CLDRD_FMT_BF16 && (ctx_f16_copy != nullptr || ctx == nullptr)), "attention_fwd: the fp16 pass writes ctx only");
+    CLDRD_CHECK(fmt == CLDRD_FMT_BF16 || fmt == CLDRD_FMT_F16 || fmt == CLDRD_FMT_F16_TAPE, "attention_fwd: fmt is 0 (bf16), 1 (fp16, L <= 128, no keep bits) or 5 (fp16, every kernel of the bf16 path)");
+    CLDRD_CHECK(fmt != CLDRD_FMT_F16 || Lt <= 128, "attention_fwd: the fp16 forward handles L <= 128");
     const AttnFwdArgs a = {(const bf16_t*)qkv, (const int64_t*)mask, cu_rows, seq_list, (bf16_t*)ctx, lse,
                            n, L, H, 0.125f /* 1 / sqrt(64) */, dropout_p, seed,
                            (uint32_t*)drop_bits_out, (bf16_t*)ctx_f16_copy, (hipStream_t)stream};
     const int nkb = (Lt + 31) / 32;
-    if (io_f16 == 5)            // fp16 activations through the whole kernel family (round 4: the all-fp16 training mode)
+    if (fmt == CLDRD_FMT_F16_TAPE)            // fp16 activations through the whole kernel family (round 4: the all-fp16 training mode)
         return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_fwd<decltype(k)::value, decltype(d)::value, true>(a); }); });
-    if (io_f16 == 1)            // fp16 activations, evaluation passes: the all-scores-in-registers kernel only
+    if (fmt == CLDRD_FMT_F16)            // fp16 activations, evaluation passes: the all-scores-in-registers kernel only
         return with_nkb<4>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_fwd_f16<decltype(k)::value, decltype(d)::value>(a); }); });
     return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_fwd<decltype(k)::value, decltype(d)::value, false>(a); }); });
 }
 
 // drop_bits (optional): what cldrd_attention_fwd left for the same (nseq, L, H, dropout_p, seed); null: the mask is re-hashed.
-// io_f16 != 0: q / k / v, ctx, dctx and dqkv are fp16 (the all-fp16 training mode: gradients carry the loss scale).
+// fmt != CLDRD_FMT_BF16: q / k / v, ctx, dctx and dqkv are fp16 (the all-fp16 training mode: gradients carry the loss scale).
 // Packed batch: rows of dqkv that do not exist in the packed layout (padding) are not written - in the padded layout they receive zeros.
 extern "C" int cldrd_attention_bwd(const void* qkv, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile,
                                    const void* ctx, const void* dctx, const float* lse, void* dqkv, int nseq, int L, int H, float dropout_p,
-                                   unsigned long long seed, int io_f16, const void* drop_bits, void* stream) {
+                                   unsigned long long seed, int fmt, const void* drop_bits, void* stream) {
     if (attn_check("attention_bwd", mask, cu_rows, seq_list, n_list, Ltile, nseq, L, H)) return 1;
     const int n = seq_list ? n_list : nseq, Lt = seq_list ? Ltile : L;          // as in cldrd_attention_fwd
     CLDRD_CHECK(lse != nullptr, "attention_bwd: lse is required");
@@ -1337,7 +1338,7 @@ extern "C" int cldrd_attention_bwd(const void* qkv, const long long* mask, const
                            (bf16_t*)dqkv, n, L, H, 0.125f, dropout_p, seed,
                            (const uint32_t*)drop_bits, (hipStream_t)stream};
     const int nkb = (Lt + 31) / 32;
-    if (io_f16)
+    if (fmt != CLDRD_FMT_BF16)
         return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_bwd<decltype(k)::value, decltype(d)::value, true>(a); }); });
     return with_nkb<8>(nkb, [&](auto k) { return with_drop(dropout_p, [&](auto d) { return launch_bwd<decltype(k)::value, decltype(d)::value, false>(a); }); });
 }
@@ -1546,13 +1547,13 @@ __global__ __launch_bounds__(256) void add_rows_strided_kernel(void* __restrict_
 // qc: 16-bit [nseq, H*64] (CLS queries); kv: [rows, 2*H*64] = K | V (padded, or packed with cu_rows: include/cldrd_hip.h); ctx: [nseq, H*64];
 // probs: fp32 [nseq, H, L] in either layout
 extern "C" int cldrd_attention_cls_fwd(const void* qc, const void* kv, const long long* mask, const int* cu_rows, void* ctx, float* probs,
-                                       int nseq, int L, int H, float dropout_p, unsigned long long seed, int io_f16, void* ctx_f16_copy,
+                                       int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* ctx_f16_copy,
                                        void* stream) {
     if (attn_check("attention_cls_fwd", mask, cu_rows, nullptr, 0, 0, nseq, L, H)) return 1;
     CLDRD_CHECK(probs != nullptr, "attention_cls_fwd: need a probs buffer");
-    CLDRD_CHECK((ctx != nullptr || ctx_f16_copy != nullptr) && !(io_f16 && (ctx_f16_copy != nullptr || ctx == nullptr)), "attention_cls_fwd: outputs");
+    CLDRD_CHECK((ctx != nullptr || ctx_f16_copy != nullptr) && !(fmt != CLDRD_FMT_BF16 && (ctx_f16_copy != nullptr || ctx == nullptr)), "attention_cls_fwd: outputs");
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
-    if (io_f16)
+    if (fmt != CLDRD_FMT_BF16)
         hipLaunchKernelGGL(attn_cls_fwd_kernel<true>, dim3(nseq * H), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)qc, (const bf16_t*)kv,
                            (const int64_t*)mask, (bf16_t*)ctx, probs, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), (bf16_t*)nullptr, cu_rows);
     else
@@ -1564,10 +1565,10 @@ extern "C" int cldrd_attention_cls_fwd(const void* qc, const void* kv, const lon
 
 // dqc: [nseq, H*64]; dkv: [rows, 2*H*64] in the layout of kv (every row written)
 extern "C" int cldrd_attention_cls_bwd(const void* qc, const void* kv, const int* cu_rows, const float* probs, const void* dctx, void* dqc,
-                                       void* dkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, int io_f16, void* stream) {
+                                       void* dkv, int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* stream) {
     if (attn_check("attention_cls_bwd", nullptr, cu_rows, nullptr, 0, 0, nseq, L, H)) return 1;
     const uint32_t th = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
-    if (io_f16)
+    if (fmt != CLDRD_FMT_BF16)
         hipLaunchKernelGGL(attn_cls_bwd_kernel<true>, dim3(nseq * H), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)qc, (const bf16_t*)kv, probs,
                            (const bf16_t*)dctx, (bf16_t*)dqc, (bf16_t*)dkv, L, H, 0.125f, th, 1.0f / (1.0f - dropout_p), seed_arg(seed), cu_rows);
     else

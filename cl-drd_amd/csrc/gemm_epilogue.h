@@ -1,30 +1,38 @@
 // Shared by the NT GEMM kernels: argument block and the fused epilogue.
 #pragma once
 #include "common.h"
+#include "../../include/cldrd_hip.h"
+#include <type_traits>
 
+// The 16-bit format code of the C ABI (`fmt` of cldrd_gemm_nt16 and the attention entry points): enum cldrd_fmt16 of the public header, which
+// this file includes - one set of names on both sides of the ABI.  Bit 0: fp16 operands; bit 1: a 16-bit C is bf16 all the same; bit 2: fp16 tape.
+constexpr int FMT_C_BF16_BIT = CLDRD_FMT_F16_C_BF16 & ~CLDRD_FMT_F16, FMT_TAPE_BIT = CLDRD_FMT_F16_TAPE & ~CLDRD_FMT_F16;
+static_assert(CLDRD_FMT_BF16 == 0 && CLDRD_FMT_F16 == 1 && FMT_C_BF16_BIT == 2 && FMT_TAPE_BIT == 4, "enum cldrd_fmt16 is a bit set over CLDRD_FMT_F16");
+
+// Every field has a default: an entry point assigns what it means and nothing else.
 struct GemmNtArgs {
-    const bf16_t* A; const bf16_t* B; void* C;
-    int M, N, K, lda, ldb, ldc;
-    const float* bias;            // [N] or null
-    const void* residual;         // [M, ldr] or null, added last; bf16, or fp32 when res_f32 (the fp32 residual stream)
-    int ldr;
+    const bf16_t* A = nullptr; const bf16_t* B = nullptr; void* C = nullptr;
+    int M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;
+    const float* bias = nullptr;            // [N] or null
+    const void* residual = nullptr;         // [M, ldr] or null, added last; bf16, or fp32 when res_f32 (the fp32 residual stream)
+    int ldr = 0;
     int res_f32 = 0;
     // fp32 residual given as a LayerNorm still to be applied: residual[m][n] holds the pre-LN sum s and the value added is
     // (s - ln_mean[m]) * ln_rstd[m] * ln_gamma[n] + ln_beta[n] - the LayerNorm kernel then need not write its fp32 output copy at all
     // (100 MB per LayerNorm at cfg2; same bytes read here).  All four or none; only with res_f32.
     const float* ln_mean = nullptr; const float* ln_rstd = nullptr; const float* ln_gamma = nullptr; const float* ln_beta = nullptr;
-    bf16_t* preact;               // [M, ldc] or null: (alpha*acc + bias) before the activation
-    const bf16_t* gelu_pre;       // [M, ldc] or null: multiply by gelu'(gelu_pre)
-    int act;                      // bit 0: erf-GELU; bit 1 (derivative form): `preact` receives gelu'(pre-activation) instead of the
+    bf16_t* preact = nullptr;               // [M, ldc] or null: (alpha*acc + bias) before the activation
+    const bf16_t* gelu_pre = nullptr;       // [M, ldc] or null: multiply by gelu'(gelu_pre)
+    int act = 0;                  // bit 0: erf-GELU; bit 1 (derivative form): `preact` receives gelu'(pre-activation) instead of the
                                   // pre-activation, and `gelu_pre` already holds that derivative (the epilogue multiplies, nothing else)
-    float alpha;
-    uint32_t drop_thresh;         // 0 = no dropout
-    float drop_scale;
-    uint64_t seed;
+    float alpha = 1.0f;
+    uint32_t drop_thresh = 0;     // 0 = no dropout
+    float drop_scale = 1.0f;
+    uint64_t seed = 0;
     const unsigned long long* seed_base = nullptr;      // SeedArg of common.h: added to `seed` on the device when set
-    int out_f32;
+    int out_f32 = 0;
     // EPI_FILTER (top-k scan): keep C[m][n] >= thr[m] as candidate (n, score) of query m
-    const float* thr; int* counts; int* cand_rows; float* cand_scores; int cap;
+    const float* thr = nullptr; int* counts = nullptr; int* cand_rows = nullptr; float* cand_scores = nullptr; int cap = 0;
     int in_f16 = 0;               // the operands (and a 16-bit C) are fp16, not bf16: top-k scan, high-precision forward flavours
     int c_bf16 = 0;               // with in_f16: a 16-bit C is bf16 all the same (fp16 operands, bf16 result: the QKV projection, whose
                                   // consumers - attention forward and backward - are bf16 kernels)
@@ -33,6 +41,8 @@ struct GemmNtArgs {
     int gn = 0;                   // ring kernel: N tiles are walked in groups of gn inside an XCD's range (0: row-major)
     int tape_f16 = 0;             // with in_f16 (the all-fp16 training mode): `preact` is written and `gelu_pre` is read as fp16, not bf16
 };
+
+constexpr int NT_RING_MIN_M = 1024;       // from this many rows on the ring kernel is tried and no K range is split (the grid fills the chip)
 
 // compile-time epilogue flavours (each GEMM kernel is instantiated per flavour so the 16x-unrolled epilogue carries
 // only the code it needs); EPI_GENERIC reads every switch from GemmNtArgs at run time.
@@ -76,6 +86,63 @@ static inline int epi_flavour(const GemmNtArgs& a) {
            (((a.act & 2) && (a.preact || a.gelu_pre)) ? EPI_DGELU : 0) |
            (a.drop_thresh ? EPI_DROPOUT : 0) | (a.residual ? EPI_RESIDUAL : 0) | (a.out_f32 ? EPI_F32 : 0) |
            ((a.residual && a.res_f32) ? EPI_RES32 : 0) | ((a.residual && a.res_f32 && a.ln_mean) ? EPI_RESLN : 0);
+}
+
+// ---- which flavours are compiled: the ops of the encoder by name, and one list per kernel ----
+enum : int {
+    OP_PLAIN = 0,                                                  // data gradient (dX = dY . W), 16-bit out
+    OP_LINEAR = EPI_BIAS,                                          // QKV projection (fp16 form: fp16 operands, bf16 q / k / v through c_bf16)
+    OP_FFN1 = EPI_BIAS | EPI_GELU,                                 // FFN1 forward of an evaluation pass: no tape
+    OP_FFN1_TAPE_X = EPI_BIAS | EPI_PREACT | EPI_GELU,             // FFN1 forward, the tape keeps the pre-activation x
+    OP_FFN1_TAPE = EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU,   // FFN1 forward, the tape keeps gelu'(x): the encoder's training form
+    OP_DGRAD_GELU = EPI_GELUGRAD | EPI_DGELU,                      // data gradient through GELU: multiply by the taped gelu'(x)
+    OP_DGRAD_GELU_X = EPI_GELUGRAD,                                // the same from a taped x
+    OP_OUT16 = EPI_BIAS | EPI_RESIDUAL,                            // out-projection / FFN2 on a bf16 residual stream
+    OP_OUT16_DROP = OP_OUT16 | EPI_DROPOUT,
+    OP_DGRAD_ADD16 = EPI_RESIDUAL,                                 // data gradient added to a bf16 gradient
+    OP_PLAIN_F32 = EPI_F32,                                        // data gradient, fp32 out
+    OP_DGRAD_ADD32 = EPI_RESIDUAL | EPI_RES32 | EPI_F32,           // data gradient of the fp32 gradient stream: the LayerNorm backward's fp32 dx in, fp32 sum out
+    OP_OUT32 = EPI_BIAS | OP_DGRAD_ADD32,                          // out-projection of the first layer: its residual is the embedding block's fp32
+    OP_OUT32_DROP = OP_OUT32 | EPI_DROPOUT,                        //   output, no LayerNorm still to apply
+    OP_OUT32_LN = OP_OUT32 | EPI_RESLN,                            // out-projection / FFN2 on the fp32 residual stream, LayerNorm on the fly
+    OP_OUT32_LN_DROP = OP_OUT32_LN | EPI_DROPOUT,
+};
+
+template <int... E> struct EpiList {};
+template <int... A, int... B> constexpr EpiList<A..., B...> operator+(EpiList<A...>, EpiList<B...>) { return {}; }
+template <int... E> constexpr EpiList<(E | EPI_F16IN)...> epi_f16(EpiList<E...>) { return {}; }
+
+// bf16 operands.  Anything else runs on the EPI_GENERIC instantiation of the same kernel (run-time switches).
+using EpiBf16Small = EpiList<OP_PLAIN, OP_LINEAR, OP_FFN1_TAPE_X, OP_FFN1_TAPE, OP_DGRAD_GELU, OP_OUT16, OP_OUT16_DROP, OP_DGRAD_GELU_X, OP_DGRAD_ADD16,
+                             OP_PLAIN_F32, OP_DGRAD_ADD32, OP_OUT32, OP_OUT32_DROP, OP_OUT32_LN, OP_OUT32_LN_DROP>;
+// The one difference: OP_FFN1, the tape-less FFN1 of the evaluation passes, is compiled for the ring only.  In the 128 x 128 kernel: not built,
+// never requested by the encoder (below 1024 rows FFN1's K goes to the 64 x 64 kernel, which has run-time switches only; EPI_GENERIC serves the rest).
+using EpiBf16Ring = decltype(EpiBf16Small{} + EpiList<OP_FFN1>{});
+// fp16 operands: the ops the fp16 mode runs, forward (evaluation and training) and the all-fp16 training mode's data gradients.  There is no
+// generic fp16 instantiation: what is not listed here is refused.
+using EpiF16Ring = decltype(epi_f16(EpiList<OP_LINEAR, OP_FFN1_TAPE, OP_FFN1, OP_OUT32, OP_OUT32_DROP, OP_OUT32_LN, OP_OUT32_LN_DROP,
+                                            OP_PLAIN, OP_DGRAD_GELU, OP_PLAIN_F32>{}));
+// The one difference: OP_DGRAD_ADD32 on fp16 operands is compiled for the 128 x 128 kernel only (the all-fp16 mode's data gradients into the fp32
+// gradient stream at small M).  In the ring: not built, never requested by the encoder; the ring declines it and the 128 x 128 kernel runs it.
+using EpiF16Small = decltype(EpiF16Ring{} + epi_f16(EpiList<OP_DGRAD_ADD32>{}));
+
+// launch(std::integral_constant<int, E>{}) for the E of the list that equals `flavour`; otherwise() if none does.
+template <int... E, class Launch, class Otherwise>
+int epi_dispatch(EpiList<E...>, int flavour, Launch&& launch, Otherwise&& otherwise) {
+    int rc = 0;
+    const bool hit = (... || (flavour == E && ((rc = launch(std::integral_constant<int, E>{})), true)));
+    return hit ? rc : otherwise();
+}
+
+// Launch of a GemmNtArgs kernel with `lds` bytes of dynamic LDS (more than a kernel gets unasked).  The attribute is set when THIS instantiation
+// is launched for the first time: once per kernel, never per launch (a training step makes ~230 of them).
+template <auto Kernel>
+int launch_lds(int nblk, int nthr, int lds, const GemmNtArgs& a, hipStream_t st) {
+    static const hipError_t attr_set = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)attr_set;
+    hipLaunchKernelGGL(Kernel, dim3(nblk), dim3(nthr), lds, st, a);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
 }
 
 __device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {

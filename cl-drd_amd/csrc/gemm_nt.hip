@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt64_kernel(GemmNtArgs p) {
 // and 4-5 slabs to add instead of the 128 x 128 kernel's 12).
 static int nt64_splits(int M, int N, int K) {
     if (g_cldrd_tune_nt64 == 0 || g_cldrd_tune_splitk != 0) return 0;          // a forced split count means the 128 x 128 kernel (tests)
-    if (K % BK != 0 || M >= 1024 || N % 8 != 0) return 0;
+    if (K % BK != 0 || M >= NT_RING_MIN_M || N % 8 != 0) return 0;
     const long long tiles = (long long)((M + SB - 1) / SB) * ((N + SB - 1) / SB);
     if (tiles > 256) return 0;
     if (K <= 1024) return 1;
@@ -306,22 +306,47 @@ static int splitk_choice(int M, int N, int K) {
     const int force = g_cldrd_tune_splitk;              // 1: never split, n > 1: n splits (cldrd_set_tuning: tests flip it in-process)
     if (force == 1) return 1;
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = K / BK;
-    if (M >= 1024 || tiles >= 128 || nk < 8) return 1;
+    if (M >= NT_RING_MIN_M || tiles >= 128 || nk < 8) return 1;
     int ks = 384 / tiles;
     if (ks > nk / 4) ks = nk / 4;
     if (force > 1) ks = force < nk ? force : nk;
     return ks < 2 ? 1 : ks;
 }
 
+// The launch plan of a shape: the one place that chooses among 64 x 64 (one launch or split), 128 x 128 split, and one pass (the ring where it
+// takes the shape, else 128 x 128).  Both the workspace query and the dispatch ask here.
+enum NtFamily { NT_TILE64, NT_TILE128, NT_LARGE_M };       // NT_LARGE_M: ring-eligible by its rows (cldrd_gemm_nt_ring_dispatch decides the rest)
+struct NtPlan {
+    NtFamily family;
+    int splits;                 // K ranges (1: one launch; n > 1: n slabs of partial sums + splitk_finish_kernel)
+    size_t ws_bytes;            // fp32 partials the split needs (0 with splits == 1)
+};
+// tile64 = false: the plan without the 64 x 64 kernel (what the dispatch falls back to when the workspace does not hold the 64 x 64 split)
+static NtPlan nt_plan(int M, int N, int K, int fmt, bool has_gelu_pre, bool tile64 = true) {
+    NtPlan p{M >= NT_RING_MIN_M ? NT_LARGE_M : NT_TILE128, 1, 0};
+    // fp16 operands with a bf16 gelu' tape are refused whatever the shape: that call goes to the one-pass path, whose check says so
+    if (K % BK != 0 || N % 8 != 0 || (fmt != CLDRD_FMT_BF16 && has_gelu_pre && !(fmt & FMT_TAPE_BIT))) return p;
+    if (const int k64 = tile64 ? nt64_splits(M, N, K) : 0) {
+        p.family = NT_TILE64;
+        p.splits = k64;
+    } else {
+        p.splits = splitk_choice(M, N, K);
+    }
+    if (p.splits > 1) p.ws_bytes = (size_t)p.splits * M * N * sizeof(float);
+    return p;
+}
+
 template <int EPI>
 int launch_nt(const GemmNtArgs& a, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-        attr_set = true;
-    }
-    const int nblk = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI>), dim3(nblk), dim3(256), 2 * STAGE_BYTES, st, a);
+    return launch_lds<gemm_nt_kernel<EPI>>(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN), 256, 2 * STAGE_BYTES, a, st);
+}
+
+// Split-K pair: the partial sums of a.ksplit K ranges per tile (nblk workgroups in all), then the fixed-order sum and the epilogue
+template <bool F16, auto Partials>
+int launch_splitk(int nblk, int lds, const GemmNtArgs& a, hipStream_t st) {
+    if (const int rc = launch_lds<Partials>(nblk, 256, lds, a, st)) return rc;
+    const size_t nthr = (size_t)a.M * (a.N / 8);
+    hipLaunchKernelGGL(splitk_finish_kernel<F16>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, a);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
@@ -333,12 +358,11 @@ int cldrd_gemm_nt_ring_scan(const GemmNtArgs& a, hipStream_t st);               
 int cldrd_topk_scan_stream(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts, int* cand_rows,
                            float* cand_scores, int cap, int f16, hipStream_t st);   // topk.hip
 
-// Bytes of workspace with which cldrd_gemm_nt16 splits the K range of this shape over several workgroups (0: it does not)
+// Bytes of workspace with which cldrd_gemm_nt16 splits the K range of this shape over several workgroups (0: it does not).  The answer is for the
+// shape alone: the dispatch declines a granted workspace for one flavour, fp16 operands with a bf16 gelu_pre (a call it refuses anyway).
 extern "C" size_t cldrd_gemm_nt_splitk_workspace(int M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % BK != 0 || N % 8 != 0) return 0;
-    if (const int k64 = nt64_splits(M, N, K)) return k64 > 1 ? (size_t)k64 * M * N * sizeof(float) : 0;
-    const int ks = splitk_choice(M, N, K);
-    return ks > 1 ? (size_t)ks * M * N * sizeof(float) : 0;
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return nt_plan(M, N, K, CLDRD_FMT_BF16, false).ws_bytes;
 }
 
 // ln_*: the fp32 residual given as a LayerNorm still to be applied (GemmNtArgs::ln_*): all four pointers or none.
@@ -348,10 +372,10 @@ extern "C" size_t cldrd_gemm_nt_splitk_workspace(int M, int N, int K) {
 extern "C" int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
                                const float* bias, const void* residual, int ldr, void* preact, const void* gelu_pre,
                                int act, float alpha, float dropout_p, unsigned long long seed, int out_f32, int res_f32,
-                               int io_f16, const float* ln_mean, const float* ln_rstd, const float* ln_gamma,
+                               int fmt, const float* ln_mean, const float* ln_rstd, const float* ln_gamma,
                                const float* ln_beta, float* workspace, size_t workspace_bytes, void* stream) {
-    CLDRD_CHECK(io_f16 == 0 || io_f16 == 1 || io_f16 == 3 || io_f16 == 5,
-                "gemm_nt: io_f16 is 0 (bf16), 1 (fp16 operands and 16-bit C), 3 (fp16 operands, bf16 C) or 5 (1 + fp16 preact / gelu_pre: the all-fp16 training mode)");
+    CLDRD_CHECK(fmt == CLDRD_FMT_BF16 || fmt == CLDRD_FMT_F16 || fmt == CLDRD_FMT_F16_C_BF16 || fmt == CLDRD_FMT_F16_TAPE,
+                "gemm_nt: fmt is 0 (bf16), 1 (fp16 operands and 16-bit C), 3 (fp16 operands, bf16 C) or 5 (1 + fp16 preact / gelu_pre: the all-fp16 training mode)");
     {
         const int nln = (ln_mean != nullptr) + (ln_rstd != nullptr) + (ln_gamma != nullptr) + (ln_beta != nullptr);
         CLDRD_CHECK(nln == 0 || nln == 4, "gemm_nt: ln_mean / ln_rstd / ln_gamma / ln_beta go together");
@@ -366,6 +390,8 @@ extern "C" int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int
                 "gemm_nt: operands must be 16-byte aligned");
     CLDRD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, "gemm_nt: dropout_p out of range");
     CLDRD_CHECK(act >= 0 && act <= 3, "gemm_nt: act must be 0..3 (bit 0 erf-GELU, bit 1 derivative form of preact / gelu_pre)");
+    const bool f16 = fmt != CLDRD_FMT_BF16;
+    hipStream_t st = (hipStream_t)stream;
     GemmNtArgs a;
     a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
@@ -376,118 +402,45 @@ extern "C" int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int
     a.drop_thresh = dropout_p > 0.f ? dropout_thresh16(dropout_p) : 0u;
     a.drop_scale = 1.0f / (1.0f - dropout_p);
     a.seed = seed; a.seed_base = g_cldrd_seed_base; a.out_f32 = out_f32;
-    a.thr = nullptr; a.counts = nullptr; a.cand_rows = nullptr; a.cand_scores = nullptr; a.cap = 0;
-    a.in_f16 = io_f16 ? 1 : 0;
-    a.c_bf16 = (io_f16 & 2) ? 1 : 0;
-    a.tape_f16 = (io_f16 & 4) ? 1 : 0;
-    if (const int k64 = (io_f16 && gelu_pre && !(io_f16 & 4)) ? 0 : nt64_splits(M, N, K);
-        k64 == 1 || (k64 > 1 && workspace != nullptr && workspace_bytes >= (size_t)k64 * M * N * sizeof(float) && (uintptr_t)workspace % 16 == 0)) {
-        a.ksplit = k64;
+    a.in_f16 = f16 ? 1 : 0;
+    a.c_bf16 = (fmt & FMT_C_BF16_BIT) ? 1 : 0;
+    a.tape_f16 = (fmt & FMT_TAPE_BIT) ? 1 : 0;
+
+    // a split needs its workspace granted; without it the 64 x 64 split gives way to the 128 x 128 kernel's own plan, and that to one pass
+    const auto granted = [&](const NtPlan& p) {
+        return p.splits == 1 || (workspace != nullptr && workspace_bytes >= p.ws_bytes && (uintptr_t)workspace % 16 == 0);
+    };
+    NtPlan plan = nt_plan(M, N, K, fmt, gelu_pre != nullptr);
+    if (plan.family == NT_TILE64 && !granted(plan)) plan = nt_plan(M, N, K, fmt, gelu_pre != nullptr, false);
+    if (!granted(plan)) plan.splits = 1;
+    if (plan.splits > 1) {
+        a.ksplit = plan.splits;
         a.slabs = workspace;
-        const int nblk = ((M + SB - 1) / SB) * ((N + SB - 1) / SB) * k64;
-        hipStream_t st = (hipStream_t)stream;
-        static bool set64 = false;
-        if (!set64) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, S_NST * S_STAGE);
-            (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, S_NST * S_STAGE);
-            (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, S_NST * S_STAGE);
-            (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, S_NST * S_STAGE);
-            set64 = true;
-        }
-        if (k64 == 1) {
-            if (io_f16) hipLaunchKernelGGL((gemm_nt64_kernel<true, false>), dim3(nblk), dim3(256), S_NST * S_STAGE, st, a);
-            else hipLaunchKernelGGL((gemm_nt64_kernel<false, false>), dim3(nblk), dim3(256), S_NST * S_STAGE, st, a);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
-        if (io_f16) hipLaunchKernelGGL((gemm_nt64_kernel<true, true>), dim3(nblk), dim3(256), S_NST * S_STAGE, st, a);
-        else hipLaunchKernelGGL((gemm_nt64_kernel<false, true>), dim3(nblk), dim3(256), S_NST * S_STAGE, st, a);
-        CLDRD_LAUNCH_CHECK();
-        const size_t nthr = (size_t)M * (N / 8);
-        if (io_f16) hipLaunchKernelGGL(splitk_finish_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(splitk_finish_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, a);
-        CLDRD_LAUNCH_CHECK();
-        return 0;
     }
-    if (workspace != nullptr && K % BK == 0 && N % 8 == 0 && !(io_f16 && gelu_pre && !(io_f16 & 4))) {
-        const int ks = splitk_choice(M, N, K);
-        if (ks > 1 && workspace_bytes >= (size_t)ks * M * N * sizeof(float) && (uintptr_t)workspace % 16 == 0) {
-            a.ksplit = ks;
-            a.slabs = workspace;
-            const int nblk = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * ks;
-            hipStream_t st = (hipStream_t)stream;
-            if (io_f16) {
-                static bool set16 = false;
-                if (!set16) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<EPI_SPLITK | EPI_F16IN>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES); set16 = true; }
-                hipLaunchKernelGGL((gemm_nt_kernel<EPI_SPLITK | EPI_F16IN>), dim3(nblk), dim3(256), 2 * STAGE_BYTES, st, a);
-            } else {
-                static bool set = false;
-                if (!set) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<EPI_SPLITK>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES); set = true; }
-                hipLaunchKernelGGL((gemm_nt_kernel<EPI_SPLITK>), dim3(nblk), dim3(256), 2 * STAGE_BYTES, st, a);
-            }
-            CLDRD_LAUNCH_CHECK();
-            const size_t nthr = (size_t)M * (N / 8);
-            if (io_f16) hipLaunchKernelGGL(splitk_finish_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL(splitk_finish_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, a);
-            CLDRD_LAUNCH_CHECK();
-            return 0;
-        }
+    if (plan.family == NT_TILE64) {
+        const int nblk = ((M + SB - 1) / SB) * ((N + SB - 1) / SB) * plan.splits;
+        constexpr int lds = S_NST * S_STAGE;
+        if (plan.splits == 1) return f16 ? launch_lds<gemm_nt64_kernel<true, false>>(nblk, 256, lds, a, st) : launch_lds<gemm_nt64_kernel<false, false>>(nblk, 256, lds, a, st);
+        return f16 ? launch_splitk<true, gemm_nt64_kernel<true, true>>(nblk, lds, a, st) : launch_splitk<false, gemm_nt64_kernel<false, true>>(nblk, lds, a, st);
     }
-    if (io_f16) {
-        // fp16 operands / 16-bit output (the high-precision forward of the query tower): small-M kernel, forward flavours only
+    if (plan.splits > 1) {
+        const int nblk = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * plan.splits;
+        return f16 ? launch_splitk<true, gemm_nt_kernel<EPI_SPLITK | EPI_F16IN>>(nblk, 2 * STAGE_BYTES, a, st)
+                   : launch_splitk<false, gemm_nt_kernel<EPI_SPLITK>>(nblk, 2 * STAGE_BYTES, a, st);
+    }
+    // one pass: the 256-row ring kernel for large M where it is built for the shape and flavour, else the 128 x 128 kernel
+    if (f16) {
         CLDRD_CHECK(K % BK == 0, "gemm_nt: K must be a multiple of 64");
-        CLDRD_CHECK(gelu_pre == nullptr || (io_f16 & 4), "gemm_nt: gelu_pre with fp16 operands needs the fp16 tape format (io_f16 = 5)");
-        {
-            const int rc = cldrd_gemm_nt_ring_dispatch(a, (hipStream_t)stream);      // large-M FFN forward flavours (gemm_nt_ring16.hip)
-            if (rc >= 0) return rc;
-        }
-        switch (epi_flavour(a)) {
-            case EPI_F16IN | EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU:
-                return launch_nt<EPI_F16IN | EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_BIAS: return launch_nt<EPI_F16IN | EPI_BIAS>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_BIAS | EPI_GELU: return launch_nt<EPI_F16IN | EPI_BIAS | EPI_GELU>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32:
-                return launch_nt<EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32:
-                return launch_nt<EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-                return launch_nt<EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-                return launch_nt<EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, (hipStream_t)stream);
-            // round 4, the all-fp16 training mode: backward flavours of the small-M kernel (CLS-only last layer, query tower)
-            case EPI_F16IN: return launch_nt<EPI_F16IN>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_GELUGRAD | EPI_DGELU: return launch_nt<EPI_F16IN | EPI_GELUGRAD | EPI_DGELU>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_F32: return launch_nt<EPI_F16IN | EPI_F32>(a, (hipStream_t)stream);
-            case EPI_F16IN | EPI_RESIDUAL | EPI_RES32 | EPI_F32: return launch_nt<EPI_F16IN | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, (hipStream_t)stream);
-            default: return cldrd_set_error("gemm_nt: this epilogue combination is not built for the fp16 format");
-        }
+        CLDRD_CHECK(gelu_pre == nullptr || (fmt & FMT_TAPE_BIT), "gemm_nt: gelu_pre with fp16 operands needs the fp16 tape format (fmt = 5)");
     }
-    {   // large-M shapes go to the 256-row ring kernel
-        const int rc = cldrd_gemm_nt_ring_dispatch(a, (hipStream_t)stream);
+    if (plan.family == NT_LARGE_M) {
+        const int rc = cldrd_gemm_nt_ring_dispatch(a, st);
         if (rc >= 0) return rc;
     }
+    const auto launch = [&](auto e) { return launch_nt<decltype(e)::value>(a, st); };
+    if (f16) return epi_dispatch(EpiF16Small{}, epi_flavour(a), launch, [] { return cldrd_set_error("gemm_nt: this epilogue combination is not built for the fp16 format"); });
     CLDRD_CHECK(K % BK == 0, "gemm_nt: K must be a multiple of 64 for M < 1024 or N not a multiple of 192/256");
-    switch (epi_flavour(a)) {
-        case 0: return launch_nt<0>(a, (hipStream_t)stream);
-        case EPI_BIAS: return launch_nt<EPI_BIAS>(a, (hipStream_t)stream);
-        case EPI_BIAS | EPI_PREACT | EPI_GELU: return launch_nt<EPI_BIAS | EPI_PREACT | EPI_GELU>(a, (hipStream_t)stream);
-        case EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU: return launch_nt<EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU>(a, (hipStream_t)stream);
-        case EPI_GELUGRAD | EPI_DGELU: return launch_nt<EPI_GELUGRAD | EPI_DGELU>(a, (hipStream_t)stream);
-        case EPI_BIAS | EPI_RESIDUAL: return launch_nt<EPI_BIAS | EPI_RESIDUAL>(a, (hipStream_t)stream);
-        case EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL: return launch_nt<EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL>(a, (hipStream_t)stream);
-        case EPI_GELUGRAD: return launch_nt<EPI_GELUGRAD>(a, (hipStream_t)stream);
-        case EPI_RESIDUAL: return launch_nt<EPI_RESIDUAL>(a, (hipStream_t)stream);
-        case EPI_F32: return launch_nt<EPI_F32>(a, (hipStream_t)stream);
-        case EPI_RESIDUAL | EPI_RES32 | EPI_F32: return launch_nt<EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, (hipStream_t)stream);     // fp32 gradient stream
-        case EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32: return launch_nt<EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, (hipStream_t)stream);
-        case EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32:
-            return launch_nt<EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, (hipStream_t)stream);
-        case EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-            return launch_nt<EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, (hipStream_t)stream);
-        case EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-            return launch_nt<EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, (hipStream_t)stream);
-        default: return launch_nt<EPI_GENERIC>(a, (hipStream_t)stream);
-    }
+    return epi_dispatch(EpiBf16Small{}, epi_flavour(a), launch, [&] { return launch_nt<EPI_GENERIC>(a, st); });
 }
 
 
@@ -499,10 +452,8 @@ extern "C" int cldrd_topk_scan_filter(const void* Q, const void* P, int nq, long
     CLDRD_CHECK(nq > 0 && rows > 0 && rows < 2147483647LL && d % BK == 0 && cap > 0, "topk_scan_filter: bad arguments");
     CLDRD_CHECK(((uintptr_t)Q % 16 == 0) && ((uintptr_t)P % 16 == 0), "topk_scan_filter: operands must be 16-byte aligned");
     GemmNtArgs a;
-    a.A = (const bf16_t*)Q; a.B = (const bf16_t*)P; a.C = nullptr;
-    a.M = nq; a.N = (int)rows; a.K = d; a.lda = d; a.ldb = d; a.ldc = 0;
-    a.bias = nullptr; a.residual = nullptr; a.ldr = 0; a.preact = nullptr; a.gelu_pre = nullptr; a.act = 0; a.alpha = 1.0f;
-    a.drop_thresh = 0; a.drop_scale = 1.0f; a.seed = 0; a.out_f32 = 0;
+    a.A = (const bf16_t*)Q; a.B = (const bf16_t*)P;
+    a.M = nq; a.N = (int)rows; a.K = d; a.lda = d; a.ldb = d;
     a.thr = thr; a.counts = counts; a.cand_rows = cand_rows; a.cand_scores = cand_scores; a.cap = cap;
     a.in_f16 = f16 ? 1 : 0;
     if (!tiled) {

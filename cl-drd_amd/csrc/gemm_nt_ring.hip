@@ -4,31 +4,11 @@
 
 namespace {
 
+// The compiled flavours are EpiBf16Ring (gemm_epilogue.h); anything else runs on the generic instantiation.
 template <int BN>
 int launch_ring(const GemmNtArgs& a, hipStream_t st) {
-    switch (epi_flavour(a)) {
-        case 0: return launch_ring_epi<BN, 0>(a, st);
-        case EPI_BIAS: return launch_ring_epi<BN, EPI_BIAS>(a, st);
-        case EPI_BIAS | EPI_PREACT | EPI_GELU: return launch_ring_epi<BN, EPI_BIAS | EPI_PREACT | EPI_GELU>(a, st);
-        case EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU: return launch_ring_epi<BN, EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU>(a, st);
-        case EPI_GELUGRAD | EPI_DGELU: return launch_ring_epi<BN, EPI_GELUGRAD | EPI_DGELU>(a, st);
-        case EPI_BIAS | EPI_GELU: return launch_ring_epi<BN, EPI_BIAS | EPI_GELU>(a, st);
-        case EPI_BIAS | EPI_RESIDUAL: return launch_ring_epi<BN, EPI_BIAS | EPI_RESIDUAL>(a, st);
-        case EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL: return launch_ring_epi<BN, EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL>(a, st);
-        case EPI_GELUGRAD: return launch_ring_epi<BN, EPI_GELUGRAD>(a, st);
-        case EPI_RESIDUAL: return launch_ring_epi<BN, EPI_RESIDUAL>(a, st);
-        case EPI_F32: return launch_ring_epi<BN, EPI_F32>(a, st);
-        // data gradients of the fp32 gradient stream: fp32 residual (the LayerNorm backward's dx) in, fp32 sum out
-        case EPI_RESIDUAL | EPI_RES32 | EPI_F32: return launch_ring_epi<BN, EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, st);
-        case EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32: return launch_ring_epi<BN, EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, st);
-        case EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32:
-            return launch_ring_epi<BN, EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, st);
-        case EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-            return launch_ring_epi<BN, EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, st);
-        case EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-            return launch_ring_epi<BN, EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, st);
-        default: return launch_ring_epi<BN, EPI_GENERIC>(a, st);
-    }
+    return epi_dispatch(EpiBf16Ring{}, epi_flavour(a), [&](auto e) { return launch_ring_epi<BN, decltype(e)::value>(a, st); },
+                        [&] { return launch_ring_epi<BN, EPI_GENERIC>(a, st); });
 }
 
 }  // namespace
@@ -45,7 +25,7 @@ int cldrd_gemm_nt_ring_dispatch(const GemmNtArgs& a_in, hipStream_t st) {
     GemmNtArgs a = a_in;
     if (a.K % BK != 0) return -1;
     if ((double)a.M * a.lda * 2.0 >= 4.0e9 || (double)a.N * a.ldb * 2.0 >= 4.0e9) return -1;   // 32-bit DMA offsets
-    if (a.M < 1024) return -1;
+    if (a.M < NT_RING_MIN_M) return -1;
     const long tiles_m = (a.M + BM - 1) / BM;
     const bool ok256 = a.N % 256 == 0, ok192 = a.N % 192 == 0;
     if (!ok256 && !ok192) return -1;

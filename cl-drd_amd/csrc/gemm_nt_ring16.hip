@@ -11,28 +11,10 @@
 
 namespace {
 
+// The compiled flavours are EpiF16Ring (gemm_epilogue.h).  -1: not built - the caller falls back to the 128 x 128 kernel (or refuses).
 template <int BN>
 int launch_ring16(const GemmNtArgs& a, hipStream_t st) {
-    switch (epi_flavour(a)) {
-        case EPI_F16IN | EPI_BIAS: return launch_ring_epi<BN, EPI_F16IN | EPI_BIAS>(a, st);      // QKV projection: fp16 operands, bf16 q / k / v (c_bf16)
-        case EPI_F16IN | EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU:
-            return launch_ring_epi<BN, EPI_F16IN | EPI_BIAS | EPI_PREACT | EPI_GELU | EPI_DGELU>(a, st);
-        case EPI_F16IN | EPI_BIAS | EPI_GELU: return launch_ring_epi<BN, EPI_F16IN | EPI_BIAS | EPI_GELU>(a, st);
-        // out-projection of the first layer (its residual is the embedding block's fp32 output: no LayerNorm still to apply)
-        case EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32:
-            return launch_ring_epi<BN, EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, st);
-        case EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32:
-            return launch_ring_epi<BN, EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32>(a, st);
-        case EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-            return launch_ring_epi<BN, EPI_F16IN | EPI_BIAS | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, st);
-        case EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN:
-            return launch_ring_epi<BN, EPI_F16IN | EPI_BIAS | EPI_DROPOUT | EPI_RESIDUAL | EPI_RES32 | EPI_F32 | EPI_RESLN>(a, st);
-        // round 4, the all-fp16 training mode: the backward's data-gradient GEMMs on fp16 operands (gradients carry the loss scale)
-        case EPI_F16IN: return launch_ring_epi<BN, EPI_F16IN>(a, st);
-        case EPI_F16IN | EPI_GELUGRAD | EPI_DGELU: return launch_ring_epi<BN, EPI_F16IN | EPI_GELUGRAD | EPI_DGELU>(a, st);
-        case EPI_F16IN | EPI_F32: return launch_ring_epi<BN, EPI_F16IN | EPI_F32>(a, st);
-        default: return -1;                               // not built: the caller falls back to the 128 x 128 kernel (or refuses)
-    }
+    return epi_dispatch(EpiF16Ring{}, epi_flavour(a), [&](auto e) { return launch_ring_epi<BN, decltype(e)::value>(a, st); }, [] { return -1; });
 }
 
 }  // namespace

@@ -243,16 +243,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(GemmNtArgs p) {
 
 template <int BN, int EPI>
 int launch_ring_epi(const GemmNtArgs& a, hipStream_t st) {
-    constexpr int lds = ring_lds_bytes<BN>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BN, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    const int nblk = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    hipLaunchKernelGGL((gemm_nt_ring_kernel<BN, EPI>), dim3(nblk), dim3(512), lds, st, a);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
+    return launch_lds<gemm_nt_ring_kernel<BN, EPI>>(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN), 512, ring_lds_bytes<BN>(), a, st);
 }
 
 }  // namespace

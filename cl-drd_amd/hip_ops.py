@@ -19,11 +19,31 @@ F32 = torch.float32
 F16 = torch.float16
 
 
+FMT_BF16, FMT_F16, FMT_F16_C_BF16, FMT_F16_TAPE = 0, 1, 3, 5        # enum cldrd_fmt16 of include/cldrd_hip.h (tests/test_capi.py compares)
+
+_SPLITK_WS = {}       # (M, N, K, gemm_splitk, gemm_nt64) -> cldrd_gemm_nt_splitk_workspace(M, N, K): everything the library's launch plan reads
+_TUNING = {}          # what set_tuning() has set
+
+
 def _fmt16(t, name):
     """16-bit activation format of a forward operand: bf16 (default) or fp16 (high-precision forward of the query tower)."""
     if t.dtype not in (BF16, F16):
         raise TypeError(f"{name}: expected bf16 or fp16, got {t.dtype}")
-    return 1 if t.dtype == F16 else 0
+    return FMT_F16 if t.dtype == F16 else FMT_BF16
+
+
+def _gemm_fmt(A, out, preact, gelu_pre):
+    """The format code of one gemm_nt call: fp16 operands give an fp16 C, or a bf16 C where ``out`` is one (the QKV projection in front of
+    the bf16 attention kernels); an fp16 tape (``preact`` / ``gelu_pre``: the all-fp16 training mode) makes it FMT_F16_TAPE."""
+    fmt = _fmt16(A, "A")
+    if fmt == FMT_F16 and out.dtype == BF16:
+        fmt = FMT_F16_C_BF16
+    for t, n in ((preact, "preact"), (gelu_pre, "gelu_pre")):
+        if t is not None and t.dtype == F16:          # the all-fp16 training mode: gelu'(x) lives on the tape in fp16 too
+            if fmt not in (FMT_F16, FMT_F16_TAPE):
+                raise TypeError(f"gemm_nt: an fp16 {n} goes with fp16 operands and an fp16 / fp32 out")
+            fmt = FMT_F16_TAPE
+    return fmt
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -212,30 +232,20 @@ def gemm_nt(A, B, out, M=None, *, bias=None, residual=None, preact=None, gelu_pr
     ``act``: bit 0 = erf-GELU; bit 1 = derivative form: ``preact`` receives gelu'(pre-activation) (act=3), ``gelu_pre`` holds it (act=2).
     ``residual_ln`` = (mean[M], rstd[M], gamma[N], beta[N]): the fp32 ``residual`` is a pre-LN sum and LayerNorm(residual) is what is added.
     fp16 operands with M >= 1024: the forward FFN flavours only (bias + GELU [+ tape]; bias [+ dropout] + residual_ln -> fp32 out)."""
-    io_f16 = _fmt16(A, "A")
-    dt16 = F16 if io_f16 else BF16
-    _chk(A, dt16, "A", 2), _chk(B, dt16, "B", 2)
-    if io_f16 and out.dtype == BF16:
-        io_f16, dt16 = 3, BF16              # fp16 operands, bf16 result (the QKV projection in front of the bf16 attention kernels)
+    fmt = _gemm_fmt(A, out, preact, gelu_pre)
+    _chk(A, A.dtype, "A", 2), _chk(B, A.dtype, "B", 2)
     M = A.shape[0] if M is None else M
     N, K = B.shape
     if A.shape[1] != K or out.shape[1] != N or out.shape[0] < M or A.shape[0] < M:
         raise ValueError(f"gemm_nt: shape mismatch A{tuple(A.shape)} B{tuple(B.shape)} out{tuple(out.shape)} M={M}")
     out_f32 = 1 if out.dtype == F32 else 0
     if not out_f32:
-        _chk(out, dt16, "out", 2)
+        _chk(out, F16 if fmt in (FMT_F16, FMT_F16_TAPE) else BF16, "out", 2)
     if bias is not None:
         _chk(bias, F32, "bias", 1)
-    tape16 = False
     for t, n in ((preact, "preact"), (gelu_pre, "gelu_pre")):
         if t is not None:
-            if t.dtype == F16:        # the all-fp16 training mode: gelu'(x) lives on the tape in fp16 too
-                if io_f16 != 1:
-                    raise TypeError(f"gemm_nt: an fp16 {n} goes with fp16 operands and an fp16 / fp32 out")
-                tape16 = True
-            _chk(t, F16 if tape16 else BF16, n, 2)
-    if tape16:
-        io_f16 = 5
+            _chk(t, F16 if fmt == FMT_F16_TAPE else BF16, n, 2)
     res_f32 = 0
     if residual is not None:
         res_f32 = 1 if residual.dtype == F32 else 0        # fp32: the residual stream kept in full precision
@@ -253,7 +263,7 @@ def gemm_nt(A, B, out, M=None, *, bias=None, residual=None, preact=None, gelu_pr
     # small-M problems (CLS-only last layer, query tower) are split along K when that fills the chip: fp32 partials in a scratch tensor
     ws, ws_bytes = None, 0
     if M < 1024:
-        key = (M, N, K, _TUNING.get("gemm_splitk", 0), _TUNING.get("gemm_nt64", 1))      # the kernel choice is part of the cache key
+        key = (M, N, K, _TUNING.get("gemm_splitk", 0), _TUNING.get("gemm_nt64", 1))
         ws_bytes = _SPLITK_WS.get(key)
         if ws_bytes is None:
             ws_bytes = _SPLITK_WS[key] = int(_lib.load().cldrd_gemm_nt_splitk_workspace(M, N, K))
@@ -261,7 +271,7 @@ def gemm_nt(A, B, out, M=None, *, bias=None, residual=None, preact=None, gelu_pr
             ws = torch.empty(ws_bytes // 4, dtype=F32, device=A.device)
     call("cldrd_gemm_nt16", _p(A), _p(B), _p(out), M, N, K, A.stride(0), B.stride(0), out.stride(0), _p(bias),
          _p(residual), residual.stride(0) if residual is not None else 0, _p(preact), _p(gelu_pre), act, alpha, dropout_p, seed,
-         out_f32, res_f32, io_f16, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(ws), ws_bytes, _stream())
+         out_f32, res_f32, fmt, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(ws), ws_bytes, _stream())
     return out
 
 
@@ -289,10 +299,6 @@ def gemm_nt_f32(A, W, out, M=None, *, bias=None, residual=None, act=0):
     call("cldrd_gemm_nt_f32", _p(A), _p(W), _p(out), M, N, K, A.stride(0), W.stride(0), out.stride(0), _p(bias), _p(residual),
          residual.stride(0) if residual is not None else 0, act, _stream())
     return out
-
-
-_SPLITK_WS = {}
-_TUNING = {}
 
 
 def set_tuning(key: str, value: int) -> None:
@@ -405,17 +411,17 @@ def attention_fwd(qkv, mask, ctx, lse, nseq, L, H, dropout_p=0.0, seed=0, drop_b
     """``ctx16`` (fp16, bf16 pass only): the same context in fp16, for an fp16-operand out-projection; ``ctx`` may then be None.
     ``cu``: qkv / ctx / ctx16 are packed [Tp, .] (see _cu_rows); ``lse`` and ``drop_bits`` keep their padded shapes.  ``seq_list`` / ``tile``:
     see _seq_list."""
-    io_f16 = _fmt16(qkv, "qkv")
+    fmt = _fmt16(qkv, "qkv")
     layout = _layout(mask, cu, seq_list, tile, nseq, L, "attention_fwd")
-    _chk(qkv, F16 if io_f16 else BF16, "qkv", 2)
+    _chk(qkv, F16 if fmt else BF16, "qkv", 2)
     if ctx16 is not None:
-        if io_f16:
+        if fmt:
             raise ValueError("attention_fwd: ctx16 goes with a bf16 pass")
         _chk(ctx16, F16, "ctx16", 2)
         if ctx16.shape[1] != H * 64 or not ctx16.is_contiguous():
             raise ValueError("attention: ctx16 must be contiguous [T, H*64]")
     if ctx is not None or ctx16 is None:
-        _chk(ctx, F16 if io_f16 else BF16, "ctx", 2)
+        _chk(ctx, F16 if fmt else BF16, "ctx", 2)
     if mask is not None:
         _chk(mask, torch.int64, "mask", 2)
         if not mask.is_contiguous() or tuple(mask.shape) != (nseq, L):
@@ -428,36 +434,36 @@ def attention_fwd(qkv, mask, ctx, lse, nseq, L, H, dropout_p=0.0, seed=0, drop_b
         _chk(drop_bits, torch.int32, "drop_bits", 1)
         if drop_bits.numel() != _lib.load().cldrd_attention_bits_words(nseq, L, H, dropout_p):
             raise ValueError("attention_fwd: drop_bits must come from attention_drop_bits() for the same shape")
-    if io_f16 and (drop_bits is not None or L > 128 or full_family):
-        io_f16 = 5                    # fp16 through the whole kernel family of the bf16 path (persistent kernel, keep bits, L > 128)
-    call("cldrd_attention_fwd", _p(qkv), *layout, _p(ctx), _p(lse), nseq, L, H, dropout_p, seed, io_f16, _p(drop_bits), _p(ctx16), _stream())
+    if fmt == FMT_F16 and (drop_bits is not None or L > 128 or full_family):
+        fmt = FMT_F16_TAPE            # fp16 through the whole kernel family of the bf16 path (persistent kernel, keep bits, L > 128)
+    call("cldrd_attention_fwd", _p(qkv), *layout, _p(ctx), _p(lse), nseq, L, H, dropout_p, seed, fmt, _p(drop_bits), _p(ctx16), _stream())
     return ctx16 if ctx is None else ctx
 
 
 def attention_bwd(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, dropout_p=0.0, seed=0, drop_bits=None, cu=None, seq_list=None, tile=0):
     """``cu``: qkv / ctx / dctx / dqkv are packed [Tp, .] (see _cu_rows); ``seq_list`` / ``tile``: see _seq_list."""
-    io_f16 = _fmt16(qkv, "qkv")       # fp16 everywhere (the all-fp16 training mode) or bf16 everywhere
+    fmt = _fmt16(qkv, "qkv")       # fp16 everywhere (the all-fp16 training mode) or bf16 everywhere
     for t, n in ((qkv, "qkv"), (ctx, "ctx"), (dctx, "dctx"), (dqkv, "dqkv")):
-        _chk(t, F16 if io_f16 else BF16, n, 2)
+        _chk(t, F16 if fmt else BF16, n, 2)
         if not t.is_contiguous():
             raise ValueError(f"attention_bwd: {n} must be contiguous")
     _chk(lse, F32, "lse")
     if drop_bits is not None:
         _chk(drop_bits, torch.int32, "drop_bits", 1)
     call("cldrd_attention_bwd", _p(qkv), *_layout(mask, cu, seq_list, tile, nseq, L, "attention_bwd"), _p(ctx), _p(dctx), _p(lse), _p(dqkv),
-         nseq, L, H, dropout_p, seed, io_f16, _p(drop_bits), _stream())
+         nseq, L, H, dropout_p, seed, fmt, _p(drop_bits), _stream())
     return dqkv
 
 
 def attention_cls_fwd(qc, kv, mask, ctx, probs, nseq, L, H, dropout_p=0.0, seed=0, ctx16=None, cu=None):
     """``cu``: kv is packed [Tp, 2*H*64] (see _cu_rows); probs stays [nseq, H, L]."""
-    io_f16 = _fmt16(qc, "qc")
-    dt16 = F16 if io_f16 else BF16
+    fmt = _fmt16(qc, "qc")
+    dt16 = F16 if fmt else BF16
     _chk(qc, dt16, "qc", 2), _chk(kv, dt16, "kv", 2), _chk(probs, F32, "probs")
     if ctx is not None:
         _chk(ctx, dt16, "ctx", 2)
     if ctx16 is not None:
-        if io_f16:
+        if fmt:
             raise ValueError("attention_cls_fwd: ctx16 goes with a bf16 pass")
         _chk(ctx16, F16, "ctx16", 2)
     if ctx is None and ctx16 is None:
@@ -465,18 +471,18 @@ def attention_cls_fwd(qc, kv, mask, ctx, probs, nseq, L, H, dropout_p=0.0, seed=
     if kv.shape[1] != 2 * H * 64 or not kv.is_contiguous() or not qc.is_contiguous() or any(t is not None and not t.is_contiguous() for t in (ctx, ctx16)):
         raise ValueError("attention_cls: kv must be contiguous [T, 2*H*64]")
     call("cldrd_attention_cls_fwd", _p(qc), _p(kv), *_layout(mask, cu, None, 0, nseq, L, "attention_cls_fwd")[:2], _p(ctx), _p(probs), nseq, L, H,
-         dropout_p, seed, io_f16, _p(ctx16), _stream())
+         dropout_p, seed, fmt, _p(ctx16), _stream())
 
 
 def attention_cls_bwd(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p=0.0, seed=0, cu=None):
     """``cu``: kv and dkv are packed [Tp, 2*H*64] (see _cu_rows)."""
-    io_f16 = _fmt16(qc, "qc")
+    fmt = _fmt16(qc, "qc")
     for t, n in ((qc, "qc"), (kv, "kv"), (dctx, "dctx"), (dqc, "dqc"), (dkv, "dkv")):
-        _chk(t, F16 if io_f16 else BF16, n, 2)
+        _chk(t, F16 if fmt else BF16, n, 2)
         if not t.is_contiguous():
             raise ValueError(f"attention_cls_bwd: {n} must be contiguous")
     call("cldrd_attention_cls_bwd", _p(qc), _p(kv), _layout(None, cu, None, 0, nseq, L, "attention_cls_bwd")[1], _p(probs), _p(dctx), _p(dqc), _p(dkv),
-         nseq, L, H, dropout_p, seed, io_f16, _stream())
+         nseq, L, H, dropout_p, seed, fmt, _stream())
 
 
 def attention_fwd_f32(qkv, mask, ctx, nseq, L, H, cu=None, qc=None):

@@ -35,6 +35,16 @@ def test_binding_table_matches_header():
     assert sorted(_lib.SIGNATURES) == declared_symbols()
 
 
+def test_format_constants_match_the_header_enum():
+    """hip_ops names the 16-bit format codes it passes as `fmt`: the names and values are enum cldrd_fmt16's, every member of it."""
+    from cldrd_amd import hip_ops as ops
+    body = re.search(r"enum\s+cldrd_fmt16\s*\{(.*?)\}", open(HEADER).read(), flags=re.S).group(1)
+    enum = {name: int(value) for name, value in re.findall(r"\bCLDRD_(FMT_[A-Z0-9_]+)\s*=\s*(\d+)", re.sub(r"/\*.*?\*/", "", body, flags=re.S))}
+    assert enum == {"FMT_BF16": 0, "FMT_F16": 1, "FMT_F16_C_BF16": 3, "FMT_F16_TAPE": 5}
+    assert {name: getattr(ops, name) for name in enum} == enum
+    assert sorted(n for n in vars(ops) if n.startswith("FMT_")) == sorted(enum)
+
+
 def test_product_library_reads_no_environment_variable():
     """An inherited environment variable must not be able to change what a run computes (round-3 review): the shipped library imports no
     getenv, contains no CLDRD_* switch name - in particular none of the timing-only ablation modes (CLDRD_GEMM_ABLATE, CLDRD_SCAN_ABLATE:

@@ -1553,7 +1553,7 @@ def test_forward_kernels_in_the_fp16_format():
         probs = torch.empty(nseq, H, L, dtype=torch.float32, device=DEV)
         ops.attention_cls_fwd(qc.to(DEV), kv.to(DEV), mask.to(DEV), ctxc, probs, nseq, L, H)
         close(ctxc, ref_ctx.view(nseq, L, d)[:, 0], 1 / 1024, 2e-3, f"fp16 CLS attention L={L}")
-    # L > 128 in fp16 goes through the whole kernel family of the bf16 path since round 4 (io_f16 = 5)
+    # L > 128 in fp16 goes through the whole kernel family of the bf16 path since round 4 (fmt = CLDRD_FMT_F16_TAPE)
     qkv = rnd(50, (2 * 256, 192)).half()
     ref_ctx, _ = attn_ref(qkv.double(), torch.ones(2, 256, dtype=torch.int64), 2, 256, 1)
     ctx = torch.empty(512, 64, dtype=torch.float16, device=DEV)
