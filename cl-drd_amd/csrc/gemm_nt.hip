@@ -388,6 +388,8 @@ extern "C" int cldrd_gemm_nt16(const void* A, const void* B, void* C, int M, int
                 "gemm_nt: N, lda, ldb, ldc, ldr must be multiples of 8");
     CLDRD_CHECK(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0) && ((uintptr_t)residual % 16 == 0),
                 "gemm_nt: operands must be 16-byte aligned");
+    CLDRD_CHECK(((uintptr_t)bias % 16 == 0) && ((uintptr_t)preact % 16 == 0) && ((uintptr_t)gelu_pre % 16 == 0),
+                "gemm_nt: bias / preact / gelu_pre must be 16-byte aligned");
     CLDRD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, "gemm_nt: dropout_p out of range");
     CLDRD_CHECK(act >= 0 && act <= 3, "gemm_nt: act must be 0..3 (bit 0 erf-GELU, bit 1 derivative form of preact / gelu_pre)");
     const bool f16 = fmt != CLDRD_FMT_BF16;

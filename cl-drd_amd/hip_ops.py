@@ -229,6 +229,7 @@ def gemm_nt(A, B, out, M=None, *, bias=None, residual=None, preact=None, gelu_pr
             dropout_p=0.0, seed=0, residual_ln=None):
     """out[M,N] = epilogue(alpha * A[M,K] @ B[N,K]^T); A, B bf16 (or both fp16: forward flavours, M < 1024); out 16-bit like A, or fp32.
 
+    A, B, out and residual take row pitches (``stride(0)``); ``preact`` / ``gelu_pre`` are [>= M, N] views with the row pitch of ``out``.
     ``act``: bit 0 = erf-GELU; bit 1 = derivative form: ``preact`` receives gelu'(pre-activation) (act=3), ``gelu_pre`` holds it (act=2).
     ``residual_ln`` = (mean[M], rstd[M], gamma[N], beta[N]): the fp32 ``residual`` is a pre-LN sum and LayerNorm(residual) is what is added.
     fp16 operands with M >= 1024: the forward FFN flavours only (bias + GELU [+ tape]; bias [+ dropout] + residual_ln -> fp32 out)."""
@@ -243,9 +244,14 @@ def gemm_nt(A, B, out, M=None, *, bias=None, residual=None, preact=None, gelu_pr
         _chk(out, F16 if fmt in (FMT_F16, FMT_F16_TAPE) else BF16, "out", 2)
     if bias is not None:
         _chk(bias, F32, "bias", 1)
+        if bias.numel() != N:
+            raise ValueError("gemm_nt: bias must be [N]")
     for t, n in ((preact, "preact"), (gelu_pre, "gelu_pre")):
         if t is not None:
             _chk(t, F16 if fmt == FMT_F16_TAPE else BF16, n, 2)
+            # the tape has no leading dimension of its own in the C ABI: the kernels index it with out's
+            if t.shape[0] < M or t.shape[1] != N or t.stride(0) != out.stride(0):
+                raise ValueError(f"gemm_nt: {n} must be [>= M, N] with the row pitch of out")
     res_f32 = 0
     if residual is not None:
         res_f32 = 1 if residual.dtype == F32 else 0        # fp32: the residual stream kept in full precision

@@ -43,6 +43,7 @@ int cldrd_set_tuning(const char* key, int value);
  *   pre-activation (forward, act = 3), and `gelu_pre` is taken to hold that derivative already (backward, act = 2: the epilogue
  *   multiplies by it and evaluates nothing) - what torch saves for GELU's backward is its input; saving the derivative moves the
  *   erf / exp out of the data-gradient GEMM's epilogue, which was VALU-bound.
+ *   `preact` / `gelu_pre` are [M, ldc]: they have no leading dimension of their own and share C's row pitch; both and `bias` 16-byte aligned.
  *   K % 64 == 0; A/B/C 16-byte aligned; out_f32 != 0 stores fp32 instead of bf16; res_f32 != 0: `residual` is fp32
  *   (the fp32 residual stream: out-projection / FFN2 add the fp32 LayerNorm output and store the fp32 pre-LN sum, as the
  *   reference's autocast does - trainer/multistep-curriculum/nway_listwise_1.py:334).
