@@ -24,7 +24,11 @@ Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
     (``scripts/unity/kd_nway_listwise.sh``, ``logit_reg_nway_listwise.sh``) but never published;
   * ``--dev_path / --dev_queries_path / --dev_qrels_path`` (the reference's flags): at every saved checkpoint rank 0 re-ranks the dev run with
     the student (``NwayTrainer.validate``: evaluation.DevPool + RerankingEvaluator) and writes ``dev_logs.log`` / ``dev_best.json``; the
-    reference tokenises and encodes every (query, passage) pair of the run per validation, here each distinct text once.
+    reference tokenises and encodes every (query, passage) pair of the run per validation, here each distinct text once;
+  * ``--resume CKPT --resume_exact`` goes on where the checkpoint was written instead of restarting its epoch (``--resume`` alone: the
+    reference's behaviour, unchanged): checkpoints carry one more key, ``resume_state`` - dropout step counters, the loss-scale block, both
+    step counts (`NwayTrainer.resume_state`) and the data position (`train`, `_EpochPosition`) - and are moved into place whole
+    (`save_checkpoint`).  With ``--deterministic`` the resumed run equals the uninterrupted one bit for bit (one process).
 """
 from __future__ import annotations
 
@@ -42,6 +46,9 @@ from ..retriever.retrieval_utils import cap_host_threads
 
 LOSS_KINDS = ("lambda_mrr", "ranknet", "kl_div", "margin_mse")
 DISTILL_KINDS = ("kl_div", "margin_mse")      # --distill_loss: the term on batch["teacher_scores"] added to the rank loss
+RESUME_VERSION = 1                            # of the checkpoint's "resume_state" (NwayTrainer.resume_state, train())
+# what the data position of a checkpoint depends on: an exact resume under another value of any of them is refused (check_resume_position)
+POSITION_FIELDS = ("train_batch_size", "nranks", "seed", "dataset_len", "steps_per_epoch", "num_train_epochs")
 
 
 def no_decay(name: str) -> bool:
@@ -874,17 +881,69 @@ class NwayTrainer:
             raise ValueError(f"optimizer state: per-parameter step counts differ ({sorted(steps)[:4]}...): one fused step counter here")
         self._opt_step_loaded = steps.pop() if steps else None
 
+    def _arithmetic(self):
+        """What identifies the arithmetic of a step (``resume_state``): an exact resume under another mode would not be one."""
+        return {"amp": "fp16" if self.amp16 else "bf16", "share_weights": bool(self.model.share_weights), "n_towers": len(self.model.towers())}
+
+    def resume_state(self):
+        """What the reference's checkpoint keys do not carry and an exact resume needs (``load_state_dict(exact=True)``): plain CPU tensors and
+        Python scalars.  Reads the loss-scale block back from the device: checkpoint time only, like `skipped_steps`."""
+        scale = self._scale_state.detach().cpu().clone() if self._scale_state is not None else None
+        return {"version": RESUME_VERSION, "step_seeds": [int(t.step_seed) for t in self.model.towers()], "loss_scale": scale,
+                "skipped_steps": int(scale[3].item()) if scale is not None else 0, "adam_step": int(self.adam_step),
+                "global_step": int(self.global_step), **self._arithmetic()}
+
+    def _checked_resume_state(self, ckpt):
+        """``ckpt["resume_state"]`` if this trainer can continue from it bit for bit; ValueError naming the field otherwise."""
+        rs = ckpt.get("resume_state")
+        if not isinstance(rs, dict):
+            raise ValueError("exact resume: the checkpoint has no 'resume_state' (written by the reference or by an earlier version of this "
+                             "package): load it with exact=False / without --resume_exact")
+        if rs.get("version") != RESUME_VERSION:
+            raise ValueError(f"exact resume: resume_state 'version' is {rs.get('version')!r}, this package reads version {RESUME_VERSION}")
+        for field, mine in self._arithmetic().items():
+            if rs.get(field) != mine:
+                raise ValueError(f"exact resume: '{field}' was {rs.get(field)!r} when the checkpoint was written and is {mine!r} in this trainer"
+                                 + (" (CLDRD_AMP)" if field == "amp" else ""))
+        for field in ("step_seeds", "loss_scale", "skipped_steps", "adam_step", "global_step"):
+            if field not in rs:
+                raise ValueError(f"exact resume: resume_state has no '{field}'")
+        scale = rs["loss_scale"]
+        if self._scale_state is not None and (not isinstance(scale, torch.Tensor) or tuple(scale.shape) != tuple(self._scale_state.shape)):
+            raise ValueError(f"exact resume: 'loss_scale' must be the float[{self._scale_state.numel()}] loss-scale block")
+        if len(rs["step_seeds"]) != len(self.model.towers()):
+            raise ValueError("exact resume: 'step_seeds' must hold one dropout step counter per tower")
+        if int(rs["skipped_steps"]) != (int(scale[3].item()) if self._scale_state is not None else 0):
+            raise ValueError("exact resume: 'skipped_steps' disagrees with the skipped count of the 'loss_scale' block")
+        return rs
+
     def state_dict(self):
         """Checkpoint payload in the reference's shape (nway_listwise_1.py:418-426): DDP-style ``module.`` prefixed keys, the
-        optimizer in torch's ``state_dict()`` layout, the scheduler as ``LambdaLR.state_dict()`` would give it."""
+        optimizer in torch's ``state_dict()`` layout, the scheduler as ``LambdaLR.state_dict()`` would give it; plus ONE key the reference does
+        not know and, loading by name, ignores: ``resume_state`` (`resume_state`)."""
         return {"global_step": self.global_step,
                 "state_dict": {"module." + k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
                 "optimizer": self.optimizer_state_dict(),
                 "scheduler": {"base_lrs": [self.lr0, self.lr0], "last_epoch": self.global_step, "_step_count": self.global_step + 1,
                               "_get_lr_called_within_step": False, "_last_lr": [self.lr(), self.lr()], "lr_lambdas": [None, None],
-                              "warmup_steps": self.warmup_steps, "total_steps": self.total_steps}}
+                              "warmup_steps": self.warmup_steps, "total_steps": self.total_steps},
+                "resume_state": self.resume_state()}
 
-    def load_state_dict(self, ckpt):
+    def load_state_dict(self, ckpt, exact=False):
+        """``exact=False``: parameters, moments and the step counters, as the reference's ``--resume`` (``resume_state`` is ignored): the dropout
+        step counters and the loss-scale block stay as they are, Adam's step is the loaded one, which already excludes skipped steps.
+
+        ``exact=True``: after that, everything else a step depends on is put back from ``resume_state`` - every tower's dropout step counter,
+        the whole loss-scale block (copied INTO the tensor: a captured graph holds its address), ``adam_step`` and ``global_step`` as the saving
+        trainer held them.  ``adam_step`` then counts the skipped steps again and the block's skipped count is back, so the bias-correction
+        exponent (their difference), ``skipped_steps()`` and the ``step`` of later checkpoints are those of the run that was never interrupted.
+        ValueError (nothing loaded) when the checkpoint has no ``resume_state``, an unknown ``version``, or another arithmetic mode
+        (CLDRD_AMP), ``share_weights`` or tower count than this trainer.
+        The capture policy is no part of the state: a fresh trainer runs its eager warm-up steps and captures again, and with
+        ``deterministic=True`` an eager step equals a replayed one bit for bit (tests/test_gpu_deterministic.py), so the warm-up does not
+        show in the results; a trainer that has captured already keeps replaying.  Bit equality with the uninterrupted run needs
+        ``deterministic=True`` on both sides (float atomics otherwise) and holds for one process."""
+        rs = self._checked_resume_state(ckpt) if exact else None
         sd = {k[7:] if k.startswith("module.") else k: v for k, v in ckpt["state_dict"].items()}
         self.model.load_state_dict(sd)
         self._opt_step_loaded = None
@@ -896,6 +955,12 @@ class NwayTrainer:
         self.adam_step = self.global_step if self._opt_step_loaded is None else self._opt_step_loaded
         if self._scale_state is not None:
             self._scale_state[3] = 0.0          # the loaded step already excludes the skipped ones
+        if rs is not None:
+            self.global_step, self.adam_step = int(rs["global_step"]), int(rs["adam_step"])
+            if self._scale_state is not None:
+                self._scale_state.copy_(rs["loss_scale"])
+            for t, s in zip(self.model.towers(), rs["step_seeds"]):
+                t.step_seed = int(s)
         for t in self.model.towers():
             t.refresh_shadows(need_transposed=True)
 
@@ -915,6 +980,9 @@ def get_args(argv=None):
     ap.add_argument("--model_name_or_path", default="sebastian-hofstaetter/distilbert-dot-tas_b-b256-msmarco")
     ap.add_argument("--tokenizer_name_or_path", default="distilbert-base-uncased")
     ap.add_argument("--resume", default=None)
+    ap.add_argument("--resume_exact", action="store_true", default=False,
+                    help="with --resume: go on where the checkpoint was written - dropout seeds, loss-scale state and the position in the epoch's "
+                         "data from its resume_state - instead of restarting the epoch as the reference does (README: Resuming a run)")
     ap.add_argument("--model_checkpoint", default=None)
     ap.add_argument("--seed", default=4680, type=int)
     ap.add_argument("--show_progress", default=True, type=bool)
@@ -966,6 +1034,8 @@ def get_args(argv=None):
     ap.add_argument("--dev_batch_size", default=512, type=int, help="sequences per encoder batch of a validation")
     ap.add_argument("--dev_qrels_trec", action="store_true", default=False, help="--dev_qrels_path is space separated (TREC)")
     args = ap.parse_args(argv)
+    if args.resume_exact and not args.resume:
+        ap.error("--resume_exact needs --resume CKPT")
     dev_flags = [args.dev_path, args.dev_queries_path, args.dev_qrels_path]
     if any(v is not None for v in dev_flags) and not all(v is not None for v in dev_flags):
         ap.error("--dev_path, --dev_queries_path and --dev_qrels_path go together: all three or none")
@@ -1032,6 +1102,88 @@ class _Avg:
         return self.sum / max(self.n, 1)
 
 
+class _EpochPosition(torch.utils.data.Sampler):
+    """The index stream of a training loader (a batch sampler, or the plain sampler of a ``batch_size=None`` loader), handed on unchanged,
+    with the two things an exact resume needs from it:
+
+    ``epoch_state``: the state of the loader's ``torch.Generator`` at the moment the current epoch's stream was started, that is right
+    before the sampler under it draws the epoch's permutation (None without a generator).  A state, not a count of draws, and taken HERE and
+    not around ``iter(loader)``: the DataLoader draws a worker seed of its own from the same generator whenever it builds an iterator - every
+    epoch without workers, once in its life with persistent ones - so a resumed epoch (always a new iterator) would meet the generator one
+    draw further than the epoch it continues.  From this point on the draws are the sampler's alone.
+
+    ``resume(skip, state)``: the NEXT stream that is started first puts ``state`` back into the generator and then passes over its first
+    ``skip`` items: index batches that are never fetched, tokenised or collated.  Streams after it are untouched.  (A stream counts as
+    started at its first item: the DataLoader makes iterators it never reads from.)"""
+
+    def __init__(self, inner, generator=None):
+        self.inner, self.generator = inner, generator
+        self.epoch_state = None
+        self._pending = None
+
+    def resume(self, skip, state):
+        self._pending = (int(skip), state)
+
+    def __len__(self):
+        return len(self.inner)
+
+    def __iter__(self):
+        (skip, state), self._pending = self._pending or (0, None), None
+        if self.generator is not None:
+            if state is not None:
+                self.generator.set_state(state)
+            self.epoch_state = self.generator.get_state()
+        for i, item in enumerate(self.inner):
+            if i >= skip:
+                yield item
+
+
+def _position_of(loader) -> _EpochPosition:
+    return loader.batch_sampler if loader.batch_sampler is not None else loader.sampler
+
+
+def replayed_epoch_state(loader, seed, epochs):
+    """``epoch_state`` of epoch ``epochs`` (zero-based) of ``loader`` as a generator seeded ``seed`` reaches it: what a rank other than 0 puts
+    in the place of the checkpoint's state, which is rank 0's.  Replays the draws of the completed epochs without fetching anything: the
+    DataLoader's worker seed where it builds an iterator (see `_EpochPosition`), then one pass over the sampler."""
+    pos = _position_of(loader)
+    if pos.generator is None:
+        return None
+    g = torch.Generator()
+    g.manual_seed(seed)
+    sampler = torch.utils.data.RandomSampler(loader.dataset, generator=g)
+    keeps_iterator = loader.persistent_workers and loader.num_workers > 0
+    for e in range(epochs + 1):
+        if e == 0 or not keeps_iterator:
+            torch.empty((), dtype=torch.int64).random_(generator=g)
+        if e < epochs:
+            for _ in sampler:
+                pass
+    return g.get_state()
+
+
+def check_resume_position(saved, current):
+    """``--resume_exact``: the position (epoch, step_in_epoch) of a checkpoint means the same batches only under the values it was written
+    with.  ValueError naming the first of POSITION_FIELDS that differs, with both values."""
+    for field in POSITION_FIELDS:
+        if field not in saved:
+            raise ValueError(f"--resume_exact: the checkpoint's resume_state has no '{field}' (it was not written by the training command line)")
+        if saved[field] != current[field]:
+            raise ValueError(f"--resume_exact: {field} was {saved[field]} when the checkpoint was written and is {current[field]} now")
+
+
+def save_checkpoint(ckpt, path):
+    """``torch.save`` under a temporary name in the same directory, then ``os.replace``: a job killed during the write leaves no truncated file
+    under the name a restart would pick."""
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        torch.save(ckpt, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
 def build_dataloader(args):
     """Label mode -> file constructor as reference :173-245; per-rank batch = train_batch_size // nranks, shuffle, drop_last."""
     from transformers import AutoTokenizer
@@ -1077,9 +1229,12 @@ def build_dataloader(args):
     g = torch.Generator()
     g.manual_seed(args.seed + args.rank)
     nw = max(int(getattr(args, "loader_workers", 1)), 0)
-    return ds, torch.utils.data.DataLoader(ds, batch_size=args.train_batch_size // args.nranks, shuffle=True, num_workers=nw,
-                                           collate_fn=ds.collate_fn, drop_last=True, generator=g, pin_memory=True,
-                                           **(dict(prefetch_factor=4, persistent_workers=True) if nw else {}))
+    # shuffle=True, drop_last=True spelled out as the samplers the DataLoader would build from them (same generator, same draws, same
+    # batches), so that the batch sampler can be the one that knows its position (`_EpochPosition`, --resume_exact)
+    U = torch.utils.data
+    batches = U.BatchSampler(U.RandomSampler(ds, generator=g), args.train_batch_size // args.nranks, drop_last=True)
+    return ds, U.DataLoader(ds, batch_sampler=_EpochPosition(batches, g), num_workers=nw, collate_fn=ds.collate_fn, generator=g, pin_memory=True,
+                            **(dict(prefetch_factor=4, persistent_workers=True) if nw else {}))
 
 
 class _SyntheticBatches(torch.utils.data.Dataset):
@@ -1105,8 +1260,10 @@ class _SyntheticBatches(torch.utils.data.Dataset):
 
 def _synthetic_loader(args):
     nw = max(int(getattr(args, "loader_workers", 1)), 0)
-    return torch.utils.data.DataLoader(_SyntheticBatches(args), batch_size=None, shuffle=False, num_workers=nw, pin_memory=True,
-                                       **(dict(prefetch_factor=4, persistent_workers=True) if nw else {}))
+    ds = _SyntheticBatches(args)
+    # item i is batch i: the sequential sampler (what shuffle=False builds) under the position wrapper skips whole batches by index
+    return torch.utils.data.DataLoader(ds, batch_size=None, sampler=_EpochPosition(torch.utils.data.SequentialSampler(ds)), num_workers=nw,
+                                       pin_memory=True, **(dict(prefetch_factor=4, persistent_workers=True) if nw else {}))
 
 
 def common_steps_per_epoch(local_steps: int, distributed: bool, dev=None, group=None) -> int:
@@ -1203,12 +1360,28 @@ def train(args):
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)            # after model / loader construction, as the reference does (:282)
-    start_epoch = 0
+    start_epoch, first_step = 0, 0
+    position = _position_of(loader)
+    # what (epoch, step_in_epoch) of a checkpoint depends on (POSITION_FIELDS): written into every checkpoint, compared by --resume_exact
+    where = {"train_batch_size": args.train_batch_size, "nranks": args.nranks, "seed": args.seed, "dataset_len": len(loader.dataset),
+             "steps_per_epoch": steps_per_epoch, "num_train_epochs": args.num_train_epochs}
     if args.resume:
         assert args.model_checkpoint is None
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=False)
-        trainer.load_state_dict(ckpt)
-        start_epoch = ckpt["epoch"] - 1
+        if getattr(args, "resume_exact", False):
+            # go on at (epoch, step_in_epoch): the first epoch's index stream starts from the generator state that epoch started from and
+            # passes over the batches already consumed (a checkpoint of an epoch's last batch: all of them, and the loop moves on to the next
+            # epoch).  The state in the checkpoint is rank 0's; any other rank replays its own generator up to that epoch.
+            rs = ckpt.get("resume_state")
+            if isinstance(rs, dict):            # (a checkpoint without one: load_state_dict says so)
+                check_resume_position(rs, where)
+            trainer.load_state_dict(ckpt, exact=True)
+            start_epoch, first_step = int(rs["epoch"]), int(rs["step_in_epoch"])
+            state = rs["generator_state"] if args.rank == 0 else replayed_epoch_state(loader, args.seed + args.rank, start_epoch)
+            position.resume(first_step, state)
+        else:
+            trainer.load_state_dict(ckpt)
+            start_epoch = ckpt["epoch"] - 1
     if args.model_checkpoint:
         assert args.resume is None
         ckpt = torch.load(args.model_checkpoint, map_location="cpu", weights_only=False)
@@ -1222,7 +1395,9 @@ def train(args):
     topk = 10
     log_file = os.path.join(args.log_dir, "train_logs.log")
     for epoch in range(start_epoch, args.num_train_epochs):
-        for step_i, batch in enumerate(loader):
+        # (first_step > 0: the first epoch of an exact resume, whose loader passes over that many batches; the meters start empty, so the first
+        # log line after a resume averages over the logging steps since the resume only)
+        for step_i, batch in enumerate(loader, start=first_step if epoch == start_epoch else 0):
             if step_i >= steps_per_epoch:       # ranks whose shard is one batch longer stop with the others (no unmatched all-reduce)
                 break
             batch = batch_to_device(batch, dev)
@@ -1254,8 +1429,10 @@ def train(args):
             if main_rank and trainer.global_step % args.evaluate_steps == 0:
                 ckpt = trainer.state_dict()
                 ckpt["epoch"] = epoch + 1
+                # the data position, for --resume_exact: zero-based epoch, batches of it consumed, the generator state its index stream started from
+                ckpt["resume_state"].update(where, epoch=epoch, step_in_epoch=step_i + 1, generator_state=position.epoch_state)
                 ckpt_path = os.path.join(args.model_save_dir, f"checkpoint_{trainer.global_step}.pth.tar")
-                torch.save(ckpt, ckpt_path)
+                save_checkpoint(ckpt, ckpt_path)
                 if dev_run is not None:
                     # rank 0 alone, no collective: the other ranks meet it at the next step's first all-reduce
                     dev_run.validate(trainer, epoch + 1, ckpt_path)
