@@ -82,6 +82,12 @@ SIGNATURES = {
     "cldrd_index_center_cast": (ci, [vp, vp, csz, csz, ci, vp, vp, csz, csz, vp, vp, vp]),
     "cldrd_map_ids": (ci, [vp, vp, C.c_longlong, vp, csz, vp]),
     "cldrd_query_dot64": (ci, [vp, vp, ci, vp, ci, vp]),
+    "cldrd_index_quantize_i8": (ci, [vp, vp, csz, csz, ci, vp, vp, vp, csz, csz, vp, vp, vp, vp]),
+    "cldrd_topk_prep_queries_i8": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp]),
+    "cldrd_topk_thresholds_i8": (ci, [vp, vp, vp, cf, cf, ci, vp, vp, ci, vp]),
+    "cldrd_topk_scan_i8": (ci, [vp, C.c_longlong, vp, vp, vp, vp, ci, C.c_longlong, ci, vp, vp, vp, ci, vp]),
+    "cldrd_topk_rescore_i8": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, vp]),
+    "cldrd_flatip_search_i8": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_longlong, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp]),
     "cldrd_unpack_rows16": (ci, [vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_gather_rows": (ci, [vp, vp, vp, ci, ci, vp]),
     "cldrd_gather_i64": (ci, [vp, vp, vp, ci, vp]),

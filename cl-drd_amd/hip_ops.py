@@ -1144,6 +1144,105 @@ def index_center_cast(P32, mu, P16, sample_bf16, s_stride, s_rows, flag, row0=0,
     return cmax
 
 
+# int8-row mode (csrc/topk_i8.hip; include/cldrd_hip.h states the definition)
+I8 = torch.int8
+
+
+def _chk_i8_width(d, what):
+    if d <= 0 or d % 64 or d > 2048:
+        raise ValueError(f"{what}: int8 rows need an embedding width that is a multiple of 64 and at most 2048, got {d}")
+
+
+def index_quantize_i8(P32, mu, R8, scale, sample_bf16, s_stride, s_rows, flag, b1, c2, row0=0):
+    """One fp32 chunk of a shard -> ``R8`` (int8, the matching [rows, d] slice), ``scale`` (fp32 [rows] slice), the whole shard's bf16 sample
+    (rows that fall inside the chunk) and the running maxima ``b1`` / ``c2`` (int32 [1] each, zeroed before the first chunk: bit patterns of the
+    fp32 values of max a_r |R8[r]|_1 and max a_r^2 |R8[r]|_2^2); ``flag`` |= 1 for a value that is not finite (cldrd_index_quantize_i8)."""
+    _chk(P32, F32, "P32", 2), _chk(mu, F32, "mu", 1), _chk(R8, I8, "R8", 2), _chk(scale, F32, "scale", 1)
+    _chk(b1, torch.int32, "b1", 1), _chk(c2, torch.int32, "c2", 1)
+    _chk_i8_width(P32.shape[1], "index_quantize_i8")
+    if sample_bf16 is not None:
+        _chk(sample_bf16, BF16, "sample_bf16", 2)
+        if int(s_rows) > sample_bf16.shape[0] or sample_bf16.shape[1] != P32.shape[1] or not sample_bf16.is_contiguous():
+            raise ValueError("index_quantize_i8: the sample needs s_rows rows of width d")
+    if R8.shape != P32.shape or scale.numel() != P32.shape[0] or mu.numel() != P32.shape[1] \
+            or not (P32.is_contiguous() and R8.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("index_quantize_i8: R8 / scale must be the contiguous slices that match P32")
+    call("cldrd_index_quantize_i8", _p(P32), _p(mu), P32.shape[0], int(row0), P32.shape[1], _p(R8), _p(scale), _p(sample_bf16), int(s_stride),
+         int(s_rows), _p(b1), _p(c2), _p(flag), _stream())
+
+
+def topk_prep_queries_i8(q32, qd, qb, sq, qnorm, flag):
+    """``qd`` int8 [2, nq, d]: the digit planes h, l of the queries; ``sq`` / ``qnorm`` fp32 [nq]; ``qb`` the bf16 copy (cldrd_topk_prep_queries_i8)"""
+    _chk(q32, F32, "q32", 2), _chk(qd, I8, "qd", 3), _chk(qb, BF16, "qb", 2), _chk(sq, F32, "sq", 1), _chk(qnorm, F32, "qnorm", 1)
+    nq, d = q32.shape
+    _chk_i8_width(d, "topk_prep_queries_i8")
+    if qd.shape != (2, nq, d) or qb.shape != (nq, d) or sq.numel() != nq or qnorm.numel() != nq \
+            or not (q32.is_contiguous() and qd.is_contiguous() and qb.is_contiguous()):
+        raise ValueError("topk_prep_queries_i8: contiguous q32 [nq, d], qd [2, nq, d], qb [nq, d], sq / qnorm [nq]")
+    call("cldrd_topk_prep_queries_i8", _p(q32), _p(qd), _p(qb), _p(sq), _p(qnorm), nq, d, _p(flag), _stream())
+
+
+def topk_thresholds_i8(est, sq, qnorm, b1, cnorm, d, thr, eps):
+    _chk(sq, F32, "sq", 1), _chk(qnorm, F32, "qnorm", 1), _chk(eps, F32, "eps", 1)
+    if sq.numel() != qnorm.numel() or eps.numel() != qnorm.numel():
+        raise ValueError("topk_thresholds_i8: sq, qnorm and eps are [nq]")
+    call("cldrd_topk_thresholds_i8", _p(est), _p(sq), _p(qnorm), float(b1), float(cnorm), int(d), _p(thr), _p(eps), qnorm.numel(), _stream())
+
+
+def topk_scan_i8(qd, sq, thr, R8, scale, counts, cand_rows, cand_scores):
+    """Every (query, row) with scan score >= thr[query] -> the query's candidate list; ``qd`` int8 [2, nq, d] with nq <= 256, ``counts`` int32
+    [nq + 1] zeroed by the caller (cldrd_topk_scan_i8)."""
+    _chk(qd, I8, "qd", 3), _chk(sq, F32, "sq", 1), _chk(thr, F32, "thr", 1), _chk(R8, I8, "R8", 2), _chk(scale, F32, "scale", 1)
+    _chk(counts, torch.int32, "counts", 1), _chk(cand_rows, torch.int32, "cand_rows", 2), _chk(cand_scores, F32, "cand_scores", 2)
+    _, nq, d = qd.shape
+    _chk_i8_width(d, "topk_scan_i8")
+    if qd.shape[0] != 2 or R8.shape[1] != d or scale.numel() != R8.shape[0] or sq.numel() != nq or thr.numel() != nq or counts.numel() < nq + 1 \
+            or cand_rows.shape != cand_scores.shape or cand_rows.shape[0] < nq \
+            or not (qd.is_contiguous() and R8.is_contiguous() and scale.is_contiguous() and cand_rows.is_contiguous() and cand_scores.is_contiguous()):
+        raise ValueError("topk_scan_i8: shape mismatch (counts needs nq + 1 entries)")
+    call("cldrd_topk_scan_i8", _p(qd), nq, _p(sq), _p(thr), _p(R8), _p(scale), nq, R8.shape[0], d, _p(counts), _p(cand_rows), _p(cand_scores),
+         cand_rows.shape[1], _stream())
+
+
+def topk_rescore_i8(q32, R8, scale, qmu, counts, cand_rows, cand_scores):
+    """cand_scores[q, c] = fp32(qmu[q] + scale[row] * <q32[q], R8[row]>) for c < counts[q], sums and product in fp64 (cldrd_topk_rescore_i8)"""
+    _chk(q32, F32, "q32", 2), _chk(R8, I8, "R8", 2), _chk(scale, F32, "scale", 1), _chk(qmu, torch.float64, "qmu", 1)
+    _chk(counts, torch.int32, "counts", 1), _chk(cand_rows, torch.int32, "cand_rows", 2), _chk(cand_scores, F32, "cand_scores", 2)
+    _chk_i8_width(q32.shape[1], "topk_rescore_i8")
+    if not (q32.is_contiguous() and R8.is_contiguous() and scale.is_contiguous() and cand_rows.is_contiguous() and cand_scores.is_contiguous()):
+        raise ValueError("topk_rescore_i8: operands must be contiguous")
+    if R8.shape[1] != q32.shape[1] or scale.numel() != R8.shape[0] or qmu.numel() < q32.shape[0] or counts.numel() < q32.shape[0] \
+            or cand_rows.shape != cand_scores.shape or cand_rows.shape[0] < q32.shape[0]:
+        raise ValueError("topk_rescore_i8: shape mismatch")
+    call("cldrd_topk_rescore_i8", _p(q32), _p(R8), _p(scale), _p(qmu), q32.shape[1], _p(counts), _p(cand_rows), _p(cand_scores), q32.shape[0],
+         cand_rows.shape[1], _stream())
+
+
+def flatip_search_i8(q32, qd, sq, thr, eps, R8, scale, qmu, k, counts, cand_rows, cand_scores, rows2, scores2, n2, status, khat, D, I,
+                     exhaustive=False, qtile=128):
+    """The whole search of one shard in int8-row mode (include/cldrd_hip.h: cldrd_flatip_search_i8): the buffers and the counts / status / n2 /
+    khat contract of :func:`flatip_search`; ``qd`` / ``sq`` may be None on an exhaustive search."""
+    _chk(q32, F32, "q32", 2), _chk(thr, F32, "thr", 1), _chk(eps, F32, "eps", 1), _chk(D, F32, "D", 2), _chk(I, torch.int32, "I", 2)
+    _chk(R8, I8, "R8", 2), _chk(scale, F32, "scale", 1), _chk(qmu, torch.float64, "qmu", 1)
+    nq, d = q32.shape
+    _chk_i8_width(d, "flatip_search_i8")
+    if not exhaustive:
+        _chk(qd, I8, "qd", 3), _chk(sq, F32, "sq", 1)
+        if qd.shape != (2, nq, d) or sq.numel() != nq or not qd.is_contiguous():
+            raise ValueError("flatip_search_i8: qd must be the contiguous [2, nq, d] digit planes of these queries, sq [nq]")
+    if R8.shape[1] != d or scale.numel() != R8.shape[0] or qmu.numel() < nq:
+        raise ValueError("flatip_search_i8: the rows must be [rows, d], their scales [rows] and qmu [nq]")
+    if cand_rows.shape[0] < qtile or rows2.shape[0] < qtile:
+        raise ValueError("flatip_search_i8: the candidate buffers need qtile rows")
+    if counts.numel() < ((nq + qtile - 1) // qtile) * (qtile + 1) or n2.numel() < nq or status.numel() < nq or khat.numel() < nq or D.shape != (nq, k) or I.shape != (nq, k):
+        raise ValueError("flatip_search_i8: buffer sizes do not match nq / k")
+    if not (q32.is_contiguous() and R8.is_contiguous() and scale.is_contiguous() and D.is_contiguous() and I.is_contiguous() and qmu.is_contiguous()):
+        raise ValueError("flatip_search_i8: operands must be contiguous")
+    call("cldrd_flatip_search_i8", _p(q32), _p(qd), _p(sq), _p(thr), _p(eps), _p(R8), _p(scale), _p(qmu), R8.shape[0], d, nq, int(k), int(qtile),
+         _p(counts), _p(cand_rows), _p(cand_scores), cand_rows.shape[1], _p(rows2), _p(scores2), rows2.shape[1], _p(n2), _p(status), _p(khat),
+         _p(D), _p(I), 1 if exhaustive else 0, _stream())
+
+
 def map_ids(I32, ids_table, id_offset):
     """row positions int32 [...] -> ids int64 [...] on the device: the id table when there is one, else position + id_offset; -1 stays -1"""
     _chk(I32, torch.int32, "I32")

@@ -3,7 +3,7 @@
 other run files (100.6 M lines each at 503 k queries x top-200).
 
     python -m cldrd_amd.retriever.build_stage_file --resume CKPT --model_name_or_path STUDENT --tokenizer_name_or_path TOK [--share_weights] \\
-        --index_path IDX [--use_float16] --queries_path Q.tsv --collection_path C.tsv [--query_max_len 30] [--top_k 200] \\
+        --index_path IDX [--use_float16 | --use_int8] --queries_path Q.tsv --collection_path C.tsv [--query_max_len 30] [--top_k 200] \\
         --teacher_name_or_path DIR [--teacher_tokenizer_name_or_path TOK] [--teacher_max_len 256] [--teacher_batch_size 2048] \\
         [--token_cache_dir DIR] --label_mode M [--most_hard_ranks LO:HI] [--semi_hard_ranks LO:HI] [--n_most_hard N] [--seed S] \\
         [--with_scores] --output_path train.json [--student_run_path RUN] [--teacher_run_path RUN] \\
@@ -63,9 +63,13 @@ def get_args(argv=None):
     ap.add_argument("--output_path", required=True)
     ap.add_argument("--student_run_path", default="", help="also write the student's run (what retrieve_top_passages writes)")
     ap.add_argument("--teacher_run_path", default="", help="also write the teacher-ranked run (what rerank_top_passages writes)")
+    ap.add_argument("--use_int8", action="store_true", default=False, help="attach the index in int8-row mode (excludes --use_float16)")
     from .score_store import add_arguments
     add_arguments(ap)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.use_int8 and args.use_float16:
+        ap.error("--use_int8 and --use_float16 exclude one another")
+    return args
 
 
 def read_query_ids(path) -> np.ndarray:
@@ -144,7 +148,7 @@ def main(args):
     query_embs, query_ids = get_embeddings_from_scratch(model, loader, use_fp16=True, is_query=True, show_progress_bar=True)
     del model
     lap("encode_queries_s")
-    index = convert_index_to_gpu(index, 0, bool(args.use_float16))
+    index = index.to_gpu(0, int8_rows=True) if getattr(args, "use_int8", False) else convert_index_to_gpu(index, 0, bool(args.use_float16))
     lap("index_to_gpu_s")
     q_dev = torch.from_numpy(np.ascontiguousarray(query_embs, dtype=np.float32)).to(dev)
     student_scores, pid = index.search_ids_device(q_dev, k)            # fp32 [nq, k], int64 [nq, k] in HBM

@@ -2,7 +2,7 @@
 the collection with the passage tower, build the flat inner-product index with ids, write it plus ``meta.pkl``.
 
 Same flags; extra: ``--synthetic_rows N`` (encode N synthetic MSMARCO-shaped passages instead of ``--passages_path``), ``--index_fp16``
-(write the fp16-row index format, ``retrieval_utils.FlatIPIndex.write``) and
+(write the fp16-row index format, ``retrieval_utils.FlatIPIndex.write``), ``--index_int8`` (write the int8-row format; excludes ``--index_fp16``) and
 ``--rank/--world`` style sharding through torch.distributed env vars: rank r encodes and stores the contiguous shard r
 (independent units, no collective)."""
 from __future__ import annotations
@@ -37,6 +37,7 @@ _FLAGS = {
     "token_cache_stem": dict(default=""),                 # ours: memory-map an EXISTING token cache by its file stem (no collection / tokenizer opened)
     "loader_workers": dict(type=int, default=2),          # ours: DataLoader workers of the token-cache path
     "index_fp16": dict(action="store_true", default=False),      # ours: write the fp16-row index format (mean row + centred fp16 rows: half the file)
+    "index_int8": dict(action="store_true", default=False),      # ours: write the int8-row index format (mean row + int8 rows + one scale per row: a quarter of the file)
     "fp32_encode": dict(action="store_true", default=False),     # ours: encode with the exact fp32 evaluation pass (get_embeddings_from_scratch(use_fp16=False))
     "bucket_window": dict(type=int, default=16384),       # ours (token-cache path): rows are batched by LENGTH inside windows of this many rows (0: 512 consecutive rows)
 }
@@ -47,6 +48,8 @@ def get_args(argv=None):
     for name, kw in _FLAGS.items():
         ap.add_argument("--" + name, **kw)
     args = ap.parse_args(argv)
+    if args.index_fp16 and args.index_int8:
+        ap.error("--index_fp16 and --index_int8 exclude one another")
     args.max_length = int(args.max_length)      # a str when given on the command line (the reference declares no type)
     os.makedirs(args.index_dir, exist_ok=True)
     return args
@@ -125,7 +128,9 @@ def main(args):
     lap("index_build_s")
     stem = Path(args.resume).stem.split(".")[0] if args.resume else "random_init"
     index_path = os.path.join(args.index_dir, stem + (f".shard{rank}of{world}" if world > 1 else "") + ".index")
-    if getattr(args, "index_fp16", False):
+    if getattr(args, "index_int8", False):
+        write_index(index, index_path, int8=True)        # quantised at write time from the fp32 rows of the encode loop
+    elif getattr(args, "index_fp16", False):
         write_index(index, index_path, fp16=True)        # the encode loop delivered fp32 rows; they are centred and cast at write time
     else:
         write_index(index, index_path)

@@ -53,6 +53,7 @@ ATTACH_CHUNK_ROWS = 65536    # fp16-row mode: fp32 rows reach the GPU in chunks 
 HOST_CHUNK_ROWS = 16384      # fp16-row file written from a host index: rows converted per numpy step
 FORMAT_F32 = "cldrd-flatip-v1"
 FORMAT_F16 = "cldrd-flatip-f16-v1"
+FORMAT_I8 = "cldrd-flatip-i8-v1"
 PROGRESS_HOOK = None         # tools: callable(timings dict) every 500 batches of get_embeddings_from_scratch
 _MERGE_DEVICE, _MERGE_HOST = "device (cldrd_merge_topk_device)", "host (cldrd_merge_topk)"       # last_merge["path"] of a sharded search
 
@@ -201,7 +202,7 @@ class _Resident:
     """What an attached shard keeps in HBM and what the search needs to know about it.  Built completely by ``FlatIPIndex._attach`` and
     never changed afterwards, except for the lazily filled members at the end."""
     device: torch.device
-    p16: torch.Tensor            # fp16 [n, d] = fp16(p - mu): what the scan reads; in fp16-row mode also the stored rows
+    p16: object                  # fp16 [n, d] = fp16(p - mu): what the scan reads; in fp16-row mode also the stored rows; None = int8-row mode
     p32: object                  # fp32 [n, d], the rows the re-score reads; None = fp16-row mode
     mu: torch.Tensor             # fp32 [d]: mean row of the shard
     sample: torch.Tensor         # bf16 [s_rows rounded up to 8, d]: every s_stride-th centred row (threshold estimate)
@@ -211,9 +212,16 @@ class _Resident:
     raw_max: float               # max |p|
     max_norm: float              # the norm the eps bound multiplies (FlatIPIndex._attach)
     query_tile: int              # queries per pass over the index bytes
+    r8: object = None            # int8-row mode: int8 [n, d], the quantised centred rows (scan operand AND stored rows) ...
+    scale: object = None         # ... and fp32 [n], their scales a_r: the stored row is mu + a_r R8[r]
+    b1: float = 0.0              # int8-row mode: max_r a_r |R8[r]|_1, what the query-digit term of eps multiplies
     ids_dev: object = None       # int64 [n]: the id table, uploaded by the first search that maps ids
     mu_host: object = None       # np.float32 [d]: the host copy of mu, made when first asked for
     ws: dict = dataclasses.field(default_factory=dict)       # cap2 -> per-batch scratch of the search
+
+    @property
+    def n(self) -> int:
+        return (self.p16 if self.r8 is None else self.r8).shape[0]
 
 
 def _host_tensor(a: np.ndarray) -> torch.Tensor:
@@ -226,6 +234,14 @@ def _host_tensor(a: np.ndarray) -> torch.Tensor:
 def _sel(t, sel):
     """the entries ``sel`` (a slice or an index tensor) of a per-query tensor that may be None"""
     return None if t is None else (t[sel] if isinstance(sel, slice) else t.index_select(0, sel))
+
+
+def _sel_scan(qs, sel):
+    """:func:`_sel` of the queries' scan operand: the fp16 copy [nq, d], or in int8-row mode the pair (digit planes int8 [2, nq, d], sq [nq])"""
+    if isinstance(qs, tuple):
+        qd = qs[0][:, sel] if isinstance(sel, slice) else qs[0].index_select(1, sel)
+        return qd.contiguous(), _sel(qs[1], sel)
+    return _sel(qs, sel)
 
 
 def _all_missing(nq: int, k: int):
@@ -296,8 +312,19 @@ class FlatIPIndex:
     embeddings the stored rows are closer to the fp32 ones.  ``mu`` is the fp32 value of the fp64 column mean; a host-written file and a
     device-attached index of the same rows may differ in the last bit of ``mu`` and therefore of a few ``R16`` values.
 
+    **int8-row mode** (``to_gpu(dev, int8_rows=True)`` or an index read from an int8-row file; ``row_dtype == "int8"``; ``d % 64 == 0``,
+    ``d <= 2048``): the shard keeps ``mu``, ``R8`` (int8 [n, d]) and ``a`` (fp32 [n]) - ``d + 4`` bytes per row.  With ``c = p - mu`` (fp32):
+    ``a_r = max_j |c_j| / 127``, ``R8[r, j] = clamp(rint(c_j / a_r), -127, 127)`` (correctly rounded fp32 divisions, half to even; an all-zero
+    ``c`` gives ``a_r = 0``), the stored row is ``mu + a_r R8[r]`` and
+
+        s(q, r) = fp32( sum_j q_j mu_j + a_r sum_j q_j R8[r, j] )       both sums and the product in fp64, one rounding
+
+    The scan runs on the i8 MFMA with the query split into two int8 digits; its integer sums are exact, so the scan's only error is the
+    rounding of the query, and the top-k of ``s`` is PROVEN as in the other modes (csrc/topk_i8.hip derives the bound).  What is approximate
+    is the stored row, not the search: rankings differ from the fp32 rows' where quantisation moves a score across a neighbour's.
+
     State.  Host side: ``embeddings`` / ``ids`` / ``id_offset``, or - an index read from an fp16-row file - ``_file16`` (its rows, ``mu`` and
-    norms).  Device side: ONE :class:`_Resident` in ``_res``, None until an attach has succeeded: :meth:`_attach` assigns it as its last
+    norms), or - read from an int8-row file - ``_file8`` (``R8``, ``a``, ``mu``, the bound's two maxima, max |p|).  Device side: ONE :class:`_Resident` in ``_res``, None until an attach has succeeded: :meth:`_attach` assigns it as its last
     statement, :meth:`add_with_ids` drops it.  ``device``, ``query_tile``, ``_p16``, ``_p32``, ``_sample`` and
     ``_max_norm`` are read-only views of it (what bench.py, the tools and the tests read)."""
 
@@ -309,6 +336,8 @@ class FlatIPIndex:
         self.id_offset = 0
         self._file16 = None          # an index read from an fp16-row file (no fp32 rows anywhere): (np.float16 [n, d] = fp16(p - mu),
                                      # np.float32 mu [d], max |p - mu|, max |p|) as the file holds them
+        self._file8 = None           # an index read from an int8-row file: (np.int8 [n, d] R8, np.float32 a [n], np.float32 mu [d],
+                                     # max a_r |R8[r]|_1, max a_r |R8[r]|_2, max |p|) as the file holds them
         self._res = None             # _Resident: the attached shard
         self.last_stats = {}
         self.profile = False          # bench.py: time the search with HIP events and count candidates
@@ -324,7 +353,10 @@ class FlatIPIndex:
 
     @property
     def row_dtype(self) -> str:
-        """``"float16"``: fp16-row mode (attached with ``fp16_rows=True`` or read from an fp16-row file); ``"float32"`` otherwise."""
+        """``"float16"``: fp16-row mode (attached with ``fp16_rows=True`` or read from an fp16-row file); ``"int8"``: int8-row mode (attached with
+        ``int8_rows=True`` or read from an int8-row file); ``"float32"`` otherwise."""
+        if self._file8 is not None or (self._res is not None and self._res.r8 is not None):
+            return "int8"
         return "float16" if (self._file16 is not None or (self._res is not None and self._res.p32 is None)) else "float32"
 
     @property
@@ -336,6 +368,8 @@ class FlatIPIndex:
             mu = self._res.mu_host
         elif self._file16 is not None:
             mu = self._file16[1]
+        elif self._file8 is not None:
+            mu = self._file8[2]
         else:
             return None
         out = mu.view()
@@ -346,6 +380,8 @@ class FlatIPIndex:
     def add_with_ids(self, embeddings, ids):
         if self._file16 is not None:
             raise ValueError("an index read from an fp16-row file holds no fp32 rows: rows cannot be added to it")
+        if self._file8 is not None:
+            raise ValueError("an index read from an int8-row file holds no fp32 rows: rows cannot be added to it")
         emb = np.ascontiguousarray(embeddings, dtype=np.float32)
         if emb.ndim != 2 or emb.shape[1] != self.d:
             raise ValueError("embeddings must be [n, d]")
@@ -364,28 +400,44 @@ class FlatIPIndex:
         self.add_with_ids(embeddings, None)
 
     @classmethod
-    def from_device_rows(cls, rows32: torch.Tensor, id_offset: int = 0, fp16_rows: bool = False) -> "FlatIPIndex":
+    def from_device_rows(cls, rows32: torch.Tensor, id_offset: int = 0, fp16_rows: bool = False, int8_rows: bool = False) -> "FlatIPIndex":
         """Index over fp32 rows that already live in HBM (e.g. an encode shard that never left the GPU).  ``fp16_rows``: centre + cast on the
-        device and keep no reference to ``rows32`` (fp16-row mode, class docstring)."""
+        device and keep no reference to ``rows32`` (fp16-row mode, class docstring); ``int8_rows``: the same into int8-row mode."""
+        if fp16_rows and int8_rows:
+            raise ValueError("FlatIPIndex.from_device_rows: fp16_rows and int8_rows exclude one another")
         idx = cls(rows32.shape[1])
         n = idx.ntotal = rows32.shape[0]
         idx.id_offset = id_offset
         rows32 = rows32.contiguous()
-        if fp16_rows:
+        if int8_rows:
+            idx._attach8(rows32.device, n, lambda: ((lo, rows32[lo:lo + ATTACH_CHUNK_ROWS]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
+        elif fp16_rows:
             idx._attach(rows32.device, n, lambda: ((lo, rows32[lo:lo + ATTACH_CHUNK_ROWS]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
         else:
             idx._attach(rows32.device, n, lambda: ((0, rows32),), keep32=rows32)
         return idx
 
-    def to_gpu(self, device, fp16_rows: bool = False):
+    def to_gpu(self, device, fp16_rows: bool = False, int8_rows: bool = False):
         """Make the shard resident in HBM.  Default: fp32 rows (exact re-score), fp16 shadow (scan), bf16 row sample (threshold).
         ``fp16_rows=True`` (or an index read from an fp16-row file, whatever the argument says): fp16-row mode - only ``mu``, the centred fp16
-        rows and the sample become resident; the fp32 rows pass through two staging buffers of ``ATTACH_CHUNK_ROWS`` rows."""
+        rows and the sample become resident; the fp32 rows pass through two staging buffers of ``ATTACH_CHUNK_ROWS`` rows.
+        ``int8_rows=True`` (or an index read from an int8-row file, whatever the arguments say): int8-row mode - ``mu``, the int8 rows, their
+        scales and the sample, staged the same way.  The two flags exclude one another."""
+        if fp16_rows and int8_rows:
+            raise ValueError("FlatIPIndex.to_gpu: fp16_rows and int8_rows exclude one another")
         device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("FlatIPIndex.search runs on the GPU only (no CPU path)")
-        if self._file16 is not None:
+        if self._file8 is not None:
+            self._attach8(device, self._file8[0].shape[0], None)
+        elif self._file16 is not None:
+            if int8_rows:
+                raise ValueError("FlatIPIndex.to_gpu: this index holds fp16 rows only (read from an fp16-row file): int8 rows are quantised from fp32 rows")
             self._attach(device, self._file16[0].shape[0], None)
+        elif int8_rows:
+            if self.embeddings is None:
+                raise ValueError("FlatIPIndex.to_gpu: the index holds no rows")
+            self._attach8(device, self.embeddings.shape[0], lambda: self._staged_chunks(device))
         elif fp16_rows:
             if self.embeddings is None:
                 raise ValueError("FlatIPIndex.to_gpu: the index holds no rows")
@@ -424,6 +476,78 @@ class FlatIPIndex:
             cur.wait_stream(side)
             cur.synchronize()            # the staging buffers go back to the allocator only when nothing reads or writes them
 
+    def _shard_stats(self, device, n: int, chunks, one_chunk: bool):
+        """First walk of an attach over fp32 chunks: max |p|^2 and the mean row of every chunk (cldrd_row_sqnorm_max, cldrd_index_col_mean: fp64
+        column sums) -> (mu on the device, its host copy or None, max |p|)."""
+        raw = torch.zeros(1, dtype=torch.int32, device=device)
+        means, sizes = [], []
+        for lo, c in chunks():
+            ops.row_sqnorm_max_into(c, raw)
+            means.append(ops.index_col_mean(c))
+            sizes.append(c.shape[0])
+        del c                        # the last view of a staging buffer: the second walk allocates its own
+        raw_max = math.sqrt(float(raw.view(torch.float32).item()))
+        if not math.isfinite(raw_max):
+            return torch.zeros(self.d, dtype=torch.float32, device=device), None, raw_max
+        if one_chunk:
+            return means[0], None, raw_max            # one chunk: the device's mean row as it is
+        # the chunk means combined on the host in fp64 weighted by chunk size (mu depends neither on the device nor on timing;
+        # it need not equal the fp32 mode's mu bit for bit)
+        w = np.asarray(sizes, dtype=np.float64)[:, None]
+        mu_h = ((torch.stack(means).cpu().numpy().astype(np.float64) * w).sum(axis=0) / float(n)).astype(np.float32)
+        return torch.from_numpy(mu_h).to(device), mu_h, raw_max
+
+    def _new_sample(self, device, n: int):
+        """-> (s_stride, s_rows, the zeroed bf16 sample buffer).  The threshold sample: SAMPLE_ROWS rows, or 1 / 64 of the rows on a larger index
+        (the whole 8.84 M-row collection on one GPU: with 16 384 rows the expected number of sample rows inside the top 1000 is 1.9, the estimate
+        is the 9th largest sample score and the candidate lists come out at ~6 300 +- 2 000 of their 8 192 slots: overflowing queries, one or two
+        extra passes; with 138 k rows ~2 300).  The GEMM wants a column count that is a multiple of 8: zero rows pad the sample (never read by
+        the select)."""
+        s_stride = max(1, n // min(max(SAMPLE_ROWS, n // 64), 1 << 18))
+        s_rows = min(n, (n + s_stride - 1) // s_stride)
+        return s_stride, s_rows, torch.zeros((s_rows + 7) // 8 * 8, self.d, dtype=torch.bfloat16, device=device)
+
+    def _attach8(self, device, n: int, chunks):
+        """The attach of int8-row mode.  ``chunks()`` as in :meth:`_attach`, walked twice: statistics (``mu``), then cldrd_index_quantize_i8 per
+        chunk - ``R8``, ``a``, the bf16 sample of the stored centred rows and the two maxima of the bound, max_r a_r |R8[r]|_1 and
+        max_r a_r |R8[r]|_2.  ``chunks=None``: an index read from an int8-row file - ``R8`` / ``a`` go to HBM as they are, ``mu`` and the maxima
+        come from the file, the sample rows are dequantised on the host (every s_stride-th row)."""
+        d, file8 = self.d, self._file8 if chunks is None else None
+        if d % 64 or d > 2048 or d <= 0:
+            raise ValueError(f"FlatIPIndex: int8-row mode supports an embedding width that is a multiple of 64 and at most 2048, got {d}")
+        if n <= 0:
+            raise ValueError("FlatIPIndex: no rows to attach")
+        i32 = dict(dtype=torch.int32, device=device)
+        with torch.cuda.device(device):
+            s_stride, s_rows, sample = self._new_sample(device, n)
+            r8 = torch.empty(n, d, dtype=torch.int8, device=device)
+            scale = torch.empty(n, dtype=torch.float32, device=device)
+            flag = 0
+            if file8 is not None:
+                mu_h, b1, cnorm, raw_max = file8[2], file8[3], file8[4], file8[5]
+                mu = torch.from_numpy(np.ascontiguousarray(mu_h, dtype=np.float32)).to(device)
+                for lo in range(0, n, ATTACH_CHUNK_ROWS):
+                    r8[lo:lo + ATTACH_CHUNK_ROWS].copy_(_host_tensor(np.ascontiguousarray(file8[0][lo:lo + ATTACH_CHUNK_ROWS])))
+                scale.copy_(_host_tensor(np.ascontiguousarray(file8[1], dtype=np.float32)))
+                for lo in range(0, s_rows, HOST_CHUNK_ROWS):
+                    sel = np.arange(lo, min(s_rows, lo + HOST_CHUNK_ROWS)) * s_stride
+                    rows = file8[1][sel][:, None] * np.asarray(file8[0][sel], dtype=np.float32)       # fp32 products, as the device forms them
+                    sample[lo:lo + sel.size].copy_(torch.from_numpy(rows).to(torch.bfloat16))
+            else:
+                mu, mu_h, raw_max = self._shard_stats(device, n, chunks, one_chunk=False)
+                flag_d, b1_d, c2_d = torch.zeros(1, **i32), torch.zeros(1, **i32), torch.zeros(1, **i32)
+                for lo, c in chunks():
+                    m = c.shape[0]
+                    ops.index_quantize_i8(c, mu, r8[lo:lo + m], scale[lo:lo + m], sample, s_stride, s_rows, flag_d, b1_d, c2_d, row0=lo)
+                del c
+                b1 = float(b1_d.view(torch.float32).item())
+                cnorm, flag = math.sqrt(float(c2_d.view(torch.float32).item())), int(flag_d.item())
+        if flag or not (math.isfinite(raw_max) and math.isfinite(b1) and math.isfinite(cnorm)):
+            raise ValueError("FlatIPIndex: embeddings must be finite for the int8 rows")
+        # the bound's two norms with the slack of their own fp32 rounding (csrc/topk_i8.hip: thresholds_i8_kernel)
+        self._res = _Resident(device=device, p16=None, p32=None, mu=mu, sample=sample, s_stride=s_stride, s_rows=s_rows, cnorm=cnorm,
+                              raw_max=raw_max, max_norm=cnorm * (1.0 + 1e-6), query_tile=128, mu_host=mu_h, r8=r8, scale=scale, b1=b1)
+
     def _attach(self, device, n: int, chunks, keep32=None):
         """Every attach.  ``chunks()`` yields (first row, fp32 device tensor) over the shard in order and is walked twice (statistics, then
         centre + cast); the fp32 form is the one-chunk case over the whole tensor, which ``keep32`` keeps resident for the re-score.
@@ -453,32 +577,8 @@ class FlatIPIndex:
                 mu_h, cnorm, raw_max = file16[1], file16[2], file16[3]
                 mu = torch.from_numpy(np.ascontiguousarray(mu_h, dtype=np.float32)).to(device)
             else:
-                raw = torch.zeros(1, **i32)
-                means, sizes = [], []
-                for lo, c in chunks():
-                    ops.row_sqnorm_max_into(c, raw)
-                    means.append(ops.index_col_mean(c))
-                    sizes.append(c.shape[0])
-                del c                        # the last view of a staging buffer: the second walk allocates its own
-                raw_max = math.sqrt(float(raw.view(torch.float32).item()))
-                if not math.isfinite(raw_max):
-                    mu = torch.zeros(d, dtype=torch.float32, device=device)
-                elif keep32 is not None:
-                    mu = means[0]            # one chunk: the device's mean row as it is
-                else:
-                    # the chunk means combined on the host in fp64 weighted by chunk size (mu depends neither on the device nor on timing;
-                    # it need not equal the fp32 mode's mu bit for bit)
-                    w = np.asarray(sizes, dtype=np.float64)[:, None]
-                    mu_h = ((torch.stack(means).cpu().numpy().astype(np.float64) * w).sum(axis=0) / float(n)).astype(np.float32)
-                    mu = torch.from_numpy(mu_h).to(device)
-                del means
-            # the threshold sample: SAMPLE_ROWS rows, or 1 / 64 of the rows on a larger index (the whole 8.84 M-row collection on one GPU:
-            # with 16 384 rows the expected number of sample rows inside the top 1000 is 1.9, the estimate is the 9th largest sample score
-            # and the candidate lists come out at ~6 300 +- 2 000 of their 8 192 slots: overflowing queries, one or two extra passes; with
-            # 138 k rows ~2 300).  The GEMM wants a column count that is a multiple of 8: zero rows pad the sample (never read by the select)
-            s_stride = max(1, n // min(max(SAMPLE_ROWS, n // 64), 1 << 18))
-            s_rows = min(n, (n + s_stride - 1) // s_stride)
-            sample = torch.zeros((s_rows + 7) // 8 * 8, d, dtype=torch.bfloat16, device=device)
+                mu, mu_h, raw_max = self._shard_stats(device, n, chunks, one_chunk=keep32 is not None)
+            s_stride, s_rows, sample = self._new_sample(device, n)
             p16 = torch.empty(n, d, dtype=torch.float16, device=device)
             # centre + cast: fp16 rows + max centred norm + bf16 sample + range flag in ONE pass per chunk (cldrd_index_center_cast)
             flag = 0
@@ -541,7 +641,7 @@ class FlatIPIndex:
         [nq, k], -1 = missing) and the statistics dict.  ONE host synchronisation (the proof flags) when nothing is redone."""
         res = self._res
         dev, QT = res.device, res.query_tile
-        n, d = res.p16.shape
+        n, d = res.n, self.d
         nq = q32.shape[0]
         kk = min(k, n)
         exhaustive = n <= CAND_CAP
@@ -551,13 +651,18 @@ class FlatIPIndex:
         i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
         # 0. queries: 16-bit copies, norms, range flag; fp16-row mode: <q, mu> in fp64, added by the re-score
         q32 = q32.contiguous()
-        qh = torch.empty(nq, d, dtype=torch.float16, device=dev)
         qb = torch.empty(nq, d, dtype=torch.bfloat16, device=dev)
         qnorm, flag = torch.empty(nq, **f32), torch.zeros(1, **i32)
-        ops.topk_prep_queries(q32, qh, qb, qnorm, flag)
+        if res.r8 is None:
+            qh = torch.empty(nq, d, dtype=torch.float16, device=dev)
+            ops.topk_prep_queries(q32, qh, qb, qnorm, flag)
+        else:
+            # int8-row mode: the scan's operand of the queries is the pair (digit planes h, l; their common scale sq)
+            qh = (torch.empty(2, nq, d, dtype=torch.int8, device=dev), torch.empty(nq, **f32))
+            ops.topk_prep_queries_i8(q32, qh[0], qb, qh[1], qnorm, flag)
         qmu = ops.query_dot64(q32, res.mu) if res.p32 is None else None
         # 1. thresholds
-        thr, eps = self._estimate_thresholds(qb, qnorm, kk, exhaustive)
+        thr, eps = self._estimate_thresholds(qb, qnorm, kk, exhaustive, sq=None if res.r8 is None else qh[1])
         # 2. the first pass over every query
         stats = dict(scans=0, rescans=0, candidates=0, rescored=0, unproven_first_pass=0, exhaustive=bool(exhaustive))
         cap2 = CAND_CAP if exhaustive else self._cap2(kk)
@@ -573,11 +678,11 @@ class FlatIPIndex:
         probe = 0 if (exhaustive or nq <= 2 * QT or not self.probe) else QT
         if probe:
             head, tail = slice(0, probe), slice(probe, nq)
-            first = self._run(q32[head], qh[head], thr[head], eps[head], _sel(qmu, head), k, cap2, D[head], I[head])
+            first = self._run(q32[head], _sel_scan(qh, head), thr[head], eps[head], _sel(qmu, head), k, cap2, D[head], I[head])
             pr = torch.stack([first[0], first[2]]).cpu().numpy()
             cap2_rest = _cap2_after_probe(cap2, pr[0], pr[1])
             stats["cap2"] = [cap2, cap2_rest]
-            rest = self._run(q32[tail], qh[tail], thr[tail], eps[tail], _sel(qmu, tail), k, cap2_rest, D[tail], I[tail])
+            rest = self._run(q32[tail], _sel_scan(qh, tail), thr[tail], eps[tail], _sel(qmu, tail), k, cap2_rest, D[tail], I[tail])
             st, counts, n2, khat = (torch.cat(pair) for pair in zip(first, rest))
             cap2 = cap2_rest
         else:
@@ -587,7 +692,11 @@ class FlatIPIndex:
         # 3. the proof flags
         status = st.cpu().numpy()                       # the synchronisation of a search (plus the probe's)
         if int(flag.item()):
-            raise ValueError("queries must be finite and inside the fp16 range (|x| <= 65504)")
+            raise ValueError("queries must be finite" + (" and inside the fp16 range (|x| <= 65504)" if res.r8 is None else ""))
+        # int8-row mode: the scan has no on-chip hit list, a hit is lost only to a full candidate list - bit 2 of THAT query; the dropped-hit
+        # counter (bit 4) marks every query of its pass and carries nothing more
+        keep_bits = ~0 if res.r8 is None else ~4
+        status = status & keep_bits
         nb = (nq + QT - 1) // QT
         stats["scans"] = 0 if exhaustive else nb
         stats["query_tile"] = QT
@@ -623,9 +732,9 @@ class FlatIPIndex:
             t_b, tiled, full = _retry_step(status[bad], thr_h[bad], eps_h[bad], khat.cpu().numpy().astype(np.float64)[bad], attempt)
             cap2_b = CAND_CAP if full else cap2
             Db, Ib = torch.empty(bad.size, k, **f32), torch.empty(bad.size, k, **i32)
-            st2, _, _, khat2 = self._run(q32.index_select(0, idx), qh.index_select(0, idx), torch.from_numpy(t_b.astype(np.float32)).to(dev),
+            st2, _, _, khat2 = self._run(q32.index_select(0, idx), _sel_scan(qh, idx), torch.from_numpy(t_b.astype(np.float32)).to(dev),
                                          eps.index_select(0, idx), _sel(qmu, idx), k, cap2_b, Db, Ib, tiled=tiled)
-            status_b = st2.cpu().numpy()
+            status_b = st2.cpu().numpy() & keep_bits
             good = status_b == 0
             if good.any():
                 gi = torch.from_numpy(bad[good]).to(dev)
@@ -645,18 +754,25 @@ class FlatIPIndex:
             bad = bad[~good]
         return D, I, stats
 
-    def _estimate_thresholds(self, qb, qnorm, kk: int, exhaustive: bool):
+    def _estimate_thresholds(self, qb, qnorm, kk: int, exhaustive: bool, sq=None):
         """-> (thr, eps) fp32 [nq] on the device: eps_q bounds |scan score - exact score|, thr_q = est_q - 2 eps_q with est_q the kth largest
-        bf16 score of query q against the row sample (-inf, i.e. every row, on an exhaustive search)."""
+        bf16 score of query q against the row sample (-inf, i.e. every row, on an exhaustive search).  ``sq``: the queries' digit scale
+        (int8-row mode: the bound of csrc/topk_i8.hip)."""
         res, nq = self._res, qb.shape[0]
         f32 = dict(dtype=torch.float32, device=res.device)
         thr, eps = torch.full((nq,), -float("inf"), **f32), torch.empty(nq, **f32)
+
+        def bound(est, thr_out):
+            if res.r8 is None:
+                ops.topk_thresholds(est, qnorm, res.max_norm, self.d, thr_out, eps)
+            else:
+                ops.topk_thresholds_i8(est, sq, qnorm, res.b1, res.max_norm, self.d, thr_out, eps)
         if exhaustive:
-            ops.topk_thresholds(None, qnorm, res.max_norm, self.d, None, eps)
+            bound(None, None)
             return thr, eps
         # lam = expected number of sample rows inside the global top-kk; +4.5 sigma makes a too-high estimate (-> that query is searched
         # again) a ~1e-5 event per query
-        S, n = res.s_rows, res.p16.shape[0]
+        S, n = res.s_rows, res.n
         lam = kk * S / n
         kth = int(min(S, math.ceil(lam + 4.5 * math.sqrt(lam) + 1.0))) if S < n else kk
         est = torch.empty(nq, **f32)
@@ -665,16 +781,16 @@ class FlatIPIndex:
             m = min(EST_CHUNK, nq - lo)
             ops.gemm_nt(qb[lo:lo + m], res.sample, samp[:m], m)
             ops.topk_kth_largest(samp[:m], S, kth, est[lo:lo + m])
-        ops.topk_thresholds(est, qnorm, res.max_norm, self.d, thr, eps)
+        bound(est, thr)
         return thr, eps
 
     def _search_exhaustive_chunks(self, q32: torch.Tensor, k: int):
         """Exact top-k of a few queries with EVERY row re-scored in fp32, CAND_CAP rows at a time (the exhaustive form of
         cldrd_flatip_search on row slices), the running top-k merged with each chunk's by the same sort kernel (score desc, row position
         asc).  The last resort of :meth:`search_device`: reads the fp32 rows once per 128/256 queries, needs no threshold, cannot fail.
-        fp16-row mode: the same over slices of the fp16 rows (scores as the class docstring defines them)."""
+        fp16-row / int8-row mode: the same over slices of the stored rows (scores as the class docstring defines them)."""
         res = self._res
-        n, nq = res.p16.shape[0], q32.shape[0]
+        n, nq = res.n, q32.shape[0]
         qmu = ops.query_dot64(q32.contiguous(), res.mu) if res.p32 is None else None
         if 2 * k > CAND_CAP:
             raise ValueError(f"exact fallback: top_k = {k} > {CAND_CAP // 2}")
@@ -709,17 +825,32 @@ class FlatIPIndex:
         n2 = torch.empty(nq, dtype=torch.int32, device=dev)
         status = torch.empty(nq, dtype=torch.int32, device=dev)
         khat = torch.empty(nq, dtype=torch.float32, device=dev)
+        if res.r8 is not None:
+            qd, sq = qh if qh is not None else (None, None)
+            ops.flatip_search_i8(q32, qd, sq, thr, eps, res.r8[rows], res.scale[rows], qmu, k, counts, ws["cand_rows"], ws["cand_scores"],
+                                 ws["rows2"], ws["scores2"], n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT)
+            return status, counts, n2, khat
         ops.flatip_search(q32, qh, thr, eps, res.p16[rows], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
                           n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled,
                           P32=None if res.p32 is None else res.p32[rows], qmu=qmu)
         return status, counts, n2, khat
 
     # -- persistence (own format; faiss' binary layout is not reproduced) ----------------
-    def write(self, path: str, fp16: bool = False):
+    def write(self, path: str, fp16: bool = False, int8: bool = False):
         """``path.emb.npy`` (fp32 rows) + ``path.meta.pkl``; ``fp16=True``: the fp16-row format - ``path.emb16.npy`` (``R16 = fp16(p - mu)``,
         numpy float16, memory-mappable) and ``mu``, ``max_centred_norm``, ``raw_max_norm`` next to ``d / ids / id_offset`` in the meta file.  An
         index that is on a GPU writes the ``mu`` / ``R16`` it searches with; a host index computes them with numpy in chunks (same definition:
-        ``mu`` = fp32 of the fp64 column mean - the last bit of ``mu``, and with it a few ``R16`` values, may differ between the two)."""
+        ``mu`` = fp32 of the fp64 column mean - the last bit of ``mu``, and with it a few ``R16`` values, may differ between the two).
+        ``int8=True``: the int8-row format - ``path.emb8.npy`` (``R8``, int8 [n, d], memory-mappable), ``path.scale.npy`` (``a``, fp32 [n]) and
+        ``mu``, ``bound_l1`` (max a_r |R8[r]|_1), ``max_centred_norm`` (max a_r |R8[r]|_2), ``raw_max_norm`` in the meta file; an index attached in
+        int8-row mode writes what it searches with, a host index quantises with numpy in chunks (the class docstring's definition; the same
+        last-bit caveat for ``mu``).  The flags exclude one another; a refused call writes nothing."""
+        if fp16 and int8:
+            raise ValueError("FlatIPIndex.write: fp16 and int8 exclude one another")
+        if int8:
+            return self._write8(path)
+        if self._file8 is not None or (self._res is not None and self._res.r8 is not None and self.embeddings is None):
+            raise ValueError("this index holds int8 rows only: write it with int8=True")
         if fp16:
             return self._write16(path)
         if self.embeddings is None:
@@ -728,7 +859,69 @@ class FlatIPIndex:
         with open(path + ".meta.pkl", "wb") as fh:
             pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F32}, fh)
 
+    @staticmethod
+    def quantize_rows_i8(rows32: np.ndarray, mu: np.ndarray):
+        """The definition of int8-row mode on the host, for fp32 rows [m, d] and the shard's mean row: -> (R8 int8 [m, d], a fp32 [m],
+        a_r |R8[r]|_1 and a_r^2 |R8[r]|_2^2 as the fp32 values of the fp64 products with the exact integer sums).  numpy's float32 division is
+        correctly rounded and ``rint`` rounds half to even, as the device kernel does."""
+        c = np.asarray(rows32, dtype=np.float32) - np.asarray(mu, dtype=np.float32)
+        if not np.isfinite(c).all():
+            raise ValueError("FlatIPIndex: embeddings must be finite for the int8 rows")
+        a = (np.abs(c).max(axis=1) / np.float32(127.0)).astype(np.float32)
+        live = a > 0
+        t = np.zeros_like(c)
+        np.divide(c, a[:, None], out=t, where=live[:, None])
+        r8 = np.clip(np.rint(t), -127.0, 127.0).astype(np.int8)
+        r64 = r8.astype(np.int64)
+        a64 = a.astype(np.float64)
+        l1 = (a64 * np.abs(r64).sum(axis=1)).astype(np.float32)
+        l2sq = ((a64 * a64) * (r64 * r64).sum(axis=1)).astype(np.float32)
+        return r8, a, l1, l2sq
+
+    def _write8(self, path: str):
+        def meta(mu, b1, cnorm, raw):
+            with open(path + ".meta.pkl", "wb") as fh:
+                pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_I8, "mu": mu, "bound_l1": float(b1),
+                             "max_centred_norm": float(cnorm), "raw_max_norm": float(raw)}, fh)
+        res = self._res
+        if res is not None and res.r8 is not None:
+            np.save(path + ".emb8.npy", res.r8.cpu().numpy())
+            np.save(path + ".scale.npy", res.scale.cpu().numpy())
+            return meta(np.array(self.mu), res.b1, res.cnorm, res.raw_max)
+        if self._file8 is not None:
+            r8, a, mu, b1, cnorm, raw = self._file8
+            np.save(path + ".emb8.npy", r8)
+            np.save(path + ".scale.npy", a)
+            return meta(mu, b1, cnorm, raw)
+        emb = self.embeddings
+        if emb is None or emb.shape[0] == 0:
+            raise ValueError("FlatIPIndex.write: the index holds no fp32 rows to quantise")
+        n, d = emb.shape
+        if d % 64 or d > 2048:
+            raise ValueError(f"FlatIPIndex: int8-row mode supports an embedding width that is a multiple of 64 and at most 2048, got {d}")
+        colsum, raw_sq = np.zeros(d, dtype=np.float64), 0.0
+        for lo in range(0, n, HOST_CHUNK_ROWS):
+            c = np.asarray(emb[lo:lo + HOST_CHUNK_ROWS], dtype=np.float32)
+            colsum += c.sum(axis=0, dtype=np.float64)
+            raw_sq = max(raw_sq, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max()))
+        if not (math.isfinite(raw_sq) and np.isfinite(colsum).all()):
+            raise ValueError("FlatIPIndex: embeddings must be finite for the int8 rows")
+        mu = (colsum / float(n)).astype(np.float32)
+        out = np.lib.format.open_memmap(path + ".emb8.npy", mode="w+", dtype=np.int8, shape=(n, d))
+        scale = np.empty(n, dtype=np.float32)
+        b1, c_sq = np.float32(0.0), np.float32(0.0)
+        for lo in range(0, n, HOST_CHUNK_ROWS):
+            r8, a, l1, l2sq = self.quantize_rows_i8(emb[lo:lo + HOST_CHUNK_ROWS], mu)
+            out[lo:lo + r8.shape[0]], scale[lo:lo + r8.shape[0]] = r8, a
+            b1, c_sq = max(b1, l1.max()), max(c_sq, l2sq.max())
+        out.flush()
+        del out
+        np.save(path + ".scale.npy", scale)
+        meta(mu, b1, math.sqrt(float(c_sq)), math.sqrt(float(np.float32(raw_sq))))
+
     def _write16(self, path: str):
+        if self._res is not None and self._res.p16 is None:
+            raise ValueError("this index is attached in int8-row mode: write it with int8=True (or detach it: the fp16 rows come from fp32 rows)")
         if self._res is not None:
             # attached (either mode): the device's centred fp16 rows and statistics
             mu, cnorm, raw = np.array(self.mu), self._res.cnorm, self._res.raw_max
@@ -778,20 +971,35 @@ class FlatIPIndex:
             idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
             idx.ntotal = r16.shape[0]
             return idx
+        if meta.get("format") == FORMAT_I8:
+            r8 = np.load(path + ".emb8.npy", mmap_mode="r")
+            a = np.load(path + ".scale.npy")
+            if r8.dtype != np.int8 or r8.ndim != 2 or r8.shape[1] != idx.d or a.dtype != np.float32 or a.shape != (r8.shape[0],):
+                raise ValueError(f"{path}.emb8.npy / .scale.npy: expected int8 [n, {idx.d}] and float32 [n]")
+            idx._file8 = (r8, a, np.ascontiguousarray(meta["mu"], dtype=np.float32), float(meta["bound_l1"]), float(meta["max_centred_norm"]),
+                          float(meta["raw_max_norm"]))
+            idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
+            idx.ntotal = r8.shape[0]
+            return idx
         idx.embeddings = np.load(path + ".emb.npy", mmap_mode="r")
         idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
         idx.ntotal = idx.embeddings.shape[0]
         return idx
 
 
-def write_index(index: FlatIPIndex, path: str, faiss_format: bool = False, fp16: bool = False):
+def write_index(index: FlatIPIndex, path: str, faiss_format: bool = False, fp16: bool = False, int8: bool = False):
     """``faiss.write_index`` of the reference (index_text.py:103).  Default: this package's memory-mappable pair of files;
     ``faiss_format=True`` writes faiss' own ``IndexIDMap(IndexFlatIP)`` serialisation to ``path`` (see ``write_faiss_index``);
-    ``fp16=True`` writes the fp16-row format (:meth:`FlatIPIndex.write`; not available in faiss' layout)."""
+    ``fp16=True`` writes the fp16-row format, ``int8=True`` the int8-row format (:meth:`FlatIPIndex.write`; neither is available in faiss'
+    layout).  The three flags exclude one another: a call with two of them raises and writes nothing."""
     if faiss_format and fp16:
         raise ValueError("write_index: the fp16-row format exists in this package's own layout only (faiss_format=True with fp16=True)")
+    if int8 and (faiss_format or fp16):
+        raise ValueError("write_index: int8=True excludes faiss_format=True and fp16=True (the int8-row format is this package's own)")
     if faiss_format:
         write_faiss_index(index, path)
+    elif int8:
+        index.write(path, int8=True)
     elif fp16:
         index.write(path, fp16=True)
     else:
@@ -996,7 +1204,8 @@ class MultiDeviceFlatIPIndex:
     (``cldrd_merge_topk_device``; more than 8192 candidates per query: the native host merge).  Order: score desc, ties -> shard asc, then
     list position asc = global row position asc, the single-index rule.  An index without rows answers with all-missing lists.
     The production path for 8 GPUs stays one process per GPU (:class:`ShardedFlatIPIndex`, retrieve_top_passages.py under RANK /
-    WORLD_SIZE): one Python thread drives all devices here."""
+    WORLD_SIZE): one Python thread drives all devices here.  int8-row mode is not offered here (an index read from an int8-row file holds no
+    host rows to shard and is refused like any index without them); a sharded int8 search is one process per GPU."""
 
     def __init__(self, index: FlatIPIndex, devices, fp16_rows: bool = False):
         if not devices:
@@ -1060,7 +1269,9 @@ def convert_index_to_gpu(index, faiss_gpu_index, useFloat16=False):
     intends); the 8-GPU production path is still one process per GPU (:class:`ShardedFlatIPIndex`).  ``useFloat16=False``: fp32 rows and the
     fp16 scan shadow are resident, scores are exact fp32.  ``useFloat16=True``: fp16-row mode (:class:`FlatIPIndex`) - as in faiss the vectors
     live on the GPU in half precision only (a third of the default's bytes) and scores come from the half-precision vectors; unlike faiss the
-    stored vectors are the CENTRED rows ``fp16(p - mu)`` plus ``mu``.  An index read from an fp16-row file is in that mode whatever the flag."""
+    stored vectors are the CENTRED rows ``fp16(p - mu)`` plus ``mu``.  An index read from an fp16-row file is in that mode whatever the flag, and
+    one read from an int8-row file attaches in int8-row mode whatever the flag; int8-row mode on an fp32-format index is
+    ``index.to_gpu(device, int8_rows=True)``."""
     if type(faiss_gpu_index) == list and len(faiss_gpu_index) == 1:
         faiss_gpu_index = faiss_gpu_index[0]
     if isinstance(faiss_gpu_index, int):

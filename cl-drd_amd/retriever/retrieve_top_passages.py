@@ -1,7 +1,8 @@
 """``retriever/retrieve_top_passages.py`` of the reference (:28-109) on MI355X: encode the queries, load the index into HBM,
 search top-k in batches of 128 and write the run file ``qid\\tdocid\\trank\\tscore``.
 
-Same flags; extra: ``--synthetic_queries N``, ``--use_float16`` (fp16-row mode: half-precision rows only in HBM).  With WORLD_SIZE > 1 (one process per GPU) rank r loads index shard r, every
+Same flags; extra: ``--synthetic_queries N``, ``--use_float16`` (fp16-row mode: half-precision rows only in HBM), ``--use_int8`` (int8-row mode: int8 rows and one scale per row; excludes
+``--use_float16``).  With WORLD_SIZE > 1 (one process per GPU) rank r loads index shard r, every
 rank encodes all queries (they are 21 MB), and rank 0 merges the per-shard lists on the host and writes the file."""
 from __future__ import annotations
 
@@ -32,6 +33,7 @@ _FLAGS = {
     "synthetic_queries": dict(type=int, default=0),       # ours: N generated queries instead of --queries_path
     "fp32_encode": dict(action="store_true", default=False),     # ours: encode the queries with the exact fp32 evaluation pass (use_fp16=False)
     "use_float16": dict(action="store_true", default=False),      # ours: attach the index in fp16-row mode (convert_index_to_gpu(..., useFloat16=True))
+    "use_int8": dict(action="store_true", default=False),         # ours: attach an fp32-format index in int8-row mode (FlatIPIndex.to_gpu(dev, int8_rows=True))
 }
 
 
@@ -40,6 +42,8 @@ def get_args(argv=None):
     for name, kw in _FLAGS.items():
         ap.add_argument("--" + name, **kw)
     args = ap.parse_args(argv)
+    if args.use_int8 and args.use_float16:
+        ap.error("--use_int8 and --use_float16 exclude one another")
     args.max_length, args.top_k = int(args.max_length), int(args.top_k)
     return args
 
@@ -128,7 +132,11 @@ def main(args):
     lap("index_read_s")
     # --use_float16: only the centred fp16 rows of an fp32-format file become resident (a third of the bytes; scores from the stored fp16
     # rows).  A file written by index_text --index_fp16 is searched in that mode with or without the flag.
-    index = convert_index_to_gpu(index, local_rank, bool(getattr(args, "use_float16", False)))
+    # --use_int8: the same for int8-row mode; a file written by index_text --index_int8 is searched in that mode with or without the flag.
+    if getattr(args, "use_int8", False):
+        index = index.to_gpu(local_rank, int8_rows=True)
+    else:
+        index = convert_index_to_gpu(index, local_rank, bool(getattr(args, "use_float16", False)))
     lap("index_to_gpu_s")
     index = ShardedFlatIPIndex(index, rank, world)
     # the reference converts every 128-query slice to nested Python lists (retrieval_utils.py:145-146) and loops over 7 M scalars to

@@ -358,6 +358,38 @@ int cldrd_index_col_mean(const float* P, size_t rows, int d, float* mu, void* wo
 int cldrd_index_center_cast(const float* P, const float* mu, size_t rows, size_t row0, int d, void* P16, void* sample_bf16, size_t s_stride,
                             size_t s_rows, unsigned int* cmax_bits, unsigned int* flag, void* stream);
 int cldrd_map_ids(const int* I, const long long* ids, long long id_offset, long long* out, size_t n, void* stream);
+/* int8-row mode (csrc/topk_i8.hip; d % 64 == 0, d <= 2048): the shard keeps mu, R8 (int8 [rows, d]) and a (fp32 [rows]) and no other form of the rows.
+ * With c = p - mu (fp32): a_r = max_j |c_j| / 127, R8[r, j] = clamp(rint(c_j / a_r), -127, 127) (correctly rounded divisions, half to even; an
+ * all-zero c gives a_r = 0, R8[r] = 0).  The stored row is mu + a_r R8[r]; its score is fp32(<q, mu> + a_r <q, R8[r]>), sums and product in fp64, one
+ * rounding.  The scan multiplies int8 query digits (sq = max|q| / 16256, t = rint(q / sq), l = ((t + 64) mod 128) - 64, h = (t - l) / 128) with R8 on
+ * the i8 MFMA, H = <h, R8[r]>, L = <l, R8[r]> exact in int32, and scores s^ = fmaf(128.0f, (float)H, (float)L) * (sq * a_r) in fp32.
+ *   cldrd_index_quantize_i8    one fp32 chunk of a shard (rows [row0, row0 + rows), as cldrd_index_center_cast): R8, a, the bf16 threshold sample of the
+ *                              stored centred rows, *b1_bits / *c2_bits = bit patterns of the fp32 values of max_r a_r |R8[r]|_1 and max_r a_r^2 |R8[r]|_2^2
+ *                              (fp64 products with the exact integer sums), *flag |= 1 for a value that is not finite; the three words accumulate over
+ *                              the chunks (zero them first)
+ *   cldrd_topk_prep_queries_i8 qd = int8 [2, nq, d] (plane 0: h, plane 1: l), sq and |q| (fp32 [nq]), the bf16 copy for the threshold GEMM, *flag |= 1
+ *                              for a value that is not finite.  A query with max|q| < 2^-100 gets zero digits and sq = 2 max|q|
+ *   cldrd_topk_thresholds_i8   eps[q] >= |s^ - a_r <q, R8[r]>| from sq, |q|, b1 = max_r a_r |R8[r]|_1 and cnorm = max_r a_r |R8[r]|_2 (derivation in
+ *                              csrc/topk_i8.hip); thr = est - 2 eps (est may be NULL: eps only)
+ *   cldrd_topk_scan_i8         nq <= 256 queries of the digit planes (`qd` points at this call's first query in plane 0, the planes hold nq_plane queries
+ *                              each) against the rows: every (query, row) with s^ >= thr[query] is appended to the query's list; counts = nq list lengths
+ *                              + 1 counter of the hits that found their list full (those also count in counts[query]), zeroed by the caller
+ *   cldrd_topk_rescore_i8      cand_scores[q][c] = fp32(qmu[q] + a_r <q, R8[row]>) for c < counts[q] (qmu: cldrd_query_dot64)
+ *   cldrd_flatip_search_i8     the chain of cldrd_flatip_search per tile of qtile = 128 queries: scan (exhaustive = 1: every row, rows <= cap) -> select
+ *                              -> rescore_i8 -> sort; the same counts / n2 / status / khat contract */
+int cldrd_index_quantize_i8(const float* P, const float* mu, size_t rows, size_t row0, int d, void* R8, float* scale, void* sample_bf16,
+                            size_t s_stride, size_t s_rows, unsigned int* b1_bits, unsigned int* c2_bits, unsigned int* flag, void* stream);
+int cldrd_topk_prep_queries_i8(const float* q, void* qd, void* q_bf16, float* sq, float* qnorm, int nq, int d, unsigned int* flag, void* stream);
+int cldrd_topk_thresholds_i8(const float* est, const float* sq, const float* qnorm, float b1, float cnorm, int d, float* thr, float* eps, int nq,
+                             void* stream);
+int cldrd_topk_scan_i8(const void* qd, long long nq_plane, const float* sq, const float* thr, const void* R8, const float* scale, int nq,
+                       long long rows, int d, int* counts, int* cand_rows, float* cand_scores, int cap, void* stream);
+int cldrd_topk_rescore_i8(const float* q, const void* R8, const float* scale, const double* qmu, int d, const int* counts, const int* cand_rows,
+                          float* cand_scores, int nq, int cap, void* stream);
+int cldrd_flatip_search_i8(const float* q32, const void* qd, const float* sq, const float* thr, const float* eps, const void* R8,
+                           const float* scale, const double* qmu, long long rows, int d, int nq, int k, int qtile, int* counts, int* cand_rows,
+                           float* cand_scores, int cap, int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D,
+                           int* I, int exhaustive, void* stream);
 
 /* ---- variable-length packing (csrc/pack.hip) -----------------------------------------------------------------------------------
  * The reference pads every sequence of a batch to the longest one (dataset/sequence_dataset.py:50-51, nway_dataset.py:103-107) and the
