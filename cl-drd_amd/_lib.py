@@ -36,6 +36,10 @@ SIGNATURES = {
     "cldrd_gemm_nt_f32": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
     "cldrd_attention_fwd_f32": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_attention_cls_fwd_f32": (ci, [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
+    "cldrd_attention_fwd_hd32": (ci, [vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp]),
+    "cldrd_attention_cls_fwd_hd32": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "cldrd_attention_fwd_f32_hd32": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
+    "cldrd_attention_cls_fwd_f32_hd32": (ci, [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
     "cldrd_attention_bits_words": (C.c_longlong, [ci, ci, ci, cf]),
     "cldrd_add_rows": (ci, [vp, vp, ci, ci, ci, vp, ci, vp]),
     "cldrd_ln_partial_blocks": (ci, [ci]),

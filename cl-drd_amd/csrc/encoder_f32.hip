@@ -15,7 +15,7 @@
 //   W is the fp32 master weight, read in place.  GELU = 0.5 x (1 + erff(x / sqrt 2)) with libm-grade erff, no fast-math intrinsic.
 //
 // cldrd_attention_fwd_f32 / cldrd_attention_cls_fwd_f32   softmax(Q K^T / 8 + key mask) . V, head dim 64, L <= 256, padded rows + int64 mask or
-//   packed rows through cu_rows.  Chosen schedule: STREAMING 32-key blocks with an online softmax, no LDS at all.  One wave owns 32 queries of one
+//   packed rows through cu_rows (the _hd32 pair: the same kernel at head dim 32, scale 1 / sqrt(32), see attention_f32_kernel).  Chosen schedule: STREAMING 32-key blocks with an online softmax, no LDS at all.  One wave owns 32 queries of one
 //   (sequence, head); per key block it computes S^T = K_blk . Q^T (keys in the accumulator rows, queries on the lanes: the softmax reductions run
 //   over a lane's own 16 registers plus one exchange between the lane halves), and the accumulator tile is then the A operand of P . V as it
 //   stands (a product that sums over the tile's row index needs no lane movement).  K rows (as MFMA A operand) and V elements (as B operand)
@@ -26,6 +26,7 @@
 //   The CLS form is the same kernel body given one query row per sequence (qc, with a pitch) and K | V rows of width 2 d: bit for bit row 0
 //   of the full form.  Queries of a wave's tile beyond the sequence are computed on a clamped row and not stored.
 #include "common.h"
+#include <cstdio>
 
 namespace {
 
@@ -115,6 +116,12 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restric
 
 // One wave = 32 queries of one (sequence, head).  q / k / v / o: element 0 of the first row; ld*: row pitches in floats.
 // CLS form: q_per_seq != 0: one query row per sequence (row m of q, pitch ldq; output row m of o).
+// DH: the head dim, 64 or 32.  Lane half h holds head dims DH/2 h .. DH/2 h + DH/2 - 1 of its Q / K row, so the chain of a score adds the head dims
+// 0, DH/2, 1, DH/2 + 1, ... (DH = 32: 0, 16, 1, 17, ..., 15, 31), and the context is DH / 32 accumulator tiles of 32 head dims.  The finished score
+// is multiplied ONCE by 1 / sqrt(DH): 0.125, exact, at 64; at 32 the fp32 nearest to 1 / sqrt(32), which is no power of two - the product rounds
+// once more (two relative errors of 2^-24 on the score, paid for in the tests' bound).  Everything else - key order, masking, skipping - is the
+// same text for both.
+template <int DH>
 __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, const float* __restrict__ v,
                                                              int ldkv, float* __restrict__ o, int ldo, const long long* __restrict__ mask,
                                                              const int* __restrict__ cu, int L, int H, int q_per_seq) {
@@ -135,11 +142,13 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
     if (qt * 32 >= nq) return;
     // Q fragment (B operand): query qt * 32 + r (clamped to the sequence), head dims 32 h .. 32 h + 31
     const int qi = min(qt * 32 + r, nq - 1);
-    const float* qrow = q_per_seq ? q + (size_t)m * ldq + head * 64 : q + (size_t)(row0 + qi) * ldq + head * 64;
-    float qf[32];
+    constexpr int HB = DH / 2;            // head dims per lane half
+    constexpr float SCALE = DH == 64 ? 0.125f : 0.17677669529663688110f;
+    const float* qrow = q_per_seq ? q + (size_t)m * ldq + head * DH : q + (size_t)(row0 + qi) * ldq + head * DH;
+    float qf[HB];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float4 t = *(const float4*)(qrow + 32 * h + 4 * i);
+    for (int i = 0; i < HB / 4; ++i) {
+        const float4 t = *(const float4*)(qrow + HB * h + 4 * i);
         qf[4 * i] = t.x; qf[4 * i + 1] = t.y; qf[4 * i + 2] = t.z; qf[4 * i + 3] = t.w;
     }
     f32x16 o0, o1;                       // context, head dims r and 32 + r of query (e & 3) + 8 (e >> 2) + 4 h
@@ -154,10 +163,10 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
         const unsigned long long valid = __ballot(ok) & 0xFFFFFFFFull;       // bit j: key kb * 32 + j takes part
         if (valid == 0ull) continue;                                        // (wave-uniform)
         // K fragment (A operand): key row, clamped into the sequence; head dims as Q
-        const float* krow = k + (size_t)(row0 + min(key, klen - 1)) * ldkv + head * 64 + 32 * h;
-        float kf[32];
+        const float* krow = k + (size_t)(row0 + min(key, klen - 1)) * ldkv + head * DH + HB * h;
+        float kf[HB];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < HB / 4; ++i) {
             const float4 t = *(const float4*)(krow + 4 * i);
             kf[4 * i] = t.x; kf[4 * i + 1] = t.y; kf[4 * i + 2] = t.z; kf[4 * i + 3] = t.w;
         }
@@ -167,8 +176,8 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
         for (int t = 0; t < 16; ++t) {
             const int j = (t & 3) + 8 * (t >> 2) + 4 * h;
             const bool vj = (valid >> j) & 1ull;
-            const float* vrow = v + (size_t)(row0 + min(kb * 32 + j, klen - 1)) * ldkv + head * 64;
-            const float a = vrow[r], b = vrow[32 + r];
+            const float* vrow = v + (size_t)(row0 + min(kb * 32 + j, klen - 1)) * ldkv + head * DH;
+            const float a = vrow[r], b = DH == 64 ? vrow[DH - 32 + r] : 0.f;
             v0[t] = vj ? a : 0.f;
             v1[t] = vj ? b : 0.f;
         }
@@ -176,13 +185,13 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = 0.f;
 #pragma unroll
-        for (int i = 0; i < 32; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[i], qf[i], s, 0, 0, 0);
+        for (int i = 0; i < HB; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[i], qf[i], s, 0, 0, 0);
         // s[e]: score of key (e & 3) + 8 (e >> 2) + 4 h (block-relative) and query r
         float mx = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int j = (e & 3) + 8 * (e >> 2) + 4 * h;
-            s[e] = ((valid >> j) & 1ull) ? s[e] * 0.125f : -INFINITY;
+            s[e] = ((valid >> j) & 1ull) ? s[e] * SCALE : -INFINITY;
             mx = fmaxf(mx, s[e]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -203,12 +212,12 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
         for (int e = 0; e < 16; ++e) {
             const float ar = __shfl(alpha, (e & 3) + 8 * (e >> 2) + 4 * h, 64);
             o0[e] *= ar;
-            o1[e] *= ar;
+            if constexpr (DH == 64) o1[e] *= ar;
         }
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(s[t], v0[t], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(s[t], v1[t], o1, 0, 0, 0);
+            if constexpr (DH == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(s[t], v1[t], o1, 0, 0, 0);
         }
     }
 #pragma unroll
@@ -217,9 +226,9 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
         const float lr = __shfl(lrun, qq, 64);
         const int qabs = qt * 32 + qq;
         if (qabs >= nq) continue;
-        float* orow = q_per_seq ? o + (size_t)m * ldo + head * 64 : o + (size_t)(row0 + qabs) * ldo + head * 64;
+        float* orow = q_per_seq ? o + (size_t)m * ldo + head * DH : o + (size_t)(row0 + qabs) * ldo + head * DH;
         orow[r] = lr > 0.f ? o0[e] / lr : 0.f;
-        orow[32 + r] = lr > 0.f ? o1[e] / lr : 0.f;
+        if constexpr (DH == 64) orow[32 + r] = lr > 0.f ? o1[e] / lr : 0.f;
     }
 }
 
@@ -245,31 +254,66 @@ extern "C" int cldrd_gemm_nt_f32(const float* A, const float* W, float* C, int M
     return 0;
 }
 
-extern "C" int cldrd_attention_fwd_f32(const float* qkv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L, int H, void* stream) {
-    CLDRD_CHECK(qkv != nullptr, "attention_fwd_f32: null qkv");
-    CLDRD_CHECK(ctx != nullptr, "attention_fwd_f32: null output");
-    CLDRD_CHECK(mask == nullptr || cu_rows == nullptr, "attention_fwd_f32: a packed batch (cu_rows) takes its key mask from the lengths: mask must be NULL");
-    CLDRD_CHECK(nseq > 0 && H > 0 && L > 0 && L <= 256, "attention_fwd_f32: need nseq > 0, H > 0, 0 < L <= 256");
-    CLDRD_CHECK((long long)nseq * H <= 0x7FFFFFFFll && (long long)nseq * L * 3 * H * 64 <= 0x7FFFFFFFFFFll, "attention_fwd_f32: batch too large");
-    CLDRD_CHECK(aligned16(qkv), "attention_fwd_f32: qkv must be 16-byte aligned");
-    const int d = H * 64;
-    hipLaunchKernelGGL(attention_f32_kernel, dim3(nseq * H, (L + 127) / 128), dim3(256), 0, (hipStream_t)stream, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d,
-                       ctx, d, mask, cu_rows, L, H, 0);
+namespace {
+
+// The two attention entry points of a head dim DH: the argument checks (messages under the entry point's own name `op`) and the launch
+int attn_f32_refuse(const char* op, const char* why) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", op, why);
+    return cldrd_set_error(msg);
+}
+#define ATTN_F32_CHECK(cond, why) do { if (!(cond)) return attn_f32_refuse(op, why); } while (0)
+
+template <int DH>
+int attention_f32_full(const char* op, const float* qkv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L, int H, void* stream) {
+    ATTN_F32_CHECK(qkv != nullptr, "null qkv");
+    ATTN_F32_CHECK(ctx != nullptr, "null output");
+    ATTN_F32_CHECK(mask == nullptr || cu_rows == nullptr, "a packed batch (cu_rows) takes its key mask from the lengths: mask must be NULL");
+    ATTN_F32_CHECK(nseq > 0 && H > 0 && L > 0 && L <= 256, "need nseq > 0, H > 0, 0 < L <= 256");
+    ATTN_F32_CHECK((long long)nseq * H <= 0x7FFFFFFFll && (long long)nseq * L * 3 * H * DH <= 0x7FFFFFFFFFFll, "batch too large");
+    ATTN_F32_CHECK(aligned16(qkv), "qkv must be 16-byte aligned");
+    const int d = H * DH;
+    hipLaunchKernelGGL(attention_f32_kernel<DH>, dim3(nseq * H, (L + 127) / 128), dim3(256), 0, (hipStream_t)stream, qkv, 3 * d, qkv + d, qkv + 2 * d,
+                       3 * d, ctx, d, mask, cu_rows, L, H, 0);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int cldrd_attention_cls_fwd_f32(const float* qc, int ldq, const float* kv, const long long* mask, const int* cu_rows, float* ctx, int nseq,
-                                           int L, int H, void* stream) {
-    CLDRD_CHECK(qc != nullptr && kv != nullptr, "attention_cls_fwd_f32: null operand");
-    CLDRD_CHECK(ctx != nullptr, "attention_cls_fwd_f32: null output");
-    CLDRD_CHECK(mask == nullptr || cu_rows == nullptr, "attention_cls_fwd_f32: a packed batch (cu_rows) takes its key mask from the lengths: mask must be NULL");
-    CLDRD_CHECK(nseq > 0 && H > 0 && L > 0 && L <= 256, "attention_cls_fwd_f32: need nseq > 0, H > 0, 0 < L <= 256");
-    CLDRD_CHECK((long long)nseq * H <= 0x7FFFFFFFll, "attention_cls_fwd_f32: batch too large");
-    CLDRD_CHECK(ldq >= H * 64 && ldq % 4 == 0, "attention_cls_fwd_f32: the query row pitch must cover a row and be a multiple of 4");
-    CLDRD_CHECK(aligned16(qc) && aligned16(kv), "attention_cls_fwd_f32: qc and kv must be 16-byte aligned");
-    const int d = H * 64;
-    hipLaunchKernelGGL(attention_f32_kernel, dim3(nseq * H, 1), dim3(64), 0, (hipStream_t)stream, qc, ldq, kv, kv + d, 2 * d, ctx, d, mask, cu_rows, L, H, 1);
+template <int DH>
+int attention_f32_cls(const char* op, const float* qc, int ldq, const float* kv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L,
+                      int H, void* stream) {
+    ATTN_F32_CHECK(qc != nullptr && kv != nullptr, "null operand");
+    ATTN_F32_CHECK(ctx != nullptr, "null output");
+    ATTN_F32_CHECK(mask == nullptr || cu_rows == nullptr, "a packed batch (cu_rows) takes its key mask from the lengths: mask must be NULL");
+    ATTN_F32_CHECK(nseq > 0 && H > 0 && L > 0 && L <= 256, "need nseq > 0, H > 0, 0 < L <= 256");
+    ATTN_F32_CHECK((long long)nseq * H <= 0x7FFFFFFFll, "batch too large");
+    ATTN_F32_CHECK(ldq >= H * DH && ldq % 4 == 0, "the query row pitch must cover a row and be a multiple of 4");
+    ATTN_F32_CHECK(aligned16(qc) && aligned16(kv), "qc and kv must be 16-byte aligned");
+    const int d = H * DH;
+    hipLaunchKernelGGL(attention_f32_kernel<DH>, dim3(nseq * H, 1), dim3(64), 0, (hipStream_t)stream, qc, ldq, kv, kv + d, 2 * d, ctx, d, mask, cu_rows,
+                       L, H, 1);
     CLDRD_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int cldrd_attention_fwd_f32(const float* qkv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L, int H, void* stream) {
+    return attention_f32_full<64>("attention_fwd_f32", qkv, mask, cu_rows, ctx, nseq, L, H, stream);
+}
+
+extern "C" int cldrd_attention_cls_fwd_f32(const float* qc, int ldq, const float* kv, const long long* mask, const int* cu_rows, float* ctx, int nseq,
+                                           int L, int H, void* stream) {
+    return attention_f32_cls<64>("attention_cls_fwd_f32", qc, ldq, kv, mask, cu_rows, ctx, nseq, L, H, stream);
+}
+
+// Head dim 32: qkv [rows, 3*H*32], ctx [rows, H*32]; qc [nseq, H*32] with pitch ldq, kv [rows, 2*H*32].  Any H (no head pairs here: a wave owns one head).
+extern "C" int cldrd_attention_fwd_f32_hd32(const float* qkv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L, int H,
+                                            void* stream) {
+    return attention_f32_full<32>("attention_fwd_f32_hd32", qkv, mask, cu_rows, ctx, nseq, L, H, stream);
+}
+
+extern "C" int cldrd_attention_cls_fwd_f32_hd32(const float* qc, int ldq, const float* kv, const long long* mask, const int* cu_rows, float* ctx,
+                                                int nseq, int L, int H, void* stream) {
+    return attention_f32_cls<32>("attention_cls_fwd_f32_hd32", qc, ldq, kv, mask, cu_rows, ctx, nseq, L, H, stream);
 }

@@ -55,10 +55,15 @@ class EncoderConfig:
     def validate(self):
         if self.arch not in ("distilbert", "bert"):
             raise ValueError(f"unsupported arch {self.arch}")
-        if self.dim != self.n_heads * 64:
-            raise ValueError("the attention kernel needs head dim 64 (dim == 64 * n_heads)")
+        if self.dim != self.n_heads * 64 and not (self.dim == self.n_heads * 32 and self.n_heads % 2 == 0):
+            raise ValueError("the attention kernels need head dim 64 (dim == 64 * n_heads: every pass) or head dim 32 with an even number of "
+                             f"heads (dim == 32 * n_heads: evaluation passes only); got dim {self.dim}, n_heads {self.n_heads}")
         if self.dim % 128 or self.hidden_dim % 128 or self.dim > 1024:
             raise ValueError("dim and hidden_dim must be multiples of 128, dim <= 1024")
+
+    @property
+    def head_dim(self) -> int:
+        return self.dim // self.n_heads
 
     @classmethod
     def from_hf_dict(cls, c: dict) -> "EncoderConfig":
@@ -209,6 +214,11 @@ def _attach(root: nn.Module, dotted: str, param: nn.Parameter):
             mod.add_module(p, nn.Module())
         mod = mod._modules[p]
     mod.register_parameter(parts[-1], param)
+
+
+# A head-dim-32 tower (MiniLM shapes) has the evaluation attention kernels only (csrc/attention_hd32.hip): no backward, dropout or tape
+HD32_EVAL_ONLY = ("head dim 32 runs the evaluation passes only (encode(train=False, save=False), fp32=True): training, a tape (save=True) and "
+                  "encode_autograd need head dim 64")
 
 
 class _Tape:
@@ -593,6 +603,8 @@ class HipEncoder(nn.Module):
         (the batch is then packed), ``token_type_ids`` and ``packed`` like the evaluation pass, and refuses ``save`` / ``train`` /
         ``device_seed`` / ``fp16=True``: it keeps no tape and has no dropout.  A sequence's CLS vector does not depend on the rest of the
         batch, bit for bit."""
+        if self.cfg.head_dim == 32 and (save or (self.training if train is None else train)):
+            raise ValueError(HD32_EVAL_ONLY)
         if fp32:
             if save or train or device_seed or fp16:
                 raise ValueError("encode(fp32=True) is an evaluation pass and nothing else: no save / train / device_seed / fp16")
@@ -772,6 +784,9 @@ class HipEncoder(nn.Module):
             cu = pk.cu if pk is not None else None
             ctx = self._buf(T, d, dev, dt16) if not FFN16 else None
             for sl, tile in (pk.groups if pk is not None else [(None, 0)]):
+                if cfg.head_dim == 32:         # evaluation only (encode() refuses the rest): one kernel family, bf16 or fp16 at every L
+                    ops.attention_fwd(qkv, mask if pk is None else None, ctx, None, M, L, H, ctx16=ctx16, cu=cu, seq_list=sl, tile=tile, head_dim=32)
+                    continue
                 ops.attention_fwd(qkv, mask if pk is None else None, ctx, lse, M, L, H, p_a, s_l + 1, drop_bits=dbits, ctx16=ctx16,
                                   full_family=all_fp16, cu=cu, seq_list=sl, tile=tile)
             s1 = self._buf(T, d, dev, torch.float32)      # pre-LN sums are stored in fp32: the fp32 residual stream
@@ -827,6 +842,7 @@ class HipEncoder(nn.Module):
                          pos_idx=pk.pos if pk is not None else None, type_ids=tt.to(torch.int32) if tt is not None else None)
         cls = torch.empty(M, d, **f32)
         cu = pk.cu if pk is not None else None
+        hd = dict(head_dim=32) if cfg.head_dim == 32 else {}          # (a head-dim-64 tower's calls stay as they were)
         for i in range(cfg.n_layers):
             W = self._layer_weights_f32(i)
             last = i == cfg.n_layers - 1
@@ -841,7 +857,7 @@ class HipEncoder(nn.Module):
                 qc = buf(M, d)
                 ops.gemm_nt_f32(xc, W["Wqkv"][:d], qc, M, bias=W["bqkv"][:d])
                 ctxc = buf(M, d)
-                ops.attention_fwd_f32(kv, mask, ctxc, M, L, H, cu=cu, qc=qc)
+                ops.attention_fwd_f32(kv, mask, ctxc, M, L, H, cu=cu, qc=qc, **hd)
                 s1 = buf(M, d)
                 ops.gemm_nt_f32(ctxc, W["Wo"], s1, M, bias=W["bo"], residual=xc)
                 x1 = buf(M, d)
@@ -855,7 +871,7 @@ class HipEncoder(nn.Module):
             qkv = buf(T, 3 * d)
             ops.gemm_nt_f32(x, W["Wqkv"], qkv, T, bias=W["bqkv"])
             ctx = buf(T, d)
-            ops.attention_fwd_f32(qkv, mask, ctx, M, L, H, cu=cu)
+            ops.attention_fwd_f32(qkv, mask, ctx, M, L, H, cu=cu, **hd)
             s1 = buf(T, d)
             ops.gemm_nt_f32(ctx, W["Wo"], s1, T, bias=W["bo"], residual=x)
             del qkv, ctx
@@ -904,9 +920,14 @@ class HipEncoder(nn.Module):
         ops.gemm_nt(xc, Wq["Wqkv"][:d], qc, M, bias=W["bqkv"][:d])
         ctxc = self._buf(M, d, dev, dt16) if not FFN16 else None
         ctxc16 = self._buf(M, d, dev, torch.float16) if FFN16 else None
-        probs = torch.empty(M, H, L, **f32)
-        ops.attention_cls_fwd(qc, kv, mask if pk is None else None, ctxc, probs, M, L, H, p_a, s_l + 1, ctx16=ctxc16,
-                              cu=pk.cu if pk is not None else None)
+        if cfg.head_dim == 32:                 # evaluation only (encode() refuses the rest): no probabilities are kept
+            probs = None
+            ops.attention_cls_fwd(qc, kv, mask if pk is None else None, ctxc, None, M, L, H, ctx16=ctxc16, cu=pk.cu if pk is not None else None,
+                                  head_dim=32)
+        else:
+            probs = torch.empty(M, H, L, **f32)
+            ops.attention_cls_fwd(qc, kv, mask if pk is None else None, ctxc, probs, M, L, H, p_a, s_l + 1, ctx16=ctxc16,
+                                  cu=pk.cu if pk is not None else None)
         s1 = self._buf(M, d, dev, torch.float32)
         ops.gemm_nt(ctxc16 if FFN16 else ctxc, Wf["Wo"], s1, M, bias=W["bo"], residual=xc32, dropout_p=p_out, seed=s_l + 2)
         x1_32 = self._buf(M, d, dev, torch.float32)
@@ -1215,6 +1236,8 @@ class _EncodeFn(torch.autograd.Function):
 
 def encode_autograd(enc: HipEncoder, ids, mask, fp16=None, lengths=None):
     if torch.is_grad_enabled() and any(p.requires_grad for p in enc.parameters()):
+        if enc.cfg.head_dim == 32:         # (without gradients this is the evaluation pass: index encode, retrieval, dev re-ranking)
+            raise ValueError(HD32_EVAL_ONLY)
         if enc._anchor is None or enc._anchor.device != enc.flat_p.device:
             enc._anchor = torch.zeros(1, device=enc.flat_p.device, requires_grad=True)
         return _EncodeFn.apply(enc._anchor, enc, ids, mask, fp16, lengths)

@@ -413,10 +413,53 @@ def _layout(mask, cu, seq_list, tile, nseq, L, what):
     return (_p(mask), None, *lst)
 
 
-def attention_fwd(qkv, mask, ctx, lse, nseq, L, H, dropout_p=0.0, seed=0, drop_bits=None, ctx16=None, full_family=False, cu=None, seq_list=None, tile=0):
+def _head_dim(head_dim, what, H=None, **training_only):
+    """The ``head_dim`` keyword of the attention calls: 64 (every pass), or 32 - the evaluation forward of csrc/attention_hd32.hip, which has no
+    dropout, tape or keep bits (``training_only``: the arguments that must then be unset) and, in the 16-bit kernels, needs an even ``H``."""
+    if head_dim == 64:
+        return 64
+    if head_dim != 32:
+        raise ValueError(f"{what}: head dim {head_dim} is not supported (the attention kernels exist for head dim 64 and 32)")
+    bad = [k for k, v in training_only.items() if v]
+    if bad:
+        raise ValueError(f"{what}: head dim 32 runs the evaluation forward only: no {' / '.join(bad)}")
+    if H is not None and H % 2:
+        raise ValueError(f"{what}: head dim 32 needs an even number of heads, got {H}")
+    return 32
+
+
+def _attention_fwd_hd32(qkv, mask, ctx, nseq, L, H, ctx16, cu, seq_list, tile):
+    what = "attention_fwd(head_dim=32)"
+    fmt = _fmt16(qkv, "qkv")
+    layout = _layout(mask, cu, seq_list, tile, nseq, L, what)
+    dt16 = F16 if fmt else BF16
+    _chk(qkv, dt16, "qkv", 2)
+    if ctx is None and ctx16 is None:
+        raise ValueError(f"{what}: no output")
+    if ctx16 is not None and fmt:
+        raise ValueError(f"{what}: ctx16 goes with a bf16 pass")
+    for t, n, dt in ((ctx, "ctx", dt16), (ctx16, "ctx16", F16)):
+        if t is not None:
+            _chk(t, dt, n, 2)
+            if t.shape[1] != H * 32 or not t.is_contiguous():
+                raise ValueError(f"{what}: {n} must be contiguous [T, H*32]")
+    if mask is not None:
+        _chk(mask, torch.int64, "mask", 2)
+        if not mask.is_contiguous() or tuple(mask.shape) != (nseq, L):
+            raise ValueError(f"{what}: mask must be contiguous int64 [nseq, L]")
+    if qkv.shape[1] != 3 * H * 32 or not qkv.is_contiguous():
+        raise ValueError(f"{what}: qkv must be contiguous [T, 3*H*32]")
+    call("cldrd_attention_fwd_hd32", _p(qkv), *layout, _p(ctx), nseq, L, H, fmt, _p(ctx16), _stream())
+    return ctx16 if ctx is None else ctx
+
+
+def attention_fwd(qkv, mask, ctx, lse, nseq, L, H, dropout_p=0.0, seed=0, drop_bits=None, ctx16=None, full_family=False, cu=None, seq_list=None, tile=0,
+                  head_dim=64):
     """``ctx16`` (fp16, bf16 pass only): the same context in fp16, for an fp16-operand out-projection; ``ctx`` may then be None.
     ``cu``: qkv / ctx / ctx16 are packed [Tp, .] (see _cu_rows); ``lse`` and ``drop_bits`` keep their padded shapes.  ``seq_list`` / ``tile``:
-    see _seq_list."""
+    see _seq_list.  ``head_dim=32``: the evaluation forward at head dim 32 (shapes against H*32; bf16 or fp16 at every L <= 256; see _head_dim)."""
+    if _head_dim(head_dim, "attention_fwd", H, dropout_p=dropout_p > 0, lse=lse is not None, drop_bits=drop_bits is not None, full_family=full_family) == 32:
+        return _attention_fwd_hd32(qkv, mask, ctx, nseq, L, H, ctx16, cu, seq_list, tile)
     fmt = _fmt16(qkv, "qkv")
     layout = _layout(mask, cu, seq_list, tile, nseq, L, "attention_fwd")
     _chk(qkv, F16 if fmt else BF16, "qkv", 2)
@@ -461,10 +504,33 @@ def attention_bwd(qkv, mask, ctx, dctx, lse, dqkv, nseq, L, H, dropout_p=0.0, se
     return dqkv
 
 
-def attention_cls_fwd(qc, kv, mask, ctx, probs, nseq, L, H, dropout_p=0.0, seed=0, ctx16=None, cu=None):
-    """``cu``: kv is packed [Tp, 2*H*64] (see _cu_rows); probs stays [nseq, H, L]."""
+def attention_cls_fwd(qc, kv, mask, ctx, probs, nseq, L, H, dropout_p=0.0, seed=0, ctx16=None, cu=None, head_dim=64):
+    """``cu``: kv is packed [Tp, 2*H*64] (see _cu_rows); probs stays [nseq, H, L].  ``head_dim=32``: the evaluation form at head dim 32
+    (kv [T, 2*H*32]; ``probs`` must be None: see _head_dim)."""
+    hd = _head_dim(head_dim, "attention_cls_fwd", H, dropout_p=dropout_p > 0, probs=probs is not None)
     fmt = _fmt16(qc, "qc")
     dt16 = F16 if fmt else BF16
+    if hd == 32:
+        what = "attention_cls_fwd(head_dim=32)"
+        _chk(qc, dt16, "qc", 2), _chk(kv, dt16, "kv", 2)
+        if ctx is None and ctx16 is None:
+            raise ValueError(f"{what}: no output")
+        if ctx16 is not None and fmt:
+            raise ValueError(f"{what}: ctx16 goes with a bf16 pass")
+        for t, n, dt in ((ctx, "ctx", dt16), (ctx16, "ctx16", F16)):
+            if t is not None:
+                _chk(t, dt, n, 2)
+                if t.shape[1] != H * 32 or t.shape[0] < nseq or not t.is_contiguous():
+                    raise ValueError(f"{what}: {n} must be contiguous [nseq, H*32]")
+        if kv.shape[1] != 2 * H * 32 or not kv.is_contiguous() or qc.shape[1] != H * 32 or qc.shape[0] < nseq or not qc.is_contiguous():
+            raise ValueError(f"{what}: kv must be contiguous [T, 2*H*32], qc contiguous [nseq, H*32]")
+        if mask is not None:
+            _chk(mask, torch.int64, "mask", 2)
+            if not mask.is_contiguous() or tuple(mask.shape) != (nseq, L):
+                raise ValueError(f"{what}: mask must be contiguous int64 [nseq, L]")
+        call("cldrd_attention_cls_fwd_hd32", _p(qc), _p(kv), *_layout(mask, cu, None, 0, nseq, L, what)[:2], _p(ctx), nseq, L, H, fmt, _p(ctx16),
+             _stream())
+        return
     _chk(qc, dt16, "qc", 2), _chk(kv, dt16, "kv", 2), _chk(probs, F32, "probs")
     if ctx is not None:
         _chk(ctx, dt16, "ctx", 2)
@@ -491,13 +557,16 @@ def attention_cls_bwd(qc, kv, probs, dctx, dqc, dkv, nseq, L, H, dropout_p=0.0, 
          nseq, L, H, dropout_p, seed, fmt, _stream())
 
 
-def attention_fwd_f32(qkv, mask, ctx, nseq, L, H, cu=None, qc=None):
+def attention_fwd_f32(qkv, mask, ctx, nseq, L, H, cu=None, qc=None, head_dim=64):
     """fp32 attention of the fp32 evaluation pass (csrc/encoder_f32.hip): ``ctx = softmax(Q K^T / 8 + key mask) V``, head dim 64, L <= 256.
     Full form (``qc`` None): ``qkv`` fp32 [T, 3*H*64], ``ctx`` [T, H*64].  CLS form (``qc`` fp32 [nseq, H*64], a row pitch allowed): ``qkv`` is
     K | V of every token, [T, 2*H*64], ``ctx`` [nseq, H*64] - bit for bit row 0 of the full form.  Layout: padded rows with ``mask`` (int64
-    [nseq, L] or None) or packed rows through ``cu`` (see _cu_rows), never both."""
+    [nseq, L] or None) or packed rows through ``cu`` (see _cu_rows), never both.  ``head_dim=32``: the same at head dim 32 (every 64 above reads 32,
+    the scale is the fp32 nearest to 1 / sqrt(32))."""
     what = "attention_fwd_f32"
-    d = H * 64
+    hd = _head_dim(head_dim, what)
+    d = H * hd
+    sfx = "" if hd == 64 else "_hd32"
     _chk(qkv, F32, "qkv", 2), _chk(ctx, F32, "ctx", 2)
     if mask is not None:
         _chk(mask, torch.int64, "mask", 2)
@@ -508,16 +577,16 @@ def attention_fwd_f32(qkv, mask, ctx, nseq, L, H, cu=None, qc=None):
         raise ValueError(f"{what}: need nseq > 0 and 0 < L <= 256")
     rows = nseq * L if cu is None else 1
     if qkv.shape[1] != (3 if qc is None else 2) * d or not qkv.is_contiguous() or qkv.shape[0] < rows:
-        raise ValueError(f"{what}: qkv must be contiguous [T, 3*H*64] (CLS form: K | V, [T, 2*H*64])")
+        raise ValueError(f"{what}: qkv must be contiguous [T, 3*H*{hd}] (CLS form: K | V, [T, 2*H*{hd}])")
     if ctx.shape[1] != d or not ctx.is_contiguous() or ctx.shape[0] < (rows if qc is None else nseq):
-        raise ValueError(f"{what}: ctx must be contiguous [T, H*64] (CLS form: [nseq, H*64])")
+        raise ValueError(f"{what}: ctx must be contiguous [T, H*{hd}] (CLS form: [nseq, H*{hd}])")
     if qc is None:
-        call("cldrd_attention_fwd_f32", _p(qkv), mask_p, cu_p, _p(ctx), nseq, L, H, _stream())
+        call("cldrd_attention_fwd_f32" + sfx, _p(qkv), mask_p, cu_p, _p(ctx), nseq, L, H, _stream())
     else:
         _chk(qc, F32, "qc", 2)
         if qc.shape[1] != d or qc.shape[0] < nseq:
-            raise ValueError(f"{what}: qc must be [nseq, H*64]")
-        call("cldrd_attention_cls_fwd_f32", _p(qc), qc.stride(0), _p(qkv), mask_p, cu_p, _p(ctx), nseq, L, H, _stream())
+            raise ValueError(f"{what}: qc must be [nseq, H*{hd}]")
+        call("cldrd_attention_cls_fwd_f32" + sfx, _p(qc), qc.stride(0), _p(qkv), mask_p, cu_p, _p(ctx), nseq, L, H, _stream())
     return ctx
 
 

@@ -118,8 +118,9 @@ class CrossEncoder(nn.Module):
         if _ARCHS[mt] not in archs:
             raise ValueError(f"{path}: architectures {archs} - expected {_ARCHS[mt]}")
         dim, heads = (c["hidden_size"], c["num_attention_heads"]) if mt == "bert" else (c["dim"], c["n_heads"])
-        if dim % heads or dim // heads != 64:
-            raise ValueError(f"{path}: head dim {dim / heads:g} is not supported (the attention kernels need head dim 64)")
+        if dim % heads or not (dim // heads == 64 or (dim // heads == 32 and heads % 2 == 0)):
+            raise ValueError(f"{path}: head dim {dim / heads:g} with {heads} heads is not supported (the attention kernels need head dim 64, or "
+                             "head dim 32 with an even number of heads)")
         num_labels = len(c["id2label"]) if "id2label" in c else int(c.get("num_labels", 2))
         if num_labels not in (1, 2):
             raise ValueError(f"{path}: num_labels {num_labels} is not supported (1 or 2)")
@@ -132,10 +133,14 @@ class CrossEncoder(nn.Module):
         return cfg, num_labels
 
     @classmethod
-    def from_pretrained(cls, path: str, max_len: int = MAX_PAIR_LEN) -> "CrossEncoder":
+    def from_pretrained(cls, path: str, max_len: int = MAX_PAIR_LEN, eval_only: bool = False) -> "CrossEncoder":
         """An HF ``BertForSequenceClassification`` / ``DistilBertForSequenceClassification`` directory (``config.json`` and
-        ``model.safetensors`` or ``pytorch_model.bin``).  The model stays on the host: move it with ``.to(device)``."""
+        ``model.safetensors`` or ``pytorch_model.bin``).  The model stays on the host: move it with ``.to(device)``.
+        ``eval_only=True`` (the scoring programs): the caller runs evaluation passes only, so a model whose encoder has no other pass - head
+        dim 32, the MiniLM shapes - is accepted.  Without it such a directory is refused as before (tests/test_rerank_host.py pins that)."""
         cfg, num_labels = cls.read_config(path, max_len)
+        if cfg.head_dim != 64 and not eval_only:
+            raise ValueError(f"{path}: head dim {cfg.head_dim} runs the evaluation passes only: load it with from_pretrained(..., eval_only=True)")
         model = cls(cfg, num_labels=num_labels, max_len=max_len)
         st = os.path.join(path, "model.safetensors")
         if os.path.exists(st):

@@ -164,7 +164,7 @@ def main(args):
 
     # 2. the teacher's score of every (query, candidate) pair, one fp32 [nq, k] tensor in HBM
     t_tok = AutoTokenizer.from_pretrained(args.teacher_tokenizer_name_or_path or args.teacher_name_or_path)
-    teacher = CrossEncoder.from_pretrained(args.teacher_name_or_path, max_len=args.teacher_max_len).cuda()
+    teacher = CrossEncoder.from_pretrained(args.teacher_name_or_path, max_len=args.teacher_max_len, eval_only=True).cuda()
     lap("teacher_load_s")
     with tempfile.TemporaryDirectory() as tmp:
         cache_dir = args.token_cache_dir or tmp

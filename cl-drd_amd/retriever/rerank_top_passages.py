@@ -185,7 +185,7 @@ def main(args, on_batch=None):
     torch.cuda.set_device(0)
     from transformers import AutoTokenizer
     tokenizer = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path or args.model_name_or_path)
-    model = CrossEncoder.from_pretrained(args.model_name_or_path, max_len=args.max_len).cuda()
+    model = CrossEncoder.from_pretrained(args.model_name_or_path, max_len=args.max_len, eval_only=True).cuda()
     qids, pids, group, starts = read_run(args.run_path, args.top_k)
     with tempfile.TemporaryDirectory() as tmp:
         cache_dir = args.token_cache_dir or tmp

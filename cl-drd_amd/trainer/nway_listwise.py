@@ -40,7 +40,7 @@ import torch.distributed as dist
 
 from .. import hip_ops as ops
 from ..dataset.nway_dataset import attach_lengths
-from ..encoder import _env_flag
+from ..encoder import HD32_EVAL_ONLY, _env_flag
 from ..models.nway_dual_encoder import NwayDualEncoder, _lengths, score_mode
 from ..retriever.retrieval_utils import cap_host_threads
 
@@ -246,6 +246,8 @@ class NwayTrainer:
             raise ValueError("distill_alpha must be >= 0 and distill_T > 0")
         if distill_only and distill is None:
             raise ValueError("distill_only needs a distill loss")
+        if any(t.cfg.head_dim == 32 for t in model.towers()):
+            raise ValueError("NwayTrainer: " + HD32_EVAL_ONLY)
         # teacher-score term: total = loss(logits, labels) + distill_alpha * kd(logits[:, :nway], batch["teacher_scores"]); distill_only drops
         # the first summand.  last_kd: the unweighted term of the last step (device scalar, like last_reg)
         self.distill, self.distill_alpha, self.distill_T, self.distill_only = distill, float(distill_alpha), float(distill_T), bool(distill_only)

@@ -134,6 +134,21 @@ int cldrd_attention_cls_bwd(const void* qc, const void* kv, const int* cu_rows, 
                             int nseq, int L, int H, float dropout_p, unsigned long long seed, int fmt, void* stream);
 int cldrd_add_rows(void* dst, const void* src, int M, int d, int stride_rows, const int* idx, int fmt, void* stream);
 
+/* ---- attention at head dim 32 (MiniLM-shaped BERT: hidden 384 / 12 heads), EVALUATION forward only (csrc/attention_hd32.hip) ---------------
+ * No dropout, no LSE, no keep bits, no probs, no backward: a head-dim-32 model runs the evaluation passes and is refused for training.
+ * cldrd_attention_fwd_hd32: qkv: 16-bit [rows, 3*H*32] = Q | K | V, heads contiguous inside each; ctx: [rows, H*32].  Layout rule (mask / cu_rows /
+ *   seq_list, n_list, Ltile) exactly that of cldrd_attention_fwd; 0 < L <= 256.  H must be EVEN: a workgroup loads a PAIR of adjacent heads as one
+ *   128-byte row slice, and with an even H no slice reads past a row.  fmt: CLDRD_FMT_BF16 (bf16 in, bf16 ctx and / or an fp16 copy in ctx_f16_copy;
+ *   at least one of the two) or CLDRD_FMT_F16 (fp16 in, fp16 ctx, no copy; every L <= 256); anything else is refused.
+ *   A packed batch gives the padded batch's bits on every real row and writes nothing else.  One schedule: the bits of a sequence's rows depend on
+ *   its own length and the format, not on the tile height, the other sequences of the launch, their number or their order.
+ * cldrd_attention_cls_fwd_hd32: the CLS form of the last layer - qc: [nseq, H*32] queries of token 0; kv: [rows, 2*H*32] = K | V of every token,
+ *   padded or packed as above (no lists); ctx / ctx_f16_copy: [nseq, H*32]; fmt and the even-H rule as above. */
+int cldrd_attention_fwd_hd32(const void* qkv, const long long* mask, const int* cu_rows, const int* seq_list, int n_list, int Ltile,
+                             void* ctx, int nseq, int L, int H, int fmt, void* ctx_f16_copy, void* stream);
+int cldrd_attention_cls_fwd_hd32(const void* qc, const void* kv, const long long* mask, const int* cu_rows, void* ctx, int nseq, int L, int H,
+                                 int fmt, void* ctx_f16_copy, void* stream);
+
 /* ---- the fp32 evaluation pass (csrc/encoder_f32.hip): the reference's `use_fp16=False` encode, retriever/retrieval_utils.py:30-58 ----------
  * Every operand fp32, accumulation on the f32-input MFMA (bit for bit a k-ordered fmaf chain).  Each op has ONE schedule, whatever the shape:
  * a row's result does not depend on which other rows share the launch, so packed == padded and a batch == its sequences alone, bit for bit.
@@ -143,12 +158,18 @@ int cldrd_add_rows(void* dst, const void* src, int M, int d, int stride_rows, co
  * cldrd_attention_fwd_f32: ctx[rows, H*64] = softmax(Q K^T / 8 + key mask) V from qkv fp32 [rows, 3*H*64]; layouts as cldrd_attention_fwd
  *   (padded rows + int64 mask or NULL, or packed rows through cu_rows - never both; no lists); L <= 256.  A masked key contributes exactly zero.
  * cldrd_attention_cls_fwd_f32: the CLS form - qc: [nseq, H*64] queries of token 0 with row pitch ldq; kv: [rows, 2*H*64] = K | V of every token,
- *   padded or packed as above; ctx: [nseq, H*64].  Bit for bit row 0 of the full form. */
+ *   padded or packed as above; ctx: [nseq, H*64].  Bit for bit row 0 of the full form.
+ * cldrd_attention_fwd_f32_hd32 / cldrd_attention_cls_fwd_f32_hd32: the same two at head dim 32 (every 64 above reads 32; any H): the same kernel
+ *   text and guarantees.  A score's chain adds the head dims 0, 16, 1, 17, ..., 15, 31; the finished score is multiplied once by the fp32 nearest
+ *   to 1 / sqrt(32) (no power of two: one more rounding than the exact 1 / 8 of head dim 64). */
 int cldrd_gemm_nt_f32(const float* A, const float* W, float* C, int M, int N, int K, int lda, int ldw, int ldc, const float* bias,
                       const float* residual, int ldr, int act, void* stream);
 int cldrd_attention_fwd_f32(const float* qkv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L, int H, void* stream);
 int cldrd_attention_cls_fwd_f32(const float* qc, int ldq, const float* kv, const long long* mask, const int* cu_rows, float* ctx, int nseq,
                                 int L, int H, void* stream);
+int cldrd_attention_fwd_f32_hd32(const float* qkv, const long long* mask, const int* cu_rows, float* ctx, int nseq, int L, int H, void* stream);
+int cldrd_attention_cls_fwd_f32_hd32(const float* qc, int ldq, const float* kv, const long long* mask, const int* cu_rows, float* ctx, int nseq,
+                                     int L, int H, void* stream);
 
 /* ---- embeddings + LayerNorm (HF Embeddings.forward, sa_layer_norm / output_layer_norm) --------------------
  * d <= 1024, d % 4 == 0.  `partial` scratch: cldrd_ln_partial_blocks(T) * 3 * d floats. */
