@@ -14,6 +14,8 @@
 // Kernels here: per-query k-th largest of the sample scores (threshold estimate, radix select), fp32 re-score,
 // bitonic sort + cut, max row norm; and the fp16-row mode's re-score from the centred fp16 rows (an index without fp32 rows).
 #include "common.h"
+#include "topk_chain.h"
+#include "../../include/cldrd_hip.h"
 #ifndef CLDRD_SCAN_NT
 #define CLDRD_SCAN_NT 1
 #endif
@@ -956,11 +958,6 @@ extern "C" int cldrd_topk_select(const int* counts, const int* cand_rows, const 
                          (hipStream_t)stream);
 }
 
-int cldrd_topk_scan_stream(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts, int* cand_rows,
-                           float* cand_scores, int cap, int f16, hipStream_t st);
-extern "C" int cldrd_topk_scan_filter(const void* Q, const void* P, int nq, long long rows, int d, const float* thr, int* counts,
-                                      int* cand_rows, float* cand_scores, int cap, int f16, int tiled, void* stream);
-
 // The whole search of one shard for nq queries (device resident, fp32 + fp16 copies), in batches of 128 as the reference searches
 // (retriever/retrieve_top_passages.py:88, retrieval_utils.py:131-153), enqueued back to back on `stream` with no host round trip:
 //   scan (fp16 MFMA, HBM-bound) -> select t^ and the 2 eps band -> exact fp32 re-score -> sort + cut -> D, I, status.
@@ -982,11 +979,18 @@ extern "C" int cldrd_flatip_search(const float* q32, const void* qh, const float
     CLDRD_CHECK(P32 ? qmu == nullptr : (P16 != nullptr && qmu != nullptr), "flatip_search: fp32 rows take no qmu, fp16 rows need P16 and qmu");
     CLDRD_CHECK(nq > 0 && rows > 0 && k > 0 && cap > 0 && cap <= 8192 && cap2 > 0 && cap2 <= 8192 && d % 4 == 0, "flatip_search: bad arguments");
     CLDRD_CHECK(qtile == 128 || qtile == 256, "flatip_search: the query tile is 128 (the reference's batch) or 256 (two batches per pass over the index)");
-    const int tiled = (exhaustive >> 1) & 1;
-    exhaustive &= 1;
-    CLDRD_CHECK(!exhaustive || rows <= cap, "flatip_search: exhaustive mode needs rows <= cap");
-    hipStream_t st = (hipStream_t)stream;
-    const int kk = (int)(k < rows ? k : rows);
+    CLDRD_CHECK(!(exhaustive & 1) || rows <= cap, "flatip_search: exhaustive mode needs rows <= cap");
+    return cldrd_flatip_chain(FlatipQueries{q32, qh, nullptr, nullptr, thr, eps, qmu, nq}, FlatipRows{P16, P32, nullptr, nullptr, rows}, d, k, qtile, counts,
+                              cand_rows, cand_scores, cap, rows2, scores2, cap2, n2, status, khat, D, I, exhaustive & 1, (exhaustive >> 1) & 1,
+                              (hipStream_t)stream);
+}
+
+// The per-tile loop of every row mode (topk_chain.h).  int8-row mode scans and re-scores with the kernels of topk_i8.hip; its scan has no tiled form.
+int cldrd_flatip_chain(const FlatipQueries& Q, const FlatipRows& P, int d, int k, int qtile, int* counts, int* cand_rows, float* cand_scores, int cap,
+                       int* rows2, float* scores2, int cap2, int* n2, int* status, float* khat, float* D, int* I, int exhaustive, int tiled,
+                       hipStream_t st) {
+    const long long rows = P.rows;
+    const int nq = Q.nq, kk = (int)(k < rows ? k : rows);
     for (int lo = 0, b = 0; lo < nq; lo += qtile, ++b) {
         const int m = nq - lo < qtile ? nq - lo : qtile;
         int* cb = counts + (size_t)b * (qtile + 1);
@@ -994,21 +998,25 @@ extern "C" int cldrd_flatip_search(const float* q32, const void* qh, const float
         if (exhaustive) {
             hipLaunchKernelGGL(all_candidates_kernel, dim3((unsigned)((rows + 255) / 256), m), dim3(256), 0, st, cb, cand_rows, cand_scores, (int)rows, cap);
             CLDRD_LAUNCH_CHECK();
+        } else if (P.R8) {
+            rc = cldrd_topk_scan_i8((const char*)Q.qd + (size_t)lo * d, nq, Q.sq + lo, Q.thr + lo, P.R8, P.scale, m, rows, d, cb, cand_rows, cand_scores, cap, st);
+            if (rc) return rc;
         } else if (tiled) {
             // the tiled kernels take at most 128 queries per call; list lengths of query j of this pass stay at cb[j]
             for (int h = 0; h < m; h += 128) {
                 const int mh = m - h < 128 ? m - h : 128;
-                rc = cldrd_topk_scan_filter((const char*)qh + (size_t)(lo + h) * d * 2, P16, mh, rows, d, thr + lo + h, cb + h,
+                rc = cldrd_topk_scan_filter((const char*)Q.qh + (size_t)(lo + h) * d * 2, P.P16, mh, rows, d, Q.thr + lo + h, cb + h,
                                             cand_rows + (size_t)h * cap, cand_scores + (size_t)h * cap, cap, 1, 1, st);
                 if (rc) return rc;
             }
         } else {
-            rc = cldrd_topk_scan_filter(qh ? (const char*)qh + (size_t)lo * d * 2 : nullptr, P16, m, rows, d, thr + lo, cb, cand_rows, cand_scores, cap, 1, 0, st);
+            rc = cldrd_topk_scan_filter(Q.qh ? (const char*)Q.qh + (size_t)lo * d * 2 : nullptr, P.P16, m, rows, d, Q.thr + lo, cb, cand_rows, cand_scores, cap, 1, 0, st);
             if (rc) return rc;
         }
-        rc = launch_select(cb, cb + m, cand_rows, cand_scores, m, cap, kk, thr + lo, eps + lo, rows2, cap2, n2 + lo, status + lo, khat + lo, exhaustive, st);
+        rc = launch_select(cb, cb + m, cand_rows, cand_scores, m, cap, kk, Q.thr + lo, Q.eps + lo, rows2, cap2, n2 + lo, status + lo, khat + lo, exhaustive, st);
         if (rc) return rc;
-        rc = cldrd_topk_rescore(q32 + (size_t)lo * d, P32, P16, qmu ? qmu + lo : nullptr, d, n2 + lo, rows2, scores2, m, cap2, st);
+        if (P.R8) rc = cldrd_topk_rescore_i8(Q.q32 + (size_t)lo * d, P.R8, P.scale, Q.qmu + lo, d, n2 + lo, rows2, scores2, m, cap2, st);
+        else rc = cldrd_topk_rescore(Q.q32 + (size_t)lo * d, P.P32, P.P16, Q.qmu ? Q.qmu + lo : nullptr, d, n2 + lo, rows2, scores2, m, cap2, st);
         if (rc) return rc;
         rc = cldrd_topk_sort(n2 + lo, rows2, scores2, m, cap2, k, D + (size_t)lo * k, I + (size_t)lo * k, st);
         if (rc) return rc;

@@ -26,6 +26,7 @@
 //   eps = (1. + 2.) (1 + 1e-6) + 1e-30 (results below the fp32 normal range).  thr = est - 2 eps, as in the 16-bit modes (select_compact_kernel of
 //   topk.hip explains the 2).  At d = 768 term 1 is ~2-3e-3 of the score spread, a tenth of the fp16 scan's eps; term 2 is ~1e-2 of term 1.
 #include "common.h"
+#include "topk_chain.h"
 #include "../../include/cldrd_hip.h"
 #include <float.h>
 
@@ -323,16 +324,6 @@ __global__ __launch_bounds__(256) void rescore_i8_kernel(const float* __restrict
     }
 }
 
-// exhaustive mode (rows <= cap): every row is a candidate of every query
-__global__ void all_candidates_i8_kernel(int* __restrict__ counts, int* __restrict__ cand_rows, float* __restrict__ cand_scores, int rows, int cap) {
-    const int q = blockIdx.y;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += gridDim.x * blockDim.x) {
-        cand_rows[(size_t)q * cap + i] = i;
-        cand_scores[(size_t)q * cap + i] = 0.f;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) counts[q] = rows;
-}
-
 template <int KS, int NW, int R>
 int launch_scan_i8(const int8_t* R8, const float* scale, const int8_t* qd, size_t plane, const float* sq, const float* thr, int nq, int rows, int d,
                    int* counts, int* dropped, int* cand_rows, float* cand_scores, int cap, hipStream_t st) {
@@ -434,25 +425,6 @@ extern "C" int cldrd_flatip_search_i8(const float* q32, const void* qd, const fl
     CLDRD_CHECK(exhaustive == 0 || exhaustive == 1, "flatip_search_i8: exhaustive is 0 or 1");
     CLDRD_CHECK(!exhaustive || rows <= cap, "flatip_search_i8: exhaustive mode needs rows <= cap");
     CLDRD_CHECK(exhaustive || (qd != nullptr && sq != nullptr), "flatip_search_i8: a scan needs the query digits");
-    hipStream_t st = (hipStream_t)stream;
-    const int kk = (int)(k < rows ? k : rows);
-    for (int lo = 0, b = 0; lo < nq; lo += qtile, ++b) {
-        const int m = nq - lo < qtile ? nq - lo : qtile;
-        int* cb = counts + (size_t)b * (qtile + 1);
-        int rc;
-        if (exhaustive) {
-            hipLaunchKernelGGL(all_candidates_i8_kernel, dim3((unsigned)((rows + 255) / 256), m), dim3(256), 0, st, cb, cand_rows, cand_scores, (int)rows, cap);
-            CLDRD_LAUNCH_CHECK();
-        } else {
-            rc = cldrd_topk_scan_i8((const char*)qd + (size_t)lo * d, nq, sq + lo, thr + lo, R8, scale, m, rows, d, cb, cand_rows, cand_scores, cap, stream);
-            if (rc) return rc;
-        }
-        rc = cldrd_topk_select(cb, cand_rows, cand_scores, m, cap, kk, thr + lo, eps + lo, rows2, cap2, n2 + lo, status + lo, khat + lo, exhaustive, stream);
-        if (rc) return rc;
-        rc = cldrd_topk_rescore_i8(q32 + (size_t)lo * d, R8, scale, qmu + lo, d, n2 + lo, rows2, scores2, m, cap2, stream);
-        if (rc) return rc;
-        rc = cldrd_topk_sort(n2 + lo, rows2, scores2, m, cap2, k, D + (size_t)lo * k, I + (size_t)lo * k, stream);
-        if (rc) return rc;
-    }
-    return 0;
+    return cldrd_flatip_chain(FlatipQueries{q32, nullptr, qd, sq, thr, eps, qmu, nq}, FlatipRows{nullptr, nullptr, R8, scale, rows}, d, k, qtile, counts,
+                              cand_rows, cand_scores, cap, rows2, scores2, cap2, n2, status, khat, D, I, exhaustive, 0, (hipStream_t)stream);
 }

@@ -1087,6 +1087,16 @@ def topk_select(counts, cand_rows, cand_scores, kk, thr, eps, rows2, n2, status,
          rows2.shape[1], _p(n2), _p(status), _p(khat), 1 if exhaustive else 0, _stream())
 
 
+def _chk_search_buffers(op, nq, k, qtile, counts, cand_rows, rows2, n2, status, khat, D, I, contiguous):
+    """the buffer contract both chained searches share (include/cldrd_hip.h: cldrd_flatip_search); ``contiguous``: the mode's own operands"""
+    if cand_rows.shape[0] < qtile or rows2.shape[0] < qtile:
+        raise ValueError(f"{op}: the candidate buffers need qtile rows")
+    if counts.numel() < ((nq + qtile - 1) // qtile) * (qtile + 1) or n2.numel() < nq or status.numel() < nq or khat.numel() < nq or D.shape != (nq, k) or I.shape != (nq, k):
+        raise ValueError(f"{op}: buffer sizes do not match nq / k")
+    if not all(t.is_contiguous() for t in (*contiguous, D, I) if t is not None):
+        raise ValueError(f"{op}: operands must be contiguous")
+
+
 def flatip_search(q32, qh, thr, eps, P16, k, counts, cand_rows, cand_scores, rows2, scores2, n2, status, khat, D, I, exhaustive=False,
                   qtile=128, tiled=False, P32=None, qmu=None):
     """The whole search of one shard (include/cldrd_hip.h: cldrd_flatip_search); everything device resident, no host sync.
@@ -1106,12 +1116,7 @@ def flatip_search(q32, qh, thr, eps, P16, k, counts, cand_rows, cand_scores, row
         _chk(qh, F16, "qh", 2), _chk(P16, F16, "P16", 2)
     if P.shape[1] != d or (qmu is not None and qmu.numel() < nq):
         raise ValueError("flatip_search: the rows must be [rows, d] and qmu [nq]")
-    if cand_rows.shape[0] < qtile or rows2.shape[0] < qtile:
-        raise ValueError("flatip_search: the candidate buffers need qtile rows")
-    if counts.numel() < ((nq + qtile - 1) // qtile) * (qtile + 1) or n2.numel() < nq or status.numel() < nq or khat.numel() < nq or D.shape != (nq, k) or I.shape != (nq, k):
-        raise ValueError("flatip_search: buffer sizes do not match nq / k")
-    if not (q32.is_contiguous() and P.is_contiguous() and D.is_contiguous() and I.is_contiguous() and (qmu is None or qmu.is_contiguous())):
-        raise ValueError("flatip_search: operands must be contiguous")
+    _chk_search_buffers("flatip_search", nq, k, qtile, counts, cand_rows, rows2, n2, status, khat, D, I, (q32, P, qmu))
     call("cldrd_flatip_search", _p(q32), _p(qh), _p(thr), _p(eps), _p(P16), _p(P32), _p(qmu), P.shape[0], d, nq, int(k), int(qtile), _p(counts),
          _p(cand_rows), _p(cand_scores), cand_rows.shape[1], _p(rows2), _p(scores2), rows2.shape[1], _p(n2), _p(status), _p(khat), _p(D), _p(I),
          (1 if exhaustive else 0) | (2 if tiled else 0), _stream())
@@ -1193,16 +1198,21 @@ def index_col_mean(P32):
     return mu
 
 
+def _chk_sample(op, sample_bf16, s_rows, d):
+    """the whole shard's bf16 threshold sample an index op writes into, or None"""
+    if sample_bf16 is not None:
+        _chk(sample_bf16, BF16, "sample_bf16", 2)
+        if int(s_rows) > sample_bf16.shape[0] or sample_bf16.shape[1] != d or not sample_bf16.is_contiguous():
+            raise ValueError(f"{op}: the sample needs s_rows rows of width d")
+
+
 def index_center_cast(P32, mu, P16, sample_bf16, s_stride, s_rows, flag, row0=0, cmax=None):
     """P16 = fp16(P32 - mu), sample = bf16 of every s_stride-th centred row; returns the DEVICE int32 word holding the bit pattern of
     max_r |P32[r] - mu|^2 as fp32 (cldrd_index_center_cast) - read it with ``.view(torch.float32).item()``.
     A shard attached chunk by chunk: ``P32`` / ``P16`` are rows [row0, row0 + len(P32)) of it, ``sample_bf16`` is the whole shard's sample;
     ``cmax`` (int32 [1], zeroed before the first chunk; None: a fresh one) and ``flag`` accumulate over the chunks."""
     _chk(P32, F32, "P32", 2), _chk(mu, F32, "mu", 1), _chk(P16, F16, "P16", 2)
-    if sample_bf16 is not None:
-        _chk(sample_bf16, BF16, "sample_bf16", 2)
-        if int(s_rows) > sample_bf16.shape[0] or sample_bf16.shape[1] != P32.shape[1] or not sample_bf16.is_contiguous():
-            raise ValueError("index_center_cast: the sample needs s_rows rows of width d")
+    _chk_sample("index_center_cast", sample_bf16, s_rows, P32.shape[1])
     if P16.shape != P32.shape or mu.numel() != P32.shape[1] or not (P32.is_contiguous() and P16.is_contiguous()):
         raise ValueError("index_center_cast: P16 must be the contiguous [rows, d] slice that matches P32")
     if cmax is None:
@@ -1229,10 +1239,7 @@ def index_quantize_i8(P32, mu, R8, scale, sample_bf16, s_stride, s_rows, flag, b
     _chk(P32, F32, "P32", 2), _chk(mu, F32, "mu", 1), _chk(R8, I8, "R8", 2), _chk(scale, F32, "scale", 1)
     _chk(b1, torch.int32, "b1", 1), _chk(c2, torch.int32, "c2", 1)
     _chk_i8_width(P32.shape[1], "index_quantize_i8")
-    if sample_bf16 is not None:
-        _chk(sample_bf16, BF16, "sample_bf16", 2)
-        if int(s_rows) > sample_bf16.shape[0] or sample_bf16.shape[1] != P32.shape[1] or not sample_bf16.is_contiguous():
-            raise ValueError("index_quantize_i8: the sample needs s_rows rows of width d")
+    _chk_sample("index_quantize_i8", sample_bf16, s_rows, P32.shape[1])
     if R8.shape != P32.shape or scale.numel() != P32.shape[0] or mu.numel() != P32.shape[1] \
             or not (P32.is_contiguous() and R8.is_contiguous() and scale.is_contiguous()):
         raise ValueError("index_quantize_i8: R8 / scale must be the contiguous slices that match P32")
@@ -1301,12 +1308,7 @@ def flatip_search_i8(q32, qd, sq, thr, eps, R8, scale, qmu, k, counts, cand_rows
             raise ValueError("flatip_search_i8: qd must be the contiguous [2, nq, d] digit planes of these queries, sq [nq]")
     if R8.shape[1] != d or scale.numel() != R8.shape[0] or qmu.numel() < nq:
         raise ValueError("flatip_search_i8: the rows must be [rows, d], their scales [rows] and qmu [nq]")
-    if cand_rows.shape[0] < qtile or rows2.shape[0] < qtile:
-        raise ValueError("flatip_search_i8: the candidate buffers need qtile rows")
-    if counts.numel() < ((nq + qtile - 1) // qtile) * (qtile + 1) or n2.numel() < nq or status.numel() < nq or khat.numel() < nq or D.shape != (nq, k) or I.shape != (nq, k):
-        raise ValueError("flatip_search_i8: buffer sizes do not match nq / k")
-    if not (q32.is_contiguous() and R8.is_contiguous() and scale.is_contiguous() and D.is_contiguous() and I.is_contiguous() and qmu.is_contiguous()):
-        raise ValueError("flatip_search_i8: operands must be contiguous")
+    _chk_search_buffers("flatip_search_i8", nq, k, qtile, counts, cand_rows, rows2, n2, status, khat, D, I, (q32, R8, scale, qmu))
     call("cldrd_flatip_search_i8", _p(q32), _p(qd), _p(sq), _p(thr), _p(eps), _p(R8), _p(scale), _p(qmu), R8.shape[0], d, nq, int(k), int(qtile),
          _p(counts), _p(cand_rows), _p(cand_scores), cand_rows.shape[1], _p(rows2), _p(scores2), rows2.shape[1], _p(n2), _p(status), _p(khat),
          _p(D), _p(I), 1 if exhaustive else 0, _stream())

@@ -36,6 +36,7 @@ import os
 import pickle
 import warnings
 from timeit import default_timer as timer
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -202,26 +203,52 @@ class _Resident:
     """What an attached shard keeps in HBM and what the search needs to know about it.  Built completely by ``FlatIPIndex._attach`` and
     never changed afterwards, except for the lazily filled members at the end."""
     device: torch.device
-    p16: object                  # fp16 [n, d] = fp16(p - mu): what the scan reads; in fp16-row mode also the stored rows; None = int8-row mode
-    p32: object                  # fp32 [n, d], the rows the re-score reads; None = fp16-row mode
+    mode: str                    # "float32" | "float16" | "int8": the key of ``_MODES``, which says which of the row tensors below exist
+    n: int                       # rows of the shard
     mu: torch.Tensor             # fp32 [d]: mean row of the shard
     sample: torch.Tensor         # bf16 [s_rows rounded up to 8, d]: every s_stride-th centred row (threshold estimate)
     s_stride: int
     s_rows: int
-    cnorm: float                 # max |p - mu|
+    cnorm: float                 # max |p - mu| (int8-row mode: of the stored centred rows, max_r a_r |R8[r]|_2)
     raw_max: float               # max |p|
     max_norm: float              # the norm the eps bound multiplies (FlatIPIndex._attach)
     query_tile: int              # queries per pass over the index bytes
-    r8: object = None            # int8-row mode: int8 [n, d], the quantised centred rows (scan operand AND stored rows) ...
+    p16: object = None           # float32 / float16: fp16 [n, d] = fp16(p - mu), what the scan reads; in fp16-row mode also the stored rows
+    p32: object = None           # float32: fp32 [n, d], the rows the re-score reads
+    r8: object = None            # int8: int8 [n, d], the quantised centred rows (scan operand AND stored rows) ...
     scale: object = None         # ... and fp32 [n], their scales a_r: the stored row is mu + a_r R8[r]
-    b1: float = 0.0              # int8-row mode: max_r a_r |R8[r]|_1, what the query-digit term of eps multiplies
+    b1: float = 0.0              # int8: max_r a_r |R8[r]|_1, what the query-digit term of eps multiplies
     ids_dev: object = None       # int64 [n]: the id table, uploaded by the first search that maps ids
     mu_host: object = None       # np.float32 [d]: the host copy of mu, made when first asked for
     ws: dict = dataclasses.field(default_factory=dict)       # cap2 -> per-batch scratch of the search
 
-    @property
-    def n(self) -> int:
-        return (self.p16 if self.r8 is None else self.r8).shape[0]
+
+@dataclasses.dataclass
+class _StoredRows:
+    """The stored rows of fp16-row or int8-row mode on the host, as their file holds them: what ``FlatIPIndex.read`` keeps of such a file
+    (``rows`` memory-mapped) and what ``FlatIPIndex.write`` writes, from a file, from an attached shard or freshly encoded."""
+    mode: str                    # "float16" | "int8"
+    rows: np.ndarray             # np.float16 [n, d] = fp16(p - mu) | np.int8 [n, d] = R8
+    scale: object                # int8: np.float32 [n], the scales a_r; float16: None
+    mu: np.ndarray               # np.float32 [d]
+    cnorm: float                 # max |p - mu| | max_r a_r |R8[r]|_2
+    raw_max: float               # max |p|
+    b1: float = 0.0              # int8: max_r a_r |R8[r]|_1
+
+
+@dataclasses.dataclass
+class _ScanQueries:
+    """The queries as the scan reads them: the fp16 copy ``qh`` [nq, d], or - int8-row mode - the digit planes ``qd`` int8 [2, nq, d] and their
+    common scale ``sq`` [nq].  Empty for a search that does not scan (exhaustive)."""
+    qh: object = None
+    qd: object = None
+    sq: object = None
+
+    def select(self, sel) -> "_ScanQueries":         # the queries ``sel`` (a slice or an index tensor)
+        qd = self.qd
+        if qd is not None:
+            qd = (qd[:, sel] if isinstance(sel, slice) else qd.index_select(1, sel)).contiguous()
+        return _ScanQueries(_sel(self.qh, sel), qd, _sel(self.sq, sel))
 
 
 def _host_tensor(a: np.ndarray) -> torch.Tensor:
@@ -234,14 +261,6 @@ def _host_tensor(a: np.ndarray) -> torch.Tensor:
 def _sel(t, sel):
     """the entries ``sel`` (a slice or an index tensor) of a per-query tensor that may be None"""
     return None if t is None else (t[sel] if isinstance(sel, slice) else t.index_select(0, sel))
-
-
-def _sel_scan(qs, sel):
-    """:func:`_sel` of the queries' scan operand: the fp16 copy [nq, d], or in int8-row mode the pair (digit planes int8 [2, nq, d], sq [nq])"""
-    if isinstance(qs, tuple):
-        qd = qs[0][:, sel] if isinstance(sel, slice) else qs[0].index_select(1, sel)
-        return qd.contiguous(), _sel(qs[1], sel)
-    return _sel(qs, sel)
 
 
 def _all_missing(nq: int, k: int):
@@ -296,10 +315,146 @@ def _retry_step(status: np.ndarray, thr: np.ndarray, eps: np.ndarray, khat: np.n
     return t, bool(((status & 4) != 0).any()), bool(((status & 16) != 0).any())
 
 
+# ---- the three row modes: everything that differs between them, from the file to the chained search, is stated here and nowhere else ----
+_EXCLUSION = {"FlatIPIndex.to_gpu": "FlatIPIndex.to_gpu: fp16_rows and int8_rows exclude one another",
+              "FlatIPIndex.from_device_rows": "FlatIPIndex.from_device_rows: fp16_rows and int8_rows exclude one another",
+              "FlatIPIndex.write": "FlatIPIndex.write: fp16 and int8 exclude one another",
+              "write_index": "write_index: int8=True excludes faiss_format=True and fp16=True (the int8-row format is this package's own)"}
+_NOT_FINITE16 = "FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow"
+_NOT_FINITE8 = "FlatIPIndex: embeddings must be finite for the int8 rows"
+
+
+def _requested_mode(fp16: bool, int8: bool, who: str) -> str:
+    """The row mode a caller's two flags ask for; ``who`` (a key of ``_EXCLUSION``) names the caller in the refusal of both at once."""
+    if fp16 and int8:
+        raise ValueError(_EXCLUSION[who])
+    return "int8" if int8 else ("float16" if fp16 else "float32")
+
+
+def _attach_mode(holds, requested: str) -> str:
+    """The mode ``to_gpu`` attaches in: the stored rows of a file (``holds`` "float16" / "int8") as they are, fp32 rows ("float32") as ``requested``."""
+    if (holds, requested) == ("float16", "int8"):
+        raise ValueError("FlatIPIndex.to_gpu: this index holds fp16 rows only (read from an fp16-row file): int8 rows are quantised from fp32 rows")
+    if holds in ("float16", "int8"):
+        return holds
+    if holds is None and requested != "float32":
+        raise ValueError("FlatIPIndex.to_gpu: the index holds no rows")
+    return requested
+
+
+def _check16(d, n, fresh):
+    """the shard a 16-bit attach takes; ``fresh``: fp16-row mode made from fp32 rows (the mean-row kernel's limit applies, the fp32 form keeps its own)"""
+    if d % 4:
+        raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
+    if fresh and d > 2048:
+        raise ValueError(f"FlatIPIndex: fp16-row mode supports an embedding width of at most 2048 (the mean-row kernel's limit), got {d}")
+    if fresh and n <= 0:
+        raise ValueError("FlatIPIndex: no rows to attach")
+
+
+def _check8(d, n=1, fresh=True):
+    if d % 64 or d > 2048 or d <= 0:
+        raise ValueError(f"FlatIPIndex: int8-row mode supports an embedding width that is a multiple of 64 and at most 2048, got {d}")
+    if n <= 0:
+        raise ValueError("FlatIPIndex: no rows to attach")
+
+
+def _upload_rest8(st, dest, sample, s_stride, s_rows):      # the scales as they are; the sample rows are dequantised on the host
+    dest["scale"].copy_(_host_tensor(np.ascontiguousarray(st.scale, dtype=np.float32)))
+    for lo in range(0, s_rows, HOST_CHUNK_ROWS):
+        sel = np.arange(lo, min(s_rows, lo + HOST_CHUNK_ROWS)) * s_stride
+        rows = st.scale[sel][:, None] * np.asarray(st.rows[sel], dtype=np.float32)       # fp32 products, as the device forms them
+        sample[lo:lo + sel.size].copy_(torch.from_numpy(rows).to(torch.bfloat16))
+
+
+def _encode16(chunk, mu):
+    c = np.asarray(chunk, dtype=np.float32) - mu                  # fp32 subtraction, as the device does it
+    if not (np.abs(c) <= 65504.0).all():
+        raise ValueError(_NOT_FINITE16)
+    return c.astype(np.float16), None, 0.0, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max())          # round to nearest even
+
+
+def _prep16(q32, qb, qnorm, flag):
+    qh = torch.empty(q32.shape, dtype=torch.float16, device=q32.device)
+    ops.topk_prep_queries(q32, qh, qb, qnorm, flag)
+    return _ScanQueries(qh=qh)
+
+
+def _prep8(q32, qb, qnorm, flag):
+    qs = _ScanQueries(qd=torch.empty(2, *q32.shape, dtype=torch.int8, device=q32.device), sq=torch.empty(q32.shape[0], dtype=torch.float32, device=q32.device))
+    ops.topk_prep_queries_i8(q32, qs.qd, qb, qs.sq, qnorm, flag)
+    return qs
+
+
+# One record per mode.  Storage: `rows_field` names the _Resident member the scan reads (in the two compact modes also the stored rows), `new_rows`
+# allocates the mode's resident row tensors as a dict of _Resident members; `file_format` / `rows_ext` / `np_dtype` / `bad_file`: the mode's file.
+# Attach (FlatIPIndex._attach is the skeleton): `check(d, n, fresh)` refuses a shard (fresh: made from fp32 rows, not uploaded from a file),
+# `alloc_first`: the resident tensors are allocated before the statistics walk, `convert`: the per-chunk op over `n_maxima` running maxima, which
+# `norms(values) -> (cnorm, b1)` reads, `upload_rest` finishes an upload from a file (the sample), `max_norm`: the norm eps multiplies.  Host writer:
+# `host_check(d)`, `encode(chunk, mu) -> (rows, scales or None, chunk max of the l1 bound, chunk max of the squared centred norm)`.  Search: `prep`
+# makes the queries' scan operand, `bound` runs the threshold / eps op, `chain` the chained search over the rows `rows` of the shard; `qmu`: scores
+# are <q, mu> + ... of the stored rows; `status_mask`: the status bits that count; `bad_queries`: the refusal of the range flag.
+_MODES = {"float16": SimpleNamespace(
+    rows_field="p16", new_rows=lambda n, d, dev: {"p16": torch.empty(n, d, dtype=torch.float16, device=dev)},
+    file_format=FORMAT_F16, rows_ext=".emb16.npy", np_dtype=np.float16, bad_file="{path}.emb16.npy: expected float16 [n, {d}]",
+    check=_check16, alloc_first=False, n_maxima=1, norms=lambda v: (math.sqrt(v[0]), 0.0),
+    # centre + cast: fp16 rows + max centred norm + bf16 sample + range flag in ONE pass per chunk (cldrd_index_center_cast)
+    convert=lambda c, mu, dest, lo, sample, s_stride, s_rows, flag, maxima: ops.index_center_cast(
+        c, mu, dest["p16"][lo:lo + c.shape[0]], sample, s_stride, s_rows, flag, row0=lo, cmax=maxima[0]),
+    upload_rest=lambda st, dest, sample, s_stride, s_rows: ops.gather_cast_rows(dest["p16"], sample, s_rows, s_stride),
+    # max |p - mu| for the bound, plus 2^-12 max|p|: the fp32 subtraction p - mu itself rounds (2^-24 |p| per element), which moves a
+    # centred score by up to |q| sqrt(d) 2^-24 max|p| < 2^-10 |q| (2^-12 max|p|) - folded into the norm the eps formula multiplies by 2^-10
+    # (fp16-row mode: the scan's operand IS the stored row, so that term is slack there; the bound is kept as it is)
+    max_norm=lambda cnorm, raw_max: cnorm * (1.0 + 1e-6) + raw_max * 2.0 ** -12,
+    # queries per pass over the index bytes: 256 at d = 768 (the streaming scan's two-batch form), else the reference's 128
+    # (`query_tile_request`: a test hook that asks for 128 at d = 768)
+    query_tile=lambda d, request: 256 if (d == 768 and request != 128) else 128,
+    not_finite=_NOT_FINITE16, no_host_rows="FlatIPIndex.write: the index holds no rows", host_check=lambda d: None, encode=_encode16,
+    prep=_prep16, bound=lambda res, d, est, sq, qnorm, thr, eps: ops.topk_thresholds(est, qnorm, res.max_norm, d, thr, eps),
+    chain=lambda res, rows, q32, qs, thr, eps, qmu, bufs, exhaustive, tiled: ops.flatip_search(
+        q32, qs.qh, thr, eps, res.p16[rows], *bufs, exhaustive=exhaustive, qtile=res.query_tile, tiled=tiled, qmu=qmu),
+    qmu=True, status_mask=~0, bad_queries="queries must be finite and inside the fp16 range (|x| <= 65504)")}
+# the fp32 form: the fp16 rows are the scan's shadow of ONE resident fp32 tensor, which the re-score reads; it has no file of stored rows
+_MODES["float32"] = SimpleNamespace(**{
+    **vars(_MODES["float16"]), "check": lambda d, n, fresh: _check16(d, n, False), "qmu": False,
+    "chain": lambda res, rows, q32, qs, thr, eps, qmu, bufs, exhaustive, tiled: ops.flatip_search(
+        q32, qs.qh, thr, eps, res.p16[rows], *bufs, exhaustive=exhaustive, qtile=res.query_tile, tiled=tiled, P32=res.p32[rows])})
+_MODES["int8"] = SimpleNamespace(
+    rows_field="r8", new_rows=lambda n, d, dev: {"r8": torch.empty(n, d, dtype=torch.int8, device=dev), "scale": torch.empty(n, dtype=torch.float32, device=dev)},
+    file_format=FORMAT_I8, rows_ext=".emb8.npy", np_dtype=np.int8, bad_file="{path}.emb8.npy / .scale.npy: expected int8 [n, {d}] and float32 [n]",
+    check=_check8, alloc_first=True, n_maxima=2, norms=lambda v: (math.sqrt(v[1]), v[0]),
+    # quantise: R8, a, the bf16 sample of the stored centred rows and the two maxima of the bound per chunk (cldrd_index_quantize_i8)
+    convert=lambda c, mu, dest, lo, sample, s_stride, s_rows, flag, maxima: ops.index_quantize_i8(
+        c, mu, dest["r8"][lo:lo + c.shape[0]], dest["scale"][lo:lo + c.shape[0]], sample, s_stride, s_rows, flag, *maxima, row0=lo),
+    # the bound's two norms with the slack of their own fp32 rounding (csrc/topk_i8.hip: thresholds_i8_kernel)
+    max_norm=lambda cnorm, raw_max: cnorm * (1.0 + 1e-6), query_tile=lambda d, request: 128, upload_rest=_upload_rest8,
+    not_finite=_NOT_FINITE8, no_host_rows="FlatIPIndex.write: the index holds no fp32 rows to quantise", host_check=_check8,
+    encode=lambda chunk, mu: (lambda r8, a, l1, l2sq: (r8, a, l1.max(), l2sq.max()))(*FlatIPIndex.quantize_rows_i8(chunk, mu)),
+    prep=_prep8, bound=lambda res, d, est, sq, qnorm, thr, eps: ops.topk_thresholds_i8(est, sq, qnorm, res.b1, res.max_norm, d, thr, eps),
+    # the int8 scan has no tiled form and no on-chip hit list: a hit is lost only to a full candidate list - bit 2 of THAT query; the
+    # dropped-hit counter (bit 4) marks every query of its pass and carries nothing more
+    chain=lambda res, rows, q32, qs, thr, eps, qmu, bufs, exhaustive, tiled: ops.flatip_search_i8(
+        q32, qs.qd, qs.sq, thr, eps, res.r8[rows], res.scale[rows], qmu, *bufs, exhaustive=exhaustive, qtile=res.query_tile),
+    qmu=True, status_mask=~4, bad_queries="queries must be finite")
+_FILE_MODES = {m.file_format: name for name, m in _MODES.items() if name != "float32"}
+
+
+def _host_stats(emb, not_finite: str):
+    """The statistics pass of the host encoder over fp32 rows in chunks: -> (mu = fp32 of the fp64 column mean, max |p|^2 in fp64)."""
+    colsum, raw_sq = np.zeros(emb.shape[1], dtype=np.float64), 0.0
+    for lo in range(0, emb.shape[0], HOST_CHUNK_ROWS):
+        c = np.asarray(emb[lo:lo + HOST_CHUNK_ROWS], dtype=np.float32)
+        colsum += c.sum(axis=0, dtype=np.float64)
+        raw_sq = max(raw_sq, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max()))
+    if not (math.isfinite(raw_sq) and np.isfinite(colsum).all()):
+        raise ValueError(not_finite)
+    return (colsum / float(emb.shape[0])).astype(np.float32), raw_sq
+
+
 class FlatIPIndex:
     """Exact inner-product index over one shard of rows (faiss ``IndexIDMap(IndexFlatIP(d))`` semantics).
 
-    Two row modes.  Default (``row_dtype == "float32"``): the fp32 rows are resident next to the fp16 scan shadow and scores are exact fp32
+    Three row modes.  Default (``row_dtype == "float32"``): the fp32 rows are resident next to the fp16 scan shadow and scores are exact fp32
     inner products (6 B per element in HBM).  **fp16-row mode** (``to_gpu(dev, fp16_rows=True)``, ``convert_index_to_gpu(..., useFloat16=True)``,
     or an index read from an fp16-row file; ``row_dtype == "float16"``): the shard keeps ``mu`` (fp32 [d], its mean row) and
     ``R16 = fp16(p - mu)`` (round to nearest even) and nothing else of the rows - 2 B per element.  The stored row is ``mu + R16[r]`` and
@@ -323,10 +478,11 @@ class FlatIPIndex:
     rounding of the query, and the top-k of ``s`` is PROVEN as in the other modes (csrc/topk_i8.hip derives the bound).  What is approximate
     is the stored row, not the search: rankings differ from the fp32 rows' where quantisation moves a score across a neighbour's.
 
-    State.  Host side: ``embeddings`` / ``ids`` / ``id_offset``, or - an index read from an fp16-row file - ``_file16`` (its rows, ``mu`` and
-    norms), or - read from an int8-row file - ``_file8`` (``R8``, ``a``, ``mu``, the bound's two maxima, max |p|).  Device side: ONE :class:`_Resident` in ``_res``, None until an attach has succeeded: :meth:`_attach` assigns it as its last
-    statement, :meth:`add_with_ids` drops it.  ``device``, ``query_tile``, ``_p16``, ``_p32``, ``_sample`` and
-    ``_max_norm`` are read-only views of it (what bench.py, the tools and the tests read)."""
+    State.  Host side: ``embeddings`` / ``ids`` / ``id_offset``, or - an index read from an fp16-row or int8-row file - ``_stored``, a
+    :class:`_StoredRows` (the rows as the file holds them, ``mu``, the norms of the bound; its ``mode`` is the index's).  Device side: ONE
+    :class:`_Resident` in ``_res``, None until an attach has succeeded: :meth:`_attach` assigns it as its last statement, :meth:`add_with_ids`
+    drops it; its ``mode`` keys ``_MODES``, the one place that says what differs between the modes.  ``device``, ``query_tile``, ``_p16``,
+    ``_p32``, ``_sample`` and ``_max_norm`` are read-only views of it (what bench.py, the tools and the tests read)."""
 
     def __init__(self, d: int):
         self.d = d
@@ -334,10 +490,7 @@ class FlatIPIndex:
         self.embeddings = None       # np.float32 [n, d] on the host until moved to a GPU
         self.ids = None              # np.int64 [n] or None (ids = row positions + id_offset)
         self.id_offset = 0
-        self._file16 = None          # an index read from an fp16-row file (no fp32 rows anywhere): (np.float16 [n, d] = fp16(p - mu),
-                                     # np.float32 mu [d], max |p - mu|, max |p|) as the file holds them
-        self._file8 = None           # an index read from an int8-row file: (np.int8 [n, d] R8, np.float32 a [n], np.float32 mu [d],
-                                     # max a_r |R8[r]|_1, max a_r |R8[r]|_2, max |p|) as the file holds them
+        self._stored = None          # _StoredRows: an index read from an fp16-row or int8-row file (no fp32 rows anywhere)
         self._res = None             # _Resident: the attached shard
         self.last_stats = {}
         self.profile = False          # bench.py: time the search with HIP events and count candidates
@@ -355,9 +508,7 @@ class FlatIPIndex:
     def row_dtype(self) -> str:
         """``"float16"``: fp16-row mode (attached with ``fp16_rows=True`` or read from an fp16-row file); ``"int8"``: int8-row mode (attached with
         ``int8_rows=True`` or read from an int8-row file); ``"float32"`` otherwise."""
-        if self._file8 is not None or (self._res is not None and self._res.r8 is not None):
-            return "int8"
-        return "float16" if (self._file16 is not None or (self._res is not None and self._res.p32 is None)) else "float32"
+        return self._stored.mode if self._stored is not None else (self._res.mode if self._res is not None else "float32")
 
     @property
     def mu(self):
@@ -366,10 +517,8 @@ class FlatIPIndex:
             if self._res.mu_host is None:
                 self._res.mu_host = self._res.mu.cpu().numpy()
             mu = self._res.mu_host
-        elif self._file16 is not None:
-            mu = self._file16[1]
-        elif self._file8 is not None:
-            mu = self._file8[2]
+        elif self._stored is not None:
+            mu = self._stored.mu
         else:
             return None
         out = mu.view()
@@ -378,10 +527,8 @@ class FlatIPIndex:
 
     # -- construction -----------------------------------------------------------------------------------------
     def add_with_ids(self, embeddings, ids):
-        if self._file16 is not None:
-            raise ValueError("an index read from an fp16-row file holds no fp32 rows: rows cannot be added to it")
-        if self._file8 is not None:
-            raise ValueError("an index read from an int8-row file holds no fp32 rows: rows cannot be added to it")
+        if self._stored is not None:
+            raise ValueError(f"an index read from an {self._stored.mode.replace('float', 'fp')}-row file holds no fp32 rows: rows cannot be added to it")
         emb = np.ascontiguousarray(embeddings, dtype=np.float32)
         if emb.ndim != 2 or emb.shape[1] != self.d:
             raise ValueError("embeddings must be [n, d]")
@@ -403,18 +550,15 @@ class FlatIPIndex:
     def from_device_rows(cls, rows32: torch.Tensor, id_offset: int = 0, fp16_rows: bool = False, int8_rows: bool = False) -> "FlatIPIndex":
         """Index over fp32 rows that already live in HBM (e.g. an encode shard that never left the GPU).  ``fp16_rows``: centre + cast on the
         device and keep no reference to ``rows32`` (fp16-row mode, class docstring); ``int8_rows``: the same into int8-row mode."""
-        if fp16_rows and int8_rows:
-            raise ValueError("FlatIPIndex.from_device_rows: fp16_rows and int8_rows exclude one another")
+        mode = _requested_mode(fp16_rows, int8_rows, "FlatIPIndex.from_device_rows")
         idx = cls(rows32.shape[1])
         n = idx.ntotal = rows32.shape[0]
         idx.id_offset = id_offset
         rows32 = rows32.contiguous()
-        if int8_rows:
-            idx._attach8(rows32.device, n, lambda: ((lo, rows32[lo:lo + ATTACH_CHUNK_ROWS]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
-        elif fp16_rows:
-            idx._attach(rows32.device, n, lambda: ((lo, rows32[lo:lo + ATTACH_CHUNK_ROWS]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
+        if mode == "float32":
+            idx._attach(rows32.device, n, mode, lambda: ((0, rows32),), keep32=rows32)
         else:
-            idx._attach(rows32.device, n, lambda: ((0, rows32),), keep32=rows32)
+            idx._attach(rows32.device, n, mode, lambda: ((lo, rows32[lo:lo + ATTACH_CHUNK_ROWS]) for lo in range(0, n, ATTACH_CHUNK_ROWS)))
         return idx
 
     def to_gpu(self, device, fp16_rows: bool = False, int8_rows: bool = False):
@@ -423,28 +567,19 @@ class FlatIPIndex:
         rows and the sample become resident; the fp32 rows pass through two staging buffers of ``ATTACH_CHUNK_ROWS`` rows.
         ``int8_rows=True`` (or an index read from an int8-row file, whatever the arguments say): int8-row mode - ``mu``, the int8 rows, their
         scales and the sample, staged the same way.  The two flags exclude one another."""
-        if fp16_rows and int8_rows:
-            raise ValueError("FlatIPIndex.to_gpu: fp16_rows and int8_rows exclude one another")
+        requested = _requested_mode(fp16_rows, int8_rows, "FlatIPIndex.to_gpu")
         device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("FlatIPIndex.search runs on the GPU only (no CPU path)")
-        if self._file8 is not None:
-            self._attach8(device, self._file8[0].shape[0], None)
-        elif self._file16 is not None:
-            if int8_rows:
-                raise ValueError("FlatIPIndex.to_gpu: this index holds fp16 rows only (read from an fp16-row file): int8 rows are quantised from fp32 rows")
-            self._attach(device, self._file16[0].shape[0], None)
-        elif int8_rows:
-            if self.embeddings is None:
-                raise ValueError("FlatIPIndex.to_gpu: the index holds no rows")
-            self._attach8(device, self.embeddings.shape[0], lambda: self._staged_chunks(device))
-        elif fp16_rows:
-            if self.embeddings is None:
-                raise ValueError("FlatIPIndex.to_gpu: the index holds no rows")
-            self._attach(device, self.embeddings.shape[0], lambda: self._staged_chunks(device))
-        else:
+        stored = self._stored
+        mode = _attach_mode(stored.mode if stored is not None else ("float32" if self.embeddings is not None else None), requested)
+        if stored is not None:
+            self._attach(device, stored.rows.shape[0], mode, None)
+        elif mode == "float32":
             rows32 = _host_tensor(np.ascontiguousarray(self.embeddings)).to(device)        # the fp32 form uploads once
-            self._attach(device, rows32.shape[0], lambda: ((0, rows32),), keep32=rows32)
+            self._attach(device, rows32.shape[0], mode, lambda: ((0, rows32),), keep32=rows32)
+        else:
+            self._attach(device, self.embeddings.shape[0], mode, lambda: self._staged_chunks(device))
         return self
 
     def _staged_chunks(self, device):
@@ -507,102 +642,50 @@ class FlatIPIndex:
         s_rows = min(n, (n + s_stride - 1) // s_stride)
         return s_stride, s_rows, torch.zeros((s_rows + 7) // 8 * 8, self.d, dtype=torch.bfloat16, device=device)
 
-    def _attach8(self, device, n: int, chunks):
-        """The attach of int8-row mode.  ``chunks()`` as in :meth:`_attach`, walked twice: statistics (``mu``), then cldrd_index_quantize_i8 per
-        chunk - ``R8``, ``a``, the bf16 sample of the stored centred rows and the two maxima of the bound, max_r a_r |R8[r]|_1 and
-        max_r a_r |R8[r]|_2.  ``chunks=None``: an index read from an int8-row file - ``R8`` / ``a`` go to HBM as they are, ``mu`` and the maxima
-        come from the file, the sample rows are dequantised on the host (every s_stride-th row)."""
-        d, file8 = self.d, self._file8 if chunks is None else None
-        if d % 64 or d > 2048 or d <= 0:
-            raise ValueError(f"FlatIPIndex: int8-row mode supports an embedding width that is a multiple of 64 and at most 2048, got {d}")
-        if n <= 0:
-            raise ValueError("FlatIPIndex: no rows to attach")
-        i32 = dict(dtype=torch.int32, device=device)
-        with torch.cuda.device(device):
-            s_stride, s_rows, sample = self._new_sample(device, n)
-            r8 = torch.empty(n, d, dtype=torch.int8, device=device)
-            scale = torch.empty(n, dtype=torch.float32, device=device)
-            flag = 0
-            if file8 is not None:
-                mu_h, b1, cnorm, raw_max = file8[2], file8[3], file8[4], file8[5]
-                mu = torch.from_numpy(np.ascontiguousarray(mu_h, dtype=np.float32)).to(device)
-                for lo in range(0, n, ATTACH_CHUNK_ROWS):
-                    r8[lo:lo + ATTACH_CHUNK_ROWS].copy_(_host_tensor(np.ascontiguousarray(file8[0][lo:lo + ATTACH_CHUNK_ROWS])))
-                scale.copy_(_host_tensor(np.ascontiguousarray(file8[1], dtype=np.float32)))
-                for lo in range(0, s_rows, HOST_CHUNK_ROWS):
-                    sel = np.arange(lo, min(s_rows, lo + HOST_CHUNK_ROWS)) * s_stride
-                    rows = file8[1][sel][:, None] * np.asarray(file8[0][sel], dtype=np.float32)       # fp32 products, as the device forms them
-                    sample[lo:lo + sel.size].copy_(torch.from_numpy(rows).to(torch.bfloat16))
-            else:
-                mu, mu_h, raw_max = self._shard_stats(device, n, chunks, one_chunk=False)
-                flag_d, b1_d, c2_d = torch.zeros(1, **i32), torch.zeros(1, **i32), torch.zeros(1, **i32)
-                for lo, c in chunks():
-                    m = c.shape[0]
-                    ops.index_quantize_i8(c, mu, r8[lo:lo + m], scale[lo:lo + m], sample, s_stride, s_rows, flag_d, b1_d, c2_d, row0=lo)
-                del c
-                b1 = float(b1_d.view(torch.float32).item())
-                cnorm, flag = math.sqrt(float(c2_d.view(torch.float32).item())), int(flag_d.item())
-        if flag or not (math.isfinite(raw_max) and math.isfinite(b1) and math.isfinite(cnorm)):
-            raise ValueError("FlatIPIndex: embeddings must be finite for the int8 rows")
-        # the bound's two norms with the slack of their own fp32 rounding (csrc/topk_i8.hip: thresholds_i8_kernel)
-        self._res = _Resident(device=device, p16=None, p32=None, mu=mu, sample=sample, s_stride=s_stride, s_rows=s_rows, cnorm=cnorm,
-                              raw_max=raw_max, max_norm=cnorm * (1.0 + 1e-6), query_tile=128, mu_host=mu_h, r8=r8, scale=scale, b1=b1)
+    def _attach(self, device, n: int, mode: str, chunks, keep32=None):
+        """Every attach, in row mode ``mode``.  ``chunks()`` yields (first row, fp32 device tensor) over the shard in order and is walked twice
+        (statistics, then the mode's conversion: centre + cast, or quantise); the fp32 form is the one-chunk case over the whole tensor, which
+        ``keep32`` keeps resident for the re-score.  In the other two modes no fp32 row stays in HBM.  ``chunks=None``: an index read from an
+        fp16-row or int8-row file - the stored rows go to HBM as they are (chunked H2D straight into their tensor), the sample is made from
+        them, ``mu`` and the norms come from the file: no statistics pass.
 
-    def _attach(self, device, n: int, chunks, keep32=None):
-        """Every attach.  ``chunks()`` yields (first row, fp32 device tensor) over the shard in order and is walked twice (statistics, then
-        centre + cast); the fp32 form is the one-chunk case over the whole tensor, which ``keep32`` keeps resident for the re-score.
-        ``keep32=None``: fp16-row mode, no fp32 row stays in HBM.  ``chunks=None``: an index read from an fp16-row file - the fp16 rows go
-        to HBM as they are (chunked H2D straight into P16), the sample is gathered on the device, ``mu`` and the norms come from the file:
-        no statistics pass.
-
-        The 16-bit rows are CENTRED on the shard's mean row mu.  <q, p - mu> = <q, p> - <q, mu> moves every score of a query by the same
+        The stored / shadow rows are CENTRED on the shard's mean row mu.  <q, p - mu> = <q, p> - <q, mu> moves every score of a query by the same
         constant, so the ranking - all the scan decides - is unchanged, while the rounding bound of the scan, eps ~ 2^-10 |q| max|p - mu|,
         shrinks with the rows' common component.  Dual-encoder CLS embeddings are dominated by one (reference model: q . p = 17 +- 2 over a
         corpus): on the CLS-like shard of the tests eps goes from 0.042 to 0.007 and the 2 eps band under the k-th score from ~1 250 rows to
         ~200, i.e. the re-score gathers about half the rows and the scan emits half the hits; on an isotropic corpus mu ~ 0 and nothing
         changes.  In fp32 mode the exact scores still come from the untouched fp32 rows (re-score)."""
-        d, file16 = self.d, self._file16 if chunks is None else None
-        if d % 4:
-            raise ValueError("FlatIPIndex: the embedding width must be a multiple of 4")
-        if keep32 is None and file16 is None:
-            if d > 2048:
-                raise ValueError(f"FlatIPIndex: fp16-row mode supports an embedding width of at most 2048 (the mean-row kernel's limit), got {d}")
-            if n <= 0:
-                raise ValueError("FlatIPIndex: no rows to attach")
-        i32 = dict(dtype=torch.int32, device=device)
+        d, m = self.d, _MODES[mode]
+        stored = self._stored if chunks is None else None
+        m.check(d, n, stored is None)
         with torch.cuda.device(device):
+            if m.alloc_first:
+                (s_stride, s_rows, sample), dest = self._new_sample(device, n), m.new_rows(n, d, device)
             # statistics: max |p|^2 and the mean row of every chunk (cldrd_row_sqnorm_max, cldrd_index_col_mean: fp64 column sums)
-            mu_h = None
-            if file16 is not None:
-                mu_h, cnorm, raw_max = file16[1], file16[2], file16[3]
+            if stored is not None:
+                mu_h, raw_max = stored.mu, stored.raw_max
                 mu = torch.from_numpy(np.ascontiguousarray(mu_h, dtype=np.float32)).to(device)
             else:
                 mu, mu_h, raw_max = self._shard_stats(device, n, chunks, one_chunk=keep32 is not None)
-            s_stride, s_rows, sample = self._new_sample(device, n)
-            p16 = torch.empty(n, d, dtype=torch.float16, device=device)
-            # centre + cast: fp16 rows + max centred norm + bf16 sample + range flag in ONE pass per chunk (cldrd_index_center_cast)
-            flag = 0
-            if file16 is not None:
+            if not m.alloc_first:
+                (s_stride, s_rows, sample), dest = self._new_sample(device, n), m.new_rows(n, d, device)
+            if stored is not None:
+                cnorm, b1, flag, rows = stored.cnorm, stored.b1, 0, dest[m.rows_field]
                 for lo in range(0, n, ATTACH_CHUNK_ROWS):
-                    p16[lo:lo + ATTACH_CHUNK_ROWS].copy_(_host_tensor(np.ascontiguousarray(file16[0][lo:lo + ATTACH_CHUNK_ROWS])))
-                ops.gather_cast_rows(p16, sample, s_rows, s_stride)
+                    rows[lo:lo + ATTACH_CHUNK_ROWS].copy_(_host_tensor(np.ascontiguousarray(stored.rows[lo:lo + ATTACH_CHUNK_ROWS])))
+                m.upload_rest(stored, dest, sample, s_stride, s_rows)
             else:
-                flag_d, cmax = torch.zeros(1, **i32), torch.zeros(1, **i32)
+                flag_d, *maxima = (torch.zeros(1, dtype=torch.int32, device=device) for _ in range(1 + m.n_maxima))
                 for lo, c in chunks():
-                    ops.index_center_cast(c, mu, p16[lo:lo + c.shape[0]], sample, s_stride, s_rows, flag_d, row0=lo, cmax=cmax)
+                    m.convert(c, mu, dest, lo, sample, s_stride, s_rows, flag_d, maxima)
                 del c
-                cnorm, flag = math.sqrt(float(cmax.view(torch.float32).item())), int(flag_d.item())
-        # max |p - mu| for the bound, plus 2^-12 max|p|: the fp32 subtraction p - mu itself rounds (2^-24 |p| per element), which moves a
-        # centred score by up to |q| sqrt(d) 2^-24 max|p| < 2^-10 |q| (2^-12 max|p|) - folded into the norm the eps formula multiplies by 2^-10
-        # (fp16-row mode: the scan's operand IS the stored row, so that term is slack there; the bound is kept as it is)
-        max_norm = cnorm * (1.0 + 1e-6) + raw_max * 2.0 ** -12
-        if flag or not math.isfinite(max_norm):
-            raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
-        # queries per pass over the index bytes: 256 at d = 768 (the streaming scan's two-batch form), else the reference's 128
-        # (`query_tile_request`: a test hook that asks for 128 at d = 768)
-        self._res = _Resident(device=device, p16=p16, p32=keep32, mu=mu, sample=sample, s_stride=s_stride, s_rows=s_rows, cnorm=cnorm,
-                              raw_max=raw_max, max_norm=max_norm, query_tile=256 if (d == 768 and self.query_tile_request != 128) else 128,
-                              mu_host=mu_h)
+                cnorm, b1 = m.norms([float(t.view(torch.float32).item()) for t in maxima])
+                flag = int(flag_d.item())
+        if flag or not (math.isfinite(raw_max) and math.isfinite(b1) and math.isfinite(cnorm)):
+            raise ValueError(m.not_finite)
+        self._res = _Resident(device=device, mode=mode, n=n, mu=mu, sample=sample, s_stride=s_stride, s_rows=s_rows, cnorm=cnorm, raw_max=raw_max,
+                              max_norm=m.max_norm(cnorm, raw_max), query_tile=m.query_tile(d, self.query_tile_request), mu_host=mu_h,
+                              p32=keep32, b1=b1, **dest)
 
     # -- search -------------------------------------------------------------------------------------------------
     @staticmethod
@@ -640,6 +723,7 @@ class FlatIPIndex:
         """Search with device-resident fp32 queries [nq, d]; returns device tensors (D fp32 [nq, k], I int32 row positions
         [nq, k], -1 = missing) and the statistics dict.  ONE host synchronisation (the proof flags) when nothing is redone."""
         res = self._res
+        m = _MODES[res.mode]
         dev, QT = res.device, res.query_tile
         n, d = res.n, self.d
         nq = q32.shape[0]
@@ -649,20 +733,14 @@ class FlatIPIndex:
             raise ValueError(f"top_k = {k} is not supported on an index of {n} rows: the candidate lists hold {CAND_CAP} entries "
                              f"(top_k <= {CAND_CAP // 2}, or an index of at most {CAND_CAP} rows)")
         i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
-        # 0. queries: 16-bit copies, norms, range flag; fp16-row mode: <q, mu> in fp64, added by the re-score
+        # 0. queries: the bf16 copy and the mode's scan operand, norms, range flag; stored-row modes: <q, mu> in fp64, added by the re-score
         q32 = q32.contiguous()
         qb = torch.empty(nq, d, dtype=torch.bfloat16, device=dev)
         qnorm, flag = torch.empty(nq, **f32), torch.zeros(1, **i32)
-        if res.r8 is None:
-            qh = torch.empty(nq, d, dtype=torch.float16, device=dev)
-            ops.topk_prep_queries(q32, qh, qb, qnorm, flag)
-        else:
-            # int8-row mode: the scan's operand of the queries is the pair (digit planes h, l; their common scale sq)
-            qh = (torch.empty(2, nq, d, dtype=torch.int8, device=dev), torch.empty(nq, **f32))
-            ops.topk_prep_queries_i8(q32, qh[0], qb, qh[1], qnorm, flag)
-        qmu = ops.query_dot64(q32, res.mu) if res.p32 is None else None
+        qh = m.prep(q32, qb, qnorm, flag)
+        qmu = ops.query_dot64(q32, res.mu) if m.qmu else None
         # 1. thresholds
-        thr, eps = self._estimate_thresholds(qb, qnorm, kk, exhaustive, sq=None if res.r8 is None else qh[1])
+        thr, eps = self._estimate_thresholds(qb, qnorm, kk, exhaustive, sq=qh.sq)
         # 2. the first pass over every query
         stats = dict(scans=0, rescans=0, candidates=0, rescored=0, unproven_first_pass=0, exhaustive=bool(exhaustive))
         cap2 = CAND_CAP if exhaustive else self._cap2(kk)
@@ -678,11 +756,11 @@ class FlatIPIndex:
         probe = 0 if (exhaustive or nq <= 2 * QT or not self.probe) else QT
         if probe:
             head, tail = slice(0, probe), slice(probe, nq)
-            first = self._run(q32[head], _sel_scan(qh, head), thr[head], eps[head], _sel(qmu, head), k, cap2, D[head], I[head])
+            first = self._run(q32[head], qh.select(head), thr[head], eps[head], _sel(qmu, head), k, cap2, D[head], I[head])
             pr = torch.stack([first[0], first[2]]).cpu().numpy()
             cap2_rest = _cap2_after_probe(cap2, pr[0], pr[1])
             stats["cap2"] = [cap2, cap2_rest]
-            rest = self._run(q32[tail], _sel_scan(qh, tail), thr[tail], eps[tail], _sel(qmu, tail), k, cap2_rest, D[tail], I[tail])
+            rest = self._run(q32[tail], qh.select(tail), thr[tail], eps[tail], _sel(qmu, tail), k, cap2_rest, D[tail], I[tail])
             st, counts, n2, khat = (torch.cat(pair) for pair in zip(first, rest))
             cap2 = cap2_rest
         else:
@@ -692,11 +770,8 @@ class FlatIPIndex:
         # 3. the proof flags
         status = st.cpu().numpy()                       # the synchronisation of a search (plus the probe's)
         if int(flag.item()):
-            raise ValueError("queries must be finite" + (" and inside the fp16 range (|x| <= 65504)" if res.r8 is None else ""))
-        # int8-row mode: the scan has no on-chip hit list, a hit is lost only to a full candidate list - bit 2 of THAT query; the dropped-hit
-        # counter (bit 4) marks every query of its pass and carries nothing more
-        keep_bits = ~0 if res.r8 is None else ~4
-        status = status & keep_bits
+            raise ValueError(m.bad_queries)
+        status = status & m.status_mask
         nb = (nq + QT - 1) // QT
         stats["scans"] = 0 if exhaustive else nb
         stats["query_tile"] = QT
@@ -732,9 +807,9 @@ class FlatIPIndex:
             t_b, tiled, full = _retry_step(status[bad], thr_h[bad], eps_h[bad], khat.cpu().numpy().astype(np.float64)[bad], attempt)
             cap2_b = CAND_CAP if full else cap2
             Db, Ib = torch.empty(bad.size, k, **f32), torch.empty(bad.size, k, **i32)
-            st2, _, _, khat2 = self._run(q32.index_select(0, idx), _sel_scan(qh, idx), torch.from_numpy(t_b.astype(np.float32)).to(dev),
+            st2, _, _, khat2 = self._run(q32.index_select(0, idx), qh.select(idx), torch.from_numpy(t_b.astype(np.float32)).to(dev),
                                          eps.index_select(0, idx), _sel(qmu, idx), k, cap2_b, Db, Ib, tiled=tiled)
-            status_b = st2.cpu().numpy() & keep_bits
+            status_b = st2.cpu().numpy() & m.status_mask
             good = status_b == 0
             if good.any():
                 gi = torch.from_numpy(bad[good]).to(dev)
@@ -762,13 +837,9 @@ class FlatIPIndex:
         f32 = dict(dtype=torch.float32, device=res.device)
         thr, eps = torch.full((nq,), -float("inf"), **f32), torch.empty(nq, **f32)
 
-        def bound(est, thr_out):
-            if res.r8 is None:
-                ops.topk_thresholds(est, qnorm, res.max_norm, self.d, thr_out, eps)
-            else:
-                ops.topk_thresholds_i8(est, sq, qnorm, res.b1, res.max_norm, self.d, thr_out, eps)
+        bound = _MODES[res.mode].bound
         if exhaustive:
-            bound(None, None)
+            bound(res, self.d, None, sq, qnorm, None, eps)
             return thr, eps
         # lam = expected number of sample rows inside the global top-kk; +4.5 sigma makes a too-high estimate (-> that query is searched
         # again) a ~1e-5 event per query
@@ -781,7 +852,7 @@ class FlatIPIndex:
             m = min(EST_CHUNK, nq - lo)
             ops.gemm_nt(qb[lo:lo + m], res.sample, samp[:m], m)
             ops.topk_kth_largest(samp[:m], S, kth, est[lo:lo + m])
-        bound(est, thr)
+        bound(res, self.d, est, sq, qnorm, thr, eps)
         return thr, eps
 
     def _search_exhaustive_chunks(self, q32: torch.Tensor, k: int):
@@ -791,7 +862,7 @@ class FlatIPIndex:
         fp16-row / int8-row mode: the same over slices of the stored rows (scores as the class docstring defines them)."""
         res = self._res
         n, nq = res.n, q32.shape[0]
-        qmu = ops.query_dot64(q32.contiguous(), res.mu) if res.p32 is None else None
+        qmu = ops.query_dot64(q32.contiguous(), res.mu) if _MODES[res.mode].qmu else None
         if 2 * k > CAND_CAP:
             raise ValueError(f"exact fallback: top_k = {k} > {CAND_CAP // 2}")
         i32, f32 = dict(dtype=torch.int32, device=res.device), dict(dtype=torch.float32, device=res.device)
@@ -811,8 +882,8 @@ class FlatIPIndex:
         return D, I
 
     def _run(self, q32, qh, thr, eps, qmu, k, cap2, D, I, exhaustive=False, tiled=False, rows=slice(None)):
-        """One ``cldrd_flatip_search`` over the queries given and the rows ``rows`` of the shard, kept sets in buffers of ``cap2`` slots ->
-        (status, counts, n2, khat) on the device.  The per-batch scratch is reused by every batch of every search (same stream: no hazard)."""
+        """One chained search in the shard's row mode over the queries given and the rows ``rows`` of the shard, kept sets in buffers of ``cap2``
+        slots -> (status, counts, n2, khat) on the device.  The per-batch scratch is reused by every batch of every search (same stream: no hazard)."""
         res = self._res
         dev, QT, nq = res.device, res.query_tile, q32.shape[0]
         if cap2 not in res.ws:
@@ -825,14 +896,8 @@ class FlatIPIndex:
         n2 = torch.empty(nq, dtype=torch.int32, device=dev)
         status = torch.empty(nq, dtype=torch.int32, device=dev)
         khat = torch.empty(nq, dtype=torch.float32, device=dev)
-        if res.r8 is not None:
-            qd, sq = qh if qh is not None else (None, None)
-            ops.flatip_search_i8(q32, qd, sq, thr, eps, res.r8[rows], res.scale[rows], qmu, k, counts, ws["cand_rows"], ws["cand_scores"],
-                                 ws["rows2"], ws["scores2"], n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT)
-            return status, counts, n2, khat
-        ops.flatip_search(q32, qh, thr, eps, res.p16[rows], k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"],
-                          n2, status, khat, D, I, exhaustive=exhaustive, qtile=QT, tiled=tiled,
-                          P32=None if res.p32 is None else res.p32[rows], qmu=qmu)
+        bufs = (k, counts, ws["cand_rows"], ws["cand_scores"], ws["rows2"], ws["scores2"], n2, status, khat, D, I)
+        _MODES[res.mode].chain(res, rows, q32, qh or _ScanQueries(), thr, eps, qmu, bufs, exhaustive, tiled)
         return status, counts, n2, khat
 
     # -- persistence (own format; faiss' binary layout is not reproduced) ----------------
@@ -845,19 +910,59 @@ class FlatIPIndex:
         ``mu``, ``bound_l1`` (max a_r |R8[r]|_1), ``max_centred_norm`` (max a_r |R8[r]|_2), ``raw_max_norm`` in the meta file; an index attached in
         int8-row mode writes what it searches with, a host index quantises with numpy in chunks (the class docstring's definition; the same
         last-bit caveat for ``mu``).  The flags exclude one another; a refused call writes nothing."""
-        if fp16 and int8:
-            raise ValueError("FlatIPIndex.write: fp16 and int8 exclude one another")
-        if int8:
-            return self._write8(path)
-        if self._file8 is not None or (self._res is not None and self._res.r8 is not None and self.embeddings is None):
+        mode = _requested_mode(fp16, int8, "FlatIPIndex.write")
+        res, stored = self._res, self._stored
+        if mode != "int8" and ((stored is not None and stored.mode == "int8") or (res is not None and res.mode == "int8" and self.embeddings is None)):
             raise ValueError("this index holds int8 rows only: write it with int8=True")
-        if fp16:
-            return self._write16(path)
-        if self.embeddings is None:
-            raise ValueError("this index holds fp16 rows only (read from an fp16-row file): write it with fp16=True")
-        np.save(path + ".emb.npy", self.embeddings)
+        if mode == "float32":
+            if self.embeddings is None:
+                raise ValueError("this index holds fp16 rows only (read from an fp16-row file): write it with fp16=True")
+            np.save(path + ".emb.npy", self.embeddings)
+            with open(path + ".meta.pkl", "wb") as fh:
+                pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F32}, fh)
+            return
+        m = _MODES[mode]
+        if mode == "float16" and res is not None and res.mode == "int8":
+            raise ValueError("this index is attached in int8-row mode: write it with int8=True (or detach it: the fp16 rows come from fp32 rows)")
+        # what an attached shard searches with (the fp32 form: its fp16 shadow), else the file's rows, else encoded straight into the rows file
+        encoded = False
+        if res is not None and (res.mode == mode or (mode, res.mode) == ("float16", "float32")):
+            st = _StoredRows(mode, getattr(res, m.rows_field).cpu().numpy(), None if res.scale is None else res.scale.cpu().numpy(),
+                             np.array(self.mu), res.cnorm, res.raw_max, res.b1)
+        elif stored is not None and stored.mode == mode:
+            st = stored
+        else:
+            st, encoded = self._encode_host(mode, path + m.rows_ext), True
+        if not encoded:
+            np.save(path + m.rows_ext, st.rows)
+        meta = {"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": m.file_format, "mu": st.mu}
+        if st.scale is not None:
+            np.save(path + ".scale.npy", st.scale)
+            meta["bound_l1"] = float(st.b1)
+        meta.update(max_centred_norm=float(st.cnorm), raw_max_norm=float(st.raw_max))
         with open(path + ".meta.pkl", "wb") as fh:
-            pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F32}, fh)
+            pickle.dump(meta, fh)
+
+    def _encode_host(self, mode: str, rows_path: str) -> _StoredRows:
+        """The host encoder of fp16-row / int8-row mode: the host's fp32 rows in chunks of ``HOST_CHUNK_ROWS`` -> the stored rows, written into
+        ``rows_path`` (a memory-mapped .npy) as they are made, and their statistics (the device's definitions in numpy)."""
+        m, emb = _MODES[mode], self.embeddings
+        if emb is None or emb.shape[0] == 0:
+            raise ValueError(m.no_host_rows)
+        n, d = emb.shape
+        m.host_check(d)
+        mu, raw_sq = _host_stats(emb, m.not_finite)
+        out = np.lib.format.open_memmap(rows_path, mode="w+", dtype=m.np_dtype, shape=(n, d))
+        scale, b1, c_sq = None, 0.0, 0.0
+        for lo in range(0, n, HOST_CHUNK_ROWS):
+            rows, a, l1, c2 = m.encode(emb[lo:lo + HOST_CHUNK_ROWS], mu)
+            out[lo:lo + rows.shape[0]] = rows
+            if a is not None:
+                scale = np.empty(n, dtype=np.float32) if scale is None else scale
+                scale[lo:lo + rows.shape[0]] = a
+            b1, c_sq = max(b1, l1), max(c_sq, c2)
+        out.flush()
+        return _StoredRows(mode, out, scale, mu, math.sqrt(float(np.float32(c_sq))), math.sqrt(float(np.float32(raw_sq))), float(b1))
 
     @staticmethod
     def quantize_rows_i8(rows32: np.ndarray, mu: np.ndarray):
@@ -866,7 +971,7 @@ class FlatIPIndex:
         correctly rounded and ``rint`` rounds half to even, as the device kernel does."""
         c = np.asarray(rows32, dtype=np.float32) - np.asarray(mu, dtype=np.float32)
         if not np.isfinite(c).all():
-            raise ValueError("FlatIPIndex: embeddings must be finite for the int8 rows")
+            raise ValueError(_NOT_FINITE8)
         a = (np.abs(c).max(axis=1) / np.float32(127.0)).astype(np.float32)
         live = a > 0
         t = np.zeros_like(c)
@@ -878,112 +983,25 @@ class FlatIPIndex:
         l2sq = ((a64 * a64) * (r64 * r64).sum(axis=1)).astype(np.float32)
         return r8, a, l1, l2sq
 
-    def _write8(self, path: str):
-        def meta(mu, b1, cnorm, raw):
-            with open(path + ".meta.pkl", "wb") as fh:
-                pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_I8, "mu": mu, "bound_l1": float(b1),
-                             "max_centred_norm": float(cnorm), "raw_max_norm": float(raw)}, fh)
-        res = self._res
-        if res is not None and res.r8 is not None:
-            np.save(path + ".emb8.npy", res.r8.cpu().numpy())
-            np.save(path + ".scale.npy", res.scale.cpu().numpy())
-            return meta(np.array(self.mu), res.b1, res.cnorm, res.raw_max)
-        if self._file8 is not None:
-            r8, a, mu, b1, cnorm, raw = self._file8
-            np.save(path + ".emb8.npy", r8)
-            np.save(path + ".scale.npy", a)
-            return meta(mu, b1, cnorm, raw)
-        emb = self.embeddings
-        if emb is None or emb.shape[0] == 0:
-            raise ValueError("FlatIPIndex.write: the index holds no fp32 rows to quantise")
-        n, d = emb.shape
-        if d % 64 or d > 2048:
-            raise ValueError(f"FlatIPIndex: int8-row mode supports an embedding width that is a multiple of 64 and at most 2048, got {d}")
-        colsum, raw_sq = np.zeros(d, dtype=np.float64), 0.0
-        for lo in range(0, n, HOST_CHUNK_ROWS):
-            c = np.asarray(emb[lo:lo + HOST_CHUNK_ROWS], dtype=np.float32)
-            colsum += c.sum(axis=0, dtype=np.float64)
-            raw_sq = max(raw_sq, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max()))
-        if not (math.isfinite(raw_sq) and np.isfinite(colsum).all()):
-            raise ValueError("FlatIPIndex: embeddings must be finite for the int8 rows")
-        mu = (colsum / float(n)).astype(np.float32)
-        out = np.lib.format.open_memmap(path + ".emb8.npy", mode="w+", dtype=np.int8, shape=(n, d))
-        scale = np.empty(n, dtype=np.float32)
-        b1, c_sq = np.float32(0.0), np.float32(0.0)
-        for lo in range(0, n, HOST_CHUNK_ROWS):
-            r8, a, l1, l2sq = self.quantize_rows_i8(emb[lo:lo + HOST_CHUNK_ROWS], mu)
-            out[lo:lo + r8.shape[0]], scale[lo:lo + r8.shape[0]] = r8, a
-            b1, c_sq = max(b1, l1.max()), max(c_sq, l2sq.max())
-        out.flush()
-        del out
-        np.save(path + ".scale.npy", scale)
-        meta(mu, b1, math.sqrt(float(c_sq)), math.sqrt(float(np.float32(raw_sq))))
-
-    def _write16(self, path: str):
-        if self._res is not None and self._res.p16 is None:
-            raise ValueError("this index is attached in int8-row mode: write it with int8=True (or detach it: the fp16 rows come from fp32 rows)")
-        if self._res is not None:
-            # attached (either mode): the device's centred fp16 rows and statistics
-            mu, cnorm, raw = np.array(self.mu), self._res.cnorm, self._res.raw_max
-            np.save(path + ".emb16.npy", self._res.p16.cpu().numpy())
-        elif self._file16 is not None:
-            r16, mu, cnorm, raw = self._file16
-            np.save(path + ".emb16.npy", r16)
-        else:
-            emb = self.embeddings
-            if emb is None or emb.shape[0] == 0:
-                raise ValueError("FlatIPIndex.write: the index holds no rows")
-            n, d = emb.shape
-            colsum, raw_sq = np.zeros(d, dtype=np.float64), 0.0
-            for lo in range(0, n, HOST_CHUNK_ROWS):
-                c = np.asarray(emb[lo:lo + HOST_CHUNK_ROWS], dtype=np.float32)
-                colsum += c.sum(axis=0, dtype=np.float64)
-                raw_sq = max(raw_sq, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max()))
-            if not (math.isfinite(raw_sq) and np.isfinite(colsum).all()):
-                raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
-            mu = (colsum / float(n)).astype(np.float32)
-            out = np.lib.format.open_memmap(path + ".emb16.npy", mode="w+", dtype=np.float16, shape=(n, d))
-            c_sq = 0.0
-            for lo in range(0, n, HOST_CHUNK_ROWS):
-                c = np.asarray(emb[lo:lo + HOST_CHUNK_ROWS], dtype=np.float32) - mu            # fp32 subtraction, as the device does it
-                if not (np.abs(c) <= 65504.0).all():
-                    del out
-                    raise ValueError("FlatIPIndex: embeddings must be finite and inside the fp16 range (|x| <= 65504) for the scan shadow")
-                out[lo:lo + c.shape[0]] = c.astype(np.float16)                                 # round to nearest even
-                c_sq = max(c_sq, float(np.einsum("ij,ij->i", c, c, dtype=np.float64).max()))
-            out.flush()
-            del out
-            cnorm, raw = math.sqrt(float(np.float32(c_sq))), math.sqrt(float(np.float32(raw_sq)))
-        with open(path + ".meta.pkl", "wb") as fh:
-            pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F16, "mu": mu,
-                         "max_centred_norm": float(cnorm), "raw_max_norm": float(raw)}, fh)
-
     @classmethod
     def read(cls, path: str) -> "FlatIPIndex":
         with open(path + ".meta.pkl", "rb") as fh:
             meta = pickle.load(fh)
         idx = cls(meta["d"])
-        if meta.get("format") == FORMAT_F16:
-            r16 = np.load(path + ".emb16.npy", mmap_mode="r")
-            if r16.dtype != np.float16 or r16.ndim != 2 or r16.shape[1] != idx.d:
-                raise ValueError(f"{path}.emb16.npy: expected float16 [n, {idx.d}]")
-            idx._file16 = (r16, np.ascontiguousarray(meta["mu"], dtype=np.float32), float(meta["max_centred_norm"]), float(meta["raw_max_norm"]))
-            idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
-            idx.ntotal = r16.shape[0]
-            return idx
-        if meta.get("format") == FORMAT_I8:
-            r8 = np.load(path + ".emb8.npy", mmap_mode="r")
-            a = np.load(path + ".scale.npy")
-            if r8.dtype != np.int8 or r8.ndim != 2 or r8.shape[1] != idx.d or a.dtype != np.float32 or a.shape != (r8.shape[0],):
-                raise ValueError(f"{path}.emb8.npy / .scale.npy: expected int8 [n, {idx.d}] and float32 [n]")
-            idx._file8 = (r8, a, np.ascontiguousarray(meta["mu"], dtype=np.float32), float(meta["bound_l1"]), float(meta["max_centred_norm"]),
-                          float(meta["raw_max_norm"]))
-            idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
-            idx.ntotal = r8.shape[0]
-            return idx
-        idx.embeddings = np.load(path + ".emb.npy", mmap_mode="r")
+        mode = _FILE_MODES.get(meta.get("format"))
+        if mode is None:
+            rows = idx.embeddings = np.load(path + ".emb.npy", mmap_mode="r")
+        else:
+            m = _MODES[mode]
+            rows = np.load(path + m.rows_ext, mmap_mode="r")
+            scale = np.load(path + ".scale.npy") if mode == "int8" else None
+            if rows.dtype != m.np_dtype or rows.ndim != 2 or rows.shape[1] != idx.d \
+                    or (scale is not None and (scale.dtype != np.float32 or scale.shape != (rows.shape[0],))):
+                raise ValueError(m.bad_file.format(path=path, d=idx.d))
+            idx._stored = _StoredRows(mode, rows, scale, np.ascontiguousarray(meta["mu"], dtype=np.float32), float(meta["max_centred_norm"]),
+                                      float(meta["raw_max_norm"]), float(meta.get("bound_l1", 0.0)))
         idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
-        idx.ntotal = idx.embeddings.shape[0]
+        idx.ntotal = rows.shape[0]
         return idx
 
 
@@ -994,16 +1012,13 @@ def write_index(index: FlatIPIndex, path: str, faiss_format: bool = False, fp16:
     layout).  The three flags exclude one another: a call with two of them raises and writes nothing."""
     if faiss_format and fp16:
         raise ValueError("write_index: the fp16-row format exists in this package's own layout only (faiss_format=True with fp16=True)")
-    if int8 and (faiss_format or fp16):
-        raise ValueError("write_index: int8=True excludes faiss_format=True and fp16=True (the int8-row format is this package's own)")
+    if int8 and faiss_format:
+        raise ValueError(_EXCLUSION["write_index"])
+    _requested_mode(fp16, int8, "write_index")
     if faiss_format:
         write_faiss_index(index, path)
-    elif int8:
-        index.write(path, int8=True)
-    elif fp16:
-        index.write(path, fp16=True)
     else:
-        index.write(path)
+        index.write(path, fp16=fp16, int8=int8)
 
 
 def read_index(path: str) -> FlatIPIndex:

@@ -125,7 +125,7 @@ def test_attention_entry_points_reject_inconsistent_layouts():
 
 
 def test_merged_entry_points_reject_inconsistent_arguments():
-    """The row-mode rule of the search (P32 / P16 / qmu), the token-type rule of the embedding forward, the gradient-stream rule of the two
+    """The row-mode rule of the search (P32 / P16 / qmu) and the int8 chain's own rules, the token-type rule of the embedding forward, the gradient-stream rule of the two
     LayerNorm backwards (enum cldrd_stream_fmt), the fp16 shadow range of the optimizer step and the row rule of the CLS scatter
     (include/cldrd_hip.h), without a GPU: as above, every call is rejected in front of any HIP call and none may pass the checks."""
     from cldrd_amd import _lib
@@ -135,6 +135,10 @@ def test_merged_entry_points_reject_inconsistent_arguments():
 
     def search(P16=P, P32=None, qmu=None):
         return "flatip_search", lib.cldrd_flatip_search(P, P, P, P, P16, P32, qmu, 1000, 128, 4, 10, 128, P, P, P, 1024, P, P, 1024, P, P, P, P, P, 0, None)
+
+    def search8(qd=P, sq=P, scale=P, d=128, qtile=128, exhaustive=0):
+        return "flatip_search_i8", lib.cldrd_flatip_search_i8(P, qd, sq, P, P, P, scale, P, 1000, d, 4, 10, qtile, P, P, P, 1024, P, P, 1024, P, P, P, P, P,
+                                                              exhaustive, None)
 
     def rescore(P16=P, P32=None, qmu=None):
         return "topk_rescore", lib.cldrd_topk_rescore(P, P32, P16, qmu, 128, P, P, P, 4, 1024, None)
@@ -159,6 +163,8 @@ def test_merged_entry_points_reject_inconsistent_arguments():
         lambda: search(), lambda: rescore(),                                            # neither P32 nor qmu
         lambda: search(P16=None, qmu=P), lambda: rescore(P16=None, qmu=P),              # fp16-row mode without the fp16 rows
         lambda: search(P16=None), lambda: rescore(P16=None),                            # no rows at all
+        lambda: search8(qtile=256), lambda: search8(exhaustive=2), lambda: search8(d=132),             # the int8 chain: its tile, no tiled form, its widths,
+        lambda: search8(qd=None), lambda: search8(scale=None),                                         # a scan without the query digits, no scales
         lambda: embed_fwd(table=None), lambda: embed_fwd(type_vocab=0), lambda: embed_fwd(type_vocab=-1),
         lambda: ln_bwd(x_f32=0, fmt=F32), lambda: ln_bwd(fmt=F32, dx_dropped=None), lambda: ln_bwd(x_f32=0, fmt=F16),
         lambda: ln_bwd(fmt=BF16, branch=P), lambda: ln_bwd(fmt=3), lambda: ln_bwd(fmt=-1),

@@ -179,11 +179,12 @@ def test_search_parity_cls_like_200k(cls200k):
         assert st["fallback_queries"] == 0, st
 
 
-@pytest.mark.parametrize("n,d", [(3000, 128), (500, 64), (RU.CAND_CAP, 768)])
-def test_search_parity_exhaustive_form(n, d):
+@pytest.mark.parametrize("n,d,nq", [(3000, 128, 6), (500, 64, 6), (RU.CAND_CAP, 768, 6), (3000, 128, 130)],
+                         ids=["3000-128", "500-64", f"{RU.CAND_CAP}-768", "3000-128-nq130"])          # 130 queries: two query tiles through the chain
+def test_search_parity_exhaustive_form(n, d, nq):
     emb = syn.corpus_embeddings(73, n, d)
     emb[n // 2] = emb[n // 3]
-    q = syn.corpus_embeddings(74, 6, d)
+    q = syn.corpus_embeddings(74, nq, d)
     ids = np.arange(n, dtype=np.int64) + 9
     index = attach16(emb, ids)
     mu = check_mu(index, emb)

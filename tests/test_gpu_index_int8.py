@@ -245,7 +245,7 @@ def _corpus(n, d, nq, seed):
 
 
 @pytest.mark.parametrize("nq,n,d,with_ids", [(37, 5003, 768, True), (16, 9000, 128, False), (129, 40000, 768, True), (257, 70001, 256, False),
-                                             (600, 40000, 768, False)])
+                                             (600, 40000, 768, False), (130, 3000, 128, False)])          # the last: exhaustive, two query tiles
 def test_search_equals_the_definition(nq, n, d, with_ids):
     emb, q = _corpus(n, d, nq, 300 + nq)
     ids = np.arange(n, dtype=np.int64) * 3 + 5 if with_ids else None

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Digest of what the flat index (retriever.retrieval_utils) computes, for comparing two commits bit for bit: for fixed seeds and a handful
-of cases that between them take every path of attach and search, one line per case with the SHA-256 of ``D`` and of ``I``, the ``last_stats``
-counts (without ``search_ms``) and the SHA-256 of the two files ``write_index(index, path, fp16=True)`` writes for the attached index (``mu``,
-the fp16 rows and both norms).  Only the public surface is used, so the same file runs on either commit; the outputs must be equal line for
+of cases that between them take every path of attach and search in the three row modes, one line per case with the SHA-256 of ``D`` and of
+``I``, the ``last_stats`` counts (without ``search_ms``) and the SHA-256 of every file ``write_index`` writes for the attached index in the compact
+format of its own ``row_dtype`` (int8 rows: ``int8=True`` - ``R8``, the scales, ``mu`` and the bound's norms; fp16 rows, and the fp16 shadow of an
+fp32-row index: ``fp16=True`` - ``mu``, the fp16 rows and both norms).  Only the public surface is used, so the same file runs on either commit; the outputs must be equal line for
 line.
 
     timeout -k 10 600 python tools/index_digest.py [--out FILE]
@@ -42,8 +43,11 @@ def clean(stats):
 
 def files(index, tmp) -> str:
     path = os.path.join(tmp, "digest.index")
-    RU.write_index(index, path, fp16=True)
-    return f"emb16 {file_sha(path + '.emb16.npy')} meta {file_sha(path + '.meta.pkl')}"
+    written = lambda: sorted(f for f in os.listdir(tmp) if f.startswith("digest.index."))
+    for f in written():                          # the previous case's files
+        os.remove(os.path.join(tmp, f))
+    RU.write_index(index, path, **({"int8": True} if index.row_dtype == "int8" else {"fp16": True}))
+    return " ".join(f"{f[len('digest.index.'):]} {file_sha(os.path.join(tmp, f))}" for f in written())
 
 
 def report(name, index, q, k, tmp):
@@ -74,6 +78,7 @@ def main():
         # 1. exhaustive
         emb, q = syn.corpus_embeddings(1, 3000, 128), syn.corpus_embeddings(2, 40, 128)
         report("1 exhaustive 3000x128 k10", RU.convert_index_to_gpu(host_index(emb), 0, False), q, 10, tmp)
+        report("13 exhaustive 3000x128 k10 int8-row", host_index(emb).to_gpu(0, int8_rows=True), q, 10, tmp)
         # 2. probe pass at QT = 128, with an id table, both modes; 8. the fp16-row file of the second one read back and attached
         emb, q = syn.corpus_embeddings(3, 20000, 128) + np.float32(0.2), syn.corpus_embeddings(4, 300, 128)
         ids = np.arange(20000, dtype=np.int64) * 3 + 5
@@ -83,6 +88,12 @@ def main():
         path = os.path.join(tmp, "case8.index")
         RU.write_index(index, path, fp16=True)
         report("8 fp16-row file read back and attached", RU.convert_index_to_gpu(RU.read_index(path), 0, False), q, 100, tmp)
+        # 10. the same in int8-row mode; 11. its int8-row file read back and attached
+        index = host_index(emb, ids).to_gpu(0, int8_rows=True)
+        report("10 probe 20000x128 nq300 k100 ids int8-row", index, q, 100, tmp)
+        path = os.path.join(tmp, "case11.index")
+        RU.write_index(index, path, int8=True)
+        report("11 int8-row file read back and attached", RU.convert_index_to_gpu(RU.read_index(path), 0, False), q, 100, tmp)
         # 3. several passes at QT = 256, with and without the probe pass
         emb, q = syn.corpus_embeddings(5, 60000, 768), syn.corpus_embeddings(6, 700, 768)
         for hooks in ({}, {"probe": False}):
@@ -101,10 +112,11 @@ def main():
             report("5 fallback 40000x128 9000 identical rows k1000 MAX_ATTEMPTS=3", index, q, 1000, tmp)
         finally:
             RU.MAX_ATTEMPTS = attempts
-        # 6. device rows, fp16-row mode, three chunks
+        # 6. device rows, fp16-row mode, three chunks; 12. the same rows in int8-row mode
         P, u = syn.cls_like_corpus(150000, 768, 91, DEV)
         q = syn.cls_like_queries(10, u, 92).cpu().numpy()
         report("6 from_device_rows 150000x768 fp16-row k100", RU.FlatIPIndex.from_device_rows(P, id_offset=11, fp16_rows=True), q, 100, tmp)
+        report("12 from_device_rows 150000x768 int8-row k100", RU.FlatIPIndex.from_device_rows(P, id_offset=11, int8_rows=True), q, 100, tmp)
         del P
         # 7. two shards on one device, both modes
         emb = syn.corpus_embeddings(83, 30001, 128) + np.float32(0.3) * (np.arange(30001, dtype=np.float32)[:, None] / 30001)
