@@ -6,6 +6,8 @@
 // host twice per call (ranknet.py:16,40); here one workgroup owns one row: ranks come from an in-LDS count
 // (stable: ties by index), the pair loop runs over LDS, loss and pair count are wave-reduced, and the
 // gradient is written directly (no autograd graph, no host sync).
+#include <atomic>
+
 #include "common.h"
 
 namespace {
@@ -231,30 +233,99 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(int kind, const floa
 // the gradient where its input is >= the bound, as torch.clamp does.
 enum { LL_NONE = 0, LL_NDCG1 = 1, LL_NDCG2 = 2, LL_LAMBDARANK = 3, LL_NDCG2PP = 4, LL_RANKNET = 5, LL_GTDIFF = 6, LL_GTDIFF_POW = 7 };
 
-__global__ __launch_bounds__(256) void lambda_loss_row_kernel(const float* __restrict__ y_pred, const float* __restrict__ y_true,
-                                                               float* __restrict__ grad, float* __restrict__ row_out, int N, int scheme,
-                                                               int k, float eps, float sigma, float mu, float pad, int log2_red,
-                                                               int gain_linear) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
+struct LambdaParams { int scheme, k; float eps, sigma, mu; int log2_red, gain_linear; };      // k: already min'ed against "no truncation"
+
+// LDS floats of one slate of N items: the labels (lambda_stage_labels) and the five arrays of lambda_row_body.
+__host__ __device__ constexpr size_t lambda_lds_floats(int N) { return (size_t)6 * N; }
+
+// lab[0..N) <- the slate's labels, -inf where the label equals the padding indicator (judged on the label as given); then, on the
+// labels that are not padding: flags bit 0: columns n_rel..N-1 become their mean (left-to-right fp32 sum, one division); bit 1: the
+// row's minimum is subtracted; `offset` is added last.  flags == 0 and offset == 0 leave the labels as given.  Ends with a barrier.
+__device__ __forceinline__ void lambda_stage_labels(const float* __restrict__ yt, float* lab, float* red, int N, float pad, int flags,
+                                                    int n_rel, float offset) {
+    const float NINF = NEG_INF_F();
+    for (int i = threadIdx.x; i < N; i += blockDim.x) lab[i] = yt[i] == pad ? NINF : yt[i];
+    __syncthreads();
+    if (flags & 1) {
+        if (threadIdx.x == 0) {
+            float s = 0.f;
+            int n = 0;
+            for (int i = n_rel; i < N; ++i)
+                if (lab[i] != NINF) { s += lab[i]; ++n; }
+            red[0] = n > 0 ? s / (float)n : 0.f;
+        }
+        __syncthreads();
+        const float m = red[0];
+        for (int i = n_rel + threadIdx.x; i < N; i += blockDim.x)
+            if (lab[i] != NINF) lab[i] = m;
+        __syncthreads();
+    }
+    if (flags & 2) {
+        float v = NINF;                                         // max of the negated labels = -(row minimum); padding never wins
+        for (int i = threadIdx.x; i < N; i += blockDim.x)
+            if (lab[i] != NINF) v = fmaxf(v, -lab[i]);
+        const float mn = -block_max(v, red);
+        for (int i = threadIdx.x; i < N; i += blockDim.x)
+            if (lab[i] != NINF) lab[i] -= mn;
+        __syncthreads();
+    }
+    if (offset != 0.f) {
+        for (int i = threadIdx.x; i < N; i += blockDim.x)
+            if (lab[i] != NINF) lab[i] += offset;
+        __syncthreads();
+    }
+}
+
+// Number of pairs lambda_row_body counts for this slate, without their terms (the 'mean' reduction of the term kernel divides by
+// the count of ALL rows, which every workgroup takes this way before it writes a gradient).  top: [N] ints of LDS scratch.
+__device__ __forceinline__ float lambda_row_pairs(const float* __restrict__ yp, const float* lab, int* top, float* red, int N,
+                                                  int scheme, int k) {
+    const float NINF = NEG_INF_F();
+    const int kk = k < N ? k : N;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        int in = lab[i] != NINF;
+        if (in && kk < N) {                                     // position of item i in the stable descending order of the predictions
+            const float si = yp[i];
+            int pos_s = 0;
+            for (int j = 0; j < N; ++j) {
+                const float sj = lab[j] == NINF ? NINF : yp[j];
+                pos_s += (sj > si) || (sj == si && j < i);
+            }
+            in = pos_s < kk;
+        }
+        top[i] = in;
+    }
+    __syncthreads();
+    float c = 0.f;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        if (!top[i]) continue;
+        for (int j = 0; j < N; ++j) c += (top[j] && (scheme == LL_NDCG1 || lab[i] > lab[j])) ? 1.f : 0.f;
+    }
+    return block_sum(c, red);                                   // whole numbers <= N^2 <= 2^24: exact in fp32, whatever the order
+}
+
+// One slate: yp its N predictions (global), lab its N labels (LDS, -inf = padding), sm 5 * N floats of LDS.  On return (all threads,
+// behind a barrier) gp[p] = d sum-of-terms / d prediction of the item at sorted position p, item[p] = that item's column, and
+// lsum / cnt = the slate's sum of terms / number of pairs in every thread.
+__device__ __forceinline__ void lambda_row_body(const float* __restrict__ yp, const float* lab, float* sm, float* red, int N,
+                                                const LambdaParams& P, float& lsum_out, float& cnt_out) {
     float* ps = sm;                  // [N] prediction at sorted position (padded: -inf)
     float* ts = ps + N;              // [N] label at sorted position (padded: -inf)
     float* G = ts + N;               // [N] gain at sorted position
     float* gp = G + N;               // [N] gradient at sorted position
     int* item = (int*)(gp + N);      // [N] original column at sorted position
-    __shared__ float red[4];
-    const int b = blockIdx.x;
-    const float* yp = y_pred + (size_t)b * N;
-    const float* yt = y_true + (size_t)b * N;
+    const int scheme = P.scheme, k = P.k, log2_red = P.log2_red, gain_linear = P.gain_linear;
+    const float eps = P.eps, sigma = P.sigma, mu = P.mu;
     const float NINF = NEG_INF_F();
     // ---- positions: stable descending order of the (masked) predictions; maxDCG from the descending labels
     float dcg = 0.f;
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
-        const bool padded = yt[i] == pad;
-        const float si = padded ? NINF : yp[i], ti = padded ? NINF : yt[i];
+        const bool padded = lab[i] == NINF;
+        const float si = padded ? NINF : yp[i], ti = lab[i];
         int pos_s = 0, pos_t = 0;
         for (int j = 0; j < N; ++j) {
-            const bool pj = yt[j] == pad;
-            const float sj = pj ? NINF : yp[j], tj = pj ? NINF : yt[j];
+            const float tj = lab[j];
+            const float sj = tj == NINF ? NINF : yp[j];
             pos_s += (sj > si) || (sj == si && j < i);
             pos_t += (tj > ti) || (tj == ti && j < i);
         }
@@ -326,10 +397,94 @@ __global__ __launch_bounds__(256) void lambda_loss_row_kernel(const float* __res
         gp[p] = g;
     }
     __syncthreads();
+    lsum_out = block_sum(lsum, red);
+    cnt_out = block_sum(cnt, red);
+}
+
+__global__ __launch_bounds__(256) void lambda_loss_row_kernel(const float* __restrict__ y_pred, const float* __restrict__ y_true,
+                                                               float* __restrict__ grad, float* __restrict__ row_out, int N,
+                                                               LambdaParams P, float pad) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    float* lab = sm;
+    lambda_stage_labels(y_true + (size_t)b * N, lab, red, N, pad, 0, N, 0.f);
+    float lsum, cnt;
+    lambda_row_body(y_pred + (size_t)b * N, lab, sm + N, red, N, P, lsum, cnt);
+    const float* gp = sm + 4 * N;
+    const int* item = (const int*)(sm + 5 * N);
     for (int p = threadIdx.x; p < N; p += blockDim.x) grad[(size_t)b * N + item[p]] = gp[p];
-    lsum = block_sum(lsum, red);
-    cnt = block_sum(cnt, red);
     if (threadIdx.x == 0) { row_out[2 * b] = lsum; row_out[2 * b + 1] = cnt; }
+}
+
+// Arrival counters of lambda_term_kernel launches: a launch takes the next slot in turn (cldrd_lambda_term), its last workgroup puts
+// the slot back to 0.  Zero at module load; LAMBDA_TICKETS launches of it may be in flight on one device at a time.
+enum { LAMBDA_TICKETS = 32 };
+__device__ unsigned int lambda_term_tickets[LAMBDA_TICKETS];
+
+// The term form of lambda_loss (cldrd_lambda_term): one workgroup per slate = the first Ns columns of a row of logits [B, Np].
+//   term = lambda_loss(logits[:, :Ns], labels'), labels' = the staged labels (lambda_stage_labels);
+//   grad[b, :Ns] (+)= alpha * d term / d logits, loss_out[0] (+)= alpha * term, *term_out = term.
+// Under the 'mean' reduction every gradient entry is divided by the pair count of ALL rows; each workgroup takes that count itself
+// (lambda_row_pairs over every row: compares only, cheap next to its own row's pair loop of exp / pow / log), so it writes its
+// final gradient in one pass and the accumulate form needs no second buffer.  The value is the one cross-row sum: thread 0 of every
+// workgroup publishes {sum of terms, pairs} to row_out (agent-scope release, then a ticket), the workgroup that draws the last ticket
+// adds the rows in ascending order (agent-scope acquire; loads that bypass its L1).  Fixed order, no float atomics: the same bits on
+// every launch, and the bits of lambda_loss_row_kernel + loss_finalize_kernel where the two forms compute the same thing.
+__global__ __launch_bounds__(256) void lambda_term_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
+                                                           float* __restrict__ grad, float* row_out, float* __restrict__ loss_out,
+                                                           float* __restrict__ term_out, int B, int Np, int Ns, LambdaParams P, float pad,
+                                                           int mean_reduction, int label_flags, int n_rel, float label_offset, float alpha,
+                                                           int accumulate, int slot) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const float QNAN = __int_as_float(0x7fc00000);
+    float* lab = sm;
+    float c = 0.f;
+    if (mean_reduction) {
+        for (int r = 0; r < B; ++r) {
+            lambda_stage_labels(labels + (size_t)r * Ns, lab, red, Ns, pad, label_flags, n_rel, label_offset);
+            c += lambda_row_pairs(logits + (size_t)r * Np, lab, (int*)(sm + Ns), red, Ns, P.scheme, P.k);
+            __syncthreads();                                    // lab / top are rewritten for the next row
+        }
+    }
+    const float inv = 1.0f / c;
+    lambda_stage_labels(labels + (size_t)b * Ns, lab, red, Ns, pad, label_flags, n_rel, label_offset);
+    float lsum, cnt;
+    lambda_row_body(logits + (size_t)b * Np, lab, sm + Ns, red, Ns, P, lsum, cnt);
+    const float* gp = sm + 4 * Ns;
+    const int* item = (const int*)(sm + 5 * Ns);
+    float* g = grad + (size_t)b * Np;
+    for (int p = threadIdx.x; p < Ns; p += blockDim.x) {
+        float v = gp[p];
+        if (mean_reduction) v = c > 0.f ? v * inv : QNAN;       // c == 0: the mean of an empty selection, as loss_finalize_kernel
+        if (!accumulate) g[item[p]] = alpha * v;
+        else if (alpha != 0.f) g[item[p]] += alpha * v;         // alpha == 0 leaves grad bit for bit (x + 0 would turn a -0 into +0)
+    }
+    if (!accumulate)
+        for (int j = Ns + threadIdx.x; j < Np; j += blockDim.x) g[j] = 0.f;
+    if (threadIdx.x != 0) return;
+    row_out[2 * b] = lsum;
+    row_out[2 * b + 1] = cnt;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned int* ticket = lambda_term_tickets + slot;
+    if (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned int)(B - 1)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    float l = 0.f, n = 0.f;
+    for (int r = 0; r < B; ++r) {
+        l += __hip_atomic_load(row_out + 2 * r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        n += __hip_atomic_load(row_out + 2 * r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    float term = l;
+    if (mean_reduction) term = n > 0.f ? l * (1.0f / n) : QNAN;
+    if (!accumulate) { loss_out[0] = alpha * term; loss_out[1] = n; }
+    else if (alpha != 0.f) loss_out[0] += alpha * term;
+    if (term_out) *term_out = term;
 }
 
 // Logit-norm regulariser of the multistep-curriculum trainers (reference nway_listwise_1.py:348-350):
@@ -482,11 +637,36 @@ extern "C" int cldrd_lambda_loss_fwd_bwd(const float* y_pred, const float* y_tru
                                          int mean_reduction, int log2_reduction, int gain_linear, void* stream) {
     CLDRD_CHECK(B > 0 && N > 0 && N <= 4096, "lambda_loss: need 0 < N <= 4096");
     CLDRD_CHECK(scheme >= 0 && scheme <= 7, "lambda_loss: unknown weighing scheme");
-    hipLaunchKernelGGL(lambda_loss_row_kernel, dim3(B), dim3(256), 5 * N * sizeof(float), (hipStream_t)stream, y_pred, y_true, grad,
-                       workspace, N, scheme, k > 0 ? k : N, eps, sigma, mu, pad_indicator, log2_reduction, gain_linear);
+    const LambdaParams P{scheme, k > 0 ? k : N, eps, sigma, mu, log2_reduction, gain_linear};
+    hipLaunchKernelGGL(lambda_loss_row_kernel, dim3(B), dim3(256), lambda_lds_floats(N) * sizeof(float), (hipStream_t)stream, y_pred, y_true,
+                       grad, workspace, N, P, pad_indicator);
     CLDRD_LAUNCH_CHECK();
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (int)LOSS_RANKNET, (const float*)workspace, grad,
                        loss_out, B, N, mean_reduction);
+    CLDRD_LAUNCH_CHECK();
+    return 0;
+}
+
+// The term form of cldrd_lambda_loss_fwd_bwd, one launch (include/cldrd_hip.h): the slate of row b is logits[b, :Ns], its labels
+// labels[b, :] after the label transform; accumulate 0 writes loss_out / grad (columns >= Ns: zero), 1 adds to them.
+extern "C" int cldrd_lambda_term(const float* logits, int B, int Np, const float* labels, int Ns, int label_flags, int n_rel,
+                                 float label_offset, int scheme, int k, float eps, float sigma, float mu, float pad_indicator,
+                                 int mean_reduction, int log2_reduction, int gain_linear, float alpha, int accumulate, float* loss_out,
+                                 float* grad, float* term_out, float* workspace, void* stream) {
+    CLDRD_CHECK(logits && labels && loss_out && grad && workspace, "lambda_term: null pointer");
+    CLDRD_CHECK(B > 0 && Ns >= 1 && Ns <= Np, "lambda_term: need B > 0 and 1 <= Ns <= Np");
+    CLDRD_CHECK(Ns <= 4096, "lambda_term: need Ns <= 4096");
+    CLDRD_CHECK(scheme >= 0 && scheme <= 7, "lambda_term: unknown weighing scheme");
+    CLDRD_CHECK(label_flags >= 0 && label_flags <= 3, "lambda_term: label_flags must be 0..3 (bit 0 mean, bit 1 row_min)");
+    CLDRD_CHECK(n_rel >= 0 && n_rel <= Ns, "lambda_term: need 0 <= n_rel <= Ns");
+    CLDRD_CHECK(alpha >= 0.f, "lambda_term: need alpha >= 0");
+    CLDRD_CHECK(accumulate == 0 || accumulate == 1, "lambda_term: accumulate must be 0 or 1");
+    static std::atomic<unsigned int> launches{0};
+    const int slot = (int)(launches.fetch_add(1u) % LAMBDA_TICKETS);
+    const LambdaParams P{scheme, k > 0 ? k : Ns, eps, sigma, mu, log2_reduction, gain_linear};
+    hipLaunchKernelGGL(lambda_term_kernel, dim3(B), dim3(256), lambda_lds_floats(Ns) * sizeof(float), (hipStream_t)stream, logits, labels,
+                       grad, workspace, loss_out, term_out, B, Np, Ns, P, pad_indicator, mean_reduction, label_flags, n_rel, label_offset,
+                       alpha, accumulate, slot);
     CLDRD_LAUNCH_CHECK();
     return 0;
 }

@@ -993,6 +993,44 @@ def distill_term(kind, logits, teacher, alpha, T, loss_out, grad, term_out=None)
          _p(grad), _p(term_out), _stream())
 
 
+LAMBDA_LABEL_FLAGS = {"mean": 1, "row_min": 2}          # label_flags bits of cldrd_lambda_term
+
+
+def lambda_term(logits, labels, loss_out, grad, term_out=None, *, alpha=1.0, accumulate=False, neg_mean=False, row_min=False, n_rel=None,
+                label_offset=0.0, eps=1e-4, padded_value_indicator=-1, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
+                reduction="mean", reduction_log="natural", gain="power"):
+    """The term form of lambda_loss (cldrd_lambda_term, one launch): term = lambda_loss(logits[:, :Ns], labels') with the loss parameters
+    of `lambda_loss_fwd_bwd`; labels [B, Ns], Ns <= Np.  labels': columns n_rel.. replaced by their mean (``neg_mean``), the row's minimum
+    subtracted (``row_min``), ``label_offset`` added, in this order, on the labels that are not padding.
+    accumulate=False: loss_out = {alpha * term, pairs}, grad[:, :Ns] = alpha * d term / d logits, grad[:, Ns:] = 0;
+    accumulate=True: loss_out[0] += alpha * term, grad[:, :Ns] += ...; columns >= Ns untouched.  term_out[0] = term."""
+    if weighing_scheme not in LAMBDA_SCHEMES:
+        raise KeyError(weighing_scheme)
+    if gain not in ("power", "linear"):
+        raise ValueError(f"{gain} not defined.")
+    if reduction_log not in ("natural", "binary"):
+        raise ValueError("Reduction logarithm base can be either natural or binary")
+    if reduction not in ("mean", "sum"):
+        raise ValueError("Reduction method can be either sum or mean")
+    _chk(logits, F32, "logits", 2), _chk(labels, F32, "labels", 2), _chk(loss_out, F32, "loss_out", 1), _chk(grad, F32, "grad", 2)
+    if not (logits.is_contiguous() and grad.is_contiguous() and labels.is_contiguous()) or grad.shape != logits.shape:
+        raise ValueError("lambda_term: logits, grad and labels must be contiguous, grad of the shape of logits")
+    B, Np = logits.shape
+    if labels.shape[0] != B or not 1 <= labels.shape[1] <= Np:
+        raise ValueError(f"lambda_term: labels must be [{B}, 1..{Np}], got {tuple(labels.shape)}")
+    if loss_out.numel() < 2:
+        raise ValueError("lambda_term: loss_out must hold 2 floats")
+    if term_out is not None:
+        _chk(term_out, F32, "term_out", 1)
+    Ns = labels.shape[1]
+    flags = (LAMBDA_LABEL_FLAGS["mean"] if neg_mean else 0) | (LAMBDA_LABEL_FLAGS["row_min"] if row_min else 0)
+    ws = torch.empty(2 * B, dtype=F32, device=logits.device)
+    call("cldrd_lambda_term", _p(logits), B, Np, _p(labels), Ns, flags, Ns if n_rel is None else int(n_rel), float(label_offset),
+         LAMBDA_SCHEMES[weighing_scheme], 0 if k is None else int(k), float(eps), float(sigma), float(mu), float(padded_value_indicator),
+         1 if reduction == "mean" else 0, 1 if reduction_log == "binary" else 0, 1 if gain == "linear" else 0, float(alpha),
+         1 if accumulate else 0, _p(loss_out), _p(grad), _p(term_out), _p(ws), _stream())
+
+
 def sqnorm_blocks() -> int:
     return _lib.load().cldrd_sqnorm_blocks()
 

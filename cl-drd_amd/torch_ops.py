@@ -10,6 +10,7 @@ formula where the reference differentiates through the call:
     cldrd::listwise_loss      losses/{kl_div,margin_mse,ranknet,lambda_rank,weighted_pointwise}.py     value + d loss / d y_pred in one launch
     cldrd::lambda_loss        losses/standard_lambda_rank.py:3-95
     cldrd::distill_term       alpha * {KLDiv(T), MarginMSE}(y_pred[:, :Nt], teacher scores): the term the fused trainer adds behind its rank loss
+    cldrd::lambda_term        alpha * lambda_loss(y_pred[:, :Ns], transformed labels): the fused trainer's --loss lambda_loss, in one launch
     cldrd::nway_score         models/nway_dual_encoder.py:30-47 (N-way / in-batch scoring), backward cldrd::nway_score_bwd
     cldrd::linear             torch.nn.Linear inside the HF encoder (bias / erf-GELU / residual epilogue), forward
     cldrd::layer_norm         HF LayerNorm (eps 1e-12), forward
@@ -119,6 +120,43 @@ def _distill_backward(ctx, g_out, g_grad):
 torch.library.register_autograd("cldrd::distill_term", _distill_backward, setup_context=_distill_setup)
 
 
+@torch.library.custom_op("cldrd::lambda_term", mutates_args=(), device_types="cuda")
+def lambda_term(y_pred: Tensor, labels: Tensor, alpha: float, label_flags: int, n_rel: int, label_offset: float, scheme: int, k: int,
+                eps: float, sigma: float, mu: float, pad: float, mean_reduction: bool, log2_reduction: bool,
+                gain_linear: bool) -> Tuple[Tensor, Tensor]:
+    """(out float[3] = {alpha * term, pairs, term}, d (alpha * term) / d y_pred [B, Np]) with term = lambda_loss of y_pred[:, :Ns] against
+    the transformed labels [B, Ns] (cldrd_lambda_term: label_flags bit 0 mean of the columns n_rel.., bit 1 row minimum subtracted, then
+    label_offset); the columns >= Ns of the gradient are zero.  scheme / k / ... as cldrd::lambda_loss."""
+    y = y_pred.detach().float().contiguous()
+    out = torch.empty(3, dtype=torch.float32, device=y.device)
+    grad = torch.empty_like(y)
+    ops.lambda_term(y, labels.detach().float().contiguous(), out[0:2], grad, out[2:3], alpha=alpha,
+                    neg_mean=bool(label_flags & ops.LAMBDA_LABEL_FLAGS["mean"]), row_min=bool(label_flags & ops.LAMBDA_LABEL_FLAGS["row_min"]),
+                    n_rel=n_rel, label_offset=label_offset, eps=eps, padded_value_indicator=pad, weighing_scheme=_SCHEMES[scheme],
+                    k=(k if k > 0 else None), sigma=sigma, mu=mu, reduction="mean" if mean_reduction else "sum",
+                    reduction_log="binary" if log2_reduction else "natural", gain="linear" if gain_linear else "power")
+    return out, grad
+
+
+@lambda_term.register_fake
+def _(y_pred, labels, alpha, label_flags, n_rel, label_offset, scheme, k, eps, sigma, mu, pad, mean_reduction, log2_reduction, gain_linear):
+    return y_pred.new_empty((3,), dtype=torch.float32), y_pred.new_empty(y_pred.shape, dtype=torch.float32)
+
+
+def _lambda_term_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.in_dtype, ctx.alpha = inputs[0].dtype, float(inputs[2])
+
+
+def _lambda_term_backward(ctx, g_out, g_grad):
+    (grad,) = ctx.saved_tensors          # d (alpha term): the unweighted term's gradient is 1 / alpha of it (alpha == 0: both are zero here)
+    coef = g_out[0] + (g_out[2] / ctx.alpha if ctx.alpha > 0.0 else 0.0)
+    return ((grad * coef).to(ctx.in_dtype),) + (None,) * 14
+
+
+torch.library.register_autograd("cldrd::lambda_term", _lambda_term_backward, setup_context=_lambda_term_setup)
+
+
 # ---------------------------------------------------------------------------------------------------------------- scoring
 def _score_cols(B: int, N: int, mode: int) -> int:
     return N if mode == 0 else (B * N if mode == 1 else 2 * N)
@@ -210,4 +248,4 @@ def _(qkv, mask, nseq, L, H):
     return qkv.new_empty((qkv.shape[0], H * 64))
 
 
-OPS = ("listwise_loss", "lambda_loss", "distill_term", "nway_score", "nway_score_bwd", "linear", "layer_norm", "self_attention")
+OPS = ("listwise_loss", "lambda_loss", "distill_term", "lambda_term", "nway_score", "nway_score_bwd", "linear", "layer_norm", "self_attention")

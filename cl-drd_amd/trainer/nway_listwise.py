@@ -22,6 +22,11 @@ Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
   * ``--distill_loss kl_div | margin_mse`` adds ``distill_alpha * kd(logits[:, :nway], batch["teacher_scores"])`` to that loss (one more
     launch on the loss stream, ``cldrd_distill_term``): the role of the knowledge-distillation trainers the reference's scripts name
     (``scripts/unity/kd_nway_listwise.sh``, ``logit_reg_nway_listwise.sh``) but never published;
+  * ``--loss lambda_loss`` trains on allRank's LambdaLoss (``losses/standard_lambda_rank.py:3-117``; ``--weighing_scheme`` and the
+    ``--lambda_*`` flags are its arguments) in the same place on the loss stream, one launch (``cldrd_lambda_term``); with
+    ``--label_source teacher`` its labels are ``batch["teacher_scores"]`` instead of the label-mode constants (``--neg_score_mode``,
+    ``--teacher_label_shift``): the role of the ``ndcg_nway_listwise*`` trainers the reference's scripts name but its tree lacks, so what
+    these two flags mean is defined here (README: nDCG training);
   * ``--dev_path / --dev_queries_path / --dev_qrels_path`` (the reference's flags): at every saved checkpoint rank 0 re-ranks the dev run with
     the student (``NwayTrainer.validate``: evaluation.DevPool + RerankingEvaluator) and writes ``dev_logs.log`` / ``dev_best.json``; the
     reference tokenises and encodes every (query, passage) pair of the run per validation, here each distinct text once;
@@ -44,11 +49,41 @@ from ..encoder import HD32_EVAL_ONLY, _env_flag
 from ..models.nway_dual_encoder import NwayDualEncoder, _lengths, score_mode
 from ..retriever.retrieval_utils import cap_host_threads
 
-LOSS_KINDS = ("lambda_mrr", "ranknet", "kl_div", "margin_mse")
+LOSS_KINDS = ("lambda_mrr", "ranknet", "kl_div", "margin_mse", "lambda_loss")
 DISTILL_KINDS = ("kl_div", "margin_mse")      # --distill_loss: the term on batch["teacher_scores"] added to the rank loss
+# --loss lambda_loss (allRank's LambdaLoss framework, reference losses/standard_lambda_rank.py:3-117; cldrd_lambda_term in the fused step).
+# The reference's launch scripts name ndcg trainers (--weighing_scheme, --neg_score_mode) that its tree does not contain: which labels the
+# loss sees (LABEL_SOURCES) and what the two teacher-label options do are THIS package's definition (README: nDCG training).
+WEIGHING_SCHEMES = tuple(k_ for k_ in ops.LAMBDA_SCHEMES if k_ is not None) + ("none",)       # --weighing_scheme; none: every pair weighs 1
+LABEL_SOURCES = ("rank", "teacher")           # --label_source: the label-mode constants | batch["teacher_scores"] as the labels
+NEG_SCORE_MODES = ("original", "mean")        # --neg_score_mode: the teacher's score of every negative | their mean for all of them
+LABEL_SHIFTS = ("none", "row_min")            # --teacher_label_shift: row_min subtracts the row's lowest score (lambda_loss clamps labels at 0)
+# the options that mean something under --loss lambda_loss only, with the reference function's defaults (lambda_k 0: no truncation)
+LAMBDA_DEFAULTS = {"weighing_scheme": "none", "lambda_k": 0, "lambda_sigma": 1.0, "lambda_mu": 10.0, "lambda_gain": "power",
+                   "lambda_log": "natural"}
+TEACHER_LABEL_DEFAULTS = {"neg_score_mode": "original", "teacher_label_shift": "none"}
 RESUME_VERSION = 1                            # of the checkpoint's "resume_state" (NwayTrainer.resume_state, train())
 # what the data position of a checkpoint depends on: an exact resume under another value of any of them is refused (check_resume_position)
 POSITION_FIELDS = ("train_batch_size", "nranks", "seed", "dataset_len", "steps_per_epoch", "num_train_epochs")
+
+
+def check_loss_options(loss, label_source="rank", in_batch_loss=False, label_mode=None, synthetic=False, given=()):
+    """The combinations of --loss / --label_source / the lambda flags that mean nothing: a ``ValueError`` that names the flag.  ``given``:
+    the names of LAMBDA_DEFAULTS / TEACHER_LABEL_DEFAULTS set by the caller (None = not set, on the command line and in NwayTrainer)."""
+    if label_source not in LABEL_SOURCES:
+        raise ValueError(f"--label_source must be one of {LABEL_SOURCES}")
+    for name in given:
+        if name in LAMBDA_DEFAULTS and loss != "lambda_loss":
+            raise ValueError(f"--{name} is an option of --loss lambda_loss; it was given with --loss {loss}")
+        if name in TEACHER_LABEL_DEFAULTS and label_source != "teacher":
+            raise ValueError(f"--{name} is an option of --label_source teacher; it was given with --label_source {label_source}")
+    if label_source == "teacher":
+        if loss != "lambda_loss":
+            raise ValueError(f"--label_source teacher needs --loss lambda_loss (the other rank losses read the label-mode constants); got --loss {loss}")
+        if in_batch_loss:
+            raise ValueError("--label_source teacher cannot go with --in_batch_loss: the in-batch columns have no teacher score")
+        if label_mode == "1" and not synthetic:
+            raise ValueError("--label_source teacher needs a relT / most-hard / semi-hard training file with scores; --label_mode 1 files have none")
 
 
 def no_decay(name: str) -> bool:
@@ -237,9 +272,31 @@ class NwayTrainer:
                  weight_decay: float = 0.01, adam_epsilon: float = 1e-8, max_grad_norm: float = 1.0, warmup_steps: int = 4000,
                  total_steps: int = 100000, betas=(0.9, 0.999), bucket_layers: int = 1, reg_lambda: float = 0.0,
                  distill=None, distill_alpha: float = 1.0, distill_T: float = 1.0, distill_only: bool = False,
-                 deterministic: bool = False):
+                 deterministic: bool = False, weighing_scheme=None, lambda_k=None, lambda_sigma=None, lambda_mu=None, lambda_gain=None,
+                 lambda_log=None, label_source: str = "rank", neg_score_mode=None, teacher_label_shift=None, n_rel=None):
         if loss not in LOSS_KINDS:
             raise ValueError(f"loss must be one of {LOSS_KINDS}")
+        opts = dict(weighing_scheme=weighing_scheme, lambda_k=lambda_k, lambda_sigma=lambda_sigma, lambda_mu=lambda_mu, lambda_gain=lambda_gain,
+                    lambda_log=lambda_log, neg_score_mode=neg_score_mode, teacher_label_shift=teacher_label_shift)
+        check_loss_options(loss, label_source, getattr(model, "in_batch_loss", False), given=[k_ for k_, v_ in opts.items() if v_ is not None])
+        opts = {k_: ({**LAMBDA_DEFAULTS, **TEACHER_LABEL_DEFAULTS}[k_] if v_ is None else v_) for k_, v_ in opts.items()}
+        for name, allowed in (("weighing_scheme", WEIGHING_SCHEMES), ("lambda_gain", ("power", "linear")), ("lambda_log", ("natural", "binary")),
+                              ("neg_score_mode", NEG_SCORE_MODES), ("teacher_label_shift", LABEL_SHIFTS)):
+            if opts[name] not in allowed:
+                raise ValueError(f"--{name} must be one of {allowed}")
+        if int(opts["lambda_k"]) < 0 or not float(opts["lambda_sigma"]) > 0.0:
+            raise ValueError("--lambda_k must be >= 0 (0: no truncation) and --lambda_sigma > 0")
+        if opts["neg_score_mode"] == "mean" and n_rel is None:
+            raise ValueError("--neg_score_mode mean needs n_rel, the number of relT passages of the label mode")
+        # --loss lambda_loss: the keyword arguments of ops.lambda_term.  label_source "teacher": the slate is the row's own nway columns, its
+        # labels this step's teacher scores (transformed inside the kernel: they stay the one per-step input of a captured step), no padding
+        self.label_source = label_source
+        self._lambda_kw = dict(weighing_scheme=None if opts["weighing_scheme"] == "none" else opts["weighing_scheme"],
+                               k=int(opts["lambda_k"]) or None, sigma=float(opts["lambda_sigma"]), mu=float(opts["lambda_mu"]),
+                               gain=opts["lambda_gain"], reduction_log=opts["lambda_log"])
+        if label_source == "teacher":
+            self._lambda_kw.update(padded_value_indicator=float("-inf"), neg_mean=opts["neg_score_mode"] == "mean",
+                                   row_min=opts["teacher_label_shift"] == "row_min", n_rel=n_rel)
         if distill is not None and distill not in DISTILL_KINDS:
             raise ValueError(f"distill must be None or one of {DISTILL_KINDS}")
         if distill is not None and (not float(distill_alpha) >= 0.0 or not float(distill_T) > 0.0):
@@ -434,12 +491,17 @@ class NwayTrainer:
                 labels = torch.cat([labels, torch.full((bz, Np - nway), -0.5, dtype=torch.float32, device=logits.device)], dim=-1)
             if self.distill_only:
                 loss_out, dlogits = torch.zeros(2, dtype=torch.float32, device=logits.device), torch.zeros_like(logits)
+            elif self.loss_kind == "lambda_loss":
+                loss_out, dlogits = torch.empty(2, dtype=torch.float32, device=logits.device), torch.empty_like(logits)
+                if self.label_source == "teacher":
+                    labels = teacher.to(device=logits.device, dtype=torch.float32)
+                ops.lambda_term(logits, labels.contiguous(), loss_out, dlogits, **self._lambda_kw)
             else:
                 loss_out, dlogits = ops.loss_fwd_bwd(self.loss_kind, logits, labels.contiguous(), T=self.T)
             if self.reg_lambda > 0.0 and mode == 0:     # reference nway_listwise_1.py:346-350: only without in-batch negatives
                 self.last_reg = torch.empty(1, dtype=torch.float32, device=logits.device)
                 ops.logit_norm_reg(logits, self.reg_lambda, loss_out, dlogits, self.last_reg)
-            if teacher is not None:
+            if self.distill is not None:
                 # the row's own nway columns only: the in-batch columns behind them have no teacher score and keep the rank loss's gradient
                 self.last_kd = torch.empty(1, dtype=torch.float32, device=logits.device)
                 ops.distill_term(self.distill, logits, teacher.to(device=logits.device, dtype=torch.float32).contiguous(), self.distill_alpha,
@@ -460,13 +522,18 @@ class NwayTrainer:
             self._backward(q_tape, p_tape, dq, dp, main, side, lst, write_once)
         return loss_out, logits
 
+    def _reads_teacher_scores(self) -> bool:
+        return self.distill is not None or self.label_source == "teacher"
+
     def _teacher_scores(self, batch, bz, nway):
-        """batch["teacher_scores"] of a distilling trainer ([B, nway], checked); None for a trainer without ``distill`` (the key is ignored)."""
-        if self.distill is None:
+        """batch["teacher_scores"] of a trainer that distils or takes its labels from the teacher ([B, nway], checked); None for any other
+        trainer (the key is ignored)."""
+        if not self._reads_teacher_scores():
             return None
         t = batch.get("teacher_scores")
         if not isinstance(t, torch.Tensor):
-            raise ValueError(f"this trainer distils ({self.distill}) and needs batch['teacher_scores'] (float [B, nway]): build the training "
+            why = f"distils ({self.distill})" if self.distill is not None else "takes its labels from the teacher (label_source)"
+            raise ValueError(f"this trainer {why} and needs batch['teacher_scores'] (float [B, nway]): build the training "
                              "file with dataset.curriculum_file --with_scores and the dataset with teacher_scores=True")
         if tuple(t.shape) != (bz, nway):
             raise ValueError(f"batch['teacher_scores'] must be [{bz}, {nway}] like the passages, got {tuple(t.shape)}")
@@ -676,13 +743,13 @@ class NwayTrainer:
     def _step_inputs(self, batch):
         """The per-step inputs of the captured step: [(where it sits in the batch dict, tensor, dtype the static batch holds it in - None: its
         own)], in ONE order for the batch key, the static batch and every incoming one (at most 6 segments; cldrd_copy_segments takes 8).
-        The teacher scores are one of them: a distilling step reads this step's scores, like its labels."""
+        The teacher scores are one of them, once: a step that distils or takes its labels from the teacher reads this step's scores."""
         q, nw = batch["query"], batch["nway_passages"]
         items = [(("query", "input_ids"), q["input_ids"], None), (("nway_passages", "input_ids"), nw["input_ids"], None),
                  (("nway_passages", "attention_mask"), nw["attention_mask"], None), (("labels",), batch["labels"], torch.float32)]
         if q.get("attention_mask") is not None:
             items.append((("query", "attention_mask"), q["attention_mask"], None))
-        if self.distill is not None:
+        if self._reads_teacher_scores():
             bz, nway, _ = nw["input_ids"].shape
             items.append((("teacher_scores",), self._teacher_scores(batch, bz, nway), torch.float32))
         return items
@@ -801,6 +868,18 @@ class NwayTrainer:
         if len(keep) == 0:
             return 0.0, 0.0
         return float(np.sum(1.0 / (keep + 1.0)) / len(first)), float(len(keep) / len(first))
+
+    def metric_labels(self, batch, n_cols: int):
+        """The labels `train_metrics` ranks against, [B, n_cols] (in-batch columns: -0.5).  label_source "teacher": no label equals 1 there,
+        so the column with the highest teacher score of a row is its relevant one."""
+        if self.label_source == "teacher":
+            t = batch["teacher_scores"]
+            labels = torch.zeros(t.shape, dtype=torch.float32, device=t.device).scatter_(1, t.argmax(dim=1, keepdim=True), 1.0)
+        else:
+            labels = batch["labels"]
+        if n_cols != labels.shape[1]:
+            labels = torch.cat([labels, torch.full((labels.shape[0], n_cols - labels.shape[1]), -0.5, device=labels.device)], dim=-1)
+        return labels
 
     # ---- validation on a dev run (the reference's launch scripts pass --dev_path ...; its trainers import RerankingEvaluator) --
     def validate(self, pool, evaluator, batch_size: int = 512) -> dict:
@@ -1012,6 +1091,21 @@ def get_args(argv=None):
     ap.add_argument("--n_gpu", default=1, type=int)
     ap.add_argument("--local_rank", default=-1, type=int)
     ap.add_argument("--loss", default="lambda_mrr", choices=LOSS_KINDS)
+    ap.add_argument("--weighing_scheme", default=None, choices=WEIGHING_SCHEMES,
+                    help="--loss lambda_loss: the pair weights (reference losses/standard_lambda_rank.py:98-127; default none: every pair 1)")
+    ap.add_argument("--lambda_k", default=None, type=int, help="--loss lambda_loss: rank truncation k (default 0: none)")
+    ap.add_argument("--lambda_sigma", default=None, type=float, help="--loss lambda_loss: score-difference weight (default 1)")
+    ap.add_argument("--lambda_mu", default=None, type=float, help="--loss lambda_loss: mu of ndcgLoss2PP_scheme (default 10)")
+    ap.add_argument("--lambda_gain", default=None, choices=("power", "linear"), help="--loss lambda_loss: gain 2^label - 1 | label - 1 (default power)")
+    ap.add_argument("--lambda_log", default=None, choices=("natural", "binary"), help="--loss lambda_loss: logarithm of the loss (default natural)")
+    ap.add_argument("--label_source", default="rank", choices=LABEL_SOURCES,
+                    help="labels of --loss lambda_loss: the label-mode constants (rank) or the teacher scores of the training file "
+                         "(teacher; dataset.curriculum_file --with_scores)")
+    ap.add_argument("--neg_score_mode", default=None, choices=NEG_SCORE_MODES,
+                    help="--label_source teacher: every negative keeps its own teacher score (original, the default) or gets the mean over the negatives")
+    ap.add_argument("--teacher_label_shift", default=None, choices=LABEL_SHIFTS,
+                    help="--label_source teacher: row_min subtracts the row's lowest score first (scores <= 0, such as log-softmax outputs, would "
+                         "otherwise all clamp to label 0); default none")
     ap.add_argument("--distill_loss", default=None, choices=DISTILL_KINDS,
                     help="add distill_alpha * KLDiv(distill_T) / MarginMSE of the logits against the teacher scores of the training file "
                          "(dataset.curriculum_file --with_scores) to --loss")
@@ -1051,6 +1145,11 @@ def get_args(argv=None):
         ap.error("--distill_loss needs a relT / most-hard / semi-hard training file with scores; --label_mode 1 files have none")
     if args.distill_loss is not None and (not args.distill_alpha >= 0.0 or not args.distill_T > 0.0):
         ap.error("--distill_alpha must be >= 0 and --distill_T > 0")
+    defaults = {**LAMBDA_DEFAULTS, **TEACHER_LABEL_DEFAULTS}
+    check_loss_options(args.loss, args.label_source, args.in_batch_loss, args.label_mode, args.synthetic_steps > 0,
+                       given=[k_ for k_ in defaults if getattr(args, k_) is not None])           # a ValueError that names the flag
+    if args.lambda_k is not None and args.lambda_k < 0 or args.lambda_sigma is not None and not args.lambda_sigma > 0.0:
+        raise ValueError("--lambda_k must be >= 0 (0: no truncation) and --lambda_sigma > 0")
     args.run_folder = os.path.join(args.experiment_folder, args.run_folder)
     args.log_dir = os.path.join(args.run_folder, args.log_dir)
     args.model_save_dir = os.path.join(args.run_folder, args.model_save_dir)
@@ -1190,6 +1289,7 @@ def build_dataloader(args):
     """Label mode -> file constructor as reference :173-245; per-rank batch = train_batch_size // nranks, shuffle, drop_last."""
     from transformers import AutoTokenizer
     from ..dataset.nway_dataset import NwayDataset
+    check_loss_options(getattr(args, "loss", "lambda_mrr"), getattr(args, "label_source", "rank"), label_mode=args.label_mode)      # before anything is loaded
     tok = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path)
     a = (args.queries_path, args.collection_path, args.training_path, tok)
     kw = dict(max_query_len=args.query_max_len, max_passage_len=args.passage_max_len, label_mode=args.label_mode)
@@ -1198,7 +1298,7 @@ def build_dataloader(args):
     distill = getattr(args, "distill_loss", None) is not None
     if distill and mode == "1":
         raise ValueError("--distill_loss: label mode 1 files ({qid, rel_pid, neg_pids}) carry no teacher scores")
-    if distill:
+    if distill or getattr(args, "label_source", "rank") == "teacher":
         shard["teacher_scores"] = True
     if mode == "1":
         if args.distributed:
@@ -1256,7 +1356,7 @@ class _SyntheticBatches(torch.utils.data.Dataset):
         b = syn.nway_batch(a.seed + 1000 * a.rank + i, a.train_batch_size // a.nranks, a.synthetic_nway, a.query_max_len,
                            a.passage_max_len, vocab=getattr(a, "synthetic_vocab", syn.VOCAB), ragged=not getattr(a, "synthetic_fixed", False),
                            label_kind="teacher" if a.loss in ("kl_div", "margin_mse") else "mode9",
-                           with_teacher_scores=getattr(a, "distill_loss", None) is not None)
+                           with_teacher_scores=getattr(a, "distill_loss", None) is not None or getattr(a, "label_source", "rank") == "teacher")
         return attach_lengths(b)
 
 
@@ -1327,6 +1427,14 @@ def _dev_validation(args):
     return _DevValidation(args) if getattr(args, "dev_path", None) else None
 
 
+def _n_rel(args):
+    """The label mode's number of relT passages: where the negatives of a slate begin (--neg_score_mode mean).  Synthetic batches have
+    --synthetic_nway passages whatever the label mode."""
+    from ..dataset.nway_dataset import _REL
+    n = _REL.get(str(getattr(args, "label_mode", None)))
+    return min(n, args.synthetic_nway) if n is not None and args.synthetic_steps > 0 else n
+
+
 def train(args):
     """Epoch / step loop of reference :328-426 on top of NwayTrainer.train_step."""
     import random
@@ -1358,7 +1466,9 @@ def train(args):
                           adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm, warmup_steps=args.warmup_steps,
                           total_steps=t_total, reg_lambda=args.reg_lambda, distill=getattr(args, "distill_loss", None),
                           distill_alpha=getattr(args, "distill_alpha", 1.0), distill_T=getattr(args, "distill_T", 1.0),
-                          distill_only=getattr(args, "distill_only", False), deterministic=getattr(args, "deterministic", False))
+                          distill_only=getattr(args, "distill_only", False), deterministic=getattr(args, "deterministic", False),
+                          label_source=getattr(args, "label_source", "rank"), n_rel=_n_rel(args),
+                          **{k_: getattr(args, k_, None) for k_ in (*LAMBDA_DEFAULTS, *TEACHER_LABEL_DEFAULTS)})
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)            # after model / loader construction, as the reference does (:282)
@@ -1406,11 +1516,8 @@ def train(args):
             loss_out = trainer.train_step(batch)
             if main_rank and trainer.global_step % args.logging_steps == 0:
                 # the reference reads loss / MRR back every step (:369-389); here only on logging steps (no per-step sync)
-                labels = batch["labels"]
                 logits = trainer.last_logits
-                if logits.shape[1] != labels.shape[1]:
-                    labels = torch.cat([labels, torch.full((labels.shape[0], logits.shape[1] - labels.shape[1]), -0.5,
-                                                           device=labels.device)], dim=-1)
+                labels = trainer.metric_labels(batch, logits.shape[1])
                 b_mrr, b_rec = trainer.train_metrics(logits, labels, topk)
                 loss_val = float(loss_out[0].item())
                 loss_m.update(loss_val), mrr_m.update(b_mrr), rec_m.update(b_rec)

@@ -284,6 +284,25 @@ int cldrd_lambda_loss_fwd_bwd(const float* y_pred, const float* y_true, float* l
                               int scheme, int k, float eps, float sigma, float mu, float pad_indicator, int mean_reduction,
                               int log2_reduction, int gain_linear, void* stream);
 
+/* The term form of cldrd_lambda_loss_fwd_bwd, on the model of cldrd_distill_term: ONE launch, one workgroup per slate.
+ *   term = lambda_loss(logits[:, :Ns], labels') with scheme ... gain_linear as above (pad_indicator may be -inf: nothing is padding);
+ *   accumulate 0: loss_out[2] = {alpha * term, pairs}, grad[b, i] = alpha * d term / d logits[b, i] for i < Ns, 0 for Ns <= i < Np;
+ *   accumulate 1: loss_out[0] += alpha * term, grad[b, i] += ... for i < Ns; columns Ns..Np-1 are neither read nor written, and
+ *                 alpha == 0 leaves loss_out and grad bit for bit;
+ *   *term_out = term (unweighted; term_out may be null).
+ * logits and grad are [B, Np] (row stride Np), labels is [B, Ns], 1 <= Ns <= Np, Ns <= 4096, alpha >= 0.
+ * labels': padding is judged on the labels as given (label == pad_indicator); on the other labels of a row, in this order:
+ *   label_flags bit 0 (mean): columns n_rel..Ns-1 become their fp32 mean (left-to-right sum, one division; n_rel == Ns: nothing),
+ *   label_flags bit 1 (row_min): the row's minimum is subtracted (lambda_loss clamps labels at 0: log-softmax teacher scores, all
+ *   <= 0, would otherwise have no gain at all), then label_offset is added.  0 <= n_rel <= Ns.
+ * workspace: 2*B floats, as for cldrd_lambda_loss_fwd_bwd.  Deterministic: the cross-row sum has a fixed order (no float atomics);
+ * with accumulate 0, alpha 1, Ns == Np, label_flags 0 and label_offset 0 the outputs equal cldrd_lambda_loss_fwd_bwd's bit for bit.
+ * Up to 32 launches of this entry point may be in flight on one device at a time (each takes one of 32 arrival counters in turn). */
+int cldrd_lambda_term(const float* logits, int B, int Np, const float* labels, int Ns, int label_flags, int n_rel, float label_offset,
+                      int scheme, int k, float eps, float sigma, float mu, float pad_indicator, int mean_reduction, int log2_reduction,
+                      int gain_linear, float alpha, int accumulate, float* loss_out, float* grad, float* term_out, float* workspace,
+                      void* stream);
+
 /* ---- optimizer step (trainer/multistep-curriculum/nway_listwise_1.py:353-367) ------------------------------
  * One flat fp32 buffer for all parameters.  clip out: float[3] = {grad L2 norm, clip coefficient, non-finite flag}.
  * decay_flags: one byte per 64 parameters: bit 0 = weight decay applies, bit 1 = leave the 16-bit shadows of this chunk unwritten
