@@ -56,6 +56,9 @@ SIGNATURES = {
     "cldrd_scatter_cls_grad": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, vp]),
     "cldrd_score_fwd": (ci, [vp, vp, vp, ci, ci, ci, ci, vp]),
     "cldrd_score_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "cldrd_score_cos_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, vp]),
+    "cldrd_score_cos_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
+    "cldrd_l2_normalize_rows": (ci, [vp, csz, vp, csz, ci, cf, vp]),
     "cldrd_loss_fwd_bwd": (ci, [ci, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, ci, vp]),
     "cldrd_logit_norm_reg": (ci, [vp, ci, cf, vp, vp, vp, vp]),
     "cldrd_distill_term": (ci, [ci, vp, ci, ci, vp, ci, cf, cf, vp, vp, vp, vp]),

@@ -37,6 +37,8 @@ def get_args(argv=None):
     ap.add_argument("--passage_max_len", type=int, default=256)
     ap.add_argument("--token_cache_dir", default=None)
     ap.add_argument("--output_path", required=True)
+    ap.add_argument("--apply_consine_similarity", "--apply_cosine_similarity", dest="apply_consine_similarity", action="store_true", default=False,
+                    help="score by cosine similarity even if the checkpoint does not say so (a checkpoint written with the flag is read as one anyway)")
     return ap.parse_args(argv)
 
 
@@ -53,7 +55,7 @@ def checkpoints_in_step_order(folder):
 def main(args):
     from transformers import AutoTokenizer
     from ..models.nway_dual_encoder import NwayDualEncoder
-    from ..retriever.retrieval_utils import cap_host_threads
+    from ..retriever.retrieval_utils import cap_host_threads, set_score_mode
     from .dev_pool import DevPool
     from .reranking_evaluator import RerankingEvaluator, update_dev_best, write_dev_logs
     ckpts = checkpoints_in_step_order(args.resume_folder)
@@ -72,6 +74,7 @@ def main(args):
     for step, path in ckpts:
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         model.load_state_dict({(k[7:] if k.startswith("module.") else k): v for k, v in ckpt["state_dict"].items()})
+        set_score_mode(model, ckpt, getattr(args, "apply_consine_similarity", False))        # per checkpoint: each says how it scores
         t0 = time.perf_counter()
         metrics = evaluator.compute_metrics_pool(model, pool, batch_size=args.dev_batch_size)
         epoch = int(ckpt.get("epoch", 0))

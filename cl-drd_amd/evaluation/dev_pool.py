@@ -9,6 +9,7 @@ Scoring a model against the pool (:meth:`DevPool.score`): every distinct query t
 so
 
     score(q, p) = fp32 of the fp64-accumulated inner product of the two fp32 CLS embeddings
+                  (of a cosine model, ``model.cosine``: of the two unit vectors ``x / max(||x||, 1e-8)``, ``cldrd_l2_normalize_rows``)
 
 is the number ``FlatIPIndex.search`` returns for the same vectors, bit for bit: a student re-rank of the student's own retrieval run
 reproduces that run's scores.  There is one implementation of that sum in the package (``cldrd_topk_rescore``), on purpose.  The result is a
@@ -186,6 +187,11 @@ class DevPool:
         q_emb = self._encode(model, "q", batch_size, dev)
         lap("query_encode_s")
         p_emb = self._encode(model, "p", batch_size, dev)
+        if getattr(model, "cosine", False):
+            # a cosine model: the pool's rows become unit vectors where they lie (the kernel the index's rows went through), so the re-score
+            # below is the cosine - still the number FlatIPIndex.search returns for these vectors
+            ops.l2_normalize_rows(q_emb)
+            ops.l2_normalize_rows(p_emb)
         lap("passage_encode_s")
         scores = self.score_embeddings(q_emb, p_emb)
         lap("score_s")

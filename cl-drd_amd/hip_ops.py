@@ -913,6 +913,41 @@ def score_bwd(dlogits, q, p, dq, dp, B, N, mode=0):
     call("cldrd_score_bwd", _p(dlogits), _p(q), _p(p), _p(dq), _p(dp), B, N, q.shape[1], mode, _stream())
 
 
+COSINE_EPS = 1e-8        # of the cosine scorer and of every place that normalises embeddings (torch.nn.functional.cosine_similarity's eps)
+
+
+def score_cos_fwd(q, p, logits, inv_norms, B, N, mode=0, scale=1.0, eps=COSINE_EPS):
+    """logits = scale * cos(q, p) in the layout of score_fwd; inv_norms: float[B + B*N], written here and read by score_cos_bwd."""
+    _chk(q, F32, "q", 2), _chk(p, F32, "p", 2), _chk(logits, F32, "logits", 2), _chk(inv_norms, F32, "inv_norms", 1)
+    if inv_norms.numel() < B + B * N:
+        raise ValueError(f"inv_norms: need B + B*N = {B + B * N} floats, got {inv_norms.numel()}")
+    call("cldrd_score_cos_fwd", _p(q), _p(p), _p(logits), _p(inv_norms), B, N, q.shape[1], mode, float(scale), float(eps), _stream())
+    return logits
+
+
+def score_cos_bwd(dlogits, logits, q, p, inv_norms, dq, dp, B, N, mode=0, scale=1.0):
+    for t, n in ((dlogits, "dlogits"), (logits, "logits"), (q, "q"), (p, "p"), (dq, "dq"), (dp, "dp")):
+        _chk(t, F32, n, 2)
+    _chk(inv_norms, F32, "inv_norms", 1)
+    if inv_norms.numel() < B + B * N:
+        raise ValueError(f"inv_norms: need B + B*N = {B + B * N} floats, got {inv_norms.numel()}")
+    call("cldrd_score_cos_bwd", _p(dlogits), _p(logits), _p(q), _p(p), _p(inv_norms), _p(dq), _p(dp), B, N, q.shape[1], mode, float(scale),
+         _stream())
+
+
+def l2_normalize_rows(x, out=None, eps=COSINE_EPS):
+    """out[r] = x[r] / max(||x[r]||, eps) for the rows of x [n, d] (fp32; row stride >= d); out: dense [n, d], default x itself (in place,
+    which needs a dense x).  Returns out."""
+    _chk(x, F32, "x", 2)
+    out = x if out is None else _chk(out, F32, "out", 2)
+    if out.shape != x.shape or not out.is_contiguous():
+        raise ValueError("l2_normalize_rows: out must be a dense tensor of x's shape")
+    if x.shape[0] == 0:
+        return out
+    call("cldrd_l2_normalize_rows", _p(x), x.stride(0) if x.shape[0] > 1 else x.shape[1], _p(out), x.shape[0], x.shape[1], float(eps), _stream())
+    return out
+
+
 LOSS_KINDS = {"kl_div": 0, "margin_mse": 1, "ranknet": 2, "lambda_mrr": 3, "weighted_pointwise": 4}
 LAMBDA_SCHEMES = {None: 0, "ndcgLoss1_scheme": 1, "ndcgLoss2_scheme": 2, "lambdaRank_scheme": 3, "ndcgLoss2PP_scheme": 4, "rankNet_scheme": 5,
                   "rankNetWeightedByGTDiff_scheme": 6, "rankNetWeightedByGTDiffPowed_scheme": 7}

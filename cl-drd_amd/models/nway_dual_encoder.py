@@ -8,6 +8,8 @@ Same constructor, attributes (``query_encoder`` / ``passage_encoder``, aliased w
 """
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.nn as nn
 
@@ -33,8 +35,14 @@ def _lengths(mapping):
 
 
 class NwayDualEncoder(nn.Module):
-    def __init__(self, model_name_or_path, share_weights, in_batch_loss=False, all_in_batch_neg=True):
+    def __init__(self, model_name_or_path, share_weights, in_batch_loss=False, all_in_batch_neg=True, *, cosine=False, cosine_scale=1.0):
         super().__init__()
+        # cosine (ours; the reference's --apply_consine_similarity names it, its tree has no code for it): `forward` scores with
+        # cosine_scale * cosine similarity (torch_ops: cldrd::nway_score_cos).  The embeddings stay what they are - raw CLS rows; where they
+        # leave the model for an index or a validation they are normalised there (retrieval_utils, evaluation.DevPool).
+        if not (math.isfinite(float(cosine_scale)) and float(cosine_scale) > 0.0):
+            raise ValueError(f"cosine_scale must be finite and > 0, got {cosine_scale}")
+        self.cosine, self.cosine_scale = bool(cosine), float(cosine_scale)
         self.model_name_or_path = model_name_or_path
         self.share_weights = share_weights
         self.in_batch_loss = in_batch_loss
@@ -62,6 +70,8 @@ class NwayDualEncoder(nn.Module):
         assert query_reps.dim() == 2 and nway_passage_reps.dim() == 3
         bz, nway, D = nway_passage_reps.shape
         mode = score_mode(self.in_batch_loss, self.all_in_batch_neg)
+        if self.cosine:
+            return torch.ops.cldrd.nway_score_cos(query_reps, nway_passage_reps.reshape(bz * nway, D), bz, nway, mode, self.cosine_scale)
         return torch.ops.cldrd.nway_score(query_reps, nway_passage_reps.reshape(bz * nway, D), bz, nway, mode)
 
     def _embs_fp32(self, enc, ids, mask, lengths=None):

@@ -64,6 +64,8 @@ def get_args(argv=None):
     ap.add_argument("--student_run_path", default="", help="also write the student's run (what retrieve_top_passages writes)")
     ap.add_argument("--teacher_run_path", default="", help="also write the teacher-ranked run (what rerank_top_passages writes)")
     ap.add_argument("--use_int8", action="store_true", default=False, help="attach the index in int8-row mode (excludes --use_float16)")
+    ap.add_argument("--apply_consine_similarity", "--apply_cosine_similarity", dest="apply_consine_similarity", action="store_true", default=False,
+                    help="score by cosine similarity even if the checkpoint does not say so (a checkpoint written with the flag is read as one anyway)")
     from .score_store import add_arguments
     add_arguments(ap)
     args = ap.parse_args(argv)
@@ -115,7 +117,8 @@ def main(args):
     from ..models.nway_dual_encoder import NwayDualEncoder
     from .index_text import load_checkpoint_into
     from .rerank_top_passages import score_pairs, score_pairs_stored, write_ranked_run
-    from .retrieval_utils import cap_host_threads, convert_index_to_gpu, get_embeddings_from_scratch, read_index
+    from .retrieval_utils import (cap_host_threads, check_index_normalized, convert_index_to_gpu, get_embeddings_from_scratch, read_index,
+                                  set_score_mode)
     from .retrieve_top_passages import write_run_file
     from transformers import AutoTokenizer
 
@@ -138,8 +141,9 @@ def main(args):
 
     # 1. encode the queries and search, as retrieve_top_passages does; ids and scores stay in HBM
     model = NwayDualEncoder(args.model_name_or_path, share_weights=args.share_weights)
-    if args.resume:
-        load_checkpoint_into(model, args.resume)
+    ckpt = load_checkpoint_into(model, args.resume) if args.resume else None
+    check_index_normalized(index, set_score_mode(model, ckpt, getattr(args, "apply_consine_similarity", False)), args.index_path)
+    del ckpt
     model.cuda()
     lap("model_load_s")
     tokenizer = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path)

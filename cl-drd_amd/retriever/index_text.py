@@ -18,7 +18,7 @@ import torch
 
 from ..dataset import CachedSequenceDataset, SequenceDataset, SequenceTokenCache, SyntheticSequenceDataset
 from ..models.nway_dual_encoder import NwayDualEncoder
-from .retrieval_utils import ShardedFlatIPIndex, cap_host_threads, construct_flatindex_from_embeddings, get_embeddings_from_scratch, write_index
+from .retrieval_utils import ShardedFlatIPIndex, cap_host_threads, construct_flatindex_from_embeddings, get_embeddings_from_scratch, set_score_mode, write_index
 
 
 # flag name -> argparse keyword arguments: names and defaults of the reference's command line (index_text.py:30-41)
@@ -39,6 +39,7 @@ _FLAGS = {
     "index_fp16": dict(action="store_true", default=False),      # ours: write the fp16-row index format (mean row + centred fp16 rows: half the file)
     "index_int8": dict(action="store_true", default=False),      # ours: write the int8-row index format (mean row + int8 rows + one scale per row: a quarter of the file)
     "fp32_encode": dict(action="store_true", default=False),     # ours: encode with the exact fp32 evaluation pass (get_embeddings_from_scratch(use_fp16=False))
+    "apply_consine_similarity": dict(action="store_true", default=False),      # ours (the reference trainer's spelling): unit rows, see main()
     "bucket_window": dict(type=int, default=16384),       # ours (token-cache path): rows are batched by LENGTH inside windows of this many rows (0: 512 consecutive rows)
 }
 
@@ -46,7 +47,7 @@ _FLAGS = {
 def get_args(argv=None):
     ap = argparse.ArgumentParser(description="encode a collection with the passage tower and write the flat inner-product index")
     for name, kw in _FLAGS.items():
-        ap.add_argument("--" + name, **kw)
+        ap.add_argument("--" + name, *(["--apply_cosine_similarity"] if name == "apply_consine_similarity" else []), **kw)
     args = ap.parse_args(argv)
     if args.index_fp16 and args.index_int8:
         ap.error("--index_fp16 and --index_int8 exclude one another")
@@ -57,13 +58,15 @@ def get_args(argv=None):
 
 def load_checkpoint_into(model, path, is_parallel=True):
     """``checkpoint["state_dict"]`` of a trainer checkpoint into ``model``; DDP's ``module.`` prefix goes when ``is_parallel``
-    (reference index_text.py:63-73)."""
+    (reference index_text.py:63-73).  Returns the loaded checkpoint (retrieval_utils.set_score_mode reads its ``score`` key)."""
     # weights_only=False: a reference checkpoint carries its optimizer and a pickled LambdaLR scheduler next to the weights
     # (nway_listwise_1.py:418-426), which torch >= 2.6 refuses under the default weights_only=True
-    sd = torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    sd = ckpt["state_dict"]
     if is_parallel:
         sd = OrderedDict((k[len("module."):] if k.startswith("module.") else k, v) for k, v in sd.items())
     model.load_state_dict(sd)
+    return ckpt
 
 
 def collection_loader(path, tokenizer, max_length, is_query, token_cache_dir, rank, world, bucket_window=0):
@@ -98,9 +101,13 @@ def main(args):
         t_last[0] = now
     model = NwayDualEncoder(args.model_name_or_path, share_weights=args.share_weights)
     print("************************* share weights = {} *************************".format(args.share_weights))
+    ckpt = None
     if args.resume:
         print(f"load model from ==> {args.resume}")
-        load_checkpoint_into(model, args.resume, args.is_parallel)
+        ckpt = load_checkpoint_into(model, args.resume, args.is_parallel)
+    # a cosine model (the checkpoint's `score` key, or --apply_consine_similarity): the encode loop delivers unit rows and the index says so
+    cosine = set_score_mode(model, ckpt, getattr(args, "apply_consine_similarity", False))
+    del ckpt
     model.cuda()
     lap("model_load_s")
 
@@ -125,6 +132,7 @@ def main(args):
     text_id_to_idx = {tid: idx for idx, tid in enumerate(text_ids)}
     print("embs dtype: ", text_embs.dtype)
     index = construct_flatindex_from_embeddings(text_embs, np.array(text_ids))
+    index.normalized = cosine
     lap("index_build_s")
     stem = Path(args.resume).stem.split(".")[0] if args.resume else "random_init"
     index_path = os.path.join(args.index_dir, stem + (f".shard{rank}of{world}" if world > 1 else "") + ".index")

@@ -55,6 +55,8 @@ def get_args(argv=None):
                     help="student mode: re-score with the dual encoder --model_name_or_path [--resume CKPT] instead of a cross-encoder")
     ap.add_argument("--resume", default="", help="--dual_encoder: trainer checkpoint (checkpoint_<step>.pth.tar) loaded into the student")
     ap.add_argument("--share_weights", action="store_true", default=False)
+    ap.add_argument("--apply_consine_similarity", "--apply_cosine_similarity", dest="apply_consine_similarity", action="store_true", default=False,
+                    help="--dual_encoder: ""score by cosine similarity even if the checkpoint does not say so (a checkpoint written with the flag is read as one anyway)")
     ap.add_argument("--query_max_len", type=int, default=30)
     ap.add_argument("--passage_max_len", type=int, default=256)
     from .score_store import add_arguments
@@ -147,8 +149,8 @@ def main_dual_encoder(args):
     from transformers import AutoTokenizer
     tokenizer = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path or args.model_name_or_path)
     model = NwayDualEncoder(args.model_name_or_path, share_weights=args.share_weights)
-    if args.resume:
-        load_checkpoint_into(model, args.resume)
+    from .retrieval_utils import set_score_mode
+    set_score_mode(model, load_checkpoint_into(model, args.resume) if args.resume else None, getattr(args, "apply_consine_similarity", False))
     model.cuda()
     model.eval_fp32 = bool(args.fp32_encode)
     pool = DevPool(args.run_path, args.queries_path, args.collection_path, tokenizer, args.query_max_len, args.passage_max_len,

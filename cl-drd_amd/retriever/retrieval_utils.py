@@ -91,7 +91,33 @@ def batch_to_device(batch, target_device: torch.device):
     return batch
 
 
-def get_embeddings_from_scratch(model, dataloader, use_fp16, is_query, show_progress_bar=False):
+def cosine_of(checkpoint, flag: bool = False) -> bool:
+    """Whether a model built from ``checkpoint`` (the loaded dict of a trainer checkpoint, or None) scores by cosine similarity: it does if
+    the checkpoint's ``score`` key says so (written by a trainer run with --apply_consine_similarity) or if the program's own
+    --apply_consine_similarity (``flag``) is given - as an --index_fp16 file is searched in its mode with or without the flag."""
+    score = checkpoint.get("score") if isinstance(checkpoint, dict) else None
+    return bool(flag) or (isinstance(score, dict) and score.get("kind") == "cosine")
+
+
+def set_score_mode(model, checkpoint, flag: bool = False) -> bool:
+    """``model.cosine`` (and the checkpoint's ``cosine_scale``) from `cosine_of`: the one call of every program that builds a model from
+    ``--resume``.  -> model.cosine"""
+    model.cosine = cosine_of(checkpoint, flag)
+    score = checkpoint.get("score") if isinstance(checkpoint, dict) else None
+    if model.cosine and isinstance(score, dict) and "scale" in score:
+        model.cosine_scale = float(score["scale"])
+    return model.cosine
+
+
+def check_index_normalized(index, cosine: bool, index_path: str = ""):
+    """A cosine model searches unit rows: refuse an index without the ``normalized`` mark of index_text.  (An index of unit rows searched
+    with a dot-product model is an ordinary inner-product search and is not refused.)"""
+    if cosine and not getattr(index, "normalized", False):
+        raise ValueError(f"the model scores by cosine similarity, but the index {index_path} holds raw rows (its .meta.pkl has no "
+                         "'normalized' mark): rebuild it with index_text from the same checkpoint (or with --apply_consine_similarity)")
+
+
+def get_embeddings_from_scratch(model, dataloader, use_fp16, is_query, show_progress_bar=False, normalize=None):
     """Encode every batch of ``dataloader`` ({"seq": {input_ids, attention_mask}, "id": list[int]}) with the query or
     passage tower in eval mode -> (np.float32 [n, D], list[int]).
 
@@ -105,18 +131,22 @@ def get_embeddings_from_scratch(model, dataloader, use_fp16, is_query, show_prog
     from the cache / tokeniser), ``h2d_enqueue_s`` moving the batch and enqueuing the encode, ``d2h_wait_s`` waiting for the PREVIOUS
     batch's embeddings (the GPU's encode of it, as far as the host sees it: one batch of D2H stays in flight), ``gather_s`` collecting the
     rows.  When the loader knows its row count (``dataset.n_rows``: the token-cache and synthetic datasets) the [n, D] result is allocated
-    once and filled in place; the reference appends per-batch arrays and concatenates 27 GB at the end (:51)."""
+    once and filled in place; the reference appends per-batch arrays and concatenates 27 GB at the end (:51).
+
+    ``normalize`` (ours; None: ``getattr(model, "cosine", False)``): every row leaves as ``x / max(||x||, 1e-8)``, taken on the device
+    (``cldrd_l2_normalize_rows``) in front of the D2H copy: inner products of what is returned are cosines."""
+    normalize = bool(getattr(model, "cosine", False)) if normalize is None else bool(normalize)
     if use_fp16 or not hasattr(model, "eval_fp32"):
-        return _embeddings_from_scratch(model, dataloader, is_query)
+        return _embeddings_from_scratch(model, dataloader, is_query, normalize)
     before = model.eval_fp32
     model.eval_fp32 = True
     try:
-        return _embeddings_from_scratch(model, dataloader, is_query)
+        return _embeddings_from_scratch(model, dataloader, is_query, normalize)
     finally:
         model.eval_fp32 = before
 
 
-def _embeddings_from_scratch(model, dataloader, is_query):
+def _embeddings_from_scratch(model, dataloader, is_query, normalize=False):
     """The loop of :func:`get_embeddings_from_scratch` in whichever arithmetic mode the model is in."""
     import time
     tm = {"load_s": 0.0, "h2d_enqueue_s": 0.0, "d2h_wait_s": 0.0, "gather_s": 0.0, "batches": 0}
@@ -159,6 +189,8 @@ def _embeddings_from_scratch(model, dataloader, is_query):
         with torch.no_grad():
             batch = batch_to_device(batch, dev)
             reps = model.query_embs(batch["seq"]) if is_query else model.passage_embs(batch["seq"])
+            if normalize:
+                reps = ops.l2_normalize_rows(reps, torch.empty(reps.shape, dtype=torch.float32, device=reps.device))
             text_ids = batch["id"]
         # keep one batch in flight: the D2H copy of batch i overlaps the encode of batch i+1 (the reference syncs per batch, :47)
         host = torch.empty(reps.shape, dtype=torch.float32, pin_memory=True)
@@ -491,6 +523,7 @@ class FlatIPIndex:
         self.ids = None              # np.int64 [n] or None (ids = row positions + id_offset)
         self.id_offset = 0
         self._stored = None          # _StoredRows: an index read from an fp16-row or int8-row file (no fp32 rows anywhere)
+        self.normalized = False      # the rows are unit vectors (index_text with a cosine model): written to / read from the meta file
         self._res = None             # _Resident: the attached shard
         self.last_stats = {}
         self.profile = False          # bench.py: time the search with HIP events and count candidates
@@ -919,7 +952,7 @@ class FlatIPIndex:
                 raise ValueError("this index holds fp16 rows only (read from an fp16-row file): write it with fp16=True")
             np.save(path + ".emb.npy", self.embeddings)
             with open(path + ".meta.pkl", "wb") as fh:
-                pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F32}, fh)
+                pickle.dump({"d": self.d, "ids": self.ids, "id_offset": self.id_offset, "format": FORMAT_F32, **self._normalized_mark()}, fh)
             return
         m = _MODES[mode]
         if mode == "float16" and res is not None and res.mode == "int8":
@@ -939,9 +972,12 @@ class FlatIPIndex:
         if st.scale is not None:
             np.save(path + ".scale.npy", st.scale)
             meta["bound_l1"] = float(st.b1)
-        meta.update(max_centred_norm=float(st.cnorm), raw_max_norm=float(st.raw_max))
+        meta.update(max_centred_norm=float(st.cnorm), raw_max_norm=float(st.raw_max), **self._normalized_mark())
         with open(path + ".meta.pkl", "wb") as fh:
             pickle.dump(meta, fh)
+
+    def _normalized_mark(self) -> dict:
+        return {"normalized": True} if self.normalized else {}          # a raw-row index has exactly the keys it had
 
     def _encode_host(self, mode: str, rows_path: str) -> _StoredRows:
         """The host encoder of fp16-row / int8-row mode: the host's fp32 rows in chunks of ``HOST_CHUNK_ROWS`` -> the stored rows, written into
@@ -1001,6 +1037,7 @@ class FlatIPIndex:
             idx._stored = _StoredRows(mode, rows, scale, np.ascontiguousarray(meta["mu"], dtype=np.float32), float(meta["max_centred_norm"]),
                                       float(meta["raw_max_norm"]), float(meta.get("bound_l1", 0.0)))
         idx.ids, idx.id_offset = meta["ids"], meta.get("id_offset", 0)
+        idx.normalized = bool(meta.get("normalized", False))
         idx.ntotal = rows.shape[0]
         return idx
 

@@ -15,7 +15,8 @@ import torch
 from ..dataset import SequenceDataset, SyntheticSequenceDataset
 from ..models.nway_dual_encoder import NwayDualEncoder
 from .index_text import load_checkpoint_into
-from .retrieval_utils import ShardedFlatIPIndex, cap_host_threads, convert_index_to_gpu, get_embeddings_from_scratch, index_retrieve, read_index
+from .retrieval_utils import (ShardedFlatIPIndex, cap_host_threads, check_index_normalized, convert_index_to_gpu, get_embeddings_from_scratch,
+                              index_retrieve, read_index, set_score_mode)
 
 
 # names and defaults of the reference's command line (retrieve_top_passages.py:28-40) + ours
@@ -33,6 +34,7 @@ _FLAGS = {
     "synthetic_queries": dict(type=int, default=0),       # ours: N generated queries instead of --queries_path
     "fp32_encode": dict(action="store_true", default=False),     # ours: encode the queries with the exact fp32 evaluation pass (use_fp16=False)
     "use_float16": dict(action="store_true", default=False),      # ours: attach the index in fp16-row mode (convert_index_to_gpu(..., useFloat16=True))
+    "apply_consine_similarity": dict(action="store_true", default=False),     # ours (the reference trainer's spelling): a cosine model, see main()
     "use_int8": dict(action="store_true", default=False),         # ours: attach an fp32-format index in int8-row mode (FlatIPIndex.to_gpu(dev, int8_rows=True))
 }
 
@@ -40,7 +42,7 @@ _FLAGS = {
 def get_args(argv=None):
     ap = argparse.ArgumentParser(description="encode queries, search the flat index (top-k), write the run file")
     for name, kw in _FLAGS.items():
-        ap.add_argument("--" + name, **kw)
+        ap.add_argument("--" + name, *(["--apply_cosine_similarity"] if name == "apply_consine_similarity" else []), **kw)
     args = ap.parse_args(argv)
     if args.use_int8 and args.use_float16:
         ap.error("--use_int8 and --use_float16 exclude one another")
@@ -111,8 +113,15 @@ def main(args):
         t_last[0] = now
 
     model = NwayDualEncoder(args.model_name_or_path, share_weights=args.share_weights)
-    if args.resume:
-        load_checkpoint_into(model, args.resume, args.is_parallel)
+    ckpt = load_checkpoint_into(model, args.resume, args.is_parallel) if args.resume else None
+    cosine = set_score_mode(model, ckpt, getattr(args, "apply_consine_similarity", False))
+    del ckpt
+    path = args.index_path
+    if world > 1:
+        path = path.replace(".index", f".shard{rank}of{world}.index") if ".shard" not in path else path
+    if cosine:
+        # a cosine model's queries are unit vectors: the rows must be too.  Checked on the index's meta file before anything is encoded
+        check_index_normalized(read_index(path), True, path)         # (memory-mapped: no rows are read)
     model.cuda()
     lap("model_load_s")
     if args.synthetic_queries:
@@ -125,9 +134,6 @@ def main(args):
     query_embs, query_ids = get_embeddings_from_scratch(model, loader, use_fp16=not getattr(args, "fp32_encode", False), is_query=True, show_progress_bar=True)
     lap("encode_queries_s")
 
-    path = args.index_path
-    if world > 1:
-        path = path.replace(".index", f".shard{rank}of{world}.index") if ".shard" not in path else path
     index = read_index(path)
     lap("index_read_s")
     # --use_float16: only the centred fp16 rows of an fp32-format file become resident (a third of the bytes; scores from the stored fp16

@@ -12,6 +12,7 @@ formula where the reference differentiates through the call:
     cldrd::distill_term       alpha * {KLDiv(T), MarginMSE}(y_pred[:, :Nt], teacher scores): the term the fused trainer adds behind its rank loss
     cldrd::lambda_term        alpha * lambda_loss(y_pred[:, :Ns], transformed labels): the fused trainer's --loss lambda_loss, in one launch
     cldrd::nway_score         models/nway_dual_encoder.py:30-47 (N-way / in-batch scoring), backward cldrd::nway_score_bwd
+    cldrd::nway_score_cos     the same layout, logits = scale * cosine similarity (--apply_consine_similarity), backward cldrd::nway_score_cos_bwd
     cldrd::linear             torch.nn.Linear inside the HF encoder (bias / erf-GELU / residual epilogue), forward
     cldrd::layer_norm         HF LayerNorm (eps 1e-12), forward
     cldrd::self_attention     HF DistilBertSelfAttention / BertSelfAttention (head dim 64, L <= 256), forward
@@ -207,6 +208,55 @@ def _score_backward(ctx, dlogits):
 torch.library.register_autograd("cldrd::nway_score", _score_backward, setup_context=_score_setup)
 
 
+@torch.library.custom_op("cldrd::nway_score_cos", mutates_args=(), device_types="cuda")
+def nway_score_cos(q: Tensor, p: Tensor, B: int, N: int, mode: int, scale: float) -> Tensor:
+    """logits[B, N'] = scale * cosine similarity (eps 1e-8) in the layout of cldrd::nway_score (--apply_consine_similarity)."""
+    q, p = q.contiguous(), p.contiguous()
+    logits = torch.empty(B, _score_cols(B, N, mode), dtype=torch.float32, device=q.device)
+    ops.score_cos_fwd(q, p, logits, torch.empty(B + B * N, dtype=torch.float32, device=q.device), B, N, mode, scale)
+    return logits
+
+
+@nway_score_cos.register_fake
+def _(q, p, B, N, mode, scale):
+    return q.new_empty((B, _score_cols(B, N, mode)), dtype=torch.float32)
+
+
+@torch.library.custom_op("cldrd::nway_score_cos_bwd", mutates_args=(), device_types="cuda")
+def nway_score_cos_bwd(dlogits: Tensor, q: Tensor, p: Tensor, B: int, N: int, mode: int, scale: float) -> Tuple[Tensor, Tensor]:
+    # The inverse norms the backward kernel reads are no output of the forward op (it returns what cldrd::nway_score returns), so the two
+    # small forward launches run again here: every sum has one order, the logits and norms are the forward's bit for bit.  (The fused
+    # trainer calls the C pair directly and keeps them.)
+    q, p = q.contiguous(), p.contiguous()
+    logits = torch.empty(B, _score_cols(B, N, mode), dtype=torch.float32, device=q.device)
+    inv_norms = torch.empty(B + B * N, dtype=torch.float32, device=q.device)
+    ops.score_cos_fwd(q, p, logits, inv_norms, B, N, mode, scale)
+    dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)          # row-major whatever the strides of q / p (see nway_score_bwd)
+    dp = torch.empty(p.shape, dtype=p.dtype, device=p.device)
+    ops.score_cos_bwd(dlogits.contiguous().float(), logits, q, p, inv_norms, dq, dp, B, N, mode, scale)
+    return dq, dp
+
+
+@nway_score_cos_bwd.register_fake
+def _(dlogits, q, p, B, N, mode, scale):
+    return q.new_empty(q.shape), p.new_empty(p.shape)
+
+
+def _score_cos_setup(ctx, inputs, output):
+    q, p, B, N, mode, scale = inputs
+    ctx.save_for_backward(q, p)
+    ctx.dims = (B, N, mode, scale)
+
+
+def _score_cos_backward(ctx, dlogits):
+    q, p = ctx.saved_tensors
+    dq, dp = torch.ops.cldrd.nway_score_cos_bwd(dlogits, q, p, *ctx.dims)
+    return dq, dp, None, None, None, None
+
+
+torch.library.register_autograd("cldrd::nway_score_cos", _score_cos_backward, setup_context=_score_cos_setup)
+
+
 # ------------------------------------------------------------------------------------------- encoder building blocks (forward)
 @torch.library.custom_op("cldrd::linear", mutates_args=(), device_types="cuda")
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], residual: Optional[Tensor], gelu: bool, out_f32: bool) -> Tensor:
@@ -248,4 +298,4 @@ def _(qkv, mask, nseq, L, H):
     return qkv.new_empty((qkv.shape[0], H * 64))
 
 
-OPS = ("listwise_loss", "lambda_loss", "distill_term", "lambda_term", "nway_score", "nway_score_bwd", "linear", "layer_norm", "self_attention")
+OPS = ("listwise_loss", "lambda_loss", "distill_term", "lambda_term", "nway_score", "nway_score_bwd", "nway_score_cos", "nway_score_cos_bwd", "linear", "layer_norm", "self_attention")

@@ -27,6 +27,10 @@ Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
     ``--label_source teacher`` its labels are ``batch["teacher_scores"]`` instead of the label-mode constants (``--neg_score_mode``,
     ``--teacher_label_shift``): the role of the ``ndcg_nway_listwise*`` trainers the reference's scripts name but its tree lacks, so what
     these two flags mean is defined here (README: nDCG training);
+  * ``--apply_consine_similarity`` (the reference's spelling, ``scripts/unity/cosine_nway_listwise.sh``; its trainer is not in the tree)
+    scores with ``--cosine_scale`` times the cosine of the two CLS embeddings instead of their dot product (``cldrd_score_cos_fwd`` /
+    ``cldrd_score_cos_bwd`` in the place of the dot-product pair on the loss stream, one launch more); the checkpoint then carries a
+    ``score`` key, which index, retrieval and validation read (README: Cosine-similarity scoring);
   * ``--dev_path / --dev_queries_path / --dev_qrels_path`` (the reference's flags): at every saved checkpoint rank 0 re-ranks the dev run with
     the student (``NwayTrainer.validate``: evaluation.DevPool + RerankingEvaluator) and writes ``dev_logs.log`` / ``dev_best.json``; the
     reference tokenises and encodes every (query, passage) pair of the run per validation, here each distinct text once;
@@ -310,6 +314,9 @@ class NwayTrainer:
         self.distill, self.distill_alpha, self.distill_T, self.distill_only = distill, float(distill_alpha), float(distill_T), bool(distill_only)
         self.last_kd = None
         self.model = model
+        # the scorer is the model's (NwayDualEncoder(cosine=..., cosine_scale=...)): cosine_scale * cosine similarity instead of the dot product;
+        # everything behind the logits is the same
+        self.cosine, self.cosine_scale = bool(getattr(model, "cosine", False)), float(getattr(model, "cosine_scale", 1.0))
         self.loss_kind, self.T = loss, T
         self.reg_lambda = float(reg_lambda)
         self.last_reg = None
@@ -485,7 +492,11 @@ class NwayTrainer:
             lst.wait_stream(main)
         with torch.cuda.stream(lst):
             logits = torch.empty(bz, Np, dtype=torch.float32, device=q_cls.device)
-            ops.score_fwd(q_cls, p_cls, logits, bz, nway, mode)
+            if self.cosine:
+                inv_norms = torch.empty(bz + bz * nway, dtype=torch.float32, device=q_cls.device)
+                ops.score_cos_fwd(q_cls, p_cls, logits, inv_norms, bz, nway, mode, self.cosine_scale)
+            else:
+                ops.score_fwd(q_cls, p_cls, logits, bz, nway, mode)
             labels = batch["labels"].to(device=logits.device, dtype=torch.float32)
             if mode != 0:   # in-batch negatives get the -0.5 label (reference nway_listwise_1.py:341-344)
                 labels = torch.cat([labels, torch.full((bz, Np - nway), -0.5, dtype=torch.float32, device=logits.device)], dim=-1)
@@ -509,7 +520,10 @@ class NwayTrainer:
             if self.world > 1:
                 dlogits.mul_(1.0 / self.world)      # gradient mean over ranks == DDP's all-reduce / world_size
             dq, dp = torch.empty_like(q_cls), torch.empty_like(p_cls)
-            ops.score_bwd(dlogits, q_cls, p_cls, dq, dp, bz, nway, mode)
+            if self.cosine:
+                ops.score_cos_bwd(dlogits, logits, q_cls, p_cls, inv_norms, dq, dp, bz, nway, mode, self.cosine_scale)
+            else:
+                ops.score_bwd(dlogits, q_cls, p_cls, dq, dp, bz, nway, mode)
             if self.amp16:
                 ops.loss_scale_adapt(dq, dp, self._scale_state)          # dq, dp leave multiplied by S; every fp16 gradient downstream carries it
         if lst is not main:
@@ -964,7 +978,15 @@ class NwayTrainer:
 
     def _arithmetic(self):
         """What identifies the arithmetic of a step (``resume_state``): an exact resume under another mode would not be one."""
-        return {"amp": "fp16" if self.amp16 else "bf16", "share_weights": bool(self.model.share_weights), "n_towers": len(self.model.towers())}
+        a = {"amp": "fp16" if self.amp16 else "bf16", "share_weights": bool(self.model.share_weights), "n_towers": len(self.model.towers())}
+        if self.cosine:           # a dot-product trainer's resume_state has today's fields, no more
+            a["score"] = self.score_state()
+        return a
+
+    def score_state(self):
+        """The checkpoint's top-level ``score`` key of a cosine trainer (None for the dot product: no key): what the programs that build a model
+        from ``--resume`` read (retriever.retrieval_utils.cosine_of)."""
+        return {"kind": "cosine", "scale": self.cosine_scale, "eps": ops.COSINE_EPS} if self.cosine else None
 
     def resume_state(self):
         """What the reference's checkpoint keys do not carry and an exact resume needs (``load_state_dict(exact=True)``): plain CPU tensors and
@@ -982,7 +1004,7 @@ class NwayTrainer:
                              "package): load it with exact=False / without --resume_exact")
         if rs.get("version") != RESUME_VERSION:
             raise ValueError(f"exact resume: resume_state 'version' is {rs.get('version')!r}, this package reads version {RESUME_VERSION}")
-        for field, mine in self._arithmetic().items():
+        for field, mine in {"score": None, **self._arithmetic()}.items():        # 'score' is absent on both sides of a dot-product resume
             if rs.get(field) != mine:
                 raise ValueError(f"exact resume: '{field}' was {rs.get(field)!r} when the checkpoint was written and is {mine!r} in this trainer"
                                  + (" (CLDRD_AMP)" if field == "amp" else ""))
@@ -1008,7 +1030,7 @@ class NwayTrainer:
                 "scheduler": {"base_lrs": [self.lr0, self.lr0], "last_epoch": self.global_step, "_step_count": self.global_step + 1,
                               "_get_lr_called_within_step": False, "_last_lr": [self.lr(), self.lr()], "lr_lambdas": [None, None],
                               "warmup_steps": self.warmup_steps, "total_steps": self.total_steps},
-                "resume_state": self.resume_state()}
+                "resume_state": self.resume_state(), **({"score": self.score_state()} if self.cosine else {})}
 
     def load_state_dict(self, ckpt, exact=False):
         """``exact=False``: parameters, moments and the step counters, as the reference's ``--resume`` (``resume_state`` is ignored): the dropout
@@ -1112,6 +1134,10 @@ def get_args(argv=None):
     ap.add_argument("--distill_alpha", default=1.0, type=float, help="weight of the --distill_loss term")
     ap.add_argument("--distill_T", default=1.0, type=float, help="temperature of --distill_loss kl_div")
     ap.add_argument("--distill_only", action="store_true", default=False, help="drop the --loss term: total = distill_alpha * distill loss")
+    ap.add_argument("--apply_consine_similarity", "--apply_cosine_similarity", dest="apply_consine_similarity", action="store_true", default=False,
+                    help="score with cosine_scale * cosine similarity instead of the dot product (the reference's spelling, "
+                         "scripts/unity/cosine_nway_listwise.sh; README: Cosine-similarity scoring)")
+    ap.add_argument("--cosine_scale", default=None, type=float, help="--apply_consine_similarity: the factor on the cosine (default 1)")
     ap.add_argument("--deterministic", action="store_true", default=False,
                     help="bit-reproducible steps: embedding-table gradients as fixed-order per-row sums instead of float atomics (README: cost)")
     ap.add_argument("--token_cache_dir", default=None)
@@ -1139,6 +1165,10 @@ def get_args(argv=None):
         ap.error("--dev_path needs --collection_path for the passage texts; --synthetic_steps runs have no collection file")
     if args.dev_path is not None and (args.dev_batch_size < 1 or args.dev_top_k < 0):
         ap.error("--dev_batch_size must be >= 1 and --dev_top_k >= 0")
+    if args.cosine_scale is not None and not args.apply_consine_similarity:
+        ap.error("--cosine_scale is an option of --apply_consine_similarity; it was given without it")
+    if args.cosine_scale is not None and not (math.isfinite(args.cosine_scale) and args.cosine_scale > 0.0):
+        ap.error("--cosine_scale must be finite and > 0")
     if args.distill_loss is None and args.distill_only:
         ap.error("--distill_only needs --distill_loss")
     if args.distill_loss is not None and args.label_mode == "1" and args.synthetic_steps <= 0:
@@ -1435,6 +1465,14 @@ def _n_rel(args):
     return min(n, args.synthetic_nway) if n is not None and args.synthetic_steps > 0 else n
 
 
+def _cosine_kw(args):
+    """NwayDualEncoder's scorer keywords from --apply_consine_similarity / --cosine_scale (none of them without the flag)."""
+    if not getattr(args, "apply_consine_similarity", False):
+        return {}
+    scale = getattr(args, "cosine_scale", None)
+    return {"cosine": True, "cosine_scale": 1.0 if scale is None else float(scale)}
+
+
 def train(args):
     """Epoch / step loop of reference :328-426 on top of NwayTrainer.train_step."""
     import random
@@ -1454,10 +1492,10 @@ def train(args):
             cfg = EncoderConfig(arch="distilbert")
         args.synthetic_vocab = cfg.vocab_size
         model = NwayDualEncoder(cfg, share_weights=args.share_weights, in_batch_loss=args.in_batch_loss,
-                                all_in_batch_neg=args.all_in_batch_neg)
+                                all_in_batch_neg=args.all_in_batch_neg, **_cosine_kw(args))
     else:
         model = NwayDualEncoder(args.model_name_or_path, share_weights=args.share_weights, in_batch_loss=args.in_batch_loss,
-                                all_in_batch_neg=args.all_in_batch_neg)
+                                all_in_batch_neg=args.all_in_batch_neg, **_cosine_kw(args))
     model.to(dev)
     model.train()
     steps_per_epoch = common_steps_per_epoch(len(loader), args.distributed, dev)

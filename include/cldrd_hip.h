@@ -252,6 +252,24 @@ int cldrd_score_fwd(const float* q, const float* p, float* logits, int B, int N,
 int cldrd_score_bwd(const float* dlogits, const float* q, const float* p, float* dq, float* dp, int B, int N, int d,
                     int mode, void* stream);
 
+/* ---- cosine-similarity scoring (--apply_consine_similarity; csrc/cosine.hip) ----------------------------------
+ * The reference's scripts/unity/cosine_nway_listwise.sh names the flag, its tree has no trainer behind it: the arithmetic is this
+ * package's.  With nq = max(||q||, eps), np_j = max(||p_j||, eps) (eps as in torch.nn.functional.cosine_similarity: 1e-8):
+ *     logits[b, j] = scale * <q[b], p[passage(b, j)]> / (nq_b * np_j)          modes, B, N, d as cldrd_score_fwd; fp32
+ * inv_norms: device float[B + B*N], written by the forward (1 / nq per query, then 1 / np per passage; the entry of a row whose norm
+ * was clamped, ||row|| <= eps, is stored negated) and read by the backward, which also reads the forward's logits:
+ *     dq[b] = iq * (scale * sum_j g_j ip_j p_j - (sum_j g_j logit_j) * iq * q[b])
+ *     dp[m] = ip * (scale * sum g iq_b q[b]    - (sum g logit)       * ip * p[m])      sums over every (b, j) with passage(b, j) == m
+ * with the second term dropped for a clamped row (its norm is the constant eps).  Forward: two launches (norms, logits); backward: two.
+ * No float atomics, every sum in one fixed order: two calls give the same bits.  d % 4 == 0; scale finite and > 0; eps > 0. */
+int cldrd_score_cos_fwd(const float* q, const float* p, float* logits, float* inv_norms, int B, int N, int d, int mode, float scale,
+                        float eps, void* stream);
+int cldrd_score_cos_bwd(const float* dlogits, const float* logits, const float* q, const float* p, const float* inv_norms, float* dq,
+                        float* dp, int B, int N, int d, int mode, float scale, void* stream);
+/* out[r, :d] = x[r * ld_x : +d] / max(||x[r]||, eps) for r < n, fp32; out is dense [n, d] and may be x itself (then ld_x == d).  The sum
+ * of squares, the norm and each division are taken in fp64 and the quotient rounded to fp32 once.  d % 4 == 0, ld_x >= d, ld_x % 4 == 0. */
+int cldrd_l2_normalize_rows(const float* x, size_t ld_x, float* out, size_t n, int d, float eps, void* stream);
+
 /* ---- losses (losses/kl_div.py, margin_mse.py, ranknet.py, lambda_rank.py) ---------------------------------
  * kind 0 KLDiv(T) | 1 MarginMSE | 2 ranknet_loss | 3 lambda_mrr_loss (batch_weight != NULL: bweight_lambda_mrr_loss).
  * loss_out: float[2] = {loss, valid pair count}; grad [B,N] = dloss/dy_pred; workspace float[2*B]. */
