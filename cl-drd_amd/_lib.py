@@ -64,6 +64,7 @@ SIGNATURES = {
     "cldrd_distill_term": (ci, [ci, vp, ci, ci, vp, ci, cf, cf, vp, vp, vp, vp]),
     "cldrd_lambda_loss_fwd_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cf, cf, ci, ci, ci, vp]),
     "cldrd_lambda_term": (ci, [vp, ci, ci, vp, ci, ci, ci, cf, ci, ci, cf, cf, cf, cf, ci, ci, ci, cf, ci, vp, vp, vp, vp, vp]),
+    "cldrd_softmax_ce": (ci, [vp, vp, ci, ci, vp, ci, ci, cf, cf, ci, cf, ci, vp, vp, vp, vp]),
     "cldrd_sqnorm_blocks": (ci, []),
     "cldrd_grad_clip_coef": (ci, [vp, csz, cf, vp, vp, vp]),
     "cldrd_sqnorm_partial": (ci, [vp, csz, vp, ci, vp]),

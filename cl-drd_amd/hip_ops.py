@@ -1066,6 +1066,37 @@ def lambda_term(logits, labels, loss_out, grad, term_out=None, *, alpha=1.0, acc
          1 if accumulate else 0, _p(loss_out), _p(grad), _p(term_out), _p(ws), _stream())
 
 
+def softmax_ce(logits, labels, loss_out, grad, *, pids=None, nway=None, mode=0, temperature=1.0, pos_min=None, neg_max=0.0, reduction="mean"):
+    """Softmax cross-entropy (InfoNCE) of each row's positives against its negatives (cldrd_softmax_ce, one launch; the definition is in
+    include/cldrd_hip.h): loss_out = {loss, valid rows}, grad [B, Np] = d loss / d logits, every element written.  labels [B, Np] decide the
+    classes: positive ``label >= pos_min`` (``pos_min=None``: the row's maximum label), negative ``label <= neg_max``, the rest neutral.
+    ``pids`` (int64 [B, nway], with the scoring ``mode`` of `score_fwd`): a negative whose passage id is also behind a positive or neutral
+    column of its row becomes neutral."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError("Reduction method can be either sum or mean")
+    if not float(temperature) > 0.0:
+        raise ValueError("softmax_ce: temperature must be > 0")
+    if pos_min is not None and not float(pos_min) > float(neg_max):
+        raise ValueError("softmax_ce: pos_min must be > neg_max")
+    _chk(logits, F32, "logits", 2), _chk(labels, F32, "labels", 2), _chk(loss_out, F32, "loss_out", 1), _chk(grad, F32, "grad", 2)
+    if not (logits.is_contiguous() and grad.is_contiguous() and labels.is_contiguous()) or grad.shape != logits.shape or labels.shape != logits.shape:
+        raise ValueError("softmax_ce: logits, grad and labels must be contiguous and of one shape")
+    if loss_out.numel() < 2:
+        raise ValueError("softmax_ce: loss_out must hold 2 floats")
+    B, Np = logits.shape
+    N = 0
+    if pids is not None:
+        _chk(pids, torch.int64, "pids", 2)
+        N = pids.shape[1] if nway is None else int(nway)
+        if mode not in (0, 1, 2) or not pids.is_contiguous() or tuple(pids.shape) != (B, N) or Np != (N if mode == 0 else (B * N if mode == 1 else 2 * N)):
+            raise ValueError(f"softmax_ce: pids must be contiguous [B, nway] = [{B}, {N}] with {Np} = nway | B * nway | 2 * nway logit columns "
+                             f"for mode 0 | 1 | 2; got {tuple(pids.shape)}, mode {mode}")
+    ws = torch.empty(2 * B, dtype=F32, device=logits.device)
+    call("cldrd_softmax_ce", _p(logits), _p(labels), B, Np, _p(pids), N, int(mode) if pids is not None else 0, float(temperature),
+         0.0 if pos_min is None else float(pos_min), 0 if pos_min is None else 1, float(neg_max), 1 if reduction == "mean" else 0,
+         _p(loss_out), _p(grad), _p(ws), _stream())
+
+
 def sqnorm_blocks() -> int:
     return _lib.load().cldrd_sqnorm_blocks()
 

@@ -8,3 +8,4 @@ from .standard_lambda_rank import lambda_loss  # noqa: F401
 from .margin_mse import MarginMSE  # noqa: F401
 from .kl_div import KLDiv  # noqa: F401
 from .distill import DistillLoss  # noqa: F401
+from .softmax_ce import SoftmaxCE  # noqa: F401

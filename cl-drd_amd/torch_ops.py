@@ -11,6 +11,7 @@ formula where the reference differentiates through the call:
     cldrd::lambda_loss        losses/standard_lambda_rank.py:3-95
     cldrd::distill_term       alpha * {KLDiv(T), MarginMSE}(y_pred[:, :Nt], teacher scores): the term the fused trainer adds behind its rank loss
     cldrd::lambda_term        alpha * lambda_loss(y_pred[:, :Ns], transformed labels): the fused trainer's --loss lambda_loss, in one launch
+    cldrd::softmax_ce         softmax cross-entropy (InfoNCE) of the positives against the negatives at a temperature: the fused trainer's --loss softmax_ce
     cldrd::nway_score         models/nway_dual_encoder.py:30-47 (N-way / in-batch scoring), backward cldrd::nway_score_bwd
     cldrd::nway_score_cos     the same layout, logits = scale * cosine similarity (--apply_consine_similarity), backward cldrd::nway_score_cos_bwd
     cldrd::linear             torch.nn.Linear inside the HF encoder (bias / erf-GELU / residual epilogue), forward
@@ -158,6 +159,33 @@ def _lambda_term_backward(ctx, g_out, g_grad):
 torch.library.register_autograd("cldrd::lambda_term", _lambda_term_backward, setup_context=_lambda_term_setup)
 
 
+@torch.library.custom_op("cldrd::softmax_ce", mutates_args=(), device_types="cuda")
+def softmax_ce(y_pred: Tensor, labels: Tensor, pids: Optional[Tensor], mode: int, temperature: float, pos_min: Optional[float], neg_max: float,
+               mean_reduction: bool) -> Tuple[Tensor, Tensor]:
+    """(out float[2] = {loss, valid rows}, d loss / d y_pred [B, Np]): softmax cross-entropy of each row's positives against its negatives
+    at ``temperature`` (cldrd_softmax_ce); labels [B, Np] decide the classes (pos_min None: the row's maximum label is the positive), pids
+    (int64 [B, N], optional, with the scoring mode 0 / 1 / 2) turn the negatives that repeat a positive or neutral passage of their row neutral."""
+    y = y_pred.detach().float().contiguous()
+    out = torch.empty(2, dtype=torch.float32, device=y.device)
+    grad = torch.empty_like(y)
+    ops.softmax_ce(y, labels.detach().float().contiguous(), out, grad, pids=None if pids is None else pids.contiguous(), mode=mode,
+                   temperature=temperature, pos_min=pos_min, neg_max=neg_max, reduction="mean" if mean_reduction else "sum")
+    return out, grad
+
+
+@softmax_ce.register_fake
+def _(y_pred, labels, pids, mode, temperature, pos_min, neg_max, mean_reduction):
+    return y_pred.new_empty((2,), dtype=torch.float32), y_pred.new_empty(y_pred.shape, dtype=torch.float32)
+
+
+def _softmax_ce_backward(ctx, g_out, g_grad):
+    (grad,) = ctx.saved_tensors
+    return ((grad * g_out[0]).to(ctx.in_dtype),) + (None,) * 7
+
+
+torch.library.register_autograd("cldrd::softmax_ce", _softmax_ce_backward, setup_context=_loss_setup)
+
+
 # ---------------------------------------------------------------------------------------------------------------- scoring
 def _score_cols(B: int, N: int, mode: int) -> int:
     return N if mode == 0 else (B * N if mode == 1 else 2 * N)
@@ -298,4 +326,4 @@ def _(qkv, mask, nseq, L, H):
     return qkv.new_empty((qkv.shape[0], H * 64))
 
 
-OPS = ("listwise_loss", "lambda_loss", "distill_term", "lambda_term", "nway_score", "nway_score_bwd", "nway_score_cos", "nway_score_cos_bwd", "linear", "layer_norm", "self_attention")
+OPS = ("listwise_loss", "lambda_loss", "distill_term", "lambda_term", "softmax_ce", "nway_score", "nway_score_bwd", "nway_score_cos", "nway_score_cos_bwd", "linear", "layer_norm", "self_attention")

@@ -27,6 +27,11 @@ Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
     ``--label_source teacher`` its labels are ``batch["teacher_scores"]`` instead of the label-mode constants (``--neg_score_mode``,
     ``--teacher_label_shift``): the role of the ``ndcg_nway_listwise*`` trainers the reference's scripts name but its tree lacks, so what
     these two flags mean is defined here (README: nDCG training);
+  * ``--loss softmax_ce`` trains on the softmax cross-entropy (InfoNCE) of a row's positives against its negatives at ``--ce_temperature``,
+    the loss the in-batch columns of ``--in_batch_loss`` and cosine scoring are normally paired with (``cldrd_softmax_ce``, one launch in the
+    same place on the loss stream; ``--ce_pos_min`` / ``--ce_neg_max`` say which labels are positives and negatives, ``--ce_mask_duplicate_pids``
+    keeps a passage that is a row's positive or neutral out of its negatives): the reference has no such loss, the definition is this
+    package's (README: Contrastive training);
   * ``--apply_consine_similarity`` (the reference's spelling, ``scripts/unity/cosine_nway_listwise.sh``; its trainer is not in the tree)
     scores with ``--cosine_scale`` times the cosine of the two CLS embeddings instead of their dot product (``cldrd_score_cos_fwd`` /
     ``cldrd_score_cos_bwd`` in the place of the dot-product pair on the loss stream, one launch more); the checkpoint then carries a
@@ -55,6 +60,11 @@ from ..retriever.retrieval_utils import cap_host_threads
 
 LOSS_KINDS = ("lambda_mrr", "ranknet", "kl_div", "margin_mse", "lambda_loss")
 DISTILL_KINDS = ("kl_div", "margin_mse")      # --distill_loss: the term on batch["teacher_scores"] added to the rank loss
+# --loss softmax_ce (cldrd_softmax_ce in the fused step; this package's definition, README: Contrastive training), in a tuple of its own:
+# --loss takes LOSS_KINDS + CONTRASTIVE_KINDS.  CE_DEFAULTS: the options that mean something under it only (ce_pos_min None: the row's
+# maximum label is its positive), None = not set on the command line and in NwayTrainer; --ce_mask_duplicate_pids is a switch.
+CONTRASTIVE_KINDS = ("softmax_ce",)
+CE_DEFAULTS = {"ce_temperature": 1.0, "ce_pos_min": None, "ce_neg_max": 0.0}
 # --loss lambda_loss (allRank's LambdaLoss framework, reference losses/standard_lambda_rank.py:3-117; cldrd_lambda_term in the fused step).
 # The reference's launch scripts name ndcg trainers (--weighing_scheme, --neg_score_mode) that its tree does not contain: which labels the
 # loss sees (LABEL_SOURCES) and what the two teacher-label options do are THIS package's definition (README: nDCG training).
@@ -71,9 +81,11 @@ RESUME_VERSION = 1                            # of the checkpoint's "resume_stat
 POSITION_FIELDS = ("train_batch_size", "nranks", "seed", "dataset_len", "steps_per_epoch", "num_train_epochs")
 
 
-def check_loss_options(loss, label_source="rank", in_batch_loss=False, label_mode=None, synthetic=False, given=()):
-    """The combinations of --loss / --label_source / the lambda flags that mean nothing: a ``ValueError`` that names the flag.  ``given``:
-    the names of LAMBDA_DEFAULTS / TEACHER_LABEL_DEFAULTS set by the caller (None = not set, on the command line and in NwayTrainer)."""
+def check_loss_options(loss, label_source="rank", in_batch_loss=False, label_mode=None, synthetic=False, given=(), *, ce_temperature=None,
+                       ce_pos_min=None, ce_neg_max=None, ce_mask_duplicate_pids=False):
+    """The combinations of --loss / --label_source / the lambda flags / the ce flags that mean nothing: a ``ValueError`` that names the flag.
+    ``given``: the names of LAMBDA_DEFAULTS / TEACHER_LABEL_DEFAULTS set by the caller (None = not set, on the command line and in
+    NwayTrainer); the ce flags come as their values (None / False = not set)."""
     if label_source not in LABEL_SOURCES:
         raise ValueError(f"--label_source must be one of {LABEL_SOURCES}")
     for name in given:
@@ -88,6 +100,28 @@ def check_loss_options(loss, label_source="rank", in_batch_loss=False, label_mod
             raise ValueError("--label_source teacher cannot go with --in_batch_loss: the in-batch columns have no teacher score")
         if label_mode == "1" and not synthetic:
             raise ValueError("--label_source teacher needs a relT / most-hard / semi-hard training file with scores; --label_mode 1 files have none")
+    ce = {"ce_temperature": ce_temperature, "ce_pos_min": ce_pos_min, "ce_neg_max": ce_neg_max, "ce_mask_duplicate_pids": ce_mask_duplicate_pids or None}
+    if loss not in CONTRASTIVE_KINDS:
+        for name, value in ce.items():
+            if value is not None:
+                raise ValueError(f"--{name} is an option of --loss softmax_ce; it was given with --loss {loss}")
+        return
+    if ce_temperature is not None and not (math.isfinite(ce_temperature) and ce_temperature > 0.0):
+        raise ValueError("--ce_temperature must be finite and > 0")
+    neg_max = CE_DEFAULTS["ce_neg_max"] if ce_neg_max is None else float(ce_neg_max)
+    if not math.isfinite(neg_max):
+        raise ValueError("--ce_neg_max must be finite")
+    if ce_pos_min is not None and not float(ce_pos_min) > neg_max:
+        raise ValueError(f"--ce_pos_min must be > --ce_neg_max ({neg_max}): a label cannot make its column a positive and a negative")
+    if label_mode is not None and not synthetic and not in_batch_loss:
+        # the label row is a constant of the label mode: a row without a negative column of its own is never valid without in-batch columns
+        from ..dataset.nway_dataset import _REL, labels_for_mode
+        if str(label_mode) in _REL:
+            row = labels_for_mode(str(label_mode))
+            pos = [(v >= ce_pos_min) if ce_pos_min is not None else (v == max(row)) for v in row]
+            if not any(v <= neg_max and not p_ for v, p_ in zip(row, pos)):
+                raise ValueError(f"--label_mode {label_mode} has no negative column under --loss softmax_ce (no label <= --ce_neg_max {neg_max}): "
+                                 "it needs the in-batch columns of --in_batch_loss")
 
 
 def no_decay(name: str) -> bool:
@@ -277,12 +311,14 @@ class NwayTrainer:
                  total_steps: int = 100000, betas=(0.9, 0.999), bucket_layers: int = 1, reg_lambda: float = 0.0,
                  distill=None, distill_alpha: float = 1.0, distill_T: float = 1.0, distill_only: bool = False,
                  deterministic: bool = False, weighing_scheme=None, lambda_k=None, lambda_sigma=None, lambda_mu=None, lambda_gain=None,
-                 lambda_log=None, label_source: str = "rank", neg_score_mode=None, teacher_label_shift=None, n_rel=None):
-        if loss not in LOSS_KINDS:
-            raise ValueError(f"loss must be one of {LOSS_KINDS}")
+                 lambda_log=None, label_source: str = "rank", neg_score_mode=None, teacher_label_shift=None, n_rel=None, ce_temperature=None,
+                 ce_pos_min=None, ce_neg_max=None, ce_mask_duplicate_pids: bool = False):
+        if loss not in LOSS_KINDS + CONTRASTIVE_KINDS:
+            raise ValueError(f"loss must be one of {LOSS_KINDS + CONTRASTIVE_KINDS}")
         opts = dict(weighing_scheme=weighing_scheme, lambda_k=lambda_k, lambda_sigma=lambda_sigma, lambda_mu=lambda_mu, lambda_gain=lambda_gain,
                     lambda_log=lambda_log, neg_score_mode=neg_score_mode, teacher_label_shift=teacher_label_shift)
-        check_loss_options(loss, label_source, getattr(model, "in_batch_loss", False), given=[k_ for k_, v_ in opts.items() if v_ is not None])
+        check_loss_options(loss, label_source, getattr(model, "in_batch_loss", False), given=[k_ for k_, v_ in opts.items() if v_ is not None],
+                           ce_temperature=ce_temperature, ce_pos_min=ce_pos_min, ce_neg_max=ce_neg_max, ce_mask_duplicate_pids=ce_mask_duplicate_pids)
         opts = {k_: ({**LAMBDA_DEFAULTS, **TEACHER_LABEL_DEFAULTS}[k_] if v_ is None else v_) for k_, v_ in opts.items()}
         for name, allowed in (("weighing_scheme", WEIGHING_SCHEMES), ("lambda_gain", ("power", "linear")), ("lambda_log", ("natural", "binary")),
                               ("neg_score_mode", NEG_SCORE_MODES), ("teacher_label_shift", LABEL_SHIFTS)):
@@ -301,6 +337,11 @@ class NwayTrainer:
         if label_source == "teacher":
             self._lambda_kw.update(padded_value_indicator=float("-inf"), neg_mean=opts["neg_score_mode"] == "mean",
                                    row_min=opts["teacher_label_shift"] == "row_min", n_rel=n_rel)
+        # --loss softmax_ce: the keyword arguments of ops.softmax_ce; with ce_mask_duplicate_pids this step's batch["nway_pids"] go with them
+        self._ce_kw = dict(temperature=float(CE_DEFAULTS["ce_temperature"] if ce_temperature is None else ce_temperature),
+                           pos_min=None if ce_pos_min is None else float(ce_pos_min),
+                           neg_max=float(CE_DEFAULTS["ce_neg_max"] if ce_neg_max is None else ce_neg_max))
+        self.ce_mask_duplicate_pids = bool(ce_mask_duplicate_pids)
         if distill is not None and distill not in DISTILL_KINDS:
             raise ValueError(f"distill must be None or one of {DISTILL_KINDS}")
         if distill is not None and (not float(distill_alpha) >= 0.0 or not float(distill_T) > 0.0):
@@ -448,6 +489,7 @@ class NwayTrainer:
         q, nw = batch["query"], batch["nway_passages"]
         bz, nway, L = nw["input_ids"].shape
         teacher = self._teacher_scores(batch, bz, nway)
+        pids = self._nway_pids(batch, bz, nway)
         write_once = not model.share_weights and not self.zero_all_grads      # (test hook: zero_all_grads = True zeroes + accumulates)
         main = torch.cuda.current_stream()
         # The query tower is ~1 % of the FLOPs but dozens of small, latency-bound launches: it runs on its own stream
@@ -507,6 +549,10 @@ class NwayTrainer:
                 if self.label_source == "teacher":
                     labels = teacher.to(device=logits.device, dtype=torch.float32)
                 ops.lambda_term(logits, labels.contiguous(), loss_out, dlogits, **self._lambda_kw)
+            elif self.loss_kind in CONTRASTIVE_KINDS:
+                loss_out, dlogits = torch.empty(2, dtype=torch.float32, device=logits.device), torch.empty_like(logits)
+                ops.softmax_ce(logits, labels.contiguous(), loss_out, dlogits, mode=mode, nway=nway,
+                               pids=None if pids is None else pids.to(device=logits.device, dtype=torch.int64).contiguous(), **self._ce_kw)
             else:
                 loss_out, dlogits = ops.loss_fwd_bwd(self.loss_kind, logits, labels.contiguous(), T=self.T)
             if self.reg_lambda > 0.0 and mode == 0:     # reference nway_listwise_1.py:346-350: only without in-batch negatives
@@ -552,6 +598,23 @@ class NwayTrainer:
         if tuple(t.shape) != (bz, nway):
             raise ValueError(f"batch['teacher_scores'] must be [{bz}, {nway}] like the passages, got {tuple(t.shape)}")
         return t
+
+    def _reads_nway_pids(self) -> bool:
+        return self.ce_mask_duplicate_pids and not self.distill_only
+
+    def _nway_pids(self, batch, bz, nway):
+        """batch["nway_pids"] of a trainer that masks duplicate passages (int64 [B, nway], checked); None for any other trainer."""
+        if not self._reads_nway_pids():
+            return None
+        p = batch.get("nway_pids")
+        if p is not None and not isinstance(p, torch.Tensor):
+            p = torch.as_tensor(p)               # collate_fn returns the ids as a numpy array
+        if p is None:
+            raise ValueError("this trainer masks duplicate passages (ce_mask_duplicate_pids) and needs batch['nway_pids'] (int64 [B, nway], the "
+                             "passage ids NwayDataset.collate_fn returns); synthetic batches have none")
+        if tuple(p.shape) != (bz, nway) or p.dtype != torch.int64:
+            raise ValueError(f"batch['nway_pids'] must be int64 [{bz}, {nway}] like the passages, got {p.dtype} {tuple(p.shape)}")
+        return p
 
     def _backward(self, q_tape, p_tape, dq, dp, main, side, lst, write_once):
         """both towers' backward from dq / dp (scaled by the loss scale in the amp16 mode) + the bucket all-reduces.  ``main``, ``side``, ``lst``:
@@ -756,8 +819,9 @@ class NwayTrainer:
 
     def _step_inputs(self, batch):
         """The per-step inputs of the captured step: [(where it sits in the batch dict, tensor, dtype the static batch holds it in - None: its
-        own)], in ONE order for the batch key, the static batch and every incoming one (at most 6 segments; cldrd_copy_segments takes 8).
-        The teacher scores are one of them, once: a step that distils or takes its labels from the teacher reads this step's scores."""
+        own)], in ONE order for the batch key, the static batch and every incoming one (at most 7 segments; cldrd_copy_segments takes 8).
+        The teacher scores are one of them, once: a step that distils or takes its labels from the teacher reads this step's scores; so are
+        the passage ids of a step that masks duplicate passages."""
         q, nw = batch["query"], batch["nway_passages"]
         items = [(("query", "input_ids"), q["input_ids"], None), (("nway_passages", "input_ids"), nw["input_ids"], None),
                  (("nway_passages", "attention_mask"), nw["attention_mask"], None), (("labels",), batch["labels"], torch.float32)]
@@ -766,6 +830,9 @@ class NwayTrainer:
         if self._reads_teacher_scores():
             bz, nway, _ = nw["input_ids"].shape
             items.append((("teacher_scores",), self._teacher_scores(batch, bz, nway), torch.float32))
+        if self._reads_nway_pids():
+            bz, nway, _ = nw["input_ids"].shape
+            items.append((("nway_pids",), self._nway_pids(batch, bz, nway), None))
         return items
 
     def _batch_key(self, batch):
@@ -1112,7 +1179,15 @@ def get_args(argv=None):
     ap.add_argument("--all_in_batch_neg", action="store_true", default=False)
     ap.add_argument("--n_gpu", default=1, type=int)
     ap.add_argument("--local_rank", default=-1, type=int)
-    ap.add_argument("--loss", default="lambda_mrr", choices=LOSS_KINDS)
+    ap.add_argument("--loss", default="lambda_mrr", choices=LOSS_KINDS + CONTRASTIVE_KINDS)
+    ap.add_argument("--ce_temperature", default=None, type=float,
+                    help="--loss softmax_ce: the temperature the logits are divided by (default 1; it multiplies with --cosine_scale)")
+    ap.add_argument("--ce_pos_min", default=None, type=float,
+                    help="--loss softmax_ce: columns with label >= this are positives (default: the columns at the row's maximum label)")
+    ap.add_argument("--ce_neg_max", default=None, type=float,
+                    help="--loss softmax_ce: columns with label <= this (and not positive) are negatives, the rest is left out (default 0)")
+    ap.add_argument("--ce_mask_duplicate_pids", action="store_true", default=False,
+                    help="--loss softmax_ce: a negative column whose passage id is also behind a positive or left-out column of its row is left out")
     ap.add_argument("--weighing_scheme", default=None, choices=WEIGHING_SCHEMES,
                     help="--loss lambda_loss: the pair weights (reference losses/standard_lambda_rank.py:98-127; default none: every pair 1)")
     ap.add_argument("--lambda_k", default=None, type=int, help="--loss lambda_loss: rank truncation k (default 0: none)")
@@ -1177,13 +1252,22 @@ def get_args(argv=None):
         ap.error("--distill_alpha must be >= 0 and --distill_T > 0")
     defaults = {**LAMBDA_DEFAULTS, **TEACHER_LABEL_DEFAULTS}
     check_loss_options(args.loss, args.label_source, args.in_batch_loss, args.label_mode, args.synthetic_steps > 0,
-                       given=[k_ for k_ in defaults if getattr(args, k_) is not None])           # a ValueError that names the flag
+                       given=[k_ for k_ in defaults if getattr(args, k_) is not None],           # a ValueError that names the flag
+                       **_ce_options(args))
+    if args.ce_mask_duplicate_pids and args.synthetic_steps > 0:
+        raise ValueError("--ce_mask_duplicate_pids needs the passage ids of a training file (batch['nway_pids']); --synthetic_steps batches have none")
     if args.lambda_k is not None and args.lambda_k < 0 or args.lambda_sigma is not None and not args.lambda_sigma > 0.0:
         raise ValueError("--lambda_k must be >= 0 (0: no truncation) and --lambda_sigma > 0")
     args.run_folder = os.path.join(args.experiment_folder, args.run_folder)
     args.log_dir = os.path.join(args.run_folder, args.log_dir)
     args.model_save_dir = os.path.join(args.run_folder, args.model_save_dir)
     return args
+
+
+def _ce_options(args):
+    """The --ce_* flags as the keyword arguments of check_loss_options / NwayTrainer (None / False: not given)."""
+    return {"ce_temperature": getattr(args, "ce_temperature", None), "ce_pos_min": getattr(args, "ce_pos_min", None),
+            "ce_neg_max": getattr(args, "ce_neg_max", None), "ce_mask_duplicate_pids": bool(getattr(args, "ce_mask_duplicate_pids", False))}
 
 
 def set_env(args):
@@ -1319,7 +1403,8 @@ def build_dataloader(args):
     """Label mode -> file constructor as reference :173-245; per-rank batch = train_batch_size // nranks, shuffle, drop_last."""
     from transformers import AutoTokenizer
     from ..dataset.nway_dataset import NwayDataset
-    check_loss_options(getattr(args, "loss", "lambda_mrr"), getattr(args, "label_source", "rank"), label_mode=args.label_mode)      # before anything is loaded
+    check_loss_options(getattr(args, "loss", "lambda_mrr"), getattr(args, "label_source", "rank"), getattr(args, "in_batch_loss", False),
+                       label_mode=args.label_mode, **_ce_options(args))      # before anything is loaded
     tok = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path)
     a = (args.queries_path, args.collection_path, args.training_path, tok)
     kw = dict(max_query_len=args.query_max_len, max_passage_len=args.passage_max_len, label_mode=args.label_mode)
@@ -1506,7 +1591,7 @@ def train(args):
                           distill_alpha=getattr(args, "distill_alpha", 1.0), distill_T=getattr(args, "distill_T", 1.0),
                           distill_only=getattr(args, "distill_only", False), deterministic=getattr(args, "deterministic", False),
                           label_source=getattr(args, "label_source", "rank"), n_rel=_n_rel(args),
-                          **{k_: getattr(args, k_, None) for k_ in (*LAMBDA_DEFAULTS, *TEACHER_LABEL_DEFAULTS)})
+                          **{k_: getattr(args, k_, None) for k_ in (*LAMBDA_DEFAULTS, *TEACHER_LABEL_DEFAULTS)}, **_ce_options(args))
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)            # after model / loader construction, as the reference does (:282)
@@ -1551,6 +1636,8 @@ def train(args):
             if step_i >= steps_per_epoch:       # ranks whose shard is one batch longer stop with the others (no unmatched all-reduce)
                 break
             batch = batch_to_device(batch, dev)
+            if trainer.ce_mask_duplicate_pids:          # the one id array a step reads on the device (collate_fn: a numpy array)
+                batch["nway_pids"] = torch.as_tensor(batch["nway_pids"]).to(dev, non_blocking=True)
             loss_out = trainer.train_step(batch)
             if main_rank and trainer.global_step % args.logging_steps == 0:
                 # the reference reads loss / MRR back every step (:369-389); here only on logging steps (no per-step sync)

@@ -321,6 +321,30 @@ int cldrd_lambda_term(const float* logits, int B, int Np, const float* labels, i
                       int gain_linear, float alpha, int accumulate, float* loss_out, float* grad, float* term_out, float* workspace,
                       void* stream);
 
+/* Softmax cross-entropy (InfoNCE) of a row's positives against its negatives, with a temperature: value + d loss / d logits in ONE launch,
+ * one workgroup per row; the fused trainer's --loss softmax_ce, in the place of cldrd_loss_fwd_bwd / cldrd_lambda_term on the loss stream.
+ * The reference has no such loss: this is this package's definition.
+ * logits, labels, grad: [B, Np] fp32 (labels: the label-mode constants, in-batch columns at -0.5).  Column classes of a row, from the labels:
+ *   positive: label >= pos_min when has_pos_min, else label == the row's maximum label (an exact tie at the maximum: several positives);
+ *   negative: label <= neg_max and not positive;   neutral: everything else - in neither sum, gradient 0.   has_pos_min: pos_min > neg_max.
+ * Duplicate rule, only when pids != NULL (int64 [B, N], the passage ids of the rows' own columns; mode 0 / 1 / 2 and N as cldrd_score_fwd,
+ * Np = N | B * N | 2 * N): a negative column whose pid equals the pid of a positive or neutral column of the same row becomes neutral.  The
+ * passage behind column c of row b: c < N: pids[b][c]; mode 1, c >= N: global index g = c - N, shifted by N when g >= b * N; mode 2,
+ * c >= N: pids[(b + 1) % B][c - N].  pids == NULL: mode and N are not used.
+ * With z = logits / tau, P / G the positive / negative sets of row b and Z = sum_{j in G} exp(z_j):
+ *   L_b  = (1/|P|) * sum_{i in P} [ log(exp(z_i) + Z) - z_i ]
+ *   loss = mean of L_b over the valid rows (|P| >= 1 and |G| >= 1) when mean_reduction, else their sum; no valid row: 0
+ *   d loss / d logits[b,i], i in P:  w * (exp(z_i) / (exp(z_i) + Z) - 1)
+ *   d loss / d logits[b,j], j in G:  w * exp(z_j) * sum_{i in P} 1 / (exp(z_i) + Z)
+ *        w = 1 / (tau * |P| * R),  R = number of valid rows (mean) or 1 (sum);   neutral columns and invalid rows: 0
+ * evaluated after subtracting the row's maximum z over P u G.  With one positive this is cross_entropy(z[P u G], target).
+ * loss_out: float[2] = {loss, valid rows}; grad: every element is written; workspace: 2*B floats.  tau > 0, 1 <= Np <= 8192.
+ * Deterministic: the cross-row sum has a fixed order (no float atomics).  Up to 32 launches of this entry point may be in flight on one
+ * device at a time (arrival counters as cldrd_lambda_term). */
+int cldrd_softmax_ce(const float* logits, const float* labels, int B, int Np, const long long* pids, int N, int mode, float tau,
+                     float pos_min, int has_pos_min, float neg_max, int mean_reduction, float* loss_out, float* grad, float* workspace,
+                     void* stream);
+
 /* ---- optimizer step (trainer/multistep-curriculum/nway_listwise_1.py:353-367) ------------------------------
  * One flat fp32 buffer for all parameters.  clip out: float[3] = {grad L2 norm, clip coefficient, non-finite flag}.
  * decay_flags: one byte per 64 parameters: bit 0 = weight decay applies, bit 1 = leave the 16-bit shadows of this chunk unwritten

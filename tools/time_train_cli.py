@@ -9,9 +9,12 @@ except through the queue depth).
                                    [--weighing_scheme S] [--lambda_k K] [--lambda_sigma X] [--lambda_mu X] [--lambda_gain G] [--lambda_log L]
                                    [--label_source rank|teacher] [--neg_score_mode M] [--teacher_label_shift S]
                                    [--apply_consine_similarity [--cosine_scale X]]
+                                   [--ce_temperature X] [--ce_pos_min X] [--ce_neg_max X] [--in_batch_loss [--all_in_batch_neg]]
         --fixed: every passage 128 tokens (the bench's headline batch: one shape, replayed as a HIP graph); default: MS MARCO-shaped lengths
         --loss: the trainer's --loss (default here: kl_div, the bench's); with lambda_loss the lambda / label flags above are passed through too
         --distill_loss kl_div | margin_mse: passed through to the trainer (the synthetic loader then adds teacher_scores to every batch)
+        --ce_temperature, --ce_pos_min, --ce_neg_max: passed through to the trainer with --loss softmax_ce (cldrd_softmax_ce on the loss stream);
+                 --in_batch_loss, --all_in_batch_neg: passed through (the [B, B*N] / [B, 2N] logit matrices)
         --apply_consine_similarity, --cosine_scale: passed through to the trainer (the cosine scorer on the loss stream)
         --deterministic: passed through to the trainer (embedding-table gradients as fixed-order sums instead of float atomics)
         --ddp1:  the data-parallel code path (bucket hooks, RCCL all-reduces, agreement step) with a process group of ONE rank (CLDRD_FORCE_DDP=1)
@@ -31,8 +34,8 @@ workers = int(sys.argv[sys.argv.index("--workers") + 1]) if "--workers" in sys.a
 distill = sys.argv[sys.argv.index("--distill_loss") + 1] if "--distill_loss" in sys.argv else None
 loss = sys.argv[sys.argv.index("--loss") + 1] if "--loss" in sys.argv else "kl_div"
 passed = [a for f in ("--weighing_scheme", "--lambda_k", "--lambda_sigma", "--lambda_mu", "--lambda_gain", "--lambda_log", "--label_source",
-                      "--neg_score_mode", "--teacher_label_shift", "--cosine_scale") if f in sys.argv for a in (f, sys.argv[sys.argv.index(f) + 1])] \
-    + [f for f in ("--apply_consine_similarity",) if f in sys.argv]
+                      "--neg_score_mode", "--teacher_label_shift", "--cosine_scale", "--ce_temperature", "--ce_pos_min", "--ce_neg_max") if f in sys.argv for a in (f, sys.argv[sys.argv.index(f) + 1])] \
+    + [f for f in ("--apply_consine_similarity", "--in_batch_loss", "--all_in_batch_neg") if f in sys.argv]
 det = "--deterministic" in sys.argv
 with tempfile.TemporaryDirectory(dir="/tmp") as td:
     argv = ["--experiment_folder", td, "--run_folder", "run", "--synthetic_steps", str(steps), "--synthetic_model", "distilbert", "--synthetic_nway", "32",
