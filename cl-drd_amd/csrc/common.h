@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 typedef uint16_t bf16_t;   // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;    // MFMA A/B fragment (8 bf16 = 4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
@@ -62,6 +64,60 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+// Sum / maximum over the workgroup, the same value in every thread: wave shuffle, one float of LDS per wave (red: blockDim.x / 64 floats),
+// then the waves in ascending order.  Both begin with a barrier, so red may be reused from one call to the next.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float s = 0.f;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+    return s;
+}
+__device__ __forceinline__ float block_max(float v, float* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float s = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = fmaxf(s, red[w]);
+    return s;
+}
+
+// Last arrival: how a launch whose workgroups each leave a partial result in global memory lets ONE of them combine the results, in a fixed
+// order and without a second launch.  Every workgroup stores its part, then ALL its threads call arrived_last(); the workgroup for which it
+// returns true (block-uniform) may read what every other workgroup of the launch stored before its own call.  In order:
+//   every thread waits for its own stores (vmcnt(0)), and the barrier collects the waves: the workgroup's stores have all left the CU;
+//   thread 0 releases at agent scope (the XCD's L2 is written back: L2s of different XCDs are not coherent), waits again (the compiler may
+//   drop the fence's own wait), and only then takes a ticket of the launch's counter;
+//   the workgroup that draws the last ticket acquires at agent scope (its CU's L1 may hold stale copies of the other workgroups' lines),
+//   waits for the invalidate, and puts the counter back to 0 for the launch that gets the slot next;
+//   the answer goes through LDS, and the second barrier holds every wave until the invalidate is done.
+// A workgroup-scope fence, or a fence behind the ticket, is not a publish: the sum comes out right on most runs and wrong on some.
+// The counter is one of ARRIVAL_SLOTS of the kernel's own array (a __device__ array cannot be shared between the translation units of this
+// library); a launch takes the next slot in turn (arrival_next_slot, host), so ARRIVAL_SLOTS launches of one kernel may be in flight on a
+// device at a time.  The slots are zero at module load and every launch leaves its slot zero.
+enum { ARRIVAL_SLOTS = 32 };
+static inline int arrival_next_slot(std::atomic<unsigned int>& launches) { return (int)(launches.fetch_add(1u) % ARRIVAL_SLOTS); }
+__device__ __forceinline__ bool arrived_last(unsigned int* ticket, int workgroups) {
+    __shared__ int last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const bool l = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(workgroups - 1);
+        if (l) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        last = l ? 1 : 0;
+    }
+    __syncthreads();
+    return last != 0;
 }
 
 // erf-GELU and its derivative (HF GELUActivation == F.gelu).  erf by Abramowitz-Stegun 7.1.26

@@ -16,51 +16,20 @@
 //   d loss / d logits[b,j], j in G:  w exp(z_j) sum_{i in P} 1 / (exp(z_i) + Z)
 //   neutral columns and invalid rows: 0.
 // Everything is evaluated after subtracting the row's maximum z over P u G.
-#include <atomic>
-
 #include "common.h"
+#include "score_layout.h"
 
 namespace {
 
 enum { CE_NEUTRAL = 0, CE_POS = 1, CE_NEG = 2 };
 
-__device__ __forceinline__ float ce_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-    return s;
-}
-__device__ __forceinline__ float ce_block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = fmaxf(s, red[w]);
-    return s;
-}
-
-// index into pids [B * N] of the passage behind logit column j of row b: the layout of score_fwd_kernel (loss.hip)
-__device__ __forceinline__ int ce_col_to_passage(int mode, int b, int j, int B, int N) {
-    if (j < N) return b * N + j;
-    const int jj = j - N;
-    if (mode == 1) return jj < b * N ? jj : jj + N;
-    return ((b + 1) % B) * N + jj;
-}
-
 // LDS bytes of one row: z [Np] floats, the columns kept out of the negatives by their label [Np] uint16, the class [Np] bytes
 __host__ __device__ constexpr size_t softmax_ce_lds_bytes(int Np) { return (size_t)7 * Np + 16; }
 
-// Arrival counters of softmax_ce_kernel launches, as lambda_term_tickets (loss.hip): a launch takes the next slot in turn, its last
-// workgroup puts the slot back to 0.  Zero at module load; CE_TICKETS launches may be in flight on one device at a time.
-enum { CE_TICKETS = 32 };
-__device__ unsigned int softmax_ce_tickets[CE_TICKETS];
+__device__ unsigned int softmax_ce_tickets[ARRIVAL_SLOTS];      // arrival counters of softmax_ce_kernel launches (common.h: arrived_last)
 
 // One workgroup per row.  A row's sums are block reductions in a fixed order; the one cross-row quantity, {sum of L_b, R}, is added in a
-// fixed order by the workgroup that draws the last ticket (agent-scope release by every workgroup, agent-scope acquire by the last one):
+// fixed order by the workgroup that arrives last (common.h: arrived_last):
 // no float atomics, the same bits on every launch.  Every workgroup writes its row's gradient for R = 1; under the 'mean' reduction the
 // last workgroup then multiplies the whole gradient by 1 / R (R is not known before every row's duplicate rule has run).
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
@@ -69,7 +38,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
                                                           float pos_min, int has_pos_min, float neg_max, int mean_reduction, int slot) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[4];
-    __shared__ int shared_int[2];                    // [0] number of kept columns, [1] "this workgroup drew the last ticket"
+    __shared__ int n_keep;                           // number of kept columns
     float* z = sm;                                                   // [Np]
     unsigned short* keep = (unsigned short*)(z + Np);                // [Np] columns that are positive or neutral by their label
     unsigned char* cls = (unsigned char*)(keep + Np);                // [Np]
@@ -84,9 +53,9 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     float lmax = NINF;
     if (!has_pos_min) {
         for (int i = tid; i < Np; i += blockDim.x) lmax = fmaxf(lmax, lab[i]);
-        lmax = ce_block_max(lmax, red);
+        lmax = block_max(lmax, red);
     }
-    if (tid == 0) shared_int[0] = 0;
+    if (tid == 0) n_keep = 0;
     __syncthreads();
     for (int i = tid; i < Np; i += blockDim.x) {
         const float l = lab[i];
@@ -94,17 +63,17 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
         const int c = pos ? CE_POS : (l <= neg_max ? CE_NEG : CE_NEUTRAL);
         cls[i] = (unsigned char)c;
         z[i] = lg[i] / tau;
-        if (pids && c != CE_NEG) keep[atomicAdd(&shared_int[0], 1)] = (unsigned short)i;      // the order of the list decides nothing
+        if (pids && c != CE_NEG) keep[atomicAdd(&n_keep, 1)] = (unsigned short)i;      // the order of the list decides nothing
     }
     __syncthreads();
     // ---- duplicate rule: a negative whose passage is also behind a positive or neutral column of this row leaves the negatives
     if (pids) {
-        const int nk = shared_int[0];
+        const int nk = n_keep;
         for (int i = tid; i < Np; i += blockDim.x) {
             if (cls[i] != CE_NEG) continue;
-            const long long p = pids[ce_col_to_passage(mode, b, i, B, N)];
+            const long long p = pids[col_to_passage(mode, b, i, B, N)];
             bool dup = false;
-            for (int k = 0; k < nk && !dup; ++k) dup = pids[ce_col_to_passage(mode, b, keep[k], B, N)] == p;
+            for (int k = 0; k < nk && !dup; ++k) dup = pids[col_to_passage(mode, b, keep[k], B, N)] == p;
             if (dup) cls[i] = CE_NEUTRAL;            // keep[] lists label classes only: no thread reads another thread's cls here
         }
         __syncthreads();
@@ -117,16 +86,16 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
         m = fmaxf(m, z[i]);
         if (c == CE_POS) np += 1.f; else ng += 1.f;
     }
-    m = ce_block_max(m, red);
-    np = ce_block_sum(np, red);                      // whole numbers <= 8192: exact
-    ng = ce_block_sum(ng, red);
+    m = block_max(m, red);
+    np = block_sum(np, red);                         // whole numbers <= 8192: exact
+    ng = block_sum(ng, red);
     const bool valid = np >= 1.f && ng >= 1.f;
     float row_loss = 0.f;
     if (valid) {                                     // (block-uniform)
         float zp = 0.f;
         for (int i = tid; i < Np; i += blockDim.x)
             if (cls[i] == CE_NEG) zp += expf(z[i] - m);
-        const float Z = ce_block_sum(zp, red);
+        const float Z = block_sum(zp, red);
         float lp = 0.f, sp = 0.f;
         for (int i = tid; i < Np; i += blockDim.x) {
             if (cls[i] != CE_POS) continue;
@@ -134,8 +103,8 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
             lp += e >= Z ? log1pf(Z / e) : logf(D) - zi;         // log(e + Z) - zi; the first form keeps a small Z beside e = 1
             sp += 1.f / D;
         }
-        const float l = ce_block_sum(lp, red);
-        const float S = ce_block_sum(sp, red);
+        const float l = block_sum(lp, red);
+        const float S = block_sum(sp, red);
         const float w = 1.0f / (tau * np);
         for (int i = tid; i < Np; i += blockDim.x) {
             const int c = cls[i];
@@ -152,31 +121,16 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     } else {
         for (int i = tid; i < Np; i += blockDim.x) g[i] = 0.f;
     }
-    // ---- publish the row, take a ticket; the last workgroup finishes the call
+    // ---- publish the row; the workgroup that arrives last finishes the call
     if (tid == 0) { row_out[2 * b] = row_loss; row_out[2 * b + 1] = valid ? 1.f : 0.f; }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned int* ticket = softmax_ce_tickets + slot;
-        const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(B - 1);
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        shared_int[1] = last ? 1 : 0;
-    }
-    __syncthreads();
-    if (!shared_int[1]) return;
+    if (!arrived_last(softmax_ce_tickets + slot, B)) return;
     float ls = 0.f, rs = 0.f;
     for (int r = tid; r < B; r += blockDim.x) {      // thread t adds rows t, t + 256, ... in ascending order, then the block sum: a fixed order
         ls += __hip_atomic_load(row_out + 2 * r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         rs += __hip_atomic_load(row_out + 2 * r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    const float L = ce_block_sum(ls, red);
-    const float R = ce_block_sum(rs, red);
+    const float L = block_sum(ls, red);
+    const float R = block_sum(rs, red);
     if (tid == 0) {
         loss_out[0] = mean_reduction ? (R > 0.f ? L / R : 0.f) : L;
         loss_out[1] = R;
@@ -206,11 +160,10 @@ extern "C" int cldrd_softmax_ce(const float* logits, const float* labels, int B,
     CLDRD_CHECK(!has_pos_min || pos_min > neg_max, "softmax_ce: need pos_min > neg_max");
     if (pids) {
         CLDRD_CHECK(N >= 1 && (long long)B * N <= 0x7fffffffLL, "softmax_ce: pids need N >= 1");
-        const long long want = mode == 0 ? N : (mode == 1 ? (long long)B * N : 2LL * N);
-        CLDRD_CHECK((long long)Np == want, "softmax_ce: Np does not match mode, B and N (mode 0: N, 1: B * N, 2: 2 * N)");
+        CLDRD_CHECK(Np == score_cols(B, N, mode), "softmax_ce: Np does not match mode, B and N (mode 0: N, 1: B * N, 2: 2 * N)");
     }
     static std::atomic<unsigned int> launches{0};
-    const int slot = (int)(launches.fetch_add(1u) % CE_TICKETS);
+    const int slot = arrival_next_slot(launches);
     hipLaunchKernelGGL(softmax_ce_kernel, dim3(B), dim3(256), softmax_ce_lds_bytes(Np), (hipStream_t)stream, logits, labels, pids, grad,
                        workspace, loss_out, B, Np, N, mode, tau, pos_min, has_pos_min, neg_max, mean_reduction, slot);
     CLDRD_LAUNCH_CHECK();

@@ -1,13 +1,10 @@
-// N-way scoring and the list-wise distillation losses, forward + analytic backward, fp32.
+// The list-wise distillation losses, forward + analytic backward, fp32 (the scorers in front of them: score.hip).
 //
-// Reference: models/nway_dual_encoder.py:30-47 (dot-product scoring, optional in-batch negatives),
-// losses/kl_div.py:11-22, losses/margin_mse.py:8-19, losses/ranknet.py:3-44, losses/lambda_rank.py:3-96
+// Reference: losses/kl_div.py:11-22, losses/margin_mse.py:8-19, losses/ranknet.py:3-44, losses/lambda_rank.py:3-96
 // (SURVEY.md K6-K10).  The reference materialises three [B,N,N] tensors, sorts, and synchronises with the
 // host twice per call (ranknet.py:16,40); here one workgroup owns one row: ranks come from an in-LDS count
 // (stable: ties by index), the pair loop runs over LDS, loss and pair count are wave-reduced, and the
 // gradient is written directly (no autograd graph, no host sync).
-#include <atomic>
-
 #include "common.h"
 
 namespace {
@@ -15,90 +12,6 @@ namespace {
 enum { LOSS_KL = 0, LOSS_MSE = 1, LOSS_RANKNET = 2, LOSS_LAMBDA = 3, LOSS_WPOINT = 4 };
 
 __device__ __forceinline__ float NEG_INF_F() { return -__builtin_inff(); }
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-    return s;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = fmaxf(s, red[w]);
-    return s;
-}
-
-// idx of the passage behind logit column j of row b.  mode 0: own N; 1: own N then every other sample's passages in
-// global order; 2: own N then the next sample's N (cyclic)   (reference models/nway_dual_encoder.py:30-44)
-__device__ __forceinline__ int col_to_passage(int mode, int b, int j, int B, int N) {
-    if (j < N) return b * N + j;
-    const int jj = j - N;
-    if (mode == 1) return jj < b * N ? jj : jj + N;
-    return ((b + 1) % B) * N + jj;
-}
-
-__global__ __launch_bounds__(256) void score_fwd_kernel(const float* __restrict__ q, const float* __restrict__ p,
-                                                         float* __restrict__ logits, int B, int N, int Np, int d, int mode) {
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (o >= B * Np) return;
-    const int lane = threadIdx.x & 63;
-    const int b = o / Np, j = o % Np;
-    const float* qr = q + (size_t)b * d;
-    const float* pr = p + (size_t)col_to_passage(mode, b, j, B, N) * d;
-    float s = 0.f;
-    for (int c = lane * 4; c < d; c += 256) {
-        const float4 a = *(const float4*)(qr + c), w = *(const float4*)(pr + c);
-        s += a.x * w.x + a.y * w.y + a.z * w.z + a.w * w.w;
-    }
-    s = wave_sum(s);
-    if (lane == 0) logits[o] = s;
-}
-
-// dq[b] = sum_j dl[b][j] * p[passage(b, j)]
-__global__ __launch_bounds__(256) void score_bwd_q_kernel(const float* __restrict__ dl, const float* __restrict__ p,
-                                                           float* __restrict__ dq, int B, int N, int Np, int d, int mode) {
-    // grid (B, column chunks of 256): with one block per query a thread walked its Np passages one dependent load after the other
-    // (26 us at B = 8, N = 32 on the step's critical path between the loss and the first backward GEMM); the loads of eight passages are
-    // now in flight together.  Same summation order (j ascending): same bits.
-    const int b = blockIdx.x;
-    const int c = blockIdx.y * blockDim.x + threadIdx.x;
-    if (c >= d) return;
-    float s = 0.f;
-    int j = 0;
-    for (; j + 8 <= Np; j += 8) {
-        float v[8], w[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { w[u] = dl[(size_t)b * Np + j + u]; v[u] = p[(size_t)col_to_passage(mode, b, j + u, B, N) * d + c]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += w[u] * v[u];
-    }
-    for (; j < Np; ++j) s += dl[(size_t)b * Np + j] * p[(size_t)col_to_passage(mode, b, j, B, N) * d + c];
-    dq[(size_t)b * d + c] = s;
-}
-// dp[m] = sum over (b, j) with passage(b, j) == m of dl[b][j] * q[b]
-__global__ __launch_bounds__(256) void score_bwd_p_kernel(const float* __restrict__ dl, const float* __restrict__ q,
-                                                           float* __restrict__ dp, int B, int N, int Np, int d, int mode) {
-    const int m = blockIdx.x;
-    const int bo = m / N, o = m % N;
-    for (int c = threadIdx.x; c < d; c += blockDim.x) {
-        float s = dl[(size_t)bo * Np + o] * q[(size_t)bo * d + c];
-        if (mode == 1) {
-            for (int b = 0; b < B; ++b)
-                if (b != bo) s += dl[(size_t)b * Np + N + (m < b * N ? m : m - N)] * q[(size_t)b * d + c];
-        } else if (mode == 2 && B > 0) {
-            const int b = (bo - 1 + B) % B;
-            s += dl[(size_t)b * Np + N + o] * q[(size_t)b * d + c];
-        }
-        dp[(size_t)m * d + c] = s;
-    }
-}
 
 // One block per row.  Writes the un-normalised gradient and the row's {loss sum, pair count}.
 __global__ __launch_bounds__(256) void loss_row_kernel(int kind, const float* __restrict__ y_pred, const float* __restrict__ y_true,
@@ -417,20 +330,17 @@ __global__ __launch_bounds__(256) void lambda_loss_row_kernel(const float* __res
     if (threadIdx.x == 0) { row_out[2 * b] = lsum; row_out[2 * b + 1] = cnt; }
 }
 
-// Arrival counters of lambda_term_kernel launches: a launch takes the next slot in turn (cldrd_lambda_term), its last workgroup puts
-// the slot back to 0.  Zero at module load; LAMBDA_TICKETS launches of it may be in flight on one device at a time.
-enum { LAMBDA_TICKETS = 32 };
-__device__ unsigned int lambda_term_tickets[LAMBDA_TICKETS];
+__device__ unsigned int lambda_term_tickets[ARRIVAL_SLOTS];      // arrival counters of lambda_term_kernel launches (common.h: arrived_last)
 
 // The term form of lambda_loss (cldrd_lambda_term): one workgroup per slate = the first Ns columns of a row of logits [B, Np].
 //   term = lambda_loss(logits[:, :Ns], labels'), labels' = the staged labels (lambda_stage_labels);
 //   grad[b, :Ns] (+)= alpha * d term / d logits, loss_out[0] (+)= alpha * term, *term_out = term.
 // Under the 'mean' reduction every gradient entry is divided by the pair count of ALL rows; each workgroup takes that count itself
 // (lambda_row_pairs over every row: compares only, cheap next to its own row's pair loop of exp / pow / log), so it writes its
-// final gradient in one pass and the accumulate form needs no second buffer.  The value is the one cross-row sum: thread 0 of every
-// workgroup publishes {sum of terms, pairs} to row_out (agent-scope release, then a ticket), the workgroup that draws the last ticket
-// adds the rows in ascending order (agent-scope acquire; loads that bypass its L1).  Fixed order, no float atomics: the same bits on
-// every launch, and the bits of lambda_loss_row_kernel + loss_finalize_kernel where the two forms compute the same thing.
+// final gradient in one pass and the accumulate form needs no second buffer.  The value is the one cross-row sum: every workgroup
+// publishes {sum of terms, pairs} to row_out, and thread 0 of the workgroup that arrives last (common.h: arrived_last) adds the rows in
+// ascending order, with loads that bypass its L1.  Fixed order, no float atomics: the same bits on every launch, and the bits of
+// lambda_loss_row_kernel + loss_finalize_kernel where the two forms compute the same thing.
 __global__ __launch_bounds__(256) void lambda_term_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
                                                            float* __restrict__ grad, float* row_out, float* __restrict__ loss_out,
                                                            float* __restrict__ term_out, int B, int Np, int Ns, LambdaParams P, float pad,
@@ -464,17 +374,8 @@ __global__ __launch_bounds__(256) void lambda_term_kernel(const float* __restric
     }
     if (!accumulate)
         for (int j = Ns + threadIdx.x; j < Np; j += blockDim.x) g[j] = 0.f;
-    if (threadIdx.x != 0) return;
-    row_out[2 * b] = lsum;
-    row_out[2 * b + 1] = cnt;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned int* ticket = lambda_term_tickets + slot;
-    if (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned int)(B - 1)) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) { row_out[2 * b] = lsum; row_out[2 * b + 1] = cnt; }
+    if (!arrived_last(lambda_term_tickets + slot, B) || threadIdx.x != 0) return;
     float l = 0.f, n = 0.f;
     for (int r = 0; r < B; ++r) {
         l += __hip_atomic_load(row_out + 2 * r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -567,25 +468,6 @@ __global__ __launch_bounds__(512) void distill_term_kernel(int kind, const float
 
 }  // namespace
 
-extern "C" int cldrd_score_fwd(const float* q, const float* p, float* logits, int B, int N, int d, int mode, void* stream) {
-    CLDRD_CHECK(B > 0 && N > 0 && d > 0 && d % 4 == 0 && mode >= 0 && mode <= 2, "score_fwd: bad arguments");
-    const int Np = mode == 0 ? N : (mode == 1 ? B * N : 2 * N);
-    hipLaunchKernelGGL(score_fwd_kernel, dim3((B * Np + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, p, logits, B, N, Np, d, mode);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int cldrd_score_bwd(const float* dlogits, const float* q, const float* p, float* dq, float* dp, int B, int N, int d,
-                               int mode, void* stream) {
-    CLDRD_CHECK(B > 0 && N > 0 && d > 0 && mode >= 0 && mode <= 2, "score_bwd: bad arguments");
-    const int Np = mode == 0 ? N : (mode == 1 ? B * N : 2 * N);
-    hipLaunchKernelGGL(score_bwd_q_kernel, dim3(B, (d + 255) / 256), dim3(256), 0, (hipStream_t)stream, dlogits, p, dq, B, N, Np, d, mode);
-    CLDRD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(score_bwd_p_kernel, dim3(B * N), dim3(256), 0, (hipStream_t)stream, dlogits, q, dp, B, N, Np, d, mode);
-    CLDRD_LAUNCH_CHECK();
-    return 0;
-}
-
 // kind: 0 KLDiv(T), 1 MarginMSE, 2 ranknet, 3 lambda_mrr (batch_weight != null -> bweight_lambda_mrr).
 // loss_out: device float[2] = {loss, number of valid pairs}; grad: device [B, N] = d loss / d y_pred;
 // workspace: device float[2*B].
@@ -662,7 +544,7 @@ extern "C" int cldrd_lambda_term(const float* logits, int B, int Np, const float
     CLDRD_CHECK(alpha >= 0.f, "lambda_term: need alpha >= 0");
     CLDRD_CHECK(accumulate == 0 || accumulate == 1, "lambda_term: accumulate must be 0 or 1");
     static std::atomic<unsigned int> launches{0};
-    const int slot = (int)(launches.fetch_add(1u) % LAMBDA_TICKETS);
+    const int slot = arrival_next_slot(launches);
     const LambdaParams P{scheme, k > 0 ? k : Ns, eps, sigma, mu, log2_reduction, gain_linear};
     hipLaunchKernelGGL(lambda_term_kernel, dim3(B), dim3(256), lambda_lds_floats(Ns) * sizeof(float), (hipStream_t)stream, logits, labels,
                        grad, workspace, loss_out, term_out, B, Np, Ns, P, pad_indicator, mean_reduction, label_flags, n_rel, label_offset,

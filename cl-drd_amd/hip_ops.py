@@ -901,6 +901,11 @@ def scatter_cls_grad(dcls, g, R, T, stride=0, idx=None):
     call("cldrd_scatter_cls_grad", _p(dcls), _p(g), R, dcls.shape[1], stride, _p(idx), T, _stream_fmt(g), _stream())
 
 
+def score_cols(B: int, N: int, mode: int) -> int:
+    """Logit columns of a row: mode 0 its own N passages, 1 then every other sample's, 2 then the next sample's (csrc/score_layout.h)."""
+    return N if mode == 0 else (B * N if mode == 1 else 2 * N)
+
+
 def score_fwd(q, p, logits, B, N, mode=0):
     _chk(q, F32, "q", 2), _chk(p, F32, "p", 2), _chk(logits, F32, "logits", 2)
     call("cldrd_score_fwd", _p(q), _p(p), _p(logits), B, N, q.shape[1], mode, _stream())
@@ -972,9 +977,8 @@ def loss_fwd_bwd(kind, y_pred, y_true, *, batch_weight=None, T=1.0, pad_indicato
     return out, grad
 
 
-def lambda_loss_fwd_bwd(y_pred, y_true, *, eps=1e-4, padded_value_indicator=-1, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
-                        reduction="mean", reduction_log="natural", gain="power"):
-    """lambda_loss of reference losses/standard_lambda_rank.py:3 -> (loss_out float[2] = {loss, pairs}, grad [B, N])."""
+def _lambda_args(weighing_scheme, k, eps, sigma, mu, padded_value_indicator, reduction, reduction_log, gain):
+    """The lambda_loss options, checked as the reference checks them, in the order the C entry points take them."""
     if weighing_scheme not in LAMBDA_SCHEMES:
         raise KeyError(weighing_scheme)               # the reference looks the scheme up in globals()
     if gain not in ("power", "linear"):
@@ -983,6 +987,14 @@ def lambda_loss_fwd_bwd(y_pred, y_true, *, eps=1e-4, padded_value_indicator=-1, 
         raise ValueError("Reduction logarithm base can be either natural or binary")
     if reduction not in ("mean", "sum"):
         raise ValueError("Reduction method can be either sum or mean")
+    return (LAMBDA_SCHEMES[weighing_scheme], 0 if k is None else int(k), float(eps), float(sigma), float(mu), float(padded_value_indicator),
+            1 if reduction == "mean" else 0, 1 if reduction_log == "binary" else 0, 1 if gain == "linear" else 0)
+
+
+def lambda_loss_fwd_bwd(y_pred, y_true, *, eps=1e-4, padded_value_indicator=-1, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
+                        reduction="mean", reduction_log="natural", gain="power"):
+    """lambda_loss of reference losses/standard_lambda_rank.py:3 -> (loss_out float[2] = {loss, pairs}, grad [B, N])."""
+    largs = _lambda_args(weighing_scheme, k, eps, sigma, mu, padded_value_indicator, reduction, reduction_log, gain)
     _chk(y_pred, F32, "y_pred", 2), _chk(y_true, F32, "y_true", 2)
     if y_pred.shape != y_true.shape:
         raise ValueError("lambda_loss: y_pred and y_true must have the same shape")
@@ -991,9 +1003,7 @@ def lambda_loss_fwd_bwd(y_pred, y_true, *, eps=1e-4, padded_value_indicator=-1, 
     out = torch.empty(2, dtype=F32, device=y_pred.device)
     grad = torch.empty_like(y_pred)
     ws = torch.empty(2 * B, dtype=F32, device=y_pred.device)
-    call("cldrd_lambda_loss_fwd_bwd", _p(y_pred), _p(y_true), _p(out), _p(grad), _p(ws), B, N, LAMBDA_SCHEMES[weighing_scheme],
-         0 if k is None else int(k), float(eps), float(sigma), float(mu), float(padded_value_indicator),
-         1 if reduction == "mean" else 0, 1 if reduction_log == "binary" else 0, 1 if gain == "linear" else 0, _stream())
+    call("cldrd_lambda_loss_fwd_bwd", _p(y_pred), _p(y_true), _p(out), _p(grad), _p(ws), B, N, *largs, _stream())
     return out, grad
 
 
@@ -1005,7 +1015,6 @@ def logit_norm_reg(logits, reg_lambda, loss_out, grad, reg_out=None):
     if reg_out is not None:
         _chk(reg_out, F32, "reg_out", 1)
     call("cldrd_logit_norm_reg", _p(logits), logits.numel(), float(reg_lambda), _p(loss_out), _p(grad), _p(reg_out), _stream())
-
 
 
 DISTILL_KINDS = {"kl_div": 0, "margin_mse": 1}
@@ -1039,14 +1048,7 @@ def lambda_term(logits, labels, loss_out, grad, term_out=None, *, alpha=1.0, acc
     subtracted (``row_min``), ``label_offset`` added, in this order, on the labels that are not padding.
     accumulate=False: loss_out = {alpha * term, pairs}, grad[:, :Ns] = alpha * d term / d logits, grad[:, Ns:] = 0;
     accumulate=True: loss_out[0] += alpha * term, grad[:, :Ns] += ...; columns >= Ns untouched.  term_out[0] = term."""
-    if weighing_scheme not in LAMBDA_SCHEMES:
-        raise KeyError(weighing_scheme)
-    if gain not in ("power", "linear"):
-        raise ValueError(f"{gain} not defined.")
-    if reduction_log not in ("natural", "binary"):
-        raise ValueError("Reduction logarithm base can be either natural or binary")
-    if reduction not in ("mean", "sum"):
-        raise ValueError("Reduction method can be either sum or mean")
+    largs = _lambda_args(weighing_scheme, k, eps, sigma, mu, padded_value_indicator, reduction, reduction_log, gain)
     _chk(logits, F32, "logits", 2), _chk(labels, F32, "labels", 2), _chk(loss_out, F32, "loss_out", 1), _chk(grad, F32, "grad", 2)
     if not (logits.is_contiguous() and grad.is_contiguous() and labels.is_contiguous()) or grad.shape != logits.shape:
         raise ValueError("lambda_term: logits, grad and labels must be contiguous, grad of the shape of logits")
@@ -1060,10 +1062,8 @@ def lambda_term(logits, labels, loss_out, grad, term_out=None, *, alpha=1.0, acc
     Ns = labels.shape[1]
     flags = (LAMBDA_LABEL_FLAGS["mean"] if neg_mean else 0) | (LAMBDA_LABEL_FLAGS["row_min"] if row_min else 0)
     ws = torch.empty(2 * B, dtype=F32, device=logits.device)
-    call("cldrd_lambda_term", _p(logits), B, Np, _p(labels), Ns, flags, Ns if n_rel is None else int(n_rel), float(label_offset),
-         LAMBDA_SCHEMES[weighing_scheme], 0 if k is None else int(k), float(eps), float(sigma), float(mu), float(padded_value_indicator),
-         1 if reduction == "mean" else 0, 1 if reduction_log == "binary" else 0, 1 if gain == "linear" else 0, float(alpha),
-         1 if accumulate else 0, _p(loss_out), _p(grad), _p(term_out), _p(ws), _stream())
+    call("cldrd_lambda_term", _p(logits), B, Np, _p(labels), Ns, flags, Ns if n_rel is None else int(n_rel), float(label_offset), *largs,
+         float(alpha), 1 if accumulate else 0, _p(loss_out), _p(grad), _p(term_out), _p(ws), _stream())
 
 
 def softmax_ce(logits, labels, loss_out, grad, *, pids=None, nway=None, mode=0, temperature=1.0, pos_min=None, neg_max=0.0, reduction="mean"):
@@ -1088,7 +1088,7 @@ def softmax_ce(logits, labels, loss_out, grad, *, pids=None, nway=None, mode=0, 
     if pids is not None:
         _chk(pids, torch.int64, "pids", 2)
         N = pids.shape[1] if nway is None else int(nway)
-        if mode not in (0, 1, 2) or not pids.is_contiguous() or tuple(pids.shape) != (B, N) or Np != (N if mode == 0 else (B * N if mode == 1 else 2 * N)):
+        if mode not in (0, 1, 2) or not pids.is_contiguous() or tuple(pids.shape) != (B, N) or Np != score_cols(B, N, mode):
             raise ValueError(f"softmax_ce: pids must be contiguous [B, nway] = [{B}, {N}] with {Np} = nway | B * nway | 2 * nway logit columns "
                              f"for mode 0 | 1 | 2; got {tuple(pids.shape)}, mode {mode}")
     ws = torch.empty(2 * B, dtype=F32, device=logits.device)

@@ -187,23 +187,19 @@ torch.library.register_autograd("cldrd::softmax_ce", _softmax_ce_backward, setup
 
 
 # ---------------------------------------------------------------------------------------------------------------- scoring
-def _score_cols(B: int, N: int, mode: int) -> int:
-    return N if mode == 0 else (B * N if mode == 1 else 2 * N)
-
-
 @torch.library.custom_op("cldrd::nway_score", mutates_args=(), device_types="cuda")
 def nway_score(q: Tensor, p: Tensor, B: int, N: int, mode: int) -> Tensor:
     """logits[B, N'] of models/nway_dual_encoder.py:30-47: q [B, D], p [B*N, D] fp32; mode 0 N-way, 1 all in-batch negatives
     [B, B*N], 2 next sample's N [B, 2N]."""
     q, p = q.contiguous(), p.contiguous()
-    logits = torch.empty(B, _score_cols(B, N, mode), dtype=torch.float32, device=q.device)
+    logits = torch.empty(B, ops.score_cols(B, N, mode), dtype=torch.float32, device=q.device)
     ops.score_fwd(q, p, logits, B, N, mode)
     return logits
 
 
 @nway_score.register_fake
 def _(q, p, B, N, mode):
-    return q.new_empty((B, _score_cols(B, N, mode)), dtype=torch.float32)
+    return q.new_empty((B, ops.score_cols(B, N, mode)), dtype=torch.float32)
 
 
 @torch.library.custom_op("cldrd::nway_score_bwd", mutates_args=(), device_types="cuda")
@@ -240,14 +236,14 @@ torch.library.register_autograd("cldrd::nway_score", _score_backward, setup_cont
 def nway_score_cos(q: Tensor, p: Tensor, B: int, N: int, mode: int, scale: float) -> Tensor:
     """logits[B, N'] = scale * cosine similarity (eps 1e-8) in the layout of cldrd::nway_score (--apply_consine_similarity)."""
     q, p = q.contiguous(), p.contiguous()
-    logits = torch.empty(B, _score_cols(B, N, mode), dtype=torch.float32, device=q.device)
+    logits = torch.empty(B, ops.score_cols(B, N, mode), dtype=torch.float32, device=q.device)
     ops.score_cos_fwd(q, p, logits, torch.empty(B + B * N, dtype=torch.float32, device=q.device), B, N, mode, scale)
     return logits
 
 
 @nway_score_cos.register_fake
 def _(q, p, B, N, mode, scale):
-    return q.new_empty((B, _score_cols(B, N, mode)), dtype=torch.float32)
+    return q.new_empty((B, ops.score_cols(B, N, mode)), dtype=torch.float32)
 
 
 @torch.library.custom_op("cldrd::nway_score_cos_bwd", mutates_args=(), device_types="cuda")
@@ -256,7 +252,7 @@ def nway_score_cos_bwd(dlogits: Tensor, q: Tensor, p: Tensor, B: int, N: int, mo
     # small forward launches run again here: every sum has one order, the logits and norms are the forward's bit for bit.  (The fused
     # trainer calls the C pair directly and keeps them.)
     q, p = q.contiguous(), p.contiguous()
-    logits = torch.empty(B, _score_cols(B, N, mode), dtype=torch.float32, device=q.device)
+    logits = torch.empty(B, ops.score_cols(B, N, mode), dtype=torch.float32, device=q.device)
     inv_norms = torch.empty(B + B * N, dtype=torch.float32, device=q.device)
     ops.score_cos_fwd(q, p, logits, inv_norms, B, N, mode, scale)
     dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)          # row-major whatever the strides of q / p (see nway_score_bwd)

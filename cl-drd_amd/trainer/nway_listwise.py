@@ -522,7 +522,7 @@ class NwayTrainer:
             main.wait_stream(side)
             q_cls.record_stream(main)
         mode = score_mode(model.in_batch_loss, model.all_in_batch_neg)
-        Np = nway if mode == 0 else (bz * nway if mode == 1 else 2 * nway)
+        Np = ops.score_cols(bz, nway, mode)
         # Scoring, loss and score backward on a stream of their OWN between the two joins.  In a replayed HIP graph a cross-stream edge is
         # honoured when the source stream's run of consecutive nodes ENDS, not at the node the edge leaves from: with the loss kernels on the
         # main stream the executor kept them and the query tower's backward (the branch captured first) in one run on one hardware queue, and

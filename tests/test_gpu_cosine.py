@@ -115,6 +115,17 @@ def test_scorer_against_float64(B, N, d, mode, scale):
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("d", [4, 260])
+@pytest.mark.parametrize("N", [1, 5, 11])
+@pytest.mark.parametrize("B", [1, 3])
+def test_scorer_tails_in_every_mode(B, N, d, mode):
+    """Column counts of 1 to 33 (a tail alone, eight plus a tail, four times eight plus one; B = 1 and 3 close the cycle of mode 2 on the
+    row itself and on another row) and d of one float4 and of a second pass of the 256-wide loop."""
+    q, p, g = inputs(2000 + 100 * B + 7 * N + d + mode, B, N, d, mode)
+    check_against_float64(f"tails_B{B}_N{N}_d{d}_mode{mode}", q, p, g, B, N, mode, 20.0, with_autograd=False)
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
 @pytest.mark.parametrize("zero", ["passage", "query"])
 def test_scorer_with_a_clamped_row(zero, mode):
     """An all-zero row: its norm is clamped to eps and is a constant there - its logits are 0 and the second term of its gradient is dropped."""

@@ -1175,6 +1175,38 @@ def test_score_fwd_bwd(mode):
     close(dp, pr.grad, 1e-5, 1e-4, "score dp")
 
 
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("d", [4, 260])
+@pytest.mark.parametrize("N", [1, 5, 11])
+@pytest.mark.parametrize("B", [1, 3])
+def test_score_tails_in_every_mode(B, N, d, mode):
+    """Column counts of 1 to 33 (a tail alone, eight plus a tail, four times eight plus one; B = 1 and 3 close the cycle of mode 2 on the
+    row itself and on another row) and d of one float4 and of a second pass of the 256-wide loop, against float64 over a column layout
+    built here by listing the passages.  The bars of test_score_fwd_bwd."""
+    rows = []
+    for b in range(B):
+        own = list(range(b * N, (b + 1) * N))
+        if mode == 1:
+            own += [m for m in range(B * N) if m // N != b]
+        elif mode == 2:
+            own += list(range(((b + 1) % B) * N, ((b + 1) % B + 1) * N))
+        rows.append(own)
+    idx = torch.tensor(rows, dtype=torch.int64)
+    q, p = rnd(33, (B, d)), rnd(34, (B * N, d))
+    qr, pr = q.double().requires_grad_(True), p.double().requires_grad_(True)
+    ref = (qr[:, None, :] * pr[idx]).sum(-1)
+    dl = rnd(35, tuple(ref.shape))
+    ref.backward(dl.double())
+    logits = torch.empty(tuple(ref.shape), dtype=torch.float32, device=DEV)
+    ops.score_fwd(q.to(DEV), p.to(DEV), logits, B, N, mode)
+    close(logits, ref, 1e-5, 1e-4, "score fwd")
+    dq, dp = torch.full((B, d), float("nan"), device=DEV), torch.full((B * N, d), float("nan"), device=DEV)
+    ops.score_bwd(dl.to(DEV), q.to(DEV), p.to(DEV), dq, dp, B, N, mode)
+    assert torch.isfinite(dq).all() and torch.isfinite(dp).all()           # every element written
+    close(dq, qr.grad, 1e-5, 1e-4, "score dq")
+    close(dp, pr.grad, 1e-5, 1e-4, "score dp")
+
+
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "losses.npz"))
 
 

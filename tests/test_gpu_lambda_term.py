@@ -141,6 +141,33 @@ def test_accumulate_form_column_mask_alpha_and_determinism(shape, reduction):
     assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip((over_loss, over_grad, over_term), over2))
 
 
+@pytest.mark.parametrize("streams", [1, 2])
+@pytest.mark.parametrize("B", [1, 3])
+def test_forty_calls_in_a_row_give_the_bits_of_the_first(B, streams):
+    """More launches than the kernel has arrival slots, back to back on one stream or alternating over two: every launch finds its slot at
+    zero and leaves it at zero, and the workgroup that arrives last (B = 1: the first ticket is the last) adds the rows of its own launch.
+    The first call at the bars of test_kernel_matches_the_oracle_on_bigger_slates."""
+    yp, yt = _oracle_case()
+    yp, yt = yp[:B], yt[:B]
+    v, g = LR.lambda_loss(yp, yt, weighing_scheme="ndcgLoss2PP_scheme", k=50)
+    logits, labels = torch.tensor(yp, device=DEV), torch.tensor(yt, device=DEV)
+    outs = [(torch.full((2,), float("nan"), device=DEV), torch.full_like(logits, float("nan"))) for _ in range(40)]
+    lanes = [torch.cuda.Stream() for _ in range(streams)]
+    for s in lanes:
+        s.wait_stream(torch.cuda.current_stream())
+    for i, (loss, grad) in enumerate(outs):
+        with torch.cuda.stream(lanes[i % streams]):
+            ops.lambda_term(logits, labels, loss, grad, weighing_scheme="ndcgLoss2PP_scheme", k=50)
+    for s in lanes:
+        torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    loss0, grad0 = outs[0]
+    assert abs(loss0[0].item() - v) <= 2e-4 * abs(v) + 1e-6
+    assert np.abs(grad0.cpu().numpy() - g).max() <= 5e-4 * np.abs(g).max() + 1e-8
+    for i, (loss, grad) in enumerate(outs[1:], 1):
+        assert torch.equal(_bits(loss), _bits(loss0)) and torch.equal(_bits(grad), _bits(grad0)), i
+
+
 def test_wrapper_and_entry_point_refusals():
     from cldrd_amd._lib import CldrdError
     z = lambda *s: torch.zeros(*s, device=DEV)          # noqa: E731

@@ -304,6 +304,34 @@ def test_equal_bits_call_after_call_and_every_element_written():
             assert torch.equal(first[0], again[0]) and torch.equal(first[1], again[1])
 
 
+@pytest.mark.parametrize("streams", [1, 2])
+@pytest.mark.parametrize("B,Np", [(1, 4), (3, 35), (300, 4)])
+def test_forty_calls_in_a_row_give_the_bits_of_the_first(B, Np, streams):
+    """More launches than the kernel has arrival slots, back to back on one stream or alternating over two: every launch finds its slot at
+    zero and leaves it at zero, and the workgroup that arrives last (B = 1: the first ticket is the last; B = 300: more rows than threads in
+    the final sum) adds the rows and rescales the gradient of its own launch.  The first call at the bars of test_kernel_against_float64.
+    (tau = 1 on the inputs of seed 1: at tau = 0.05 the one row of B = 1 has a largest gradient entry of 1.6e-54 in float64, below the range of
+    fp32, where a relative bar says nothing; here the fp32 restatement of all three cases is within 2e-7 of float64.)"""
+    logits, labels = grid_inputs(B, Np, seed=1)
+    ref = ce_reference(logits, labels, 1.0)
+    ld, lb = logits.to(DEV), labels.to(DEV)
+    outs = [(torch.full((2,), float("nan"), device=DEV), torch.full((B, Np), float("nan"), device=DEV)) for _ in range(40)]
+    lanes = [torch.cuda.Stream() for _ in range(streams)]
+    for s in lanes:
+        s.wait_stream(torch.cuda.current_stream())
+    for i, (loss_out, grad) in enumerate(outs):
+        with torch.cuda.stream(lanes[i % streams]):
+            ops.softmax_ce(ld, lb, loss_out, grad, temperature=1.0)
+    for s in lanes:
+        torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    first = outs[0][0].cpu(), outs[0][1].cpu()
+    check(f"forty_calls_B{B}_Np{Np}_streams{streams}", first, ref)
+    for i, (loss_out, grad) in enumerate(outs[1:], 1):
+        assert torch.equal(loss_out.cpu().view(torch.int32), first[0].view(torch.int32)), i
+        assert torch.equal(grad.cpu().view(torch.int32), first[1].view(torch.int32)), i
+
+
 @pytest.mark.parametrize("mode", [0, 1])
 def test_autograd_op_and_module_equal_the_raw_call(mode):
     B, N = 4, 6

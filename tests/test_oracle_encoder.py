@@ -79,3 +79,32 @@ def test_in_batch_index_shapes():
     assert idx.tolist() == [[0, 1, 2, 3, 4, 5], [2, 3, 0, 1, 4, 5], [4, 5, 0, 1, 2, 3]]
     idx = E.in_batch_index(3, 2, False)
     assert idx.tolist() == [[0, 1, 2, 3], [2, 3, 4, 5], [4, 5, 0, 1]]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_score_cols_and_the_column_layout_against_a_brute_force_table(mode):
+    """B in 1..4, N in 1..5: the package's column count and the oracle's column index against a table built by listing the passages;
+    every column maps to a passage, and every passage back to the columns that score it."""
+    from cldrd_amd import hip_ops as ops
+    for B in range(1, 5):
+        for N in range(1, 6):
+            table = []
+            for b in range(B):
+                row = [b * N + o for o in range(N)]
+                if mode == 1:
+                    row += [m for m in range(B * N) if m // N != b]
+                elif mode == 2:
+                    row += [((b + 1) % B) * N + o for o in range(N)]
+                table.append(row)
+            assert all(len(row) == ops.score_cols(B, N, mode) for row in table), (B, N)
+            assert all(0 <= m < B * N for row in table for m in row)
+            if mode != 0:
+                assert E.in_batch_index(B, N, mode == 1).tolist() == table, (B, N)
+            for m in range(B * N):                                  # back: the owner's column, then the in-batch columns of the other rows
+                cols = [(b, j) for b in range(B) for j, mm in enumerate(table[b]) if mm == m]
+                want = [(m // N, m % N)]
+                if mode == 1:
+                    want += [(b, N + (m if m < b * N else m - N)) for b in range(B) if b != m // N]
+                elif mode == 2:
+                    want += [((m // N - 1) % B, N + m % N)]
+                assert sorted(cols) == sorted(want), (B, N, m)
