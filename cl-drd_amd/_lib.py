@@ -49,6 +49,9 @@ SIGNATURES = {
     "cldrd_key_order_workspace": (csz, [ci, ci]),
     "cldrd_key_order": (ci, [vp, ci, ci, vp, vp, vp, csz, vp]),
     "cldrd_segment_sum_rows": (ci, [vp, vp, vp, ci, ci, ci, vp, ci, vp]),
+    "cldrd_kmeans_assign": (ci, [vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
+    "cldrd_kmeans_half_sqnorm": (ci, [vp, ci, ci, vp, vp]),
+    "cldrd_kmeans_finish": (ci, [vp, vp, vp, vp, vp, ci, ci, vp]),
     "cldrd_layernorm_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, ci, vp, ci, vp]),
     "cldrd_layernorm_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cull, ci, ci, ci, ci, vp, vp]),
     "cldrd_ln_reduce_group": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp]),

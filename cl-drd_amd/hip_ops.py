@@ -718,6 +718,65 @@ def segment_sum_rows(rows, order, offsets, out, accumulate=False):
     return out
 
 
+# ---- k-means of embedding rows (csrc/kmeans.hip; the definition stands in include/cldrd_hip.h) -------------------------------------------
+def _kmeans_centroids(op, centroids):
+    _chk(centroids, F32, "centroids", 2)
+    k, d = centroids.shape
+    if not centroids.is_contiguous():
+        raise ValueError(f"{op}: centroids must be contiguous [k, d]")
+    if d % 32 or not 32 <= d <= 1024:
+        raise ValueError(f"{op}: d must be a multiple of 32 with 32 <= d <= 1024, got {d}")
+    if not 1 <= k <= 65536:
+        raise ValueError(f"{op}: 1 <= k <= 65536, got {k}")
+    return k, d
+
+
+def kmeans_half_sqnorm(centroids):
+    """h[j] = fp32(0.5 * sum_t centroids[j, t]^2), the sum in fp64: the constant kmeans_assign subtracts from a dot product."""
+    k, d = _kmeans_centroids("kmeans_half_sqnorm", centroids)
+    h = torch.empty(k, dtype=F32, device=centroids.device)
+    call("cldrd_kmeans_half_sqnorm", _p(centroids), k, d, _p(h), _stream())
+    return h
+
+
+def kmeans_assign(x, centroids, half_sqnorm=None, best=False):
+    """assign int64 [n]: the nearest centroid (L2) of every row of x fp32 [n, d] (a row pitch is allowed), the lowest index among equals -
+    one launch, no [n, k] matrix in memory, and a row's result does not depend on the other rows of the launch.  ``half_sqnorm``: what
+    kmeans_half_sqnorm / kmeans_update returned for these centroids (computed here when None).  ``best=True``: returns (assign, best) with
+    best[i] = fp32(dot(x_i, c) - h) of the chosen centroid."""
+    k, d = _kmeans_centroids("kmeans_assign", centroids)
+    _chk(x, F32, "x", 2)
+    n = x.shape[0]
+    if x.shape[1] != d:
+        raise ValueError(f"kmeans_assign: x is [n, {x.shape[1]}], centroids are [k, {d}]")
+    if not k <= n <= 1 << 22:
+        raise ValueError(f"kmeans_assign: k <= n <= 2^22, got n = {n}, k = {k}")
+    h = kmeans_half_sqnorm(centroids) if half_sqnorm is None else _chk(half_sqnorm, F32, "half_sqnorm", 1)
+    if h.numel() != k:
+        raise ValueError("kmeans_assign: half_sqnorm must be [k]")
+    assign = torch.empty(n, dtype=torch.int64, device=x.device)
+    b = torch.empty(n, dtype=F32, device=x.device) if best else None
+    call("cldrd_kmeans_assign", _p(x), x.stride(0) if n > 1 else max(x.stride(0), d), n, d, _p(centroids), _p(h), k, _p(assign), _p(b), _stream())
+    return (assign, b) if best else assign
+
+
+def kmeans_update(x, assign, centroids):
+    """One update step, ``centroids`` in place: every non-empty cluster's centroid becomes the mean of its rows of x (contiguous fp32 [n, d]),
+    the sum taken by key_order(assign) -> segment_sum_rows in that kernel's fixed order and divided once; an empty cluster keeps its row.
+    Returns (half_sqnorm [k] of the new centroids, sizes int32 [k], n_empty int32 [1]) - device tensors, nothing is read back."""
+    k, d = _kmeans_centroids("kmeans_update", centroids)
+    _chk(x, F32, "x", 2), _chk(assign, torch.int64, "assign", 1)
+    if x.shape[1] != d or not x.is_contiguous() or assign.numel() != x.shape[0]:
+        raise ValueError("kmeans_update: contiguous x [n, d] (the segment sum takes no row pitch) and assign [n]")
+    order, offsets = key_order(assign, k)
+    sums = torch.empty(k, d, dtype=F32, device=x.device)          # rows of empty clusters stay unwritten and unread
+    segment_sum_rows(x, order, offsets, sums)
+    h = torch.empty(k, dtype=F32, device=x.device)
+    n_empty = torch.empty(1, dtype=torch.int32, device=x.device)
+    call("cldrd_kmeans_finish", _p(sums), _p(offsets), _p(centroids), _p(h), _p(n_empty), k, d, _stream())
+    return h, offsets[1:] - offsets[:-1], n_empty
+
+
 def embed_ln_bwd_rows(dy, ids, word, pos, type0, gamma, mean, rstd, dx_rows, dtype0, dgamma, dbeta, partial, T, L,
                       dropout_p=0.0, seed=0, accumulate=True, pos_idx=None, dy_branch=None):
     """embed_ln_bwd with ``dx_rows`` (fp32 [>= T, d]) in place of the two table gradients: row r receives what embed_ln_bwd adds into both

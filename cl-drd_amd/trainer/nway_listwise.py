@@ -46,8 +46,10 @@ Differences from the reference, on purpose (SURVEY.md sections 7, 8a14):
 """
 from __future__ import annotations
 
+import copy
 import math
 import os
+import sys
 
 import torch
 import torch.distributed as dist
@@ -79,6 +81,8 @@ TEACHER_LABEL_DEFAULTS = {"neg_score_mode": "original", "teacher_label_shift": "
 RESUME_VERSION = 1                            # of the checkpoint's "resume_state" (NwayTrainer.resume_state, train())
 # what the data position of a checkpoint depends on: an exact resume under another value of any of them is refused (check_resume_position)
 POSITION_FIELDS = ("train_batch_size", "nranks", "seed", "dataset_len", "steps_per_epoch", "num_train_epochs")
+# two more under --tas_clusters (the file as given and a digest of its bytes): present in a checkpoint only when the run had the flag
+TAS_POSITION_FIELDS = ("tas_clusters", "tas_clusters_digest")
 
 
 def check_loss_options(loss, label_source="rank", in_batch_loss=False, label_mode=None, synthetic=False, given=(), *, ce_temperature=None,
@@ -1215,6 +1219,9 @@ def get_args(argv=None):
     ap.add_argument("--cosine_scale", default=None, type=float, help="--apply_consine_similarity: the factor on the cosine (default 1)")
     ap.add_argument("--deterministic", action="store_true", default=False,
                     help="bit-reproducible steps: embedding-table gradients as fixed-order per-row sums instead of float atomics (README: cost)")
+    ap.add_argument("--tas_clusters", default=None,
+                    help="topic-aware batches: the qid<TAB>cluster file of dataset.query_clusters; every batch is drawn from one cluster "
+                         "where the cluster sizes allow (README: Topic-aware batches)")
     ap.add_argument("--token_cache_dir", default=None)
     ap.add_argument("--loader_workers", default=4, type=int, help="collate (tokenise / gather from the token cache) worker processes; "
                     "batches arrive in pinned memory, a few steps ahead of the GPU")
@@ -1256,6 +1263,8 @@ def get_args(argv=None):
                        **_ce_options(args))
     if args.ce_mask_duplicate_pids and args.synthetic_steps > 0:
         raise ValueError("--ce_mask_duplicate_pids needs the passage ids of a training file (batch['nway_pids']); --synthetic_steps batches have none")
+    if args.tas_clusters is not None and args.synthetic_steps > 0:
+        raise ValueError("--tas_clusters groups the queries of a training file by cluster; --synthetic_steps batches are generated whole and have none")
     if args.lambda_k is not None and args.lambda_k < 0 or args.lambda_sigma is not None and not args.lambda_sigma > 0.0:
         raise ValueError("--lambda_k must be >= 0 (0: no truncation) and --lambda_sigma > 0")
     args.run_folder = os.path.join(args.experiment_folder, args.run_folder)
@@ -1353,6 +1362,89 @@ class _EpochPosition(torch.utils.data.Sampler):
                 yield item
 
 
+def read_query_clusters(path):
+    """The ``qid<TAB>cluster`` file of dataset.query_clusters -> ({qid: cluster}, 16-hex digest of the file's bytes).  ValueError naming
+    --tas_clusters and the line for anything else than two integer fields with cluster >= 0."""
+    import hashlib
+    with open(path, "rb") as fh:
+        data = fh.read()
+    out = {}
+    for no, line in enumerate(data.decode("utf-8", errors="replace").splitlines(), start=1):
+        a = line.split("\t")
+        try:
+            if len(a) != 2:
+                raise ValueError
+            qid, c = int(a[0]), int(a[1])
+            if c < 0:
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"--tas_clusters: line {no} of {path} is not 'qid<TAB>cluster' (two integers, cluster >= 0): {line[:80]!r}") from None
+        out[qid] = c
+    if not out:
+        raise ValueError(f"--tas_clusters: {path} holds no line")
+    return out, hashlib.sha256(data).hexdigest()[:16]
+
+
+class TopicBatchSampler(torch.utils.data.Sampler):
+    """Topic-aware batches (TAS, Hofstaetter et al. 2021): the batch sampler of --tas_clusters.  One epoch, every draw taken from
+    ``generator``:
+
+      1. ``perm = randperm(len(dataset))``;
+      2. ``perm`` grouped stably by the cluster of ``dataset.train_examples[i]["qid"]``;
+      3. each cluster's list cut into full batches of ``batch_size`` (PURE batches: one cluster);
+      4. the clusters' remainders, concatenated in ascending cluster order, cut into batches of ``batch_size`` (MIXED batches); a final
+         remainder shorter than a batch is dropped, as ``drop_last`` drops it;
+      5. all batches yielded in the order ``randperm(n_batches)``.
+
+    Exactly ``len(dataset) // batch_size`` batches and no example twice: the epoch length, the schedule and the resume position keep the
+    values they have under the RandomSampler.  Which batches are pure is decided by the cluster sizes alone, not by the draws."""
+
+    def __init__(self, dataset, cluster_of_qid, batch_size, generator=None):
+        self.batch_size, self.generator = int(batch_size), generator
+        if self.batch_size < 1:
+            raise ValueError("TopicBatchSampler: batch_size must be >= 1")
+        qids = [int(ex["qid"]) for ex in dataset.train_examples]
+        missing = [q for q in qids if q not in cluster_of_qid]
+        if missing:
+            raise ValueError(f"--tas_clusters: {len(missing)} of the {len(qids)} training examples have a qid the cluster file does not name "
+                             f"(the first: {missing[0]}); cluster the queries of this training file (dataset.query_clusters --training_path)")
+        self.cluster = torch.tensor([cluster_of_qid[q] for q in qids], dtype=torch.int64)
+        self.sizes = torch.bincount(self.cluster) if len(qids) else torch.zeros(0, dtype=torch.int64)
+        self.n_pure = int((self.sizes // self.batch_size).sum())
+        self.n_batches = len(qids) // self.batch_size
+
+    def with_generator(self, generator):
+        """the same sampler drawing from another generator (replayed_epoch_state)"""
+        other = copy.copy(self)
+        other.generator = generator
+        return other
+
+    def describe(self):
+        n = int(self.cluster.numel())
+        share = self.n_pure * self.batch_size / n if n else 0.0
+        return (f"--tas_clusters: {self.n_pure} pure + {self.n_batches - self.n_pure} mixed batches of {self.batch_size} per epoch over "
+                f"{int((self.sizes > 0).sum())} clusters; {100.0 * share:.1f} % of the examples are in pure batches")
+
+    def __len__(self):
+        return self.n_batches
+
+    def __iter__(self):
+        B, n = self.batch_size, int(self.cluster.numel())
+        perm = torch.randperm(n, generator=self.generator)
+        grouped = perm[torch.sort(self.cluster[perm], stable=True).indices]
+        pure, rest, start = [], [], 0
+        for m in self.sizes.tolist():
+            full = m - m % B
+            pure.append(grouped[start:start + full])
+            rest.append(grouped[start + full:start + m])
+            start += m
+        rest = torch.cat(rest) if rest else grouped[:0]
+        rows = torch.cat(pure + [rest[:rest.numel() - rest.numel() % B]]).view(-1, B) if n >= B else grouped[:0].view(0, B)
+        assert rows.shape[0] == self.n_batches
+        for b in torch.randperm(self.n_batches, generator=self.generator).tolist():
+            yield rows[b].tolist()
+
+
 def _position_of(loader) -> _EpochPosition:
     return loader.batch_sampler if loader.batch_sampler is not None else loader.sampler
 
@@ -1360,13 +1452,14 @@ def _position_of(loader) -> _EpochPosition:
 def replayed_epoch_state(loader, seed, epochs):
     """``epoch_state`` of epoch ``epochs`` (zero-based) of ``loader`` as a generator seeded ``seed`` reaches it: what a rank other than 0 puts
     in the place of the checkpoint's state, which is rank 0's.  Replays the draws of the completed epochs without fetching anything: the
-    DataLoader's worker seed where it builds an iterator (see `_EpochPosition`), then one pass over the sampler."""
+    DataLoader's worker seed where it builds an iterator (see `_EpochPosition`), then one pass over a sampler that draws what the one in
+    use draws: a `TopicBatchSampler` on the replay's generator under --tas_clusters, a RandomSampler otherwise."""
     pos = _position_of(loader)
     if pos.generator is None:
         return None
     g = torch.Generator()
     g.manual_seed(seed)
-    sampler = torch.utils.data.RandomSampler(loader.dataset, generator=g)
+    sampler = pos.inner.with_generator(g) if isinstance(pos.inner, TopicBatchSampler) else torch.utils.data.RandomSampler(loader.dataset, generator=g)
     keeps_iterator = loader.persistent_workers and loader.num_workers > 0
     for e in range(epochs + 1):
         if e == 0 or not keeps_iterator:
@@ -1385,6 +1478,10 @@ def check_resume_position(saved, current):
             raise ValueError(f"--resume_exact: the checkpoint's resume_state has no '{field}' (it was not written by the training command line)")
         if saved[field] != current[field]:
             raise ValueError(f"--resume_exact: {field} was {saved[field]} when the checkpoint was written and is {current[field]} now")
+    for field in TAS_POSITION_FIELDS:          # absent on both sides without --tas_clusters
+        if saved.get(field) != current.get(field):
+            raise ValueError(f"--resume_exact: {field} was {saved.get(field)!r} when the checkpoint was written and is {current.get(field)!r} now "
+                             "(--tas_clusters: the batches of an epoch depend on the cluster file)")
 
 
 def save_checkpoint(ckpt, path):
@@ -1405,6 +1502,8 @@ def build_dataloader(args):
     from ..dataset.nway_dataset import NwayDataset
     check_loss_options(getattr(args, "loss", "lambda_mrr"), getattr(args, "label_source", "rank"), getattr(args, "in_batch_loss", False),
                        label_mode=args.label_mode, **_ce_options(args))      # before anything is loaded
+    tas = getattr(args, "tas_clusters", None)
+    cluster_of_qid, tas_digest = read_query_clusters(tas) if tas else (None, None)          # a malformed file is refused before the tokenizer is loaded
     tok = AutoTokenizer.from_pretrained(args.tokenizer_name_or_path)
     a = (args.queries_path, args.collection_path, args.training_path, tok)
     kw = dict(max_query_len=args.query_max_len, max_passage_len=args.passage_max_len, label_mode=args.label_mode)
@@ -1449,7 +1548,13 @@ def build_dataloader(args):
     # shuffle=True, drop_last=True spelled out as the samplers the DataLoader would build from them (same generator, same draws, same
     # batches), so that the batch sampler can be the one that knows its position (`_EpochPosition`, --resume_exact)
     U = torch.utils.data
-    batches = U.BatchSampler(U.RandomSampler(ds, generator=g), args.train_batch_size // args.nranks, drop_last=True)
+    if cluster_of_qid is not None:
+        batches = TopicBatchSampler(ds, cluster_of_qid, args.train_batch_size // args.nranks, generator=g)
+        batches.file_digest = tas_digest          # of the file's bytes: a position field of the checkpoints (train)
+        if args.rank == 0:
+            sys.stderr.write(batches.describe() + "\n")
+    else:
+        batches = U.BatchSampler(U.RandomSampler(ds, generator=g), args.train_batch_size // args.nranks, drop_last=True)
     return ds, U.DataLoader(ds, batch_sampler=_EpochPosition(batches, g), num_workers=nw, collate_fn=ds.collate_fn, generator=g, pin_memory=True,
                             **(dict(prefetch_factor=4, persistent_workers=True) if nw else {}))
 
@@ -1600,6 +1705,8 @@ def train(args):
     # what (epoch, step_in_epoch) of a checkpoint depends on (POSITION_FIELDS): written into every checkpoint, compared by --resume_exact
     where = {"train_batch_size": args.train_batch_size, "nranks": args.nranks, "seed": args.seed, "dataset_len": len(loader.dataset),
              "steps_per_epoch": steps_per_epoch, "num_train_epochs": args.num_train_epochs}
+    if getattr(args, "tas_clusters", None):
+        where.update(tas_clusters=str(args.tas_clusters), tas_clusters_digest=position.inner.file_digest)
     if args.resume:
         assert args.model_checkpoint is None
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=False)

@@ -211,6 +211,26 @@ size_t cldrd_key_order_workspace(int T, int n_keys);          /* bytes; 0 outsid
 int cldrd_key_order(const long long* keys, int T, int n_keys, int* order, int* offsets, void* workspace, size_t workspace_bytes, void* stream);
 int cldrd_segment_sum_rows(const float* rows, const int* order, const int* offsets, int T, int d, int n_keys, float* out, int accumulate,
                            void* stream);
+/* ---- k-means of embedding rows (csrc/kmeans.hip): topic-aware batches cluster the query embeddings once, cldrd_amd/cluster.py ----------------
+ * X fp32 [n, d] with row pitch ldx; C fp32 [k, d] contiguous; h_j = fp32(0.5 * sum_t C[j,t]^2), the sum taken in fp64 and rounded once.
+ *     s(i, j)   = fp32( dot(x_i, c_j) - h_j )     dot: an fp32 fma chain over t in ONE fixed order, the same for every (i, j)
+ *     assign[i] = the lowest j that attains max_j s(i, j)          (= nearest centroid in L2; ties go to the lower index)
+ *     best[i]   = that maximum                                      (||x_i||^2 - 2 best[i] is the squared distance)
+ * cldrd_kmeans_assign: one launch on the f32-input MFMA; the [n, k] scores never reach memory.  assign int64 [n]; best fp32 [n] or NULL.  One
+ *   schedule for every n and k: assign[i] and best[i] are a function of row i and of C only - not of n, of the other rows or of how the rows are
+ *   spread over launches.  No atomic, no cross-workgroup reduction.  A row holding a NaN gets centroid 0 and best = -inf.
+ * cldrd_kmeans_half_sqnorm: h as defined above.
+ * cldrd_kmeans_finish: the end of an update step.  sums fp32 [k, d] and offsets int32 [k + 1] come from cldrd_key_order(assign) ->
+ *   cldrd_segment_sum_rows(X, order, offsets): a cluster's sum is taken in that kernel's documented order (ascending row, chunks of
+ *   CLDRD_SEGMENT_CHUNK).  m = offsets[j + 1] - offsets[j] > 0: C[j] = fp32(sums[j] / fp32(m)), one rounding per element; m == 0: the centroid keeps
+ *   its row (sums[j] is not read) and is counted in n_empty (int32 [1], overwritten).  h is recomputed for every row.  With the sort and the segment sum
+ *   a whole Lloyd iteration is bit-reproducible: no float atomics anywhere.
+ * Limits, checked before anything touches the device (cldrd_last_error names the entry point and the argument): d % 32 == 0, 32 <= d <= 1024
+ *   (the segment sum's bound); 1 <= k <= 65536; assign: k <= n <= 2^22 (the key sort's bound), ldx >= d, ldx % 4 == 0; every pointer
+ *   16-byte aligned; no null pointer except best.  The update needs contiguous X (ldx == d): cldrd_segment_sum_rows takes no pitch. */
+int cldrd_kmeans_assign(const float* X, int ldx, int n, int d, const float* C, const float* h, int k, long long* assign, float* best, void* stream);
+int cldrd_kmeans_half_sqnorm(const float* C, int k, int d, float* h, void* stream);
+int cldrd_kmeans_finish(const float* sums, const int* offsets, float* C, float* h, int* n_empty, int k, int d, void* stream);
 /* out = LN(x)*gamma+beta (bf16); cls_out (fp32 [T/cls_stride, d], optional) receives rows r % cls_stride == 0:
  * the `[0][:, 0, :]` CLS pooling of models/nway_dual_encoder.py:52,56,64.
  * x_f32 != 0: x is fp32 (the pre-LN sum of the fp32 residual stream) and out32 (optional) receives the fp32 output next to
